@@ -11,10 +11,22 @@ A "step" is ONE frame: every 64x64 bucket of the 1080p frame through the HIP hot
           workload where sharding pays).
 The scene is resident in HBM when the timed region starts.  Rank 0 prints ONE JSON line.
 
-Timed region: `--repeats` (5) repetitions of: barrier + synchronize, EXACTLY `--steps` steps, barrier + synchronize; the max
-over ranks of each repetition; `ms_per_step` is the median repetition (min / max beside it).  The frame buffers are zeroed
-after the warm-up, so the frame left behind was produced by the timed launches: its CRC32 must equal the committed oracle
-vector (tests/golden/oracle_vectors.json) or the run fails.
+A plain run (no `--full`) does only what the headline needs: set-up, `--warmup` steps (continued, untimed, until the warm-up has
+lasted `--min-warmup-time` seconds: the library picks a tile list's dispatch order by timing candidates over its first launches,
+INTEGRATION.md), ONE repetition of EXACTLY `--steps` timed steps, `--dump-outputs` if given, and the line (metric, value, unit,
+ms_per_step, higher_is_better, dtype, the configuration).  Everything below that is not the headline -- the repetitions that
+--full adds by default, the frame CRC check, `roofline`, `flat`, `frames_in_flight`, `configs`, `first_frame_ms`, `seam`, `make_image`,
+`cpu_baseline`, the N > 1 side keys and `native_gang` -- runs only with `--full` (the `--no-*` options still thin it out there).
+The one timed region also holds the synchronisation at its two ends (tens of microseconds): size --steps by `ms_per_step`.
+
+Timed region: `--repeats` repetitions (1; 5 with --full) of: barrier + synchronize, EXACTLY `--steps` steps, barrier +
+synchronize; the max over ranks of each repetition; `ms_per_step` is the median repetition (min / max beside it).  The frame
+buffers are zeroed after the warm-up, so the frame left behind was produced by the timed launches: with --full its CRC32 must
+equal the committed oracle vector (tests/golden/oracle_vectors.json) or the run fails.
+`--dump-outputs DIR` (rank 0): that frame -- what a caller of the timed path receives from its last step, uint8 RGBA -- as
+DIR/frame.npy, float32 [height, width, 4]; a frame above 48 MB as float32 is written as a fixed sample instead (seed 0, sorted
+row-major pixel indices in DIR/frame_sample_pixels.npy as float64, their RGBA in DIR/frame_sample.npy).  The scenes are
+deterministic, so the same arguments give the same inputs on every run.
 
 `roofline` (rank 0's render kernel): bound = VALU issue -- this path is un-fused f32 arithmetic on records that live in the
 scalar cache / L2, not an HBM stream.  achieved = SURVEY.md 8(d)'s 17 flops per ray x record test x the tests of one launch
@@ -28,7 +40,7 @@ loops (rt_skip.hpp, VAR 16) rule most tests out with 4 - 6 fused operations inst
 kernel issues.  `valu_lane_utilisation` = those lane-ops / (SQ_INSTS_VALU x 64), when profiles/ holds counters of these sources.
 Figures that need rocprofv3 counters (instruction issue, HBM traffic) are quoted from profiles/ under `from_profiles`, stamped with
 the kernel sources they were collected on, and dropped when that stamp is not the sources' of this run.
-The timed region is at least 0.2 s: when --steps x --repeats frames take less, more repetitions are run (a step stays one frame).
+With --full the timed region is at least 0.2 s: when --steps x --repeats frames take less, more repetitions are run (a step stays one frame).
 
 `configs` (N = 1): BASELINE's neighbouring configurations (config 2 = 800x600, `make image`, config 5) in one short repetition each after
 the headline -- ms per frame, the same 17-flop fraction of the nominal peak, the kernel the library chose, the frame CRC against the
@@ -42,6 +54,7 @@ host_tiles / host_region / end_to_end (render + D2H + PPM write).  `flat`: the n
 `cpu_baseline`: the oracle on this host's cores.
 
     python bench.py --gpus 1 --steps 100 --warmup 10
+    python bench.py --gpus 1 --steps 100 --warmup 10 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus N --steps K --warmup W
 """
@@ -272,14 +285,38 @@ def make_image_wall(cores):
     return res
 
 
+DUMP_LIMIT_BYTES = 48 << 20             # a frame above this as float32 is sampled (the outputs stay under 64 MB in all)
+
+
+def dump_outputs(d, frame):
+    """--dump-outputs: the frame of the timed path's last step (uint8 [h, w, 4]) under d as float32 .npy -- whole, or a fixed sample."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    h, w, c = frame.shape
+    if frame.size * 4 <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(d, "frame.npy"), frame.astype(np.float32))
+        return {"dir": d, "frame": [h, w, c]}
+    k = DUMP_LIMIT_BYTES // (4 * c + 8)     # the sample's RGBA (float32) and its pixel indices (float64) together
+    pix = np.sort(np.random.default_rng(0).choice(h * w, size=k, replace=False))
+    np.save(os.path.join(d, "frame_sample.npy"), frame.reshape(h * w, c)[pix].astype(np.float32))
+    np.save(os.path.join(d, "frame_sample_pixels.npy"), pix.astype(np.float64))
+    return {"dir": d, "frame_sample": [k, c], "frame_sample_pixels": [k], "of_frame": [h, w, c]}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--repeats", type=int, default=5, help="repetitions of the timed --steps loop (median reported)")
-    ap.add_argument("--min-timed-region", type=float, default=0.2,
-                    help="seconds: more repetitions of the --steps loop are run until the timed region is at least this long")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check beside the headline (module docstring); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame the timed launches left (their last step) under DIR as .npy, float32 (module docstring)")
+    ap.add_argument("--repeats", type=int, default=None, help="repetitions of the timed --steps loop (median reported; default 1, 5 with --full)")
+    ap.add_argument("--min-timed-region", type=float, default=None,
+                    help="seconds: more repetitions of the --steps loop are run until the timed region is at least this long (default 0, 0.2 with --full)")
+    ap.add_argument("--min-warmup-time", type=float, default=0.2,
+                    help="seconds: the headline's warm-up goes on, untimed, past --warmup steps until it has lasted this long")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-flat", action="store_true", help="skip the secondary flat-scan measurement")
     ap.add_argument("--no-seam", action="store_true", help="skip the host-boundary legs (seam_bench child process)")
@@ -301,6 +338,10 @@ def main():
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="1080p",
                     help="1080p = the headline workload; the others are BASELINE's neighbouring configs")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if args.min_timed_region is None:
+        args.min_timed_region = 0.2 if args.full else 0.0
     width, height, spp, level, golden_name = WORKLOADS[args.workload]
     n_items = 100000 if level == "100k" else (4 ** level - 1) // 3
 
@@ -319,9 +360,9 @@ def main():
                          % (args.gpus, world, args.gpus))
 
     seam, image_wall = None, None
-    if world == 1 and not args.no_seam and not args.force_collective and args.workload == "1080p":
+    if args.full and world == 1 and not args.no_seam and not args.force_collective and args.workload == "1080p":
         seam = run_seam(min(64, os.cpu_count() or 1))       # a child process, before anything here initialises the GPU
-    if world == 1 and not args.no_make_image and not args.force_collective and args.workload == "1080p":
+    if args.full and world == 1 and not args.no_make_image and not args.force_collective and args.workload == "1080p":
         image_wall = make_image_wall(len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1))
 
     import numpy as np
@@ -362,9 +403,9 @@ def main():
                 scenes[lv] = rta.Scene.default(lv, rta.RT_F32)
         return scenes[lv]
 
-    def measure(wl, traversal, steps, warmup, repeats, mode, min_region_s=0.0):
+    def measure(wl, traversal, steps, warmup, repeats, mode, min_region_s=0.0, full=True, min_warmup_s=0.0, keep_frame=False):
         """-> dict: whole-job ms per step of each repetition (max over ranks), this rank's kernel ms (HIP events), counters,
-        and the CRC of the frame the timed launches left on rank 0."""
+        and (full) the CRC of the frame the timed launches left on rank 0 / (keep_frame) that frame itself."""
         w, h, k, lv, gname = WORKLOADS[wl]
         opts = rta.RenderOptions(w, h, k)
         fs = FrameSharder(scene_of(lv), opts, rank, world, local, traversal, force_collective=args.force_collective, mode=mode,
@@ -378,6 +419,18 @@ def main():
         primary, shadow = (int(v) for v in cnt.tolist())
         fs.run(warmup)
         barrier()
+        # the warm-up goes on until it has lasted min_warmup_s (chunks of 1, 2, 4 ... steps; every rank runs the same chunks)
+        settle, chunk, t_warm = 0, 1, time.perf_counter()
+        while min_warmup_s > 0:
+            done = torch.tensor([1 if time.perf_counter() - t_warm >= min_warmup_s else 0], dtype=torch.int64, device=comm_dev)
+            if dist is not None:
+                dist.all_reduce(done, op=dist.ReduceOp.MIN)
+            if int(done.item()):
+                break
+            fs.run(chunk)
+            barrier()
+            settle += chunk
+            chunk *= 2
         # what the timed launches leave behind is checked afterwards: start from zeroed buffers
         for b in fs.shards:
             b.zero_()
@@ -413,13 +466,19 @@ def main():
         # The clock the card holds under this load: one more counting launch right behind the timed ones -- its longest
         # wave's s_memtime (shader clock) over s_memrealtime (constant 100 MHz) span; counting launches are a diagnostic flavour, the
         # timed kernels carry no stamp.
-        clk = None
-        if traversal == rta.RT_TRAVERSAL_SKIP:
+        clk, last = None, None
+        if keep_frame and rank == 0:
+            # the frame of the last timed step, read before the counting launch below can touch the buffers
+            if mode == "frames" and fs.collective:
+                last = fs.frame_host(slot=(len(fs._counts) - 1) & 1, of_rank=world - 1, index=fs._counts[-1] - 1)
+            else:
+                last = fs.frame_host()
+        if full and traversal == rta.RT_TRAVERSAL_SKIP:
             st2 = fs.render_shard(want_stats=True)
             if st2.get("longest_wave_ref100mhz"):
                 clk = {"mhz": 100.0 * st2["longest_wave_cycles"] / st2["longest_wave_ref100mhz"], "over_us": st2["longest_wave_ref100mhz"] / 100.0}
         crc, crc_ok = None, None
-        if rank == 0:
+        if full and rank == 0:
             if mode == "frames" and fs.collective:
                 frame = fs.frame_host(slot=0, of_rank=world - 1, index=0)        # a frame that crossed the wire
             else:
@@ -427,7 +486,7 @@ def main():
             crc = zlib.crc32(np.ascontiguousarray(frame).tobytes()) & 0xFFFFFFFF
             g = golden_case(gname)
             crc_ok = (crc == g["frame_crc32"]) if g else None
-        if fs.collective:
+        if full and fs.collective:
             # N > 1: the main stream also carries the waits on RCCL's stream, so the kernel alone is timed right after the
             # timed region: `steps` launches back to back between two HIP events (agrees with rocprofv3 --kernel-trace --stats)
             k0, k1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -438,9 +497,10 @@ def main():
             torch.cuda.synchronize()
             kern.append(k0.elapsed_time(k1) / steps)
         srt = sorted(reps)
-        return {"ms_reps": reps, "ms_per_step": srt[len(srt) // 2], "kern_ms": sorted(kern)[len(kern) // 2], "primary": primary, "shadow": shadow,
+        return {"ms_reps": reps, "ms_per_step": srt[len(srt) // 2], "kern_ms": sorted(kern)[len(kern) // 2] if kern else None, "primary": primary, "shadow": shadow,
                 "my_tests": st["sphere_tests"] + st["bound_tests"], "my_stats": st, "crc": crc, "crc_ok": crc_ok, "launched": launched,
-                "timed_region_s": sum(r * steps for r in reps) / 1e3, "frames_per_step": world if (mode == "frames" and fs.collective) else 1, "clock": clk}
+                "timed_region_s": sum(r * steps for r in reps) / 1e3, "frames_per_step": world if (mode == "frames" and fs.collective) else 1, "clock": clk,
+                "settle_steps": settle, "last_frame": last}
 
     def measure_in_flight(wl, steps, n_streams=2):
         """N = 1 only, never `value`: the same `steps` launches dealt round-robin over n_streams HIP streams (each its own frame
@@ -593,21 +653,26 @@ def main():
 
     head_trav = rta.RT_TRAVERSAL_SKIP if args.traversal == "skip" else rta.RT_TRAVERSAL_FLAT
     multi = args.multi if (world > 1 or args.force_collective) else "tiles"
-    m = measure(args.workload, head_trav, args.steps, args.warmup, max(1, args.repeats), multi, min_region_s=args.min_timed_region)
+    m = measure(args.workload, head_trav, args.steps, args.warmup, max(1, args.repeats), multi, min_region_s=args.min_timed_region,
+                full=args.full, min_warmup_s=args.min_warmup_time, keep_frame=args.dump_outputs is not None)
+    dumped = None
+    if rank == 0 and args.dump_outputs is not None:
+        dumped = dump_outputs(args.dump_outputs, m["last_frame"])
+    m["last_frame"] = None
     # which kernel the library chose for this workload (rt_capi.hip skip2_by_default): large frames walk two rays per lane
     skip_kernel = "k_render_skip2" if "two_rays" in m["launched"] else "k_render_skip"
     flat = None
-    if args.traversal == "skip" and not args.no_flat and world == 1:
+    if args.full and args.traversal == "skip" and not args.no_flat and world == 1:
         flat = measure(args.workload, rta.RT_TRAVERSAL_FLAT, max(2, min(5, args.steps)), 1, 3, multi)
     in_flight = None
-    if world == 1 and not args.force_collective and not args.no_extras and args.traversal == "skip":
+    if args.full and world == 1 and not args.force_collective and not args.no_extras and args.traversal == "skip":
         try:
             in_flight = measure_in_flight(args.workload, max(args.steps, 100))
         except Exception as e:                       # a side measurement must not take the headline down with it
             sys.stderr.write("bench.py: frames_in_flight skipped: %r\n" % (e,))
     peak_nominal = N_SIMD * LANES * CLOCK_HZ / 2.0 / 1e12
     configs, first_frame = None, None
-    if world == 1 and not args.force_collective and not args.no_configs and args.workload == "1080p" and args.traversal == "skip":
+    if args.full and world == 1 and not args.force_collective and not args.no_configs and args.workload == "1080p" and args.traversal == "skip":
         # BASELINE's neighbouring configurations, one short leg each (never `value`): what the driver's record otherwise never sees
         configs = {}
         for wl, steps_c, warm_c in (("config2", 200, 60), ("make_image", 50, 10), ("config5", 4, 2)):
@@ -653,7 +718,7 @@ def main():
         except Exception as ex:
             first_frame = {"error": repr(ex)}
     latency = None
-    if (world > 1 or args.force_collective) and args.workload == "1080p" and args.traversal == "skip":
+    if args.full and (world > 1 or args.force_collective) and args.workload == "1080p" and args.traversal == "skip":
         # ONE frame end to end, nothing batched, nothing pipelined: render -> gather -> blit, synchronised -- what a caller who wants
         # THIS frame waits for.  And the host cost of a collective call (what batching several frames per gather amortises).
         fs1 = FrameSharder(scene_of(8), rta.RenderOptions(1920, 1080, 1), rank, world, local, head_trav, force_collective=args.force_collective, mode="tiles",
@@ -676,7 +741,7 @@ def main():
             lat.append(float(tt.item()) * 1e3)
         latency = {"frame_latency_ms": round(sorted(lat)[len(lat) // 2], 4), "collective_call_host_ms": round(sorted(host)[len(host) // 2] * 1e3, 4)}
     extras = {}
-    if world > 1 and not args.no_extras and args.workload == "1080p" and args.traversal == "skip":
+    if args.full and world > 1 and not args.no_extras and args.workload == "1080p" and args.traversal == "skip":
         other = "frames" if multi == "tiles" else "tiles"
         e = measure("1080p", head_trav, args.steps, max(2, args.warmup // 2), 3, other)
         extras["weak_frames" if other == "frames" else "strong_tiles"] = e
@@ -719,7 +784,7 @@ def main():
                       "Mrays/sec + ms/frame, %dx%d spp %d %s (non-headline workload %s)" % (width, height, spp, "100k spheres" if level == "100k" else "L%d" % level, args.workload),
             "value": round(rays / (ms_per_step * 1e-3) / 1e6, 3),      # rays of every frame of a step (summed over ranks) / step time
             "unit": "Mrays/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
+            "steps": args.steps, "warmup": args.warmup, "warmup_settle_steps": m["settle_steps"], "ms_per_step": round(ms_per_step, 4),
             "higher_is_better": True, "scaling": "weak" if (multi == "frames" and world > 1) else "strong", "vs_baseline": None, "dtype": "f32",
             "data": ("synthetic (100,000 seeded random spheres, tests/scenes.py; hierarchy built by the host)" if level == "100k" else
                      "synthetic (the reference's deterministic default scene: pyramid level %d)" % level),
@@ -733,13 +798,17 @@ def main():
                        "rccl_world_size": (dist.get_world_size() if dist is not None else None)},
             "repeats": {"n": len(m["ms_reps"]), "ms_per_step_each": [round(r, 4) for r in m["ms_reps"]], "median": round(ms_per_step, 4),
                         "min": round(srt[0], 4), "max": round(srt[-1], 4), "timed_region_s": round(m["timed_region_s"], 4)},
-            "frame_crc32": m["crc"], "frame_crc_ok": m["crc_ok"],
-            "frame_crc_source": "tests/golden/oracle_vectors.json:%s.frame_crc32 (frame buffers zeroed after the warm-up; read back after the timed loop)" % golden_name,
             "mprimary_per_s": round(m["primary"] / (ms_per_step * 1e-3) / 1e6, 3),
-            "git_head": git_head(), "kernel_src_sha": src_sha,
-            "roofline": roofline(m, skip_kernel if args.traversal == "skip" else "k_flat_primary", FLOPS_PER_TEST if args.traversal == "skip" else 8,
-                                 skip_note if args.traversal == "skip" else flat_note),
+            "git_head": git_head(), "kernel_src_sha": src_sha, "full": args.full,
         }
+        if dumped is not None:
+            out["outputs"] = dumped
+        if args.full:
+            out["frame_crc32"], out["frame_crc_ok"] = m["crc"], m["crc_ok"]
+            out["frame_crc_source"] = ("tests/golden/oracle_vectors.json:%s.frame_crc32 (frame buffers zeroed after the warm-up; read back after the timed loop)"
+                                       % golden_name)
+            out["roofline"] = roofline(m, skip_kernel if args.traversal == "skip" else "k_flat_primary", FLOPS_PER_TEST if args.traversal == "skip" else 8,
+                                       skip_note if args.traversal == "skip" else flat_note)
         if flat is not None:
             fst = flat["my_stats"]
             shadow_tests = fst["tests_executed"] - fst["primary"] * n_items       # what the any-hit passes really ran
@@ -804,7 +873,7 @@ def main():
                 out["expected_shard_render_us"] = {"n_%d" % world: (exp.get("1080p") or {}).get(str(world)), "source": exp.get("source")}
             except Exception:
                 pass
-        if args.workload == "1080p" and args.traversal == "skip":
+        if args.full and args.workload == "1080p" and args.traversal == "skip":
             try:
                 # what the builder's one-GPU measurements add up to for ONE frame of BASELINE config 4 at N = 2 / 4 / 8 (rank 0's shard render + one
                 # collective call + the root's blit) beside the N = 1 frame: written down before any curve exists (tools/shard_expect.py)
@@ -825,7 +894,7 @@ def main():
             if "make_image_wall_ms" in image_wall:
                 out["make_image_wall_ms"] = image_wall["make_image_wall_ms"]
         out["library"] = {"path": os.path.relpath(rta.capi.LIB_PATH, ROOT), "build": rta.capi.build_info(), "test_hooks": rta.capi.HAVE_TEST_HOOKS}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(width, height, spp, level)
         ok = m["crc_ok"] is not False and (flat is None or flat["crc_ok"] is not False) and all(e["crc_ok"] is not False for e in extras.values()) and ok_in_flight
         ok = ok and all(c.get("frame_crc_ok") is not False for c in (configs or {}).values()) and (first_frame or {}).get("frame_crc_ok") is not False
@@ -833,7 +902,7 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        if world > 1 and not args.no_native_gang and real_rccl and args.workload == "1080p" and args.traversal == "skip":
+        if args.full and world > 1 and not args.no_native_gang and real_rccl and args.workload == "1080p" and args.traversal == "skip":
             # The other ranks are on their way out and their GPUs are free: ONE process over all N devices (rt_gang_*: ncclCommInitAll, one
             # ncclGather per frame, no torch.distributed call on the path).  A child process with a time limit: whatever happens to it, the
             # headline above stands.

@@ -182,7 +182,7 @@ def test_bench_collective_path_checks_its_own_frame(multi):
     env = dict(os.environ, RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env.pop("RTRACE_HIP_LIBRARY", None)                            # bench.py runs the product library
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--force-collective", "--multi", multi, "--steps", "4",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "1", "--force-collective", "--multi", multi, "--steps", "4",
                         "--warmup", "2", "--repeats", "2", "--min-timed-region", "0", "--no-cpu-baseline", "--no-flat", "--no-seam"], capture_output=True, text=True, env=env,
                        timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -216,7 +216,7 @@ def test_two_real_bench_ranks_share_gpu_0(multi, extra):
     procs = []
     for rank in (0, 1):
         env = util.product_env(RANK=str(rank), WORLD_SIZE="2", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-        procs.append(subprocess.Popen([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--process-group-backend", "gloo", "--sharder", "tests.host_staged:HostStagedFrameSharder", "--multi", multi,
+        procs.append(subprocess.Popen([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--process-group-backend", "gloo", "--sharder", "tests.host_staged:HostStagedFrameSharder", "--multi", multi,
                                        "--frames-per-gather", "3", "--steps", "7", "--warmup", "3", "--repeats", "2", "--min-timed-region", "0",
                                        "--no-cpu-baseline"] + extra, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env))
     outs = []
