@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define RTRACE_HIP_ABI_VERSION 4
+#define RTRACE_HIP_ABI_VERSION 5
 
 typedef enum rt_status {
     RT_OK = 0,
@@ -255,6 +255,31 @@ rt_status rt_gang_render_frame(rt_gang *gang, const rt_options *options, rt_trav
 rt_status rt_gang_render_frames(rt_gang *gang, const rt_options *options, rt_traversal traversal,
                                 const rt_region *tiles, uint32_t n_tiles, uint8_t *const *frames_rgba_host, uint32_t n_frames,
                                 rt_stats *stats);
+
+/* ---- ray queries (ABI 5): TypedGroup::intersect(&mut hit, &ray) (group.rs:72-83 over primitive.rs:55-84) for a batch of ANY rays ----
+ * Ray i is rays[6i .. 6i+6] = pos.xyz, dir.xyz and starts with hit.distance = tmax[i] (tmax NULL: +inf, Hit::missed(); a tmax <= 0
+ * finds nothing).  The walk is the reference's hierarchy walk, test for test, in REAL (as for rt_scene_create); a scene created without
+ * bounds has no hierarchy, and the query is then the flat nearest hit over all its items in DFS order.
+ *   RT_QUERY_NEAREST  distance_out[i] = the final hit.distance (tmax[i] when nothing was closer); normal_out[3i..] = the final Hit.pos,
+ *                     the unit normal primitive.rs:82 forms ({0, 0, 0} when nothing was closer); item_out[i] = the DFS index of the item
+ *                     that won (the first in DFS order on equal distances), or -1
+ *   RT_QUERY_ANY      occlusion: the walk stops at the first item closer than tmax[i] -- distance_out[i] = that item's distance, item_out[i]
+ *                     its DFS index, normal_out its normal there; tmax[i], -1 and {0, 0, 0} when there is none (then the nearest
+ *                     query finds nothing below tmax either, and the other way round).
+ * normal_out and item_out may be NULL.  stats (may be NULL): primary = n, hits = rays with a result below tmax, sphere_tests / bound_tests /
+ * tests_executed of the walk, every other counter 0; asking for it runs the counting flavour of the kernel (same bytes). */
+typedef enum rt_query { RT_QUERY_NEAREST = 0, RT_QUERY_ANY = 1 } rt_query;
+/* Host memory.  Returns when the results are in place.  RT_ERR_INVALID_ARGUMENT, before the device is touched, for a NULL scene, rays or
+ * distance_out, n == 0, an unknown mode, and for rays outside the domain rt_scene_create puts on the light and the eye: a non-finite
+ * component, |pos coordinate| > 1e15, a direction whose squared length is not within 2e-3 of 1, a NaN tmax.  Memory from rt_host_alloc /
+ * rt_host_register is read and written by the kernel directly; pageable memory is copied through the call's device workspace. */
+rt_status rt_intersect_rays(rt_scene *scene, rt_query mode, const void *rays, const void *tmax, uint32_t n,
+                            void *distance_out, void *normal_out, int32_t *item_out, rt_stats *stats);
+/* The same over DEVICE memory on the scene's device, enqueued on `hip_stream` (a hipStream_t as void*; NULL = the null stream) without
+ * waiting for it.  Only pointers, alignment, n and mode are checked: a ray outside the domain above gives unspecified values, never a
+ * fault -- the walk ends for any input bits.  stats != NULL: filled after an internal synchronisation of hip_stream. */
+rt_status rt_intersect_rays_device(rt_scene *scene, rt_query mode, const void *rays, const void *tmax, uint32_t n,
+                                   void *distance_out, void *normal_out, int32_t *item_out, void *hip_stream, rt_stats *stats);
 
 /* Bytes rt_render_tiles writes for this tile list (4 * total area), or 0 on an invalid list. */
 uint64_t rt_tiles_rgba_bytes(const rt_region *tiles, uint32_t n_tiles);

@@ -14,6 +14,7 @@
 #include "rt_flat_wf.hpp"
 #include "rt_flat_sc.hpp"
 #include "rt_flat_f64.hpp"
+#include "rt_query.hpp"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>       // types and prototypes only: librccl.so is loaded with dlopen when the first gang is created
@@ -121,6 +122,8 @@ struct Context {
     void *d_queue1 = nullptr, *d_queue2 = nullptr;   // flat wavefront pipeline: shadow-ray queues, Quad<REAL> per sample
     size_t queue_cap = 0;             // bytes of each queue
     rt::FlatQueues *d_queues = nullptr;
+    void *d_query = nullptr;          // rt_intersect_rays: device copies of the rays and results of pageable / unmapped host buffers
+    size_t query_cap = 0;             // bytes of d_query
     unsigned flat_first_pass_items = 0;   // items the first shadow pass of the last flat launch covered (rt_stats.tests_executed)
     bool busy = false;       // leased to a caller right now
     bool inflight = false;   // released by an asynchronous caller; reusable once ev1 has completed
@@ -140,6 +143,7 @@ struct Context {
         if (d_queue1) (void)hipFree(d_queue1);
         if (d_queue2) (void)hipFree(d_queue2);
         if (d_queues) (void)hipFree(d_queues);
+        if (d_query) (void)hipFree(d_query);
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
         if (stream2) (void)hipStreamDestroy(stream2);
@@ -238,6 +242,11 @@ struct rt_scene {
                         rt_options seen_o{}; rt_traversal seen_trav = RT_TRAVERSAL_SKIP; int seen_idx = -1;      // the last lone request (frame-ahead engages with the second bucket)
                         hipStream_t stream = nullptr; hipEvent_t ev = nullptr; int readers = 0; std::mutex mu; std::condition_variable cv; } ahead;
     std::mutex comb_mu;
+    // ray queries on a scene without bounds: its items as a stream of ITEM nodes (rt_query.hpp k_items_stream), made on the stream of the
+    // first query; until `query_items_ev` (recorded there) has completed, later queries wait for it
+    std::mutex query_mu;
+    void *d_query_items = nullptr;
+    hipEvent_t query_items_ev = nullptr;
     std::vector<RegionReq *> comb_pending;
     int comb_leaders = 0;              // passes being led right now (<= kMaxRegionLeaders)
 };

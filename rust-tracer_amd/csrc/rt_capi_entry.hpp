@@ -269,6 +269,8 @@ rt_status rt_scene_destroy(rt_scene *s)
     if (s->d_items) (void)hipFree(s->d_items);
     if (s->d_prim) (void)hipFree(s->d_prim);
     if (s->d_shad) (void)hipFree(s->d_shad);
+    if (s->d_query_items) (void)hipFree(s->d_query_items);
+    if (s->query_items_ev) (void)hipEventDestroy(s->query_items_ev);
     if (s->d_cprim) (void)hipFree(s->d_cprim);
     if (s->d_cshad) (void)hipFree(s->d_cshad);
     for (void *p : { s->d_xprim, s->d_xshad, s->d_xcprim, s->d_xcshad, s->d_xown, s->d_fc, s->d_coop_prim, s->d_coop_shad, s->d_cost_arena }) if (p) (void)hipFree(p);
@@ -707,6 +709,100 @@ rt_status rt_render_frame_stream(rt_scene *s, const rt_options *o, rt_traversal 
         if (callback) callback(user, first, cnt);
     }
     // (the last batch's event is behind everything on both streams: the context goes back idle)
+    return RT_OK;
+}
+
+// ---- ray queries: TypedGroup::intersect(&mut hit, &ray) for a batch of arbitrary rays (rt_query.hpp) ----
+
+rt_status rt_intersect_rays_device(rt_scene *s, rt_query mode, const void *rays, const void *tmax, uint32_t n, void *distance_out, void *normal_out,
+                                   int32_t *item_out, void *hip_stream, rt_stats *stats)
+{
+    if (!query_args_ok(s, mode, rays, tmax, n, distance_out, normal_out, item_out, "rt_intersect_rays_device")) return RT_ERR_INVALID_ARGUMENT;
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    const void *nodes = nullptr;
+    uint32_t n_nodes = 0;
+    rt_status st = query_stream(s, stream, &nodes, &n_nodes);
+    if (st != RT_OK) return st;
+    if (!stats) return enqueue_query(s, nodes, n_nodes, mode, rays, tmax, n, distance_out, normal_out, item_out, nullptr, stream);
+    Context *c = nullptr;
+    if ((st = acquire(s, &c)) != RT_OK) return st;
+    Lease lease{ s, c };
+    HIP_TRY(hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, stream));
+    HIP_TRY(hipEventRecord(c->ev0, stream));
+    st = enqueue_query(s, nodes, n_nodes, mode, rays, tmax, n, distance_out, normal_out, item_out, c->d_counters, stream);
+    (void)hipEventRecord(c->ev1, stream);
+    if (st != RT_OK) { (void)hipGetLastError(); lease.inflight = true; return st; }      // (the context goes back behind what is enqueued)
+    return read_query_stats(c, stream, stats);
+}
+
+rt_status rt_intersect_rays(rt_scene *s, rt_query mode, const void *rays, const void *tmax, uint32_t n, void *distance_out, void *normal_out,
+                            int32_t *item_out, rt_stats *stats)
+{
+    if (!query_args_ok(s, mode, rays, tmax, n, distance_out, normal_out, item_out, "rt_intersect_rays")) return RT_ERR_INVALID_ARGUMENT;
+    const bool f32 = s->precision == RT_F32;
+    if (!(f32 ? query_rays_valid(static_cast<const float *>(rays), static_cast<const float *>(tmax), n)
+              : query_rays_valid(static_cast<const double *>(rays), static_cast<const double *>(tmax), n)))
+        return RT_ERR_INVALID_ARGUMENT;
+    HIP_TRY(hipSetDevice(s->device));
+    rt_status st = RT_OK;
+    // Every buffer is either the caller's own memory, read and written by the kernel directly (rt_host_alloc / rt_host_register), or a
+    // device copy in the call's workspace (pageable memory: the copies go through the runtime's staging).
+    const size_t esz = f32 ? sizeof(float) : sizeof(double);
+    struct Buf { void *host; size_t bytes; bool out; uint8_t *dev; size_t off; bool staged; };
+    Buf b[5] = { { const_cast<void *>(rays), 6 * esz * n, false, nullptr, 0, false }, { const_cast<void *>(tmax), esz * n, false, nullptr, 0, false },
+                 { distance_out, esz * n, true, nullptr, 0, false }, { normal_out, 3 * esz * n, true, nullptr, 0, false },
+                 { item_out, sizeof(int32_t) * n, true, nullptr, 0, false } };
+    size_t need = 0;
+    for (Buf &x : b) {
+        if (!x.host) continue;
+        const HostDest d = classify_host_pointer(x.host);
+        if (d.bad) {
+            snprintf(g_err, sizeof g_err, "rt_intersect_rays: a buffer is device memory; use rt_intersect_rays_device");
+            return RT_ERR_INVALID_ARGUMENT;
+        }
+        if (d.pinned && d.dev_alias && d.room >= x.bytes) { x.dev = d.dev_alias; continue; }
+        x.staged = true;
+        x.off = need;
+        need += (x.bytes + 255) & ~(size_t)255;
+    }
+    Context *c = nullptr;
+    if ((st = acquire(s, &c)) != RT_OK) return st;
+    Lease lease{ s, c };
+    const void *nodes = nullptr;
+    uint32_t n_nodes = 0;
+    if ((st = query_stream(s, c->stream, &nodes, &n_nodes)) != RT_OK) return st;
+    if (need > c->query_cap) {
+        if (c->d_query) HIP_TRY(hipFree(c->d_query));
+        c->d_query = nullptr; c->query_cap = 0;
+        HIP_TRY(hipMalloc(&c->d_query, need));
+        c->query_cap = need;
+    }
+    for (Buf &x : b)
+        if (x.staged) x.dev = static_cast<uint8_t *>(c->d_query) + x.off;
+    // from the first copy on, work of this call may be queued: an error return first waits for it
+#define HIP_DRAIN(expr)                                                                                                   \
+    do {                                                                                                                  \
+        hipError_t e__ = (expr);                                                                                          \
+        if (e__ != hipSuccess) { (void)hipStreamSynchronize(c->stream); return hip_fail(e__, #expr, __LINE__); }          \
+    } while (0)
+    for (const Buf &x : b)
+        if (x.staged && !x.out)
+            HIP_DRAIN(hipMemcpyAsync(x.dev, x.host, x.bytes, hipMemcpyHostToDevice, c->stream));
+    if (stats) {
+        HIP_DRAIN(hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, c->stream));
+        HIP_DRAIN(hipEventRecord(c->ev0, c->stream));
+    }
+    st = enqueue_query(s, nodes, n_nodes, mode, b[0].dev, b[1].dev, n, b[2].dev, b[3].dev, reinterpret_cast<int32_t *>(b[4].dev),
+                       stats ? c->d_counters : nullptr, c->stream);
+    if (st != RT_OK) { (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return st; }
+    if (stats) HIP_DRAIN(hipEventRecord(c->ev1, c->stream));
+    for (const Buf &x : b)
+        if (x.staged && x.out)
+            HIP_DRAIN(hipMemcpyAsync(x.host, x.dev, x.bytes, hipMemcpyDeviceToHost, c->stream));
+    if (stats) return read_query_stats(c, c->stream, stats);          // synchronises the stream
+    HIP_DRAIN(hipStreamSynchronize(c->stream));
+#undef HIP_DRAIN
     return RT_OK;
 }
 

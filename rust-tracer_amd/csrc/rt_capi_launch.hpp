@@ -560,3 +560,130 @@ bool items_valid(const void *p, uint32_t n, bool need_positive_radius)
     return true;
 }
 
+
+// ---- ray queries (rt_intersect_rays*, rt_query.hpp) ----
+
+// The stream a ray query walks: the scene's plain per-origin stream, or -- for a scene created without bounds -- its items as a stream of
+// ITEM nodes, derived by the first query on that query's own stream (no other caller's work is waited for).  Until the derivation's
+// event has completed, every later query makes its stream wait for it.
+rt_status query_stream(rt_scene *s, hipStream_t stream, const void **nodes, uint32_t *n_nodes)
+{
+    if (s->n_nodes) { *nodes = s->d_shad; *n_nodes = s->n_nodes; return RT_OK; }
+    std::lock_guard<std::mutex> lk(s->query_mu);
+    if (!s->d_query_items) {
+        const bool f32 = s->precision == RT_F32;
+        const unsigned total = s->n_items + rt::kNodePad;
+        void *p = nullptr;
+        hipEvent_t ev = nullptr;
+        HIP_TRY(hipMalloc(&p, (f32 ? sizeof(rt::Node<float>) : sizeof(rt::Node<double>)) * total));
+        hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+        if (e == hipSuccess) {
+            const dim3 grid((total + 255) / 256), block(256);
+            if (f32) hipLaunchKernelGGL(rt::k_items_stream<float>, grid, block, 0, stream, static_cast<const rt::Item<float> *>(s->d_items), s->n_items, static_cast<rt::Node<float> *>(p));
+            else hipLaunchKernelGGL(rt::k_items_stream<double>, grid, block, 0, stream, static_cast<const rt::Item<double> *>(s->d_items), s->n_items, static_cast<rt::Node<double> *>(p));
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipEventRecord(ev, stream);
+        if (e != hipSuccess) {
+            if (ev) (void)hipEventDestroy(ev);
+            (void)hipStreamSynchronize(stream);          // (a launched derivation must not write freed memory)
+            (void)hipFree(p);
+            return hip_fail(e, "k_items_stream", __LINE__);
+        }
+        s->d_query_items = p; s->query_items_ev = ev;
+    } else if (s->query_items_ev) {
+        const hipError_t q = hipEventQuery(s->query_items_ev);
+        if (q == hipSuccess) { (void)hipEventDestroy(s->query_items_ev); s->query_items_ev = nullptr; }
+        else {
+            (void)hipGetLastError();
+            HIP_TRY(hipStreamWaitEvent(stream, s->query_items_ev, 0));
+        }
+    }
+    *nodes = s->d_query_items; *n_nodes = s->n_items;
+    return RT_OK;
+}
+
+// Pointers and sizes every query entry checks (device pointers are not dereferenced here).
+bool query_args_ok(const rt_scene *s, rt_query mode, const void *rays, const void *tmax, uint32_t n, const void *dist, const void *normal, const int32_t *item,
+                   const char *what)
+{
+    if (!s || !rays || !dist || n == 0 || (mode != RT_QUERY_NEAREST && mode != RT_QUERY_ANY)) {
+        snprintf(g_err, sizeof g_err, "%s: NULL scene, rays or distance_out, n == 0 or unknown mode", what);
+        return false;
+    }
+    const uintptr_t esz = s->precision == RT_F32 ? sizeof(float) : sizeof(double);
+    for (const void *p : { rays, tmax, dist, normal })
+        if ((reinterpret_cast<uintptr_t>(p) % esz) != 0) { snprintf(g_err, sizeof g_err, "%s: REAL buffers must be %u-byte aligned", what, (unsigned)esz); return false; }
+    if ((reinterpret_cast<uintptr_t>(item) & 3u) != 0) { snprintf(g_err, sizeof g_err, "%s: item_out must be 4-byte aligned", what); return false; }
+    return true;
+}
+
+// The host entry's domain, the bounds rt_scene_create puts on the light and the eye: finite, |pos| <= 1e15, a unit direction (squared
+// length within 2e-3 of 1) and a tmax that is not NaN -- no intermediate of the walk overflows.
+template <typename T>
+bool query_rays_valid(const T *rays, const T *tmax, uint32_t n)
+{
+    for (uint32_t i = 0; i < n; ++i) {
+        const T *r = rays + 6 * (size_t)i;
+        for (int k = 0; k < 6; ++k) {
+            if (!std::isfinite(r[k]) || (k < 3 && std::fabs((double)r[k]) > 1e15)) {
+                snprintf(g_err, sizeof g_err, "rt_intersect_rays: ray %u has a non-finite component or |pos| > 1e15", i);
+                return false;
+            }
+        }
+        const double d2 = (double)r[3] * r[3] + (double)r[4] * r[4] + (double)r[5] * r[5];
+        if (std::fabs(d2 - 1.0) > 2e-3) {
+            snprintf(g_err, sizeof g_err, "rt_intersect_rays: ray %u's direction is not a unit vector (its squared length is %.6g)", i, d2);
+            return false;
+        }
+        if (tmax && std::isnan(tmax[i])) {
+            snprintf(g_err, sizeof g_err, "rt_intersect_rays: tmax[%u] is NaN", i);
+            return false;
+        }
+    }
+    return true;
+}
+
+// One query launch on `stream`: counters != NULL runs the counting flavour (same bytes).
+template <typename T>
+rt_status enqueue_query(const rt_scene *s, const void *nodes, uint32_t n_nodes, rt_query mode, const void *rays, const void *tmax, uint32_t n,
+                        void *dist, void *normal, int32_t *item, rt::Counters *counters, hipStream_t stream)
+{
+    const rt::QueryArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), static_cast<const rt::Item<T> *>(s->d_items), static_cast<const T *>(rays),
+                              static_cast<const T *>(tmax), static_cast<T *>(dist), static_cast<T *>(normal), item, counters, n_nodes, n };
+    const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
+    const bool any = mode == RT_QUERY_ANY;
+    if (counters) {
+        if (any) hipLaunchKernelGGL((rt::k_query_rays<T, true, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((rt::k_query_rays<T, true, false>), grid, block, 0, stream, a);
+    } else {
+        if (any) hipLaunchKernelGGL((rt::k_query_rays<T, false, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((rt::k_query_rays<T, false, false>), grid, block, 0, stream, a);
+    }
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+rt_status enqueue_query(const rt_scene *s, const void *nodes, uint32_t n_nodes, rt_query mode, const void *rays, const void *tmax, uint32_t n,
+                        void *dist, void *normal, int32_t *item, rt::Counters *counters, hipStream_t stream)
+{
+    return s->precision == RT_F32 ? enqueue_query<float>(s, nodes, n_nodes, mode, rays, tmax, n, dist, normal, item, counters, stream)
+                                  : enqueue_query<double>(s, nodes, n_nodes, mode, rays, tmax, n, dist, normal, item, counters, stream);
+}
+
+// A counting query's rt_stats: primary = rays, hits = results below tmax, the tests; every other counter 0.  Synchronises `stream`.
+rt_status read_query_stats(Context *c, hipStream_t stream, rt_stats *st)
+{
+    std::vector<rt::Counters> stripes(rt::kCounterStripes);
+    HIP_TRY(hipMemcpyAsync(stripes.data(), c->d_counters, sizeof(rt::Counters) * rt::kCounterStripes, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    rt::Counters h{};
+    for (const rt::Counters &k : stripes) { h.primary += k.primary; h.hits += k.hits; h.sphere_tests += k.sphere_tests; h.bound_tests += k.bound_tests; }
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    *st = rt_stats{};
+    st->primary = h.primary; st->hits = h.hits;
+    st->sphere_tests = h.sphere_tests; st->bound_tests = h.bound_tests; st->tests_executed = h.sphere_tests + h.bound_tests;
+    st->device_ms = ms;
+    return RT_OK;
+}

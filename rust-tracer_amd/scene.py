@@ -5,6 +5,7 @@ All scene arithmetic is done in the scene's REAL type with numpy scalars (IEEE, 
 reference operation order) -- centres accumulate rounding level by level, so the builder replays the
 recursion instead of using a closed form.  Rendering never happens here; see render.py / capi.py."""
 import ctypes as C
+import sys
 
 import numpy as np
 
@@ -13,6 +14,16 @@ from . import capi
 
 def _real(precision):
     return np.float32 if precision == capi.RT_F32 else np.float64
+
+
+def _tmax_array(tmax, R, n):
+    """A query's tmax as a contiguous REAL[n]: one value (a Python float, a 0-d array) is rounded to REAL; an array must already be REAL."""
+    t = np.asarray(tmax)
+    if t.ndim == 0 and t.dtype.kind in "fiu":
+        t = t.astype(R)
+    if t.dtype != R or t.size not in (1, n):
+        raise ValueError("tmax must be one value or an (n,) array of %s" % np.dtype(R).name)
+    return np.ascontiguousarray(np.broadcast_to(t.reshape(-1), (n,)))
 
 
 def pyramid(level, origin, radius, precision=capi.RT_F32):
@@ -347,6 +358,85 @@ class DeviceScene:
                                              C.c_void_p(stream), C.byref(st) if want_stats else None)
         capi.check(rc, "rt_render_frame_device")
         return st.as_dict() if want_stats else None
+
+    def intersect(self, rays, tmax=None, any_hit=False, want_stats=False, stream=None, out=None):
+        """rt_intersect_rays / rt_intersect_rays_device: TypedGroup::intersect for every ray of `rays` (n x 6: pos.xyz, dir.xyz, the scene's REAL
+        dtype) -> (distance[n], normal[n, 3], item[n] (DFS index or -1)[, stats dict]).  tmax: hit.distance going in, per ray (an array of
+        the scene's REAL) or one value (rounded to REAL; None: +inf).  any_hit: occlusion -- the first item closer than tmax instead of the nearest.
+        A numpy array goes through the host entry and gets numpy results (out: optional (distance, normal, item) arrays to fill, e.g. from
+        capi.HostBuffer, which the kernel then writes directly); a torch tensor on this scene's device goes through the device entry on
+        `stream` (a torch stream or a hipStream_t as int; default the current torch stream) and gets torch tensors on that device: the
+        query waits for the work queued on the current torch stream, and its results belong to `stream` (use them there, or synchronise)."""
+        R = _real(self.scene.precision)
+        mode = capi.RT_QUERY_ANY if any_hit else capi.RT_QUERY_NEAREST
+        st = capi.Stats()
+        stp = C.byref(st) if want_stats else None
+        torch = sys.modules.get("torch")
+        if torch is not None and isinstance(rays, torch.Tensor):
+            tdt = torch.float32 if R == np.float32 else torch.float64
+            dev = torch.device("cuda", self.device)
+            if rays.dtype != tdt or rays.dim() != 2 or rays.shape[1] != 6 or rays.shape[0] == 0:
+                raise ValueError("rays must be a non-empty (n, 6) %s tensor" % tdt)
+            if rays.device != dev:
+                raise ValueError("rays must be on %s, not %s" % (dev, rays.device))
+            n = rays.shape[0]
+            if isinstance(tmax, torch.Tensor):
+                if tmax.dim() == 0 and tmax.dtype.is_floating_point:
+                    tmax = tmax.to(tdt)                                  # one value: rounded to the scene's REAL
+                if tmax.dtype != tdt or tmax.numel() not in (1, n):
+                    raise ValueError("tmax must be a %s value or (n,) tensor" % tdt)
+            elif tmax is not None:
+                tmax = _tmax_array(tmax, R, n)
+            # The query runs on `qs`.  It first waits for what the caller has queued on the current stream (the inputs were made there),
+            # and everything this call allocates -- copies of the inputs, the results -- comes from qs's pool, so no allocation of another
+            # stream can reuse that memory while the query still uses it.  The caller's own input tensors are marked as used on qs.
+            cur = torch.cuda.current_stream(dev)
+            if stream is None:
+                qs = cur
+            elif isinstance(stream, torch.cuda.Stream):
+                qs = stream
+            else:
+                h = int(stream)
+                qs = torch.cuda.default_stream(dev) if h == 0 else torch.cuda.ExternalStream(h, device=dev)
+            if qs != cur:
+                qs.wait_stream(cur)
+            with torch.cuda.stream(qs):
+                r = rays.contiguous()
+                t = None
+                if isinstance(tmax, torch.Tensor):
+                    t = tmax.to(dev).reshape(-1).expand(n).contiguous()
+                elif tmax is not None:
+                    t = torch.from_numpy(tmax).to(dev)
+                dist = torch.empty(n, dtype=tdt, device=dev)
+                normal = torch.empty((n, 3), dtype=tdt, device=dev)
+                item = torch.empty(n, dtype=torch.int32, device=dev)
+                rc = capi.lib.rt_intersect_rays_device(self._h, mode, C.c_void_p(r.data_ptr()), C.c_void_p(t.data_ptr()) if t is not None else None, n,
+                                                       C.c_void_p(dist.data_ptr()), C.c_void_p(normal.data_ptr()), C.c_void_p(item.data_ptr()),
+                                                       C.c_void_p(qs.cuda_stream), stp)
+            if qs != cur:
+                for x in (rays, tmax):
+                    if isinstance(x, torch.Tensor) and x.is_cuda:
+                        x.record_stream(qs)
+            capi.check(rc, "rt_intersect_rays_device")
+        else:
+            if not isinstance(rays, np.ndarray) or rays.dtype != R or rays.ndim != 2 or rays.shape[1] != 6 or rays.shape[0] == 0:
+                raise ValueError("rays must be a non-empty (n, 6) numpy array of %s (or a torch tensor on the scene's device)" % np.dtype(R).name)
+            n = rays.shape[0]
+            rays = np.ascontiguousarray(rays)
+            t = None if tmax is None else _tmax_array(tmax, R, n)
+            if out is None:
+                dist, normal, item = np.empty(n, dtype=R), np.empty((n, 3), dtype=R), np.empty(n, dtype=np.int32)
+            else:
+                dist, normal, item = out
+                for a, dt, shape in ((dist, R, (n,)), (normal, R, (n, 3)), (item, np.int32, (n,))):
+                    if a.dtype != dt or a.shape != shape or not a.flags.c_contiguous:
+                        raise ValueError("out: contiguous arrays of %s, %s and int32 of shapes (n,), (n, 3), (n,)" % ((np.dtype(R).name,) * 2))
+            rc = capi.lib.rt_intersect_rays(self._h, mode, rays.ctypes.data, t.ctypes.data if t is not None else None, n,
+                                            dist.ctypes.data, normal.ctypes.data, item.ctypes.data, stp)
+            capi.check(rc, "rt_intersect_rays")
+        if want_stats:
+            return dist, normal, item, st.as_dict()
+        return dist, normal, item
 
     def blit_tiles_device(self, options, regions, src_ptr, frame_ptr, stream=0, src_px_offset=None):
         """rt_blit_tiles_device: tile-major device tiles -> row-major device frame (set_pixels_from_buffer)."""
