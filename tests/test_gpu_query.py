@@ -9,6 +9,7 @@ import oracle
 import rust_tracer_amd as rta
 from rust_tracer_amd import capi
 from tests import util
+from tests.edge_scenes import sample_rays
 from tests.scenes import hundred_thousand_spheres, random_nested_scene
 
 pytestmark = pytest.mark.gpu
@@ -154,18 +155,11 @@ def test_tangent_ties_and_scenes_without_bounds(precision):
     assert (item >= 0).any() and (item < 0).any()
 
 
-def camera_rays(w, h, eye):
-    """The render's primary rays (render.rs:231-241, spp 1) restated in numpy float32: dir = (x - w/2, (h - y) - h/2, w) normalised as vec.rs:87-95."""
-    f = np.float32
-    y, x = np.meshgrid(np.arange(h, dtype=f), np.arange(w, dtype=f), indexing="ij")
-    fw, fh = f(w), f(h)
-    dx, dy, dz = x - fw / f(2), (fh - y) - fh / f(2), np.full_like(x, fw)
-    ln = np.sqrt((dx * dx + dy * dy) + dz * dz)
-    inv = f(1) / ln
-    rays = np.empty((w * h, 6), dtype=f)
-    rays[:, :3] = np.asarray(eye, dtype=f)
-    rays[:, 3], rays[:, 4], rays[:, 5] = (dx * inv).ravel(), (dy * inv).ravel(), (dz * inv).ravel()
-    return rays
+def camera_rays(w, h, eye, spp=1, prec=oracle.F32):
+    """The render's primary rays (render.rs:231-241), one per pixel and sample, in the order y, x, ssx, ssy (tests/edge_scenes.py
+    sample_rays, the one restatement of the sample ray)."""
+    y, x, sx, sy = np.meshgrid(np.arange(h), np.arange(w), np.arange(spp), np.arange(spp), indexing="ij")
+    return sample_rays(w, h, spp, x, y, sx, sy, eye, prec).reshape(-1, 6)
 
 
 @pytest.mark.parametrize("w,h", [(1920, 1080), (800, 600), (1024, 768)])
