@@ -281,6 +281,33 @@ rt_status rt_intersect_rays(rt_scene *scene, rt_query mode, const void *rays, co
 rt_status rt_intersect_rays_device(rt_scene *scene, rt_query mode, const void *rays, const void *tmax, uint32_t n,
                                    void *distance_out, void *normal_out, int32_t *item_out, void *hip_stream, rt_stats *stats);
 
+/* ---- traced rays and camera frames (additive to ABI 5): Renderer::raytrace (render.rs:171-215) for ANY rays, render_region (render.rs:218-255)
+ * for ANY pinhole camera ----
+ * A ray is traced as the render traces a sample: the nearest hit from pos (the hierarchy walk of rt_intersect_rays; a scene created without
+ * bounds: the flat nearest hit), the shading of render.rs:190-199 and, where n.light < 0, the any-hit shadow ray from
+ * (pos + dir*d) + n*(d*sqrt(EPSILON)) along -light -- one kernel, in REAL, every operation in the reference's order.
+ * stats (may be NULL): primary = rays (samples), hits / shadow / occluded as rt_render_tiles counts them, sphere_tests / bound_tests /
+ * tests_executed / primary_tests of both walks, device_ms; the longest_wave_* fields 0.  Asking for it runs the counting flavour (same bytes). */
+/* Ray i is rays[6i .. 6i+6] = pos.xyz, dir.xyz.  color_out[3i ..] (REAL) = the colour raytrace(s, r, &mut c) leaves in a c that starts at
+ * {0, 0, 0}; alpha_out[i] (REAL, may be NULL) = its return value, 1 when lit, else 0.  Host memory, validated as rt_intersect_rays validates
+ * its rays (RT_ERR_INVALID_ARGUMENT before the device is touched, also for a NULL scene, rays or color_out and n == 0); memory from
+ * rt_host_alloc / rt_host_register is used in place, pageable memory goes through the call's device workspace. */
+rt_status rt_trace_rays(rt_scene *scene, const void *rays, uint32_t n, void *color_out, void *alpha_out, rt_stats *stats);
+/* The same over DEVICE memory, enqueued on `hip_stream` as rt_intersect_rays_device is: only pointers, alignment and n are checked. */
+rt_status rt_trace_rays_device(rt_scene *scene, const void *rays, uint32_t n, void *color_out, void *alpha_out,
+                               void *hip_stream, rt_stats *stats);
+/* rt_render_tiles through a pinhole camera: `camera` is REAL[12] in HOST memory (both entries) = eye.xyz, right.xyz, up.xyz, forward.xyz.
+ * Sample (x, y, ssx, ssy): u = xres - width/2, v = (height - yres) - height/2 (render.rs:238-242) and the ray from eye along
+ * normalized((right*u + up*v) + forward*width), every operation rounded once.  The identity camera {Scene::eye, (1,0,0), (0,1,0), (0,0,1)}
+ * renders the bytes of rt_render_tiles; |forward| sets the field of view (1: the reference's, horizontally 2*atan(0.5)).  Options, regions,
+ * output layout and status codes as rt_render_tiles / rt_render_tiles_device; a scene with bounds is walked as the reference's hierarchy,
+ * one without as the flat scan.  RT_ERR_INVALID_ARGUMENT before the device is touched for a camera with a non-finite value, an eye
+ * coordinate beyond +-1e15, an axis whose length is outside [1e-2, 1e2], or |det(right, up, forward)| < 1e-2 |right| |up| |forward|. */
+rt_status rt_render_camera(rt_scene *scene, const rt_options *options, const void *camera,
+                           const rt_region *tiles, uint32_t n_tiles, uint8_t *rgba_out, rt_stats *stats);
+rt_status rt_render_camera_device(rt_scene *scene, const rt_options *options, const void *camera,
+                                  const rt_region *tiles, uint32_t n_tiles, void *rgba_out_device, void *hip_stream, rt_stats *stats);
+
 /* Bytes rt_render_tiles writes for this tile list (4 * total area), or 0 on an invalid list. */
 uint64_t rt_tiles_rgba_bytes(const rt_region *tiles, uint32_t n_tiles);
 

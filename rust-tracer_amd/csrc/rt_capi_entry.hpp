@@ -806,6 +806,187 @@ rt_status rt_intersect_rays(rt_scene *s, rt_query mode, const void *rays, const 
     return RT_OK;
 }
 
+// ---- traced rays and camera frames: Renderer::raytrace for any ray, render_region for any pinhole camera (rt_trace.hpp) ----
+
+rt_status rt_trace_rays_device(rt_scene *s, const void *rays, uint32_t n, void *color_out, void *alpha_out, void *hip_stream, rt_stats *stats)
+{
+    if (!trace_args_ok(s, rays, n, color_out, alpha_out, "rt_trace_rays_device")) return RT_ERR_INVALID_ARGUMENT;
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    const void *nodes = nullptr;
+    uint32_t n_nodes = 0;
+    rt_status st = query_stream(s, stream, &nodes, &n_nodes);
+    if (st != RT_OK) return st;
+    if (!stats) return enqueue_trace(s, nodes, n_nodes, rays, n, color_out, alpha_out, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, stream);
+    Context *c = nullptr;
+    if ((st = acquire(s, &c)) != RT_OK) return st;
+    Lease lease{ s, c };
+    HIP_TRY(hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, stream));
+    HIP_TRY(hipEventRecord(c->ev0, stream));
+    st = enqueue_trace(s, nodes, n_nodes, rays, n, color_out, alpha_out, nullptr, nullptr, nullptr, 0, 0, nullptr, c->d_counters, stream);
+    (void)hipEventRecord(c->ev1, stream);
+    if (st != RT_OK) { (void)hipGetLastError(); lease.inflight = true; return st; }      // (the context goes back behind what is enqueued)
+    return read_trace_stats(c, stream, stats);
+}
+
+rt_status rt_trace_rays(rt_scene *s, const void *rays, uint32_t n, void *color_out, void *alpha_out, rt_stats *stats)
+{
+    if (!trace_args_ok(s, rays, n, color_out, alpha_out, "rt_trace_rays")) return RT_ERR_INVALID_ARGUMENT;
+    const bool f32 = s->precision == RT_F32;
+    if (!(f32 ? query_rays_valid(static_cast<const float *>(rays), static_cast<const float *>(nullptr), n)
+              : query_rays_valid(static_cast<const double *>(rays), static_cast<const double *>(nullptr), n)))
+        return RT_ERR_INVALID_ARGUMENT;
+    HIP_TRY(hipSetDevice(s->device));
+    rt_status st = RT_OK;
+    // pinned buffers are read and written by the kernel in place, pageable ones go through the call's workspace (as rt_intersect_rays)
+    const size_t esz = f32 ? sizeof(float) : sizeof(double);
+    struct Buf { void *host; size_t bytes; bool out; uint8_t *dev; size_t off; bool staged; };
+    Buf b[3] = { { const_cast<void *>(rays), 6 * esz * n, false, nullptr, 0, false }, { color_out, 3 * esz * n, true, nullptr, 0, false },
+                 { alpha_out, esz * n, true, nullptr, 0, false } };
+    size_t need = 0;
+    for (Buf &x : b) {
+        if (!x.host) continue;
+        const HostDest d = classify_host_pointer(x.host);
+        if (d.bad) {
+            snprintf(g_err, sizeof g_err, "rt_trace_rays: a buffer is device memory; use rt_trace_rays_device");
+            return RT_ERR_INVALID_ARGUMENT;
+        }
+        if (d.pinned && d.dev_alias && d.room >= x.bytes) { x.dev = d.dev_alias; continue; }
+        x.staged = true;
+        x.off = need;
+        need += (x.bytes + 255) & ~(size_t)255;
+    }
+    Context *c = nullptr;
+    if ((st = acquire(s, &c)) != RT_OK) return st;
+    Lease lease{ s, c };
+    const void *nodes = nullptr;
+    uint32_t n_nodes = 0;
+    if ((st = query_stream(s, c->stream, &nodes, &n_nodes)) != RT_OK) return st;
+    if (need > c->query_cap) {
+        if (c->d_query) HIP_TRY(hipFree(c->d_query));
+        c->d_query = nullptr; c->query_cap = 0;
+        HIP_TRY(hipMalloc(&c->d_query, need));
+        c->query_cap = need;
+    }
+    for (Buf &x : b)
+        if (x.staged) x.dev = static_cast<uint8_t *>(c->d_query) + x.off;
+    // from the first copy on, work of this call may be queued: an error return first waits for it
+#define HIP_DRAIN(expr)                                                                                                   \
+    do {                                                                                                                  \
+        hipError_t e__ = (expr);                                                                                          \
+        if (e__ != hipSuccess) { (void)hipStreamSynchronize(c->stream); return hip_fail(e__, #expr, __LINE__); }          \
+    } while (0)
+    if (b[0].staged) HIP_DRAIN(hipMemcpyAsync(b[0].dev, b[0].host, b[0].bytes, hipMemcpyHostToDevice, c->stream));
+    if (stats) {
+        HIP_DRAIN(hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, c->stream));
+        HIP_DRAIN(hipEventRecord(c->ev0, c->stream));
+    }
+    st = enqueue_trace(s, nodes, n_nodes, b[0].dev, n, b[1].dev, b[2].dev, nullptr, nullptr, nullptr, 0, 0, nullptr, stats ? c->d_counters : nullptr, c->stream);
+    if (st != RT_OK) { (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return st; }
+    if (stats) HIP_DRAIN(hipEventRecord(c->ev1, c->stream));
+    for (const Buf &x : b)
+        if (x.staged && x.out)
+            HIP_DRAIN(hipMemcpyAsync(x.host, x.dev, x.bytes, hipMemcpyDeviceToHost, c->stream));
+    if (stats) return read_trace_stats(c, c->stream, stats);          // synchronises the stream
+    HIP_DRAIN(hipStreamSynchronize(c->stream));
+#undef HIP_DRAIN
+    return RT_OK;
+}
+
+// Shared body of both rt_render_camera entries: the frame into d_out (tile-major, 4 * total_px bytes) on `stream` through a leased
+// context.  spp == 0 is the reference's black frame, as launch_render makes it.  On RT_OK the context's ev1 follows the frame.
+static rt_status enqueue_camera(rt_scene *s, Context *c, const rt_options *o, const void *camera, const std::vector<rt::TileDev> &tab, uint32_t blocks,
+                                uint64_t total_px, uint8_t *d_out, hipStream_t stream, bool counting)
+{
+    const void *nodes = nullptr;
+    uint32_t n_nodes = 0;
+    rt_status st = query_stream(s, stream, &nodes, &n_nodes);
+    if (st != RT_OK) return st;
+    const rt::TileDev *d_tab = nullptr;
+    if ((st = upload_tiles(c, tab, stream, 0, &d_tab)) != RT_OK) return st;
+    if (counting) {
+        HIP_TRY(hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, stream));
+        HIP_TRY(hipEventRecord(c->ev0, stream));
+    }
+    if (o->samples_per_pixel == 0) HIP_TRY(hipMemsetAsync(d_out, 0, (size_t)total_px * 4, stream));
+    else if ((st = enqueue_trace(s, nodes, n_nodes, nullptr, 0, nullptr, nullptr, o, camera, d_tab, (uint32_t)tab.size(), blocks, d_out,
+                                 counting ? c->d_counters : nullptr, stream)) != RT_OK) return st;
+    HIP_TRY(hipEventRecord(c->ev1, stream));
+    return RT_OK;
+}
+
+static bool camera_args_ok(rt_scene *s, const rt_options *o, const void *camera, const rt_region *tiles, uint32_t n, const void *out, const char *what)
+{
+    if (!check_common(s, o, tiles, n, out)) return false;
+    if (!camera) { snprintf(g_err, sizeof g_err, "%s: NULL camera", what); return false; }
+    return camera_valid(s, camera, what);
+}
+
+rt_status rt_render_camera_device(rt_scene *s, const rt_options *o, const void *camera, const rt_region *tiles, uint32_t n, void *rgba_out_device,
+                                  void *hip_stream, rt_stats *stats)
+{
+    if (!camera_args_ok(s, o, camera, tiles, n, rgba_out_device, "rt_render_camera_device")) return RT_ERR_INVALID_ARGUMENT;
+    if ((reinterpret_cast<uintptr_t>(rgba_out_device) & 3u) != 0) {
+        snprintf(g_err, sizeof g_err, "the device output buffer must be 4-byte aligned");
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    std::vector<rt::TileDev> tab;
+    uint64_t total_px = 0; uint32_t total_blocks = 0;
+    rt_status st = build_tile_table(o, tiles, n, tab, &total_px, &total_blocks);
+    if (st != RT_OK) return st;
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    Context *c = nullptr;
+    if ((st = acquire(s, &c)) != RT_OK) return st;
+    Lease lease{ s, c };
+    st = enqueue_camera(s, c, o, camera, tab, total_blocks, total_px, static_cast<uint8_t *>(rgba_out_device), stream, stats != nullptr);
+    if (st != RT_OK) {
+        (void)hipEventRecord(c->ev1, stream);           // (the context goes back behind what is enqueued)
+        (void)hipGetLastError();
+        lease.inflight = true;
+        return st;
+    }
+    if (stats) return read_trace_stats(c, stream, stats);
+    lease.inflight = true;                              // the tile table is in use until ev1: asynchronous return
+    return RT_OK;
+}
+
+rt_status rt_render_camera(rt_scene *s, const rt_options *o, const void *camera, const rt_region *tiles, uint32_t n, uint8_t *rgba_out, rt_stats *stats)
+{
+    if (!camera_args_ok(s, o, camera, tiles, n, rgba_out, "rt_render_camera")) return RT_ERR_INVALID_ARGUMENT;
+    std::vector<rt::TileDev> tab;
+    uint64_t total_px = 0; uint32_t total_blocks = 0;
+    rt_status st = build_tile_table(o, tiles, n, tab, &total_px, &total_blocks);
+    if (st != RT_OK) return st;
+    HIP_TRY(hipSetDevice(s->device));
+    const HostDest dest = classify_host_pointer(rgba_out);
+    if (dest.bad) {
+        snprintf(g_err, sizeof g_err, "rt_render_camera: rgba_out is device memory; use rt_render_camera_device");
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    const size_t bytes = (size_t)total_px * 4;
+    Context *c = nullptr;
+    if ((st = acquire(s, &c)) != RT_OK) return st;
+    Lease lease{ s, c };
+    // pinned memory is written by the kernel in place; anything else gets the context's device output and one copy back
+    const bool direct = dest.pinned && dest.dev_alias && dest.room >= bytes;
+    if (!direct && c->out_cap < bytes) {
+        if (c->d_out) HIP_TRY(hipFree(c->d_out));
+        c->d_out = nullptr; c->out_cap = 0;
+        HIP_TRY(hipMalloc(&c->d_out, bytes));
+        c->out_cap = bytes;
+    }
+    st = enqueue_camera(s, c, o, camera, tab, total_blocks, total_px, direct ? dest.dev_alias : c->d_out, c->stream, stats != nullptr);
+    if (st != RT_OK) { (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return st; }
+    if (!direct) {
+        const hipError_t e = hipMemcpyAsync(rgba_out, c->d_out, bytes, hipMemcpyDeviceToHost, c->stream);
+        if (e != hipSuccess) { (void)hipStreamSynchronize(c->stream); return hip_fail(e, "hipMemcpyAsync", __LINE__); }
+    }
+    if (stats) return read_trace_stats(c, c->stream, stats);          // synchronises the stream
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return RT_OK;
+}
+
 rt_status rt_host_alloc(size_t bytes, void **out)
 {
     if (!out || bytes == 0) { snprintf(g_err, sizeof g_err, "rt_host_alloc: NULL argument or 0 bytes"); return RT_ERR_INVALID_ARGUMENT; }

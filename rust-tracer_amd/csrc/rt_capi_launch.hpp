@@ -687,3 +687,119 @@ rt_status read_query_stats(Context *c, hipStream_t stream, rt_stats *st)
     st->device_ms = ms;
     return RT_OK;
 }
+
+// ---- traced rays and camera frames (rt_trace_rays*, rt_render_camera*, rt_trace.hpp) ----
+
+// The camera domain both rt_render_camera entries check (in double, before the device is touched): 12 finite values, |eye coordinate|
+// <= 1e15 (rt_scene_create's eye), every axis of length within [1e-2, 1e2] and |det(right, up, forward)| >= 1e-2 |right| |up| |forward|.
+// Within it no sample direction is zero, underflows or overflows, so every normalised direction lies in the ray queries' domain.
+template <typename T>
+bool camera_valid(const T *cam, const char *what)
+{
+    double v[12];
+    for (int k = 0; k < 12; ++k) {
+        v[k] = (double)cam[k];
+        if (!std::isfinite(v[k])) { snprintf(g_err, sizeof g_err, "%s: camera value %d is not finite", what, k); return false; }
+    }
+    for (int k = 0; k < 3; ++k)
+        if (std::fabs(v[k]) > 1e15) { snprintf(g_err, sizeof g_err, "%s: |camera eye coordinate| > 1e15", what); return false; }
+    double len[3];
+    for (int a = 0; a < 3; ++a) {
+        const double *p = v + 3 + 3 * a;
+        len[a] = std::sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]);
+        if (!(len[a] >= 1e-2 && len[a] <= 1e2)) {
+            snprintf(g_err, sizeof g_err, "%s: camera axis %d has length %.6g, outside [1e-2, 1e2]", what, a, len[a]);
+            return false;
+        }
+    }
+    const double *r = v + 3, *u = v + 6, *f = v + 9;
+    const double det = r[0] * (u[1] * f[2] - u[2] * f[1]) - r[1] * (u[0] * f[2] - u[2] * f[0]) + r[2] * (u[0] * f[1] - u[1] * f[0]);
+    if (!(std::fabs(det) >= 1e-2 * len[0] * len[1] * len[2])) {
+        snprintf(g_err, sizeof g_err, "%s: the camera's right, up and forward axes are (nearly) coplanar", what);
+        return false;
+    }
+    return true;
+}
+
+bool camera_valid(const rt_scene *s, const void *cam, const char *what)
+{
+    return s->precision == RT_F32 ? camera_valid(static_cast<const float *>(cam), what) : camera_valid(static_cast<const double *>(cam), what);
+}
+
+// Pointers and sizes both rt_trace_rays entries check (device pointers are not dereferenced here).
+bool trace_args_ok(const rt_scene *s, const void *rays, uint32_t n, const void *color, const void *alpha, const char *what)
+{
+    if (!s || !rays || !color || n == 0) {
+        snprintf(g_err, sizeof g_err, "%s: NULL scene, rays or color_out, or n == 0", what);
+        return false;
+    }
+    const uintptr_t esz = s->precision == RT_F32 ? sizeof(float) : sizeof(double);
+    for (const void *p : { rays, color, alpha })
+        if ((reinterpret_cast<uintptr_t>(p) % esz) != 0) { snprintf(g_err, sizeof g_err, "%s: REAL buffers must be %u-byte aligned", what, (unsigned)esz); return false; }
+    return true;
+}
+
+// One rt_trace_rays launch (rays != NULL) or one camera frame over a device tile table on `stream`; counters != NULL runs the counting
+// flavour (same bytes).
+template <typename T>
+rt_status enqueue_trace(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *rays, uint32_t n, void *color, void *alpha,
+                        const rt_options *o, const void *cam, const rt::TileDev *d_tab, uint32_t n_tiles, uint32_t blocks, uint8_t *d_out,
+                        rt::Counters *counters, hipStream_t stream)
+{
+    rt::TraceArgs<T> a{};
+    a.stream = static_cast<const rt::Node<T> *>(nodes);
+    a.items = static_cast<const rt::Item<T> *>(s->d_items);
+    a.counters = counters;
+    a.rays = static_cast<const T *>(rays);
+    a.color = static_cast<T *>(color);
+    a.alpha = static_cast<T *>(alpha);
+    a.tiles = d_tab;
+    a.out = d_out;
+    if (cam) for (int k = 0; k < 12; ++k) a.cam[k] = static_cast<const T *>(cam)[k];
+    for (int k = 0; k < 3; ++k) a.light[k] = (T)s->light[k];
+    a.n_nodes = n_nodes;
+    if (rays) {
+        a.n = n;
+        const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
+        if (counters) hipLaunchKernelGGL((rt::k_trace_rays<T, true, rt::kTraceRays>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((rt::k_trace_rays<T, false, rt::kTraceRays>), grid, block, 0, stream, a);
+    } else {
+        a.n = n_tiles;
+        a.width = o->width; a.height = o->height; a.spp = o->samples_per_pixel;
+        const dim3 grid(blocks), block(rt::kBlockThreads);
+        if (counters) hipLaunchKernelGGL((rt::k_trace_rays<T, true, rt::kTraceCamera>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((rt::k_trace_rays<T, false, rt::kTraceCamera>), grid, block, 0, stream, a);
+    }
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+rt_status enqueue_trace(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *rays, uint32_t n, void *color, void *alpha,
+                        const rt_options *o, const void *cam, const rt::TileDev *d_tab, uint32_t n_tiles, uint32_t blocks, uint8_t *d_out,
+                        rt::Counters *counters, hipStream_t stream)
+{
+    return s->precision == RT_F32 ? enqueue_trace<float>(s, nodes, n_nodes, rays, n, color, alpha, o, cam, d_tab, n_tiles, blocks, d_out, counters, stream)
+                                  : enqueue_trace<double>(s, nodes, n_nodes, rays, n, color, alpha, o, cam, d_tab, n_tiles, blocks, d_out, counters, stream);
+}
+
+// A counting trace's rt_stats: primary = rays or samples, hits / shadow / occluded as the render counts them, the walks' tests and the
+// primary walks' share of them; the longest-wave fields 0.  Synchronises `stream`.
+rt_status read_trace_stats(Context *c, hipStream_t stream, rt_stats *st)
+{
+    std::vector<rt::Counters> stripes(rt::kCounterStripes);
+    HIP_TRY(hipMemcpyAsync(stripes.data(), c->d_counters, sizeof(rt::Counters) * rt::kCounterStripes, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    rt::Counters h{};
+    for (const rt::Counters &k : stripes) {
+        h.primary += k.primary; h.hits += k.hits; h.shadow += k.shadow; h.occluded += k.occluded;
+        h.sphere_tests += k.sphere_tests; h.bound_tests += k.bound_tests; h.primary_tests += k.primary_tests;
+    }
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    *st = rt_stats{};
+    st->primary = h.primary; st->hits = h.hits; st->shadow = h.shadow; st->occluded = h.occluded;
+    st->sphere_tests = h.sphere_tests; st->bound_tests = h.bound_tests; st->tests_executed = h.sphere_tests + h.bound_tests;
+    st->primary_tests = h.primary_tests;
+    st->device_ms = ms;
+    return RT_OK;
+}

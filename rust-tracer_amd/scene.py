@@ -66,6 +66,33 @@ def normalized(v, precision=capi.RT_F32):
     return np.array([x * rc, y * rc, z * rc], dtype=R)
 
 
+def look_at(eye, target, up=(0.0, 1.0, 0.0), hfov_deg=None, precision=capi.RT_F32):
+    """A camera for DeviceScene.render_camera -> REAL[12] = eye, right, up, forward, formed in double and rounded to REAL once:
+    forward = normalize(target - eye), right = normalize(cross(up, forward)), up' = cross(forward, right).  hfov_deg: the horizontal
+    field of view, by scaling forward to 0.5 / tan(hfov / 2); None keeps |forward| = 1, the reference's view (2 * atan(0.5), about 53.13
+    degrees).  look_at((0, 0, -4), (0, 0, 0)) is the identity camera of the default eye.  ValueError when eye == target or when up is
+    parallel to the view."""
+    e, t, u = (np.asarray(v, dtype=np.float64).reshape(3) for v in (eye, target, up))
+    f = t - e
+    fl = float(np.sqrt(f @ f))
+    if not fl > 0.0 or not np.isfinite(fl):
+        raise ValueError("look_at: eye and target must be distinct finite points")
+    f = f / fl
+    r = np.cross(u, f)
+    rl = float(np.sqrt(r @ r))
+    ul = float(np.sqrt(u @ u))
+    if not rl > 1e-9 * ul:
+        raise ValueError("look_at: up is parallel to the view direction (or zero)")
+    r = r / rl
+    u2 = np.cross(f, r)
+    if hfov_deg is not None:
+        if not 0.0 < hfov_deg < 180.0:
+            raise ValueError("look_at: hfov_deg must lie in (0, 180)")
+        f = f * (0.5 / np.tan(np.radians(hfov_deg) / 2.0))
+    # (+ 0.0: no axis component is a negative zero)
+    return np.concatenate([e, r + 0.0, u2 + 0.0, f + 0.0]).astype(_real(precision))
+
+
 def build_hierarchy(spheres, leaf_size=4, precision=capi.RT_F32, eye=None):
     """Bounding-sphere hierarchy for an arbitrary sphere list (scenes other than the pyramid, e.g. BASELINE
     config 5 with exactly 100,000 spheres).  Not in the reference -- its only scene builder is `pyramid` -- but the result
@@ -437,6 +464,94 @@ class DeviceScene:
         if want_stats:
             return dist, normal, item, st.as_dict()
         return dist, normal, item
+
+    def _camera(self, camera):
+        cam = np.asarray(camera)
+        R = _real(self.scene.precision)
+        if cam.dtype != R or cam.size != 12:
+            raise ValueError("camera must be 12 values of %s (eye, right, up, forward; see look_at)" % np.dtype(R).name)
+        return np.ascontiguousarray(cam.reshape(12))
+
+    def trace(self, rays, want_stats=False, stream=None, out=None):
+        """rt_trace_rays / rt_trace_rays_device: Renderer::raytrace (render.rs:171-215) for every ray of `rays` (n x 6: pos.xyz, dir.xyz, the
+        scene's REAL dtype) -> (color[n, 3], alpha[n][, stats dict]): primary hit, shading and shadow ray, as the render traces a sample.
+        numpy arrays go through the host entry (out: optional (color, alpha) arrays to fill, e.g. from capi.HostBuffer); a torch tensor on
+        this scene's device goes through the device entry on `stream`, with the stream discipline of intersect()."""
+        R = _real(self.scene.precision)
+        st = capi.Stats()
+        stp = C.byref(st) if want_stats else None
+        torch = sys.modules.get("torch")
+        if torch is not None and isinstance(rays, torch.Tensor):
+            tdt = torch.float32 if R == np.float32 else torch.float64
+            dev = torch.device("cuda", self.device)
+            if rays.dtype != tdt or rays.dim() != 2 or rays.shape[1] != 6 or rays.shape[0] == 0:
+                raise ValueError("rays must be a non-empty (n, 6) %s tensor" % tdt)
+            if rays.device != dev:
+                raise ValueError("rays must be on %s, not %s" % (dev, rays.device))
+            n = rays.shape[0]
+            cur = torch.cuda.current_stream(dev)
+            if stream is None:
+                qs = cur
+            elif isinstance(stream, torch.cuda.Stream):
+                qs = stream
+            else:
+                h = int(stream)
+                qs = torch.cuda.default_stream(dev) if h == 0 else torch.cuda.ExternalStream(h, device=dev)
+            if qs != cur:
+                qs.wait_stream(cur)
+            with torch.cuda.stream(qs):
+                r = rays.contiguous()
+                color = torch.empty((n, 3), dtype=tdt, device=dev)
+                alpha = torch.empty(n, dtype=tdt, device=dev)
+                rc = capi.lib.rt_trace_rays_device(self._h, C.c_void_p(r.data_ptr()), n, C.c_void_p(color.data_ptr()), C.c_void_p(alpha.data_ptr()),
+                                                   C.c_void_p(qs.cuda_stream), stp)
+            if qs != cur:
+                rays.record_stream(qs)
+            capi.check(rc, "rt_trace_rays_device")
+        else:
+            if not isinstance(rays, np.ndarray) or rays.dtype != R or rays.ndim != 2 or rays.shape[1] != 6 or rays.shape[0] == 0:
+                raise ValueError("rays must be a non-empty (n, 6) numpy array of %s (or a torch tensor on the scene's device)" % np.dtype(R).name)
+            n = rays.shape[0]
+            rays = np.ascontiguousarray(rays)
+            if out is None:
+                color, alpha = np.empty((n, 3), dtype=R), np.empty(n, dtype=R)
+            else:
+                color, alpha = out
+                for a, shape in ((color, (n, 3)), (alpha, (n,))):
+                    if a.dtype != R or a.shape != shape or not a.flags.c_contiguous:
+                        raise ValueError("out: contiguous %s arrays of shapes (n, 3) and (n,)" % np.dtype(R).name)
+            rc = capi.lib.rt_trace_rays(self._h, rays.ctypes.data, n, color.ctypes.data, alpha.ctypes.data, stp)
+            capi.check(rc, "rt_trace_rays")
+        if want_stats:
+            return color, alpha, st.as_dict()
+        return color, alpha
+
+    def render_camera(self, options, camera, regions, want_stats=True, out=None):
+        """rt_render_camera: render_tiles through a pinhole camera (REAL[12] = eye, right, up, forward; see look_at) -> (uint8[total_px*4]
+        tile-major, stats dict | None).  The identity camera of Scene::eye gives render_tiles' bytes."""
+        cam = self._camera(camera)
+        arr = regions if isinstance(regions, C.Array) else self._regions(regions)
+        nbytes = capi.lib.rt_tiles_rgba_bytes(arr, len(arr))
+        if out is None:
+            out = np.empty(max(int(nbytes), 1), dtype=np.uint8)
+        elif out.dtype != np.uint8 or not out.flags.c_contiguous or out.size < nbytes:
+            raise ValueError("out must be a contiguous uint8 array of at least %d bytes" % nbytes)
+        st = capi.Stats()
+        o = capi.Options(*options)
+        rc = capi.lib.rt_render_camera(self._h, C.byref(o), cam.ctypes.data, arr, len(arr), out.ctypes.data, C.byref(st) if want_stats else None)
+        capi.check(rc, "rt_render_camera")
+        return out.reshape(-1)[:int(nbytes)], (st.as_dict() if want_stats else None)
+
+    def render_camera_device(self, options, camera, regions, out_ptr, stream=0, want_stats=False):
+        """rt_render_camera_device: render_tiles_device through a pinhole camera (host REAL[12]), enqueued on `stream` (hipStream_t as int)."""
+        cam = self._camera(camera)
+        arr = regions if isinstance(regions, C.Array) else self._regions(regions)
+        st = capi.Stats()
+        o = capi.Options(*options)
+        rc = capi.lib.rt_render_camera_device(self._h, C.byref(o), cam.ctypes.data, arr, len(arr), C.c_void_p(out_ptr), C.c_void_p(stream),
+                                              C.byref(st) if want_stats else None)
+        capi.check(rc, "rt_render_camera_device")
+        return st.as_dict() if want_stats else None
 
     def blit_tiles_device(self, options, regions, src_ptr, frame_ptr, stream=0, src_px_offset=None):
         """rt_blit_tiles_device: tile-major device tiles -> row-major device frame (set_pixels_from_buffer)."""
