@@ -281,6 +281,30 @@ rt_status rt_intersect_rays(rt_scene *scene, rt_query mode, const void *rays, co
 rt_status rt_intersect_rays_device(rt_scene *scene, rt_query mode, const void *rays, const void *tmax, uint32_t n,
                                    void *distance_out, void *normal_out, int32_t *item_out, void *hip_stream, rt_stats *stats);
 
+/* ---- multi-hit ray queries (additive to ABI 5): the k closest hits along each ray, or every hit below tmax ----
+ * Rays, tmax and the walk as rt_intersect_rays.  Each ray keeps a list of k slots (distance, item), sorted by distance, every slot
+ * starting as (tmax[i], -1).  A bound culls its subtree when its distance is >= the cutoff: the last slot's distance (CLOSEST) or
+ * tmax[i] (ALL).  An item whose distance is below the last slot's is inserted behind every slot whose distance is <= its own (equal
+ * distances stay in DFS order) and the last slot drops out.
+ *   RT_MULTIHIT_CLOSEST  the k closest items below tmax; hits_out[i] = the filled slots (<= k).  With k = 1 this is RT_QUERY_NEAREST,
+ *                        test for test: the same bytes and counters.
+ *   RT_MULTIHIT_ALL      no culling below tmax: the k closest of all items below tmax[i], and hits_out[i] = how many there are (may be > k).
+ * Slot j of ray i is at index i*k + j: distance_out (REAL[n*k]), normal_out (REAL[3*n*k], the normal primitive.rs:82 forms for the slot's
+ * item and distance), item_out (int32[n*k], DFS index).  An empty slot reads tmax[i], -1 and {0, 0, 0}.  normal_out, item_out and hits_out
+ * (uint32[n]) may be NULL.  stats (may be NULL): primary = n, hits = rays with hits_out > 0, sphere_tests / bound_tests / tests_executed,
+ * every other counter 0; asking for it runs the counting flavour (same bytes). */
+typedef enum rt_multihit { RT_MULTIHIT_CLOSEST = 0, RT_MULTIHIT_ALL = 1 } rt_multihit;
+#define RT_MULTIHIT_MAX_K 16
+/* Host memory, validated as rt_intersect_rays validates it; also RT_ERR_INVALID_ARGUMENT, before the device is touched, for k == 0,
+ * k > RT_MULTIHIT_MAX_K, an unknown mode and a misaligned hits_out.  Pinned memory is used in place, pageable memory goes through the
+ * call's device workspace. */
+rt_status rt_intersect_rays_multi(rt_scene *scene, rt_multihit mode, uint32_t k, const void *rays, const void *tmax, uint32_t n,
+                                  void *distance_out, void *normal_out, int32_t *item_out, uint32_t *hits_out, rt_stats *stats);
+/* The same over DEVICE memory, enqueued on `hip_stream` as rt_intersect_rays_device is: only pointers, alignment, n, k and mode are checked. */
+rt_status rt_intersect_rays_multi_device(rt_scene *scene, rt_multihit mode, uint32_t k, const void *rays, const void *tmax, uint32_t n,
+                                         void *distance_out, void *normal_out, int32_t *item_out, uint32_t *hits_out, void *hip_stream,
+                                         rt_stats *stats);
+
 /* ---- traced rays and camera frames (additive to ABI 5): Renderer::raytrace (render.rs:171-215) for ANY rays, render_region (render.rs:218-255)
  * for ANY pinhole camera ----
  * A ray is traced as the render traces a sample: the nearest hit from pos (the hierarchy walk of rt_intersect_rays; a scene created without

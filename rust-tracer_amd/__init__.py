@@ -4,11 +4,13 @@ Layout: csrc/ (hand-written HIP kernels + C ABI -> librtrace_hip.so), capi.py (c
 include/rtrace_hip.h), scene.py / render.py (host-side mirror of the reference's Scene / Renderer surface),
 dist.py (tile sharding across GPUs + RCCL gather).  Importing this package requires the built library."""
 from . import capi
-from .capi import RT_F32, RT_F64, RT_TRAVERSAL_FLAT, RT_TRAVERSAL_SKIP, RT_QUERY_NEAREST, RT_QUERY_ANY, RtError, device_count
+from .capi import (RT_F32, RT_F64, RT_TRAVERSAL_FLAT, RT_TRAVERSAL_SKIP, RT_QUERY_NEAREST, RT_QUERY_ANY, RT_MULTIHIT_CLOSEST, RT_MULTIHIT_ALL,
+                   RT_MULTIHIT_MAX_K, RtError, device_count)
 from .scene import Scene, DeviceScene, Gang, pyramid, normalized, build_hierarchy, look_at
 from .render import (RenderOptions, ImageRegion, RGBABuffer, RGBABufferWriter, PPMStdoutRGBABufferWriter,
                      Renderer, buckets, CHUNK_SIZE)
 
-__all__ = ["capi", "RT_F32", "RT_F64", "RT_TRAVERSAL_FLAT", "RT_TRAVERSAL_SKIP", "RT_QUERY_NEAREST", "RT_QUERY_ANY", "RtError", "device_count",
+__all__ = ["capi", "RT_F32", "RT_F64", "RT_TRAVERSAL_FLAT", "RT_TRAVERSAL_SKIP", "RT_QUERY_NEAREST", "RT_QUERY_ANY", "RT_MULTIHIT_CLOSEST", "RT_MULTIHIT_ALL",
+           "RT_MULTIHIT_MAX_K", "RtError", "device_count",
            "Scene", "DeviceScene", "Gang", "pyramid", "normalized", "build_hierarchy", "look_at", "RenderOptions", "ImageRegion", "RGBABuffer",
            "RGBABufferWriter", "PPMStdoutRGBABufferWriter", "Renderer", "buckets", "CHUNK_SIZE"]

@@ -20,6 +20,8 @@ RT_F32, RT_F64 = 0, 1
 RT_TRAVERSAL_FLAT, RT_TRAVERSAL_SKIP = 0, 1
 ABI_VERSION = 5
 RT_QUERY_NEAREST, RT_QUERY_ANY = 0, 1
+RT_MULTIHIT_CLOSEST, RT_MULTIHIT_ALL = 0, 1
+RT_MULTIHIT_MAX_K = 16
 
 # every symbol include/rtrace_hip.h declares
 SYMBOLS = ("rt_abi_version", "rt_build_hierarchy", "rt_device_count", "rt_scene_create", "rt_scene_destroy", "rt_scene_traits", "rt_scene_setup_cost", "rt_render_tiles",
@@ -27,7 +29,8 @@ SYMBOLS = ("rt_abi_version", "rt_build_hierarchy", "rt_device_count", "rt_scene_
            "rt_host_alloc", "rt_host_free", "rt_host_register", "rt_host_unregister",
            "rt_gang_create", "rt_gang_destroy", "rt_gang_size", "rt_gang_render_frame", "rt_gang_render_frames", "rt_render_tiles_stream",
            "rt_last_launch_flags", "rt_build_info", "rt_render_frame_stream", "rt_intersect_rays", "rt_intersect_rays_device",
-           "rt_trace_rays", "rt_trace_rays_device", "rt_render_camera", "rt_render_camera_device")
+           "rt_trace_rays", "rt_trace_rays_device", "rt_render_camera", "rt_render_camera_device",
+           "rt_intersect_rays_multi", "rt_intersect_rays_multi_device")
 # csrc/rt_debug.h: only in the -DRT_TEST_HOOKS build
 DEBUG_SYMBOLS = ("rt_debug_set", "rt_debug_count", "rt_debug_wave_trace", "rt_debug_flat_filter_check", "rt_debug_gang_layout", "rt_debug_rccl_library",
                  "rt_debug_shard_costs")
@@ -96,6 +99,10 @@ lib.rt_render_frame_stream.argtypes = [C.c_void_p, C.POINTER(Options), C.c_int, 
 lib.rt_intersect_rays.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
 lib.rt_intersect_rays_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.POINTER(Stats)]
+lib.rt_intersect_rays_multi.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.POINTER(Stats)]
+lib.rt_intersect_rays_multi_device.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
 lib.rt_trace_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
 lib.rt_trace_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
 lib.rt_render_camera.argtypes = [C.c_void_p, C.POINTER(Options), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(Stats)]
@@ -190,7 +197,7 @@ def selftest_rcp(device=0):
 (DEBUG_SKIP_VARIANT, DEBUG_BLOCK_ORDER, DEBUG_NARROW_MAX, DEBUG_PACKED_SAMPLES, DEBUG_PRINT_STEPS, DEBUG_PRINT_COSTS,
  DEBUG_HOST_COPY, DEBUG_COALESCE, DEBUG_LDS_BYTES, DEBUG_WG_POLICY, DEBUG_NARROW_L2, DEBUG_FLAT_KERNELS, DEBUG_SKIP_RAYS,
  DEBUG_FRAME_AHEAD, DEBUG_FILTER_RO_PERCENT, DEBUG_COOP, DEBUG_COOP_THR, DEBUG_COOP_MAX, DEBUG_COOP_LEVEL, DEBUG_COOP_REST, DEBUG_ASYNC_ORDERS,
- DEBUG_FAST_KERNEL, DEBUG_EXACT_COSTS) = range(23)
+ DEBUG_FAST_KERNEL, DEBUG_EXACT_COSTS, DEBUG_MULTIHIT_BUCKET) = range(24)
 if HAVE_TEST_HOOKS:
     lib.rt_debug_set.argtypes = [C.c_int, C.c_longlong]
     lib.rt_debug_wave_trace.argtypes = [C.c_char_p]

@@ -806,6 +806,103 @@ rt_status rt_intersect_rays(rt_scene *s, rt_query mode, const void *rays, const 
     return RT_OK;
 }
 
+// ---- multi-hit ray queries: the k closest hits, or every hit below tmax, for a batch of arbitrary rays (rt_multihit.hpp) ----
+
+rt_status rt_intersect_rays_multi_device(rt_scene *s, rt_multihit mode, uint32_t k, const void *rays, const void *tmax, uint32_t n, void *distance_out,
+                                         void *normal_out, int32_t *item_out, uint32_t *hits_out, void *hip_stream, rt_stats *stats)
+{
+    if (!query_args_ok(s, RT_QUERY_NEAREST, rays, tmax, n, distance_out, normal_out, item_out, "rt_intersect_rays_multi_device") ||
+        !multihit_args_ok(mode, k, hits_out, "rt_intersect_rays_multi_device"))
+        return RT_ERR_INVALID_ARGUMENT;
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    const void *nodes = nullptr;
+    uint32_t n_nodes = 0;
+    rt_status st = query_stream(s, stream, &nodes, &n_nodes);
+    if (st != RT_OK) return st;
+    if (!stats) return enqueue_multihit(s, nodes, n_nodes, mode, k, rays, tmax, n, distance_out, normal_out, item_out, hits_out, nullptr, stream);
+    Context *c = nullptr;
+    if ((st = acquire(s, &c)) != RT_OK) return st;
+    Lease lease{ s, c };
+    HIP_TRY(hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, stream));
+    HIP_TRY(hipEventRecord(c->ev0, stream));
+    st = enqueue_multihit(s, nodes, n_nodes, mode, k, rays, tmax, n, distance_out, normal_out, item_out, hits_out, c->d_counters, stream);
+    (void)hipEventRecord(c->ev1, stream);
+    if (st != RT_OK) { (void)hipGetLastError(); lease.inflight = true; return st; }      // (the context goes back behind what is enqueued)
+    return read_query_stats(c, stream, stats);
+}
+
+rt_status rt_intersect_rays_multi(rt_scene *s, rt_multihit mode, uint32_t k, const void *rays, const void *tmax, uint32_t n, void *distance_out,
+                                  void *normal_out, int32_t *item_out, uint32_t *hits_out, rt_stats *stats)
+{
+    if (!query_args_ok(s, RT_QUERY_NEAREST, rays, tmax, n, distance_out, normal_out, item_out, "rt_intersect_rays_multi") ||
+        !multihit_args_ok(mode, k, hits_out, "rt_intersect_rays_multi"))
+        return RT_ERR_INVALID_ARGUMENT;
+    const bool f32 = s->precision == RT_F32;
+    if (!(f32 ? query_rays_valid(static_cast<const float *>(rays), static_cast<const float *>(tmax), n)
+              : query_rays_valid(static_cast<const double *>(rays), static_cast<const double *>(tmax), n)))
+        return RT_ERR_INVALID_ARGUMENT;
+    HIP_TRY(hipSetDevice(s->device));
+    rt_status st = RT_OK;
+    // pinned buffers are read and written by the kernel in place, pageable ones go through the call's workspace (as rt_intersect_rays)
+    const size_t esz = f32 ? sizeof(float) : sizeof(double), nk = (size_t)n * k;
+    struct Buf { void *host; size_t bytes; bool out; uint8_t *dev; size_t off; bool staged; };
+    Buf b[6] = { { const_cast<void *>(rays), 6 * esz * n, false, nullptr, 0, false }, { const_cast<void *>(tmax), esz * n, false, nullptr, 0, false },
+                 { distance_out, esz * nk, true, nullptr, 0, false }, { normal_out, 3 * esz * nk, true, nullptr, 0, false },
+                 { item_out, sizeof(int32_t) * nk, true, nullptr, 0, false }, { hits_out, sizeof(uint32_t) * n, true, nullptr, 0, false } };
+    size_t need = 0;
+    for (Buf &x : b) {
+        if (!x.host) continue;
+        const HostDest d = classify_host_pointer(x.host);
+        if (d.bad) {
+            snprintf(g_err, sizeof g_err, "rt_intersect_rays_multi: a buffer is device memory; use rt_intersect_rays_multi_device");
+            return RT_ERR_INVALID_ARGUMENT;
+        }
+        if (d.pinned && d.dev_alias && d.room >= x.bytes) { x.dev = d.dev_alias; continue; }
+        x.staged = true;
+        x.off = need;
+        need += (x.bytes + 255) & ~(size_t)255;
+    }
+    Context *c = nullptr;
+    if ((st = acquire(s, &c)) != RT_OK) return st;
+    Lease lease{ s, c };
+    const void *nodes = nullptr;
+    uint32_t n_nodes = 0;
+    if ((st = query_stream(s, c->stream, &nodes, &n_nodes)) != RT_OK) return st;
+    if (need > c->query_cap) {
+        if (c->d_query) HIP_TRY(hipFree(c->d_query));
+        c->d_query = nullptr; c->query_cap = 0;
+        HIP_TRY(hipMalloc(&c->d_query, need));
+        c->query_cap = need;
+    }
+    for (Buf &x : b)
+        if (x.staged) x.dev = static_cast<uint8_t *>(c->d_query) + x.off;
+    // from the first copy on, work of this call may be queued: an error return first waits for it
+#define HIP_DRAIN(expr)                                                                                                   \
+    do {                                                                                                                  \
+        hipError_t e__ = (expr);                                                                                          \
+        if (e__ != hipSuccess) { (void)hipStreamSynchronize(c->stream); return hip_fail(e__, #expr, __LINE__); }          \
+    } while (0)
+    for (const Buf &x : b)
+        if (x.staged && !x.out)
+            HIP_DRAIN(hipMemcpyAsync(x.dev, x.host, x.bytes, hipMemcpyHostToDevice, c->stream));
+    if (stats) {
+        HIP_DRAIN(hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, c->stream));
+        HIP_DRAIN(hipEventRecord(c->ev0, c->stream));
+    }
+    st = enqueue_multihit(s, nodes, n_nodes, mode, k, b[0].dev, b[1].dev, n, b[2].dev, b[3].dev, reinterpret_cast<int32_t *>(b[4].dev),
+                          reinterpret_cast<uint32_t *>(b[5].dev), stats ? c->d_counters : nullptr, c->stream);
+    if (st != RT_OK) { (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return st; }
+    if (stats) HIP_DRAIN(hipEventRecord(c->ev1, c->stream));
+    for (const Buf &x : b)
+        if (x.staged && x.out)
+            HIP_DRAIN(hipMemcpyAsync(x.host, x.dev, x.bytes, hipMemcpyDeviceToHost, c->stream));
+    if (stats) return read_query_stats(c, c->stream, stats);          // synchronises the stream
+    HIP_DRAIN(hipStreamSynchronize(c->stream));
+#undef HIP_DRAIN
+    return RT_OK;
+}
+
 // ---- traced rays and camera frames: Renderer::raytrace for any ray, render_region for any pinhole camera (rt_trace.hpp) ----
 
 rt_status rt_trace_rays_device(rt_scene *s, const void *rays, uint32_t n, void *color_out, void *alpha_out, void *hip_stream, rt_stats *stats)

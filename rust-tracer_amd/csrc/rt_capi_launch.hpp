@@ -688,6 +688,64 @@ rt_status read_query_stats(Context *c, hipStream_t stream, rt_stats *st)
     return RT_OK;
 }
 
+// ---- multi-hit ray queries (rt_intersect_rays_multi*, rt_multihit.hpp) ----
+
+// What both multi-hit entries check besides query_args_ok: k, the mode and hits_out's alignment.
+bool multihit_args_ok(rt_multihit mode, uint32_t k, const uint32_t *hits, const char *what)
+{
+    if (k == 0 || k > RT_MULTIHIT_MAX_K || (mode != RT_MULTIHIT_CLOSEST && mode != RT_MULTIHIT_ALL)) {
+        snprintf(g_err, sizeof g_err, "%s: k must be 1 .. %d and the mode closest (0) or all (1)", what, RT_MULTIHIT_MAX_K);
+        return false;
+    }
+    if ((reinterpret_cast<uintptr_t>(hits) & 3u) != 0) { snprintf(g_err, sizeof g_err, "%s: hits_out must be 4-byte aligned", what); return false; }
+    return true;
+}
+
+template <typename T, bool COUNT, bool ALL>
+void launch_multihit(unsigned bucket, dim3 grid, dim3 block, hipStream_t stream, const rt::MultiArgs<T> &a)
+{
+    switch (bucket) {
+    case 1: hipLaunchKernelGGL((rt::k_multihit_rays<T, COUNT, ALL, 1>), grid, block, 0, stream, a); break;
+    case 4: hipLaunchKernelGGL((rt::k_multihit_rays<T, COUNT, ALL, 4>), grid, block, 0, stream, a); break;
+    case 8: hipLaunchKernelGGL((rt::k_multihit_rays<T, COUNT, ALL, 8>), grid, block, 0, stream, a); break;
+    default: hipLaunchKernelGGL((rt::k_multihit_rays<T, COUNT, ALL, 16>), grid, block, 0, stream, a); break;
+    }
+}
+
+// One multi-hit launch on `stream`: the list capacity is the smallest bucket >= k (RT_DEBUG_MULTIHIT_BUCKET: a larger one); counters
+// != NULL runs the counting flavour (same bytes).
+template <typename T>
+rt_status enqueue_multihit(const rt_scene *s, const void *nodes, uint32_t n_nodes, rt_multihit mode, uint32_t k, const void *rays, const void *tmax,
+                           uint32_t n, void *dist, void *normal, int32_t *item, uint32_t *hits, rt::Counters *counters, hipStream_t stream)
+{
+    const rt::MultiArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), static_cast<const rt::Item<T> *>(s->d_items), static_cast<const T *>(rays),
+                              static_cast<const T *>(tmax), static_cast<T *>(dist), static_cast<T *>(normal), item, hits, counters, n_nodes, n, k };
+    unsigned bucket = 0;
+    for (unsigned b : rt::kMultiBuckets)
+        if (bucket == 0 && b >= k) bucket = b;
+    const long long forced = knob(RT_DEBUG_MULTIHIT_BUCKET);
+    for (unsigned b : rt::kMultiBuckets)
+        if (forced == (long long)b && b >= k) bucket = b;
+    const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
+    const bool all = mode == RT_MULTIHIT_ALL;
+    if (counters) {
+        if (all) launch_multihit<T, true, true>(bucket, grid, block, stream, a);
+        else launch_multihit<T, true, false>(bucket, grid, block, stream, a);
+    } else {
+        if (all) launch_multihit<T, false, true>(bucket, grid, block, stream, a);
+        else launch_multihit<T, false, false>(bucket, grid, block, stream, a);
+    }
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+rt_status enqueue_multihit(const rt_scene *s, const void *nodes, uint32_t n_nodes, rt_multihit mode, uint32_t k, const void *rays, const void *tmax,
+                           uint32_t n, void *dist, void *normal, int32_t *item, uint32_t *hits, rt::Counters *counters, hipStream_t stream)
+{
+    return s->precision == RT_F32 ? enqueue_multihit<float>(s, nodes, n_nodes, mode, k, rays, tmax, n, dist, normal, item, hits, counters, stream)
+                                  : enqueue_multihit<double>(s, nodes, n_nodes, mode, k, rays, tmax, n, dist, normal, item, hits, counters, stream);
+}
+
 // ---- traced rays and camera frames (rt_trace_rays*, rt_render_camera*, rt_trace.hpp) ----
 
 // The camera domain both rt_render_camera entries check (in double, before the device is touched): 12 finite values, |eye coordinate|

@@ -394,13 +394,33 @@ class DeviceScene:
         capi.HostBuffer, which the kernel then writes directly); a torch tensor on this scene's device goes through the device entry on
         `stream` (a torch stream or a hipStream_t as int; default the current torch stream) and gets torch tensors on that device: the
         query waits for the work queued on the current torch stream, and its results belong to `stream` (use them there, or synchronise)."""
-        R = _real(self.scene.precision)
         mode = capi.RT_QUERY_ANY if any_hit else capi.RT_QUERY_NEAREST
+        return self._ray_query("rt_intersect_rays", lambda f, r, t, n, *rest: f(self._h, mode, r, t, n, *rest),
+                               (((), "R"), ((3,), "R"), ((), np.int32)), rays, tmax, want_stats, stream, out)
+
+    def intersect_multi(self, rays, k, tmax=None, all_hits=False, want_stats=False, stream=None, out=None):
+        """rt_intersect_rays_multi / rt_intersect_rays_multi_device: the k closest hits of every ray, nearest first, equal distances in DFS
+        order -> (distance[n, k], normal[n, k, 3], item[n, k] (DFS index or -1), hits[n] (uint32)[, stats dict]).  An empty slot reads tmax,
+        -1 and (0, 0, 0).  all_hits=False (RT_MULTIHIT_CLOSEST): hits = the filled slots; with k = 1 this is intersect() exactly.
+        all_hits=True (RT_MULTIHIT_ALL): no culling below tmax, hits = every item below tmax (may exceed k), the list its k closest.
+        1 <= k <= RT_MULTIHIT_MAX_K.  rays, tmax, stream and out (here (distance, normal, item, hits)) as for intersect()."""
+        k = int(k)
+        if not 1 <= k <= capi.RT_MULTIHIT_MAX_K:
+            raise ValueError("k must be 1 .. %d, not %d" % (capi.RT_MULTIHIT_MAX_K, k))
+        mode = capi.RT_MULTIHIT_ALL if all_hits else capi.RT_MULTIHIT_CLOSEST
+        return self._ray_query("rt_intersect_rays_multi", lambda f, r, t, n, *rest: f(self._h, mode, k, r, t, n, *rest),
+                               (((k,), "R"), ((k, 3), "R"), ((k,), np.int32), ((), np.uint32)), rays, tmax, want_stats, stream, out)
+
+    def _ray_query(self, entry, call, results, rays, tmax, want_stats, stream, out):
+        """The body every ray query shares: checks rays and tmax, makes the results -- (shape behind n, dtype) each, "R" for the scene's
+        REAL -- and calls `entry` (numpy) or `entry`_device (torch) as call(f, rays, tmax, n, *result pointers[, stream], stats)."""
+        R = _real(self.scene.precision)
         st = capi.Stats()
         stp = C.byref(st) if want_stats else None
         torch = sys.modules.get("torch")
         if torch is not None and isinstance(rays, torch.Tensor):
             tdt = torch.float32 if R == np.float32 else torch.float64
+            tdts = {"R": tdt, np.int32: torch.int32, np.uint32: torch.uint32}
             dev = torch.device("cuda", self.device)
             if rays.dtype != tdt or rays.dim() != 2 or rays.shape[1] != 6 or rays.shape[0] == 0:
                 raise ValueError("rays must be a non-empty (n, 6) %s tensor" % tdt)
@@ -434,36 +454,32 @@ class DeviceScene:
                     t = tmax.to(dev).reshape(-1).expand(n).contiguous()
                 elif tmax is not None:
                     t = torch.from_numpy(tmax).to(dev)
-                dist = torch.empty(n, dtype=tdt, device=dev)
-                normal = torch.empty((n, 3), dtype=tdt, device=dev)
-                item = torch.empty(n, dtype=torch.int32, device=dev)
-                rc = capi.lib.rt_intersect_rays_device(self._h, mode, C.c_void_p(r.data_ptr()), C.c_void_p(t.data_ptr()) if t is not None else None, n,
-                                                       C.c_void_p(dist.data_ptr()), C.c_void_p(normal.data_ptr()), C.c_void_p(item.data_ptr()),
-                                                       C.c_void_p(qs.cuda_stream), stp)
+                res = tuple(torch.empty((n,) + shape, dtype=tdts[dt], device=dev) for shape, dt in results)
+                rc = call(getattr(capi.lib, entry + "_device"), C.c_void_p(r.data_ptr()), C.c_void_p(t.data_ptr()) if t is not None else None, n,
+                          *[C.c_void_p(x.data_ptr()) for x in res], C.c_void_p(qs.cuda_stream), stp)
             if qs != cur:
                 for x in (rays, tmax):
                     if isinstance(x, torch.Tensor) and x.is_cuda:
                         x.record_stream(qs)
-            capi.check(rc, "rt_intersect_rays_device")
+            capi.check(rc, entry + "_device")
         else:
             if not isinstance(rays, np.ndarray) or rays.dtype != R or rays.ndim != 2 or rays.shape[1] != 6 or rays.shape[0] == 0:
                 raise ValueError("rays must be a non-empty (n, 6) numpy array of %s (or a torch tensor on the scene's device)" % np.dtype(R).name)
             n = rays.shape[0]
             rays = np.ascontiguousarray(rays)
             t = None if tmax is None else _tmax_array(tmax, R, n)
+            specs = [((n,) + shape, R if dt == "R" else dt) for shape, dt in results]
             if out is None:
-                dist, normal, item = np.empty(n, dtype=R), np.empty((n, 3), dtype=R), np.empty(n, dtype=np.int32)
+                res = tuple(np.empty(shape, dtype=dt) for shape, dt in specs)
             else:
-                dist, normal, item = out
-                for a, dt, shape in ((dist, R, (n,)), (normal, R, (n, 3)), (item, np.int32, (n,))):
-                    if a.dtype != dt or a.shape != shape or not a.flags.c_contiguous:
-                        raise ValueError("out: contiguous arrays of %s, %s and int32 of shapes (n,), (n, 3), (n,)" % ((np.dtype(R).name,) * 2))
-            rc = capi.lib.rt_intersect_rays(self._h, mode, rays.ctypes.data, t.ctypes.data if t is not None else None, n,
-                                            dist.ctypes.data, normal.ctypes.data, item.ctypes.data, stp)
-            capi.check(rc, "rt_intersect_rays")
+                res = tuple(out)
+                if len(res) != len(specs) or any(a.dtype != dt or a.shape != shape or not a.flags.c_contiguous for a, (shape, dt) in zip(res, specs)):
+                    raise ValueError("out: contiguous arrays of " + ", ".join("%s %s" % (np.dtype(dt).name, shape) for shape, dt in specs))
+            rc = call(getattr(capi.lib, entry), rays.ctypes.data, t.ctypes.data if t is not None else None, n, *[a.ctypes.data for a in res], stp)
+            capi.check(rc, entry)
         if want_stats:
-            return dist, normal, item, st.as_dict()
-        return dist, normal, item
+            return res + (st.as_dict(),)
+        return res
 
     def _camera(self, camera):
         cam = np.asarray(camera)
