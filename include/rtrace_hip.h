@@ -332,6 +332,28 @@ rt_status rt_render_camera(rt_scene *scene, const rt_options *options, const voi
 rt_status rt_render_camera_device(rt_scene *scene, const rt_options *options, const void *camera,
                                   const rt_region *tiles, uint32_t n_tiles, void *rgba_out_device, void *hip_stream, rt_stats *stats);
 
+/* ---- undersampled camera frames that refine in place (additive to ABI 5) ----
+ * F(x, y) is the pixel rt_render_camera writes for (x, y).  The LATTICE of a step s is every pixel with x % s == 0 and y % s == 0, anchored
+ * at the image origin (not at a tile's corner); the anchor of (x, y) is (x - x % s, y - y % s).  The step-s frame holds F(anchor(x, y)) in
+ * every pixel of every listed tile -- the same bytes whatever tile list it is rendered through; step 1 is rt_render_camera's frame.
+ *   prev_step == 0         a fresh frame: every cell that meets a tile is traced from its anchor (inside the tile or not) and written.
+ *   prev_step == 2 * step  the buffer holds the step-2s frame of the same scene, options, camera and tile list.  A cell whose anchor also
+ *                          lies on the 2s lattice is correct already: it is neither traced nor written.  Every other cell that meets a
+ *                          tile is traced and filled; afterwards the buffer holds the step-s frame.  The chain s0, s0/2, ..., 1 traces
+ *                          each sample of the full frame exactly once when the tiles' l and b are multiples of s0.
+ * step is any integer in [1, RT_UNDERSAMPLE_MAX_STEP]; any other step or prev_step is RT_ERR_INVALID_ARGUMENT before the device is touched.
+ * Everything else -- options, camera, regions, the tile-major layout, status codes, stream and stats -- as rt_render_camera /
+ * rt_render_camera_device; stats->primary counts the samples actually traced (traced cells x samples_per_pixel^2).  With prev_step != 0
+ * the buffer is read-modify-write for the caller: pinned and device memory are refined in place, pageable memory goes up into the call's
+ * device output first and comes back whole.  samples_per_pixel == 0 writes {0, 0, 0, 0} into the traced cells. */
+#define RT_UNDERSAMPLE_MAX_STEP 64      /* the scheduler's bucket edge */
+rt_status rt_render_camera_undersampled(rt_scene *scene, const rt_options *options, const void *camera,
+                                        const rt_region *tiles, uint32_t n_tiles, uint32_t step, uint32_t prev_step,
+                                        uint8_t *rgba_inout, rt_stats *stats);
+rt_status rt_render_camera_undersampled_device(rt_scene *scene, const rt_options *options, const void *camera,
+                                               const rt_region *tiles, uint32_t n_tiles, uint32_t step, uint32_t prev_step,
+                                               void *rgba_inout_device, void *hip_stream, rt_stats *stats);
+
 /* Bytes rt_render_tiles writes for this tile list (4 * total area), or 0 on an invalid list. */
 uint64_t rt_tiles_rgba_bytes(const rt_region *tiles, uint32_t n_tiles);
 

@@ -22,6 +22,7 @@ ABI_VERSION = 5
 RT_QUERY_NEAREST, RT_QUERY_ANY = 0, 1
 RT_MULTIHIT_CLOSEST, RT_MULTIHIT_ALL = 0, 1
 RT_MULTIHIT_MAX_K = 16
+RT_UNDERSAMPLE_MAX_STEP = 64
 
 # every symbol include/rtrace_hip.h declares
 SYMBOLS = ("rt_abi_version", "rt_build_hierarchy", "rt_device_count", "rt_scene_create", "rt_scene_destroy", "rt_scene_traits", "rt_scene_setup_cost", "rt_render_tiles",
@@ -30,7 +31,8 @@ SYMBOLS = ("rt_abi_version", "rt_build_hierarchy", "rt_device_count", "rt_scene_
            "rt_gang_create", "rt_gang_destroy", "rt_gang_size", "rt_gang_render_frame", "rt_gang_render_frames", "rt_render_tiles_stream",
            "rt_last_launch_flags", "rt_build_info", "rt_render_frame_stream", "rt_intersect_rays", "rt_intersect_rays_device",
            "rt_trace_rays", "rt_trace_rays_device", "rt_render_camera", "rt_render_camera_device",
-           "rt_intersect_rays_multi", "rt_intersect_rays_multi_device")
+           "rt_intersect_rays_multi", "rt_intersect_rays_multi_device",
+           "rt_render_camera_undersampled", "rt_render_camera_undersampled_device")
 # csrc/rt_debug.h: only in the -DRT_TEST_HOOKS build
 DEBUG_SYMBOLS = ("rt_debug_set", "rt_debug_count", "rt_debug_wave_trace", "rt_debug_flat_filter_check", "rt_debug_gang_layout", "rt_debug_rccl_library",
                  "rt_debug_shard_costs")
@@ -108,6 +110,10 @@ lib.rt_trace_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_voi
 lib.rt_render_camera.argtypes = [C.c_void_p, C.POINTER(Options), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(Stats)]
 lib.rt_render_camera_device.argtypes = [C.c_void_p, C.POINTER(Options), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                         C.POINTER(Stats)]
+lib.rt_render_camera_undersampled.argtypes = [C.c_void_p, C.POINTER(Options), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                              C.POINTER(Stats)]
+lib.rt_render_camera_undersampled_device.argtypes = [C.c_void_p, C.POINTER(Options), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                     C.c_void_p, C.c_void_p, C.POINTER(Stats)]
 lib.rt_selftest_sqrt.argtypes = [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
 lib.rt_selftest_rcp.argtypes = [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
 lib.rt_scene_traits.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]

@@ -16,6 +16,7 @@
 #include "rt_flat_f64.hpp"
 #include "rt_query.hpp"
 #include "rt_trace.hpp"
+#include "rt_undersample.hpp"
 #include "rt_multihit.hpp"
 
 #include <hip/hip_runtime.h>

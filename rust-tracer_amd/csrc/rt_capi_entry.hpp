@@ -1084,6 +1084,111 @@ rt_status rt_render_camera(rt_scene *s, const rt_options *o, const void *camera,
     return RT_OK;
 }
 
+// ---- undersampled camera frames: one sample per step x step cell, refined in place (rt_undersample.hpp) ----
+
+// Shared body of both rt_render_camera_undersampled entries, as enqueue_camera: the pass into d_out (which holds the step-2s frame when
+// prev_step != 0) on `stream` through a leased context.  On RT_OK the context's ev1 follows the pass.
+static rt_status enqueue_camera_undersampled(rt_scene *s, Context *c, const rt_options *o, const void *camera, std::vector<rt::TileDev> &tab,
+                                             uint32_t blocks16, uint64_t total_px, uint32_t step, uint32_t prev_step, uint8_t *d_out, hipStream_t stream,
+                                             bool counting)
+{
+    if (step == 1 && prev_step == 0) return enqueue_camera(s, c, o, camera, tab, blocks16, total_px, d_out, stream, counting);
+    const void *nodes = nullptr;
+    uint32_t n_nodes = 0;
+    rt_status st = query_stream(s, stream, &nodes, &n_nodes);
+    if (st != RT_OK) return st;
+    uint32_t blocks = 0;
+    if ((st = undersample_blocks(tab, step, prev_step != 0, &blocks)) != RT_OK) return st;
+    const rt::TileDev *d_tab = nullptr;
+    if ((st = upload_tiles(c, tab, stream, 0, &d_tab)) != RT_OK) return st;
+    if (counting) {
+        HIP_TRY(hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, stream));
+        HIP_TRY(hipEventRecord(c->ev0, stream));
+    }
+    rt::Counters *const counters = counting ? c->d_counters : nullptr;
+    st = s->precision == RT_F32
+             ? enqueue_undersampled<float>(s, nodes, n_nodes, o, camera, d_tab, (uint32_t)tab.size(), blocks, step, prev_step != 0, d_out, counters, stream)
+             : enqueue_undersampled<double>(s, nodes, n_nodes, o, camera, d_tab, (uint32_t)tab.size(), blocks, step, prev_step != 0, d_out, counters, stream);
+    if (st != RT_OK) return st;
+    HIP_TRY(hipEventRecord(c->ev1, stream));
+    return RT_OK;
+}
+
+rt_status rt_render_camera_undersampled_device(rt_scene *s, const rt_options *o, const void *camera, const rt_region *tiles, uint32_t n, uint32_t step,
+                                               uint32_t prev_step, void *rgba_inout_device, void *hip_stream, rt_stats *stats)
+{
+    if (!undersample_args_ok(step, prev_step, "rt_render_camera_undersampled_device")) return RT_ERR_INVALID_ARGUMENT;
+    if (!camera_args_ok(s, o, camera, tiles, n, rgba_inout_device, "rt_render_camera_undersampled_device")) return RT_ERR_INVALID_ARGUMENT;
+    if ((reinterpret_cast<uintptr_t>(rgba_inout_device) & 3u) != 0) {
+        snprintf(g_err, sizeof g_err, "the device output buffer must be 4-byte aligned");
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    std::vector<rt::TileDev> tab;
+    uint64_t total_px = 0; uint32_t total_blocks = 0;
+    rt_status st = build_tile_table(o, tiles, n, tab, &total_px, &total_blocks);
+    if (st != RT_OK) return st;
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    Context *c = nullptr;
+    if ((st = acquire(s, &c)) != RT_OK) return st;
+    Lease lease{ s, c };
+    st = enqueue_camera_undersampled(s, c, o, camera, tab, total_blocks, total_px, step, prev_step, static_cast<uint8_t *>(rgba_inout_device), stream,
+                                     stats != nullptr);
+    if (st != RT_OK) {
+        (void)hipEventRecord(c->ev1, stream);           // (the context goes back behind what is enqueued)
+        (void)hipGetLastError();
+        lease.inflight = true;
+        return st;
+    }
+    if (stats) return read_trace_stats(c, stream, stats);
+    lease.inflight = true;                              // the tile table is in use until ev1: asynchronous return
+    return RT_OK;
+}
+
+rt_status rt_render_camera_undersampled(rt_scene *s, const rt_options *o, const void *camera, const rt_region *tiles, uint32_t n, uint32_t step,
+                                        uint32_t prev_step, uint8_t *rgba_inout, rt_stats *stats)
+{
+    if (!undersample_args_ok(step, prev_step, "rt_render_camera_undersampled")) return RT_ERR_INVALID_ARGUMENT;
+    if (!camera_args_ok(s, o, camera, tiles, n, rgba_inout, "rt_render_camera_undersampled")) return RT_ERR_INVALID_ARGUMENT;
+    std::vector<rt::TileDev> tab;
+    uint64_t total_px = 0; uint32_t total_blocks = 0;
+    rt_status st = build_tile_table(o, tiles, n, tab, &total_px, &total_blocks);
+    if (st != RT_OK) return st;
+    HIP_TRY(hipSetDevice(s->device));
+    const HostDest dest = classify_host_pointer(rgba_inout);
+    if (dest.bad) {
+        snprintf(g_err, sizeof g_err, "rt_render_camera_undersampled: rgba_inout is device memory; use rt_render_camera_undersampled_device");
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    const size_t bytes = (size_t)total_px * 4;
+    Context *c = nullptr;
+    if ((st = acquire(s, &c)) != RT_OK) return st;
+    Lease lease{ s, c };
+    // pinned memory is refined by the kernel in place; anything else goes through the context's device output: up first when the pass
+    // keeps cells of the frame it finds (prev_step != 0), and one copy back
+    const bool direct = dest.pinned && dest.dev_alias && dest.room >= bytes;
+    if (!direct && c->out_cap < bytes) {
+        if (c->d_out) HIP_TRY(hipFree(c->d_out));
+        c->d_out = nullptr; c->out_cap = 0;
+        HIP_TRY(hipMalloc(&c->d_out, bytes));
+        c->out_cap = bytes;
+    }
+    if (!direct && prev_step != 0) {
+        const hipError_t e = hipMemcpyAsync(c->d_out, rgba_inout, bytes, hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) { (void)hipStreamSynchronize(c->stream); return hip_fail(e, "hipMemcpyAsync", __LINE__); }
+    }
+    st = enqueue_camera_undersampled(s, c, o, camera, tab, total_blocks, total_px, step, prev_step, direct ? dest.dev_alias : c->d_out, c->stream,
+                                     stats != nullptr);
+    if (st != RT_OK) { (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return st; }
+    if (!direct) {
+        const hipError_t e = hipMemcpyAsync(rgba_inout, c->d_out, bytes, hipMemcpyDeviceToHost, c->stream);
+        if (e != hipSuccess) { (void)hipStreamSynchronize(c->stream); return hip_fail(e, "hipMemcpyAsync", __LINE__); }
+    }
+    if (stats) return read_trace_stats(c, c->stream, stats);          // synchronises the stream
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return RT_OK;
+}
+
 rt_status rt_host_alloc(size_t bytes, void **out)
 {
     if (!out || bytes == 0) { snprintf(g_err, sizeof g_err, "rt_host_alloc: NULL argument or 0 bytes"); return RT_ERR_INVALID_ARGUMENT; }

@@ -861,3 +861,64 @@ rt_status read_trace_stats(Context *c, hipStream_t stream, rt_stats *st)
     st->device_ms = ms;
     return RT_OK;
 }
+
+// ---- undersampled camera frames (rt_render_camera_undersampled*, rt_undersample.hpp) ----
+
+// step in [1, RT_UNDERSAMPLE_MAX_STEP]; prev_step 0 (a fresh frame) or exactly 2 * step (a refinement of the step-2s frame in the buffer).
+bool undersample_args_ok(uint32_t step, uint32_t prev_step, const char *what)
+{
+    if (step < 1 || step > RT_UNDERSAMPLE_MAX_STEP) {
+        snprintf(g_err, sizeof g_err, "%s: step is %u, outside 1 .. %d", what, step, RT_UNDERSAMPLE_MAX_STEP);
+        return false;
+    }
+    if (prev_step != 0 && prev_step != 2 * step) {
+        snprintf(g_err, sizeof g_err, "%s: prev_step is %u; it must be 0 (a fresh frame) or 2 * step = %u", what, prev_step, 2 * step);
+        return false;
+    }
+    return true;
+}
+
+// The blocks of an undersampled pass over a validated tile table (rt_undersample.hpp): per tile, 16 x 16 cells of its step grid (fresh)
+// or 8 x 8 cells of its 2 * step grid (refinement), counted in blk_first / blks_x.
+rt_status undersample_blocks(std::vector<rt::TileDev> &tab, uint32_t step, bool refine, uint32_t *total_blocks)
+{
+    const uint32_t unit = refine ? 2 * step : step, per_block = refine ? 8 : (uint32_t)rt::kBlockW;
+    uint64_t blocks = 0;
+    for (rt::TileDev &t : tab) {
+        const uint32_t nx = (t.r - 1u) / unit - t.l / unit + 1u, ny = (t.t - 1u) / unit - t.b / unit + 1u;
+        const uint32_t bxs = (nx + per_block - 1) / per_block, bys = (ny + per_block - 1) / per_block;
+        t.blk_first = (uint32_t)blocks;
+        t.blks_x = bxs;
+        blocks += (uint64_t)bxs * bys;
+    }
+    *total_blocks = (uint32_t)blocks;          // (never more than build_tile_table's 16 x 16 pixel blocks)
+    return RT_OK;
+}
+
+// One undersampled pass over a device tile table (blocks as undersample_blocks counts them) on `stream`; counters != NULL runs the
+// counting flavour (same bytes).
+template <typename T>
+rt_status enqueue_undersampled(const rt_scene *s, const void *nodes, uint32_t n_nodes, const rt_options *o, const void *cam, const rt::TileDev *d_tab,
+                               uint32_t n_tiles, uint32_t blocks, uint32_t step, bool refine, uint8_t *d_out, rt::Counters *counters, hipStream_t stream)
+{
+    rt::UnderArgs<T> a{};
+    a.t.stream = static_cast<const rt::Node<T> *>(nodes);
+    a.t.items = static_cast<const rt::Item<T> *>(s->d_items);
+    a.t.counters = counters;
+    a.t.tiles = d_tab;
+    a.t.out = d_out;
+    for (int k = 0; k < 12; ++k) a.t.cam[k] = static_cast<const T *>(cam)[k];
+    for (int k = 0; k < 3; ++k) a.t.light[k] = (T)s->light[k];
+    a.t.n_nodes = n_nodes;
+    a.t.n = n_tiles;
+    a.t.width = o->width; a.t.height = o->height; a.t.spp = o->samples_per_pixel;
+    a.step = step;
+    a.refine = refine ? 1u : 0u;
+    while ((1u << a.lg_pw) < step) ++a.lg_pw;
+    a.lg_p = std::min(6u, 2 * a.lg_pw);
+    const dim3 grid(blocks), block(refine ? 192 : rt::kBlockThreads);
+    if (counters) hipLaunchKernelGGL((rt::k_trace_undersampled<T, true>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((rt::k_trace_undersampled<T, false>), grid, block, 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}

@@ -93,6 +93,57 @@ def look_at(eye, target, up=(0.0, 1.0, 0.0), hfov_deg=None, precision=capi.RT_F3
     return np.concatenate([e, r + 0.0, u2 + 0.0, f + 0.0]).astype(_real(precision))
 
 
+def expand_undersampled(image, regions, step):
+    """The step-s frame of `regions`, from the full image: every pixel (x, y) of every region holds image[y - y % step, x - x % step] (the
+    lattice is anchored at the image origin, so an anchor may lie outside its region).  image: uint8[height, width, 4] row-major, what
+    render_camera returns for the single region (0, height, width, 0); regions: (l, t, r, b) tuples.  -> uint8[total_px * 4] tile-major,
+    the bytes render_camera_undersampled(step) writes.  Host only (numpy)."""
+    img = np.asarray(image)
+    step = int(step)
+    if img.ndim != 3 or img.shape[2] != 4 or img.dtype != np.uint8:
+        raise ValueError("image must be uint8[height, width, 4]")
+    if step < 1:
+        raise ValueError("step must be >= 1")
+    h, w = img.shape[:2]
+    parts = []
+    for l, t, r, b in regions:
+        if not (0 <= l < r <= w and 0 <= b < t <= h):
+            raise ValueError("region %r is empty or outside the %dx%d image" % ((l, t, r, b), w, h))
+        ys, xs = np.arange(b, t), np.arange(l, r)
+        parts.append(img[(ys - ys % step)[:, None], (xs - xs % step)[None, :]].reshape(-1))
+    return np.concatenate(parts) if parts else np.empty(0, dtype=np.uint8)
+
+
+def undersample_cells(regions, step, prev_step=0):
+    """(traced, reused) cells of one render_camera_undersampled pass: over the regions, the step-s cells that meet a region and are traced
+    (all of them when prev_step == 0; with prev_step == 2 * step those whose anchor is off the 2s lattice) and those that are kept."""
+    step = int(step)
+    if prev_step not in (0, 2 * step):
+        raise ValueError("prev_step must be 0 or 2 * step")
+    traced = reused = 0
+    for l, t, r, b in regions:
+        nx, ny = (r - 1) // step - l // step + 1, (t - 1) // step - b // step + 1
+        kept = 0
+        if prev_step:      # cells (cx, cy) with cx and cy even: the even numbers of [a, b] are b // 2 - (a + 1) // 2 + 1
+            kept = ((r - 1) // step // 2 - (l // step + 1) // 2 + 1) * ((t - 1) // step // 2 - (b // step + 1) // 2 + 1)
+        traced += nx * ny - kept
+        reused += kept
+    return traced, reused
+
+
+def progressive_steps(first_step):
+    """[first_step, first_step / 2, ..., 1] for a power of two first_step <= RT_UNDERSAMPLE_MAX_STEP; ValueError otherwise."""
+    if isinstance(first_step, bool) or not isinstance(first_step, (int, np.integer)) or first_step < 1 \
+            or first_step > capi.RT_UNDERSAMPLE_MAX_STEP or first_step & (first_step - 1):
+        raise ValueError("first_step must be a power of two in 1 .. %d, not %r" % (capi.RT_UNDERSAMPLE_MAX_STEP, first_step))
+    steps = []
+    s = int(first_step)
+    while s >= 1:
+        steps.append(s)
+        s //= 2
+    return steps
+
+
 def build_hierarchy(spheres, leaf_size=4, precision=capi.RT_F32, eye=None):
     """Bounding-sphere hierarchy for an arbitrary sphere list (scenes other than the pyramid, e.g. BASELINE
     config 5 with exactly 100,000 spheres).  Not in the reference -- its only scene builder is `pyramid` -- but the result
@@ -568,6 +619,51 @@ class DeviceScene:
                                               C.byref(st) if want_stats else None)
         capi.check(rc, "rt_render_camera_device")
         return st.as_dict() if want_stats else None
+
+    def render_camera_undersampled(self, options, camera, regions, step, prev_step=0, want_stats=True, out=None):
+        """rt_render_camera_undersampled: the camera frame sampled once per step x step cell of the image's lattice (expand_undersampled is
+        its definition) -> (uint8[total_px*4] tile-major, stats dict | None).  prev_step = 2 * step refines `out`, which holds the step-2s
+        frame of the same view and regions, in place: only the cells off the 2s lattice are traced and written."""
+        cam = self._camera(camera)
+        arr = regions if isinstance(regions, C.Array) else self._regions(regions)
+        nbytes = capi.lib.rt_tiles_rgba_bytes(arr, len(arr))
+        if out is None:
+            if prev_step:
+                raise ValueError("a refinement pass (prev_step != 0) needs `out`, the buffer that holds the coarser frame")
+            out = np.empty(max(int(nbytes), 1), dtype=np.uint8)
+        elif out.dtype != np.uint8 or not out.flags.c_contiguous or out.size < nbytes:
+            raise ValueError("out must be a contiguous uint8 array of at least %d bytes" % nbytes)
+        st = capi.Stats()
+        o = capi.Options(*options)
+        rc = capi.lib.rt_render_camera_undersampled(self._h, C.byref(o), cam.ctypes.data, arr, len(arr), int(step), int(prev_step), out.ctypes.data,
+                                                    C.byref(st) if want_stats else None)
+        capi.check(rc, "rt_render_camera_undersampled")
+        return out.reshape(-1)[:int(nbytes)], (st.as_dict() if want_stats else None)
+
+    def render_camera_undersampled_device(self, options, camera, regions, step, out_ptr, prev_step=0, stream=0, want_stats=False):
+        """rt_render_camera_undersampled_device: the same into (prev_step != 0: in) device memory, enqueued on `stream` (hipStream_t as int)."""
+        cam = self._camera(camera)
+        arr = regions if isinstance(regions, C.Array) else self._regions(regions)
+        st = capi.Stats()
+        o = capi.Options(*options)
+        rc = capi.lib.rt_render_camera_undersampled_device(self._h, C.byref(o), cam.ctypes.data, arr, len(arr), int(step), int(prev_step),
+                                                           C.c_void_p(out_ptr), C.c_void_p(stream), C.byref(st) if want_stats else None)
+        capi.check(rc, "rt_render_camera_undersampled_device")
+        return st.as_dict() if want_stats else None
+
+    def render_camera_progressive(self, options, camera, regions, first_step=8, out=None):
+        """A generator of (step, frame_bytes, stats) for first_step, first_step / 2, ..., 1 over ONE buffer: a coarse frame at once, then
+        refinement passes that trace no sample twice; the last frame is render_camera's.  first_step: a power of two <= 64 (ValueError
+        otherwise, raised by this call).  Stop iterating when the camera moves; frame_bytes is a view of the buffer the next pass refines."""
+        steps = progressive_steps(first_step)
+
+        def passes():
+            buf, prev = out, 0
+            for s in steps:
+                buf, st = self.render_camera_undersampled(options, camera, regions, s, prev_step=prev, out=buf)
+                prev = s
+                yield s, buf, st
+        return passes()
 
     def blit_tiles_device(self, options, regions, src_ptr, frame_ptr, stream=0, src_px_offset=None):
         """rt_blit_tiles_device: tile-major device tiles -> row-major device frame (set_pixels_from_buffer)."""
