@@ -332,6 +332,52 @@ rt_status rt_render_camera(rt_scene *scene, const rt_options *options, const voi
 rt_status rt_render_camera_device(rt_scene *scene, const rt_options *options, const void *camera,
                                   const rt_region *tiles, uint32_t n_tiles, void *rgba_out_device, void *hip_stream, rt_stats *stats);
 
+/* ---- coherent ray batches (additive to ABI 5): order the rays on the device, walk them in that order ----
+ * The query kernels put ray j of the batch into lane j % 64 of wave j / 64, and a wave walks the union of its lanes' subtrees: what a batch
+ * costs depends on the order it is stored in.  An ORDER is uint32[n]: order[j] is the index of the ray lane j carries.  Each lane makes its
+ * own ray's tests whatever its neighbours do, so the *_ordered entries below write, for ANY permutation, the bytes and the counters of the
+ * entries they extend; only the time differs.
+ *
+ * rt_ray_order computes the stable ascending sort of one 32-bit key per ray (equal keys stay in the caller's order): unique, deterministic,
+ * a permutation of 0 .. n-1.  The key depends on the ray's six values and on the batch's origin box, nothing else; the scene supplies the
+ * device, REAL and the workspace.  All of it in double (a float converts exactly), every operation rounded once:
+ *   lo[a], hi[a]  min / max of pos[a] over the batch, a = 0, 1, 2;  ext = max(hi[a] - lo[a])
+ *   scale         0 if ext == 0 (one origin, a camera: every origin bit is 0); else 2^(3 - e), e = max(E - 1022, -1000) with E the 11-bit
+ *                 biased exponent field of ext, so that ext < 2^e
+ *   c[a]          trunc(min(max((pos[a] - lo[a]) * scale, 0), 7))                                       3 bits per axis
+ *   axis          the component of dir with the largest |value|, the lowest such on a tie;  sign = 1 if that component < 0, else 0
+ *   q[b]          trunc(min(max((dir[(axis + 1 + b) % 3] + 1) * 512, 0), 1023)), b = 0, 1              10 bits each
+ *   key           M3 << 23 | (2 * axis + sign) << 20 | M2, where bit i of c[a] is bit 3i + a of M3 and bit i of q[b] is bit 2i + b of M2
+ * rust_tracer_amd.ray_keys restates it in numpy; the order is numpy.argsort(ray_keys(rays), kind="stable") bit for bit. */
+/* Host memory; rays validated as rt_intersect_rays validates them (RT_ERR_INVALID_ARGUMENT before the device is touched, also for a NULL
+ * scene, rays or order_out and n == 0).  Returns when order_out[0 .. n) is in place. */
+rt_status rt_ray_order(rt_scene *scene, const void *rays, uint32_t n, uint32_t *order_out);
+/* The same over DEVICE memory, enqueued on `hip_stream` without waiting for it: only pointers, alignment and n are checked; the result is
+ * a permutation whatever bits the rays hold.  The temporary storage is the scene's and is reused once the stream has passed the call. */
+rt_status rt_ray_order_device(rt_scene *scene, const void *rays, uint32_t n, uint32_t *order_out, void *hip_stream);
+/* rt_intersect_rays, rt_intersect_rays_multi and rt_trace_rays with the rays taken in `order`: thread j reads ray order[j] and its tmax and
+ * writes every result at index order[j] -- the outputs are indexed by ray, exactly as the unordered entries leave them.
+ *   order == NULL  the call computes rt_ray_order's order itself, in its workspace, and walks in it: the one-call form.
+ *   order != NULL  host entries: must be a permutation of 0 .. n-1 (RT_ERR_INVALID_ARGUMENT before the device is touched for an index
+ *                  >= n or a repeated one).  Device entries: pointer alignment only; a thread whose order[j] >= n carries no ray, so no
+ *                  bits in `order` fault; a ray named twice gets unspecified values, one never named is not written.
+ * Everything else as the entry each extends; stats->device_ms is the walk's time in every form (the one-call form's order is computed in
+ * front of the timed span). */
+rt_status rt_intersect_rays_ordered(rt_scene *scene, rt_query mode, const void *rays, const void *tmax, uint32_t n, const uint32_t *order,
+                                    void *distance_out, void *normal_out, int32_t *item_out, rt_stats *stats);
+rt_status rt_intersect_rays_ordered_device(rt_scene *scene, rt_query mode, const void *rays, const void *tmax, uint32_t n, const uint32_t *order,
+                                           void *distance_out, void *normal_out, int32_t *item_out, void *hip_stream, rt_stats *stats);
+rt_status rt_intersect_rays_multi_ordered(rt_scene *scene, rt_multihit mode, uint32_t k, const void *rays, const void *tmax, uint32_t n,
+                                          const uint32_t *order, void *distance_out, void *normal_out, int32_t *item_out, uint32_t *hits_out,
+                                          rt_stats *stats);
+rt_status rt_intersect_rays_multi_ordered_device(rt_scene *scene, rt_multihit mode, uint32_t k, const void *rays, const void *tmax, uint32_t n,
+                                                 const uint32_t *order, void *distance_out, void *normal_out, int32_t *item_out,
+                                                 uint32_t *hits_out, void *hip_stream, rt_stats *stats);
+rt_status rt_trace_rays_ordered(rt_scene *scene, const void *rays, uint32_t n, const uint32_t *order, void *color_out, void *alpha_out,
+                                rt_stats *stats);
+rt_status rt_trace_rays_ordered_device(rt_scene *scene, const void *rays, uint32_t n, const uint32_t *order, void *color_out, void *alpha_out,
+                                       void *hip_stream, rt_stats *stats);
+
 /* ---- undersampled camera frames that refine in place (additive to ABI 5) ----
  * F(x, y) is the pixel rt_render_camera writes for (x, y).  The LATTICE of a step s is every pixel with x % s == 0 and y % s == 0, anchored
  * at the image origin (not at a tile's corner); the anchor of (x, y) is (x - x % s, y - y % s).  The step-s frame holds F(anchor(x, y)) in

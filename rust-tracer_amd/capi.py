@@ -32,7 +32,9 @@ SYMBOLS = ("rt_abi_version", "rt_build_hierarchy", "rt_device_count", "rt_scene_
            "rt_last_launch_flags", "rt_build_info", "rt_render_frame_stream", "rt_intersect_rays", "rt_intersect_rays_device",
            "rt_trace_rays", "rt_trace_rays_device", "rt_render_camera", "rt_render_camera_device",
            "rt_intersect_rays_multi", "rt_intersect_rays_multi_device",
-           "rt_render_camera_undersampled", "rt_render_camera_undersampled_device")
+           "rt_render_camera_undersampled", "rt_render_camera_undersampled_device",
+           "rt_ray_order", "rt_ray_order_device", "rt_intersect_rays_ordered", "rt_intersect_rays_ordered_device",
+           "rt_intersect_rays_multi_ordered", "rt_intersect_rays_multi_ordered_device", "rt_trace_rays_ordered", "rt_trace_rays_ordered_device")
 # csrc/rt_debug.h: only in the -DRT_TEST_HOOKS build
 DEBUG_SYMBOLS = ("rt_debug_set", "rt_debug_count", "rt_debug_wave_trace", "rt_debug_flat_filter_check", "rt_debug_gang_layout", "rt_debug_rccl_library",
                  "rt_debug_shard_costs")
@@ -107,6 +109,18 @@ lib.rt_intersect_rays_multi_device.argtypes = [C.c_void_p, C.c_int, C.c_uint32, 
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
 lib.rt_trace_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
 lib.rt_trace_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+# coherent ray batches: `order` (uint32[n] or NULL) follows n
+lib.rt_ray_order.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+lib.rt_ray_order_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+lib.rt_intersect_rays_ordered.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+lib.rt_intersect_rays_ordered_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.POINTER(Stats)]
+lib.rt_intersect_rays_multi_ordered.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+lib.rt_intersect_rays_multi_ordered_device.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+lib.rt_trace_rays_ordered.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+lib.rt_trace_rays_ordered_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
 lib.rt_render_camera.argtypes = [C.c_void_p, C.POINTER(Options), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(Stats)]
 lib.rt_render_camera_device.argtypes = [C.c_void_p, C.POINTER(Options), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
                                         C.POINTER(Stats)]

@@ -18,6 +18,7 @@
 #include "rt_trace.hpp"
 #include "rt_undersample.hpp"
 #include "rt_multihit.hpp"
+#include "rt_order.hpp"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>       // types and prototypes only: librccl.so is loaded with dlopen when the first gang is created
@@ -127,6 +128,8 @@ struct Context {
     rt::FlatQueues *d_queues = nullptr;
     void *d_query = nullptr;          // rt_intersect_rays: device copies of the rays and results of pageable / unmapped host buffers
     size_t query_cap = 0;             // bytes of d_query
+    void *d_sort = nullptr;           // rt_ray_order / the ordered queries: keys, indices, digit table of the sort and the order it leaves (rt_order.hpp)
+    size_t sort_cap = 0;              // bytes of d_sort
     unsigned flat_first_pass_items = 0;   // items the first shadow pass of the last flat launch covered (rt_stats.tests_executed)
     bool busy = false;       // leased to a caller right now
     bool inflight = false;   // released by an asynchronous caller; reusable once ev1 has completed
@@ -147,6 +150,7 @@ struct Context {
         if (d_queue2) (void)hipFree(d_queue2);
         if (d_queues) (void)hipFree(d_queues);
         if (d_query) (void)hipFree(d_query);
+        if (d_sort) (void)hipFree(d_sort);
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
         if (stream2) (void)hipStreamDestroy(stream2);

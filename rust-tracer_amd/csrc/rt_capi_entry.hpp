@@ -714,51 +714,93 @@ rt_status rt_render_frame_stream(rt_scene *s, const rt_options *o, rt_traversal 
 
 // ---- ray queries: TypedGroup::intersect(&mut hit, &ray) for a batch of arbitrary rays (rt_query.hpp) ----
 
-rt_status rt_intersect_rays_device(rt_scene *s, rt_query mode, const void *rays, const void *tmax, uint32_t n, void *distance_out, void *normal_out,
-                                   int32_t *item_out, void *hip_stream, rt_stats *stats)
+// The ordered entries (rt_order.hpp) share the bodies of the entries they extend.  `ordered` with order == NULL: the call
+// computes the order itself in its context's workspace, then walks; a device order is checked for alignment only.
+static bool device_order_ok(const uint32_t *order, const char *what)
 {
-    if (!query_args_ok(s, mode, rays, tmax, n, distance_out, normal_out, item_out, "rt_intersect_rays_device")) return RT_ERR_INVALID_ARGUMENT;
+    if ((reinterpret_cast<uintptr_t>(order) & 3u) != 0) { snprintf(g_err, sizeof g_err, "%s: order must be 4-byte aligned", what); return false; }
+    return true;
+}
+
+// What a device entry does when a step failed after the call's own order was enqueued: the context, whose workspace the sort uses, goes
+// back behind what is enqueued.  (With nothing enqueued through the context a failure returns plainly, as the unordered entries always did.)
+static rt_status behind_enqueued(Context *c, Lease &lease, hipStream_t stream, rt_status st)
+{
+    (void)hipEventRecord(c->ev1, stream);
+    (void)hipGetLastError();
+    lease.inflight = true;
+    return st;
+}
+
+static rt_status intersect_rays_device(rt_scene *s, rt_query mode, const void *rays, const void *tmax, uint32_t n, void *distance_out, void *normal_out,
+                                       int32_t *item_out, bool ordered, const uint32_t *order, void *hip_stream, rt_stats *stats, const char *what)
+{
+    if (!query_args_ok(s, mode, rays, tmax, n, distance_out, normal_out, item_out, what)) return RT_ERR_INVALID_ARGUMENT;
+    if (ordered && !device_order_ok(order, what)) return RT_ERR_INVALID_ARGUMENT;
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     const void *nodes = nullptr;
     uint32_t n_nodes = 0;
     rt_status st = query_stream(s, stream, &nodes, &n_nodes);
     if (st != RT_OK) return st;
-    if (!stats) return enqueue_query(s, nodes, n_nodes, mode, rays, tmax, n, distance_out, normal_out, item_out, nullptr, stream);
+    const bool sort = ordered && !order;
+    if (!stats && !sort) return enqueue_query(s, nodes, n_nodes, mode, rays, tmax, n, distance_out, normal_out, item_out, nullptr, stream, order);
     Context *c = nullptr;
     if ((st = acquire(s, &c)) != RT_OK) return st;
     Lease lease{ s, c };
-    HIP_TRY(hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, stream));
-    HIP_TRY(hipEventRecord(c->ev0, stream));
-    st = enqueue_query(s, nodes, n_nodes, mode, rays, tmax, n, distance_out, normal_out, item_out, c->d_counters, stream);
+    if (sort && (st = enqueue_ray_order(s, c, rays, n, nullptr, stream, &order)) != RT_OK) return behind_enqueued(c, lease, stream, st);
+    if (stats) {
+        if (hipError_t e = hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, stream); e != hipSuccess)
+            return sort ? behind_enqueued(c, lease, stream, hip_fail(e, "hipMemsetAsync(counters)", __LINE__)) : hip_fail(e, "hipMemsetAsync(counters)", __LINE__);
+        if (hipError_t e = hipEventRecord(c->ev0, stream); e != hipSuccess)
+            return sort ? behind_enqueued(c, lease, stream, hip_fail(e, "hipEventRecord", __LINE__)) : hip_fail(e, "hipEventRecord", __LINE__);
+    }
+    st = enqueue_query(s, nodes, n_nodes, mode, rays, tmax, n, distance_out, normal_out, item_out, stats ? c->d_counters : nullptr, stream, order);
     (void)hipEventRecord(c->ev1, stream);
     if (st != RT_OK) { (void)hipGetLastError(); lease.inflight = true; return st; }      // (the context goes back behind what is enqueued)
-    return read_query_stats(c, stream, stats);
+    if (stats) return read_query_stats(c, stream, stats);
+    lease.inflight = true;                              // the order in the workspace is in use until ev1: asynchronous return
+    return RT_OK;
 }
 
-rt_status rt_intersect_rays(rt_scene *s, rt_query mode, const void *rays, const void *tmax, uint32_t n, void *distance_out, void *normal_out,
-                            int32_t *item_out, rt_stats *stats)
+rt_status rt_intersect_rays_device(rt_scene *s, rt_query mode, const void *rays, const void *tmax, uint32_t n, void *distance_out, void *normal_out,
+                                   int32_t *item_out, void *hip_stream, rt_stats *stats)
 {
-    if (!query_args_ok(s, mode, rays, tmax, n, distance_out, normal_out, item_out, "rt_intersect_rays")) return RT_ERR_INVALID_ARGUMENT;
+    return intersect_rays_device(s, mode, rays, tmax, n, distance_out, normal_out, item_out, false, nullptr, hip_stream, stats, "rt_intersect_rays_device");
+}
+
+rt_status rt_intersect_rays_ordered_device(rt_scene *s, rt_query mode, const void *rays, const void *tmax, uint32_t n, const uint32_t *order,
+                                           void *distance_out, void *normal_out, int32_t *item_out, void *hip_stream, rt_stats *stats)
+{
+    return intersect_rays_device(s, mode, rays, tmax, n, distance_out, normal_out, item_out, true, order, hip_stream, stats, "rt_intersect_rays_ordered_device");
+}
+
+static rt_status intersect_rays_host(rt_scene *s, rt_query mode, const void *rays, const void *tmax, uint32_t n, void *distance_out, void *normal_out,
+                                     int32_t *item_out, bool ordered, const uint32_t *order, rt_stats *stats, const char *what)
+{
+    if (!query_args_ok(s, mode, rays, tmax, n, distance_out, normal_out, item_out, what)) return RT_ERR_INVALID_ARGUMENT;
+    if (ordered && !device_order_ok(order, what)) return RT_ERR_INVALID_ARGUMENT;
     const bool f32 = s->precision == RT_F32;
     if (!(f32 ? query_rays_valid(static_cast<const float *>(rays), static_cast<const float *>(tmax), n)
               : query_rays_valid(static_cast<const double *>(rays), static_cast<const double *>(tmax), n)))
         return RT_ERR_INVALID_ARGUMENT;
+    if (order && !order_is_permutation(order, n, what)) return RT_ERR_INVALID_ARGUMENT;
     HIP_TRY(hipSetDevice(s->device));
     rt_status st = RT_OK;
     // Every buffer is either the caller's own memory, read and written by the kernel directly (rt_host_alloc / rt_host_register), or a
     // device copy in the call's workspace (pageable memory: the copies go through the runtime's staging).
     const size_t esz = f32 ? sizeof(float) : sizeof(double);
     struct Buf { void *host; size_t bytes; bool out; uint8_t *dev; size_t off; bool staged; };
-    Buf b[5] = { { const_cast<void *>(rays), 6 * esz * n, false, nullptr, 0, false }, { const_cast<void *>(tmax), esz * n, false, nullptr, 0, false },
+    Buf b[6] = { { const_cast<void *>(rays), 6 * esz * n, false, nullptr, 0, false }, { const_cast<void *>(tmax), esz * n, false, nullptr, 0, false },
                  { distance_out, esz * n, true, nullptr, 0, false }, { normal_out, 3 * esz * n, true, nullptr, 0, false },
-                 { item_out, sizeof(int32_t) * n, true, nullptr, 0, false } };
+                 { item_out, sizeof(int32_t) * n, true, nullptr, 0, false },
+                 { const_cast<uint32_t *>(order), sizeof(uint32_t) * n, false, nullptr, 0, false } };
     size_t need = 0;
     for (Buf &x : b) {
         if (!x.host) continue;
         const HostDest d = classify_host_pointer(x.host);
         if (d.bad) {
-            snprintf(g_err, sizeof g_err, "rt_intersect_rays: a buffer is device memory; use rt_intersect_rays_device");
+            snprintf(g_err, sizeof g_err, "%s: a buffer is device memory; use %s_device", what, what);
             return RT_ERR_INVALID_ARGUMENT;
         }
         if (d.pinned && d.dev_alias && d.room >= x.bytes) { x.dev = d.dev_alias; continue; }
@@ -789,12 +831,16 @@ rt_status rt_intersect_rays(rt_scene *s, rt_query mode, const void *rays, const 
     for (const Buf &x : b)
         if (x.staged && !x.out)
             HIP_DRAIN(hipMemcpyAsync(x.dev, x.host, x.bytes, hipMemcpyHostToDevice, c->stream));
+    const uint32_t *d_order = reinterpret_cast<const uint32_t *>(b[5].dev);
+    if (ordered && !order && (st = enqueue_ray_order(s, c, b[0].dev, n, nullptr, c->stream, &d_order)) != RT_OK) {
+        (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return st;
+    }
     if (stats) {
         HIP_DRAIN(hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, c->stream));
         HIP_DRAIN(hipEventRecord(c->ev0, c->stream));
     }
     st = enqueue_query(s, nodes, n_nodes, mode, b[0].dev, b[1].dev, n, b[2].dev, b[3].dev, reinterpret_cast<int32_t *>(b[4].dev),
-                       stats ? c->d_counters : nullptr, c->stream);
+                       stats ? c->d_counters : nullptr, c->stream, d_order);
     if (st != RT_OK) { (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return st; }
     if (stats) HIP_DRAIN(hipEventRecord(c->ev1, c->stream));
     for (const Buf &x : b)
@@ -806,56 +852,97 @@ rt_status rt_intersect_rays(rt_scene *s, rt_query mode, const void *rays, const 
     return RT_OK;
 }
 
+rt_status rt_intersect_rays(rt_scene *s, rt_query mode, const void *rays, const void *tmax, uint32_t n, void *distance_out, void *normal_out,
+                            int32_t *item_out, rt_stats *stats)
+{
+    return intersect_rays_host(s, mode, rays, tmax, n, distance_out, normal_out, item_out, false, nullptr, stats, "rt_intersect_rays");
+}
+
+rt_status rt_intersect_rays_ordered(rt_scene *s, rt_query mode, const void *rays, const void *tmax, uint32_t n, const uint32_t *order,
+                                    void *distance_out, void *normal_out, int32_t *item_out, rt_stats *stats)
+{
+    return intersect_rays_host(s, mode, rays, tmax, n, distance_out, normal_out, item_out, true, order, stats, "rt_intersect_rays_ordered");
+}
+
 // ---- multi-hit ray queries: the k closest hits, or every hit below tmax, for a batch of arbitrary rays (rt_multihit.hpp) ----
 
-rt_status rt_intersect_rays_multi_device(rt_scene *s, rt_multihit mode, uint32_t k, const void *rays, const void *tmax, uint32_t n, void *distance_out,
-                                         void *normal_out, int32_t *item_out, uint32_t *hits_out, void *hip_stream, rt_stats *stats)
+static rt_status intersect_rays_multi_device(rt_scene *s, rt_multihit mode, uint32_t k, const void *rays, const void *tmax, uint32_t n, void *distance_out,
+                                             void *normal_out, int32_t *item_out, uint32_t *hits_out, bool ordered, const uint32_t *order,
+                                             void *hip_stream, rt_stats *stats, const char *what)
 {
-    if (!query_args_ok(s, RT_QUERY_NEAREST, rays, tmax, n, distance_out, normal_out, item_out, "rt_intersect_rays_multi_device") ||
-        !multihit_args_ok(mode, k, hits_out, "rt_intersect_rays_multi_device"))
+    if (!query_args_ok(s, RT_QUERY_NEAREST, rays, tmax, n, distance_out, normal_out, item_out, what) || !multihit_args_ok(mode, k, hits_out, what))
         return RT_ERR_INVALID_ARGUMENT;
+    if (ordered && !device_order_ok(order, what)) return RT_ERR_INVALID_ARGUMENT;
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     const void *nodes = nullptr;
     uint32_t n_nodes = 0;
     rt_status st = query_stream(s, stream, &nodes, &n_nodes);
     if (st != RT_OK) return st;
-    if (!stats) return enqueue_multihit(s, nodes, n_nodes, mode, k, rays, tmax, n, distance_out, normal_out, item_out, hits_out, nullptr, stream);
+    const bool sort = ordered && !order;
+    if (!stats && !sort)
+        return enqueue_multihit(s, nodes, n_nodes, mode, k, rays, tmax, n, distance_out, normal_out, item_out, hits_out, nullptr, stream, order);
     Context *c = nullptr;
     if ((st = acquire(s, &c)) != RT_OK) return st;
     Lease lease{ s, c };
-    HIP_TRY(hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, stream));
-    HIP_TRY(hipEventRecord(c->ev0, stream));
-    st = enqueue_multihit(s, nodes, n_nodes, mode, k, rays, tmax, n, distance_out, normal_out, item_out, hits_out, c->d_counters, stream);
+    if (sort && (st = enqueue_ray_order(s, c, rays, n, nullptr, stream, &order)) != RT_OK) return behind_enqueued(c, lease, stream, st);
+    if (stats) {
+        if (hipError_t e = hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, stream); e != hipSuccess)
+            return sort ? behind_enqueued(c, lease, stream, hip_fail(e, "hipMemsetAsync(counters)", __LINE__)) : hip_fail(e, "hipMemsetAsync(counters)", __LINE__);
+        if (hipError_t e = hipEventRecord(c->ev0, stream); e != hipSuccess)
+            return sort ? behind_enqueued(c, lease, stream, hip_fail(e, "hipEventRecord", __LINE__)) : hip_fail(e, "hipEventRecord", __LINE__);
+    }
+    st = enqueue_multihit(s, nodes, n_nodes, mode, k, rays, tmax, n, distance_out, normal_out, item_out, hits_out, stats ? c->d_counters : nullptr, stream,
+                          order);
     (void)hipEventRecord(c->ev1, stream);
     if (st != RT_OK) { (void)hipGetLastError(); lease.inflight = true; return st; }      // (the context goes back behind what is enqueued)
-    return read_query_stats(c, stream, stats);
+    if (stats) return read_query_stats(c, stream, stats);
+    lease.inflight = true;                              // the order in the workspace is in use until ev1: asynchronous return
+    return RT_OK;
 }
 
-rt_status rt_intersect_rays_multi(rt_scene *s, rt_multihit mode, uint32_t k, const void *rays, const void *tmax, uint32_t n, void *distance_out,
-                                  void *normal_out, int32_t *item_out, uint32_t *hits_out, rt_stats *stats)
+rt_status rt_intersect_rays_multi_device(rt_scene *s, rt_multihit mode, uint32_t k, const void *rays, const void *tmax, uint32_t n, void *distance_out,
+                                         void *normal_out, int32_t *item_out, uint32_t *hits_out, void *hip_stream, rt_stats *stats)
 {
-    if (!query_args_ok(s, RT_QUERY_NEAREST, rays, tmax, n, distance_out, normal_out, item_out, "rt_intersect_rays_multi") ||
-        !multihit_args_ok(mode, k, hits_out, "rt_intersect_rays_multi"))
+    return intersect_rays_multi_device(s, mode, k, rays, tmax, n, distance_out, normal_out, item_out, hits_out, false, nullptr, hip_stream, stats,
+                                       "rt_intersect_rays_multi_device");
+}
+
+rt_status rt_intersect_rays_multi_ordered_device(rt_scene *s, rt_multihit mode, uint32_t k, const void *rays, const void *tmax, uint32_t n,
+                                                 const uint32_t *order, void *distance_out, void *normal_out, int32_t *item_out, uint32_t *hits_out,
+                                                 void *hip_stream, rt_stats *stats)
+{
+    return intersect_rays_multi_device(s, mode, k, rays, tmax, n, distance_out, normal_out, item_out, hits_out, true, order, hip_stream, stats,
+                                       "rt_intersect_rays_multi_ordered_device");
+}
+
+static rt_status intersect_rays_multi_host(rt_scene *s, rt_multihit mode, uint32_t k, const void *rays, const void *tmax, uint32_t n, void *distance_out,
+                                           void *normal_out, int32_t *item_out, uint32_t *hits_out, bool ordered, const uint32_t *order, rt_stats *stats,
+                                           const char *what)
+{
+    if (!query_args_ok(s, RT_QUERY_NEAREST, rays, tmax, n, distance_out, normal_out, item_out, what) || !multihit_args_ok(mode, k, hits_out, what))
         return RT_ERR_INVALID_ARGUMENT;
+    if (ordered && !device_order_ok(order, what)) return RT_ERR_INVALID_ARGUMENT;
     const bool f32 = s->precision == RT_F32;
     if (!(f32 ? query_rays_valid(static_cast<const float *>(rays), static_cast<const float *>(tmax), n)
               : query_rays_valid(static_cast<const double *>(rays), static_cast<const double *>(tmax), n)))
         return RT_ERR_INVALID_ARGUMENT;
+    if (order && !order_is_permutation(order, n, what)) return RT_ERR_INVALID_ARGUMENT;
     HIP_TRY(hipSetDevice(s->device));
     rt_status st = RT_OK;
     // pinned buffers are read and written by the kernel in place, pageable ones go through the call's workspace (as rt_intersect_rays)
     const size_t esz = f32 ? sizeof(float) : sizeof(double), nk = (size_t)n * k;
     struct Buf { void *host; size_t bytes; bool out; uint8_t *dev; size_t off; bool staged; };
-    Buf b[6] = { { const_cast<void *>(rays), 6 * esz * n, false, nullptr, 0, false }, { const_cast<void *>(tmax), esz * n, false, nullptr, 0, false },
+    Buf b[7] = { { const_cast<void *>(rays), 6 * esz * n, false, nullptr, 0, false }, { const_cast<void *>(tmax), esz * n, false, nullptr, 0, false },
                  { distance_out, esz * nk, true, nullptr, 0, false }, { normal_out, 3 * esz * nk, true, nullptr, 0, false },
-                 { item_out, sizeof(int32_t) * nk, true, nullptr, 0, false }, { hits_out, sizeof(uint32_t) * n, true, nullptr, 0, false } };
+                 { item_out, sizeof(int32_t) * nk, true, nullptr, 0, false }, { hits_out, sizeof(uint32_t) * n, true, nullptr, 0, false },
+                 { const_cast<uint32_t *>(order), sizeof(uint32_t) * n, false, nullptr, 0, false } };
     size_t need = 0;
     for (Buf &x : b) {
         if (!x.host) continue;
         const HostDest d = classify_host_pointer(x.host);
         if (d.bad) {
-            snprintf(g_err, sizeof g_err, "rt_intersect_rays_multi: a buffer is device memory; use rt_intersect_rays_multi_device");
+            snprintf(g_err, sizeof g_err, "%s: a buffer is device memory; use %s_device", what, what);
             return RT_ERR_INVALID_ARGUMENT;
         }
         if (d.pinned && d.dev_alias && d.room >= x.bytes) { x.dev = d.dev_alias; continue; }
@@ -886,12 +973,16 @@ rt_status rt_intersect_rays_multi(rt_scene *s, rt_multihit mode, uint32_t k, con
     for (const Buf &x : b)
         if (x.staged && !x.out)
             HIP_DRAIN(hipMemcpyAsync(x.dev, x.host, x.bytes, hipMemcpyHostToDevice, c->stream));
+    const uint32_t *d_order = reinterpret_cast<const uint32_t *>(b[6].dev);
+    if (ordered && !order && (st = enqueue_ray_order(s, c, b[0].dev, n, nullptr, c->stream, &d_order)) != RT_OK) {
+        (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return st;
+    }
     if (stats) {
         HIP_DRAIN(hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, c->stream));
         HIP_DRAIN(hipEventRecord(c->ev0, c->stream));
     }
     st = enqueue_multihit(s, nodes, n_nodes, mode, k, b[0].dev, b[1].dev, n, b[2].dev, b[3].dev, reinterpret_cast<int32_t *>(b[4].dev),
-                          reinterpret_cast<uint32_t *>(b[5].dev), stats ? c->d_counters : nullptr, c->stream);
+                          reinterpret_cast<uint32_t *>(b[5].dev), stats ? c->d_counters : nullptr, c->stream, d_order);
     if (st != RT_OK) { (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return st; }
     if (stats) HIP_DRAIN(hipEventRecord(c->ev1, c->stream));
     for (const Buf &x : b)
@@ -903,49 +994,88 @@ rt_status rt_intersect_rays_multi(rt_scene *s, rt_multihit mode, uint32_t k, con
     return RT_OK;
 }
 
+rt_status rt_intersect_rays_multi(rt_scene *s, rt_multihit mode, uint32_t k, const void *rays, const void *tmax, uint32_t n, void *distance_out,
+                                  void *normal_out, int32_t *item_out, uint32_t *hits_out, rt_stats *stats)
+{
+    return intersect_rays_multi_host(s, mode, k, rays, tmax, n, distance_out, normal_out, item_out, hits_out, false, nullptr, stats, "rt_intersect_rays_multi");
+}
+
+rt_status rt_intersect_rays_multi_ordered(rt_scene *s, rt_multihit mode, uint32_t k, const void *rays, const void *tmax, uint32_t n, const uint32_t *order,
+                                          void *distance_out, void *normal_out, int32_t *item_out, uint32_t *hits_out, rt_stats *stats)
+{
+    return intersect_rays_multi_host(s, mode, k, rays, tmax, n, distance_out, normal_out, item_out, hits_out, true, order, stats,
+                                     "rt_intersect_rays_multi_ordered");
+}
+
 // ---- traced rays and camera frames: Renderer::raytrace for any ray, render_region for any pinhole camera (rt_trace.hpp) ----
 
-rt_status rt_trace_rays_device(rt_scene *s, const void *rays, uint32_t n, void *color_out, void *alpha_out, void *hip_stream, rt_stats *stats)
+static rt_status trace_rays_device(rt_scene *s, const void *rays, uint32_t n, void *color_out, void *alpha_out, bool ordered, const uint32_t *order,
+                                   void *hip_stream, rt_stats *stats, const char *what)
 {
-    if (!trace_args_ok(s, rays, n, color_out, alpha_out, "rt_trace_rays_device")) return RT_ERR_INVALID_ARGUMENT;
+    if (!trace_args_ok(s, rays, n, color_out, alpha_out, what)) return RT_ERR_INVALID_ARGUMENT;
+    if (ordered && !device_order_ok(order, what)) return RT_ERR_INVALID_ARGUMENT;
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     const void *nodes = nullptr;
     uint32_t n_nodes = 0;
     rt_status st = query_stream(s, stream, &nodes, &n_nodes);
     if (st != RT_OK) return st;
-    if (!stats) return enqueue_trace(s, nodes, n_nodes, rays, n, color_out, alpha_out, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, stream);
+    const bool sort = ordered && !order;
+    if (!stats && !sort)
+        return enqueue_trace(s, nodes, n_nodes, rays, n, color_out, alpha_out, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, stream, order);
     Context *c = nullptr;
     if ((st = acquire(s, &c)) != RT_OK) return st;
     Lease lease{ s, c };
-    HIP_TRY(hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, stream));
-    HIP_TRY(hipEventRecord(c->ev0, stream));
-    st = enqueue_trace(s, nodes, n_nodes, rays, n, color_out, alpha_out, nullptr, nullptr, nullptr, 0, 0, nullptr, c->d_counters, stream);
+    if (sort && (st = enqueue_ray_order(s, c, rays, n, nullptr, stream, &order)) != RT_OK) return behind_enqueued(c, lease, stream, st);
+    if (stats) {
+        if (hipError_t e = hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, stream); e != hipSuccess)
+            return sort ? behind_enqueued(c, lease, stream, hip_fail(e, "hipMemsetAsync(counters)", __LINE__)) : hip_fail(e, "hipMemsetAsync(counters)", __LINE__);
+        if (hipError_t e = hipEventRecord(c->ev0, stream); e != hipSuccess)
+            return sort ? behind_enqueued(c, lease, stream, hip_fail(e, "hipEventRecord", __LINE__)) : hip_fail(e, "hipEventRecord", __LINE__);
+    }
+    st = enqueue_trace(s, nodes, n_nodes, rays, n, color_out, alpha_out, nullptr, nullptr, nullptr, 0, 0, nullptr, stats ? c->d_counters : nullptr, stream,
+                       order);
     (void)hipEventRecord(c->ev1, stream);
     if (st != RT_OK) { (void)hipGetLastError(); lease.inflight = true; return st; }      // (the context goes back behind what is enqueued)
-    return read_trace_stats(c, stream, stats);
+    if (stats) return read_trace_stats(c, stream, stats);
+    lease.inflight = true;                              // the order in the workspace is in use until ev1: asynchronous return
+    return RT_OK;
 }
 
-rt_status rt_trace_rays(rt_scene *s, const void *rays, uint32_t n, void *color_out, void *alpha_out, rt_stats *stats)
+rt_status rt_trace_rays_device(rt_scene *s, const void *rays, uint32_t n, void *color_out, void *alpha_out, void *hip_stream, rt_stats *stats)
 {
-    if (!trace_args_ok(s, rays, n, color_out, alpha_out, "rt_trace_rays")) return RT_ERR_INVALID_ARGUMENT;
+    return trace_rays_device(s, rays, n, color_out, alpha_out, false, nullptr, hip_stream, stats, "rt_trace_rays_device");
+}
+
+rt_status rt_trace_rays_ordered_device(rt_scene *s, const void *rays, uint32_t n, const uint32_t *order, void *color_out, void *alpha_out,
+                                       void *hip_stream, rt_stats *stats)
+{
+    return trace_rays_device(s, rays, n, color_out, alpha_out, true, order, hip_stream, stats, "rt_trace_rays_ordered_device");
+}
+
+static rt_status trace_rays_host(rt_scene *s, const void *rays, uint32_t n, void *color_out, void *alpha_out, bool ordered, const uint32_t *order,
+                                 rt_stats *stats, const char *what)
+{
+    if (!trace_args_ok(s, rays, n, color_out, alpha_out, what)) return RT_ERR_INVALID_ARGUMENT;
+    if (ordered && !device_order_ok(order, what)) return RT_ERR_INVALID_ARGUMENT;
     const bool f32 = s->precision == RT_F32;
     if (!(f32 ? query_rays_valid(static_cast<const float *>(rays), static_cast<const float *>(nullptr), n)
               : query_rays_valid(static_cast<const double *>(rays), static_cast<const double *>(nullptr), n)))
         return RT_ERR_INVALID_ARGUMENT;
+    if (order && !order_is_permutation(order, n, what)) return RT_ERR_INVALID_ARGUMENT;
     HIP_TRY(hipSetDevice(s->device));
     rt_status st = RT_OK;
     // pinned buffers are read and written by the kernel in place, pageable ones go through the call's workspace (as rt_intersect_rays)
     const size_t esz = f32 ? sizeof(float) : sizeof(double);
     struct Buf { void *host; size_t bytes; bool out; uint8_t *dev; size_t off; bool staged; };
-    Buf b[3] = { { const_cast<void *>(rays), 6 * esz * n, false, nullptr, 0, false }, { color_out, 3 * esz * n, true, nullptr, 0, false },
-                 { alpha_out, esz * n, true, nullptr, 0, false } };
+    Buf b[4] = { { const_cast<void *>(rays), 6 * esz * n, false, nullptr, 0, false }, { color_out, 3 * esz * n, true, nullptr, 0, false },
+                 { alpha_out, esz * n, true, nullptr, 0, false }, { const_cast<uint32_t *>(order), sizeof(uint32_t) * n, false, nullptr, 0, false } };
     size_t need = 0;
     for (Buf &x : b) {
         if (!x.host) continue;
         const HostDest d = classify_host_pointer(x.host);
         if (d.bad) {
-            snprintf(g_err, sizeof g_err, "rt_trace_rays: a buffer is device memory; use rt_trace_rays_device");
+            snprintf(g_err, sizeof g_err, "%s: a buffer is device memory; use %s_device", what, what);
             return RT_ERR_INVALID_ARGUMENT;
         }
         if (d.pinned && d.dev_alias && d.room >= x.bytes) { x.dev = d.dev_alias; continue; }
@@ -973,12 +1103,19 @@ rt_status rt_trace_rays(rt_scene *s, const void *rays, uint32_t n, void *color_o
         hipError_t e__ = (expr);                                                                                          \
         if (e__ != hipSuccess) { (void)hipStreamSynchronize(c->stream); return hip_fail(e__, #expr, __LINE__); }          \
     } while (0)
-    if (b[0].staged) HIP_DRAIN(hipMemcpyAsync(b[0].dev, b[0].host, b[0].bytes, hipMemcpyHostToDevice, c->stream));
+    for (const Buf &x : b)
+        if (x.staged && !x.out)
+            HIP_DRAIN(hipMemcpyAsync(x.dev, x.host, x.bytes, hipMemcpyHostToDevice, c->stream));
+    const uint32_t *d_order = reinterpret_cast<const uint32_t *>(b[3].dev);
+    if (ordered && !order && (st = enqueue_ray_order(s, c, b[0].dev, n, nullptr, c->stream, &d_order)) != RT_OK) {
+        (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return st;
+    }
     if (stats) {
         HIP_DRAIN(hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, c->stream));
         HIP_DRAIN(hipEventRecord(c->ev0, c->stream));
     }
-    st = enqueue_trace(s, nodes, n_nodes, b[0].dev, n, b[1].dev, b[2].dev, nullptr, nullptr, nullptr, 0, 0, nullptr, stats ? c->d_counters : nullptr, c->stream);
+    st = enqueue_trace(s, nodes, n_nodes, b[0].dev, n, b[1].dev, b[2].dev, nullptr, nullptr, nullptr, 0, 0, nullptr, stats ? c->d_counters : nullptr, c->stream,
+                       d_order);
     if (st != RT_OK) { (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return st; }
     if (stats) HIP_DRAIN(hipEventRecord(c->ev1, c->stream));
     for (const Buf &x : b)
@@ -987,6 +1124,84 @@ rt_status rt_trace_rays(rt_scene *s, const void *rays, uint32_t n, void *color_o
     if (stats) return read_trace_stats(c, c->stream, stats);          // synchronises the stream
     HIP_DRAIN(hipStreamSynchronize(c->stream));
 #undef HIP_DRAIN
+    return RT_OK;
+}
+
+rt_status rt_trace_rays(rt_scene *s, const void *rays, uint32_t n, void *color_out, void *alpha_out, rt_stats *stats)
+{
+    return trace_rays_host(s, rays, n, color_out, alpha_out, false, nullptr, stats, "rt_trace_rays");
+}
+
+rt_status rt_trace_rays_ordered(rt_scene *s, const void *rays, uint32_t n, const uint32_t *order, void *color_out, void *alpha_out, rt_stats *stats)
+{
+    return trace_rays_host(s, rays, n, color_out, alpha_out, true, order, stats, "rt_trace_rays_ordered");
+}
+
+// ---- coherent ray batches: the order the *_ordered entries take, computed on the device (rt_order.hpp) ----
+
+rt_status rt_ray_order_device(rt_scene *s, const void *rays, uint32_t n, uint32_t *order_out, void *hip_stream)
+{
+    if (!order_args_ok(s, rays, n, order_out, "rt_ray_order_device")) return RT_ERR_INVALID_ARGUMENT;
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    Context *c = nullptr;
+    rt_status st = acquire(s, &c);
+    if (st != RT_OK) return st;
+    Lease lease{ s, c };
+    const uint32_t *used = nullptr;
+    st = enqueue_ray_order(s, c, rays, n, order_out, stream, &used);
+    (void)hipEventRecord(c->ev1, stream);               // (the context goes back behind what is enqueued: its workspace is in use until then)
+    if (st != RT_OK) (void)hipGetLastError();
+    lease.inflight = true;
+    return st;
+}
+
+rt_status rt_ray_order(rt_scene *s, const void *rays, uint32_t n, uint32_t *order_out)
+{
+    if (!order_args_ok(s, rays, n, order_out, "rt_ray_order")) return RT_ERR_INVALID_ARGUMENT;
+    const bool f32 = s->precision == RT_F32;
+    if (!(f32 ? query_rays_valid(static_cast<const float *>(rays), static_cast<const float *>(nullptr), n)
+              : query_rays_valid(static_cast<const double *>(rays), static_cast<const double *>(nullptr), n)))
+        return RT_ERR_INVALID_ARGUMENT;
+    HIP_TRY(hipSetDevice(s->device));
+    // pinned buffers are read and written by the kernels in place, pageable ones go through the call's workspace (as rt_intersect_rays)
+    const size_t esz = f32 ? sizeof(float) : sizeof(double);
+    struct Buf { void *host; size_t bytes; bool out; uint8_t *dev; size_t off; bool staged; };
+    Buf b[2] = { { const_cast<void *>(rays), 6 * esz * n, false, nullptr, 0, false }, { order_out, sizeof(uint32_t) * n, true, nullptr, 0, false } };
+    size_t need = 0;
+    for (Buf &x : b) {
+        const HostDest d = classify_host_pointer(x.host);
+        if (d.bad) {
+            snprintf(g_err, sizeof g_err, "rt_ray_order: a buffer is device memory; use rt_ray_order_device");
+            return RT_ERR_INVALID_ARGUMENT;
+        }
+        if (d.pinned && d.dev_alias && d.room >= x.bytes) { x.dev = d.dev_alias; continue; }
+        x.staged = true;
+        x.off = need;
+        need += (x.bytes + 255) & ~(size_t)255;
+    }
+    Context *c = nullptr;
+    rt_status st = acquire(s, &c);
+    if (st != RT_OK) return st;
+    Lease lease{ s, c };
+    if (need > c->query_cap) {
+        if (c->d_query) HIP_TRY(hipFree(c->d_query));
+        c->d_query = nullptr; c->query_cap = 0;
+        HIP_TRY(hipMalloc(&c->d_query, need));
+        c->query_cap = need;
+    }
+    for (Buf &x : b)
+        if (x.staged) x.dev = static_cast<uint8_t *>(c->d_query) + x.off;
+    // from the first copy on, work of this call may be queued: an error return first waits for it
+    auto drain = [&](rt_status code) { (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return code; };
+    hipError_t e = hipSuccess;
+    if (b[0].staged && (e = hipMemcpyAsync(b[0].dev, b[0].host, b[0].bytes, hipMemcpyHostToDevice, c->stream)) != hipSuccess)
+        return drain(hip_fail(e, "hipMemcpyAsync", __LINE__));
+    const uint32_t *used = nullptr;
+    if ((st = enqueue_ray_order(s, c, b[0].dev, n, reinterpret_cast<uint32_t *>(b[1].dev), c->stream, &used)) != RT_OK) return drain(st);
+    if (b[1].staged && (e = hipMemcpyAsync(b[1].host, b[1].dev, b[1].bytes, hipMemcpyDeviceToHost, c->stream)) != hipSuccess)
+        return drain(hip_fail(e, "hipMemcpyAsync", __LINE__));
+    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize", __LINE__);
     return RT_OK;
 }
 

@@ -647,13 +647,21 @@ bool query_rays_valid(const T *rays, const T *tmax, uint32_t n)
 // One query launch on `stream`: counters != NULL runs the counting flavour (same bytes).
 template <typename T>
 rt_status enqueue_query(const rt_scene *s, const void *nodes, uint32_t n_nodes, rt_query mode, const void *rays, const void *tmax, uint32_t n,
-                        void *dist, void *normal, int32_t *item, rt::Counters *counters, hipStream_t stream)
+                        void *dist, void *normal, int32_t *item, rt::Counters *counters, hipStream_t stream, const uint32_t *order)
 {
     const rt::QueryArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), static_cast<const rt::Item<T> *>(s->d_items), static_cast<const T *>(rays),
                               static_cast<const T *>(tmax), static_cast<T *>(dist), static_cast<T *>(normal), item, counters, n_nodes, n };
     const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
     const bool any = mode == RT_QUERY_ANY;
-    if (counters) {
+    if (order) {                                                     // the rays in a given order (rt_order.hpp): the same walk, ray order[j] in lane j
+        if (counters) {
+            if (any) hipLaunchKernelGGL((rt::k_query_rays_ordered<T, true, true>), grid, block, 0, stream, a, order);
+            else hipLaunchKernelGGL((rt::k_query_rays_ordered<T, true, false>), grid, block, 0, stream, a, order);
+        } else {
+            if (any) hipLaunchKernelGGL((rt::k_query_rays_ordered<T, false, true>), grid, block, 0, stream, a, order);
+            else hipLaunchKernelGGL((rt::k_query_rays_ordered<T, false, false>), grid, block, 0, stream, a, order);
+        }
+    } else if (counters) {
         if (any) hipLaunchKernelGGL((rt::k_query_rays<T, true, true>), grid, block, 0, stream, a);
         else hipLaunchKernelGGL((rt::k_query_rays<T, true, false>), grid, block, 0, stream, a);
     } else {
@@ -665,10 +673,10 @@ rt_status enqueue_query(const rt_scene *s, const void *nodes, uint32_t n_nodes, 
 }
 
 rt_status enqueue_query(const rt_scene *s, const void *nodes, uint32_t n_nodes, rt_query mode, const void *rays, const void *tmax, uint32_t n,
-                        void *dist, void *normal, int32_t *item, rt::Counters *counters, hipStream_t stream)
+                        void *dist, void *normal, int32_t *item, rt::Counters *counters, hipStream_t stream, const uint32_t *order = nullptr)
 {
-    return s->precision == RT_F32 ? enqueue_query<float>(s, nodes, n_nodes, mode, rays, tmax, n, dist, normal, item, counters, stream)
-                                  : enqueue_query<double>(s, nodes, n_nodes, mode, rays, tmax, n, dist, normal, item, counters, stream);
+    return s->precision == RT_F32 ? enqueue_query<float>(s, nodes, n_nodes, mode, rays, tmax, n, dist, normal, item, counters, stream, order)
+                                  : enqueue_query<double>(s, nodes, n_nodes, mode, rays, tmax, n, dist, normal, item, counters, stream, order);
 }
 
 // A counting query's rt_stats: primary = rays, hits = results below tmax, the tests; every other counter 0.  Synchronises `stream`.
@@ -702,8 +710,17 @@ bool multihit_args_ok(rt_multihit mode, uint32_t k, const uint32_t *hits, const 
 }
 
 template <typename T, bool COUNT, bool ALL>
-void launch_multihit(unsigned bucket, dim3 grid, dim3 block, hipStream_t stream, const rt::MultiArgs<T> &a)
+void launch_multihit(unsigned bucket, dim3 grid, dim3 block, hipStream_t stream, const rt::MultiArgs<T> &a, const uint32_t *order)
 {
+    if (order) {                                                     // the rays in a given order (rt_order.hpp)
+        switch (bucket) {
+        case 1: hipLaunchKernelGGL((rt::k_multihit_rays_ordered<T, COUNT, ALL, 1>), grid, block, 0, stream, a, order); break;
+        case 4: hipLaunchKernelGGL((rt::k_multihit_rays_ordered<T, COUNT, ALL, 4>), grid, block, 0, stream, a, order); break;
+        case 8: hipLaunchKernelGGL((rt::k_multihit_rays_ordered<T, COUNT, ALL, 8>), grid, block, 0, stream, a, order); break;
+        default: hipLaunchKernelGGL((rt::k_multihit_rays_ordered<T, COUNT, ALL, 16>), grid, block, 0, stream, a, order); break;
+        }
+        return;
+    }
     switch (bucket) {
     case 1: hipLaunchKernelGGL((rt::k_multihit_rays<T, COUNT, ALL, 1>), grid, block, 0, stream, a); break;
     case 4: hipLaunchKernelGGL((rt::k_multihit_rays<T, COUNT, ALL, 4>), grid, block, 0, stream, a); break;
@@ -716,7 +733,8 @@ void launch_multihit(unsigned bucket, dim3 grid, dim3 block, hipStream_t stream,
 // != NULL runs the counting flavour (same bytes).
 template <typename T>
 rt_status enqueue_multihit(const rt_scene *s, const void *nodes, uint32_t n_nodes, rt_multihit mode, uint32_t k, const void *rays, const void *tmax,
-                           uint32_t n, void *dist, void *normal, int32_t *item, uint32_t *hits, rt::Counters *counters, hipStream_t stream)
+                           uint32_t n, void *dist, void *normal, int32_t *item, uint32_t *hits, rt::Counters *counters, hipStream_t stream,
+                           const uint32_t *order)
 {
     const rt::MultiArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), static_cast<const rt::Item<T> *>(s->d_items), static_cast<const T *>(rays),
                               static_cast<const T *>(tmax), static_cast<T *>(dist), static_cast<T *>(normal), item, hits, counters, n_nodes, n, k };
@@ -729,21 +747,22 @@ rt_status enqueue_multihit(const rt_scene *s, const void *nodes, uint32_t n_node
     const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
     const bool all = mode == RT_MULTIHIT_ALL;
     if (counters) {
-        if (all) launch_multihit<T, true, true>(bucket, grid, block, stream, a);
-        else launch_multihit<T, true, false>(bucket, grid, block, stream, a);
+        if (all) launch_multihit<T, true, true>(bucket, grid, block, stream, a, order);
+        else launch_multihit<T, true, false>(bucket, grid, block, stream, a, order);
     } else {
-        if (all) launch_multihit<T, false, true>(bucket, grid, block, stream, a);
-        else launch_multihit<T, false, false>(bucket, grid, block, stream, a);
+        if (all) launch_multihit<T, false, true>(bucket, grid, block, stream, a, order);
+        else launch_multihit<T, false, false>(bucket, grid, block, stream, a, order);
     }
     HIP_TRY(hipGetLastError());
     return RT_OK;
 }
 
 rt_status enqueue_multihit(const rt_scene *s, const void *nodes, uint32_t n_nodes, rt_multihit mode, uint32_t k, const void *rays, const void *tmax,
-                           uint32_t n, void *dist, void *normal, int32_t *item, uint32_t *hits, rt::Counters *counters, hipStream_t stream)
+                           uint32_t n, void *dist, void *normal, int32_t *item, uint32_t *hits, rt::Counters *counters, hipStream_t stream,
+                           const uint32_t *order = nullptr)
 {
-    return s->precision == RT_F32 ? enqueue_multihit<float>(s, nodes, n_nodes, mode, k, rays, tmax, n, dist, normal, item, hits, counters, stream)
-                                  : enqueue_multihit<double>(s, nodes, n_nodes, mode, k, rays, tmax, n, dist, normal, item, hits, counters, stream);
+    return s->precision == RT_F32 ? enqueue_multihit<float>(s, nodes, n_nodes, mode, k, rays, tmax, n, dist, normal, item, hits, counters, stream, order)
+                                  : enqueue_multihit<double>(s, nodes, n_nodes, mode, k, rays, tmax, n, dist, normal, item, hits, counters, stream, order);
 }
 
 // ---- traced rays and camera frames (rt_trace_rays*, rt_render_camera*, rt_trace.hpp) ----
@@ -802,7 +821,7 @@ bool trace_args_ok(const rt_scene *s, const void *rays, uint32_t n, const void *
 template <typename T>
 rt_status enqueue_trace(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *rays, uint32_t n, void *color, void *alpha,
                         const rt_options *o, const void *cam, const rt::TileDev *d_tab, uint32_t n_tiles, uint32_t blocks, uint8_t *d_out,
-                        rt::Counters *counters, hipStream_t stream)
+                        rt::Counters *counters, hipStream_t stream, const uint32_t *order)
 {
     rt::TraceArgs<T> a{};
     a.stream = static_cast<const rt::Node<T> *>(nodes);
@@ -819,7 +838,10 @@ rt_status enqueue_trace(const rt_scene *s, const void *nodes, uint32_t n_nodes, 
     if (rays) {
         a.n = n;
         const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
-        if (counters) hipLaunchKernelGGL((rt::k_trace_rays<T, true, rt::kTraceRays>), grid, block, 0, stream, a);
+        if (order) {                                                 // the rays in a given order (rt_order.hpp)
+            if (counters) hipLaunchKernelGGL((rt::k_trace_rays_ordered<T, true>), grid, block, 0, stream, a, order);
+            else hipLaunchKernelGGL((rt::k_trace_rays_ordered<T, false>), grid, block, 0, stream, a, order);
+        } else if (counters) hipLaunchKernelGGL((rt::k_trace_rays<T, true, rt::kTraceRays>), grid, block, 0, stream, a);
         else hipLaunchKernelGGL((rt::k_trace_rays<T, false, rt::kTraceRays>), grid, block, 0, stream, a);
     } else {
         a.n = n_tiles;
@@ -834,10 +856,10 @@ rt_status enqueue_trace(const rt_scene *s, const void *nodes, uint32_t n_nodes, 
 
 rt_status enqueue_trace(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *rays, uint32_t n, void *color, void *alpha,
                         const rt_options *o, const void *cam, const rt::TileDev *d_tab, uint32_t n_tiles, uint32_t blocks, uint8_t *d_out,
-                        rt::Counters *counters, hipStream_t stream)
+                        rt::Counters *counters, hipStream_t stream, const uint32_t *order = nullptr)
 {
-    return s->precision == RT_F32 ? enqueue_trace<float>(s, nodes, n_nodes, rays, n, color, alpha, o, cam, d_tab, n_tiles, blocks, d_out, counters, stream)
-                                  : enqueue_trace<double>(s, nodes, n_nodes, rays, n, color, alpha, o, cam, d_tab, n_tiles, blocks, d_out, counters, stream);
+    return s->precision == RT_F32 ? enqueue_trace<float>(s, nodes, n_nodes, rays, n, color, alpha, o, cam, d_tab, n_tiles, blocks, d_out, counters, stream, order)
+                                  : enqueue_trace<double>(s, nodes, n_nodes, rays, n, color, alpha, o, cam, d_tab, n_tiles, blocks, d_out, counters, stream, order);
 }
 
 // A counting trace's rt_stats: primary = rays or samples, hits / shadow / occluded as the render counts them, the walks' tests and the
@@ -859,6 +881,102 @@ rt_status read_trace_stats(Context *c, hipStream_t stream, rt_stats *st)
     st->sphere_tests = h.sphere_tests; st->bound_tests = h.bound_tests; st->tests_executed = h.sphere_tests + h.bound_tests;
     st->primary_tests = h.primary_tests;
     st->device_ms = ms;
+    return RT_OK;
+}
+
+// ---- coherent ray batches (rt_ray_order*, rt_*_ordered*; rt_order.hpp) ----
+
+// Where the pieces of a sort of n rays lie in a context's d_sort.  The head (digit totals, plan, box) is what one memset clears.
+struct SortLayout {
+    unsigned per_block = 0, n_blocks = 0;
+    size_t totals = 0, plan = 0, box = 0, head_bytes = 0, table = 0, keys[2] = { 0, 0 }, idx[2] = { 0, 0 }, order = 0, bytes = 0;
+};
+
+SortLayout sort_layout(uint32_t n)
+{
+    SortLayout l;
+    uint64_t per = ((uint64_t)n + rt::kSortMaxBlocks - 1) / rt::kSortMaxBlocks;
+    per = std::max<uint64_t>(per, rt::kSortTile);
+    per = (per + rt::kSortThreads - 1) / rt::kSortThreads * rt::kSortThreads;
+    l.per_block = (unsigned)per;
+    l.n_blocks = (unsigned)(((uint64_t)n + per - 1) / per);
+    auto take = [&](size_t bytes) { const size_t at = l.bytes; l.bytes += (bytes + 255) & ~(size_t)255; return at; };
+    l.totals = take(4 * 256 * sizeof(unsigned));
+    l.plan = take(sizeof(rt::SortPlan));
+    l.box = take(sizeof(rt::RayBox));
+    l.head_bytes = l.bytes;
+    l.table = take((size_t)256 * l.n_blocks * sizeof(unsigned));
+    for (int k = 0; k < 2; ++k) l.keys[k] = take((size_t)n * sizeof(unsigned));
+    for (int k = 0; k < 2; ++k) l.idx[k] = take((size_t)n * sizeof(unsigned));
+    l.order = take((size_t)n * sizeof(unsigned));
+    return l;
+}
+
+// rays and order_out as both rt_ray_order entries check them (device pointers are not dereferenced here).
+bool order_args_ok(const rt_scene *s, const void *rays, uint32_t n, const uint32_t *order_out, const char *what)
+{
+    if (!s || !rays || !order_out || n == 0) { snprintf(g_err, sizeof g_err, "%s: NULL scene, rays or order_out, or n == 0", what); return false; }
+    const uintptr_t esz = s->precision == RT_F32 ? sizeof(float) : sizeof(double);
+    if ((reinterpret_cast<uintptr_t>(rays) % esz) != 0) { snprintf(g_err, sizeof g_err, "%s: REAL buffers must be %u-byte aligned", what, (unsigned)esz); return false; }
+    if ((reinterpret_cast<uintptr_t>(order_out) & 3u) != 0) { snprintf(g_err, sizeof g_err, "%s: order_out must be 4-byte aligned", what); return false; }
+    return true;
+}
+
+// A host order must be a permutation of 0 .. n-1.
+bool order_is_permutation(const uint32_t *order, uint32_t n, const char *what)
+{
+    std::vector<bool> seen;
+    try { seen.assign(n, false); } catch (const std::exception &) { snprintf(g_err, sizeof g_err, "%s: out of memory checking the order", what); return false; }
+    for (uint32_t j = 0; j < n; ++j) {
+        if (order[j] >= n || seen[order[j]]) {
+            snprintf(g_err, sizeof g_err, "%s: order[%u] = %u is %s: the order must be a permutation of 0 .. n-1", what, j, order[j],
+                     order[j] >= n ? "out of range" : "repeated");
+            return false;
+        }
+        seen[order[j]] = true;
+    }
+    return true;
+}
+
+// The order of n device rays on `stream`, through the context's sort workspace (grown on demand: the context is leased, nothing that is
+// enqueued uses it).  order_out: device memory, or NULL for the workspace's own slot; *order_used is where the order ends up.
+rt_status enqueue_ray_order(const rt_scene *s, Context *c, const void *rays, uint32_t n, uint32_t *order_out, hipStream_t stream, const uint32_t **order_used)
+{
+    const SortLayout l = sort_layout(n);
+    if (c->sort_cap < l.bytes) {
+        if (c->d_sort) HIP_TRY(hipFree(c->d_sort));
+        c->d_sort = nullptr; c->sort_cap = 0;
+        HIP_TRY(hipMalloc(&c->d_sort, l.bytes));
+        c->sort_cap = l.bytes;
+    }
+    uint8_t *const w = static_cast<uint8_t *>(c->d_sort);
+    rt::SortArgs a{};
+    for (int k = 0; k < 2; ++k) { a.keys[k] = reinterpret_cast<unsigned *>(w + l.keys[k]); a.idx[k] = reinterpret_cast<unsigned *>(w + l.idx[k]); }
+    a.table = reinterpret_cast<unsigned *>(w + l.table);
+    rt::SortPlan *const plan = reinterpret_cast<rt::SortPlan *>(w + l.plan);
+    a.plan = plan;
+    a.order_out = order_out ? order_out : reinterpret_cast<unsigned *>(w + l.order);
+    a.n = n; a.per_block = l.per_block; a.n_blocks = l.n_blocks;
+    unsigned *const totals = reinterpret_cast<unsigned *>(w + l.totals);
+    a.totals = totals;
+    rt::RayBox *const box = reinterpret_cast<rt::RayBox *>(w + l.box);
+    HIP_TRY(hipMemsetAsync(w, 0, l.head_bytes, stream));
+    const dim3 wide((unsigned)std::min<uint64_t>(((uint64_t)n + rt::kSortThreads - 1) / rt::kSortThreads, rt::kSortMaxBlocks)), block(rt::kSortThreads);
+    if (s->precision == RT_F32) {
+        hipLaunchKernelGGL(rt::k_ray_box<float>, wide, block, 0, stream, static_cast<const float *>(rays), n, box);
+        hipLaunchKernelGGL(rt::k_ray_keys<float>, wide, block, 0, stream, static_cast<const float *>(rays), n, box, a.keys[0], totals);
+    } else {
+        hipLaunchKernelGGL(rt::k_ray_box<double>, wide, block, 0, stream, static_cast<const double *>(rays), n, box);
+        hipLaunchKernelGGL(rt::k_ray_keys<double>, wide, block, 0, stream, static_cast<const double *>(rays), n, box, a.keys[0], totals);
+    }
+    hipLaunchKernelGGL(rt::k_sort_plan, dim3(1), block, 0, stream, totals, n, plan);
+    for (unsigned pass = 0; pass < 4; ++pass) {
+        hipLaunchKernelGGL(rt::k_sort_hist, dim3(l.n_blocks), block, 0, stream, a, pass);
+        hipLaunchKernelGGL(rt::k_sort_scan, dim3(256), block, 0, stream, a, pass);
+        hipLaunchKernelGGL(rt::k_sort_scatter, dim3(l.n_blocks), block, 0, stream, a, pass);
+    }
+    HIP_TRY(hipGetLastError());
+    *order_used = a.order_out;
     return RT_OK;
 }
 

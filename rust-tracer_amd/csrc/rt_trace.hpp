@@ -252,4 +252,51 @@ __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(C
     }
 }
 
+// k_trace_rays<T, COUNT, kTraceRays> with the rays taken in a given order (rt_trace_rays_ordered*; rt_order.hpp): thread j
+// carries ray order[j] -- it reads that ray and writes its colour and alpha at that index; an order[j] >= n carries no ray.
+template <typename T, bool COUNT>
+__global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(COUNT ? 4 : 8))) void k_trace_rays_ordered(TraceArgs<T> a, const uint32_t *order)
+{
+    TraceCounts c;
+    unsigned rays_here = 0;
+    const unsigned gid = blockIdx.x * kBlockThreads + threadIdx.x;
+    bool live = gid < a.n;
+    size_t k = 0u;
+    if (live) {
+        const unsigned q = order[gid];
+        live = q < a.n;
+        k = live ? q : 0u;
+    }
+    V3<T> o = { T(0.0), T(0.0), T(0.0) }, d = { T(0.0), T(0.0), T(0.0) };
+    if (live) {
+        const T *r = a.rays + 6 * k;
+        o = { r[0], r[1], r[2] };
+        d = { r[3], r[4], r[5] };
+    }
+    T gdot;
+    const uint8_t state = trace_ray<T, COUNT>(a, o, d, live, gdot, c);
+    if (live) {
+        V3<T> g = { T(0.0), T(0.0), T(0.0) };
+        const T alpha = accumulate(g, state, gdot);
+        T *p = a.color + 3 * k;
+        p[0] = g.x; p[1] = g.y; p[2] = g.z;
+        if (a.alpha) a.alpha[k] = alpha;
+        rays_here = 1;
+    }
+    if constexpr (COUNT) {
+        const unsigned long long prim = wave_sum(rays_here), hits = wave_sum(c.hits), sh = wave_sum(c.shadow), oc = wave_sum(c.occ);
+        const unsigned long long its = wave_sum(c.items), bds = wave_sum(c.bounds), ptot = wave_sum(c.ptests);
+        if ((threadIdx.x & 63u) == 0u) {
+            Counters *const stripe = a.counters + blockIdx.x % kCounterStripes;
+            atomicAdd(&stripe->primary, prim);
+            atomicAdd(&stripe->hits, hits);
+            atomicAdd(&stripe->shadow, sh);
+            atomicAdd(&stripe->occluded, oc);
+            atomicAdd(&stripe->sphere_tests, its);
+            atomicAdd(&stripe->bound_tests, bds);
+            atomicAdd(&stripe->primary_tests, ptot);
+        }
+    }
+}
+
 }  // namespace rt

@@ -26,6 +26,38 @@ def _tmax_array(tmax, R, n):
     return np.ascontiguousarray(np.broadcast_to(t.reshape(-1), (n,)))
 
 
+def ray_keys(rays):
+    """The 32-bit sort key rt_ray_order gives each ray of `rays` (n x 6: pos.xyz, dir.xyz; float32 or float64) -> uint32[n], restated in numpy
+    operation for operation (include/rtrace_hip.h states it): rt_ray_order's order is np.argsort(ray_keys(rays), kind="stable").  High 9
+    bits: the Morton code of the origin's cell in the batch's own origin box (8 cells per axis; all 0 for a batch with one origin); then 3
+    bits for the direction's dominant axis and its sign; low 20 bits: the Morton code of the two other direction components, 10 bits each."""
+    r = np.asarray(rays)
+    if r.ndim != 2 or r.shape[1] != 6 or r.shape[0] == 0 or r.dtype not in (np.float32, np.float64):
+        raise ValueError("rays must be a non-empty (n, 6) array of float32 or float64")
+    r = r.astype(np.float64)                                             # exact
+    pos, d = r[:, :3], r[:, 3:]
+    lo, hi = pos.min(axis=0), pos.max(axis=0)
+    ext = np.float64((hi - lo).max())
+    scale = np.float64(0.0)
+    if ext > 0.0:
+        e = max((int(ext.view(np.uint64)) >> 52 & 0x7FF) - 1022, -1000)   # ext < 2^e
+        scale = np.ldexp(np.float64(1.0), 3 - e)
+    c = np.minimum(np.maximum((pos - lo) * scale, 0.0), 7.0).astype(np.uint32)
+    axis = np.argmax(np.abs(d), axis=1)                                  # the first of equal maxima
+    rows = np.arange(len(d))
+    sign = (d[rows, axis] < 0.0).astype(np.uint32)
+    q = [np.minimum(np.maximum((d[rows, (axis + 1 + b) % 3] + 1.0) * 512.0, 0.0), 1023.0).astype(np.uint32) for b in (0, 1)]
+    m3 = np.zeros(len(d), dtype=np.uint32)
+    for i in range(3):
+        for a in range(3):
+            m3 |= ((c[:, a] >> np.uint32(i)) & np.uint32(1)) << np.uint32(3 * i + a)
+    m2 = np.zeros(len(d), dtype=np.uint32)
+    for i in range(10):
+        for b in range(2):
+            m2 |= ((q[b] >> np.uint32(i)) & np.uint32(1)) << np.uint32(2 * i + b)
+    return (m3 << np.uint32(23)) | ((np.uint32(2) * axis.astype(np.uint32) + sign) << np.uint32(20)) | m2
+
+
 def pyramid(level, origin, radius, precision=capi.RT_F32):
     """SphericalGroup::pyramid (group.rs:58-65) -> (items REAL[n,4], bounds REAL[g,4], ranges int32[g,2]).
 
@@ -437,34 +469,96 @@ class DeviceScene:
         capi.check(rc, "rt_render_frame_device")
         return st.as_dict() if want_stats else None
 
-    def intersect(self, rays, tmax=None, any_hit=False, want_stats=False, stream=None, out=None):
+    def intersect(self, rays, tmax=None, any_hit=False, want_stats=False, stream=None, out=None, order=None):
         """rt_intersect_rays / rt_intersect_rays_device: TypedGroup::intersect for every ray of `rays` (n x 6: pos.xyz, dir.xyz, the scene's REAL
         dtype) -> (distance[n], normal[n, 3], item[n] (DFS index or -1)[, stats dict]).  tmax: hit.distance going in, per ray (an array of
         the scene's REAL) or one value (rounded to REAL; None: +inf).  any_hit: occlusion -- the first item closer than tmax instead of the nearest.
         A numpy array goes through the host entry and gets numpy results (out: optional (distance, normal, item) arrays to fill, e.g. from
         capi.HostBuffer, which the kernel then writes directly); a torch tensor on this scene's device goes through the device entry on
         `stream` (a torch stream or a hipStream_t as int; default the current torch stream) and gets torch tensors on that device: the
-        query waits for the work queued on the current torch stream, and its results belong to `stream` (use them there, or synchronise)."""
+        query waits for the work queued on the current torch stream, and its results belong to `stream` (use them there, or synchronise).
+        order (rt_intersect_rays_ordered*): None -- the rays are walked as they are stored; True -- the call orders them on the device first
+        (ray_order) and walks in that order; or an index array / tensor (uint32[n], a permutation: lane j carries ray order[j]).  The results
+        and counters are the same bytes whatever the order; only the time differs."""
         mode = capi.RT_QUERY_ANY if any_hit else capi.RT_QUERY_NEAREST
         return self._ray_query("rt_intersect_rays", lambda f, r, t, n, *rest: f(self._h, mode, r, t, n, *rest),
-                               (((), "R"), ((3,), "R"), ((), np.int32)), rays, tmax, want_stats, stream, out)
+                               (((), "R"), ((3,), "R"), ((), np.int32)), rays, tmax, want_stats, stream, out, order)
 
-    def intersect_multi(self, rays, k, tmax=None, all_hits=False, want_stats=False, stream=None, out=None):
+    def intersect_multi(self, rays, k, tmax=None, all_hits=False, want_stats=False, stream=None, out=None, order=None):
         """rt_intersect_rays_multi / rt_intersect_rays_multi_device: the k closest hits of every ray, nearest first, equal distances in DFS
         order -> (distance[n, k], normal[n, k, 3], item[n, k] (DFS index or -1), hits[n] (uint32)[, stats dict]).  An empty slot reads tmax,
         -1 and (0, 0, 0).  all_hits=False (RT_MULTIHIT_CLOSEST): hits = the filled slots; with k = 1 this is intersect() exactly.
         all_hits=True (RT_MULTIHIT_ALL): no culling below tmax, hits = every item below tmax (may exceed k), the list its k closest.
-        1 <= k <= RT_MULTIHIT_MAX_K.  rays, tmax, stream and out (here (distance, normal, item, hits)) as for intersect()."""
+        1 <= k <= RT_MULTIHIT_MAX_K.  rays, tmax, stream, order and out (here (distance, normal, item, hits)) as for intersect()."""
         k = int(k)
         if not 1 <= k <= capi.RT_MULTIHIT_MAX_K:
             raise ValueError("k must be 1 .. %d, not %d" % (capi.RT_MULTIHIT_MAX_K, k))
         mode = capi.RT_MULTIHIT_ALL if all_hits else capi.RT_MULTIHIT_CLOSEST
         return self._ray_query("rt_intersect_rays_multi", lambda f, r, t, n, *rest: f(self._h, mode, k, r, t, n, *rest),
-                               (((k,), "R"), ((k, 3), "R"), ((k,), np.int32), ((), np.uint32)), rays, tmax, want_stats, stream, out)
+                               (((k,), "R"), ((k, 3), "R"), ((k,), np.int32), ((), np.uint32)), rays, tmax, want_stats, stream, out, order)
 
-    def _ray_query(self, entry, call, results, rays, tmax, want_stats, stream, out):
+    @staticmethod
+    def _order_numpy(order, n):
+        """An index array for a host entry: contiguous uint32[n] (whether it is a permutation is the library's check)."""
+        o = np.asarray(order)
+        if o.dtype.kind not in "iu" or o.shape != (n,):
+            raise ValueError("order must be None, True or an (n,) integer array")
+        if o.dtype != np.uint32 and n and (int(o.min()) < 0 or int(o.max()) > 0xFFFFFFFF):      # (the cast below would wrap it into range)
+            raise ValueError("order holds an index outside 0 .. 2^32 - 1")
+        return np.ascontiguousarray(o, dtype=np.uint32)
+
+    @staticmethod
+    def _order_torch(torch, order, n, dev):
+        """An index tensor for a device entry: contiguous uint32 / int32 [n] on the scene's device."""
+        if not isinstance(order, torch.Tensor) or order.dtype not in (torch.uint32, torch.int32) or order.shape != (n,) or order.device != dev:
+            raise ValueError("order must be None, True or an (n,) uint32 / int32 tensor on %s" % dev)
+        return order.contiguous()
+
+    def ray_order(self, rays, stream=None):
+        """rt_ray_order / rt_ray_order_device: the coherent order of `rays` (n x 6, the scene's REAL dtype), computed on the device -> uint32[n],
+        order[j] = the ray lane j should carry: np.argsort(ray_keys(rays), kind="stable").  numpy in, numpy out; a torch tensor on this
+        scene's device goes through the device entry on `stream` (as intersect() routes) and gives a torch.uint32 tensor."""
+        R = _real(self.scene.precision)
+        torch = sys.modules.get("torch")
+        if torch is not None and isinstance(rays, torch.Tensor):
+            tdt = torch.float32 if R == np.float32 else torch.float64
+            dev = torch.device("cuda", self.device)
+            if rays.dtype != tdt or rays.dim() != 2 or rays.shape[1] != 6 or rays.shape[0] == 0:
+                raise ValueError("rays must be a non-empty (n, 6) %s tensor" % tdt)
+            if rays.device != dev:
+                raise ValueError("rays must be on %s, not %s" % (dev, rays.device))
+            n = rays.shape[0]
+            cur = torch.cuda.current_stream(dev)
+            if stream is None:
+                qs = cur
+            elif isinstance(stream, torch.cuda.Stream):
+                qs = stream
+            else:
+                h = int(stream)
+                qs = torch.cuda.default_stream(dev) if h == 0 else torch.cuda.ExternalStream(h, device=dev)
+            if qs != cur:
+                qs.wait_stream(cur)
+            with torch.cuda.stream(qs):
+                r = rays.contiguous()
+                order = torch.empty(n, dtype=torch.uint32, device=dev)
+                rc = capi.lib.rt_ray_order_device(self._h, C.c_void_p(r.data_ptr()), n, C.c_void_p(order.data_ptr()), C.c_void_p(qs.cuda_stream))
+            if qs != cur:
+                rays.record_stream(qs)
+            capi.check(rc, "rt_ray_order_device")
+            return order
+        if not isinstance(rays, np.ndarray) or rays.dtype != R or rays.ndim != 2 or rays.shape[1] != 6 or rays.shape[0] == 0:
+            raise ValueError("rays must be a non-empty (n, 6) numpy array of %s (or a torch tensor on the scene's device)" % np.dtype(R).name)
+        rays = np.ascontiguousarray(rays)
+        order = np.empty(rays.shape[0], dtype=np.uint32)
+        capi.check(capi.lib.rt_ray_order(self._h, rays.ctypes.data, rays.shape[0], order.ctypes.data), "rt_ray_order")
+        return order
+
+    def _ray_query(self, entry, call, results, rays, tmax, want_stats, stream, out, order=None):
         """The body every ray query shares: checks rays and tmax, makes the results -- (shape behind n, dtype) each, "R" for the scene's
-        REAL -- and calls `entry` (numpy) or `entry`_device (torch) as call(f, rays, tmax, n, *result pointers[, stream], stats)."""
+        REAL -- and calls `entry` (numpy) or `entry`_device (torch) as call(f, rays, tmax, n, *result pointers[, stream], stats).  With an
+        order (True or indices) it is `entry`_ordered[_device], whose order pointer (NULL for True) follows n."""
+        if order is not None:
+            entry += "_ordered"
         R = _real(self.scene.precision)
         st = capi.Stats()
         stp = C.byref(st) if want_stats else None
@@ -506,10 +600,15 @@ class DeviceScene:
                 elif tmax is not None:
                     t = torch.from_numpy(tmax).to(dev)
                 res = tuple(torch.empty((n,) + shape, dtype=tdts[dt], device=dev) for shape, dt in results)
+                ordp = ()
+                if order is not None:
+                    if order is not True:
+                        order = self._order_torch(torch, order, n, dev)
+                    ordp = (None if order is True else C.c_void_p(order.data_ptr()),)
                 rc = call(getattr(capi.lib, entry + "_device"), C.c_void_p(r.data_ptr()), C.c_void_p(t.data_ptr()) if t is not None else None, n,
-                          *[C.c_void_p(x.data_ptr()) for x in res], C.c_void_p(qs.cuda_stream), stp)
+                          *ordp, *[C.c_void_p(x.data_ptr()) for x in res], C.c_void_p(qs.cuda_stream), stp)
             if qs != cur:
-                for x in (rays, tmax):
+                for x in (rays, tmax, order):
                     if isinstance(x, torch.Tensor) and x.is_cuda:
                         x.record_stream(qs)
             capi.check(rc, entry + "_device")
@@ -526,7 +625,11 @@ class DeviceScene:
                 res = tuple(out)
                 if len(res) != len(specs) or any(a.dtype != dt or a.shape != shape or not a.flags.c_contiguous for a, (shape, dt) in zip(res, specs)):
                     raise ValueError("out: contiguous arrays of " + ", ".join("%s %s" % (np.dtype(dt).name, shape) for shape, dt in specs))
-            rc = call(getattr(capi.lib, entry), rays.ctypes.data, t.ctypes.data if t is not None else None, n, *[a.ctypes.data for a in res], stp)
+            ordp = ()
+            if order is not None:
+                o = None if order is True else self._order_numpy(order, n)
+                ordp = (None if o is None else o.ctypes.data,)
+            rc = call(getattr(capi.lib, entry), rays.ctypes.data, t.ctypes.data if t is not None else None, n, *ordp, *[a.ctypes.data for a in res], stp)
             capi.check(rc, entry)
         if want_stats:
             return res + (st.as_dict(),)
@@ -539,11 +642,12 @@ class DeviceScene:
             raise ValueError("camera must be 12 values of %s (eye, right, up, forward; see look_at)" % np.dtype(R).name)
         return np.ascontiguousarray(cam.reshape(12))
 
-    def trace(self, rays, want_stats=False, stream=None, out=None):
+    def trace(self, rays, want_stats=False, stream=None, out=None, order=None):
         """rt_trace_rays / rt_trace_rays_device: Renderer::raytrace (render.rs:171-215) for every ray of `rays` (n x 6: pos.xyz, dir.xyz, the
         scene's REAL dtype) -> (color[n, 3], alpha[n][, stats dict]): primary hit, shading and shadow ray, as the render traces a sample.
         numpy arrays go through the host entry (out: optional (color, alpha) arrays to fill, e.g. from capi.HostBuffer); a torch tensor on
-        this scene's device goes through the device entry on `stream`, with the stream discipline of intersect()."""
+        this scene's device goes through the device entry on `stream`, with the stream discipline of intersect().  order (None, True or
+        indices; rt_trace_rays_ordered*): as for intersect()."""
         R = _real(self.scene.precision)
         st = capi.Stats()
         stp = C.byref(st) if want_stats else None
@@ -570,11 +674,19 @@ class DeviceScene:
                 r = rays.contiguous()
                 color = torch.empty((n, 3), dtype=tdt, device=dev)
                 alpha = torch.empty(n, dtype=tdt, device=dev)
-                rc = capi.lib.rt_trace_rays_device(self._h, C.c_void_p(r.data_ptr()), n, C.c_void_p(color.data_ptr()), C.c_void_p(alpha.data_ptr()),
-                                                   C.c_void_p(qs.cuda_stream), stp)
+                if order is None:
+                    rc = capi.lib.rt_trace_rays_device(self._h, C.c_void_p(r.data_ptr()), n, C.c_void_p(color.data_ptr()), C.c_void_p(alpha.data_ptr()),
+                                                       C.c_void_p(qs.cuda_stream), stp)
+                else:
+                    if order is not True:
+                        order = self._order_torch(torch, order, n, dev)
+                    rc = capi.lib.rt_trace_rays_ordered_device(self._h, C.c_void_p(r.data_ptr()), n, None if order is True else C.c_void_p(order.data_ptr()),
+                                                               C.c_void_p(color.data_ptr()), C.c_void_p(alpha.data_ptr()), C.c_void_p(qs.cuda_stream), stp)
             if qs != cur:
                 rays.record_stream(qs)
-            capi.check(rc, "rt_trace_rays_device")
+                if isinstance(order, torch.Tensor):
+                    order.record_stream(qs)
+            capi.check(rc, "rt_trace_rays_device" if order is None else "rt_trace_rays_ordered_device")
         else:
             if not isinstance(rays, np.ndarray) or rays.dtype != R or rays.ndim != 2 or rays.shape[1] != 6 or rays.shape[0] == 0:
                 raise ValueError("rays must be a non-empty (n, 6) numpy array of %s (or a torch tensor on the scene's device)" % np.dtype(R).name)
@@ -587,8 +699,13 @@ class DeviceScene:
                 for a, shape in ((color, (n, 3)), (alpha, (n,))):
                     if a.dtype != R or a.shape != shape or not a.flags.c_contiguous:
                         raise ValueError("out: contiguous %s arrays of shapes (n, 3) and (n,)" % np.dtype(R).name)
-            rc = capi.lib.rt_trace_rays(self._h, rays.ctypes.data, n, color.ctypes.data, alpha.ctypes.data, stp)
-            capi.check(rc, "rt_trace_rays")
+            if order is None:
+                rc = capi.lib.rt_trace_rays(self._h, rays.ctypes.data, n, color.ctypes.data, alpha.ctypes.data, stp)
+            else:
+                o = None if order is True else self._order_numpy(order, n)
+                rc = capi.lib.rt_trace_rays_ordered(self._h, rays.ctypes.data, n, None if o is None else o.ctypes.data, color.ctypes.data,
+                                                    alpha.ctypes.data, stp)
+            capi.check(rc, "rt_trace_rays" if order is None else "rt_trace_rays_ordered")
         if want_stats:
             return color, alpha, st.as_dict()
         return color, alpha
