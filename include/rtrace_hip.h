@@ -139,7 +139,8 @@ rt_status rt_scene_destroy(rt_scene *scene);
  *   RT_SCENE_CONCENTRIC      every group bound is directly followed by an item with the same centre, bit for bit (the
  *                            reference's pyramid, group.rs:37-41): the f32 traversal loops test that item inside the
  *                            bound's step -- same tests, same order, same values, one node step fewer per entered group */
-enum { RT_SCENE_HAS_BOUNDS = 1u, RT_SCENE_CONCENTRIC = 2u };
+/*   RT_SCENE_DYNAMIC         made by rt_scene_create_dynamic (below): its spheres can be replaced; the general-ray entries serve it */
+enum { RT_SCENE_HAS_BOUNDS = 1u, RT_SCENE_CONCENTRIC = 2u, RT_SCENE_DYNAMIC = 4u };
 rt_status rt_scene_traits(const rt_scene *scene, uint32_t *traits);
 
 /* What rt_scene_create took on the host (diagnostic: a one-shot caller -- `make image` -- pays it once per process): total_ms for the whole
@@ -399,6 +400,55 @@ rt_status rt_render_camera_undersampled(rt_scene *scene, const rt_options *optio
 rt_status rt_render_camera_undersampled_device(rt_scene *scene, const rt_options *options, const void *camera,
                                                const rt_region *tiles, uint32_t n_tiles, uint32_t step, uint32_t prev_step,
                                                void *rgba_inout_device, void *hip_stream, rt_stats *stats);
+
+/* ---- dynamic scenes (additive to ABI 5): the topology fixed at creation, the spheres replaced in place, the bounds given or refit ----
+ * A scene from rt_scene_create is immutable.  A DYNAMIC scene keeps the number of items, their DFS order and the ranges it was created
+ * with, and takes new sphere values at any time; its group bounds are the caller's or are refit from the items on the device (the rule
+ * below).  It holds what the general-ray entries read -- the items and one stream of the hierarchy (without bounds: of the items) -- and
+ * the maps an update needs, all resident on the device: rt_intersect_rays*, rt_intersect_rays_multi*, rt_trace_rays*, rt_render_camera*,
+ * rt_render_camera_undersampled*, rt_ray_order* and their *_ordered forms serve it; after any update they write the bytes and counters
+ * a scene made by rt_scene_create from the same items, the bounds rt_scene_bounds reports and the same ranges writes.  rt_render_tiles*,
+ * rt_render_frame*, rt_render_region and rt_render_tiles_stream return RT_ERR_UNSUPPORTED on it (their caches assume a scene that never
+ * changes); rt_render_camera with the identity camera renders rt_render_tiles' bytes.  rt_gang_* has no dynamic form.
+ *
+ * ORDER.  An update is a WRITE of the scene, every other call a READ.  Device entries (update and queries alike) are ordered by the
+ * stream they are enqueued on; across streams the caller orders them (an event, a synchronise).  A host update is exclusive against
+ * host calls on the same scene -- a reader-writer lock inside the library: it waits for the host calls under way, and a host call that
+ * runs concurrently with it sees the old scene or the new one, never a mix.
+ *
+ * THE REFIT RULE.  All arithmetic in REAL, every operation rounded once, no FMA, sqrt the IEEE one.  EPSILON and MIN_NORMAL are REAL's
+ * machine epsilon (2^-23, 2^-52) and smallest normal number (2^-126, 2^-1022).  For a group over the items [first, first + count), count > 0,
+ * item i = {c_i, r_i}, a = x, y, z:
+ *   1. lo[a]     = min_i (c_i[a] - r_i)
+ *   2. hi[a]     = max_i (c_i[a] + r_i)
+ *   3. centre[a] = (lo[a] + hi[a]) * 0.5
+ *   4. reach_i   = dist_i + r_i with d = c_i - centre, s = (dx*dx + dy*dy) + dz*dz and
+ *                  dist_i = sqrt(s) if s >= MIN_NORMAL / EPSILON^2 (2^-80, 2^-918), else (|dx| + |dy|) + |dz|
+ *   5. radius    = max_i (reach_i) * (1 + 8 * EPSILON)
+ * and the bound is {centre, radius}.  min and max are exact, so the result does not depend on the order of the items or on how the
+ * group is split for the reduction.  The bound encloses every item of the group in exact arithmetic (NOTES.md A derives the 8; the second
+ * form of dist_i is what keeps that true where the squares underflow: it is never below the Euclidean distance and has no product in
+ * it).  A group with count == 0 has no node in the hierarchy and keeps the bound it was given.  rust_tracer_amd.refit_bounds restates
+ * the rule in numpy, bit for bit. */
+/* Arguments and validation as rt_scene_create.  bounds == NULL with n_bounds > 0: the bounds are refit from the items; in that form a
+ * range with count == 0 is RT_ERR_INVALID_ARGUMENT.  n_bounds == 0: a flat dynamic scene. */
+rt_status rt_scene_create_dynamic(int device, rt_precision precision,
+                                  const void *dfs_items, uint32_t n_items,
+                                  const void *light_unit, const void *eye,
+                                  const void *bounds, const rt_range *ranges, uint32_t n_bounds,
+                                  rt_scene **out);
+/* New values for every sphere, HOST memory: dfs_items REAL[4*n_items] in the same DFS order, bounds REAL[4*n_bounds] or NULL to refit.
+ * Validated as creation validates them (finite, |coordinate| <= 1e15, radius > 0): RT_ERR_INVALID_ARGUMENT before the device is touched,
+ * and the scene is unchanged.  Returns when the new scene is in place.  RT_ERR_UNSUPPORTED on a scene from rt_scene_create. */
+rt_status rt_scene_update(rt_scene *scene, const void *dfs_items, const void *bounds);
+/* The same from DEVICE memory, enqueued on `hip_stream` without waiting for it: no allocation and no host synchronisation in the call.
+ * Only the pointers and their alignment (one {cx, cy, cz, r} record: 16 bytes for RT_F32, 32 for RT_F64) are checked.  Skip offsets and
+ * item words come from the scene's resident topology, never from the caller's values: any bits give unspecified values in the results of
+ * later queries, never a fault or an endless walk.  The buffers are read by the work this call enqueues, not after it. */
+rt_status rt_scene_update_device(rt_scene *scene, const void *dfs_items_device, const void *bounds_device_or_null, void *hip_stream);
+/* The scene's current bounds, REAL[4*n_bounds] into host memory, after waiting for the last update (whichever stream carried it).  A
+ * scene from rt_scene_create reports the bounds it was created with. */
+rt_status rt_scene_bounds(rt_scene *scene, void *bounds_out);
 
 /* Bytes rt_render_tiles writes for this tile list (4 * total area), or 0 on an invalid list. */
 uint64_t rt_tiles_rgba_bytes(const rt_region *tiles, uint32_t n_tiles);

@@ -34,7 +34,8 @@ SYMBOLS = ("rt_abi_version", "rt_build_hierarchy", "rt_device_count", "rt_scene_
            "rt_intersect_rays_multi", "rt_intersect_rays_multi_device",
            "rt_render_camera_undersampled", "rt_render_camera_undersampled_device",
            "rt_ray_order", "rt_ray_order_device", "rt_intersect_rays_ordered", "rt_intersect_rays_ordered_device",
-           "rt_intersect_rays_multi_ordered", "rt_intersect_rays_multi_ordered_device", "rt_trace_rays_ordered", "rt_trace_rays_ordered_device")
+           "rt_intersect_rays_multi_ordered", "rt_intersect_rays_multi_ordered_device", "rt_trace_rays_ordered", "rt_trace_rays_ordered_device",
+           "rt_scene_create_dynamic", "rt_scene_update", "rt_scene_update_device", "rt_scene_bounds")
 # csrc/rt_debug.h: only in the -DRT_TEST_HOOKS build
 DEBUG_SYMBOLS = ("rt_debug_set", "rt_debug_count", "rt_debug_wave_trace", "rt_debug_flat_filter_check", "rt_debug_gang_layout", "rt_debug_rccl_library",
                  "rt_debug_shard_costs")
@@ -132,7 +133,12 @@ lib.rt_selftest_sqrt.argtypes = [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_u
 lib.rt_selftest_rcp.argtypes = [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
 lib.rt_scene_traits.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
 lib.rt_scene_setup_cost.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-RT_SCENE_HAS_BOUNDS, RT_SCENE_CONCENTRIC = 1, 2
+RT_SCENE_HAS_BOUNDS, RT_SCENE_CONCENTRIC, RT_SCENE_DYNAMIC = 1, 2, 4
+# dynamic scenes: rt_scene_create's arguments; new items and bounds (NULL: refit) from host / device memory; the current bounds
+lib.rt_scene_create_dynamic.argtypes = lib.rt_scene_create.argtypes
+lib.rt_scene_update.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+lib.rt_scene_update_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+lib.rt_scene_bounds.argtypes = [C.c_void_p, C.c_void_p]
 lib.rt_tiles_rgba_bytes.restype = C.c_uint64
 lib.rt_tiles_rgba_bytes.argtypes = [C.c_void_p, C.c_uint32]
 lib.rt_strerror.restype = C.c_char_p

@@ -19,6 +19,7 @@
 #include "rt_undersample.hpp"
 #include "rt_multihit.hpp"
 #include "rt_order.hpp"
+#include "rt_dynamic.hpp"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>       // types and prototypes only: librccl.so is loaded with dlopen when the first gang is created
@@ -38,6 +39,7 @@
 #include <memory>
 #include <mutex>
 #include <new>
+#include <shared_mutex>
 #include <string>
 #include <thread>
 #include <vector>
@@ -256,6 +258,21 @@ struct rt_scene {
     hipEvent_t query_items_ev = nullptr;
     std::vector<RegionReq *> comb_pending;
     int comb_leaders = 0;              // passes being led right now (<= kMaxRegionLeaders)
+    // rt_scene_bounds of a scene from rt_scene_create: the bounds it was created with
+    std::vector<unsigned char> h_bounds;
+    // ---- a DYNAMIC scene (rt_scene_create_dynamic, rt_dynamic.hpp): the items, ONE stream (d_shad, or d_query_items without bounds), and
+    // what an update needs, resident -- nothing of the render path (no filtered / compacted / cooperative / flat data, no cost map, no worker)
+    bool dynamic = false;
+    std::shared_mutex dyn_mu;          // an update is a write, every other call a read: a host call sees the old scene or the new one
+    void *d_dyn = nullptr;             // ONE allocation for everything below
+    uint32_t *d_item_node = nullptr, *d_bound_node = nullptr;      // node of every item (NULL without bounds: item i is node i) / of every bound
+    rt::RefitWork *d_work = nullptr;   // the refit's work records (rt_dynamic.hpp)
+    uint32_t n_work = 0, n_stream_nodes = 0;
+    void *d_pbox = nullptr, *d_reach = nullptr;                    // the refit's partial boxes and reach bits
+    void *d_bounds = nullptr;          // Item<REAL>[n_bounds]: the current bounds (rt_scene_bounds)
+    void *d_stage = nullptr;           // a host update's items and bounds on their way in: REAL[4 n_items], REAL[4 n_bounds] behind them
+    size_t stage_bounds_off = 0;
+    hipEvent_t upd_ev = nullptr;       // behind the last update
 };
 
 namespace {

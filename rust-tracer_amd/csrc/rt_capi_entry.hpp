@@ -140,32 +140,73 @@ uint64_t rt_tiles_rgba_bytes(const rt_region *tiles, uint32_t n_tiles)
     return px * 4;
 }
 
+// Scene::directional_light and Scene::eye into the scene, checked as rt_scene_create documents them.
+static rt_status scene_view_ok(const char *what, rt_scene *s, const void *light_unit, const void *eye)
+{
+    const bool f32 = s->precision == RT_F32;
+    for (int k = 0; k < 3; ++k) {
+        s->light[k] = f32 ? (double)static_cast<const float *>(light_unit)[k] : static_cast<const double *>(light_unit)[k];
+        s->eye[k] = f32 ? (double)static_cast<const float *>(eye)[k] : static_cast<const double *>(eye)[k];
+        // Bounds that keep every intermediate of primitive.rs:55-72 finite in f32 (squares of sums of coordinates stay below
+        // 2e33), so no inf - inf and no NaN can arise anywhere on the path (DESIGN.md 2): |eye| <= 1e15 like the items, and
+        // light_unit is a unit vector by contract (|component| <= 2 leaves room for rounding).
+        if (!std::isfinite(s->light[k]) || !std::isfinite(s->eye[k]) || std::fabs(s->eye[k]) > 1e15 || std::fabs(s->light[k]) > 2.0) {
+            snprintf(g_err, sizeof g_err, "%s: eye must be finite with |coordinate| <= 1e15, light_unit a unit vector", what);
+            return RT_ERR_INVALID_ARGUMENT;
+        }
+    }
+    {
+        // a unit vector as the host's `normalized` leaves it: the flat scan's shadow filter (rt_flat_sc.hpp) bounds its rounding
+        // errors with |light_unit| <= 1 + 1e-3
+        const double l2 = s->light[0] * s->light[0] + s->light[1] * s->light[1] + s->light[2] * s->light[2];
+        if (std::fabs(l2 - 1.0) > 2e-3) {
+            snprintf(g_err, sizeof g_err, "%s: light_unit must be a unit vector (its squared length is %.6g)", what, l2);
+            return RT_ERR_INVALID_ARGUMENT;
+        }
+    }
+    return RT_OK;
+}
+
+// What rt_scene_create and rt_scene_create_dynamic check of the items, bounds and ranges before any device is looked for.  refit: the
+// dynamic form whose bounds are NULL (they are refit from the items), where a range without items is an error.
+static rt_status scene_items_ok(const char *what, rt_precision precision, const void *dfs_items, uint32_t n_items, const void *light_unit, const void *eye,
+                                const void *bounds, const rt_range *ranges, uint32_t n_bounds, bool refit, rt_scene **out)
+{
+    if (!out || !dfs_items || !light_unit || !eye || n_items == 0 || (precision != RT_F32 && precision != RT_F64)) {
+        snprintf(g_err, sizeof g_err, "%s: NULL argument, n_items == 0 or bad precision", what);
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    if ((n_bounds != 0) != ((bounds != nullptr || refit) && ranges != nullptr)) {
+        snprintf(g_err, sizeof g_err, "%s: bounds, ranges and n_bounds must be given together", what);
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    const bool f32 = precision == RT_F32;
+    const bool ok = f32 ? (items_valid<float>(dfs_items, n_items, true) && (!n_bounds || refit || items_valid<float>(bounds, n_bounds, false)))
+                        : (items_valid<double>(dfs_items, n_items, true) && (!n_bounds || refit || items_valid<double>(bounds, n_bounds, false)));
+    if (!ok) {
+        snprintf(g_err, sizeof g_err, "%s: items must be finite, |v| <= 1e15, radius > 0", what);
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    for (uint32_t i = 0; i < n_bounds; ++i) {
+        if (ranges[i].first < 0 || ranges[i].count < 0 || (uint64_t)ranges[i].first + (uint64_t)ranges[i].count > n_items) {
+            snprintf(g_err, sizeof g_err, "%s: range %u outside the item array", what, i);
+            return RT_ERR_INVALID_ARGUMENT;
+        }
+        if (refit && ranges[i].count == 0) {
+            snprintf(g_err, sizeof g_err, "%s: range %u has no items: there is nothing to refit its bound from", what, i);
+            return RT_ERR_INVALID_ARGUMENT;
+        }
+    }
+    return RT_OK;
+}
+
 rt_status rt_scene_create(int device, rt_precision precision, const void *dfs_items, uint32_t n_items,
                           const void *light_unit, const void *eye, const void *bounds, const rt_range *ranges,
                           uint32_t n_bounds, rt_scene **out)
 {
     if (out) *out = nullptr;
-    if (!out || !dfs_items || !light_unit || !eye || n_items == 0 || (precision != RT_F32 && precision != RT_F64)) {
-        snprintf(g_err, sizeof g_err, "rt_scene_create: NULL argument, n_items == 0 or bad precision");
-        return RT_ERR_INVALID_ARGUMENT;
-    }
-    if ((n_bounds != 0) != (bounds != nullptr && ranges != nullptr)) {
-        snprintf(g_err, sizeof g_err, "rt_scene_create: bounds, ranges and n_bounds must be given together");
-        return RT_ERR_INVALID_ARGUMENT;
-    }
+    if (rt_status ast = scene_items_ok("rt_scene_create", precision, dfs_items, n_items, light_unit, eye, bounds, ranges, n_bounds, false, out); ast != RT_OK) return ast;
     const bool f32 = precision == RT_F32;
-    const bool ok = f32 ? (items_valid<float>(dfs_items, n_items, true) && (!n_bounds || items_valid<float>(bounds, n_bounds, false)))
-                        : (items_valid<double>(dfs_items, n_items, true) && (!n_bounds || items_valid<double>(bounds, n_bounds, false)));
-    if (!ok) {
-        snprintf(g_err, sizeof g_err, "rt_scene_create: items must be finite, |v| <= 1e15, radius > 0");
-        return RT_ERR_INVALID_ARGUMENT;
-    }
-    for (uint32_t i = 0; i < n_bounds; ++i) {
-        if (ranges[i].first < 0 || ranges[i].count < 0 || (uint64_t)ranges[i].first + (uint64_t)ranges[i].count > n_items) {
-            snprintf(g_err, sizeof g_err, "rt_scene_create: range %u outside the item array", i);
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-    }
     int ndev = 0;
     rt_status st = rt_device_count(&ndev);
     if (st != RT_OK) return st;
@@ -183,29 +224,11 @@ rt_status rt_scene_create(int device, rt_precision precision, const void *dfs_it
     if (!s) return RT_ERR_OUT_OF_MEMORY;
     s->device = device; s->precision = precision; s->n_items = n_items; s->n_bounds = n_bounds;
     const size_t esz = f32 ? sizeof(float) : sizeof(double);
-    for (int k = 0; k < 3; ++k) {
-        s->light[k] = f32 ? (double)static_cast<const float *>(light_unit)[k] : static_cast<const double *>(light_unit)[k];
-        s->eye[k] = f32 ? (double)static_cast<const float *>(eye)[k] : static_cast<const double *>(eye)[k];
-        // Bounds that keep every intermediate of primitive.rs:55-72 finite in f32 (squares of sums of coordinates stay below
-        // 2e33), so no inf - inf and no NaN can arise anywhere on the path (DESIGN.md 2): |eye| <= 1e15 like the items, and
-        // light_unit is a unit vector by contract (|component| <= 2 leaves room for rounding).
-        if (!std::isfinite(s->light[k]) || !std::isfinite(s->eye[k]) || std::fabs(s->eye[k]) > 1e15 || std::fabs(s->light[k]) > 2.0) {
-            snprintf(g_err, sizeof g_err, "rt_scene_create: eye must be finite with |coordinate| <= 1e15, light_unit a unit vector");
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-    }
-    {
-        // a unit vector as the host's `normalized` leaves it: the flat scan's shadow filter (rt_flat_sc.hpp) bounds its rounding
-        // errors with |light_unit| <= 1 + 1e-3
-        const double l2 = s->light[0] * s->light[0] + s->light[1] * s->light[1] + s->light[2] * s->light[2];
-        if (std::fabs(l2 - 1.0) > 2e-3) {
-            snprintf(g_err, sizeof g_err, "rt_scene_create: light_unit must be a unit vector (its squared length is %.6g)", l2);
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-    }
+    if (rt_status vst = scene_view_ok("rt_scene_create", s.get(), light_unit, eye); vst != RT_OK) return vst;
     auto fail = [&](rt_status code) { rt_scene_destroy(s.release()); return code; };
     hipError_t e;
     s->h_items.assign(static_cast<const unsigned char *>(dfs_items), static_cast<const unsigned char *>(dfs_items) + esz * 4 * n_items);
+    if (n_bounds) s->h_bounds.assign(static_cast<const unsigned char *>(bounds), static_cast<const unsigned char *>(bounds) + esz * 4 * n_bounds);      // rt_scene_bounds
     // ONE stream carries everything this call enqueues (uploads, the kernels that derive the streams, the cost map's counting render) and is
     // the first context's stream afterwards: the null stream is never touched
     // (the first stream of a process is ~19 ms -- the runtime makes its first hardware queue, tools/init_probe.hip --, and the library's code
@@ -266,6 +289,12 @@ rt_status rt_scene_destroy(rt_scene *s)
     if (s->ahead.stream) { (void)hipStreamSynchronize(s->ahead.stream); (void)hipStreamDestroy(s->ahead.stream); }      // a pass rendered ahead may still be running
     s->pool.clear();
     for (auto &t : s->tables) { (void)hipFree(t.dev); for (auto &od : t.orders) release_order(od); if (t.order_arena) (void)hipFree(t.order_arena); if (t.landed) (void)hipEventDestroy(t.landed); }
+    if (s->dynamic) {                                      // (its stream is part of d_dyn)
+        s->d_shad = s->d_query_items = nullptr;
+        if (s->cost_stream) (void)hipStreamSynchronize(s->cost_stream);
+        if (s->d_dyn) (void)hipFree(s->d_dyn);
+        if (s->upd_ev) (void)hipEventDestroy(s->upd_ev);
+    }
     if (s->d_items) (void)hipFree(s->d_items);
     if (s->d_prim) (void)hipFree(s->d_prim);
     if (s->d_shad) (void)hipFree(s->d_shad);
@@ -289,6 +318,100 @@ rt_status rt_scene_destroy(rt_scene *s)
     if (s->d_sg) (void)hipFree(s->d_sg);
     if (s->d_se) (void)hipFree(s->d_se);
     delete s;
+    return RT_OK;
+}
+
+// ---- dynamic scenes: the topology fixed, the spheres replaced in place, the bounds given or refit on the device (rt_dynamic.hpp) ----
+
+rt_status rt_scene_create_dynamic(int device, rt_precision precision, const void *dfs_items, uint32_t n_items, const void *light_unit, const void *eye,
+                                  const void *bounds, const rt_range *ranges, uint32_t n_bounds, rt_scene **out)
+{
+    if (out) *out = nullptr;
+    const bool refit = n_bounds != 0 && bounds == nullptr;
+    if (rt_status ast = scene_items_ok("rt_scene_create_dynamic", precision, dfs_items, n_items, light_unit, eye, bounds, ranges, n_bounds, refit, out); ast != RT_OK)
+        return ast;
+    int ndev = 0;
+    rt_status st = rt_device_count(&ndev);
+    if (st != RT_OK) return st;
+    if (device < 0 || device >= ndev) {
+        snprintf(g_err, sizeof g_err, "device %d out of range (%d visible)", device, ndev);
+        return RT_ERR_NO_DEVICE;
+    }
+    const auto t_setup = std::chrono::steady_clock::now();
+    auto ms_since_setup = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_setup).count(); };
+    HIP_TRY(hipSetDevice(device));
+    std::unique_ptr<rt_scene> s(new (std::nothrow) rt_scene());
+    if (!s) return RT_ERR_OUT_OF_MEMORY;
+    s->device = device; s->precision = precision; s->n_items = n_items; s->n_bounds = n_bounds; s->dynamic = true;
+    if (rt_status vst = scene_view_ok("rt_scene_create_dynamic", s.get(), light_unit, eye); vst != RT_OK) return vst;
+    auto fail = [&](rt_status code) { rt_scene_destroy(s.release()); return code; };
+    const bool f32 = precision == RT_F32;
+    const double t_before_stream = ms_since_setup();
+    hipError_t e = hipStreamCreateWithFlags(&s->cost_stream, hipStreamNonBlocking);      // the scene's stream: its own updates, and its first context's
+    s->setup_first_stream_ms = ms_since_setup() - t_before_stream;
+    if (e != hipSuccess) return fail(hip_fail(e, "hipStreamCreate(scene)", __LINE__));
+    if ((e = hipMalloc(&s->d_items, (f32 ? sizeof(float) : sizeof(double)) * 4 * n_items)) != hipSuccess) return fail(hip_fail(e, "hipMalloc(items)", __LINE__));
+    st = f32 ? upload_dynamic<float>(s.get(), dfs_items, bounds, ranges) : upload_dynamic<double>(s.get(), dfs_items, bounds, ranges);
+    if (st != RT_OK) return fail(st);
+    s->setup_total_ms = ms_since_setup();
+    *out = s.release();
+    return RT_OK;
+}
+
+static rt_status update_args_ok(rt_scene *s, const void *items, const char *what)
+{
+    if (!s || !items) { snprintf(g_err, sizeof g_err, "%s: NULL scene or items", what); return RT_ERR_INVALID_ARGUMENT; }
+    if (!s->dynamic) {
+        snprintf(g_err, sizeof g_err, "%s: the scene was made by rt_scene_create and is immutable; rt_scene_create_dynamic makes one that can be updated", what);
+        return RT_ERR_UNSUPPORTED;
+    }
+    return RT_OK;
+}
+
+rt_status rt_scene_update(rt_scene *s, const void *dfs_items, const void *bounds)
+{
+    if (rt_status ast = update_args_ok(s, dfs_items, "rt_scene_update"); ast != RT_OK) return ast;
+    const bool f32 = s->precision == RT_F32, with_bounds = bounds && s->n_bounds;
+    const bool ok = f32 ? (items_valid<float>(dfs_items, s->n_items, true) && (!with_bounds || items_valid<float>(bounds, s->n_bounds, false)))
+                        : (items_valid<double>(dfs_items, s->n_items, true) && (!with_bounds || items_valid<double>(bounds, s->n_bounds, false)));
+    if (!ok) {
+        snprintf(g_err, sizeof g_err, "rt_scene_update: items must be finite, |v| <= 1e15, radius > 0; the scene is unchanged");
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    std::unique_lock<std::shared_mutex> lk(s->dyn_mu);               // every host call under way has returned; none starts before this one has
+    HIP_TRY(hipSetDevice(s->device));
+    return dynamic_update_host(s, dfs_items, bounds);
+}
+
+rt_status rt_scene_update_device(rt_scene *s, const void *dfs_items_device, const void *bounds_device, void *hip_stream)
+{
+    if (rt_status ast = update_args_ok(s, dfs_items_device, "rt_scene_update_device"); ast != RT_OK) return ast;
+    const uintptr_t align = (s->precision == RT_F32 ? sizeof(float) : sizeof(double)) * 4;      // one {cx, cy, cz, r} record: the kernels load it whole
+    if ((reinterpret_cast<uintptr_t>(dfs_items_device) % align) != 0 || (reinterpret_cast<uintptr_t>(bounds_device) % align) != 0) {
+        snprintf(g_err, sizeof g_err, "rt_scene_update_device: items and bounds must be %u-byte aligned", (unsigned)align);
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    const ReadLock rl(s);                                            // (not while a host update is replacing the scene)
+    HIP_TRY(hipSetDevice(s->device));
+    return enqueue_dynamic_update(s, dfs_items_device, bounds_device, static_cast<hipStream_t>(hip_stream));
+}
+
+rt_status rt_scene_bounds(rt_scene *s, void *bounds_out)
+{
+    if (!s || (!bounds_out && s->n_bounds)) { snprintf(g_err, sizeof g_err, "rt_scene_bounds: NULL argument"); return RT_ERR_INVALID_ARGUMENT; }
+    if (s->n_bounds == 0) return RT_OK;
+    const size_t bytes = (s->precision == RT_F32 ? sizeof(float) : sizeof(double)) * 4 * s->n_bounds;
+    if (!s->dynamic) { memcpy(bounds_out, s->h_bounds.data(), bytes); return RT_OK; }
+    const ReadLock rl(s);
+    HIP_TRY(hipSetDevice(s->device));
+    Context *c = nullptr;
+    if (rt_status st = acquire(s, &c); st != RT_OK) return st;
+    Lease lease{ s, c };
+    HIP_TRY(hipStreamWaitEvent(c->stream, s->upd_ev, 0));             // behind the last update, whichever stream carried it
+    hipError_t e = hipMemcpyAsync(bounds_out, s->d_bounds, bytes, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t se = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = se;
+    if (e != hipSuccess) return hip_fail(e, "rt_scene_bounds(copy)", __LINE__);
     return RT_OK;
 }
 
@@ -737,6 +860,7 @@ static rt_status intersect_rays_device(rt_scene *s, rt_query mode, const void *r
 {
     if (!query_args_ok(s, mode, rays, tmax, n, distance_out, normal_out, item_out, what)) return RT_ERR_INVALID_ARGUMENT;
     if (ordered && !device_order_ok(order, what)) return RT_ERR_INVALID_ARGUMENT;
+    const ReadLock rl(s);
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     const void *nodes = nullptr;
@@ -785,6 +909,7 @@ static rt_status intersect_rays_host(rt_scene *s, rt_query mode, const void *ray
               : query_rays_valid(static_cast<const double *>(rays), static_cast<const double *>(tmax), n)))
         return RT_ERR_INVALID_ARGUMENT;
     if (order && !order_is_permutation(order, n, what)) return RT_ERR_INVALID_ARGUMENT;
+    const ReadLock rl(s);
     HIP_TRY(hipSetDevice(s->device));
     rt_status st = RT_OK;
     // Every buffer is either the caller's own memory, read and written by the kernel directly (rt_host_alloc / rt_host_register), or a
@@ -873,6 +998,7 @@ static rt_status intersect_rays_multi_device(rt_scene *s, rt_multihit mode, uint
     if (!query_args_ok(s, RT_QUERY_NEAREST, rays, tmax, n, distance_out, normal_out, item_out, what) || !multihit_args_ok(mode, k, hits_out, what))
         return RT_ERR_INVALID_ARGUMENT;
     if (ordered && !device_order_ok(order, what)) return RT_ERR_INVALID_ARGUMENT;
+    const ReadLock rl(s);
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     const void *nodes = nullptr;
@@ -928,6 +1054,7 @@ static rt_status intersect_rays_multi_host(rt_scene *s, rt_multihit mode, uint32
               : query_rays_valid(static_cast<const double *>(rays), static_cast<const double *>(tmax), n)))
         return RT_ERR_INVALID_ARGUMENT;
     if (order && !order_is_permutation(order, n, what)) return RT_ERR_INVALID_ARGUMENT;
+    const ReadLock rl(s);
     HIP_TRY(hipSetDevice(s->device));
     rt_status st = RT_OK;
     // pinned buffers are read and written by the kernel in place, pageable ones go through the call's workspace (as rt_intersect_rays)
@@ -1014,6 +1141,7 @@ static rt_status trace_rays_device(rt_scene *s, const void *rays, uint32_t n, vo
 {
     if (!trace_args_ok(s, rays, n, color_out, alpha_out, what)) return RT_ERR_INVALID_ARGUMENT;
     if (ordered && !device_order_ok(order, what)) return RT_ERR_INVALID_ARGUMENT;
+    const ReadLock rl(s);
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     const void *nodes = nullptr;
@@ -1063,6 +1191,7 @@ static rt_status trace_rays_host(rt_scene *s, const void *rays, uint32_t n, void
               : query_rays_valid(static_cast<const double *>(rays), static_cast<const double *>(nullptr), n)))
         return RT_ERR_INVALID_ARGUMENT;
     if (order && !order_is_permutation(order, n, what)) return RT_ERR_INVALID_ARGUMENT;
+    const ReadLock rl(s);
     HIP_TRY(hipSetDevice(s->device));
     rt_status st = RT_OK;
     // pinned buffers are read and written by the kernel in place, pageable ones go through the call's workspace (as rt_intersect_rays)
@@ -1246,6 +1375,7 @@ rt_status rt_render_camera_device(rt_scene *s, const rt_options *o, const void *
     uint64_t total_px = 0; uint32_t total_blocks = 0;
     rt_status st = build_tile_table(o, tiles, n, tab, &total_px, &total_blocks);
     if (st != RT_OK) return st;
+    const ReadLock rl(s);
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     Context *c = nullptr;
@@ -1270,6 +1400,7 @@ rt_status rt_render_camera(rt_scene *s, const rt_options *o, const void *camera,
     uint64_t total_px = 0; uint32_t total_blocks = 0;
     rt_status st = build_tile_table(o, tiles, n, tab, &total_px, &total_blocks);
     if (st != RT_OK) return st;
+    const ReadLock rl(s);
     HIP_TRY(hipSetDevice(s->device));
     const HostDest dest = classify_host_pointer(rgba_out);
     if (dest.bad) {
@@ -1342,6 +1473,7 @@ rt_status rt_render_camera_undersampled_device(rt_scene *s, const rt_options *o,
     uint64_t total_px = 0; uint32_t total_blocks = 0;
     rt_status st = build_tile_table(o, tiles, n, tab, &total_px, &total_blocks);
     if (st != RT_OK) return st;
+    const ReadLock rl(s);
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t stream = static_cast<hipStream_t>(hip_stream);
     Context *c = nullptr;
@@ -1369,6 +1501,7 @@ rt_status rt_render_camera_undersampled(rt_scene *s, const rt_options *o, const 
     uint64_t total_px = 0; uint32_t total_blocks = 0;
     rt_status st = build_tile_table(o, tiles, n, tab, &total_px, &total_blocks);
     if (st != RT_OK) return st;
+    const ReadLock rl(s);
     HIP_TRY(hipSetDevice(s->device));
     const HostDest dest = classify_host_pointer(rgba_inout);
     if (dest.bad) {
@@ -1500,7 +1633,7 @@ rt_status rt_blit_tiles_device(rt_scene *s, const rt_options *o, const rt_region
 rt_status rt_scene_traits(const rt_scene *s, uint32_t *traits)
 {
     if (!s || !traits) { snprintf(g_err, sizeof g_err, "NULL argument"); return RT_ERR_INVALID_ARGUMENT; }
-    *traits = (s->n_nodes ? RT_SCENE_HAS_BOUNDS : 0u) | (s->fused ? RT_SCENE_CONCENTRIC : 0u);
+    *traits = (s->n_nodes ? RT_SCENE_HAS_BOUNDS : 0u) | (s->fused ? RT_SCENE_CONCENTRIC : 0u) | (s->dynamic ? RT_SCENE_DYNAMIC : 0u);
     return RT_OK;
 }
 
@@ -1683,6 +1816,7 @@ rt_status rt_render_region(rt_scene *s, const rt_options *o, rt_traversal trav, 
                            rt_stats *stats)
 {
     if (!check_common(s, o, region, 1, rgba_out)) return RT_ERR_INVALID_ARGUMENT;
+    if (rt_status dst = refuse_dynamic(s, "rt_render_region"); dst != RT_OK) return dst;
     if (!stats && knob(RT_DEBUG_FRAME_AHEAD) != 0) {
         if (classify_host_pointer(rgba_out).bad) {              // the frame-ahead path copies with the CPU: same answer as rt_render_tiles gives
             snprintf(g_err, sizeof g_err, "rt_render_region: rgba_out is device memory; use rt_render_tiles_device");

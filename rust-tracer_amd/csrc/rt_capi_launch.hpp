@@ -395,6 +395,7 @@ rt_status launch_skip(const rt_scene *s, Context *c, dim3 grid, hipStream_t stre
 
 rt_status ensure_flat(rt_scene *s)
 {
+    if (rt_status dst = refuse_dynamic(s, "the flat scan"); dst != RT_OK) return dst;
     std::lock_guard<std::mutex> lk(s->flat_mu);
     if (s->flat_ready) return RT_OK;
     HIP_TRY(hipSetDevice(s->device));
@@ -418,6 +419,7 @@ rt_status check_traversal(rt_scene *s, rt_traversal trav)
         snprintf(g_err, sizeof g_err, "unknown traversal %d", (int)trav);
         return RT_ERR_INVALID_ARGUMENT;
     }
+    if (rt_status dst = refuse_dynamic(s, "rt_render_tiles / rt_render_frame"); dst != RT_OK) return dst;
     if (trav == RT_TRAVERSAL_FLAT) return ensure_flat(s);
     if (trav == RT_TRAVERSAL_SKIP && s->n_nodes == 0) {
         snprintf(g_err, sizeof g_err, "the hierarchy (skip) traversal needs a scene created with subtree bounds");

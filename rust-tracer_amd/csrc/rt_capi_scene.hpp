@@ -534,3 +534,163 @@ rt_status upload_coop(rt_scene *s, const std::vector<rt::RawNode<T>> &raw)
     return RT_OK;
 }
 
+
+// ---- dynamic scenes (rt_scene_create_dynamic, rt_scene_update*; rt_dynamic.hpp) ----
+
+// Every call but an update reads the scene: a host update waits for the host calls under way and holds off new ones while it runs.
+struct ReadLock {
+    std::shared_lock<std::shared_mutex> lk;
+    explicit ReadLock(rt_scene *s) { if (s && s->dynamic) lk = std::shared_lock<std::shared_mutex>(s->dyn_mu); }
+};
+
+// The render entry points' caches (filtered and compacted streams, cost map, dispatch orders, frames rendered ahead) assume a scene
+// that never changes: a dynamic scene has none of them.
+rt_status refuse_dynamic(const rt_scene *s, const char *what)
+{
+    if (!s || !s->dynamic) return RT_OK;
+    snprintf(g_err, sizeof g_err, "%s: a dynamic scene has no render-path data; render it with rt_render_camera (the identity camera gives rt_render_tiles' bytes)", what);
+    return RT_ERR_UNSUPPORTED;
+}
+
+// The topology of a dynamic scene from its raw stream: item word and skip offset of every node, the node of every item and of every
+// bound (kNoNode: a group without items), and the refit's work records.
+template <typename T>
+void dynamic_topology(const std::vector<rt::RawNode<T>> &raw, uint32_t n_items, const rt_range *ranges, uint32_t n_bounds, std::vector<uint2> &topo,
+                      std::vector<uint32_t> &item_node, std::vector<uint32_t> &bound_node, std::vector<rt::RefitWork> &work)
+{
+    constexpr uint32_t kStride = (uint32_t)sizeof(rt::Node<T>);
+    topo.resize(raw.size());
+    item_node.assign(n_items, 0u);
+    bound_node.assign(n_bounds, rt::kNoNode);
+    uint32_t b = 0;
+    for (uint32_t i = 0; i < (uint32_t)raw.size(); ++i) {
+        if (raw[i].skip == 0u) {                                     // ITEM
+            topo[i] = make_uint2(raw[i].item | rt::kNodeItem, (i + 1u) * kStride);
+            item_node[raw[i].item] = i;
+        } else {                                                     // BOUND: the kept ranges in their order
+            topo[i] = make_uint2(0u, raw[i].skip * kStride);
+            while (b < n_bounds && ranges[b].count == 0) ++b;
+            if (b < n_bounds) bound_node[b++] = i;
+        }
+    }
+    work.clear();
+    for (uint32_t g = 0; g < n_bounds; ++g) {
+        const uint32_t first = (uint32_t)ranges[g].first, count = (uint32_t)ranges[g].count;
+        const uint32_t pfirst = (uint32_t)work.size(), pcount = (count + rt::kRefitChunk - 1) / rt::kRefitChunk;
+        for (uint32_t p = 0; p < pcount; ++p)
+            work.push_back(rt::RefitWork{ g, first + p * rt::kRefitChunk, std::min(rt::kRefitChunk, count - p * rt::kRefitChunk), pfirst, pcount, 0u, 0u, 0u });
+    }
+}
+
+// One update on `stream`: the refit's two passes when the bounds are not given, then the rewrite.  Nothing is allocated and nothing waited for.
+template <typename T>
+rt_status enqueue_dynamic_update(rt_scene *s, const void *src_items, const void *src_bounds, hipStream_t stream)
+{
+    typedef typename rt::BitsOf<T>::type Bits;
+    const dim3 block(rt::kBlockThreads);
+    if (s->n_bounds && !src_bounds && s->n_work) {
+        const rt::RefitArgs<T> a{ static_cast<const rt::Item<T> *>(src_items), s->d_work, static_cast<T *>(s->d_pbox), static_cast<Bits *>(s->d_reach),
+                                  static_cast<rt::Item<T> *>(s->d_bounds), s->n_work };
+        const dim3 grid((s->n_work + rt::kBlockThreads / 64 - 1) / (rt::kBlockThreads / 64));
+        hipLaunchKernelGGL(rt::k_refit_box<T>, grid, block, 0, stream, a);
+        hipLaunchKernelGGL(rt::k_refit_reach<T>, grid, block, 0, stream, a);
+    }
+    rt::RewriteArgs<T> r{};
+    r.src_items = static_cast<const rt::Item<T> *>(src_items);
+    r.src_bounds = s->n_bounds ? static_cast<const rt::Item<T> *>(src_bounds) : nullptr;
+    r.items = static_cast<rt::Item<T> *>(s->d_items);
+    r.bounds = static_cast<rt::Item<T> *>(s->d_bounds);
+    r.reach = static_cast<const Bits *>(s->d_reach);
+    r.stream = static_cast<rt::Node<T> *>(s->n_nodes ? s->d_shad : s->d_query_items);
+    r.item_node = s->d_item_node;
+    r.bound_node = s->d_bound_node;
+    r.n_items = s->n_items; r.n_bounds = s->n_bounds;
+    const uint64_t threads = (uint64_t)s->n_items + s->n_bounds;
+    hipLaunchKernelGGL(rt::k_dynamic_rewrite<T>, dim3((unsigned)((threads + rt::kBlockThreads - 1) / rt::kBlockThreads)), block, 0, stream, r);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(s->upd_ev, stream));
+    return RT_OK;
+}
+
+rt_status enqueue_dynamic_update(rt_scene *s, const void *src_items, const void *src_bounds, hipStream_t stream)
+{
+    return s->precision == RT_F32 ? enqueue_dynamic_update<float>(s, src_items, src_bounds, stream)
+                                  : enqueue_dynamic_update<double>(s, src_items, src_bounds, stream);
+}
+
+// A host update's values into the scene's staging (pinned arena -> k_upload_words, as rt_scene_create uploads) and the update behind
+// them, on the scene's stream; returns when the new scene is in place.  The caller holds the scene's write lock (or is creating it).
+rt_status dynamic_update_host(rt_scene *s, const void *items, const void *bounds)
+{
+    const size_t esz = s->precision == RT_F32 ? sizeof(float) : sizeof(double);
+    const size_t ib = esz * 4 * s->n_items, bb = (bounds && s->n_bounds) ? esz * 4 * s->n_bounds : 0;
+    memcpy(s->h_up, items, ib);
+    if (bb) memcpy(s->h_up + s->stage_bounds_off, bounds, bb);
+    rt_status st = upload_words(s->d_stage, s->h_up, bb ? s->stage_bounds_off + bb : ib, s->cost_stream);
+    if (st == RT_OK) st = enqueue_dynamic_update(s, s->d_stage, bb ? static_cast<char *>(s->d_stage) + s->stage_bounds_off : nullptr, s->cost_stream);
+    const hipError_t e = hipStreamSynchronize(s->cost_stream);
+    if (st == RT_OK && e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(update)", __LINE__);
+    return st;
+}
+
+// Everything a dynamic scene has on the device besides its items: the stream, the maps, the refit's workspace, the staging -- one
+// allocation, uploaded through the scene's pinned arena, which stays: it is where a host update stages its values.
+template <typename T>
+rt_status upload_dynamic(rt_scene *s, const void *items, const void *bounds, const rt_range *ranges)
+{
+    std::vector<rt::RawNode<T>> raw;
+    std::vector<T> no_bounds;
+    if (s->n_bounds && !bounds) no_bounds.assign((size_t)4 * s->n_bounds, T(0));
+    rt_status st = build_raw_stream<T>(static_cast<const T *>(items), s->n_items, bounds ? static_cast<const T *>(bounds) : no_bounds.data(), ranges, s->n_bounds, raw);
+    if (st != RT_OK) return st;
+    if (((uint64_t)raw.size() + rt::kNodePad) * sizeof(rt::Node<T>) > 0xFFFFFFFFull || s->n_items > rt::kNodeIndexMask) {
+        snprintf(g_err, sizeof g_err, "rt_scene_create_dynamic: %zu stream nodes exceed what the traversal streams can address", raw.size());
+        return RT_ERR_UNSUPPORTED;
+    }
+    std::vector<uint2> topo;
+    std::vector<uint32_t> item_node, bound_node;
+    std::vector<rt::RefitWork> work;
+    dynamic_topology<T>(raw, s->n_items, ranges, s->n_bounds, topo, item_node, bound_node, work);
+    s->n_stream_nodes = (uint32_t)raw.size();
+    s->n_nodes = s->n_bounds ? s->n_stream_nodes : 0u;               // (without bounds the entries walk d_query_items: query_stream)
+    s->n_work = (uint32_t)work.size();
+
+    size_t bytes = 0;
+    auto take = [&](size_t b) { const size_t at = bytes; bytes += (b + 255) & ~(size_t)255; return at; };
+    const size_t o_stream = take(sizeof(rt::Node<T>) * (raw.size() + rt::kNodePad));
+    const size_t o_topo = take(sizeof(uint2) * topo.size());          // (read once, by k_dynamic_topology)
+    const size_t o_inode = take(s->n_bounds ? sizeof(uint32_t) * item_node.size() : 0);
+    const size_t o_bnode = take(sizeof(uint32_t) * bound_node.size());
+    const size_t o_work = take(sizeof(rt::RefitWork) * work.size());
+    const size_t o_pbox = take(sizeof(T) * 6 * work.size());
+    const size_t o_reach = take(sizeof(typename rt::BitsOf<T>::type) * s->n_bounds);
+    const size_t o_bounds = take(sizeof(rt::Item<T>) * s->n_bounds);
+    s->stage_bounds_off = (sizeof(rt::Item<T>) * s->n_items + 255) & ~(size_t)255;
+    const size_t stage_bytes = s->stage_bounds_off + sizeof(rt::Item<T>) * s->n_bounds;
+    const size_t o_stage = take(stage_bytes);
+    HIP_TRY(hipMalloc(&s->d_dyn, bytes));
+    char *const d = static_cast<char *>(s->d_dyn);
+    void *const d_stream = d + o_stream;
+    s->d_item_node = s->n_bounds ? reinterpret_cast<uint32_t *>(d + o_inode) : nullptr;
+    s->d_bound_node = reinterpret_cast<uint32_t *>(d + o_bnode);
+    s->d_work = reinterpret_cast<rt::RefitWork *>(d + o_work);
+    s->d_pbox = d + o_pbox; s->d_reach = d + o_reach; s->d_bounds = d + o_bounds; s->d_stage = d + o_stage;
+
+    // the pinned arena: the topology's uploads now, a host update's items and bounds from then on
+    const size_t topo_bytes = sizeof(uint2) * topo.size() + sizeof(uint32_t) * (item_node.size() + bound_node.size()) + sizeof(rt::RefitWork) * work.size() + 4 * 256;
+    const size_t want = std::max(topo_bytes, stage_bytes) + 256;
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s->h_up), want, hipHostMallocDefault));
+    s->up_cap = want; s->up_used = 0;
+    if ((st = scene_upload(s, d + o_topo, topo.data(), sizeof(uint2) * topo.size())) != RT_OK) return st;
+    if (s->n_bounds && (st = scene_upload(s, s->d_item_node, item_node.data(), sizeof(uint32_t) * item_node.size())) != RT_OK) return st;
+    if (s->n_bounds && (st = scene_upload(s, s->d_bound_node, bound_node.data(), sizeof(uint32_t) * bound_node.size())) != RT_OK) return st;
+    if (!work.empty() && (st = scene_upload(s, s->d_work, work.data(), sizeof(rt::RefitWork) * work.size())) != RT_OK) return st;
+    hipLaunchKernelGGL(rt::k_dynamic_topology<T>, dim3((unsigned)((raw.size() + rt::kNodePad + rt::kBlockThreads - 1) / rt::kBlockThreads)), dim3(rt::kBlockThreads), 0,
+                       s->cost_stream, reinterpret_cast<const uint2 *>(d + o_topo), (unsigned)raw.size(), static_cast<rt::Node<T> *>(d_stream));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s->cost_stream));                    // (the arena is reused from its start by the update below)
+    s->up_used = 0;
+    (s->n_bounds ? s->d_shad : s->d_query_items) = d_stream;          // (part of d_dyn: rt_scene_destroy does not free it on its own)
+    HIP_TRY(hipEventCreateWithFlags(&s->upd_ev, hipEventDisableTiming));
+    return dynamic_update_host(s, items, bounds);
+}

@@ -211,14 +211,11 @@ __global__ void k_items_stream(const Item<T> *__restrict__ items, unsigned n, No
     if (i >= n + kNodePad) return;
     constexpr unsigned kStride = (unsigned)sizeof(Node<T>);
     Node<T> s;
-    s.a4 = T(0); s.own_rr = T(0);
     if (i >= n) {
-        s.a0 = s.a1 = s.a2 = T(0); s.a3 = inf<T>();
-        s.item = kNodeEnd;
-        s.skip_off = n * kStride;
+        per_origin_end(s, n);
     } else {
         const Item<T> it = items[i];
-        s.a0 = it.cx; s.a1 = it.cy; s.a2 = it.cz; s.a3 = it.r * it.r;      // primitive.rs:58
+        per_origin_terms(s, it.cx, it.cy, it.cz, it.r);
         s.item = i | kNodeItem;
         s.skip_off = (i + 1u) * kStride;
     }

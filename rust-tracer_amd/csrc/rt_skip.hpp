@@ -272,6 +272,25 @@ __global__ void k_build_fstreams(const Node<float> *__restrict__ prim, const Nod
     if (own_item) own_item[i] = (compacted && !end && !item) ? p.item : 0u;
 }
 
+// The ray-independent terms of a node of the per-origin (shadow / query) stream: the centre and radius * radius (primitive.rs:58).  ONE
+// statement of them for every kernel that writes such a record: k_build_streams, k_items_stream (rt_query.hpp) and the rewrite of a
+// dynamic scene's stream (rt_dynamic.hpp) write the same bits for the same sphere.
+template <typename T>
+__device__ __forceinline__ void per_origin_terms(Node<T> &s, T cx, T cy, T cz, T r)
+{
+    s.a0 = cx; s.a1 = cy; s.a2 = cz; s.a3 = r * r; s.a4 = T(0);
+    s.own_rr = T(0);
+}
+// ... and of the END nodes behind the last node: v = 0 and rr = +inf make disc = (b*b - vv) + rr = +inf for every ray
+template <typename T>
+__device__ __forceinline__ void per_origin_end(Node<T> &s, unsigned n_nodes)
+{
+    s.a0 = s.a1 = s.a2 = T(0); s.a3 = inf<T>(); s.a4 = T(0);
+    s.own_rr = T(0);
+    s.item = kNodeEnd;
+    s.skip_off = n_nodes * (unsigned)sizeof(Node<T>);
+}
+
 // Derives both streams from the raw one: exact IEEE ops, no contraction (same products the CPU path forms).  Threads
 // n .. n + kNodePad - 1 write the END nodes.
 template <typename T>
@@ -285,17 +304,17 @@ __global__ void k_build_streams(const RawNode<T> *__restrict__ raw, unsigned n, 
     if (i >= n) {
         // END: v = 0 and rr = +inf make disc = (b*b - vv) + rr = +inf for every ray of either kind
         p.a0 = p.a1 = p.a2 = p.a3 = T(0); p.a4 = inf<T>();
-        s.a0 = s.a1 = s.a2 = T(0); s.a3 = inf<T>(); s.a4 = T(0);
-        p.own_rr = s.own_rr = T(0);
-        p.item = s.item = kNodeEnd;
-        p.skip_off = s.skip_off = n * kStride;
+        p.own_rr = T(0);
+        p.item = kNodeEnd;
+        p.skip_off = n * kStride;
+        per_origin_end(s, n);
     } else {
         const RawNode<T> r = raw[i];
         const V3<T> v = { r.cx - eye.x, r.cy - eye.y, r.cz - eye.z };      // primitive.rs:56
         const T rr = r.r * r.r;                                           // primitive.rs:58
         p.a0 = v.x; p.a1 = v.y; p.a2 = v.z; p.a3 = dot(v, v); p.a4 = rr;
-        s.a0 = r.cx; s.a1 = r.cy; s.a2 = r.cz; s.a3 = rr; s.a4 = T(0);
-        p.own_rr = s.own_rr = T(0);
+        per_origin_terms(s, r.cx, r.cy, r.cz, r.r);
+        p.own_rr = T(0);
         if (r.skip == 0u) {                                               // ITEM
             p.item = s.item = r.item | kNodeItem;
             p.skip_off = s.skip_off = (i + 1u) * kStride;

@@ -58,6 +58,40 @@ def ray_keys(rays):
     return (m3 << np.uint32(23)) | ((np.uint32(2) * axis.astype(np.uint32) + sign) << np.uint32(20)) | m2
 
 
+def refit_bounds(items, ranges, precision=capi.RT_F32, bounds=None):
+    """The bounds rt_scene_update refits for `items` (n x 4: cx, cy, cz, r) over `ranges` (g x 2: first item, item count) -> REAL[g, 4],
+    the rule of include/rtrace_hip.h restated in numpy bit for bit: every operation in REAL, rounded once.  Per group: lo / hi = min / max
+    of c -+ r, centre = (lo + hi) * 0.5, reach = dist(c, centre) + r with dist = sqrt((dx*dx + dy*dy) + dz*dz), or (|dx| + |dy|) + |dz|
+    where that sum of squares is below MIN_NORMAL / EPSILON^2, radius = max(reach) * (1 + 8 * EPSILON).  A group without items keeps its
+    row of `bounds` (zeros when there is none)."""
+    R = _real(precision)
+    it = np.ascontiguousarray(items, dtype=R).reshape(-1, 4)
+    rg = np.asarray(ranges, dtype=np.int64).reshape(-1, 2)
+    out = np.zeros((rg.shape[0], 4), dtype=R) if bounds is None else np.array(bounds, dtype=R).reshape(-1, 4)
+    if out.shape[0] != rg.shape[0]:
+        raise ValueError("bounds must have one row per range")
+    tiny = np.ldexp(R(1.0), -80 if R == np.float32 else -918)          # MIN_NORMAL / EPSILON^2
+    grow = R(1.0) + R(8.0) * np.finfo(R).eps
+    half = R(0.5)
+    c, r = it[:, :3], it[:, 3]
+    lo_all, hi_all = c - r[:, None], c + r[:, None]
+    for g in range(rg.shape[0]):
+        first, count = int(rg[g, 0]), int(rg[g, 1])
+        if first < 0 or count < 0 or first + count > it.shape[0]:
+            raise ValueError("range %d lies outside the items" % g)
+        if count == 0:
+            continue
+        sl = slice(first, first + count)
+        centre = (lo_all[sl].min(axis=0) + hi_all[sl].max(axis=0)) * half
+        d = c[sl] - centre
+        s = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+        a = np.abs(d)
+        dist = np.where(s >= tiny, np.sqrt(s), (a[:, 0] + a[:, 1]) + a[:, 2])
+        out[g, :3] = centre
+        out[g, 3] = (dist + r[sl]).max() * grow
+    return out
+
+
 def pyramid(level, origin, radius, precision=capi.RT_F32):
     """SphericalGroup::pyramid (group.rs:58-65) -> (items REAL[n,4], bounds REAL[g,4], ranges int32[g,2]).
 
@@ -309,27 +343,102 @@ class Scene:
         return cls.from_spheres([(0.0, -1.0, 0.0, 1.0), (-1.2, 0.2, 0.0, 0.5), (1.2, 0.2, 0.0, 0.5)],
                                 (0.0, -1.0, 0.0, 3.0), precision=precision)
 
-    def device(self, device=0):
-        """Uploads once per device and caches the handle (replaces Arc<Scene> sharing, render.rs:279)."""
-        if device not in self._device:
-            self._device[device] = DeviceScene(self, device)
-        return self._device[device]
+    def device(self, device=0, dynamic=False):
+        """Uploads once per device and caches the handle (replaces Arc<Scene> sharing, render.rs:279).  dynamic=True: a scene whose spheres
+        DeviceScene.update replaces in place (rt_scene_create_dynamic; bounds=None with ranges: refit from the items), served by the
+        ray queries, trace and render_camera*; its own handle, cached apart from the immutable one."""
+        key = (device, True) if dynamic else device
+        if key not in self._device:
+            self._device[key] = DeviceScene(self, device, dynamic)
+        return self._device[key]
 
 
 class DeviceScene:
     """Owns an rt_scene* (device copies of a Scene)."""
 
-    def __init__(self, scene, device=0):
+    def __init__(self, scene, device=0, dynamic=False):
         self.scene = scene
         self.device = device
+        self.dynamic = bool(dynamic)
         h = C.c_void_p()
         nb = 0 if scene.bounds is None else scene.bounds.shape[0]
-        st = capi.lib.rt_scene_create(
-            device, scene.precision, scene.items.ctypes.data, scene.items.shape[0],
-            scene.directional_light.ctypes.data, scene.eye.ctypes.data,
-            scene.bounds.ctypes.data if nb else None, scene.ranges.ctypes.data if nb else None, nb, C.byref(h))
-        capi.check(st, "rt_scene_create")
+        if not dynamic:
+            st = capi.lib.rt_scene_create(
+                device, scene.precision, scene.items.ctypes.data, scene.items.shape[0],
+                scene.directional_light.ctypes.data, scene.eye.ctypes.data,
+                scene.bounds.ctypes.data if nb else None, scene.ranges.ctypes.data if nb else None, nb, C.byref(h))
+            capi.check(st, "rt_scene_create")
+        else:
+            # a dynamic scene may have ranges and no bounds: they are refit from the items
+            ng = 0 if scene.ranges is None else scene.ranges.shape[0]
+            if nb and nb != ng:
+                raise ValueError("bounds and ranges must have the same number of rows")
+            st = capi.lib.rt_scene_create_dynamic(
+                device, scene.precision, scene.items.ctypes.data, scene.items.shape[0],
+                scene.directional_light.ctypes.data, scene.eye.ctypes.data,
+                scene.bounds.ctypes.data if nb else None, scene.ranges.ctypes.data if ng else None, ng, C.byref(h))
+            capi.check(st, "rt_scene_create_dynamic")
         self._h = h
+        self._n_bounds = nb if not dynamic else (0 if scene.ranges is None else scene.ranges.shape[0])
+
+    def update(self, items, bounds=None, stream=None):
+        """rt_scene_update / rt_scene_update_device: new values for every sphere of a dynamic scene (n x 4, the scene's REAL dtype, the same
+        DFS order) and, optionally, for every bound (g x 4); bounds=None refits them on the device (refit_bounds is the rule).  numpy arrays
+        go through the host entry, which returns when the new scene is in place.  A torch tensor on this scene's device -- or a raw device
+        pointer as int -- goes through the device entry, enqueued on `stream` (a torch stream or a hipStream_t as int; default the
+        current torch stream) with the stream discipline of intersect(): queries on that stream see the new scene, other streams are the
+        caller's to order."""
+        R = _real(self.scene.precision)
+        n, g = self.scene.items.shape[0], self._n_bounds
+        torch = sys.modules.get("torch")
+        is_t = lambda x: torch is not None and isinstance(x, torch.Tensor)
+        if is_t(items) or isinstance(items, int):
+            if bounds is not None and not (is_t(bounds) or isinstance(bounds, int)):
+                raise ValueError("bounds must be device memory too (a tensor or a pointer), or None")
+            if torch is None:
+                import torch
+            tdt = torch.float32 if R == np.float32 else torch.float64
+            dev = torch.device("cuda", self.device)
+            for x, rows, what in ((items, n, "items"), (bounds, g, "bounds")):
+                if is_t(x) and (x.dtype != tdt or x.device != dev or x.numel() != 4 * rows):
+                    raise ValueError("%s must be a (%d, 4) %s tensor on %s" % (what, rows, tdt, dev))
+            cur = torch.cuda.current_stream(dev)
+            if stream is None:
+                qs = cur
+            elif isinstance(stream, torch.cuda.Stream):
+                qs = stream
+            else:
+                hs = int(stream)
+                qs = torch.cuda.default_stream(dev) if hs == 0 else torch.cuda.ExternalStream(hs, device=dev)
+            if qs != cur:
+                qs.wait_stream(cur)
+            with torch.cuda.stream(qs):
+                it = items.contiguous() if is_t(items) else items
+                bd = bounds.contiguous() if is_t(bounds) else bounds
+                ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr() if is_t(x) else x)
+                rc = capi.lib.rt_scene_update_device(self._h, ptr(it), ptr(bd), C.c_void_p(qs.cuda_stream))
+            for x in (it, bd, items, bounds):
+                if is_t(x):
+                    x.record_stream(qs)
+            capi.check(rc, "rt_scene_update_device")
+            return
+        it = np.asarray(items)
+        if it.dtype != R or it.size != 4 * n:
+            raise ValueError("items must be a (%d, 4) array of %s" % (n, np.dtype(R).name))
+        it = np.ascontiguousarray(it)
+        bd = None
+        if bounds is not None:
+            bd = np.asarray(bounds)
+            if bd.dtype != R or bd.size != 4 * g:
+                raise ValueError("bounds must be a (%d, 4) array of %s" % (g, np.dtype(R).name))
+            bd = np.ascontiguousarray(bd)
+        capi.check(capi.lib.rt_scene_update(self._h, it.ctypes.data, None if bd is None or g == 0 else bd.ctypes.data), "rt_scene_update")
+
+    def bounds(self):
+        """rt_scene_bounds -> REAL[g, 4]: the scene's current bounds (after the last update; an immutable scene: as created)."""
+        out = np.zeros((self._n_bounds, 4), dtype=_real(self.scene.precision))
+        capi.check(capi.lib.rt_scene_bounds(self._h, out.ctypes.data if self._n_bounds else None), "rt_scene_bounds")
+        return out
 
     def traits(self):
         """rt_scene_traits -> bit set of capi.RT_SCENE_HAS_BOUNDS / capi.RT_SCENE_CONCENTRIC."""
