@@ -450,6 +450,55 @@ rt_status rt_scene_update_device(rt_scene *scene, const void *dfs_items_device, 
  * scene from rt_scene_create reports the bounds it was created with. */
 rt_status rt_scene_bounds(rt_scene *scene, void *bounds_out);
 
+/* ---- rebuilds (additive to ABI 5): a dynamic scene's hierarchy rebuilt on the device from spheres in any order ----
+ * An update keeps every sphere in its DFS slot.  Once the spheres have moved far -- or come in an order that means nothing in space --
+ * the groups, which span fixed slots, are no longer compact and their refit bounds swell towards the scene's extent.  A REBUILD first
+ * puts the spheres in a spatial order and then refits: the topology (item words, skip offsets, ranges) stays the resident one.
+ *
+ * THE SPHERE KEY.  One 30-bit key per sphere from its centre c and the batch's centre box; radii take no part.  All of it in double (a
+ * float converts exactly), every operation rounded once:
+ *   lo[a], hi[a]  min / max of c[a] over the batch, a = 0, 1, 2;  ext = max(hi[a] - lo[a])
+ *   scale         0 if ext == 0 (every centre the same: every key is 0); else 2^(10 - e), e = max(E - 1022, -1000) with E the 11-bit
+ *                 biased exponent field of ext, so that ext < 2^e
+ *   q[a]          trunc(min(max((c[a] - lo[a]) * scale, 0), 1023))                                      10 bits per axis
+ *   key           the Morton code of q: bit i of q[a] is bit 3i + a of the key
+ * The SPHERE ORDER is the stable ascending sort of the keys (equal keys stay in the caller's order): unique, deterministic, a permutation
+ * of 0 .. n-1.  rust_tracer_amd.sphere_keys restates the key in numpy; the order is numpy.argsort(sphere_keys(spheres), kind="stable")
+ * bit for bit. */
+/* Host memory: spheres REAL[4*n] as {cx, cy, cz, r}, validated as rt_scene_create validates items (finite, |v| <= 1e15, radius > 0):
+ * RT_ERR_INVALID_ARGUMENT before the device is touched, also for a NULL scene, spheres or order_out and n == 0.  The scene supplies the
+ * device, REAL and the workspace, as for rt_ray_order; any scene will do, static or dynamic, and n need not be its item count.  Returns
+ * when order_out[0 .. n) is in place. */
+rt_status rt_sphere_order(rt_scene *scene, const void *spheres, uint32_t n, uint32_t *order_out);
+/* The same over DEVICE memory, enqueued on `hip_stream` without waiting for it: only pointers, alignment (spheres: one {cx, cy, cz, r}
+ * record, 16 bytes for RT_F32, 32 for RT_F64) and n are checked; the result is a permutation whatever bits the spheres hold, and nothing
+ * faults.  The temporary storage is the scene's and is reused once the stream has passed the call. */
+rt_status rt_sphere_order_device(rt_scene *scene, const void *spheres, uint32_t n, uint32_t *order_out, void *hip_stream);
+/* A topology that depends on the item count alone (host only, no device is touched): the groups of the recursive halving of
+ * (first, count) = (0, n_items), in DFS pre-order.  Emit (first, count); if count > leaf_size, go on with (first, (count + 1) / 2) and
+ * then with the remainder.  Leaves are groups too; there are at most 2 * n_items - 1 groups, and ranges_out has room for 2 * n_items.
+ * The output is valid for rt_scene_create and for rt_scene_create_dynamic with bounds == NULL as it stands.  Over spheres in the sphere
+ * order it is a median-split tree along the Morton curve.  n_items == 0 (or above 2^31 - 1), leaf_size == 0 or a NULL pointer:
+ * RT_ERR_INVALID_ARGUMENT. */
+rt_status rt_balanced_ranges(uint32_t n_items, uint32_t leaf_size, rt_range *ranges_out, uint32_t *n_groups_out);
+/* The rebuild, HOST memory: spheres REAL[4*n_items] in ANY order, order_out uint32[n_items] or NULL.  Exactly
+ * rt_scene_update(scene, spheres[order], NULL) with order = the sphere order of `spheres`: DFS slot k now holds spheres[order[k]] and
+ * order_out[k] = order[k]; every group bound is refit by the rule above over the scene's own ranges, whatever ranges it was created
+ * with (rt_balanced_ranges is the companion that makes the result a good hierarchy, not a precondition) and whether its bounds were
+ * the caller's or refit.  Afterwards every general-ray entry and rt_scene_bounds answer with the bytes and counters of a scene made by
+ * rt_scene_create from spheres[order], those bounds and the same ranges; item_out values are DFS slots as always, and order_out maps
+ * them back to the caller's indices.  Validated as rt_scene_update validates (RT_ERR_INVALID_ARGUMENT before the device is touched, the
+ * scene unchanged); takes the scene's write lock as a host update does; returns when the new scene is in place.  RT_ERR_UNSUPPORTED on a
+ * scene from rt_scene_create, and on a dynamic scene created with n_bounds == 0 (nothing to refit: rt_last_error_message says so). */
+rt_status rt_scene_rebuild(rt_scene *scene, const void *spheres, uint32_t *order_out);
+/* The same from DEVICE memory, enqueued on `hip_stream` without waiting for it, a WRITE in the sense of ORDER above: no host
+ * synchronisation, and no allocation except that the first rebuild of a scene makes that scene's rebuild workspace (sized by n_items
+ * alone, kept with the scene, freed with it; rebuilds of one scene on different streams are the caller's to order, as all writes are).
+ * Only the pointers and their alignment (spheres: one record; order_out: 4 bytes) are checked.  Skip offsets and item words still come
+ * from the resident topology alone: any bits in the spheres give unspecified values in the results of later queries, never a fault or
+ * an endless walk, and order_out is a permutation of 0 .. n_items-1 all the same. */
+rt_status rt_scene_rebuild_device(rt_scene *scene, const void *spheres_device, uint32_t *order_out_device_or_null, void *hip_stream);
+
 /* Bytes rt_render_tiles writes for this tile list (4 * total area), or 0 on an invalid list. */
 uint64_t rt_tiles_rgba_bytes(const rt_region *tiles, uint32_t n_tiles);
 

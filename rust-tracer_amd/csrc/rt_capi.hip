@@ -20,6 +20,7 @@
 #include "rt_multihit.hpp"
 #include "rt_order.hpp"
 #include "rt_dynamic.hpp"
+#include "rt_rebuild.hpp"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>       // types and prototypes only: librccl.so is loaded with dlopen when the first gang is created
@@ -273,6 +274,8 @@ struct rt_scene {
     void *d_stage = nullptr;           // a host update's items and bounds on their way in: REAL[4 n_items], REAL[4 n_bounds] behind them
     size_t stage_bounds_off = 0;
     hipEvent_t upd_ev = nullptr;       // behind the last update
+    void *d_rebuild = nullptr;         // rt_scene_rebuild*: the sort's workspace for n_items keys and the gathered items behind it (rt_rebuild.hpp), made by the first rebuild
+    std::mutex rebuild_mu;             // (two first rebuilds at once make it once)
 };
 
 namespace {

@@ -294,6 +294,7 @@ rt_status rt_scene_destroy(rt_scene *s)
         if (s->cost_stream) (void)hipStreamSynchronize(s->cost_stream);
         if (s->d_dyn) (void)hipFree(s->d_dyn);
         if (s->upd_ev) (void)hipEventDestroy(s->upd_ev);
+        if (s->d_rebuild) (void)hipFree(s->d_rebuild);
     }
     if (s->d_items) (void)hipFree(s->d_items);
     if (s->d_prim) (void)hipFree(s->d_prim);
@@ -1332,6 +1333,139 @@ rt_status rt_ray_order(rt_scene *s, const void *rays, uint32_t n, uint32_t *orde
         return drain(hip_fail(e, "hipMemcpyAsync", __LINE__));
     if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize", __LINE__);
     return RT_OK;
+}
+
+// ---- sphere orders, balanced ranges and rebuilds: a dynamic scene's hierarchy rebuilt on the device (rt_rebuild.hpp) ----
+
+// A topology from the item count alone: DFS pre-order of the halving of (0, n_items) down to leaf_size.  No device is touched.
+rt_status rt_balanced_ranges(uint32_t n_items, uint32_t leaf_size, rt_range *ranges_out, uint32_t *n_groups_out)
+{
+    if (n_items == 0 || leaf_size == 0 || !ranges_out || !n_groups_out || n_items > 0x7FFFFFFFu) {
+        snprintf(g_err, sizeof g_err, "rt_balanced_ranges: NULL argument, n_items == 0 (or above 2^31 - 1) or leaf_size == 0");
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    uint32_t groups = 0, depth = 0;
+    struct { uint32_t first, count; } todo[64];                      // the right halves still to emit: one per level, the levels are < 33
+    todo[depth++] = { 0u, n_items };
+    while (depth) {
+        const uint32_t first = todo[depth - 1].first, count = todo[depth - 1].count;
+        --depth;
+        ranges_out[groups++] = rt_range{ (int32_t)first, (int32_t)count };
+        if (count > leaf_size) {
+            const uint32_t left = count / 2 + (count & 1u);          // (count + 1) / 2 without the carry
+            todo[depth++] = { first + left, count - left };
+            todo[depth++] = { first, left };
+        }
+    }
+    *n_groups_out = groups;
+    return RT_OK;
+}
+
+// spheres and order_out as both rt_sphere_order entries check them; `align`: what a spheres pointer must be a multiple of.
+static bool sphere_order_args_ok(const rt_scene *s, const void *spheres, uint32_t n, const uint32_t *order_out, uintptr_t align, const char *what)
+{
+    if (!s || !spheres || !order_out || n == 0) { snprintf(g_err, sizeof g_err, "%s: NULL scene, spheres or order_out, or n == 0", what); return false; }
+    if ((reinterpret_cast<uintptr_t>(spheres) % align) != 0) { snprintf(g_err, sizeof g_err, "%s: spheres must be %u-byte aligned", what, (unsigned)align); return false; }
+    if ((reinterpret_cast<uintptr_t>(order_out) & 3u) != 0) { snprintf(g_err, sizeof g_err, "%s: order_out must be 4-byte aligned", what); return false; }
+    return true;
+}
+
+rt_status rt_sphere_order_device(rt_scene *s, const void *spheres, uint32_t n, uint32_t *order_out, void *hip_stream)
+{
+    const uintptr_t record = s ? (s->precision == RT_F32 ? sizeof(float) : sizeof(double)) * 4 : 16;      // one {cx, cy, cz, r}: the kernels load it whole
+    if (!sphere_order_args_ok(s, spheres, n, order_out, record, "rt_sphere_order_device")) return RT_ERR_INVALID_ARGUMENT;
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    Context *c = nullptr;
+    rt_status st = acquire(s, &c);
+    if (st != RT_OK) return st;
+    Lease lease{ s, c };
+    const uint32_t *used = nullptr;
+    st = enqueue_sphere_order(s, c, spheres, n, order_out, stream, &used);
+    (void)hipEventRecord(c->ev1, stream);               // (the context goes back behind what is enqueued: its workspace is in use until then)
+    if (st != RT_OK) (void)hipGetLastError();
+    lease.inflight = true;
+    return st;
+}
+
+rt_status rt_sphere_order(rt_scene *s, const void *spheres, uint32_t n, uint32_t *order_out)
+{
+    const uintptr_t esz = s && s->precision == RT_F64 ? sizeof(double) : sizeof(float);
+    if (!sphere_order_args_ok(s, spheres, n, order_out, esz, "rt_sphere_order")) return RT_ERR_INVALID_ARGUMENT;
+    if (!(s->precision == RT_F32 ? items_valid<float>(spheres, n, true) : items_valid<double>(spheres, n, true))) {
+        snprintf(g_err, sizeof g_err, "rt_sphere_order: spheres must be finite, |v| <= 1e15, radius > 0");
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    HIP_TRY(hipSetDevice(s->device));
+    if (classify_host_pointer(spheres).bad || classify_host_pointer(order_out).bad) {
+        snprintf(g_err, sizeof g_err, "rt_sphere_order: a buffer is device memory; use rt_sphere_order_device");
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    // both buffers go through the call's workspace: the spheres up, the order back
+    const size_t in_bytes = 4 * esz * n, out_off = (in_bytes + 255) & ~(size_t)255, need = out_off + ((sizeof(uint32_t) * n + 255) & ~(size_t)255);
+    Context *c = nullptr;
+    rt_status st = acquire(s, &c);
+    if (st != RT_OK) return st;
+    Lease lease{ s, c };
+    if (need > c->query_cap) {
+        if (c->d_query) HIP_TRY(hipFree(c->d_query));
+        c->d_query = nullptr; c->query_cap = 0;
+        HIP_TRY(hipMalloc(&c->d_query, need));
+        c->query_cap = need;
+    }
+    uint8_t *const d_in = static_cast<uint8_t *>(c->d_query), *const d_out = d_in + out_off;
+    // from the first copy on, work of this call may be queued: an error return first waits for it
+    auto drain = [&](rt_status code) { (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return code; };
+    hipError_t e = hipSuccess;
+    if ((e = hipMemcpyAsync(d_in, spheres, in_bytes, hipMemcpyHostToDevice, c->stream)) != hipSuccess) return drain(hip_fail(e, "hipMemcpyAsync", __LINE__));
+    const uint32_t *used = nullptr;
+    if ((st = enqueue_sphere_order(s, c, d_in, n, reinterpret_cast<uint32_t *>(d_out), c->stream, &used)) != RT_OK) return drain(st);
+    if ((e = hipMemcpyAsync(order_out, d_out, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, c->stream)) != hipSuccess) return drain(hip_fail(e, "hipMemcpyAsync", __LINE__));
+    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize", __LINE__);
+    return RT_OK;
+}
+
+rt_status rt_scene_rebuild(rt_scene *s, const void *spheres, uint32_t *order_out)
+{
+    if (rt_status ast = rebuild_scene_ok(s, spheres, "rt_scene_rebuild"); ast != RT_OK) return ast;
+    const size_t esz = s->precision == RT_F32 ? sizeof(float) : sizeof(double);
+    if ((reinterpret_cast<uintptr_t>(spheres) % esz) != 0 || (reinterpret_cast<uintptr_t>(order_out) & 3u) != 0) {
+        snprintf(g_err, sizeof g_err, "rt_scene_rebuild: spheres must be %u-byte and order_out 4-byte aligned", (unsigned)esz);
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    if (!(s->precision == RT_F32 ? items_valid<float>(spheres, s->n_items, true) : items_valid<double>(spheres, s->n_items, true))) {
+        snprintf(g_err, sizeof g_err, "rt_scene_rebuild: spheres must be finite, |v| <= 1e15, radius > 0; the scene is unchanged");
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    std::unique_lock<std::shared_mutex> lk(s->dyn_mu);               // as a host update: every host call under way has returned, none starts before this one has
+    HIP_TRY(hipSetDevice(s->device));
+    // the spheres into the scene's staging as a host update's items go, the rebuild behind them on the scene's stream
+    memcpy(s->h_up, spheres, esz * 4 * s->n_items);
+    HIP_TRY(hipStreamWaitEvent(s->cost_stream, s->upd_ev, 0));       // (a device rebuild still in flight on another stream is using the rebuild workspace)
+    rt_status st = upload_words(s->d_stage, s->h_up, esz * 4 * s->n_items, s->cost_stream);
+    const uint32_t *used = nullptr;
+    if (st == RT_OK) st = enqueue_rebuild(s, s->d_stage, nullptr, s->cost_stream, &used);
+    hipError_t e = hipSuccess;
+    if (st == RT_OK && order_out) e = hipMemcpyAsync(order_out, used, sizeof(uint32_t) * s->n_items, hipMemcpyDeviceToHost, s->cost_stream);
+    const hipError_t se = hipStreamSynchronize(s->cost_stream);
+    if (st != RT_OK) { (void)hipGetLastError(); return st; }
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(order)", __LINE__);
+    if (se != hipSuccess) return hip_fail(se, "hipStreamSynchronize(rebuild)", __LINE__);
+    return RT_OK;
+}
+
+rt_status rt_scene_rebuild_device(rt_scene *s, const void *spheres_device, uint32_t *order_out_device, void *hip_stream)
+{
+    if (rt_status ast = rebuild_scene_ok(s, spheres_device, "rt_scene_rebuild_device"); ast != RT_OK) return ast;
+    const uintptr_t align = (s->precision == RT_F32 ? sizeof(float) : sizeof(double)) * 4;      // one {cx, cy, cz, r} record: the kernels load it whole
+    if ((reinterpret_cast<uintptr_t>(spheres_device) % align) != 0 || (reinterpret_cast<uintptr_t>(order_out_device) & 3u) != 0) {
+        snprintf(g_err, sizeof g_err, "rt_scene_rebuild_device: spheres must be %u-byte and order_out 4-byte aligned", (unsigned)align);
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    const ReadLock rl(s);                                            // (not while a host update is replacing the scene)
+    HIP_TRY(hipSetDevice(s->device));
+    const uint32_t *used = nullptr;
+    return enqueue_rebuild(s, spheres_device, order_out_device, static_cast<hipStream_t>(hip_stream), &used);
 }
 
 // Shared body of both rt_render_camera entries: the frame into d_out (tile-major, 4 * total_px bytes) on `stream` through a leased

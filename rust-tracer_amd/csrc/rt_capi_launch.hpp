@@ -982,6 +982,94 @@ rt_status enqueue_ray_order(const rt_scene *s, Context *c, const void *rays, uin
     return RT_OK;
 }
 
+// ---- sphere orders and rebuilds (rt_sphere_order*, rt_scene_rebuild*; rt_rebuild.hpp) ----
+
+// The Morton order of n device spheres on `stream`, through `workspace` (sort_layout(n).bytes of device memory: a context's d_sort or a
+// scene's rebuild workspace).  order_out: device memory, or NULL for the workspace's own slot; *order_used is where the order ends up.
+template <typename T>
+rt_status enqueue_sphere_order(void *workspace, const void *spheres, uint32_t n, uint32_t *order_out, hipStream_t stream, const uint32_t **order_used)
+{
+    const SortLayout l = sort_layout(n);
+    uint8_t *const w = static_cast<uint8_t *>(workspace);
+    rt::SortArgs a{};
+    for (int k = 0; k < 2; ++k) { a.keys[k] = reinterpret_cast<unsigned *>(w + l.keys[k]); a.idx[k] = reinterpret_cast<unsigned *>(w + l.idx[k]); }
+    a.table = reinterpret_cast<unsigned *>(w + l.table);
+    rt::SortPlan *const plan = reinterpret_cast<rt::SortPlan *>(w + l.plan);
+    a.plan = plan;
+    a.order_out = order_out ? order_out : reinterpret_cast<unsigned *>(w + l.order);
+    a.n = n; a.per_block = l.per_block; a.n_blocks = l.n_blocks;
+    unsigned *const totals = reinterpret_cast<unsigned *>(w + l.totals);
+    a.totals = totals;
+    rt::RayBox *const box = reinterpret_cast<rt::RayBox *>(w + l.box);
+    HIP_TRY(hipMemsetAsync(w, 0, l.head_bytes, stream));
+    const dim3 wide((unsigned)std::min<uint64_t>(((uint64_t)n + rt::kSortThreads - 1) / rt::kSortThreads, rt::kSortMaxBlocks)), block(rt::kSortThreads);
+    hipLaunchKernelGGL(rt::k_sphere_box<T>, wide, block, 0, stream, static_cast<const rt::Item<T> *>(spheres), n, box);
+    hipLaunchKernelGGL(rt::k_sphere_keys<T>, wide, block, 0, stream, static_cast<const rt::Item<T> *>(spheres), n, box, a.keys[0], totals);
+    hipLaunchKernelGGL(rt::k_sort_plan, dim3(1), block, 0, stream, totals, n, plan);
+    for (unsigned pass = 0; pass < 4; ++pass) {
+        hipLaunchKernelGGL(rt::k_sort_hist, dim3(l.n_blocks), block, 0, stream, a, pass);
+        hipLaunchKernelGGL(rt::k_sort_scan, dim3(256), block, 0, stream, a, pass);
+        hipLaunchKernelGGL(rt::k_sort_scatter, dim3(l.n_blocks), block, 0, stream, a, pass);
+    }
+    HIP_TRY(hipGetLastError());
+    *order_used = a.order_out;
+    return RT_OK;
+}
+
+// The same through a leased context's sort workspace, grown on demand (as enqueue_ray_order grows it).
+rt_status enqueue_sphere_order(const rt_scene *s, Context *c, const void *spheres, uint32_t n, uint32_t *order_out, hipStream_t stream, const uint32_t **order_used)
+{
+    const size_t bytes = sort_layout(n).bytes;
+    if (c->sort_cap < bytes) {
+        if (c->d_sort) HIP_TRY(hipFree(c->d_sort));
+        c->d_sort = nullptr; c->sort_cap = 0;
+        HIP_TRY(hipMalloc(&c->d_sort, bytes));
+        c->sort_cap = bytes;
+    }
+    return s->precision == RT_F32 ? enqueue_sphere_order<float>(c->d_sort, spheres, n, order_out, stream, order_used)
+                                  : enqueue_sphere_order<double>(c->d_sort, spheres, n, order_out, stream, order_used);
+}
+
+// What both rebuild entries check of the scene: a dynamic scene with groups to refit.
+rt_status rebuild_scene_ok(const rt_scene *s, const void *spheres, const char *what)
+{
+    if (!s || !spheres) { snprintf(g_err, sizeof g_err, "%s: NULL scene or spheres", what); return RT_ERR_INVALID_ARGUMENT; }
+    if (!s->dynamic) {
+        snprintf(g_err, sizeof g_err, "%s: the scene was made by rt_scene_create and is immutable; rt_scene_create_dynamic makes one that can be rebuilt", what);
+        return RT_ERR_UNSUPPORTED;
+    }
+    if (s->n_bounds == 0) {
+        snprintf(g_err, sizeof g_err, "%s: the scene was created with n_bounds == 0: a flat scene has no group to refit, so an order changes nothing it walks", what);
+        return RT_ERR_UNSUPPORTED;
+    }
+    return RT_OK;
+}
+
+// One rebuild on `stream`: the order of the spheres at `src` (device memory), the gather into the scene's rebuild staging, the refit
+// update over the gathered items.  The scene's rebuild workspace -- the sort's, sized by n_items alone, and the staging behind it -- is
+// made by the first rebuild and freed with the scene; from then on nothing is allocated and nothing waited for.
+template <typename T>
+rt_status enqueue_rebuild(rt_scene *s, const void *src, uint32_t *order_out, hipStream_t stream, const uint32_t **order_used)
+{
+    const size_t sort_bytes = sort_layout(s->n_items).bytes;
+    {
+        std::lock_guard<std::mutex> lk(s->rebuild_mu);
+        if (!s->d_rebuild) HIP_TRY(hipMalloc(&s->d_rebuild, sort_bytes + sizeof(rt::Item<T>) * s->n_items));
+    }
+    rt::Item<T> *const staged = reinterpret_cast<rt::Item<T> *>(static_cast<uint8_t *>(s->d_rebuild) + sort_bytes);      // (sort_bytes is a multiple of 256)
+    if (rt_status st = enqueue_sphere_order<T>(s->d_rebuild, src, s->n_items, order_out, stream, order_used); st != RT_OK) return st;
+    hipLaunchKernelGGL(rt::k_gather_items<T>, dim3((s->n_items + rt::kBlockThreads - 1) / rt::kBlockThreads), dim3(rt::kBlockThreads), 0, stream,
+                       static_cast<const rt::Item<T> *>(src), *order_used, s->n_items, staged);
+    HIP_TRY(hipGetLastError());
+    return enqueue_dynamic_update<T>(s, staged, nullptr, stream);
+}
+
+rt_status enqueue_rebuild(rt_scene *s, const void *src, uint32_t *order_out, hipStream_t stream, const uint32_t **order_used)
+{
+    return s->precision == RT_F32 ? enqueue_rebuild<float>(s, src, order_out, stream, order_used)
+                                  : enqueue_rebuild<double>(s, src, order_out, stream, order_used);
+}
+
 // ---- undersampled camera frames (rt_render_camera_undersampled*, rt_undersample.hpp) ----
 
 // step in [1, RT_UNDERSAMPLE_MAX_STEP]; prev_step 0 (a fresh frame) or exactly 2 * step (a refinement of the step-2s frame in the buffer).

@@ -58,6 +58,60 @@ def ray_keys(rays):
     return (m3 << np.uint32(23)) | ((np.uint32(2) * axis.astype(np.uint32) + sign) << np.uint32(20)) | m2
 
 
+def sphere_keys(spheres):
+    """The 30-bit sort key rt_sphere_order gives each sphere of `spheres` (n x 4: cx, cy, cz, r; float32 or float64) -> uint32[n], restated in
+    numpy operation for operation (include/rtrace_hip.h states it): the sphere order, and the order rt_scene_rebuild puts the spheres in, is
+    np.argsort(sphere_keys(spheres), kind="stable").  The Morton code of the centre's cell in the batch's own centre box, 1024 cells per
+    axis; the radii take no part, and a batch whose centres are all the same has every key 0."""
+    s = np.asarray(spheres)
+    if s.ndim != 2 or s.shape[1] != 4 or s.shape[0] == 0 or s.dtype not in (np.float32, np.float64):
+        raise ValueError("spheres must be a non-empty (n, 4) array of float32 or float64")
+    c = s[:, :3].astype(np.float64)                                      # exact
+    lo, hi = c.min(axis=0), c.max(axis=0)
+    ext = np.float64((hi - lo).max())
+    scale = np.float64(0.0)
+    if ext > 0.0:
+        e = max((int(ext.view(np.uint64)) >> 52 & 0x7FF) - 1022, -1000)   # ext < 2^e
+        scale = np.ldexp(np.float64(1.0), 10 - e)
+    q = np.minimum(np.maximum((c - lo) * scale, 0.0), 1023.0).astype(np.uint32)
+    key = np.zeros(len(c), dtype=np.uint32)
+    for i in range(10):
+        for a in range(3):
+            key |= ((q[:, a] >> np.uint32(i)) & np.uint32(1)) << np.uint32(3 * i + a)
+    return key
+
+
+def balanced_ranges(n, leaf_size=4):
+    """rt_balanced_ranges: a topology from the item count alone -> int32[g, 2], the groups (first item, item count) of the recursive halving
+    of (0, n) down to `leaf_size`, in DFS pre-order (a group's first half holds (count + 1) // 2 items; leaves are groups too).  Valid as
+    the `ranges` of a Scene as it stands; over spheres in the sphere order it is a median-split tree along the Morton curve, which is what
+    DeviceScene.rebuild keeps a dynamic scene in.  balanced_ranges_reference restates it in numpy."""
+    n, leaf_size = int(n), int(leaf_size)
+    if not 0 <= n <= 0xFFFFFFFF or not 0 <= leaf_size <= 0xFFFFFFFF:
+        raise ValueError("n and leaf_size must fit 32 bits")
+    ranges = np.zeros((2 * max(n, 1), 2), dtype=np.int32)
+    ng = C.c_uint32(0)
+    capi.check(capi.lib.rt_balanced_ranges(n, leaf_size, ranges.ctypes.data, C.byref(ng)), "rt_balanced_ranges")
+    return ranges[:int(ng.value)].copy()
+
+
+def balanced_ranges_reference(n, leaf_size=4):
+    """The rule of rt_balanced_ranges in plain Python (test infrastructure).  Same return value as balanced_ranges."""
+    if n < 1 or leaf_size < 1:
+        raise ValueError("balanced_ranges needs at least one item and a leaf size of at least 1")
+    out = []
+
+    def emit(first, count):
+        out.append((first, count))
+        if count > leaf_size:
+            left = (count + 1) // 2
+            emit(first, left)
+            emit(first + left, count - left)
+
+    emit(0, int(n))
+    return np.asarray(out, dtype=np.int32).reshape(-1, 2)
+
+
 def refit_bounds(items, ranges, precision=capi.RT_F32, bounds=None):
     """The bounds rt_scene_update refits for `items` (n x 4: cx, cy, cz, r) over `ranges` (g x 2: first item, item count) -> REAL[g, 4],
     the rule of include/rtrace_hip.h restated in numpy bit for bit: every operation in REAL, rounded once.  Per group: lo / hi = min / max
@@ -338,6 +392,14 @@ class Scene:
         return cls(items, normalized(light, precision), eye, bounds, ranges, precision)
 
     @classmethod
+    def from_spheres_balanced(cls, spheres, light=(-1.0, -3.0, 2.0), eye=(0.0, 0.0, -4.0), leaf_size=4, precision=capi.RT_F32):
+        """Arbitrary sphere list, in the caller's order, under the topology of balanced_ranges and with NO bounds: for
+        .device(dynamic=True) -- which refits the bounds -- followed by DeviceScene.rebuild, which puts the spheres in Morton order and is
+        what makes this topology a hierarchy worth walking."""
+        items = np.asarray(spheres, dtype=np.float64).reshape(-1, 4)
+        return cls(items, normalized(light, precision), eye, None, balanced_ranges(items.shape[0], leaf_size), precision)
+
+    @classmethod
     def three_spheres(cls, precision=capi.RT_F32):
         """The build-defined config-1 scene."""
         return cls.from_spheres([(0.0, -1.0, 0.0, 1.0), (-1.2, 0.2, 0.0, 0.5), (1.2, 0.2, 0.0, 0.5)],
@@ -433,6 +495,80 @@ class DeviceScene:
                 raise ValueError("bounds must be a (%d, 4) array of %s" % (g, np.dtype(R).name))
             bd = np.ascontiguousarray(bd)
         capi.check(capi.lib.rt_scene_update(self._h, it.ctypes.data, None if bd is None or g == 0 else bd.ctypes.data), "rt_scene_update")
+
+    def _device_stream(self, torch, stream):
+        """(the torch stream a device entry is enqueued on, the current one) for `stream`: None, a torch stream or a hipStream_t as int."""
+        dev = torch.device("cuda", self.device)
+        cur = torch.cuda.current_stream(dev)
+        if stream is None:
+            return cur, cur
+        if isinstance(stream, torch.cuda.Stream):
+            return stream, cur
+        hs = int(stream)
+        return (torch.cuda.default_stream(dev) if hs == 0 else torch.cuda.ExternalStream(hs, device=dev)), cur
+
+    def _spheres_arg(self, spheres, n, what):
+        """`spheres` for a sphere order or a rebuild: (True, contiguous tensor) for a torch tensor on this scene's device, (False, contiguous
+        numpy array) otherwise; n: the number of rows it must have, or None for any."""
+        R = _real(self.scene.precision)
+        torch = sys.modules.get("torch")
+        if torch is not None and isinstance(spheres, torch.Tensor):
+            tdt = torch.float32 if R == np.float32 else torch.float64
+            dev = torch.device("cuda", self.device)
+            if spheres.dtype != tdt or spheres.dim() != 2 or spheres.shape[1] != 4 or spheres.shape[0] == 0 or spheres.device != dev or (n is not None and spheres.shape[0] != n):
+                raise ValueError("%s: spheres must be a (%s, 4) %s tensor on %s" % (what, "n" if n is None else n, tdt, dev))
+            return True, spheres
+        if not isinstance(spheres, np.ndarray) or spheres.dtype != R or spheres.ndim != 2 or spheres.shape[1] != 4 or spheres.shape[0] == 0 or (n is not None and spheres.shape[0] != n):
+            raise ValueError("%s: spheres must be a (%s, 4) numpy array of %s (or a torch tensor on the scene's device)" % (what, "n" if n is None else n, np.dtype(R).name))
+        return False, np.ascontiguousarray(spheres)
+
+    def sphere_order(self, spheres, stream=None):
+        """rt_sphere_order / rt_sphere_order_device: the Morton order of `spheres` (n x 4, the scene's REAL dtype; any n), computed on the
+        device -> uint32[n]: np.argsort(sphere_keys(spheres), kind="stable").  numpy in, numpy out; a torch tensor on this scene's device goes
+        through the device entry on `stream` (as ray_order routes) and gives a torch.uint32 tensor."""
+        is_t, sp = self._spheres_arg(spheres, None, "sphere_order")
+        n = sp.shape[0]
+        if not is_t:
+            order = np.empty(n, dtype=np.uint32)
+            capi.check(capi.lib.rt_sphere_order(self._h, sp.ctypes.data, n, order.ctypes.data), "rt_sphere_order")
+            return order
+        import torch
+        qs, cur = self._device_stream(torch, stream)
+        if qs != cur:
+            qs.wait_stream(cur)
+        with torch.cuda.stream(qs):
+            t = sp.contiguous()
+            order = torch.empty(n, dtype=torch.uint32, device=t.device)
+            rc = capi.lib.rt_sphere_order_device(self._h, C.c_void_p(t.data_ptr()), n, C.c_void_p(order.data_ptr()), C.c_void_p(qs.cuda_stream))
+        if qs != cur:
+            spheres.record_stream(qs)
+        capi.check(rc, "rt_sphere_order_device")
+        return order
+
+    def rebuild(self, spheres, stream=None):
+        """rt_scene_rebuild / rt_scene_rebuild_device: the hierarchy of a dynamic scene rebuilt from `spheres` (n_items x 4, the scene's REAL
+        dtype) in ANY order -> the order, uint32[n_items]: DFS slot k now holds spheres[order[k]] (what a query's item index names), every
+        bound is refit, and the scene answers as a fresh one made from spheres[order], bounds() and the same ranges.  order is
+        np.argsort(sphere_keys(spheres), kind="stable").  numpy goes through the host entry, which returns when the new scene is in place;
+        a torch tensor on this scene's device goes through the device entry, enqueued on `stream` with the discipline of update()."""
+        n = self.scene.items.shape[0]
+        is_t, sp = self._spheres_arg(spheres, n, "rebuild")
+        if not is_t:
+            order = np.empty(n, dtype=np.uint32)
+            capi.check(capi.lib.rt_scene_rebuild(self._h, sp.ctypes.data, order.ctypes.data), "rt_scene_rebuild")
+            return order
+        import torch
+        qs, cur = self._device_stream(torch, stream)
+        if qs != cur:
+            qs.wait_stream(cur)
+        with torch.cuda.stream(qs):
+            t = sp.contiguous()
+            order = torch.empty(n, dtype=torch.uint32, device=t.device)
+            rc = capi.lib.rt_scene_rebuild_device(self._h, C.c_void_p(t.data_ptr()), C.c_void_p(order.data_ptr()), C.c_void_p(qs.cuda_stream))
+        for x in (t, spheres):
+            x.record_stream(qs)
+        capi.check(rc, "rt_scene_rebuild_device")
+        return order
 
     def bounds(self):
         """rt_scene_bounds -> REAL[g, 4]: the scene's current bounds (after the last update; an immutable scene: as created)."""
