@@ -499,6 +499,45 @@ rt_status rt_scene_rebuild(rt_scene *scene, const void *spheres, uint32_t *order
  * an endless walk, and order_out is a permutation of 0 .. n_items-1 all the same. */
 rt_status rt_scene_rebuild_device(rt_scene *scene, const void *spheres_device, uint32_t *order_out_device_or_null, void *hip_stream);
 
+/* ---- live and dead slots (additive to ABI 5): a dynamic scene's n_items is a CAPACITY ----
+ * Every slot of a dynamic scene is LIVE or DEAD.  Every entry above leaves every slot live; the entries below say which are.
+ *   A DEAD ITEM is never hit: no general-ray entry (rt_intersect_rays*, rt_intersect_rays_multi*, rt_trace_rays* -- primary and shadow
+ * walk --, rt_render_camera*, rt_render_camera_undersampled*, the *_ordered forms) reports its slot, its distance or a normal from it.
+ * Its node stays in the hierarchy -- the topology is fixed --, so a walk that reaches it tests it, counts it in sphere_tests /
+ * tests_executed, and misses.  Its values are never read into any result or bound: a dead slot may hold any bits, NaN included.
+ *   THE REFIT RULE runs over a group's LIVE items only (steps 1, 2 and 4); min and max stay exact, so the result is still independent of
+ * order and split, and rust_tracer_amd.refit_bounds(..., live=) restates it bit for bit.  A group without a live item is a DEAD GROUP:
+ * its node culls its subtree for every ray at the cost of one bound test, and rt_scene_bounds reports {0, 0, 0, 0} for it (radius 0 is no
+ * valid bound: it marks the group).  The caller's bounds (bounds != NULL) are validated and written as given; enclosing the live items
+ * is then the caller's business, and the dead items under them are still never hit.
+ *   After any of these calls the scene writes the bytes and counters of a scene made by rt_scene_create from the same ranges, with any
+ * sphere no ray can reach in each dead slot and as each dead group's bound.  They are WRITES in the sense of ORDER above; a later
+ * rt_scene_update* or rt_scene_rebuild* makes every slot live again. */
+/* rt_scene_update with liveness, HOST memory: live is uint8[n_items], nonzero = live; NULL = every slot live, and the call is then exactly
+ * rt_scene_update.  Only the live items are validated.  A flat dynamic scene (n_bounds == 0) takes liveness too.  RT_ERR_UNSUPPORTED on
+ * a scene from rt_scene_create. */
+rt_status rt_scene_update_live(rt_scene *scene, const void *dfs_items, const void *bounds, const uint8_t *live);
+/* The same from DEVICE memory, under rt_scene_update_device's rules: pointers and alignment alone are checked, nothing is allocated or
+ * waited for, and any bits in the items or the liveness bytes give unspecified query results, never a fault or an endless walk. */
+rt_status rt_scene_update_live_device(rt_scene *scene, const void *dfs_items_device, const void *bounds_device_or_null,
+                                      const uint8_t *live_device_or_null, void *hip_stream);
+/* rt_scene_rebuild of n spheres into a scene of capacity n_items, 0 <= n <= n_items; HOST memory, spheres REAL[4*n] in ANY order,
+ * order_out uint32[n] or NULL.  By contract rt_scene_update_live(scene, X, NULL, L) with order = the sphere order of the n spheres (the
+ * same key, the same stable sort, over n records), X[k] = spheres[order[k]] and L[k] = 1 for k < n, slots k >= n dead; order_out[k] =
+ * order[k] for k < n.  With n == n_items it is rt_scene_rebuild, byte for byte.  n == 0 empties the scene -- every query misses -- and
+ * spheres may then be NULL: the one place where n == 0 is no error.  Over rt_balanced_ranges the live prefix is covered by live groups
+ * and everything to its right is dead groups, culled at their first node.  NULL spheres with n > 0 and n > n_items are
+ * RT_ERR_INVALID_ARGUMENT before the device is touched; RT_ERR_UNSUPPORTED as for rt_scene_rebuild (a scene from rt_scene_create, a flat
+ * dynamic scene). */
+rt_status rt_scene_rebuild_n(rt_scene *scene, const void *spheres, uint32_t n, uint32_t *order_out);
+/* The same from DEVICE memory, under rt_scene_rebuild_device's rules: no host synchronisation, and no allocation beyond the scene's
+ * rebuild workspace, which is sized by the capacity. */
+rt_status rt_scene_rebuild_n_device(rt_scene *scene, const void *spheres_device, uint32_t n, uint32_t *order_out_device_or_null,
+                                    void *hip_stream);
+/* The current liveness, uint8[n_items] of 0 / 1 into host memory, after waiting for the last write as rt_scene_bounds does.  A scene
+ * from rt_scene_create reports all ones. */
+rt_status rt_scene_live(rt_scene *scene, uint8_t *live_out);
+
 /* Bytes rt_render_tiles writes for this tile list (4 * total area), or 0 on an invalid list. */
 uint64_t rt_tiles_rgba_bytes(const rt_region *tiles, uint32_t n_tiles);
 

@@ -36,7 +36,8 @@ SYMBOLS = ("rt_abi_version", "rt_build_hierarchy", "rt_device_count", "rt_scene_
            "rt_ray_order", "rt_ray_order_device", "rt_intersect_rays_ordered", "rt_intersect_rays_ordered_device",
            "rt_intersect_rays_multi_ordered", "rt_intersect_rays_multi_ordered_device", "rt_trace_rays_ordered", "rt_trace_rays_ordered_device",
            "rt_scene_create_dynamic", "rt_scene_update", "rt_scene_update_device", "rt_scene_bounds",
-           "rt_sphere_order", "rt_sphere_order_device", "rt_balanced_ranges", "rt_scene_rebuild", "rt_scene_rebuild_device")
+           "rt_sphere_order", "rt_sphere_order_device", "rt_balanced_ranges", "rt_scene_rebuild", "rt_scene_rebuild_device",
+           "rt_scene_update_live", "rt_scene_update_live_device", "rt_scene_rebuild_n", "rt_scene_rebuild_n_device", "rt_scene_live")
 # csrc/rt_debug.h: only in the -DRT_TEST_HOOKS build
 DEBUG_SYMBOLS = ("rt_debug_set", "rt_debug_count", "rt_debug_wave_trace", "rt_debug_flat_filter_check", "rt_debug_gang_layout", "rt_debug_rccl_library",
                  "rt_debug_shard_costs")
@@ -146,6 +147,12 @@ lib.rt_sphere_order_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_v
 lib.rt_balanced_ranges.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
 lib.rt_scene_rebuild.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
 lib.rt_scene_rebuild_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+# live and dead slots: update (scene, items, bounds or NULL, live uint8[n_items] or NULL[, stream]); rebuild of n (scene, spheres, n, order_out or NULL[, stream])
+lib.rt_scene_update_live.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+lib.rt_scene_update_live_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+lib.rt_scene_rebuild_n.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+lib.rt_scene_rebuild_n_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+lib.rt_scene_live.argtypes = [C.c_void_p, C.c_void_p]
 lib.rt_tiles_rgba_bytes.restype = C.c_uint64
 lib.rt_tiles_rgba_bytes.argtypes = [C.c_void_p, C.c_uint32]
 lib.rt_strerror.restype = C.c_char_p

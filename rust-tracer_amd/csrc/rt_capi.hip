@@ -272,7 +272,9 @@ struct rt_scene {
     void *d_pbox = nullptr, *d_reach = nullptr;                    // the refit's partial boxes and reach bits
     void *d_bounds = nullptr;          // Item<REAL>[n_bounds]: the current bounds (rt_scene_bounds)
     void *d_stage = nullptr;           // a host update's items and bounds on their way in: REAL[4 n_items], REAL[4 n_bounds] behind them
-    size_t stage_bounds_off = 0;
+    size_t stage_bounds_off = 0, stage_live_off = 0;
+    uint8_t *d_live = nullptr;         // uint8[n_items], 0 / 1: what the last live update left (rt_dynamic.hpp) ...
+    std::atomic<bool> live_resident{ false };      // ... and whether the last update was one: else every slot is live (rt_scene_live)
     hipEvent_t upd_ev = nullptr;       // behind the last update
     void *d_rebuild = nullptr;         // rt_scene_rebuild*: the sort's workspace for n_items keys and the gathered items behind it (rt_rebuild.hpp), made by the first rebuild
     std::mutex rebuild_mu;             // (two first rebuilds at once make it once)

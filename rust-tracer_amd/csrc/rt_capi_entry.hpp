@@ -416,6 +416,59 @@ rt_status rt_scene_bounds(rt_scene *s, void *bounds_out)
     return RT_OK;
 }
 
+// ---- live and dead slots: a dynamic scene's n_items is a capacity ----
+
+rt_status rt_scene_update_live(rt_scene *s, const void *dfs_items, const void *bounds, const uint8_t *live)
+{
+    if (!live) return rt_scene_update(s, dfs_items, bounds);
+    if (rt_status ast = update_args_ok(s, dfs_items, "rt_scene_update_live"); ast != RT_OK) return ast;
+    const bool f32 = s->precision == RT_F32, with_bounds = bounds && s->n_bounds;
+    const bool ok = f32 ? (live_items_valid<float>(dfs_items, live, s->n_items) && (!with_bounds || items_valid<float>(bounds, s->n_bounds, false)))
+                        : (live_items_valid<double>(dfs_items, live, s->n_items) && (!with_bounds || items_valid<double>(bounds, s->n_bounds, false)));
+    if (!ok) {
+        snprintf(g_err, sizeof g_err, "rt_scene_update_live: live items must be finite, |v| <= 1e15, radius > 0; the scene is unchanged");
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    std::unique_lock<std::shared_mutex> lk(s->dyn_mu);               // as rt_scene_update
+    HIP_TRY(hipSetDevice(s->device));
+    return dynamic_update_live_host(s, dfs_items, bounds, live);
+}
+
+rt_status rt_scene_update_live_device(rt_scene *s, const void *dfs_items_device, const void *bounds_device, const uint8_t *live_device, void *hip_stream)
+{
+    if (!live_device) return rt_scene_update_device(s, dfs_items_device, bounds_device, hip_stream);
+    if (rt_status ast = update_args_ok(s, dfs_items_device, "rt_scene_update_live_device"); ast != RT_OK) return ast;
+    const uintptr_t align = (s->precision == RT_F32 ? sizeof(float) : sizeof(double)) * 4;      // one {cx, cy, cz, r} record: the kernels load it whole
+    if ((reinterpret_cast<uintptr_t>(dfs_items_device) % align) != 0 || (reinterpret_cast<uintptr_t>(bounds_device) % align) != 0) {
+        snprintf(g_err, sizeof g_err, "rt_scene_update_live_device: items and bounds must be %u-byte aligned", (unsigned)align);
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    const ReadLock rl(s);                                            // (not while a host update is replacing the scene)
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    return s->precision == RT_F32 ? enqueue_dynamic_update_live<float, false>(s, dfs_items_device, bounds_device, live_device, 0u, stream)
+                                  : enqueue_dynamic_update_live<double, false>(s, dfs_items_device, bounds_device, live_device, 0u, stream);
+}
+
+rt_status rt_scene_live(rt_scene *s, uint8_t *live_out)
+{
+    if (!s || !live_out) { snprintf(g_err, sizeof g_err, "rt_scene_live: NULL argument"); return RT_ERR_INVALID_ARGUMENT; }
+    if (!s->dynamic) { memset(live_out, 1, s->n_items); return RT_OK; }
+    const ReadLock rl(s);
+    HIP_TRY(hipSetDevice(s->device));
+    Context *c = nullptr;
+    if (rt_status st = acquire(s, &c); st != RT_OK) return st;
+    Lease lease{ s, c };
+    const bool resident = s->live_resident.load();                   // (what the last update enqueued left, as upd_ev is that update's event)
+    HIP_TRY(hipStreamWaitEvent(c->stream, s->upd_ev, 0));
+    hipError_t e = resident ? hipMemcpyAsync(live_out, s->d_live, s->n_items, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+    const hipError_t se = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = se;
+    if (e != hipSuccess) return hip_fail(e, "rt_scene_live(copy)", __LINE__);
+    if (!resident) memset(live_out, 1, s->n_items);
+    return RT_OK;
+}
+
 // Shared body of rt_render_tiles_device (frame_w == 0, tile-major output) and rt_render_frame_device (row-major frame).
 static rt_status render_device(rt_scene *s, const rt_options *o, rt_traversal trav, const rt_region *tiles, uint32_t n, void *out_device,
                                unsigned frame_w, void *hip_stream, rt_stats *stats)
@@ -1466,6 +1519,54 @@ rt_status rt_scene_rebuild_device(rt_scene *s, const void *spheres_device, uint3
     HIP_TRY(hipSetDevice(s->device));
     const uint32_t *used = nullptr;
     return enqueue_rebuild(s, spheres_device, order_out_device, static_cast<hipStream_t>(hip_stream), &used);
+}
+
+// What both rt_scene_rebuild_n entries check before the device is touched; `align`: what a spheres pointer must be a multiple of.
+static rt_status rebuild_n_args_ok(const rt_scene *s, const void *spheres, uint32_t n, const uint32_t *order_out, uintptr_t align, const char *what)
+{
+    if (!s) { snprintf(g_err, sizeof g_err, "%s: NULL scene", what); return RT_ERR_INVALID_ARGUMENT; }
+    if (n != 0u && !spheres) { snprintf(g_err, sizeof g_err, "%s: NULL spheres with n = %u", what, n); return RT_ERR_INVALID_ARGUMENT; }
+    if (n > s->n_items) { snprintf(g_err, sizeof g_err, "%s: n = %u is above the scene's capacity of %u items", what, n, s->n_items); return RT_ERR_INVALID_ARGUMENT; }
+    if (rt_status ast = rebuild_scene_ok(s, s, what); ast != RT_OK) return ast;      // (a dynamic scene with groups; the spheres are checked here)
+    if ((reinterpret_cast<uintptr_t>(spheres) % align) != 0 || (reinterpret_cast<uintptr_t>(order_out) & 3u) != 0) {
+        snprintf(g_err, sizeof g_err, "%s: spheres must be %u-byte and order_out 4-byte aligned", what, (unsigned)align);
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    return RT_OK;
+}
+
+rt_status rt_scene_rebuild_n(rt_scene *s, const void *spheres, uint32_t n, uint32_t *order_out)
+{
+    const size_t esz = s && s->precision == RT_F64 ? sizeof(double) : sizeof(float);
+    if (rt_status ast = rebuild_n_args_ok(s, spheres, n, order_out, esz, "rt_scene_rebuild_n"); ast != RT_OK) return ast;
+    if (n != 0u && !(s->precision == RT_F32 ? items_valid<float>(spheres, n, true) : items_valid<double>(spheres, n, true))) {
+        snprintf(g_err, sizeof g_err, "rt_scene_rebuild_n: spheres must be finite, |v| <= 1e15, radius > 0; the scene is unchanged");
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    std::unique_lock<std::shared_mutex> lk(s->dyn_mu);               // as rt_scene_rebuild
+    HIP_TRY(hipSetDevice(s->device));
+    if (n != 0u) memcpy(s->h_up, spheres, esz * 4 * n);
+    HIP_TRY(hipStreamWaitEvent(s->cost_stream, s->upd_ev, 0));       // (a device rebuild still in flight on another stream is using the rebuild workspace)
+    rt_status st = n != 0u ? upload_words(s->d_stage, s->h_up, esz * 4 * n, s->cost_stream) : RT_OK;
+    const uint32_t *used = nullptr;
+    if (st == RT_OK) st = enqueue_rebuild_n(s, s->d_stage, n, nullptr, s->cost_stream, &used);
+    hipError_t e = hipSuccess;
+    if (st == RT_OK && order_out && n != 0u) e = hipMemcpyAsync(order_out, used, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s->cost_stream);
+    const hipError_t se = hipStreamSynchronize(s->cost_stream);
+    if (st != RT_OK) { (void)hipGetLastError(); return st; }
+    if (e != hipSuccess) return hip_fail(e, "hipMemcpyAsync(order)", __LINE__);
+    if (se != hipSuccess) return hip_fail(se, "hipStreamSynchronize(rebuild)", __LINE__);
+    return RT_OK;
+}
+
+rt_status rt_scene_rebuild_n_device(rt_scene *s, const void *spheres_device, uint32_t n, uint32_t *order_out_device, void *hip_stream)
+{
+    const uintptr_t align = (s && s->precision == RT_F64 ? sizeof(double) : sizeof(float)) * 4;      // one {cx, cy, cz, r} record: the kernels load it whole
+    if (rt_status ast = rebuild_n_args_ok(s, spheres_device, n, order_out_device, align, "rt_scene_rebuild_n_device"); ast != RT_OK) return ast;
+    const ReadLock rl(s);                                            // (not while a host update is replacing the scene)
+    HIP_TRY(hipSetDevice(s->device));
+    const uint32_t *used = nullptr;
+    return enqueue_rebuild_n(s, spheres_device, n, order_out_device, static_cast<hipStream_t>(hip_stream), &used);
 }
 
 // Shared body of both rt_render_camera entries: the frame into d_out (tile-major, 4 * total_px bytes) on `stream` through a leased

@@ -562,6 +562,14 @@ bool items_valid(const void *p, uint32_t n, bool need_positive_radius)
     return true;
 }
 
+// ... over the live slots alone (rt_scene_update_live): a dead slot may hold any bits
+template <typename T>
+bool live_items_valid(const void *items, const uint8_t *live, uint32_t n)
+{
+    for (uint32_t i = 0; i < n; ++i)
+        if (live[i] && !items_valid<T>(static_cast<const T *>(items) + 4 * (size_t)i, 1, true)) return false;
+    return true;
+}
 
 // ---- ray queries (rt_intersect_rays*, rt_query.hpp) ----
 
@@ -1045,13 +1053,23 @@ rt_status rebuild_scene_ok(const rt_scene *s, const void *spheres, const char *w
     return RT_OK;
 }
 
+// The sort's part of a scene's rebuild workspace: room for the sort of any n <= n_items keys (rt_scene_rebuild_n*).  Every piece of
+// sort_layout grows with n while a slice holds kSortTile keys; past that the digit table may shrink as n grows, so a scene that large
+// gets room for the largest table there is.
+size_t rebuild_sort_bytes(uint32_t n_items)
+{
+    size_t bytes = sort_layout(n_items).bytes;
+    if ((uint64_t)n_items > (uint64_t)rt::kSortTile * rt::kSortMaxBlocks) bytes += (size_t)256 * rt::kSortMaxBlocks * sizeof(unsigned);
+    return bytes;
+}
+
 // One rebuild on `stream`: the order of the spheres at `src` (device memory), the gather into the scene's rebuild staging, the refit
 // update over the gathered items.  The scene's rebuild workspace -- the sort's, sized by n_items alone, and the staging behind it -- is
 // made by the first rebuild and freed with the scene; from then on nothing is allocated and nothing waited for.
 template <typename T>
 rt_status enqueue_rebuild(rt_scene *s, const void *src, uint32_t *order_out, hipStream_t stream, const uint32_t **order_used)
 {
-    const size_t sort_bytes = sort_layout(s->n_items).bytes;
+    const size_t sort_bytes = rebuild_sort_bytes(s->n_items);
     {
         std::lock_guard<std::mutex> lk(s->rebuild_mu);
         if (!s->d_rebuild) HIP_TRY(hipMalloc(&s->d_rebuild, sort_bytes + sizeof(rt::Item<T>) * s->n_items));
@@ -1068,6 +1086,33 @@ rt_status enqueue_rebuild(rt_scene *s, const void *src, uint32_t *order_out, hip
 {
     return s->precision == RT_F32 ? enqueue_rebuild<float>(s, src, order_out, stream, order_used)
                                   : enqueue_rebuild<double>(s, src, order_out, stream, order_used);
+}
+
+// A rebuild of n <= n_items spheres (rt_scene_rebuild_n*): order and gather over n, the live update over the capacity
+// with the predicate slot < n for liveness.  The sort of n keys lies inside the workspace of n_items keys (rebuild_sort_bytes).
+template <typename T>
+rt_status enqueue_rebuild_n(rt_scene *s, const void *src, uint32_t n, uint32_t *order_out, hipStream_t stream, const uint32_t **order_used)
+{
+    const size_t sort_bytes = rebuild_sort_bytes(s->n_items);
+    {
+        std::lock_guard<std::mutex> lk(s->rebuild_mu);
+        if (!s->d_rebuild) HIP_TRY(hipMalloc(&s->d_rebuild, sort_bytes + sizeof(rt::Item<T>) * s->n_items));
+    }
+    rt::Item<T> *const staged = reinterpret_cast<rt::Item<T> *>(static_cast<uint8_t *>(s->d_rebuild) + sort_bytes);
+    *order_used = nullptr;
+    if (n != 0u) {
+        if (rt_status st = enqueue_sphere_order<T>(s->d_rebuild, src, n, order_out, stream, order_used); st != RT_OK) return st;
+        hipLaunchKernelGGL(rt::k_gather_items<T>, dim3((n + rt::kBlockThreads - 1) / rt::kBlockThreads), dim3(rt::kBlockThreads), 0, stream,
+                           static_cast<const rt::Item<T> *>(src), *order_used, n, staged);
+        HIP_TRY(hipGetLastError());
+    }
+    return enqueue_dynamic_update_live<T, true>(s, staged, nullptr, nullptr, n, stream);
+}
+
+rt_status enqueue_rebuild_n(rt_scene *s, const void *src, uint32_t n, uint32_t *order_out, hipStream_t stream, const uint32_t **order_used)
+{
+    return s->precision == RT_F32 ? enqueue_rebuild_n<float>(s, src, n, order_out, stream, order_used)
+                                  : enqueue_rebuild_n<double>(s, src, n, order_out, stream, order_used);
 }
 
 // ---- undersampled camera frames (rt_render_camera_undersampled*, rt_undersample.hpp) ----

@@ -609,6 +609,7 @@ rt_status enqueue_dynamic_update(rt_scene *s, const void *src_items, const void 
     hipLaunchKernelGGL(rt::k_dynamic_rewrite<T>, dim3((unsigned)((threads + rt::kBlockThreads - 1) / rt::kBlockThreads)), block, 0, stream, r);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(s->upd_ev, stream));
+    s->live_resident.store(false);                                   // every slot is live again (rt_scene_live: all ones, no bytes kept)
     return RT_OK;
 }
 
@@ -616,6 +617,60 @@ rt_status enqueue_dynamic_update(rt_scene *s, const void *src_items, const void 
 {
     return s->precision == RT_F32 ? enqueue_dynamic_update<float>(s, src_items, src_bounds, stream)
                                   : enqueue_dynamic_update<double>(s, src_items, src_bounds, stream);
+}
+
+// One update with dead slots on `stream`: the launches of enqueue_dynamic_update, their live-aware siblings.  `live`:
+// device memory, uint8[n_items]; PREFIX: slots [0, n_live) are live and no byte is read -- then n_live == 0 goes straight to the rewrite.
+template <typename T, bool PREFIX>
+rt_status enqueue_dynamic_update_live(rt_scene *s, const void *src_items, const void *src_bounds, const uint8_t *live, uint32_t n_live, hipStream_t stream)
+{
+    typedef typename rt::BitsOf<T>::type Bits;
+    const dim3 block(rt::kBlockThreads);
+    if (s->n_bounds && !src_bounds && s->n_work && !(PREFIX && n_live == 0u)) {
+        const rt::LiveRefitArgs<T> a{ { static_cast<const rt::Item<T> *>(src_items), s->d_work, static_cast<T *>(s->d_pbox), static_cast<Bits *>(s->d_reach),
+                                        static_cast<rt::Item<T> *>(s->d_bounds), s->n_work }, live, n_live };
+        const dim3 grid((s->n_work + rt::kBlockThreads / 64 - 1) / (rt::kBlockThreads / 64));
+        hipLaunchKernelGGL((rt::k_refit_box_live<T, PREFIX>), grid, block, 0, stream, a);
+        hipLaunchKernelGGL((rt::k_refit_reach_live<T, PREFIX>), grid, block, 0, stream, a);
+    }
+    rt::LiveRewriteArgs<T> r{};
+    r.r.src_items = static_cast<const rt::Item<T> *>(src_items);
+    r.r.src_bounds = s->n_bounds ? static_cast<const rt::Item<T> *>(src_bounds) : nullptr;
+    r.r.items = static_cast<rt::Item<T> *>(s->d_items);
+    r.r.bounds = static_cast<rt::Item<T> *>(s->d_bounds);
+    r.r.reach = static_cast<const Bits *>(s->d_reach);
+    r.r.stream = static_cast<rt::Node<T> *>(s->n_nodes ? s->d_shad : s->d_query_items);
+    r.r.item_node = s->d_item_node;
+    r.r.bound_node = s->d_bound_node;
+    r.r.n_items = s->n_items; r.r.n_bounds = s->n_bounds;
+    r.live = live; r.live_out = s->d_live; r.n_live = n_live;
+    const uint64_t threads = (uint64_t)s->n_items + s->n_bounds;
+    hipLaunchKernelGGL((rt::k_dynamic_rewrite_live<T, PREFIX>), dim3((unsigned)((threads + rt::kBlockThreads - 1) / rt::kBlockThreads)), block, 0, stream, r);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(s->upd_ev, stream));
+    s->live_resident.store(true);                                    // (next to the event: rt_scene_live reads both)
+    return RT_OK;
+}
+
+// A host update with dead slots: the items, the bounds and the liveness bytes into the scene's staging, the live update behind them.
+rt_status dynamic_update_live_host(rt_scene *s, const void *items, const void *bounds, const uint8_t *live)
+{
+    const size_t esz = s->precision == RT_F32 ? sizeof(float) : sizeof(double);
+    const size_t ib = esz * 4 * s->n_items, bb = (bounds && s->n_bounds) ? esz * 4 * s->n_bounds : 0;
+    // the liveness bytes go behind the bounds, or -- a refit: no bounds on their way -- where the bounds would start: one upload, no stale range in it
+    const size_t live_off = bb ? s->stage_live_off : s->stage_bounds_off;
+    memcpy(s->h_up, items, ib);
+    if (bb) memcpy(s->h_up + s->stage_bounds_off, bounds, bb);
+    if (s->n_items & 3u) memset(s->h_up + live_off + (s->n_items & ~(size_t)3), 0, 4);      // (the upload moves whole words)
+    memcpy(s->h_up + live_off, live, s->n_items);
+    rt_status st = upload_words(s->d_stage, s->h_up, live_off + (((size_t)s->n_items + 3) & ~(size_t)3), s->cost_stream);
+    const void *d_bounds = bb ? static_cast<char *>(s->d_stage) + s->stage_bounds_off : nullptr;
+    const uint8_t *d_live = static_cast<uint8_t *>(s->d_stage) + live_off;
+    if (st == RT_OK) st = s->precision == RT_F32 ? enqueue_dynamic_update_live<float, false>(s, s->d_stage, d_bounds, d_live, 0u, s->cost_stream)
+                                                 : enqueue_dynamic_update_live<double, false>(s, s->d_stage, d_bounds, d_live, 0u, s->cost_stream);
+    const hipError_t e = hipStreamSynchronize(s->cost_stream);
+    if (st == RT_OK && e != hipSuccess) return hip_fail(e, "hipStreamSynchronize(update)", __LINE__);
+    return st;
 }
 
 // A host update's values into the scene's staging (pinned arena -> k_upload_words, as rt_scene_create uploads) and the update behind
@@ -666,8 +721,10 @@ rt_status upload_dynamic(rt_scene *s, const void *items, const void *bounds, con
     const size_t o_reach = take(sizeof(typename rt::BitsOf<T>::type) * s->n_bounds);
     const size_t o_bounds = take(sizeof(rt::Item<T>) * s->n_bounds);
     s->stage_bounds_off = (sizeof(rt::Item<T>) * s->n_items + 255) & ~(size_t)255;
-    const size_t stage_bytes = s->stage_bounds_off + sizeof(rt::Item<T>) * s->n_bounds;
+    s->stage_live_off = s->stage_bounds_off + ((sizeof(rt::Item<T>) * s->n_bounds + 255) & ~(size_t)255);      // (a live update's bytes, behind the bounds)
+    const size_t stage_bytes = s->stage_live_off + (((size_t)s->n_items + 3) & ~(size_t)3);
     const size_t o_stage = take(stage_bytes);
+    const size_t o_live = take(s->n_items);
     HIP_TRY(hipMalloc(&s->d_dyn, bytes));
     char *const d = static_cast<char *>(s->d_dyn);
     void *const d_stream = d + o_stream;
@@ -675,6 +732,7 @@ rt_status upload_dynamic(rt_scene *s, const void *items, const void *bounds, con
     s->d_bound_node = reinterpret_cast<uint32_t *>(d + o_bnode);
     s->d_work = reinterpret_cast<rt::RefitWork *>(d + o_work);
     s->d_pbox = d + o_pbox; s->d_reach = d + o_reach; s->d_bounds = d + o_bounds; s->d_stage = d + o_stage;
+    s->d_live = reinterpret_cast<uint8_t *>(d + o_live);
 
     // the pinned arena: the topology's uploads now, a host update's items and bounds from then on
     const size_t topo_bytes = sizeof(uint2) * topo.size() + sizeof(uint32_t) * (item_node.size() + bound_node.size()) + sizeof(rt::RefitWork) * work.size() + 4 * 256;

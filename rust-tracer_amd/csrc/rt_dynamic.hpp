@@ -211,6 +211,140 @@ __global__ __launch_bounds__(kBlockThreads) void k_dynamic_rewrite(RewriteArgs<T
     if (node != kNoNode) rewrite_node(a.stream, node, bd.cx, bd.cy, bd.cz, bd.r);
 }
 
+// ---- live and dead slots (rt_scene_update_live*, rt_scene_rebuild_n*) ----
+// The siblings of the three kernels above for a scene whose slots are LIVE or DEAD: the same launches over the same work records, a lane
+// leaves its dead items out.  Liveness is one byte per slot (nonzero = live), or -- PREFIX, what a rebuild of n spheres leaves -- the
+// predicate slot < n_live with no byte read.  A work record without a live item keeps the identity box and adds nothing to the reach, so
+// a group is dead exactly when its reach bits are still 0 behind the reach pass (a live reach is at least a radius, > 0): the rewrite
+// gives such a group, and every dead item, the DEAD RECORD -- centre 0 and rr = -inf, disc = (b*b - vv) + rr = -inf for every ray of the
+// domain: an ITEM that is never hit, a BOUND that culls for every ray; the mirror image of per_origin_end's +inf.
+template <typename T> struct LiveRefitArgs {
+    RefitArgs<T> r;
+    const uint8_t *live;                   // [n_items].  PREFIX: not read
+    uint32_t n_live;                       // PREFIX: slots [0, n_live) are live
+};
+
+template <bool PREFIX>
+__device__ __forceinline__ bool slot_live(const uint8_t *live, uint32_t n_live, uint32_t slot)
+{
+    if (PREFIX) return slot < n_live;
+    return live[slot] != 0;                // (a wave's 64 lanes read 64 consecutive bytes: one request)
+}
+
+template <typename T, bool PREFIX>
+__global__ __launch_bounds__(kBlockThreads) void k_refit_box_live(LiveRefitArgs<T> la)
+{
+    const RefitArgs<T> &a = la.r;
+    RefitWork k; unsigned w;
+    if (!refit_work(a, k, w)) return;
+    const unsigned lane = threadIdx.x & 63u;
+    T lo[3] = { inf<T>(), inf<T>(), inf<T>() }, hi[3] = { -inf<T>(), -inf<T>(), -inf<T>() };
+    for (unsigned j = lane; j < k.count; j += 64u) {
+        if (!slot_live<PREFIX>(la.live, la.n_live, k.first + j)) continue;
+        const Item<T> it = a.src[k.first + j];
+        lo[0] = min_rn(lo[0], it.cx - it.r); lo[1] = min_rn(lo[1], it.cy - it.r); lo[2] = min_rn(lo[2], it.cz - it.r);
+        hi[0] = max_rn(hi[0], it.cx + it.r); hi[1] = max_rn(hi[1], it.cy + it.r); hi[2] = max_rn(hi[2], it.cz + it.r);
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { lo[c] = wave_extreme<false>(lo[c]); hi[c] = wave_extreme<true>(hi[c]); }
+    if (lane == 0u) {
+        T *p = a.pbox + 6 * (size_t)w;
+        p[0] = lo[0]; p[1] = lo[1]; p[2] = lo[2]; p[3] = hi[0]; p[4] = hi[1]; p[5] = hi[2];
+        if (w == k.pfirst) a.reach[k.group] = 0;
+    }
+}
+
+template <typename T, bool PREFIX>
+__global__ __launch_bounds__(kBlockThreads) void k_refit_reach_live(LiveRefitArgs<T> la)
+{
+    const RefitArgs<T> &a = la.r;
+    RefitWork k; unsigned w;
+    if (!refit_work(a, k, w)) return;
+    const unsigned lane = threadIdx.x & 63u;
+    T lo[3], hi[3];
+    if (k.pcount == 1u) {
+        const T *p = a.pbox + 6 * (size_t)w;
+        lo[0] = p[0]; lo[1] = p[1]; lo[2] = p[2]; hi[0] = p[3]; hi[1] = p[4]; hi[2] = p[5];
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { lo[c] = inf<T>(); hi[c] = -inf<T>(); }
+        for (unsigned j = lane; j < k.pcount; j += 64u) {
+            const T *p = a.pbox + 6 * (size_t)(k.pfirst + j);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { lo[c] = min_rn(lo[c], p[c]); hi[c] = max_rn(hi[c], p[3 + c]); }
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { lo[c] = wave_extreme<false>(lo[c]); hi[c] = wave_extreme<true>(hi[c]); }
+    }
+    // a group without a live item still has the identity box, whose centre would be (+inf + -inf) * 0.5 = NaN: it gets centre 0, nobody
+    // takes a reach around it, and the rewrite puts the dead record in its place
+    // (x alone decides: a live item puts finite values on all three axes, so either every axis is still the identity or none is)
+    const bool any = lo[0] <= hi[0];
+    const T cx = any ? (lo[0] + hi[0]) * T(0.5) : T(0), cy = any ? (lo[1] + hi[1]) * T(0.5) : T(0), cz = any ? (lo[2] + hi[2]) * T(0.5) : T(0);
+    T reach = T(0);
+    for (unsigned j = lane; j < k.count; j += 64u)
+        if (slot_live<PREFIX>(la.live, la.n_live, k.first + j)) reach = max_rn(reach, refit_reach(a.src[k.first + j], cx, cy, cz));
+    reach = wave_extreme<true>(reach);
+    if (lane == 0u) {
+        atomicMax(a.reach + k.group, bits_of(reach));
+        if (w == k.pfirst) { Item<T> *b = a.bounds + k.group; b->cx = cx; b->cy = cy; b->cz = cz; }
+    }
+}
+
+template <typename T> struct LiveRewriteArgs {
+    RewriteArgs<T> r;
+    const uint8_t *live;                   // as LiveRefitArgs
+    uint8_t *live_out;                     // [n_items]: the scene's resident liveness, 0 / 1 (rt_scene_live)
+    uint32_t n_live;
+};
+
+template <typename T>
+__device__ __forceinline__ void rewrite_dead(Node<T> *stream, uint32_t node)
+{
+    *reinterpret_cast<NodeTerms<T> *>(stream + node) = NodeTerms<T>{ T(0), T(0), T(0), -inf<T>() };
+}
+
+// The rewrite with dead slots: a dead item's values are not read (its slot of the scene's items is cleared), a refit group that no live
+// item reached reports {0, 0, 0, 0}.  The caller's bounds are written as given.  PREFIX with n_live == 0: the refit did not run, every
+// group is dead.
+template <typename T, bool PREFIX>
+__global__ __launch_bounds__(kBlockThreads) void k_dynamic_rewrite_live(LiveRewriteArgs<T> la)
+{
+    const RewriteArgs<T> &a = la.r;
+    const unsigned t = blockIdx.x * kBlockThreads + threadIdx.x;
+    if (t < a.n_items) {
+        const bool live = slot_live<PREFIX>(la.live, la.n_live, t);
+        const uint32_t node = a.item_node ? a.item_node[t] : t;
+        la.live_out[t] = live ? 1 : 0;
+        if (live) {
+            const Item<T> it = a.src_items[t];
+            a.items[t] = it;
+            rewrite_node(a.stream, node, it.cx, it.cy, it.cz, it.r);
+        } else {
+            a.items[t] = Item<T>{ T(0), T(0), T(0), T(0) };
+            rewrite_dead(a.stream, node);
+        }
+        return;
+    }
+    const unsigned b = t - a.n_items;
+    if (b >= a.n_bounds) return;
+    const uint32_t node = a.bound_node[b];
+    Item<T> bd;
+    bool dead = false;
+    if (a.src_bounds) bd = a.src_bounds[b];
+    else {
+        if (node == kNoNode) return;                                 // a group without items keeps the bound it was given
+        dead = a.reach[b] == 0 || (PREFIX && la.n_live == 0u);
+        bd = a.bounds[b];
+        bd.r = real_of(a.reach[b]) * (T(1.0) + T(kRefitK) * eps<T>());
+        if (dead) bd = Item<T>{ T(0), T(0), T(0), T(0) };
+    }
+    a.bounds[b] = bd;
+    if (node == kNoNode) return;
+    if (dead) rewrite_dead(a.stream, node);
+    else rewrite_node(a.stream, node, bd.cx, bd.cy, bd.cz, bd.r);
+}
+
 // The resident topology of a dynamic scene's stream: item word and skip offset of every node, the END padding whole.  The value fields
 // are k_dynamic_rewrite's, which rt_scene_create_dynamic runs behind this.
 template <typename T>

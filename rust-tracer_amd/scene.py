@@ -112,14 +112,21 @@ def balanced_ranges_reference(n, leaf_size=4):
     return np.asarray(out, dtype=np.int32).reshape(-1, 2)
 
 
-def refit_bounds(items, ranges, precision=capi.RT_F32, bounds=None):
+def refit_bounds(items, ranges, precision=capi.RT_F32, bounds=None, live=None):
     """The bounds rt_scene_update refits for `items` (n x 4: cx, cy, cz, r) over `ranges` (g x 2: first item, item count) -> REAL[g, 4],
     the rule of include/rtrace_hip.h restated in numpy bit for bit: every operation in REAL, rounded once.  Per group: lo / hi = min / max
     of c -+ r, centre = (lo + hi) * 0.5, reach = dist(c, centre) + r with dist = sqrt((dx*dx + dy*dy) + dz*dz), or (|dx| + |dy|) + |dz|
     where that sum of squares is below MIN_NORMAL / EPSILON^2, radius = max(reach) * (1 + 8 * EPSILON).  A group without items keeps its
-    row of `bounds` (zeros when there is none)."""
+    row of `bounds` (zeros when there is none).  live (n values, nonzero = live; None: all): the rule over each group's LIVE items only,
+    as rt_scene_update_live refits -- the values in dead slots take no part, NaN included, and a group without a live item gets
+    {0, 0, 0, 0}."""
     R = _real(precision)
     it = np.ascontiguousarray(items, dtype=R).reshape(-1, 4)
+    alive = None
+    if live is not None:
+        alive = np.asarray(live).reshape(-1) != 0
+        if alive.shape[0] != it.shape[0]:
+            raise ValueError("live must have one value per item")
     rg = np.asarray(ranges, dtype=np.int64).reshape(-1, 2)
     out = np.zeros((rg.shape[0], 4), dtype=R) if bounds is None else np.array(bounds, dtype=R).reshape(-1, 4)
     if out.shape[0] != rg.shape[0]:
@@ -136,6 +143,11 @@ def refit_bounds(items, ranges, precision=capi.RT_F32, bounds=None):
         if count == 0:
             continue
         sl = slice(first, first + count)
+        if alive is not None:
+            sl = first + np.flatnonzero(alive[sl])
+            if sl.size == 0:
+                out[g] = 0
+                continue
         centre = (lo_all[sl].min(axis=0) + hi_all[sl].max(axis=0)) * half
         d = c[sl] - centre
         s = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
@@ -443,13 +455,15 @@ class DeviceScene:
         self._h = h
         self._n_bounds = nb if not dynamic else (0 if scene.ranges is None else scene.ranges.shape[0])
 
-    def update(self, items, bounds=None, stream=None):
+    def update(self, items, bounds=None, stream=None, live=None):
         """rt_scene_update / rt_scene_update_device: new values for every sphere of a dynamic scene (n x 4, the scene's REAL dtype, the same
         DFS order) and, optionally, for every bound (g x 4); bounds=None refits them on the device (refit_bounds is the rule).  numpy arrays
         go through the host entry, which returns when the new scene is in place.  A torch tensor on this scene's device -- or a raw device
         pointer as int -- goes through the device entry, enqueued on `stream` (a torch stream or a hipStream_t as int; default the
         current torch stream) with the stream discipline of intersect(): queries on that stream see the new scene, other streams are the
-        caller's to order."""
+        caller's to order.  live (rt_scene_update_live*; n values, nonzero = live, memory of the same kind as `items`; None: every slot
+        live): a dead slot's sphere is never hit and takes no part in the refit, whatever bits it holds; a group without a live item
+        culls for every ray and reports the bound {0, 0, 0, 0}."""
         R = _real(self.scene.precision)
         n, g = self.scene.items.shape[0], self._n_bounds
         torch = sys.modules.get("torch")
@@ -457,6 +471,8 @@ class DeviceScene:
         if is_t(items) or isinstance(items, int):
             if bounds is not None and not (is_t(bounds) or isinstance(bounds, int)):
                 raise ValueError("bounds must be device memory too (a tensor or a pointer), or None")
+            if live is not None and not (is_t(live) or isinstance(live, int)):
+                raise ValueError("live must be device memory too (a uint8 / bool tensor or a pointer), or None")
             if torch is None:
                 import torch
             tdt = torch.float32 if R == np.float32 else torch.float64
@@ -464,6 +480,8 @@ class DeviceScene:
             for x, rows, what in ((items, n, "items"), (bounds, g, "bounds")):
                 if is_t(x) and (x.dtype != tdt or x.device != dev or x.numel() != 4 * rows):
                     raise ValueError("%s must be a (%d, 4) %s tensor on %s" % (what, rows, tdt, dev))
+            if is_t(live) and (live.dtype not in (torch.uint8, torch.bool) or live.device != dev or live.numel() != n):
+                raise ValueError("live must be a (%d,) uint8 or bool tensor on %s" % (n, dev))
             cur = torch.cuda.current_stream(dev)
             if stream is None:
                 qs = cur
@@ -478,11 +496,15 @@ class DeviceScene:
                 it = items.contiguous() if is_t(items) else items
                 bd = bounds.contiguous() if is_t(bounds) else bounds
                 ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr() if is_t(x) else x)
-                rc = capi.lib.rt_scene_update_device(self._h, ptr(it), ptr(bd), C.c_void_p(qs.cuda_stream))
-            for x in (it, bd, items, bounds):
+                lv = live.contiguous() if is_t(live) else live
+                if lv is None:
+                    rc = capi.lib.rt_scene_update_device(self._h, ptr(it), ptr(bd), C.c_void_p(qs.cuda_stream))
+                else:
+                    rc = capi.lib.rt_scene_update_live_device(self._h, ptr(it), ptr(bd), ptr(lv), C.c_void_p(qs.cuda_stream))
+            for x in (it, bd, lv, items, bounds, live):
                 if is_t(x):
                     x.record_stream(qs)
-            capi.check(rc, "rt_scene_update_device")
+            capi.check(rc, "rt_scene_update_device" if lv is None else "rt_scene_update_live_device")
             return
         it = np.asarray(items)
         if it.dtype != R or it.size != 4 * n:
@@ -494,7 +516,15 @@ class DeviceScene:
             if bd.dtype != R or bd.size != 4 * g:
                 raise ValueError("bounds must be a (%d, 4) array of %s" % (g, np.dtype(R).name))
             bd = np.ascontiguousarray(bd)
-        capi.check(capi.lib.rt_scene_update(self._h, it.ctypes.data, None if bd is None or g == 0 else bd.ctypes.data), "rt_scene_update")
+        bdp = None if bd is None or g == 0 else bd.ctypes.data
+        if live is None:
+            capi.check(capi.lib.rt_scene_update(self._h, it.ctypes.data, bdp), "rt_scene_update")
+            return
+        lv = np.asarray(live)
+        if lv.dtype not in (np.uint8, np.bool_) or lv.size != n:
+            raise ValueError("live must be a (%d,) array of uint8 or bool" % n)
+        lv = np.ascontiguousarray(lv).view(np.uint8)
+        capi.check(capi.lib.rt_scene_update_live(self._h, it.ctypes.data, bdp, lv.ctypes.data), "rt_scene_update_live")
 
     def _device_stream(self, torch, stream):
         """(the torch stream a device entry is enqueued on, the current one) for `stream`: None, a torch stream or a hipStream_t as int."""
@@ -507,9 +537,19 @@ class DeviceScene:
         hs = int(stream)
         return (torch.cuda.default_stream(dev) if hs == 0 else torch.cuda.ExternalStream(hs, device=dev)), cur
 
-    def _spheres_arg(self, spheres, n, what):
+    def _spheres_arg(self, spheres, n, what, at_least=None):
         """`spheres` for a sphere order or a rebuild: (True, contiguous tensor) for a torch tensor on this scene's device, (False, contiguous
-        numpy array) otherwise; n: the number of rows it must have, or None for any."""
+        numpy array) otherwise; n: the number of rows it must have, or None for any; at_least: a rebuild of that many takes its first rows."""
+        if at_least is not None:
+            ok = hasattr(spheres, "shape") and len(spheres.shape) == 2 and at_least <= spheres.shape[0]
+            if not ok:
+                raise ValueError("%s: spheres must have at least n = %d rows" % (what, at_least))
+            if spheres.shape[0] == 0:                                # (n = 0: nothing to read; a tensor still goes through the device entry, on its stream)
+                torch = sys.modules.get("torch")
+                if torch is not None and isinstance(spheres, torch.Tensor):
+                    return True, spheres
+                return False, np.zeros((0, 4), dtype=_real(self.scene.precision))
+            n = None
         R = _real(self.scene.precision)
         torch = sys.modules.get("torch")
         if torch is not None and isinstance(spheres, torch.Tensor):
@@ -545,12 +585,16 @@ class DeviceScene:
         capi.check(rc, "rt_sphere_order_device")
         return order
 
-    def rebuild(self, spheres, stream=None):
+    def rebuild(self, spheres, stream=None, n=None):
         """rt_scene_rebuild / rt_scene_rebuild_device: the hierarchy of a dynamic scene rebuilt from `spheres` (n_items x 4, the scene's REAL
         dtype) in ANY order -> the order, uint32[n_items]: DFS slot k now holds spheres[order[k]] (what a query's item index names), every
         bound is refit, and the scene answers as a fresh one made from spheres[order], bounds() and the same ranges.  order is
         np.argsort(sphere_keys(spheres), kind="stable").  numpy goes through the host entry, which returns when the new scene is in place;
-        a torch tensor on this scene's device goes through the device entry, enqueued on `stream` with the discipline of update()."""
+        a torch tensor on this scene's device goes through the device entry, enqueued on `stream` with the discipline of update().
+        n (rt_scene_rebuild_n*; None: all n_items): the first n rows of `spheres`, 0 <= n <= n_items, into slots 0 .. n-1 in their own
+        sphere order -> uint32[n]; every slot from n on is dead, n = 0 empties the scene."""
+        if n is not None:
+            return self._rebuild_n(spheres, int(n), stream)
         n = self.scene.items.shape[0]
         is_t, sp = self._spheres_arg(spheres, n, "rebuild")
         if not is_t:
@@ -569,6 +613,34 @@ class DeviceScene:
             x.record_stream(qs)
         capi.check(rc, "rt_scene_rebuild_device")
         return order
+
+    def _rebuild_n(self, spheres, n, stream):
+        cap = self.scene.items.shape[0]
+        if not 0 <= n <= cap:
+            raise capi.RtError(capi.RT_ERR_INVALID_ARGUMENT, "rt_scene_rebuild_n", "n = %d is outside 0 .. %d, the scene's capacity" % (n, cap))
+        is_t, sp = self._spheres_arg(spheres, None, "rebuild", at_least=n)
+        if not is_t:
+            order = np.empty(n, dtype=np.uint32)
+            capi.check(capi.lib.rt_scene_rebuild_n(self._h, sp.ctypes.data if n else None, n, order.ctypes.data if n else None), "rt_scene_rebuild_n")
+            return order
+        import torch
+        qs, cur = self._device_stream(torch, stream)
+        if qs != cur:
+            qs.wait_stream(cur)
+        with torch.cuda.stream(qs):
+            t = sp.contiguous()
+            order = torch.empty(n, dtype=torch.uint32, device=t.device)
+            rc = capi.lib.rt_scene_rebuild_n_device(self._h, C.c_void_p(t.data_ptr()) if n else None, n, C.c_void_p(order.data_ptr()) if n else None, C.c_void_p(qs.cuda_stream))
+        for x in (t, spheres):
+            x.record_stream(qs)
+        capi.check(rc, "rt_scene_rebuild_n_device")
+        return order
+
+    def live(self):
+        """rt_scene_live -> uint8[n_items] of 0 / 1: which slots are live (after the last update or rebuild; an immutable scene: all ones)."""
+        out = np.zeros(self.scene.items.shape[0], dtype=np.uint8)
+        capi.check(capi.lib.rt_scene_live(self._h, out.ctypes.data), "rt_scene_live")
+        return out
 
     def bounds(self):
         """rt_scene_bounds -> REAL[g, 4]: the scene's current bounds (after the last update; an immutable scene: as created)."""
