@@ -538,6 +538,50 @@ rt_status rt_scene_rebuild_n_device(rt_scene *scene, const void *spheres_device,
  * from rt_scene_create reports all ones. */
 rt_status rt_scene_live(rt_scene *scene, uint8_t *live_out);
 
+/* ---- proximity queries (additive to ABI 5): the k nearest spheres of a point, or every sphere within a radius ----
+ * The question a caller that moves spheres asks before its next update: which spheres are near this one?  Query g is a point p =
+ * points[3g .. 3g+3] (REAL) and a search radius rho = radius[g] (REAL; radius == NULL: +inf).  The metric is the surface GAP between p and
+ * a sphere.  For a record {c, rr} of the scene's stream -- rr is the radius squared, rounded once -- in REAL, every operation rounded
+ * once, no FMA, both roots the IEEE ones:
+ *   v   = c - p                                       component-wise
+ *   vv  = (v.x*v.x + v.y*v.y) + v.z*v.z
+ *   gap = rr > 0 ? sqrt(vv) - sqrt(rr) : +inf
+ * The gap is negative when p is inside the sphere.  The guard is part of the definition: a dead item and a dead group (rr = -inf, "live
+ * and dead slots" above) have gap +inf, so a dead item is never reported or counted and a dead group culls its subtree at its one test.
+ * rust_tracer_amd.sphere_gaps restates the gap in numpy, bit for bit.
+ *   The walk is rt_intersect_rays_multi's over the same stream with the gap in place of the distance along a ray (a bound encloses its
+ * items, so its gap is a lower bound of theirs).  Each query keeps k slots (gap, item), every slot starting as (rho, -1).  A bound culls
+ * when its gap is >= the cutoff: the last slot's gap (CLOSEST) or rho (ALL).  An item whose gap is not >= the last slot's is inserted
+ * behind every slot whose gap is <= its own (equal gaps stay in DFS order) and the last slot drops out.
+ *   RT_NEAR_CLOSEST  the k nearest items below rho; found_out[g] = the filled slots (<= k).
+ *   RT_NEAR_ALL      no culling below rho: the k nearest of all items below rho, and found_out[g] = how many there are (may be > k).
+ * The result is the walk's: a bound that encloses its items only to within rounding can cull an item whose own test would have passed by
+ * an ulp.  Whenever no item's gap lies within a few ulp of the cutoff it is the brute-force answer over all items.
+ *   exclude (int32[n] or NULL): the item slot query g ignores -- the self-query of a sphere that lives in the scene.  That item is tested
+ * and counted as a test, but never listed and never counted as found; -1 or any slot outside the scene excludes nothing.
+ *   order (uint32[n] or NULL): thread j carries query order[j], with the rules of the *_ordered entries above -- host entry: a permutation
+ * of 0 .. n-1; device entry: alignment only, and an entry >= n carries no query.  NULL: the caller's order.  The bytes and counters are
+ * the same in every order; only the time differs.  A query is a sphere-shaped record: rt_sphere_order over {p, 1} gives a coherent order.
+ *   Slot j of query g is at index g*k + j, nearest first: gap_out (REAL[n*k]; an empty slot reads rho), item_out (int32[n*k] or NULL, DFS
+ * slot; an empty slot reads -1), found_out (uint32[n] or NULL).  stats (may be NULL): primary = n, hits = queries with found_out > 0,
+ * sphere_tests / bound_tests / tests_executed, every other counter 0; asking for it runs the counting flavour (same bytes). */
+typedef enum rt_near { RT_NEAR_CLOSEST = 0, RT_NEAR_ALL = 1 } rt_near;
+#define RT_NEAR_MAX_K 16
+/* Host memory.  RT_ERR_INVALID_ARGUMENT before the device is touched for a NULL scene, points or gap_out, n == 0, k == 0 or k >
+ * RT_NEAR_MAX_K, an unknown mode, a misaligned buffer, a point with a non-finite coordinate or one beyond +-1e15 (the scene's own domain)
+ * and a NaN radius; any other radius is valid -- a negative one finds only the spheres that contain the point that deep.  Pinned memory
+ * is used in place, pageable memory goes through the call's device workspace.  On a dynamic scene the call is a READ in the sense of
+ * ORDER above: behind a host update, rebuild or live update it sees the new scene. */
+rt_status rt_near_spheres(rt_scene *scene, rt_near mode, uint32_t k, const void *points, const void *radius, uint32_t n,
+                          const int32_t *exclude, const uint32_t *order, void *gap_out, int32_t *item_out, uint32_t *found_out,
+                          rt_stats *stats);
+/* The same over DEVICE memory, enqueued on `hip_stream` as rt_intersect_rays_device is: only pointers, alignment, n, k and mode are
+ * checked.  A query outside the domain gives unspecified values, never a fault -- the walk ends for any input bits.  stats != NULL:
+ * filled after an internal synchronisation of hip_stream. */
+rt_status rt_near_spheres_device(rt_scene *scene, rt_near mode, uint32_t k, const void *points, const void *radius, uint32_t n,
+                                 const int32_t *exclude, const uint32_t *order, void *gap_out, int32_t *item_out, uint32_t *found_out,
+                                 rt_stats *stats, void *hip_stream);
+
 /* Bytes rt_render_tiles writes for this tile list (4 * total area), or 0 on an invalid list. */
 uint64_t rt_tiles_rgba_bytes(const rt_region *tiles, uint32_t n_tiles);
 

@@ -23,6 +23,8 @@ RT_QUERY_NEAREST, RT_QUERY_ANY = 0, 1
 RT_MULTIHIT_CLOSEST, RT_MULTIHIT_ALL = 0, 1
 RT_MULTIHIT_MAX_K = 16
 RT_UNDERSAMPLE_MAX_STEP = 64
+RT_NEAR_CLOSEST, RT_NEAR_ALL = 0, 1
+RT_NEAR_MAX_K = 16
 
 # every symbol include/rtrace_hip.h declares
 SYMBOLS = ("rt_abi_version", "rt_build_hierarchy", "rt_device_count", "rt_scene_create", "rt_scene_destroy", "rt_scene_traits", "rt_scene_setup_cost", "rt_render_tiles",
@@ -37,7 +39,8 @@ SYMBOLS = ("rt_abi_version", "rt_build_hierarchy", "rt_device_count", "rt_scene_
            "rt_intersect_rays_multi_ordered", "rt_intersect_rays_multi_ordered_device", "rt_trace_rays_ordered", "rt_trace_rays_ordered_device",
            "rt_scene_create_dynamic", "rt_scene_update", "rt_scene_update_device", "rt_scene_bounds",
            "rt_sphere_order", "rt_sphere_order_device", "rt_balanced_ranges", "rt_scene_rebuild", "rt_scene_rebuild_device",
-           "rt_scene_update_live", "rt_scene_update_live_device", "rt_scene_rebuild_n", "rt_scene_rebuild_n_device", "rt_scene_live")
+           "rt_scene_update_live", "rt_scene_update_live_device", "rt_scene_rebuild_n", "rt_scene_rebuild_n_device", "rt_scene_live",
+           "rt_near_spheres", "rt_near_spheres_device")
 # csrc/rt_debug.h: only in the -DRT_TEST_HOOKS build
 DEBUG_SYMBOLS = ("rt_debug_set", "rt_debug_count", "rt_debug_wave_trace", "rt_debug_flat_filter_check", "rt_debug_gang_layout", "rt_debug_rccl_library",
                  "rt_debug_shard_costs")
@@ -153,6 +156,10 @@ lib.rt_scene_update_live_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, 
 lib.rt_scene_rebuild_n.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
 lib.rt_scene_rebuild_n_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
 lib.rt_scene_live.argtypes = [C.c_void_p, C.c_void_p]
+# proximity queries: (scene, mode, k, points, radius or NULL, n, exclude or NULL, order or NULL, gap_out, item_out, found_out, stats[, stream])
+lib.rt_near_spheres.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.POINTER(Stats)]
+lib.rt_near_spheres_device.argtypes = lib.rt_near_spheres.argtypes + [C.c_void_p]
 lib.rt_tiles_rgba_bytes.restype = C.c_uint64
 lib.rt_tiles_rgba_bytes.argtypes = [C.c_void_p, C.c_uint32]
 lib.rt_strerror.restype = C.c_char_p

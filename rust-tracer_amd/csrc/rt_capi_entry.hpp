@@ -1188,6 +1188,107 @@ rt_status rt_intersect_rays_multi_ordered(rt_scene *s, rt_multihit mode, uint32_
                                      "rt_intersect_rays_multi_ordered");
 }
 
+// ---- proximity queries: the k nearest spheres of every point, or every sphere within a radius (rt_near.hpp) ----
+
+rt_status rt_near_spheres_device(rt_scene *s, rt_near mode, uint32_t k, const void *points, const void *radius, uint32_t n, const int32_t *exclude,
+                                 const uint32_t *order, void *gap_out, int32_t *item_out, uint32_t *found_out, rt_stats *stats, void *hip_stream)
+{
+    const char *const what = "rt_near_spheres_device";
+    if (!near_args_ok(s, mode, k, points, radius, n, exclude, order, gap_out, item_out, found_out, what)) return RT_ERR_INVALID_ARGUMENT;
+    const ReadLock rl(s);
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    const void *nodes = nullptr;
+    uint32_t n_nodes = 0;
+    rt_status st = query_stream(s, stream, &nodes, &n_nodes);
+    if (st != RT_OK) return st;
+    if (!stats) return enqueue_near(s, nodes, n_nodes, mode, k, points, radius, n, exclude, order, gap_out, item_out, found_out, nullptr, stream);
+    Context *c = nullptr;
+    if ((st = acquire(s, &c)) != RT_OK) return st;
+    Lease lease{ s, c };
+    HIP_TRY(hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, stream));
+    HIP_TRY(hipEventRecord(c->ev0, stream));
+    st = enqueue_near(s, nodes, n_nodes, mode, k, points, radius, n, exclude, order, gap_out, item_out, found_out, c->d_counters, stream);
+    (void)hipEventRecord(c->ev1, stream);
+    if (st != RT_OK) { (void)hipGetLastError(); lease.inflight = true; return st; }      // (the context goes back behind what is enqueued)
+    return read_query_stats(c, stream, stats);
+}
+
+rt_status rt_near_spheres(rt_scene *s, rt_near mode, uint32_t k, const void *points, const void *radius, uint32_t n, const int32_t *exclude,
+                          const uint32_t *order, void *gap_out, int32_t *item_out, uint32_t *found_out, rt_stats *stats)
+{
+    const char *const what = "rt_near_spheres";
+    if (!near_args_ok(s, mode, k, points, radius, n, exclude, order, gap_out, item_out, found_out, what)) return RT_ERR_INVALID_ARGUMENT;
+    const bool f32 = s->precision == RT_F32;
+    if (!(f32 ? near_points_valid(static_cast<const float *>(points), static_cast<const float *>(radius), n, what)
+              : near_points_valid(static_cast<const double *>(points), static_cast<const double *>(radius), n, what)))
+        return RT_ERR_INVALID_ARGUMENT;
+    if (order && !order_is_permutation(order, n, what)) return RT_ERR_INVALID_ARGUMENT;
+    const ReadLock rl(s);
+    HIP_TRY(hipSetDevice(s->device));
+    rt_status st = RT_OK;
+    // pinned buffers are read and written by the kernel in place, pageable ones go through the call's workspace (as rt_intersect_rays_multi)
+    const size_t esz = f32 ? sizeof(float) : sizeof(double), nk = (size_t)n * k;
+    struct Buf { void *host; size_t bytes; bool out; uint8_t *dev; size_t off; bool staged; };
+    Buf b[7] = { { const_cast<void *>(points), 3 * esz * n, false, nullptr, 0, false }, { const_cast<void *>(radius), esz * n, false, nullptr, 0, false },
+                 { const_cast<int32_t *>(exclude), sizeof(int32_t) * n, false, nullptr, 0, false },
+                 { const_cast<uint32_t *>(order), sizeof(uint32_t) * n, false, nullptr, 0, false },
+                 { gap_out, esz * nk, true, nullptr, 0, false }, { item_out, sizeof(int32_t) * nk, true, nullptr, 0, false },
+                 { found_out, sizeof(uint32_t) * n, true, nullptr, 0, false } };
+    size_t need = 0;
+    for (Buf &x : b) {
+        if (!x.host) continue;
+        const HostDest d = classify_host_pointer(x.host);
+        if (d.bad) {
+            snprintf(g_err, sizeof g_err, "%s: a buffer is device memory; use %s_device", what, what);
+            return RT_ERR_INVALID_ARGUMENT;
+        }
+        if (d.pinned && d.dev_alias && d.room >= x.bytes) { x.dev = d.dev_alias; continue; }
+        x.staged = true;
+        x.off = need;
+        need += (x.bytes + 255) & ~(size_t)255;
+    }
+    Context *c = nullptr;
+    if ((st = acquire(s, &c)) != RT_OK) return st;
+    Lease lease{ s, c };
+    const void *nodes = nullptr;
+    uint32_t n_nodes = 0;
+    if ((st = query_stream(s, c->stream, &nodes, &n_nodes)) != RT_OK) return st;
+    if (need > c->query_cap) {
+        if (c->d_query) HIP_TRY(hipFree(c->d_query));
+        c->d_query = nullptr; c->query_cap = 0;
+        HIP_TRY(hipMalloc(&c->d_query, need));
+        c->query_cap = need;
+    }
+    for (Buf &x : b)
+        if (x.staged) x.dev = static_cast<uint8_t *>(c->d_query) + x.off;
+    // from the first copy on, work of this call may be queued: an error return first waits for it
+#define HIP_DRAIN(expr)                                                                                                   \
+    do {                                                                                                                  \
+        hipError_t e__ = (expr);                                                                                          \
+        if (e__ != hipSuccess) { (void)hipStreamSynchronize(c->stream); return hip_fail(e__, #expr, __LINE__); }          \
+    } while (0)
+    for (const Buf &x : b)
+        if (x.staged && !x.out)
+            HIP_DRAIN(hipMemcpyAsync(x.dev, x.host, x.bytes, hipMemcpyHostToDevice, c->stream));
+    if (stats) {
+        HIP_DRAIN(hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, c->stream));
+        HIP_DRAIN(hipEventRecord(c->ev0, c->stream));
+    }
+    st = enqueue_near(s, nodes, n_nodes, mode, k, b[0].dev, b[1].dev, n, reinterpret_cast<const int32_t *>(b[2].dev),
+                      reinterpret_cast<const uint32_t *>(b[3].dev), b[4].dev, reinterpret_cast<int32_t *>(b[5].dev), reinterpret_cast<uint32_t *>(b[6].dev),
+                      stats ? c->d_counters : nullptr, c->stream);
+    if (st != RT_OK) { (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return st; }
+    if (stats) HIP_DRAIN(hipEventRecord(c->ev1, c->stream));
+    for (const Buf &x : b)
+        if (x.staged && x.out)
+            HIP_DRAIN(hipMemcpyAsync(x.host, x.dev, x.bytes, hipMemcpyDeviceToHost, c->stream));
+    if (stats) return read_query_stats(c, c->stream, stats);          // synchronises the stream
+    HIP_DRAIN(hipStreamSynchronize(c->stream));
+#undef HIP_DRAIN
+    return RT_OK;
+}
+
 // ---- traced rays and camera frames: Renderer::raytrace for any ray, render_region for any pinhole camera (rt_trace.hpp) ----
 
 static rt_status trace_rays_device(rt_scene *s, const void *rays, uint32_t n, void *color_out, void *alpha_out, bool ordered, const uint32_t *order,

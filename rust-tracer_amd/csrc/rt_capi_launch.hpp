@@ -775,6 +775,93 @@ rt_status enqueue_multihit(const rt_scene *s, const void *nodes, uint32_t n_node
                                   : enqueue_multihit<double>(s, nodes, n_nodes, mode, k, rays, tmax, n, dist, normal, item, hits, counters, stream, order);
 }
 
+// ---- proximity queries (rt_near_spheres*, rt_near.hpp) ----
+
+// What both proximity entries check (device pointers are not dereferenced here).
+bool near_args_ok(const rt_scene *s, rt_near mode, uint32_t k, const void *points, const void *radius, uint32_t n, const int32_t *exclude,
+                  const uint32_t *order, const void *gap, const int32_t *item, const uint32_t *found, const char *what)
+{
+    if (!s || !points || !gap || n == 0) { snprintf(g_err, sizeof g_err, "%s: NULL scene, points or gap_out, or n == 0", what); return false; }
+    if (k == 0 || k > RT_NEAR_MAX_K) { snprintf(g_err, sizeof g_err, "%s: k must be 1 .. %d, not %u", what, RT_NEAR_MAX_K, k); return false; }
+    if (mode != RT_NEAR_CLOSEST && mode != RT_NEAR_ALL) { snprintf(g_err, sizeof g_err, "%s: unknown mode %d (closest is 0, all is 1)", what, (int)mode); return false; }
+    const struct { const void *p; const char *name; } words[] = { { item, "item_out" }, { found, "found_out" }, { exclude, "exclude" }, { order, "order" } };
+    for (const auto &w : words)
+        if ((reinterpret_cast<uintptr_t>(w.p) & 3u) != 0) { snprintf(g_err, sizeof g_err, "%s: %s must be 4-byte aligned", what, w.name); return false; }
+    const uintptr_t esz = s->precision == RT_F32 ? sizeof(float) : sizeof(double);
+    for (const void *p : { points, radius, gap })
+        if ((reinterpret_cast<uintptr_t>(p) % esz) != 0) { snprintf(g_err, sizeof g_err, "%s: REAL buffers must be %u-byte aligned", what, (unsigned)esz); return false; }
+    return true;
+}
+
+// The host entry's domain: points finite with |coordinate| <= 1e15 (the scene's own domain: vv stays finite), a radius that is not NaN.
+template <typename T>
+bool near_points_valid(const T *points, const T *radius, uint32_t n, const char *what)
+{
+    for (uint32_t i = 0; i < n; ++i) {
+        for (int c = 0; c < 3; ++c) {
+            const T v = points[3 * (size_t)i + c];
+            if (!std::isfinite(v) || std::fabs((double)v) > 1e15) {
+                snprintf(g_err, sizeof g_err, "%s: point %u has a non-finite coordinate or one beyond +-1e15", what, i);
+                return false;
+            }
+        }
+        if (radius && std::isnan(radius[i])) { snprintf(g_err, sizeof g_err, "%s: radius[%u] is NaN", what, i); return false; }
+    }
+    return true;
+}
+
+template <typename T, bool COUNT, bool ALL, bool ORDERED>
+void launch_near(unsigned bucket, dim3 grid, dim3 block, hipStream_t stream, const rt::NearArgs<T> &a)
+{
+    switch (bucket) {
+    case 1: hipLaunchKernelGGL((rt::k_near_spheres<T, COUNT, ALL, ORDERED, 1>), grid, block, 0, stream, a); break;
+    case 4: hipLaunchKernelGGL((rt::k_near_spheres<T, COUNT, ALL, ORDERED, 4>), grid, block, 0, stream, a); break;
+    case 8: hipLaunchKernelGGL((rt::k_near_spheres<T, COUNT, ALL, ORDERED, 8>), grid, block, 0, stream, a); break;
+    default: hipLaunchKernelGGL((rt::k_near_spheres<T, COUNT, ALL, ORDERED, 16>), grid, block, 0, stream, a); break;
+    }
+}
+
+template <typename T, bool COUNT, bool ALL>
+void launch_near(unsigned bucket, dim3 grid, dim3 block, hipStream_t stream, const rt::NearArgs<T> &a)
+{
+    if (a.order) launch_near<T, COUNT, ALL, true>(bucket, grid, block, stream, a);
+    else launch_near<T, COUNT, ALL, false>(bucket, grid, block, stream, a);
+}
+
+// One proximity launch on `stream`: the list capacity is the smallest bucket >= k (RT_DEBUG_MULTIHIT_BUCKET: a larger one, as for the
+// multi-hit lists); counters != NULL runs the counting flavour (same bytes).
+template <typename T>
+rt_status enqueue_near(const void *nodes, uint32_t n_nodes, rt_near mode, uint32_t k, const void *points, const void *radius, uint32_t n,
+                       const int32_t *exclude, const uint32_t *order, void *gap, int32_t *item, uint32_t *found, rt::Counters *counters, hipStream_t stream)
+{
+    const rt::NearArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), static_cast<const T *>(points), static_cast<const T *>(radius), exclude, order,
+                             static_cast<T *>(gap), item, found, counters, n_nodes, n, k };
+    unsigned bucket = 0;
+    for (unsigned b : rt::kMultiBuckets)
+        if (bucket == 0 && b >= k) bucket = b;
+    const long long forced = knob(RT_DEBUG_MULTIHIT_BUCKET);
+    for (unsigned b : rt::kMultiBuckets)
+        if (forced == (long long)b && b >= k) bucket = b;
+    const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
+    const bool all = mode == RT_NEAR_ALL;
+    if (counters) {
+        if (all) launch_near<T, true, true>(bucket, grid, block, stream, a);
+        else launch_near<T, true, false>(bucket, grid, block, stream, a);
+    } else {
+        if (all) launch_near<T, false, true>(bucket, grid, block, stream, a);
+        else launch_near<T, false, false>(bucket, grid, block, stream, a);
+    }
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+rt_status enqueue_near(const rt_scene *s, const void *nodes, uint32_t n_nodes, rt_near mode, uint32_t k, const void *points, const void *radius, uint32_t n,
+                       const int32_t *exclude, const uint32_t *order, void *gap, int32_t *item, uint32_t *found, rt::Counters *counters, hipStream_t stream)
+{
+    return s->precision == RT_F32 ? enqueue_near<float>(nodes, n_nodes, mode, k, points, radius, n, exclude, order, gap, item, found, counters, stream)
+                                  : enqueue_near<double>(nodes, n_nodes, mode, k, points, radius, n, exclude, order, gap, item, found, counters, stream);
+}
+
 // ---- traced rays and camera frames (rt_trace_rays*, rt_render_camera*, rt_trace.hpp) ----
 
 // The camera domain both rt_render_camera entries check (in double, before the device is touched): 12 finite values, |eye coordinate|

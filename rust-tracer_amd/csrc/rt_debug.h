@@ -60,7 +60,7 @@ typedef enum rt_debug_key {
                                     plain-stream scene.  All must render the same bytes */
     RT_DEBUG_EXACT_COSTS = 22,   /* 0: cooperative quads are picked by the scene's 256 x 256 cost map only (small passes), not by counting a tile list's heaviest
                                     blocks again at the frame's own resolution (rt_capi.hip exact_block_costs).  Default 1 (read when a tile list is first seen) */
-    RT_DEBUG_MULTIHIT_BUCKET = 23, /* the list capacity of rt_intersect_rays_multi* (rt_multihit.hpp: 1, 4, 8 or 16) when it is >= k; default (and any
+    RT_DEBUG_MULTIHIT_BUCKET = 23, /* the list capacity of rt_intersect_rays_multi* and rt_near_spheres* (rt_multihit.hpp, rt_near.hpp: 1, 4, 8 or 16) when it is >= k; default (and any
                                     other value): the smallest one >= k.  Every capacity must give the same bytes */
     RT_DEBUG_KEYS = 24
 } rt_debug_key;

@@ -81,6 +81,24 @@ def sphere_keys(spheres):
     return key
 
 
+def sphere_gaps(points, spheres):
+    """The surface gap between every point of `points` (n x 3) and every sphere of `spheres` (m x 4: cx, cy, cz, r) -> REAL[n, m], the metric
+    of rt_near_spheres restated in numpy bit for bit (include/rtrace_hip.h states it), in the arrays' dtype (float32 or float64, the same for
+    both), every operation rounded once:  rr = r * r;  v = c - p;  vv = (v.x*v.x + v.y*v.y) + v.z*v.z;  gap = sqrt(vv) - sqrt(rr) where
+    rr > 0, else +inf.  Negative inside the sphere.  A record without a positive rr -- radius 0: a dead slot, a dead group's bound -- is at
+    +inf from every point.  DeviceScene.near lists, per point, the k smallest of a row (ties by index) or counts those below a radius."""
+    p, s = np.asarray(points), np.asarray(spheres)
+    if p.dtype not in (np.float32, np.float64) or s.dtype != p.dtype or p.ndim != 2 or p.shape[1] != 3 or s.ndim != 2 or s.shape[1] != 4:
+        raise ValueError("points must be (n, 3) and spheres (m, 4), both float32 or both float64")
+    R = p.dtype.type
+    rr = s[:, 3] * s[:, 3]
+    with np.errstate(invalid="ignore", over="ignore"):
+        v = s[None, :, :3] - p[:, None, :]
+        vv = (v[..., 0] * v[..., 0] + v[..., 1] * v[..., 1]) + v[..., 2] * v[..., 2]
+        gap = np.sqrt(vv) - np.sqrt(np.where(rr > 0, rr, R(1.0)))[None, :]
+    return np.where((rr > 0)[None, :], gap, R(np.inf)).astype(R, copy=False)
+
+
 def balanced_ranges(n, leaf_size=4):
     """rt_balanced_ranges: a topology from the item count alone -> int32[g, 2], the groups (first item, item count) of the recursive halving
     of (0, n) down to `leaf_size`, in DFS pre-order (a group's first half holds (count + 1) // 2 items; leaves are groups too).  Valid as
@@ -813,6 +831,112 @@ class DeviceScene:
         mode = capi.RT_MULTIHIT_ALL if all_hits else capi.RT_MULTIHIT_CLOSEST
         return self._ray_query("rt_intersect_rays_multi", lambda f, r, t, n, *rest: f(self._h, mode, k, r, t, n, *rest),
                                (((k,), "R"), ((k, 3), "R"), ((k,), np.int32), ((), np.uint32)), rays, tmax, want_stats, stream, out, order)
+
+    def near(self, points, k, radius=None, all_within=False, exclude=None, want_stats=False, stream=None, out=None, order=None):
+        """rt_near_spheres / rt_near_spheres_device: the k nearest spheres of every point of `points` (n x 3, the scene's REAL dtype), by
+        surface gap (sphere_gaps is the metric: negative inside a sphere), nearest first, equal gaps in DFS order -> (gap[n, k], item[n, k]
+        (DFS slot or -1), found[n] (uint32)[, stats dict]).  radius: the search radius per point (an array of the scene's REAL) or one value
+        (rounded to REAL; None: +inf); only spheres with a gap below it are listed, and an empty slot reads the radius and -1.
+        all_within=False (RT_NEAR_CLOSEST): found = the filled slots.  all_within=True (RT_NEAR_ALL): found = every sphere below the
+        radius (may exceed k), the list its k nearest.  1 <= k <= RT_NEAR_MAX_K.  exclude (int32[n]): the item slot each query ignores --
+        np.arange(n) for the self-queries of the scene's own items; -1 or a slot outside the scene excludes nothing.  A dead slot of a
+        dynamic scene is never listed.  numpy arrays go through the host entry, a torch tensor on this scene's device through the device
+        entry on `stream`, with the stream discipline of intersect(); out: optional (gap, item, found) arrays / tensors to fill.
+        order (uint32[n]): lane j carries query order[j]; the results and counters are the same bytes whatever the order, only the time
+        differs.  The host entry wants a permutation; through the device entry an index >= n carries no query and leaves that thread's
+        outputs alone.  A query is a sphere-shaped record, so a coherent order is
+            order = dev.sphere_order(np.concatenate([points, np.ones((n, 1), points.dtype)], axis=1))."""
+        k = int(k)
+        if not 1 <= k <= capi.RT_NEAR_MAX_K:
+            raise ValueError("k must be 1 .. %d, not %d" % (capi.RT_NEAR_MAX_K, k))
+        mode = capi.RT_NEAR_ALL if all_within else capi.RT_NEAR_CLOSEST
+        R = _real(self.scene.precision)
+        st = capi.Stats()
+        stp = C.byref(st) if want_stats else None
+        torch = sys.modules.get("torch")
+        if torch is not None and isinstance(points, torch.Tensor):
+            tdt = torch.float32 if R == np.float32 else torch.float64
+            dev = torch.device("cuda", self.device)
+            if points.dtype != tdt or points.dim() != 2 or points.shape[1] != 3 or points.shape[0] == 0:
+                raise ValueError("points must be a non-empty (n, 3) %s tensor" % tdt)
+            if points.device != dev:
+                raise ValueError("points must be on %s, not %s" % (dev, points.device))
+            n = points.shape[0]
+            if isinstance(radius, torch.Tensor):
+                if radius.dim() == 0 and radius.dtype.is_floating_point:
+                    radius = radius.to(tdt)                              # one value: rounded to the scene's REAL
+                if radius.dtype != tdt or radius.numel() not in (1, n):
+                    raise ValueError("radius must be a %s value or (n,) tensor" % tdt)
+            elif radius is not None:
+                radius = self._radius_array(radius, R, n)
+            if exclude is not None and (not isinstance(exclude, torch.Tensor) or exclude.dtype != torch.int32 or exclude.shape != (n,) or exclude.device != dev):
+                raise ValueError("exclude must be None or an (n,) int32 tensor on %s" % dev)
+            if order is not None:
+                try:
+                    order = self._order_torch(torch, order, n, dev)
+                except ValueError:
+                    raise ValueError("order must be None or an (n,) uint32 / int32 tensor on %s" % dev) from None
+            specs = (((n, k), tdt), ((n, k), torch.int32), ((n,), torch.uint32))
+            if out is not None:
+                out = tuple(out)
+                if len(out) != 3 or any(not isinstance(a, torch.Tensor) or a.dtype != dt or tuple(a.shape) != shape or a.device != dev or not a.is_contiguous()
+                                        for a, (shape, dt) in zip(out, specs)):
+                    raise ValueError("out: contiguous tensors on %s of %s" % (dev, ", ".join("%s %s" % (dt, shape) for shape, dt in specs)))
+            qs, cur = self._device_stream(torch, stream)
+            if qs != cur:
+                qs.wait_stream(cur)
+            with torch.cuda.stream(qs):
+                p = points.contiguous()
+                r = None
+                if isinstance(radius, torch.Tensor):
+                    r = radius.to(dev).reshape(-1).expand(n).contiguous()
+                elif radius is not None:
+                    r = torch.from_numpy(radius.copy()).to(dev)              # (a broadcast view is read-only)
+                ex = None if exclude is None else exclude.contiguous()
+                res = out if out is not None else tuple(torch.empty(shape, dtype=dt, device=dev) for shape, dt in specs)
+                ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
+                rc = capi.lib.rt_near_spheres_device(self._h, mode, k, ptr(p), ptr(r), n, ptr(ex), ptr(order), ptr(res[0]), ptr(res[1]), ptr(res[2]),
+                                                     stp, C.c_void_p(qs.cuda_stream))
+            if qs != cur:
+                for x in (points, radius, exclude, order) + tuple(res if out is not None else ()):
+                    if isinstance(x, torch.Tensor) and x.is_cuda:
+                        x.record_stream(qs)
+            capi.check(rc, "rt_near_spheres_device")
+        else:
+            if not isinstance(points, np.ndarray) or points.dtype != R or points.ndim != 2 or points.shape[1] != 3 or points.shape[0] == 0:
+                raise ValueError("points must be a non-empty (n, 3) numpy array of %s (or a torch tensor on the scene's device)" % np.dtype(R).name)
+            n = points.shape[0]
+            p = np.ascontiguousarray(points)
+            r = None if radius is None else self._radius_array(radius, R, n)
+            ex = None
+            if exclude is not None:
+                ex = np.asarray(exclude)
+                if ex.dtype != np.int32 or ex.shape != (n,):
+                    raise ValueError("exclude must be None or an (n,) int32 array")
+                ex = np.ascontiguousarray(ex)
+            o = None if order is None else self._order_numpy(order, n)
+            specs = (((n, k), R), ((n, k), np.int32), ((n,), np.uint32))
+            if out is None:
+                res = tuple(np.empty(shape, dtype=dt) for shape, dt in specs)
+            else:
+                res = tuple(out)
+                if len(res) != 3 or any(not isinstance(a, np.ndarray) or a.dtype != dt or a.shape != shape or not a.flags.c_contiguous
+                                        for a, (shape, dt) in zip(res, specs)):
+                    raise ValueError("out: contiguous arrays of " + ", ".join("%s %s" % (np.dtype(dt).name, shape) for shape, dt in specs))
+            ptr = lambda x: None if x is None else x.ctypes.data
+            rc = capi.lib.rt_near_spheres(self._h, mode, k, ptr(p), ptr(r), n, ptr(ex), ptr(o), ptr(res[0]), ptr(res[1]), ptr(res[2]), stp)
+            capi.check(rc, "rt_near_spheres")
+        if want_stats:
+            return tuple(res) + (st.as_dict(),)
+        return tuple(res)
+
+    @staticmethod
+    def _radius_array(radius, R, n):
+        """near()'s radius as a contiguous REAL[n] (one value is rounded to REAL; an array must already be REAL)."""
+        try:
+            return _tmax_array(radius, R, n)
+        except ValueError:
+            raise ValueError("radius must be one value or an (n,) array of %s" % np.dtype(R).name) from None
 
     @staticmethod
     def _order_numpy(order, n):

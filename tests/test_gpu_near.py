@@ -1,0 +1,542 @@
+"""Proximity queries on the GPU (rt_near_spheres / rt_near_spheres_device, csrc/rt_near.hpp): the k nearest spheres of a
+point and every sphere within a radius, bit for bit against a restatement of the walk over the scene's node stream with rta.sphere_gaps as
+its metric, and against brute force over all items wherever no gap grazes a cutoff."""
+import functools
+import threading
+
+import numpy as np
+import pytest
+
+import rust_tracer_amd as rta
+from rust_tracer_amd import capi
+from tests import util
+from tests.scenes import random_nested_scene
+from tests.test_gpu_multihit import node_stream
+from tests.test_gpu_query import REAL, bits, scene_cases
+
+pytestmark = pytest.mark.gpu
+
+PRECISIONS = pytest.mark.parametrize("precision", [rta.RT_F32, rta.RT_F64], ids=["f32", "f64"])
+BUCKETS = (1, 4, 8, 16)
+KS = (1, 3, 4, 5, 8, 16)
+RT_K = rta.RT_NEAR_MAX_K
+LIGHT, EYE = (-1.0, -3.0, 2.0), (0.0, 0.0, -4.0)
+FAMILIES = ("centres", "surfaces", "inside inner bounds", "outside the root")
+
+
+def _unit(v):
+    v = np.asarray(v, dtype=np.float64)
+    return v / np.linalg.norm(v, axis=-1, keepdims=True)
+
+
+def query_families(scene, rng, n_each=40, live=None, graze=True):
+    """(points REAL[4 n_each, 3], radius REAL[4 n_each]), family f in rows [f n_each, (f + 1) n_each): item centres (gap = -r; picked with
+    repetition, and equal spheres tie), points on item surfaces, points inside inner bounds, points outside the root at 1.2 - 3 root
+    radii; radii +inf, finite (0.01 - 0.5 root radii), 0 and negative (up to the median item radius), in turn.  A point on a surface
+    with radius 0 is the grazing case itself (a gap of a few ulp against a cutoff of 0): graze=False gives those queries a quarter of
+    the median item radius instead, with either sign."""
+    items = scene.items.astype(np.float64)
+    if live is not None:
+        items = items[np.asarray(live) != 0]
+    bounds = None
+    if scene.bounds is not None and len(scene.bounds):
+        bounds = scene.bounds.astype(np.float64)
+        bounds = bounds[bounds[:, 3] > 0]                                       # (a dead group reports {0, 0, 0, 0})
+    if bounds is None or len(bounds) == 0:
+        c = items[:, :3].mean(axis=0)
+        bounds = np.array([[c[0], c[1], c[2], np.max(np.linalg.norm(items[:, :3] - c, axis=1) + items[:, 3])]])
+    root_c, root_r = bounds[0, :3], bounds[0, 3]
+    pick = lambda: items[rng.integers(0, len(items), n_each)]
+    s = pick()
+    inner = bounds[rng.integers(0, len(bounds), n_each)]
+    pts = [pick()[:, :3],
+           s[:, :3] + _unit(rng.normal(size=(n_each, 3))) * s[:, 3:],
+           inner[:, :3] + _unit(rng.normal(size=(n_each, 3))) * inner[:, 3:] * rng.uniform(0.0, 0.5, (n_each, 1)),
+           root_c + _unit(rng.normal(size=(n_each, 3))) * root_r * rng.uniform(1.2, 3.0, (n_each, 1))]
+    R = REAL[scene.precision]
+    points = np.ascontiguousarray(np.concatenate(pts).astype(R))
+    n = len(points)
+    choice = (np.arange(n) + rng.integers(0, 4)) % 4
+    finite = root_r * 10.0 ** rng.uniform(-2.0, -0.3, n)
+    negative = -rng.uniform(0.0, 1.0, n) * np.median(items[:, 3])
+    zero = np.zeros(n)
+    if not graze:
+        zero[n_each:2 * n_each] = np.where(np.arange(n_each) % 8 < 4, 0.25, -0.25) * np.median(items[:, 3])
+    radius = np.where(choice == 0, np.inf, np.where(choice == 1, finite, np.where(choice == 2, zero, negative))).astype(R)
+    return points, radius
+
+
+class Walker:
+    """The definition of the proximity walk (include/rtrace_hip.h), one query at a time, over node_stream(s); every gap is
+    rta.sphere_gaps' in the scene's precision (made once for all points and nodes: the walks for every k and both modes share them)."""
+
+    def __init__(self, s, points):
+        R = REAL[s.precision]
+        nodes = node_stream(s)
+        self.bound = [x[1] for x in nodes]
+        self.skip = [x[2] for x in nodes]
+        self.item = [x[3] for x in nodes]
+        spheres = np.array([x[0] for x in nodes], dtype=np.float64).reshape(-1, 4).astype(R)        # (exact: they were REAL)
+        self.gaps = [row.tolist() for row in rta.sphere_gaps(np.asarray(points, dtype=R), spheres)] if len(nodes) else [[] for _ in points]
+
+    def walk(self, q, rho, k, all_within, exclude=-1):
+        gap = self.gaps[q]
+        rho = float(rho)
+        slots = [(rho, -1)] * k
+        found = tests_items = tests_bounds = 0
+        i, n = 0, len(gap)
+        while i < n:
+            g = gap[i]
+            if self.bound[i]:
+                tests_bounds += 1
+                i = self.skip[i] if g >= (rho if all_within else slots[-1][0]) else i + 1
+                continue
+            tests_items += 1
+            if self.item[i] != exclude:
+                if all_within and not g >= rho:
+                    found += 1
+                if not g >= slots[-1][0]:
+                    j = 0
+                    while slots[j][0] <= g:
+                        j += 1
+                    slots = slots[:j] + [(g, self.item[i])] + slots[j:-1]
+            i += 1
+        if not all_within:
+            found = sum(1 for _, it in slots if it >= 0)
+        return [x[0] for x in slots], [x[1] for x in slots], found, tests_items, tests_bounds
+
+    def all(self, radius, k, all_within, exclude=None):
+        return [self.walk(q, radius[q], k, all_within, -1 if exclude is None else int(exclude[q])) for q in range(len(radius))]
+
+
+def assert_walk(res, ref, R, what):
+    gap, item, found, st = res
+    np.testing.assert_array_equal(bits(gap, R), bits([x[0] for x in ref], R), err_msg=str(what))
+    np.testing.assert_array_equal(item, [x[1] for x in ref], err_msg=str(what))
+    np.testing.assert_array_equal(found, [x[2] for x in ref], err_msg=str(what))
+    assert st["sphere_tests"] == sum(x[3] for x in ref), what
+    assert st["bound_tests"] == sum(x[4] for x in ref), what
+    assert st["tests_executed"] == st["sphere_tests"] + st["bound_tests"], what
+    assert st["primary"] == len(ref) and st["hits"] == int((np.asarray(found) > 0).sum()), what
+
+
+def same_bytes(a, b):
+    for x, y in zip(a, b):
+        if hasattr(x, "cpu"):
+            x = x.cpu().numpy()
+        if hasattr(y, "cpu"):
+            y = y.cpu().numpy()
+        np.testing.assert_array_equal(np.ascontiguousarray(x).view(np.uint8), np.ascontiguousarray(y).view(np.uint8))
+
+
+def scene_of(items, bounds, ranges, precision):
+    return rta.Scene(items, rta.normalized(LIGHT, precision), EYE, bounds, ranges, precision)
+
+
+@functools.lru_cache(maxsize=None)
+def cases(precision):
+    """name -> rta.Scene: the level-3 pyramid and the 100,000 spheres of the query tests, random_nested_scene(4) (some of its bounds do
+    not enclose their items: the result is the walk's), and 300 random spheres in Morton order under balanced ranges with refit bounds
+    (which do enclose)."""
+    out = {name: s for name, s, _ in scene_cases(precision) if name in ("default_L3", "100k")}
+    it, bd, rg = random_nested_scene(4)
+    out["nested"] = scene_of(it, bd, rg, precision)
+    R = REAL[precision]
+    rng = np.random.default_rng(300)
+    sp = np.concatenate([rng.uniform(-1, 1, (300, 3)), rng.uniform(0.03, 0.12, (300, 1))], axis=1).astype(R)
+    sp = sp[np.argsort(rta.sphere_keys(sp), kind="stable")]
+    rg = rta.balanced_ranges(300, 4)
+    out["refit"] = scene_of(sp, rta.refit_bounds(sp, rg, precision), rg, precision)
+    return out
+
+
+@PRECISIONS
+def test_the_lists_restate_the_walk_bit_for_bit(precision):
+    R = REAL[precision]
+    rng = np.random.default_rng(51 + precision)
+    for name in ("default_L3", "nested", "100k"):
+        s = cases(precision)[name]
+        d = rta.DeviceScene(s)
+        points, radius = query_families(s, rng, 3 if name == "100k" else 40)
+        w = Walker(s, points)
+        for all_within in (False, True):
+            for k in KS:
+                res = d.near(points, k, radius, all_within=all_within, want_stats=True)
+                assert_walk(res, w.all(radius, k, all_within), R, (name, k, all_within))
+                gap, item, found = res[:3]
+                assert (found >= (item >= 0).sum(axis=1)).all() and (all_within or (found == (item >= 0).sum(axis=1)).all())
+                empty = item < 0
+                np.testing.assert_array_equal(bits(gap[empty], R), bits(np.broadcast_to(radius[:, None], gap.shape)[empty], R))
+                assert (gap[:, 1:] >= gap[:, :-1]).all()                         # nearest first
+        # k = 1 with no radius is "the nearest sphere": there always is one, and at a sphere's centre it is no farther than that sphere
+        n_each = len(points) // 4
+        gap, item, found = d.near(points[:n_each], 1)
+        assert (found == 1).all() and (item >= 0).all() and (gap[:, 0] <= rta.sphere_gaps(points[:n_each], s.items).min(axis=1)).all()
+        d.close()
+
+
+def brute_force(s, points, radius):
+    """(gaps[n, m], order[n, 18], radius): every gap, and the 18 smallest of each query in a stable order (ties by DFS index)."""
+    gaps = rta.sphere_gaps(points, s.items)
+    return gaps, np.argsort(gaps, axis=1, kind="stable")[:, :RT_K + 2], radius
+
+
+def expected(brute, k):
+    """(gap[n, k], item[n, k], count[n]) over all items: the k smallest gaps below the radius, and how many lie below it."""
+    gaps, order, radius = brute
+    order = order[:, :k]
+    g = np.take_along_axis(gaps, order, axis=1)
+    below = g < radius[:, None]
+    g = np.where(below, g, radius[:, None])
+    it = np.where(below, order, -1).astype(np.int32)
+    pad = k - g.shape[1]
+    if pad > 0:
+        g = np.concatenate([g, np.repeat(radius[:, None], pad, axis=1)], axis=1)
+        it = np.concatenate([it, np.full((len(g), pad), -1, np.int32)], axis=1)
+    return g, it, (gaps < radius[:, None]).sum(axis=1).astype(np.uint32)
+
+
+def grazing(brute, k, all_within, R):
+    """The queries the definition hands to the walk: some item's gap lies within 1e-5 max(1, |gap|) (f32; f64: 1e-12) of a cutoff.  The
+    cutoffs: the radius (ALL culls against nothing else; a CLOSEST list that is not full culls against it too) and, for CLOSEST, the
+    k-th and the (k + 1)-th smallest gap -- a bound can be culled by an ulp only against a cutoff one of its items all but meets."""
+    gaps, order, radius = brute
+    eps = 1e-5 if R == np.float32 else 1e-12
+    g = gaps.astype(np.float64)
+    out = (np.abs(g - radius.astype(np.float64)[:, None]) <= eps * np.maximum(1.0, np.abs(g))).any(axis=1)
+    if not all_within:
+        top = np.take_along_axis(g, order, axis=1)                              # ascending
+        meet = np.diff(top, axis=1) <= eps * np.maximum(1.0, np.abs(top[:, 1:]))  # meet[:, j]: the (j + 1)-th and (j + 2)-th smallest all but meet
+        for j in (k - 2, k - 1, k):                                             # the neighbours of the k-th and of the (k + 1)-th
+            if 0 <= j < meet.shape[1]:
+                out |= meet[:, j]
+    return out
+
+
+def brute_cases(precision):
+    """The scenes whose bounds enclose their items, so that the walk can differ from brute force by grazing alone: the refit scene, and
+    the 100,000 spheres in f64.  (In f32 the 100,000 sit too close together for the cap below: from outside the root, one query in ten
+    has two of its nearest gaps within 1e-4 of each other.  The walk over that scene is held bit for bit, f32 included, by the test above.)"""
+    return ("refit", "100k") if precision == rta.RT_F64 else ("refit",)
+
+
+@PRECISIONS
+def test_the_walk_is_brute_force_where_no_gap_grazes_a_cutoff(precision):
+    R = REAL[precision]
+    rng = np.random.default_rng(61 + precision)
+    for name in brute_cases(precision):
+        s = cases(precision)[name]
+        d = rta.DeviceScene(s)
+        n_each = 20 if name == "100k" else 40
+        points, radius = query_families(s, rng, n_each, graze=False)
+        brute = brute_force(s, points, radius)
+        for k in KS:
+            ref_g, ref_i, ref_n = expected(brute, k)
+            for all_within in (False, True):
+                left_out = grazing(brute, k, all_within, R)
+                for f, family in enumerate(FAMILIES):
+                    assert left_out[f * n_each:(f + 1) * n_each].sum() <= 0.05 * n_each, (name, k, all_within, family)
+                keep = ~left_out
+                gap, item, found = d.near(points, k, radius, all_within=all_within)
+                what = str((name, k, all_within))
+                np.testing.assert_array_equal(bits(gap[keep], R), bits(ref_g[keep], R), err_msg=what)
+                np.testing.assert_array_equal(item[keep], ref_i[keep], err_msg=what)
+                np.testing.assert_array_equal(found[keep], (ref_n if all_within else np.minimum(ref_n, k))[keep], err_msg=what)
+        d.close()
+
+
+@PRECISIONS
+def test_every_capacity_gives_the_same_bytes(precision):
+    s = cases(precision)["nested"]
+    d = rta.DeviceScene(s)
+    points, radius = query_families(s, np.random.default_rng(5), 40)
+    for all_within in (False, True):
+        for k in (1, 3, 5, 8):
+            base = d.near(points, k, radius, all_within=all_within, want_stats=True)
+            for bucket in BUCKETS:
+                if bucket >= k:
+                    with util.control(capi.DEBUG_MULTIHIT_BUCKET, bucket):
+                        got = d.near(points, k, radius, all_within=all_within, want_stats=True)
+                    same_bytes(base[:3], got[:3])
+                    assert [got[3][c] for c in ("primary", "hits", "sphere_tests", "bound_tests")] == \
+                           [base[3][c] for c in ("primary", "hits", "sphere_tests", "bound_tests")], (k, bucket, all_within)
+    d.close()
+
+
+@PRECISIONS
+def test_exclude_leaves_the_querys_own_sphere_out(precision):
+    R = REAL[precision]
+    for name in ("default_L3", "refit"):
+        s = cases(precision)[name]
+        d = rta.DeviceScene(s)
+        n = len(s.items)
+        points = np.ascontiguousarray(s.items[:, :3])
+        rng = np.random.default_rng(9)
+        radius = np.where(rng.integers(0, 3, n) == 0, np.inf, rng.uniform(-0.1, 0.6, n)).astype(R)
+        me = np.arange(n, dtype=np.int32)
+        w = Walker(s, points)
+        own_gap = np.diagonal(rta.sphere_gaps(points, s.items))
+        for k in (1, 4, 16):
+            # ALL culls against the radius alone: the walk is the same walk, one item less is found where the own sphere was
+            plain = d.near(points, k, radius, all_within=True, want_stats=True)
+            excl = d.near(points, k, radius, all_within=True, exclude=me, want_stats=True)
+            assert not (excl[1] == me[:, None]).any()
+            for c in ("primary", "sphere_tests", "bound_tests", "tests_executed"):
+                assert excl[3][c] == plain[3][c], (name, k, c)
+            was_found = own_gap < radius
+            np.testing.assert_array_equal(plain[2].astype(np.int64) - excl[2], was_found.astype(np.int64))
+            assert_walk(excl, w.all(radius, k, True, me), R, (name, k, "all"))
+            # CLOSEST: the own sphere would have tightened the cutoff, so the tests differ: the definition with `exclude` is the yardstick
+            excl = d.near(points, k, radius, exclude=me, want_stats=True)
+            assert not (excl[1] == me[:, None]).any()
+            assert_walk(excl, w.all(radius, k, False, me), R, (name, k, "closest"))
+            # -1 and slots outside the scene exclude nothing
+            plain = d.near(points, k, radius, want_stats=True)
+            for none in (np.full(n, -1, np.int32), np.full(n, n, np.int32), np.full(n, -2 ** 31, np.int32), np.full(n, 2 ** 31 - 1, np.int32)):
+                got = d.near(points, k, radius, exclude=none, want_stats=True)
+                same_bytes(plain[:3], got[:3])
+                assert {c: v for c, v in got[3].items() if c != "device_ms"} == {c: v for c, v in plain[3].items() if c != "device_ms"}
+        d.close()
+
+
+def test_any_order_gives_the_same_bytes_and_counters():
+    import torch
+    s = cases(rta.RT_F32)["refit"]
+    d = rta.DeviceScene(s)
+    points, radius = query_families(s, np.random.default_rng(13), 80)        # 320 queries: two blocks, the second one partly filled
+    n, k = len(points), 5
+    counters = lambda st: {c: v for c, v in st.items() if c != "device_ms"}
+    for all_within in (False, True):
+        ref = d.near(points, k, radius, all_within=all_within, want_stats=True)
+        perm = np.random.default_rng(14).permutation(n).astype(np.uint32)
+        coherent = d.sphere_order(np.concatenate([points, np.ones((n, 1), points.dtype)], axis=1))
+        assert sorted(coherent.tolist()) == list(range(n))
+        for order in (perm, coherent, perm.astype(np.int64)):
+            got = d.near(points, k, radius, all_within=all_within, want_stats=True, order=order)
+            same_bytes(ref[:3], got[:3])
+            assert counters(got[3]) == counters(ref[3])
+        with pytest.raises(rta.RtError):                                         # the host entry wants a permutation
+            d.near(points, k, radius, order=np.zeros(n, np.uint32))
+        # the device entry: entries >= n carry no query, and what they would have written keeps the caller's bytes
+        carried = np.random.default_rng(15).random(n) < 0.7
+        partial = perm.copy()
+        partial[~carried[perm]] = np.where(np.arange((~carried).sum()) % 2 == 0, n, 0xFFFFFFFF).astype(np.uint32)
+        tp, tr = torch.from_numpy(points).cuda(), torch.from_numpy(radius).cuda()
+        out = (torch.full((n, k), -77.0, dtype=torch.float32, device="cuda"), torch.full((n, k), -77, dtype=torch.int32, device="cuda"),
+               torch.full((n,), 77, dtype=torch.int32, device="cuda").view(torch.uint32))
+        got = d.near(tp, k, tr, all_within=all_within, want_stats=True, out=out, order=torch.from_numpy(partial.view(np.int32)).cuda().view(torch.uint32))
+        torch.cuda.synchronize()
+        gap, item, found = (x.cpu().numpy() for x in got[:3])
+        same_bytes([x[carried] for x in ref[:3]], (gap[carried], item[carried], found[carried]))
+        assert (gap[~carried] == -77.0).all() and (item[~carried] == -77).all() and (found[~carried] == 77).all()
+        part = d.near(np.ascontiguousarray(points[carried]), k, np.ascontiguousarray(radius[carried]), all_within=all_within, want_stats=True)
+        assert counters(got[3]) == counters(part[3])
+        full = d.near(tp, k, tr, all_within=all_within, want_stats=True, order=torch.from_numpy(perm.view(np.int32)).cuda())
+        same_bytes(ref[:3], full[:3])
+        assert counters(full[3]) == counters(ref[3])
+    d.close()
+
+
+@PRECISIONS
+def test_scenes_without_bounds_give_the_brute_force_answer(precision):
+    R = REAL[precision]
+    light = rta.normalized(LIGHT, precision)
+    it, _, _ = random_nested_scene(3)
+    nested = rta.Scene(it, light, EYE, precision=precision)
+    ten = rta.Scene(it[:10], light, EYE, precision=precision)
+    # exact ties: three bit-identical spheres (items 0, 2, 6), two more (1, 3) at the same gap, 2.5, from the origin
+    ties = rta.Scene([(0.0, 0.0, 0.0, 1.0), (3.0, 0.0, 0.0, 0.5), (0.0, 0.0, 0.0, 1.0), (0.0, 0.0, -3.0, 0.5), (0.0, 4.0, 0.0, 0.5),
+                      (0.0, -3.0, 4.0, 0.5), (0.0, 0.0, 0.0, 1.0)], light, EYE, precision=precision)
+    for s in (nested, ten, ties):
+        d = s.device()
+        points, radius = query_families(s, np.random.default_rng(17), 12)
+        points[0], radius[0] = 0.0, np.inf
+        for k in (1, 3, 16):
+            ref_g, ref_i, ref_n = expected(brute_force(s, points, radius), k)   # the flat stream is never culled: no query is left out
+            for all_within in (True, False):
+                gap, item, found, st = d.near(points, k, radius, all_within=all_within, want_stats=True)
+                np.testing.assert_array_equal(bits(gap, R), bits(ref_g, R))
+                np.testing.assert_array_equal(item, ref_i)
+                np.testing.assert_array_equal(found, ref_n if all_within else np.minimum(ref_n, k))
+                assert st["bound_tests"] == 0 and st["sphere_tests"] == len(points) * len(s.items)
+    # ALL with k = 16 on ten items: found is the count, and every one of them is listed
+    points = np.zeros((1, 3), R)
+    gap, item, found = ten.device().near(points, 16, all_within=True)
+    assert found[0] == 10 and sorted(item[0, :10].tolist()) == list(range(10)) and (item[0, 10:] == -1).all() and np.isinf(gap[0, 10:]).all()
+    # ... and found > k where more than k items are in range
+    gap, item, found = nested.device().near(points, 4, all_within=True)
+    assert found[0] == len(nested.items) > 4 and (item[0] >= 0).all()
+    gap, item, found = ties.device().near(points, 4, all_within=True)
+    assert item[0].tolist() == [0, 2, 6, 1] and gap[0].tolist() == [-1.0, -1.0, -1.0, 2.5] and found[0] == 7
+    gap, item, found = ties.device().near(points, 5)                             # equal gaps in DFS order
+    assert item[0].tolist() == [0, 2, 6, 1, 3] and gap[0].tolist() == [-1.0, -1.0, -1.0, 2.5, 2.5] and found[0] == 5
+    gap, item, found = ties.device().near(points, 5, 2.5)                        # strictly below the radius: the two at 2.5 stay out
+    assert item[0].tolist() == [0, 2, 6, -1, -1] and found[0] == 3 and gap[0].tolist() == [-1.0, -1.0, -1.0, 2.5, 2.5]
+    for s in (nested, ten, ties):
+        s.device().close()
+
+
+CAPACITY, LEAF = 300, 4
+
+
+def spheres_of(seed, R, n=CAPACITY, spread=1.0):
+    rng = np.random.default_rng(seed)
+    return np.ascontiguousarray(np.concatenate([rng.uniform(-spread, spread, (n, 3)), rng.uniform(0.03, 0.12, (n, 1))], axis=1).astype(R))
+
+
+def check_dynamic(d, items, live, ranges, precision, what):
+    """near() on dynamic scene d, which holds `items` with `live`, against the Walker over a fresh static scene (host side only) made from
+    the live items -- a dead slot is {0, 0, 0, 0}, which sphere_gaps puts at +inf as the walk does the dead record -- and bounds()."""
+    R = REAL[precision]
+    live = np.asarray(live) != 0
+    np.testing.assert_array_equal(d.live(), live.astype(np.uint8), err_msg=what)
+    it = np.where(live[:, None], items, 0).astype(R)
+    fresh = scene_of(it, d.bounds() if ranges is not None else None, ranges, precision)
+    n_each = 20
+    points, radius = query_families(fresh, np.random.default_rng(23), n_each, live=live)
+    points[0], radius[0] = 0.0, np.inf                                           # where the dead record's centre sits
+    points[1], radius[1] = 0.0, 0.5
+    w = Walker(fresh, points)
+    dead = np.flatnonzero(~live)
+    for all_within in (True, False):
+        for k in (1, 4, 16):
+            res = d.near(points, k, radius, all_within=all_within, want_stats=True)
+            assert_walk(res, w.all(radius, k, all_within), R, (what, k, all_within))
+            assert not np.isin(res[1], dead).any(), (what, k, all_within)
+    gap, item, found = d.near(points[:1], 16, all_within=True)
+    assert found[0] == live.sum() and np.isfinite(gap[0, :min(16, live.sum())]).all()
+    me = np.flatnonzero(live).astype(np.int32)[:64]                              # self-queries of live spheres
+    if len(me):
+        res = d.near(np.ascontiguousarray(it[me, :3]), 4, R(0.05), exclude=me, want_stats=True)
+        assert_walk(res, Walker(fresh, it[me, :3]).all(np.full(len(me), 0.05, R), 4, False, me), R, (what, "self"))
+        assert not np.isin(res[1], dead).any() and not (res[1] == me[:, None]).any()
+
+
+@PRECISIONS
+def test_dynamic_and_live_scenes_answer_as_a_fresh_scene(precision):
+    R = REAL[precision]
+    ranges = rta.balanced_ranges(CAPACITY, LEAF)
+    assert len(ranges) > 100 and ranges[0].tolist() == [0, CAPACITY]             # seven levels of halving down to leaves of four
+    d = rta.DeviceScene(rta.Scene.from_spheres_balanced(spheres_of(1, R), leaf_size=LEAF, precision=precision), 0, True)
+    everyone = np.ones(CAPACITY, np.uint8)
+    moved = spheres_of(2, R)
+    d.update(moved)
+    check_dynamic(d, moved, everyone, ranges, precision, "update")
+    sp = spheres_of(3, R, spread=2.0)
+    order = d.rebuild(sp)
+    check_dynamic(d, sp[order], everyone, ranges, precision, "rebuild")
+    live = (np.random.default_rng(4).random(CAPACITY) < 0.5).astype(np.uint8)
+    live[:8] = 0                                                                 # two whole leaves: dead groups
+    garbage = sp[order].copy()
+    garbage[live == 0] = np.nan                                                  # a dead slot may hold any bits
+    d.update(garbage, live=live)
+    check_dynamic(d, sp[order], live, ranges, precision, "50 % dead")
+    assert (d.bounds()[:, 3] == 0).any()
+    half = CAPACITY // 2
+    order = d.rebuild(sp, n=half)
+    it = np.zeros((CAPACITY, 4), R)
+    it[:half] = sp[:half][order]
+    check_dynamic(d, it, np.arange(CAPACITY) < half, ranges, precision, "rebuild of half")
+    # n = 0: every query ends at the dead root
+    d.rebuild(sp, n=0)
+    assert not d.live().any() and not d.bounds().any()
+    points = np.ascontiguousarray(np.concatenate([np.zeros((1, 3), R), sp[:99, :3]]))
+    for all_within in (True, False):
+        gap, item, found, st = d.near(points, 4, all_within=all_within, want_stats=True)
+        assert not found.any() and (item == -1).all() and np.isinf(gap).all()
+        assert st["bound_tests"] == len(points) and st["sphere_tests"] == 0 and st["hits"] == 0
+    # a flat dynamic scene takes liveness too
+    d.close()
+    flat = rta.DeviceScene(rta.Scene(spheres_of(5, R, 40), rta.normalized(LIGHT, precision), EYE, precision=precision), 0, True)
+    live = (np.arange(40) % 3 != 0).astype(np.uint8)
+    items = spheres_of(6, R, 40)
+    flat.update(items, live=live)
+    check_dynamic(flat, items, live, None, precision, "flat, a third dead")
+    flat.close()
+
+
+def test_entries_buffers_streams_and_threads_agree():
+    import torch
+    s = cases(rta.RT_F32)["default_L3"]
+    d = rta.DeviceScene(s)
+    points, radius = query_families(s, np.random.default_rng(3), 75)
+    n, k = len(points), 5
+    exclude = np.random.default_rng(4).integers(-1, len(s.items), n).astype(np.int32)
+    counters = lambda st: {c: v for c, v in st.items() if c != "device_ms"}
+    for all_within in (False, True):
+        ref = d.near(points, k, radius, all_within=all_within, exclude=exclude)
+        counted = d.near(points, k, radius, all_within=all_within, exclude=exclude, want_stats=True)
+        same_bytes(ref, counted[:3])
+        # the device entry, torch tensors made on a stream of their own
+        stream = torch.cuda.Stream()
+        with torch.cuda.stream(stream):
+            tp, tr, te = torch.from_numpy(points).cuda(), torch.from_numpy(radius).cuda(), torch.from_numpy(exclude).cuda()
+            dev = d.near(tp, k, tr, all_within=all_within, exclude=te, stream=stream)
+            dev_counted = d.near(tp, k, tr, all_within=all_within, exclude=te, stream=stream, want_stats=True)
+        stream.synchronize()
+        assert all(x.device.type == "cuda" for x in dev)
+        same_bytes(ref, dev)
+        same_bytes(ref, dev_counted[:3])
+        assert counters(dev_counted[3]) == counters(counted[3])
+        # a stream that is not the current one, inputs made on the current one, given as a torch stream and as a raw handle
+        side = torch.cuda.Stream()
+        assert side != torch.cuda.current_stream()
+        tp = torch.from_numpy(points).cuda() * 1.0
+        a = d.near(tp, k, torch.from_numpy(radius).cuda(), all_within=all_within, exclude=te, stream=side)
+        b = d.near(tp, k, radius, all_within=all_within, exclude=te, stream=side.cuda_stream)
+        del tp
+        side.synchronize()
+        same_bytes(ref, a)
+        same_bytes(ref, b)
+        # one radius for every query, as a value; none at all
+        same_bytes(d.near(points, k, np.full(n, 0.25, np.float32), all_within=all_within), d.near(points, k, 0.25, all_within=all_within))
+        same_bytes(d.near(points, k, np.full(n, np.inf, np.float32), all_within=all_within), d.near(points, k, all_within=all_within))
+        # pinned host buffers (read and written by the kernel directly) against pageable ones
+        hb = [capi.HostBuffer(x) for x in (points.nbytes, radius.nbytes, exclude.nbytes, 4 * n * k, 4 * n * k, 4 * n)]
+        pp, pr, pe = hb[0].array.view(np.float32).reshape(n, 3), hb[1].array.view(np.float32), hb[2].array.view(np.int32)
+        pp[:], pr[:], pe[:] = points, radius, exclude
+        out = (hb[3].array.view(np.float32).reshape(n, k), hb[4].array.view(np.int32).reshape(n, k), hb[5].array.view(np.uint32))
+        got = d.near(pp, k, pr, all_within=all_within, exclude=pe, out=out)
+        assert got[0] is out[0] and got[2] is out[2]
+        same_bytes(ref, got)
+    # four threads on one scene at once
+    ref = d.near(points, 4, radius)
+    results, errors = [None] * 4, []
+
+    def work(j):
+        try:
+            for _ in range(5):
+                results[j] = d.near(points, 4, radius)
+        except Exception as e:          # noqa: BLE001 (reported below)
+            errors.append(e)
+    threads = [threading.Thread(target=work, args=(j,)) for j in range(4)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    assert not errors, errors
+    for r in results:
+        same_bytes(ref, r)
+    d.close()
+
+
+@PRECISIONS
+def test_the_host_entry_rejects_queries_outside_the_domain(precision):
+    R = REAL[precision]
+    d = rta.Scene.three_spheres(precision).device()
+    good = np.array([[0, 0, -4]] * 4, dtype=R)
+    gap, item, found = d.near(good, 3, all_within=True)
+    assert (found == 3).all() and (item[:, 0] == 0).all() and (gap[:, 0] == R(np.sqrt(R(17.0)) - R(1.0))).all()
+    for c, v in ((1, np.nan), (2, np.inf), (0, -np.inf), (0, 2e15)):
+        p = good.copy()
+        p[2, c] = v
+        with pytest.raises(rta.RtError) as e:
+            d.near(p, 3)
+        assert e.value.status == capi.RT_ERR_INVALID_ARGUMENT
+    with pytest.raises(rta.RtError) as e:
+        d.near(good, 3, np.array([1, np.nan, 1, 1], dtype=R))
+    assert e.value.status == capi.RT_ERR_INVALID_ARGUMENT
+    # every other radius is valid: -inf finds nothing, a negative one only the spheres that contain the point that deep
+    gap, item, found = d.near(np.array([[0, -1, 0]] * 3, dtype=R), 2, np.array([-np.inf, -0.5, -1.5], dtype=R), all_within=True)
+    assert found.tolist() == [0, 1, 0] and item[:, 0].tolist() == [-1, 0, -1] and gap[1, 0] == -1.0
+    d.close()
