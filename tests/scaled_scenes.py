@@ -1,0 +1,133 @@
+"""Scenes away from unit scale and away from the origin, for the ray, proximity and dynamic-scene entries (tests/test_scales_host.py checks
+the inputs on the CPU, tests/test_gpu_scales.py runs them on the GPU).  numpy, the oracle and the host side of the package only.
+
+placements(precision) -> [(name, f)]: f maps float64 (items, bounds, eye) to the placed values, each rounded once to the scene's REAL and
+returned as float64 (what tests/test_gpu_fuzz.py test_scaled_scenes_every_loop_flavour's `sc` does).  bounds may be None.
+  - uniform scales 1e-20, 1e-10, 1e6, 5e13: the frame tests' own.  At 1e-20 every f32 square (rr, vv, b*b ~ 1e-40) is a denormal; 5e13
+    puts coordinates just under the 1e15 validation bound, squares at 1e29.
+  - translations, radii unchanged: +(3000, -5000, 7000) in f32 (one ulp of a coordinate ~ 5e-4, the smallest radius 0.016), +(3e9, -5e9,
+    7e9) in f64 (ulp ~ 1e-6), and in f64 the scene scaled by 1e3 and moved by +(0, 0, 9e14) (ulp 0.125, the smallest radius 16): c - o
+    cancels, which no scaled scene does.
+
+base_scenes() -> [(name, items, bounds, ranges)]: random_nested_scene(31) and the concentric random_nested_scene(32) of the frame tests
+(depth 3, fan 3, two leaf items: 80 / 120 items under 40 bounds, some of which do not enclose their items, so that culling changes
+answers), and the same items with no bounds at all: the flat walk.
+
+case(precision, placement) -> [Case]: every base scene placed, with its oracle, 84 rays (ray_families, n_each = 12: one full wave and a
+partly filled one) and 80 query points (query_families, n_each = 20).  Made once per process; nothing in a Case is written to."""
+import functools
+
+import numpy as np
+
+import oracle
+import rust_tracer_amd as rta
+from tests import util
+from tests.test_gpu_near import query_families
+from tests.test_gpu_query import PREC, REAL, ray_families
+
+SCALES = (1e-20, 1e-10, 1e6, 5e13)
+EYE = (0.07, -0.12, -3.1)                    # the scaled frame tests' eye
+LIGHT = (-1.0, -3.0, 2.0)
+N_EACH_RAYS, N_EACH_POINTS = 12, 20
+AIMED_FAMILIES = (0, 4)                      # ray_families: "outside the root, aimed at items" and "inside the root, aimed at items"
+
+
+def _placement(R, scale=1.0, shift=(0.0, 0.0, 0.0)):
+    shift = np.asarray(shift, dtype=np.float64)
+
+    def f(items, bounds, eye):
+        def spheres(a):
+            if a is None:
+                return None
+            a = np.asarray(a, dtype=np.float64).reshape(-1, 4) * scale
+            a[:, :3] += shift
+            return a.astype(R).astype(np.float64)
+        e = (np.asarray(eye, dtype=np.float64) * scale + shift).astype(R).astype(np.float64)
+        return spheres(items), spheres(bounds), tuple(float(v) for v in e)
+    return f
+
+
+def placements(precision):
+    R = REAL[precision]
+    out = [("x%g" % s, _placement(R, scale=s)) for s in SCALES]
+    if precision == rta.RT_F32:
+        out.append(("+3e3", _placement(R, shift=(3000.0, -5000.0, 7000.0))))
+    else:
+        out.append(("+3e9", _placement(R, shift=(3e9, -5e9, 7e9))))
+        out.append(("x1e3+9e14", _placement(R, scale=1e3, shift=(0.0, 0.0, 9e14))))
+    return out
+
+
+def placement_ids(precision):
+    return [name for name, _ in placements(precision)]
+
+
+def cases_of():
+    """(precision, placement name) for every placement: the parameters of the tests."""
+    return [(p, name) for p in (rta.RT_F32, rta.RT_F64) for name in placement_ids(p)]
+
+
+def case_id(param):
+    return "%s-%s" % ("f32" if param[0] == rta.RT_F32 else "f64", param[1])
+
+
+def base_scenes():
+    out = []
+    for name, seed, concentric in (("nested", 31, False), ("concentric", 32, True)):
+        items, bounds, ranges = util.random_nested_scene(seed, depth=3, fan=3, leaf_items=2, concentric=concentric)
+        out.append((name, items, bounds, ranges))
+    return out + [(name + "_flat", items, None, None) for name, items, _, _ in out]
+
+
+class Case:
+    """One base scene at one placement: .name, .scene (rta.Scene, host side), .oracle, .mode (the oracle's walk: hierarchy, or flat for the
+    scene without bounds), .rays / .tmax, .points / .radius, and the unplaced and placed float64 arrays."""
+
+
+@functools.lru_cache(maxsize=None)
+def case(precision, placement):
+    f = dict(placements(precision))[placement]
+    light = rta.normalized(LIGHT, precision)
+    out = []
+    for k, (name, items0, bounds0, ranges) in enumerate(base_scenes()):
+        c = Case()
+        c.name, c.precision, c.placement = name, precision, placement
+        c.items0, c.ranges = items0, ranges
+        c.items, c.bounds, c.eye = f(items0, bounds0, EYE)
+        if bounds0 is not None:
+            c.scene, c.oracle = util.scene_pair_ranges(c.items, c.bounds, ranges, precision, light=LIGHT, eye=c.eye)
+            c.mode = oracle.MODE_HIERARCHY
+        else:
+            c.scene = rta.Scene(c.items, light, c.eye, precision=precision)
+            # the oracle wants a group: the bounded twin's, which its flat mode never looks at
+            _, twin_bounds, twin_ranges = next(b[1:] for b in base_scenes() if b[0] == name[:-len("_flat")])
+            c.oracle = oracle.Scene.from_ranges(c.items, f(items0, twin_bounds, EYE)[1], twin_ranges, LIGHT, c.eye, PREC[precision])
+            c.mode = oracle.MODE_FLAT
+        c.rays, c.tmax = ray_families(c.scene, np.random.default_rng(100 + k), N_EACH_RAYS)
+        c.points, c.radius = query_families(c.scene, np.random.default_rng(200 + k), N_EACH_POINTS)
+        out.append(c)
+    return tuple(out)
+
+
+def oracle_nearest(c, rays=None, tmax=None):
+    """(distance[n], normal[n, 3]) of the oracle's own walk, ray by ray, in float64."""
+    rays = c.rays if rays is None else rays
+    tmax = c.tmax if tmax is None else tmax
+    out = [c.oracle.intersect(r.astype(np.float64), float(t), c.mode) for r, t in zip(rays, tmax)]
+    return np.array([x[0] for x in out]), np.array([x[1] for x in out])
+
+
+def shuffled(items, R, seed=7):
+    """The placed items in a seeded random caller order, as a rebuild takes them."""
+    it = np.ascontiguousarray(np.asarray(items).astype(R))
+    return np.ascontiguousarray(it[np.random.default_rng(seed).permutation(len(it))])
+
+
+def sort_inputs(precision, n=300001, duplicates=1000, seed=41):
+    """n spheres with centres uniform in a box, `duplicates` of them exact copies of other centres (other radii), in a seeded random order:
+    more than the 262,144 threads of one pass of the sphere sort's strided kernels."""
+    R = REAL[precision]
+    rng = np.random.default_rng(seed)
+    s = np.concatenate([rng.uniform([-3.0, -2.0, 0.0], [3.0, 2.0, 6.0], (n, 3)), rng.uniform(0.01, 0.03, (n, 1))], axis=1)
+    s[n - duplicates:, :3] = s[rng.choice(n - duplicates, duplicates, replace=False), :3]
+    return np.ascontiguousarray(s[rng.permutation(n)].astype(R))

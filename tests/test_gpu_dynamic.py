@@ -43,8 +43,10 @@ def views(precision):
             ("identity", np.concatenate([np.asarray(EYE), [1, 0, 0, 0, 1, 0, 0, 0, 1]]).astype(REAL[precision]))]
 
 
-def answers(d, rays, tmax, precision):
-    """[(entry, bytes of every result, counters)] of every general-ray entry on device scene d."""
+def answers(d, rays, tmax, precision, cameras=None):
+    """[(entry, bytes of every result, counters)] of every general-ray entry on device scene d.  cameras: (name, camera) for the frame
+    entries (None: views(precision), which look at a scene of unit size around the origin; tests/test_gpu_scales.py, whose scenes are
+    elsewhere, asks for none)."""
     out = []
 
     def put(name, res):
@@ -59,7 +61,7 @@ def answers(d, rays, tmax, precision):
         put("multi all=%d ordered" % all_hits, d.intersect_multi(rays, 4, tmax, all_hits=all_hits, want_stats=True, order=True))
     put("trace", d.trace(rays, want_stats=True))
     put("trace ordered", d.trace(rays, want_stats=True, order=True))
-    for name, cam in views(precision):
+    for name, cam in (views(precision) if cameras is None else cameras):
         for spp in (1, 2):
             put("camera %s spp %d" % (name, spp), d.render_camera(OPTS + (spp,), cam, REGIONS, want_stats=True))
         buf, prev = None, 0
@@ -78,10 +80,10 @@ def assert_same(got, ref, what):
         assert gc == rc, (what, name, gc, rc)
 
 
-def fresh_answers(items, bounds, ranges, rays, tmax, precision):
+def fresh_answers(items, bounds, ranges, rays, tmax, precision, cameras=None):
     d = rta.DeviceScene(scene_of(items, bounds, ranges, precision))
     try:
-        return answers(d, rays, tmax, precision)
+        return answers(d, rays, tmax, precision, cameras)
     finally:
         d.close()
 

@@ -60,9 +60,10 @@ def dummies(n, R):
     return np.stack([np.zeros(n), 1000.0 + np.arange(n), np.zeros(n), np.full(n, 1e-3)], axis=1).astype(R)
 
 
-def stand_in_arrays(items, live, ranges, reported_bounds, R):
-    """(items, bounds) of the stand-in scene."""
-    dm = dummies(len(items), R)
+def stand_in_arrays(items, live, ranges, reported_bounds, R, dummy=None):
+    """(items, bounds) of the stand-in scene.  dummy: one sphere {cx, cy, cz, r} that stands in for every dead slot (None: the column of
+    dummies(), for a scene of unit size around the origin)."""
+    dm = dummies(len(items), R) if dummy is None else np.tile(np.asarray(dummy, dtype=R).reshape(1, 4), (len(items), 1))
     it = np.where((np.asarray(live) != 0)[:, None], items, dm).astype(R)
     it = np.ascontiguousarray(it)
     bd = None

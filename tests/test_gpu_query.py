@@ -59,12 +59,13 @@ def ray_families(scene, rng, n_each=40):
     rays = rays.astype(R)
     n = len(rays)
     choice = rng.integers(0, 4, n)
-    tmax = np.where(choice == 0, np.inf, np.where(choice == 1, rng.uniform(0.2, 2.5 * root_r, n), np.where(choice == 2, 0.0, -1.0))).astype(R)
+    nearest = 0.2 if 2.5 * root_r > 0.2 else 0.08 * root_r         # (a scene far below unit size, tests/scaled_scenes.py: sized by its root as well)
+    tmax = np.where(choice == 0, np.inf, np.where(choice == 1, rng.uniform(nearest, 2.5 * root_r, n), np.where(choice == 2, 0.0, -1.0))).astype(R)
     return rays, tmax
 
 
-def oracle_nearest(o, rays, tmax):
-    out = [o.intersect(r.astype(np.float64), float(t)) for r, t in zip(rays, tmax)]
+def oracle_nearest(o, rays, tmax, mode=oracle.MODE_HIERARCHY):
+    out = [o.intersect(r.astype(np.float64), float(t), mode) for r, t in zip(rays, tmax)]
     return np.array([x[0] for x in out]), np.array([x[1] for x in out])
 
 
@@ -93,10 +94,10 @@ def bits(a, R):
     return a.view(np.uint32 if R == np.float32 else np.uint64)
 
 
-def check_nearest(s, o, rays, tmax):
+def check_nearest(s, o, rays, tmax, mode=oracle.MODE_HIERARCHY):
     R = REAL[s.precision]
     dist, nrm, item = s.device().intersect(rays, tmax)
-    ref_d, ref_n = oracle_nearest(o, rays, tmax)
+    ref_d, ref_n = oracle_nearest(o, rays, tmax, mode)
     np.testing.assert_array_equal(bits(dist, R), bits(ref_d, R))
     np.testing.assert_array_equal(bits(nrm, R), bits(ref_n, R))
     hit = item >= 0
