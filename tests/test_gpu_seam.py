@@ -300,13 +300,22 @@ def test_rtrace_scene_file_with_an_automatically_built_hierarchy(tmp_path):
     assert open(out, "rb").read() == open(ref, "rb").read()
 
 
-@pytest.mark.parametrize("scale", [1.0 - 1.9e-3, 1.0 + 1.9e-3])
-def test_filter_bounds_hold_at_the_edges_of_the_accepted_light_length(scale):
+_EDGE_LIGHTS = {"": (-1.0, -3.0, 2.0), "-+y": (0.0, 1.0, 0.0), "-xy_tie": (1.0, -1.0, 0.25)}
+
+
+@pytest.mark.parametrize("scale,direction", [(s, d) for d in _EDGE_LIGHTS.values() for s in (1.0 - 1.9e-3, 1.0 + 1.9e-3)],
+                         ids=["%r%s" % (s, n) for n in _EDGE_LIGHTS for s in (1.0 - 1.9e-3, 1.0 + 1.9e-3)])
+def test_filter_bounds_hold_at_the_edges_of_the_accepted_light_length(scale, direction):
     # rt_scene_create accepts a light_unit whose squared length is within 2e-3 of 1; the filtered loops' shadow bounds carry that
     # deviation (eta).  At both edges: the counting launch evaluates the bounds for every test it makes (violations are asserted 0
-    # by the autouse fixture) and the filtered assembly loops render the same bytes as the reference loops.
+    # by the autouse fixture) and the filtered assembly loops render the same bytes as the reference loops.  Under the home light, an
+    # axis light that points up (two zero components) and a light with two equal components (tests/posed_scenes.py LIGHTS).
+    # The oracle cannot be asked: its scene normalises whatever light it is given (render.rs:154-159; tests/test_poses_host.py
+    # test_the_oracle_normalises_the_light_it_is_given), so it never holds a light of another length -- the reference here is the counted
+    # launch, the reference's arithmetic in the C++ loops, which the other frame tests hold to the oracle.
     items, bounds, ranges = util.random_nested_scene(35, depth=3, fan=3, leaf_items=2, concentric=True)
-    light = rta.normalized((-1.0, -3.0, 2.0), rta.RT_F32).astype(np.float64) * np.sqrt(scale)
+    light = rta.normalized(direction, rta.RT_F32).astype(np.float64) * np.sqrt(scale)
+    assert 1.8e-3 < abs(float(np.sum(light.astype(np.float32).astype(np.float64) ** 2)) - 1.0) < 2e-3
     s = rta.Scene(items, light, (0.05, -0.1, -3.2), bounds, ranges, rta.RT_F32)
     regs = bucket_list(192, 160, 2)
     counted, st = s.device().render_tiles((192, 160, 2), regs, SKIP, want_stats=True)
