@@ -582,6 +582,56 @@ rt_status rt_near_spheres_device(rt_scene *scene, rt_near mode, uint32_t k, cons
                                  const int32_t *exclude, const uint32_t *order, void *gap_out, int32_t *item_out, uint32_t *found_out,
                                  rt_stats *stats, void *hip_stream);
 
+/* ---- sphere casts (additive to ABI 5): the first contact of a moving sphere with the scene ----
+ * The third question a caller that moves spheres asks, after "what does this ray hit" and "what is near this point": how far can this
+ * sphere move along a direction before it touches something?  Cast g is a ray rays[6g .. 6g+6] = pos.xyz, dir.xyz (REAL; dir a unit
+ * vector, as for rt_intersect_rays), a radius q = radius[g] (REAL; radius == NULL: 0) and a cutoff tmax[g] (REAL; tmax == NULL: +inf; a
+ * tmax <= 0 finds nothing).  A sphere of radius q moving along a ray touches a sphere {c, r} exactly where the ray hits {c, r + q}.  The
+ * CAST DISTANCE of a record {c, rr} of the scene's stream -- rr is the radius squared, rounded once -- in REAL, every operation rounded
+ * once, no FMA, both roots the IEEE ones:
+ *   rad  = sqrt(rr)
+ *   RR   = (rr + (q + q) * rad) + q * q               (r + q)^2 expanded; q = 0 gives RR == rr bit for bit
+ *   v    = c - pos ;  b = dot(v, dir) ;  disc = (b*b - dot(v, v)) + RR        dot(x, y) = (x.x*y.x + x.y*y.y) + x.z*y.z
+ *   t    = +inf                  if !(rr > 0)  or  disc < 0  or  b + sqrt(disc) < 0
+ *        = b - sqrt(disc)        if that is > 0
+ *        = 0                     otherwise: the moving sphere touches or overlaps the record at its start
+ * Two points differ from the ray query on purpose.  The start case is 0, not the exit distance b + sqrt(disc): the ray entries let a
+ * bound that contains the origin be culled by its exit distance, as the reference does; with 0 the inflated bound's distance is a lower
+ * bound of its inflated items' distances in exact arithmetic -- it is missed or behind only if they are, it is entered no later, and it
+ * is 0 whenever the start is inside -- and a cast that starts in contact reports distance 0 and that item, which is what a collision
+ * step needs.  And the guard rr > 0 is the proximity queries': a dead item and a dead group (rr = -inf, "live and dead slots" above) are
+ * at +inf, so a dead item never wins and a dead group culls its subtree at its one test.  rust_tracer_amd.sweep_distances restates the
+ * distance in numpy, bit for bit.
+ *   The walk is rt_intersect_rays's over the same stream; `best` starts at tmax.  A bound culls when t >= best.
+ *   RT_SWEEP_NEAREST  an item with !(t >= best) becomes the result: the first item in DFS order wins a tie, several items at 0 included.
+ *   RT_SWEEP_ANY      the first item with !(t >= tmax) is the result, and the cast ends there.
+ * The result is the walk's, as for every query here.  With q = 0, for rays on which every tested record has rr > 0 and b - sqrt(disc) >
+ * 0 wherever it is hit, a cast is rt_intersect_rays test for test: the same bytes, the same counters.
+ *   exclude (int32[n] or NULL): the item slot cast g ignores -- a sphere that lives in the scene and is cast from its own pose.  That
+ * item is tested and counted as a test, but can never be the result; -1 or any slot outside the scene excludes nothing.
+ *   order (uint32[n] or NULL): thread j carries cast order[j], with the rules of the *_ordered entries above -- host entry: a permutation
+ * of 0 .. n-1; device entry: alignment only, and an entry >= n carries no cast.  NULL: the caller's order.  The bytes and counters are
+ * the same in every order; only the time differs.
+ *   distance_out (REAL[n]): the result's t, or tmax[g] when there is none.  item_out (int32[n] or NULL): its DFS slot, or -1.  normal_out
+ * (REAL[3n] or NULL): normalized(pos + (dir * t - c)) with the result's own centre -- from the touched sphere towards the moving sphere's
+ * centre at contact --, {0, 0, 0} when there is none.  stats (may be NULL): primary = n, hits = casts with a result, sphere_tests /
+ * bound_tests / tests_executed, every other counter 0; asking for it runs the counting flavour (same bytes). */
+typedef enum rt_sweep { RT_SWEEP_NEAREST = 0, RT_SWEEP_ANY = 1 } rt_sweep;
+/* Host memory.  RT_ERR_INVALID_ARGUMENT before the device is touched for everything rt_intersect_rays rejects (a NULL scene, rays or
+ * distance_out, n == 0, a misaligned REAL buffer or item_out, a ray with a non-finite component, |pos| > 1e15 or a direction that is
+ * no unit vector, a NaN tmax, a buffer in device memory), an unknown mode, a misaligned exclude or order, an order that is no
+ * permutation, and a radius that is NaN, negative, infinite or above 1e15 (a scene's own bound on a radius).  Pinned memory is used in
+ * place, pageable memory goes through the call's device workspace.  On a dynamic scene the call is a READ in the sense of ORDER above. */
+rt_status rt_sweep_spheres(rt_scene *scene, rt_sweep mode, const void *rays, const void *radius, const void *tmax, uint32_t n,
+                           const int32_t *exclude, const uint32_t *order, void *distance_out, void *normal_out, int32_t *item_out,
+                           rt_stats *stats);
+/* The same over DEVICE memory, enqueued on `hip_stream` as rt_intersect_rays_device is: only pointers, alignment, n and mode are checked.
+ * A cast outside the domain gives unspecified values, never a fault -- the walk ends for any input bits.  stats != NULL: filled after an
+ * internal synchronisation of hip_stream. */
+rt_status rt_sweep_spheres_device(rt_scene *scene, rt_sweep mode, const void *rays, const void *radius, const void *tmax, uint32_t n,
+                                  const int32_t *exclude, const uint32_t *order, void *distance_out, void *normal_out, int32_t *item_out,
+                                  rt_stats *stats, void *hip_stream);
+
 /* Bytes rt_render_tiles writes for this tile list (4 * total area), or 0 on an invalid list. */
 uint64_t rt_tiles_rgba_bytes(const rt_region *tiles, uint32_t n_tiles);
 

@@ -19,6 +19,7 @@
 #include "rt_undersample.hpp"
 #include "rt_multihit.hpp"
 #include "rt_near.hpp"
+#include "rt_sweep.hpp"
 #include "rt_order.hpp"
 #include "rt_dynamic.hpp"
 #include "rt_rebuild.hpp"

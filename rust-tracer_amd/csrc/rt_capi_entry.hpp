@@ -1289,6 +1289,108 @@ rt_status rt_near_spheres(rt_scene *s, rt_near mode, uint32_t k, const void *poi
     return RT_OK;
 }
 
+// ---- sphere casts: the first contact of a moving sphere with the scene (rt_sweep.hpp) ----
+
+rt_status rt_sweep_spheres_device(rt_scene *s, rt_sweep mode, const void *rays, const void *radius, const void *tmax, uint32_t n, const int32_t *exclude,
+                                  const uint32_t *order, void *distance_out, void *normal_out, int32_t *item_out, rt_stats *stats, void *hip_stream)
+{
+    const char *const what = "rt_sweep_spheres_device";
+    if (!sweep_args_ok(s, mode, rays, radius, tmax, n, exclude, order, distance_out, normal_out, item_out, what)) return RT_ERR_INVALID_ARGUMENT;
+    const ReadLock rl(s);
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    const void *nodes = nullptr;
+    uint32_t n_nodes = 0;
+    rt_status st = query_stream(s, stream, &nodes, &n_nodes);
+    if (st != RT_OK) return st;
+    if (!stats) return enqueue_sweep(s, nodes, n_nodes, mode, rays, radius, tmax, n, exclude, order, distance_out, normal_out, item_out, nullptr, stream);
+    Context *c = nullptr;
+    if ((st = acquire(s, &c)) != RT_OK) return st;
+    Lease lease{ s, c };
+    HIP_TRY(hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, stream));
+    HIP_TRY(hipEventRecord(c->ev0, stream));
+    st = enqueue_sweep(s, nodes, n_nodes, mode, rays, radius, tmax, n, exclude, order, distance_out, normal_out, item_out, c->d_counters, stream);
+    (void)hipEventRecord(c->ev1, stream);
+    if (st != RT_OK) { (void)hipGetLastError(); lease.inflight = true; return st; }      // (the context goes back behind what is enqueued)
+    return read_query_stats(c, stream, stats);
+}
+
+rt_status rt_sweep_spheres(rt_scene *s, rt_sweep mode, const void *rays, const void *radius, const void *tmax, uint32_t n, const int32_t *exclude,
+                           const uint32_t *order, void *distance_out, void *normal_out, int32_t *item_out, rt_stats *stats)
+{
+    const char *const what = "rt_sweep_spheres";
+    if (!sweep_args_ok(s, mode, rays, radius, tmax, n, exclude, order, distance_out, normal_out, item_out, what)) return RT_ERR_INVALID_ARGUMENT;
+    const bool f32 = s->precision == RT_F32;
+    if (!(f32 ? sweep_casts_valid(static_cast<const float *>(rays), static_cast<const float *>(radius), static_cast<const float *>(tmax), n, what)
+              : sweep_casts_valid(static_cast<const double *>(rays), static_cast<const double *>(radius), static_cast<const double *>(tmax), n, what)))
+        return RT_ERR_INVALID_ARGUMENT;
+    if (order && !order_is_permutation(order, n, what)) return RT_ERR_INVALID_ARGUMENT;
+    const ReadLock rl(s);
+    HIP_TRY(hipSetDevice(s->device));
+    rt_status st = RT_OK;
+    // pinned buffers are read and written by the kernel in place, pageable ones go through the call's workspace (as rt_intersect_rays)
+    const size_t esz = f32 ? sizeof(float) : sizeof(double);
+    struct Buf { void *host; size_t bytes; bool out; uint8_t *dev; size_t off; bool staged; };
+    Buf b[8] = { { const_cast<void *>(rays), 6 * esz * n, false, nullptr, 0, false }, { const_cast<void *>(radius), esz * n, false, nullptr, 0, false },
+                 { const_cast<void *>(tmax), esz * n, false, nullptr, 0, false },
+                 { const_cast<int32_t *>(exclude), sizeof(int32_t) * n, false, nullptr, 0, false },
+                 { const_cast<uint32_t *>(order), sizeof(uint32_t) * n, false, nullptr, 0, false },
+                 { distance_out, esz * n, true, nullptr, 0, false }, { normal_out, 3 * esz * n, true, nullptr, 0, false },
+                 { item_out, sizeof(int32_t) * n, true, nullptr, 0, false } };
+    size_t need = 0;
+    for (Buf &x : b) {
+        if (!x.host) continue;
+        const HostDest d = classify_host_pointer(x.host);
+        if (d.bad) {
+            snprintf(g_err, sizeof g_err, "%s: a buffer is device memory; use %s_device", what, what);
+            return RT_ERR_INVALID_ARGUMENT;
+        }
+        if (d.pinned && d.dev_alias && d.room >= x.bytes) { x.dev = d.dev_alias; continue; }
+        x.staged = true;
+        x.off = need;
+        need += (x.bytes + 255) & ~(size_t)255;
+    }
+    Context *c = nullptr;
+    if ((st = acquire(s, &c)) != RT_OK) return st;
+    Lease lease{ s, c };
+    const void *nodes = nullptr;
+    uint32_t n_nodes = 0;
+    if ((st = query_stream(s, c->stream, &nodes, &n_nodes)) != RT_OK) return st;
+    if (need > c->query_cap) {
+        if (c->d_query) HIP_TRY(hipFree(c->d_query));
+        c->d_query = nullptr; c->query_cap = 0;
+        HIP_TRY(hipMalloc(&c->d_query, need));
+        c->query_cap = need;
+    }
+    for (Buf &x : b)
+        if (x.staged) x.dev = static_cast<uint8_t *>(c->d_query) + x.off;
+    // from the first copy on, work of this call may be queued: an error return first waits for it
+#define HIP_DRAIN(expr)                                                                                                   \
+    do {                                                                                                                  \
+        hipError_t e__ = (expr);                                                                                          \
+        if (e__ != hipSuccess) { (void)hipStreamSynchronize(c->stream); return hip_fail(e__, #expr, __LINE__); }          \
+    } while (0)
+    for (const Buf &x : b)
+        if (x.staged && !x.out)
+            HIP_DRAIN(hipMemcpyAsync(x.dev, x.host, x.bytes, hipMemcpyHostToDevice, c->stream));
+    if (stats) {
+        HIP_DRAIN(hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, c->stream));
+        HIP_DRAIN(hipEventRecord(c->ev0, c->stream));
+    }
+    st = enqueue_sweep(s, nodes, n_nodes, mode, b[0].dev, b[1].dev, b[2].dev, n, reinterpret_cast<const int32_t *>(b[3].dev),
+                       reinterpret_cast<const uint32_t *>(b[4].dev), b[5].dev, b[6].dev, reinterpret_cast<int32_t *>(b[7].dev),
+                       stats ? c->d_counters : nullptr, c->stream);
+    if (st != RT_OK) { (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return st; }
+    if (stats) HIP_DRAIN(hipEventRecord(c->ev1, c->stream));
+    for (const Buf &x : b)
+        if (x.staged && x.out)
+            HIP_DRAIN(hipMemcpyAsync(x.host, x.dev, x.bytes, hipMemcpyDeviceToHost, c->stream));
+    if (stats) return read_query_stats(c, c->stream, stats);          // synchronises the stream
+    HIP_DRAIN(hipStreamSynchronize(c->stream));
+#undef HIP_DRAIN
+    return RT_OK;
+}
+
 // ---- traced rays and camera frames: Renderer::raytrace for any ray, render_region for any pinhole camera (rt_trace.hpp) ----
 
 static rt_status trace_rays_device(rt_scene *s, const void *rays, uint32_t n, void *color_out, void *alpha_out, bool ordered, const uint32_t *order,

@@ -862,6 +862,86 @@ rt_status enqueue_near(const rt_scene *s, const void *nodes, uint32_t n_nodes, r
                                   : enqueue_near<double>(nodes, n_nodes, mode, k, points, radius, n, exclude, order, gap, item, found, counters, stream);
 }
 
+// ---- sphere casts (rt_sweep_spheres*, rt_sweep.hpp) ----
+
+// What both cast entries check (device pointers are not dereferenced here).
+bool sweep_args_ok(const rt_scene *s, rt_sweep mode, const void *rays, const void *radius, const void *tmax, uint32_t n, const int32_t *exclude,
+                   const uint32_t *order, const void *dist, const void *normal, const int32_t *item, const char *what)
+{
+    if (!s || !rays || !dist || n == 0) { snprintf(g_err, sizeof g_err, "%s: NULL scene, rays or distance_out, or n == 0", what); return false; }
+    if (mode != RT_SWEEP_NEAREST && mode != RT_SWEEP_ANY) { snprintf(g_err, sizeof g_err, "%s: unknown mode %d (nearest is 0, any is 1)", what, (int)mode); return false; }
+    const struct { const void *p; const char *name; } words[] = { { item, "item_out" }, { exclude, "exclude" }, { order, "order" } };
+    for (const auto &w : words)
+        if ((reinterpret_cast<uintptr_t>(w.p) & 3u) != 0) { snprintf(g_err, sizeof g_err, "%s: %s must be 4-byte aligned", what, w.name); return false; }
+    const uintptr_t esz = s->precision == RT_F32 ? sizeof(float) : sizeof(double);
+    const struct { const void *p; const char *name; } reals[] = { { rays, "rays" }, { radius, "radius" }, { tmax, "tmax" }, { dist, "distance_out" }, { normal, "normal_out" } };
+    for (const auto &w : reals)
+        if ((reinterpret_cast<uintptr_t>(w.p) % esz) != 0) { snprintf(g_err, sizeof g_err, "%s: %s must be %u-byte aligned", what, w.name, (unsigned)esz); return false; }
+    return true;
+}
+
+// The host entry's domain: the rays and tmax of rt_intersect_rays (finite, |pos| <= 1e15, a unit direction, a tmax that is not NaN) and a
+// radius in 0 .. 1e15 -- the scene's own bound on a radius, so that no intermediate of the inflated test overflows.
+template <typename T>
+bool sweep_casts_valid(const T *rays, const T *radius, const T *tmax, uint32_t n, const char *what)
+{
+    for (uint32_t i = 0; i < n; ++i) {
+        const T *r = rays + 6 * (size_t)i;
+        for (int k = 0; k < 6; ++k) {
+            if (!std::isfinite(r[k]) || (k < 3 && std::fabs((double)r[k]) > 1e15)) {
+                snprintf(g_err, sizeof g_err, "%s: rays: ray %u has a non-finite component or |pos| > 1e15", what, i);
+                return false;
+            }
+        }
+        const double d2 = (double)r[3] * r[3] + (double)r[4] * r[4] + (double)r[5] * r[5];
+        if (std::fabs(d2 - 1.0) > 2e-3) {
+            snprintf(g_err, sizeof g_err, "%s: rays: ray %u's direction is not a unit vector (its squared length is %.6g)", what, i, d2);
+            return false;
+        }
+        if (radius && !(radius[i] >= T(0.0) && (double)radius[i] <= 1e15)) {         // (NaN fails the first comparison)
+            snprintf(g_err, sizeof g_err, "%s: radius[%u] = %g is not in 0 .. 1e15", what, i, (double)radius[i]);
+            return false;
+        }
+        if (tmax && std::isnan(tmax[i])) { snprintf(g_err, sizeof g_err, "%s: tmax[%u] is NaN", what, i); return false; }
+    }
+    return true;
+}
+
+template <typename T, bool COUNT, bool ANY>
+void launch_sweep(dim3 grid, dim3 block, hipStream_t stream, const rt::SweepArgs<T> &a)
+{
+    if (a.order) hipLaunchKernelGGL((rt::k_sweep_spheres<T, COUNT, ANY, true>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((rt::k_sweep_spheres<T, COUNT, ANY, false>), grid, block, 0, stream, a);
+}
+
+// One cast launch on `stream`: counters != NULL runs the counting flavour (same bytes).
+template <typename T>
+rt_status enqueue_sweep(const rt_scene *s, const void *nodes, uint32_t n_nodes, rt_sweep mode, const void *rays, const void *radius, const void *tmax, uint32_t n,
+                        const int32_t *exclude, const uint32_t *order, void *dist, void *normal, int32_t *item, rt::Counters *counters, hipStream_t stream)
+{
+    const rt::SweepArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), static_cast<const rt::Item<T> *>(s->d_items), static_cast<const T *>(rays),
+                              static_cast<const T *>(radius), static_cast<const T *>(tmax), exclude, order, static_cast<T *>(dist), static_cast<T *>(normal),
+                              item, counters, n_nodes, n };
+    const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
+    const bool any = mode == RT_SWEEP_ANY;
+    if (counters) {
+        if (any) launch_sweep<T, true, true>(grid, block, stream, a);
+        else launch_sweep<T, true, false>(grid, block, stream, a);
+    } else {
+        if (any) launch_sweep<T, false, true>(grid, block, stream, a);
+        else launch_sweep<T, false, false>(grid, block, stream, a);
+    }
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+rt_status enqueue_sweep(const rt_scene *s, const void *nodes, uint32_t n_nodes, rt_sweep mode, const void *rays, const void *radius, const void *tmax, uint32_t n,
+                        const int32_t *exclude, const uint32_t *order, void *dist, void *normal, int32_t *item, rt::Counters *counters, hipStream_t stream)
+{
+    return s->precision == RT_F32 ? enqueue_sweep<float>(s, nodes, n_nodes, mode, rays, radius, tmax, n, exclude, order, dist, normal, item, counters, stream)
+                                  : enqueue_sweep<double>(s, nodes, n_nodes, mode, rays, radius, tmax, n, exclude, order, dist, normal, item, counters, stream);
+}
+
 // ---- traced rays and camera frames (rt_trace_rays*, rt_render_camera*, rt_trace.hpp) ----
 
 // The camera domain both rt_render_camera entries check (in double, before the device is touched): 12 finite values, |eye coordinate|

@@ -99,6 +99,42 @@ def sphere_gaps(points, spheres):
     return np.where((rr > 0)[None, :], gap, R(np.inf)).astype(R, copy=False)
 
 
+def sweep_distances(rays, radius, spheres):
+    """The cast distance of every cast of `rays` (n x 6: pos.xyz, dir.xyz, dir a unit vector) with `radius` (REAL[n], one value, or None: 0)
+    against every sphere of `spheres` (m x 4: cx, cy, cz, r) -> REAL[n, m], the metric of rt_sweep_spheres restated in numpy bit for bit
+    (include/rtrace_hip.h states it), in the arrays' dtype (float32 or float64, the same for all), every operation rounded once:
+    rr = r * r;  rad = sqrt(rr);  RR = (rr + (q + q) * rad) + q * q;  v = c - pos;  b = dot(v, dir);  disc = (b*b - dot(v, v)) + RR;
+    t = +inf where !(rr > 0), disc < 0 or b + sqrt(disc) < 0, else b - sqrt(disc) where that is > 0, else 0 (the moving sphere touches
+    or overlaps the sphere at its start).  A record without a positive rr -- radius 0: a dead slot, a dead group's bound -- is at +inf
+    from every cast, as in sphere_gaps.  DeviceScene.sweep reports, per cast, the smallest of a row below tmax as its walk finds it."""
+    ry, s = np.asarray(rays), np.asarray(spheres)
+    if ry.dtype not in (np.float32, np.float64) or s.dtype != ry.dtype or ry.ndim != 2 or ry.shape[1] != 6 or s.ndim != 2 or s.shape[1] != 4:
+        raise ValueError("rays must be (n, 6) and spheres (m, 4), both float32 or both float64")
+    R = ry.dtype.type
+    n = ry.shape[0]
+    q = np.zeros(n, R) if radius is None else np.asarray(radius)
+    if q.ndim == 0 and q.dtype.kind in "fiu":
+        q = q.astype(R)
+    if q.dtype != R or q.size not in (1, n):
+        raise ValueError("radius must be None, one value or an (n,) array of %s" % np.dtype(R).name)
+    q = np.broadcast_to(q.reshape(-1), (n,))
+    rr = s[:, 3] * s[:, 3]
+    solid = rr > 0
+    with np.errstate(invalid="ignore", over="ignore"):
+        rad = np.sqrt(np.where(solid, rr, R(1.0)))
+        RR = (rr[None, :] + (q + q)[:, None] * rad[None, :]) + (q * q)[:, None]
+        v = s[None, :, :3] - ry[:, None, :3]
+        d = ry[:, None, 3:]
+        b = (v[..., 0] * d[..., 0] + v[..., 1] * d[..., 1]) + v[..., 2] * d[..., 2]
+        vv = (v[..., 0] * v[..., 0] + v[..., 1] * v[..., 1]) + v[..., 2] * v[..., 2]
+        disc = (b * b - vv) + RR
+        root = np.sqrt(np.where(disc < 0, R(0.0), disc))
+        hit = solid[None, :] & ~(disc < 0) & ~(b + root < 0)
+        t1 = b - root
+        t = np.where(hit, np.where(t1 > 0, t1, R(0.0)), R(np.inf))
+    return t.astype(R, copy=False)
+
+
 def balanced_ranges(n, leaf_size=4):
     """rt_balanced_ranges: a topology from the item count alone -> int32[g, 2], the groups (first item, item count) of the recursive halving
     of (0, n) down to `leaf_size`, in DFS pre-order (a group's first half holds (count + 1) // 2 items; leaves are groups too).  Valid as
@@ -930,9 +966,109 @@ class DeviceScene:
             return tuple(res) + (st.as_dict(),)
         return tuple(res)
 
+    def sweep(self, rays, radius=None, tmax=None, any_hit=False, exclude=None, order=None, want_stats=False, stream=None, out=None):
+        """rt_sweep_spheres / rt_sweep_spheres_device: the first contact of a moving sphere with the scene, for every cast of `rays` (n x 6:
+        pos.xyz, dir.xyz with dir a unit vector, the scene's REAL dtype) -> (distance[n], normal[n, 3], item[n] (DFS slot or -1)[, stats
+        dict]).  radius: the moving sphere's radius per cast (an array of the scene's REAL) or one value (rounded to REAL; None: 0, a ray);
+        tmax: the cutoff per cast, likewise (None: +inf).  sweep_distances is the metric: the distance the centre travels until the
+        moving sphere touches a sphere of the scene, 0 when it touches or overlaps one at its start.  A cast without a contact below tmax
+        reads tmax, a zero normal and -1.  any_hit=False (RT_SWEEP_NEAREST): the first contact, equal distances to the first item in DFS
+        order.  any_hit=True (RT_SWEEP_ANY): some contact below tmax, found sooner.  exclude (int32[n]): the item slot each cast ignores --
+        np.arange(n) when the scene's own items are cast from their own poses; -1 or a slot outside the scene excludes nothing.  A dead
+        slot of a dynamic scene is never returned.  numpy arrays go through the host entry, a torch tensor on this scene's device through
+        the device entry on `stream`, with the stream discipline of intersect(); out: optional (distance, normal, item) arrays / tensors
+        to fill.  order (uint32[n]): lane j carries cast order[j]; the results and counters are the same bytes whatever the order, only
+        the time differs.  The host entry wants a permutation; through the device entry an index >= n carries no cast and leaves that
+        thread's outputs alone."""
+        mode = capi.RT_SWEEP_ANY if any_hit else capi.RT_SWEEP_NEAREST
+        R = _real(self.scene.precision)
+        st = capi.Stats()
+        stp = C.byref(st) if want_stats else None
+        torch = sys.modules.get("torch")
+        if torch is not None and isinstance(rays, torch.Tensor):
+            tdt = torch.float32 if R == np.float32 else torch.float64
+            dev = torch.device("cuda", self.device)
+            if rays.dtype != tdt or rays.dim() != 2 or rays.shape[1] != 6 or rays.shape[0] == 0:
+                raise ValueError("rays must be a non-empty (n, 6) %s tensor" % tdt)
+            if rays.device != dev:
+                raise ValueError("rays must be on %s, not %s" % (dev, rays.device))
+            n = rays.shape[0]
+            reals = {"radius": radius, "tmax": tmax}
+            for name, x in reals.items():
+                if isinstance(x, torch.Tensor):
+                    if x.dim() == 0 and x.dtype.is_floating_point:
+                        x = x.to(tdt)                                    # one value: rounded to the scene's REAL
+                    if x.dtype != tdt or x.numel() not in (1, n):
+                        raise ValueError("%s must be a %s value or (n,) tensor" % (name, tdt))
+                elif x is not None:
+                    x = self._radius_array(x, R, n) if name == "radius" else _tmax_array(x, R, n)
+                reals[name] = x
+            if exclude is not None and (not isinstance(exclude, torch.Tensor) or exclude.dtype != torch.int32 or exclude.shape != (n,) or exclude.device != dev):
+                raise ValueError("exclude must be None or an (n,) int32 tensor on %s" % dev)
+            if order is not None:
+                try:
+                    order = self._order_torch(torch, order, n, dev)
+                except ValueError:
+                    raise ValueError("order must be None or an (n,) uint32 / int32 tensor on %s" % dev) from None
+            specs = (((n,), tdt), ((n, 3), tdt), ((n,), torch.int32))
+            if out is not None:
+                out = tuple(out)
+                if len(out) != 3 or any(not isinstance(a, torch.Tensor) or a.dtype != dt or tuple(a.shape) != shape or a.device != dev or not a.is_contiguous()
+                                        for a, (shape, dt) in zip(out, specs)):
+                    raise ValueError("out: contiguous tensors on %s of %s" % (dev, ", ".join("%s %s" % (dt, shape) for shape, dt in specs)))
+            qs, cur = self._device_stream(torch, stream)
+            if qs != cur:
+                qs.wait_stream(cur)
+            with torch.cuda.stream(qs):
+                r = rays.contiguous()
+                staged = {}
+                for name, x in reals.items():
+                    if isinstance(x, torch.Tensor):
+                        staged[name] = x.to(dev).reshape(-1).expand(n).contiguous()
+                    else:
+                        staged[name] = None if x is None else torch.from_numpy(x.copy()).to(dev)     # (a broadcast view is read-only)
+                ex = None if exclude is None else exclude.contiguous()
+                res = out if out is not None else tuple(torch.empty(shape, dtype=dt, device=dev) for shape, dt in specs)
+                ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
+                rc = capi.lib.rt_sweep_spheres_device(self._h, mode, ptr(r), ptr(staged["radius"]), ptr(staged["tmax"]), n, ptr(ex), ptr(order),
+                                                      ptr(res[0]), ptr(res[1]), ptr(res[2]), stp, C.c_void_p(qs.cuda_stream))
+            if qs != cur:
+                for x in (rays, reals["radius"], reals["tmax"], exclude, order) + tuple(res if out is not None else ()):
+                    if isinstance(x, torch.Tensor) and x.is_cuda:
+                        x.record_stream(qs)
+            capi.check(rc, "rt_sweep_spheres_device")
+        else:
+            if not isinstance(rays, np.ndarray) or rays.dtype != R or rays.ndim != 2 or rays.shape[1] != 6 or rays.shape[0] == 0:
+                raise ValueError("rays must be a non-empty (n, 6) numpy array of %s (or a torch tensor on the scene's device)" % np.dtype(R).name)
+            n = rays.shape[0]
+            r = np.ascontiguousarray(rays)
+            q = None if radius is None else self._radius_array(radius, R, n)
+            t = None if tmax is None else _tmax_array(tmax, R, n)
+            ex = None
+            if exclude is not None:
+                ex = np.asarray(exclude)
+                if ex.dtype != np.int32 or ex.shape != (n,):
+                    raise ValueError("exclude must be None or an (n,) int32 array")
+                ex = np.ascontiguousarray(ex)
+            o = None if order is None else self._order_numpy(order, n)
+            specs = (((n,), R), ((n, 3), R), ((n,), np.int32))
+            if out is None:
+                res = tuple(np.empty(shape, dtype=dt) for shape, dt in specs)
+            else:
+                res = tuple(out)
+                if len(res) != 3 or any(not isinstance(a, np.ndarray) or a.dtype != dt or a.shape != shape or not a.flags.c_contiguous
+                                        for a, (shape, dt) in zip(res, specs)):
+                    raise ValueError("out: contiguous arrays of " + ", ".join("%s %s" % (np.dtype(dt).name, shape) for shape, dt in specs))
+            ptr = lambda x: None if x is None else x.ctypes.data
+            rc = capi.lib.rt_sweep_spheres(self._h, mode, ptr(r), ptr(q), ptr(t), n, ptr(ex), ptr(o), ptr(res[0]), ptr(res[1]), ptr(res[2]), stp)
+            capi.check(rc, "rt_sweep_spheres")
+        if want_stats:
+            return tuple(res) + (st.as_dict(),)
+        return tuple(res)
+
     @staticmethod
     def _radius_array(radius, R, n):
-        """near()'s radius as a contiguous REAL[n] (one value is rounded to REAL; an array must already be REAL)."""
+        """near()'s and sweep()'s radius as a contiguous REAL[n] (one value is rounded to REAL; an array must already be REAL)."""
         try:
             return _tmax_array(radius, R, n)
         except ValueError:
