@@ -632,6 +632,49 @@ rt_status rt_sweep_spheres_device(rt_scene *scene, rt_sweep mode, const void *ra
                                   const int32_t *exclude, const uint32_t *order, void *distance_out, void *normal_out, int32_t *item_out,
                                   rt_stats *stats, void *hip_stream);
 
+/* ---- contact pairs (additive to ABI 5): every pair of spheres of the scene that is closer than a margin ----
+ * The question a caller that moves spheres asks every step: which spheres of the scene touch each other?  The broad phase of a collision
+ * step, the neighbour list of a relaxation step.  rt_near_spheres can only approximate it -- every centre has to come back in as a query,
+ * every pair is found twice, and a query lists at most RT_NEAR_MAX_K neighbours.  This is a self-join over the scene's own stream: every
+ * pair is tested once, and the list is as long as the data makes it.
+ *   For two item slots i < j with stream records {c_i, rr_i} and {c_j, rr_j} -- rr is the radius squared, rounded once -- in REAL, every
+ * operation rounded once, no FMA, every root the IEEE one:
+ *   v   = c_j - c_i                                   component-wise
+ *   vv  = (v.x*v.x + v.y*v.y) + v.z*v.z
+ *   gap = (rr_i > 0 && rr_j > 0) ? (sqrt(vv) - sqrt(rr_j)) - sqrt(rr_i) : +inf
+ * the proximity queries' gap of record j from the point c_i, minus the radius of sphere i.  The LOWER slot is always the query, so the
+ * rounding of a pair is defined once.  The pair (i, j) is a CONTACT when !(gap >= margin): margin = 0 gives the overlapping spheres, a
+ * positive margin is a skin, a negative one gives the pairs that overlap that deep, +inf every pair of live spheres.  A dead item (rr =
+ * -inf, "live and dead slots" above) is never part of a pair, as i or as j; a sphere whose rr is 0 behaves like one, as for the proximity
+ * queries.  rust_tracer_amd.pair_gaps restates the gap in numpy, bit for bit.
+ *   The walk is the proximity queries' RT_NEAR_ALL walk with the scene's items as the queries: item i walks the part of the stream BEHIND
+ * its own node -- items appear in the stream in ascending slot order, so that is every item j > i -- with q = sqrt(rr_i); a bound culls
+ * when (sqrt(vv) - sqrt(rr)) - q >= margin (a bound without a positive rr: always), an item with !(gap >= margin) is a contact.  The
+ * result is the walk's, as for every query here: a bound encloses its items, so a pair can differ from brute force over all i < j only
+ * if its gap lies within a few ulp of the margin.
+ *   The list is made in two passes, without an atomic append, so it is the same bytes every time: the walk counts the pairs of every
+ * item, an exclusive scan of the counts gives offsets[n_items + 1], and the walk runs again and writes pair offsets[i] + (rank within i).
+ * The pairs are sorted by (i, j).  pairs_out (int32[2 capacity] or NULL): pair p is pairs_out[2p] = i, pairs_out[2p + 1] = j; gap_out
+ * (REAL[capacity] or NULL; needs pairs_out): its gap.  Only pairs p < min(capacity, total) are written -- a capacity that is too small
+ * gets the exact prefix of the list, and nothing behind it is touched.  *total_out is always the full count: size a buffer from it and
+ * call again.  capacity == 0 or pairs_out == NULL skips the second pass: the cheap "how many".  offsets_out (uint64[n_items + 1] or
+ * NULL): item i is the lower slot of pairs offsets_out[i] .. offsets_out[i + 1], and offsets_out[n_items] == *total_out.  stats (may be
+ * NULL): the counters of ONE walk, the counting pass -- primary = live items, hits = items with at least one pair as the lower slot,
+ * sphere_tests / bound_tests / tests_executed, every other counter 0; asking for it runs the counting flavour (same bytes). */
+/* Host memory.  RT_ERR_INVALID_ARGUMENT before the device is touched for a NULL scene or total_out, a NaN margin, a misaligned buffer
+ * (pairs_out 4 bytes, gap_out REAL, offsets_out and total_out 8 bytes), gap_out without pairs_out, capacity > 2^31 - 1 and a buffer in
+ * device memory.  Pinned memory is written in place, pageable memory goes through the call's device workspace.  Returns when the results
+ * are in place.  The call is a READ in the sense of ORDER above, on static, dynamic, live and flat scenes alike.  Host calls on one scene
+ * take turns (they share the scene's contacts workspace, made by the first call and freed with the scene). */
+rt_status rt_scene_contacts(rt_scene *scene, double margin, uint32_t capacity, int32_t *pairs_out, void *gap_out, uint64_t *offsets_out,
+                            uint64_t *total_out, rt_stats *stats);
+/* The same over DEVICE memory (total_out too), enqueued on `hip_stream` without a host synchronisation: only pointers, alignment, the
+ * margin and the capacity are checked.  Nothing is allocated beyond the scene's contacts workspace at the first call; a call goes behind
+ * the contacts call before it, whichever stream that was on.  Pairs p >= *total_out keep the caller's bytes.  stats != NULL: filled after
+ * an internal synchronisation of hip_stream. */
+rt_status rt_scene_contacts_device(rt_scene *scene, double margin, uint32_t capacity, int32_t *pairs_out, void *gap_out, uint64_t *offsets_out,
+                                   uint64_t *total_out, rt_stats *stats, void *hip_stream);
+
 /* Bytes rt_render_tiles writes for this tile list (4 * total area), or 0 on an invalid list. */
 uint64_t rt_tiles_rgba_bytes(const rt_region *tiles, uint32_t n_tiles);
 

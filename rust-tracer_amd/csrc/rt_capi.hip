@@ -20,6 +20,7 @@
 #include "rt_multihit.hpp"
 #include "rt_near.hpp"
 #include "rt_sweep.hpp"
+#include "rt_contacts.hpp"
 #include "rt_order.hpp"
 #include "rt_dynamic.hpp"
 #include "rt_rebuild.hpp"
@@ -280,6 +281,16 @@ struct rt_scene {
     hipEvent_t upd_ev = nullptr;       // behind the last update
     void *d_rebuild = nullptr;         // rt_scene_rebuild*: the sort's workspace for n_items keys and the gathered items behind it (rt_rebuild.hpp), made by the first rebuild
     std::mutex rebuild_mu;             // (two first rebuilds at once make it once)
+    // ---- contact pairs (rt_scene_contacts*, rt_contacts.hpp): the workspace of the two passes -- counts, offsets, the scan's block sums and,
+    // on a scene that is not dynamic, the item-to-node table -- made by the first call and shared by all: a call enqueues under contacts_mu
+    // and behind contacts_ev, which the call before it recorded on its own stream
+    std::mutex contacts_mu;
+    void *d_contacts = nullptr;
+    uint32_t *d_contacts_counts = nullptr, *d_contacts_item_node = nullptr;
+    uint64_t *d_contacts_offsets = nullptr, *d_contacts_sums = nullptr;
+    hipEvent_t contacts_ev = nullptr;
+    uint64_t *h_contacts_total = nullptr, *d_contacts_total = nullptr;      // one pinned word and its device alias: the host entry reads the total here (no copy into a caller's stack)
+    bool contacts_recorded = false;
 };
 
 namespace {

@@ -942,6 +942,110 @@ rt_status enqueue_sweep(const rt_scene *s, const void *nodes, uint32_t n_nodes, 
                                   : enqueue_sweep<double>(s, nodes, n_nodes, mode, rays, radius, tmax, n, exclude, order, dist, normal, item, counters, stream);
 }
 
+// ---- contact pairs (rt_scene_contacts*, rt_contacts.hpp) ----
+
+// What both contacts entries check (device pointers are not dereferenced here).
+bool contacts_args_ok(const rt_scene *s, double margin, uint32_t capacity, const int32_t *pairs, const void *gap, const uint64_t *offsets, const uint64_t *total,
+                      const char *what)
+{
+    if (!s || !total) { snprintf(g_err, sizeof g_err, "%s: NULL scene or total_out", what); return false; }
+    if (std::isnan(margin)) { snprintf(g_err, sizeof g_err, "%s: margin is NaN", what); return false; }
+    if (capacity > 0x7FFFFFFFu) { snprintf(g_err, sizeof g_err, "%s: capacity %u is above 2^31 - 1", what, capacity); return false; }
+    if (gap && !pairs) { snprintf(g_err, sizeof g_err, "%s: gap_out without pairs_out", what); return false; }
+    if ((reinterpret_cast<uintptr_t>(pairs) & 3u) != 0) { snprintf(g_err, sizeof g_err, "%s: pairs_out must be 4-byte aligned", what); return false; }
+    const struct { const void *p; const char *name; } longs[] = { { offsets, "offsets_out" }, { total, "total_out" } };
+    for (const auto &w : longs)
+        if ((reinterpret_cast<uintptr_t>(w.p) & 7u) != 0) { snprintf(g_err, sizeof g_err, "%s: %s must be 8-byte aligned", what, w.name); return false; }
+    const uintptr_t esz = s->precision == RT_F32 ? sizeof(float) : sizeof(double);
+    if ((reinterpret_cast<uintptr_t>(gap) % esz) != 0) { snprintf(g_err, sizeof g_err, "%s: gap_out must be %u-byte aligned", what, (unsigned)esz); return false; }
+    return true;
+}
+
+// The scene's contacts workspace, made by the first call, and this call's place behind the one before it.  Under s->contacts_mu.  A scene
+// that is not dynamic gets its item-to-node table here, on `stream`: every later call waits for contacts_ev, so for it too.
+rt_status contacts_begin(rt_scene *s, const void *nodes, uint32_t n_nodes, hipStream_t stream)
+{
+    if (!s->contacts_ev) HIP_TRY(hipEventCreateWithFlags(&s->contacts_ev, hipEventDisableTiming));
+    if (s->contacts_recorded) HIP_TRY(hipStreamWaitEvent(stream, s->contacts_ev, 0));
+    if (s->d_contacts) return RT_OK;
+    const size_t n = s->n_items, n_sums = (n + rt::kScanBlock - 1) / rt::kScanBlock;
+    const bool table = s->n_nodes != 0 && !s->d_item_node;
+    const size_t o_offsets = (sizeof(uint32_t) * n + 255) & ~(size_t)255, o_sums = o_offsets + ((sizeof(uint64_t) * (n + 1) + 255) & ~(size_t)255);
+    const size_t o_table = o_sums + ((sizeof(uint64_t) * (n_sums + 1) + 255) & ~(size_t)255);
+    if (!s->h_contacts_total) {
+        void *h = nullptr, *alias = nullptr;
+        HIP_TRY(hipHostMalloc(&h, 64, hipHostMallocDefault));
+        if (const hipError_t e = hipHostGetDevicePointer(&alias, h, 0); e != hipSuccess) { (void)hipHostFree(h); return hip_fail(e, "hipHostGetDevicePointer(total)", __LINE__); }
+        s->h_contacts_total = static_cast<uint64_t *>(h);
+        s->d_contacts_total = static_cast<uint64_t *>(alias);
+    }
+    void *p = nullptr;
+    HIP_TRY(hipMalloc(&p, o_table + (table ? sizeof(uint32_t) * n : 0) + 256));
+    uint8_t *const d = static_cast<uint8_t *>(p);
+    if (table) {
+        uint32_t *const item_node = reinterpret_cast<uint32_t *>(d + o_table);
+        const dim3 grid((n_nodes + 255) / 256), block(256);
+        if (const hipError_t e = hipMemsetAsync(item_node, 0xFF, sizeof(uint32_t) * n, stream); e != hipSuccess) { (void)hipFree(p); return hip_fail(e, "hipMemsetAsync(item_node)", __LINE__); }
+        if (s->precision == RT_F32) hipLaunchKernelGGL(rt::k_contact_item_nodes<float>, grid, block, 0, stream, static_cast<const rt::Node<float> *>(nodes), n_nodes, s->n_items, item_node);
+        else hipLaunchKernelGGL(rt::k_contact_item_nodes<double>, grid, block, 0, stream, static_cast<const rt::Node<double> *>(nodes), n_nodes, s->n_items, item_node);
+        if (const hipError_t e = hipGetLastError(); e != hipSuccess) { (void)hipFree(p); return hip_fail(e, "k_contact_item_nodes", __LINE__); }
+        s->d_contacts_item_node = item_node;
+    }
+    s->d_contacts = p;
+    s->d_contacts_counts = reinterpret_cast<uint32_t *>(d);
+    s->d_contacts_offsets = reinterpret_cast<uint64_t *>(d + o_offsets);
+    s->d_contacts_sums = reinterpret_cast<uint64_t *>(d + o_sums);
+    return RT_OK;
+}
+
+// The first pass and the scan on `stream`: counts, then offsets[n_items + 1] in the workspace and, where given, in the caller's device
+// memory.  counters != NULL runs the counting flavour (same counts).
+template <typename T>
+rt_status enqueue_contacts_count(const rt_scene *s, const void *nodes, uint32_t n_nodes, double margin, uint64_t *offsets_out, uint64_t *total_out,
+                                 rt::Counters *counters, hipStream_t stream)
+{
+    const uint32_t n = s->n_items;
+    const uint32_t *const item_node = s->n_nodes ? (s->d_item_node ? s->d_item_node : s->d_contacts_item_node) : nullptr;
+    const rt::ContactArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), item_node, s->d_contacts_counts, nullptr, nullptr, nullptr, counters, (T)margin, n_nodes, n, 0u };
+    const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
+    if (counters) hipLaunchKernelGGL((rt::k_contact_pairs<T, true, false>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((rt::k_contact_pairs<T, false, false>), grid, block, 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    const unsigned n_sums = (n + rt::kScanBlock - 1) / rt::kScanBlock;
+    const dim3 sgrid(n_sums), sblock(rt::kScanBlock);
+    hipLaunchKernelGGL(rt::k_contact_scan_sums, sgrid, sblock, 0, stream, s->d_contacts_counts, n, s->d_contacts_sums);
+    hipLaunchKernelGGL(rt::k_contact_scan_spine, dim3(1), sblock, 0, stream, s->d_contacts_sums, n_sums, s->d_contacts_offsets + n, offsets_out ? offsets_out + n : nullptr, total_out);
+    hipLaunchKernelGGL(rt::k_contact_scan_offsets, sgrid, sblock, 0, stream, s->d_contacts_counts, n, s->d_contacts_sums, s->d_contacts_offsets, offsets_out);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+rt_status enqueue_contacts_count(const rt_scene *s, const void *nodes, uint32_t n_nodes, double margin, uint64_t *offsets_out, uint64_t *total_out,
+                                 rt::Counters *counters, hipStream_t stream)
+{
+    return s->precision == RT_F32 ? enqueue_contacts_count<float>(s, nodes, n_nodes, margin, offsets_out, total_out, counters, stream)
+                                  : enqueue_contacts_count<double>(s, nodes, n_nodes, margin, offsets_out, total_out, counters, stream);
+}
+
+// The second pass on `stream`: the same walk, pair offsets[i] + rank written where it lies below `capacity`.
+template <typename T>
+rt_status enqueue_contacts_fill(const rt_scene *s, const void *nodes, uint32_t n_nodes, double margin, uint32_t capacity, int32_t *pairs, void *gap, hipStream_t stream)
+{
+    const uint32_t n = s->n_items;
+    const uint32_t *const item_node = s->n_nodes ? (s->d_item_node ? s->d_item_node : s->d_contacts_item_node) : nullptr;
+    const rt::ContactArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), item_node, nullptr, s->d_contacts_offsets, pairs, static_cast<T *>(gap), nullptr, (T)margin, n_nodes, n, capacity };
+    const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
+    hipLaunchKernelGGL((rt::k_contact_pairs<T, false, true>), grid, block, 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+rt_status enqueue_contacts_fill(const rt_scene *s, const void *nodes, uint32_t n_nodes, double margin, uint32_t capacity, int32_t *pairs, void *gap, hipStream_t stream)
+{
+    return s->precision == RT_F32 ? enqueue_contacts_fill<float>(s, nodes, n_nodes, margin, capacity, pairs, gap, stream)
+                                  : enqueue_contacts_fill<double>(s, nodes, n_nodes, margin, capacity, pairs, gap, stream);
+}
+
 // ---- traced rays and camera frames (rt_trace_rays*, rt_render_camera*, rt_trace.hpp) ----
 
 // The camera domain both rt_render_camera entries check (in double, before the device is touched): 12 finite values, |eye coordinate|

@@ -99,6 +99,32 @@ def sphere_gaps(points, spheres):
     return np.where((rr > 0)[None, :], gap, R(np.inf)).astype(R, copy=False)
 
 
+def pair_gaps(spheres, i, j):
+    """The gap of the pairs (i[k], j[k]) of `spheres` (m x 4: cx, cy, cz, r) -> REAL[len(i)], the metric of rt_scene_contacts restated in
+    numpy bit for bit (include/rtrace_hip.h states it), in the array's dtype (float32 or float64), every operation rounded once:
+    rr = r * r;  v = c_j - c_i;  vv = (v.x*v.x + v.y*v.y) + v.z*v.z;  gap = (sqrt(vv) - sqrt(rr_j)) - sqrt(rr_i) where rr_i > 0 and
+    rr_j > 0, else +inf: sphere_gaps of sphere j from the centre of sphere i, minus the radius of sphere i.  The library always takes the
+    lower slot as i.  A record without a positive rr -- radius 0: a dead slot -- is at +inf from every sphere, in either place.
+    DeviceScene.contacts lists the pairs i < j with !(gap >= margin)."""
+    s = np.asarray(spheres)
+    if s.dtype not in (np.float32, np.float64) or s.ndim != 2 or s.shape[1] != 4:
+        raise ValueError("spheres must be an (m, 4) array of float32 or float64")
+    i, j = np.asarray(i), np.asarray(j)
+    if i.dtype.kind not in "iu" or j.dtype.kind not in "iu" or i.ndim != 1 or i.shape != j.shape:
+        raise ValueError("i and j must be integer arrays of one shape, (k,)")
+    if i.size and (min(int(i.min()), int(j.min())) < 0 or max(int(i.max()), int(j.max())) >= s.shape[0]):
+        raise ValueError("i and j must be rows of spheres")
+    R = s.dtype.type
+    rr = s[:, 3] * s[:, 3]
+    rri, rrj = rr[i], rr[j]
+    solid = (rri > 0) & (rrj > 0)
+    with np.errstate(invalid="ignore", over="ignore"):
+        v = s[j, :3] - s[i, :3]
+        vv = (v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1]) + v[:, 2] * v[:, 2]
+        gap = (np.sqrt(vv) - np.sqrt(np.where(rrj > 0, rrj, R(1.0)))) - np.sqrt(np.where(rri > 0, rri, R(1.0)))
+    return np.where(solid, gap, R(np.inf)).astype(R, copy=False)
+
+
 def sweep_distances(rays, radius, spheres):
     """The cast distance of every cast of `rays` (n x 6: pos.xyz, dir.xyz, dir a unit vector) with `radius` (REAL[n], one value, or None: 0)
     against every sphere of `spheres` (m x 4: cx, cy, cz, r) -> REAL[n, m], the metric of rt_sweep_spheres restated in numpy bit for bit
@@ -1065,6 +1091,71 @@ class DeviceScene:
         if want_stats:
             return tuple(res) + (st.as_dict(),)
         return tuple(res)
+
+    def contacts(self, margin=0.0, capacity=None, gaps=False, offsets=False, stats=False, device=False, stream=None):
+        """rt_scene_contacts / rt_scene_contacts_device: every pair of spheres of the scene that is closer than `margin` (pair_gaps is the
+        metric; 0: the overlapping spheres, a positive margin is a skin, a negative one asks for that much overlap, +inf gives every pair
+        of live spheres) -> (pairs[, gap][, offsets], total[, stats dict]).  pairs: int32[m, 2], the DFS slots i < j of every contact,
+        sorted by (i, j), the same bytes every time; a dead slot of a dynamic scene is in no pair.  gaps=True: REAL[m], each pair's gap.
+        offsets=True: uint64[n_items + 1], item i is the lower slot of pairs offsets[i] .. offsets[i + 1].  total: how many pairs there
+        are.  capacity=None counts first and then allocates exactly (m = total); with a capacity, m = min(capacity, total) and the list is
+        the exact prefix of the full one; capacity=0 only counts.  device=False: the host entry, numpy results.  device=True: the device
+        entry on `stream` (a torch stream or a hipStream_t as int; default the current torch stream), torch tensors on the scene's device
+        -- with a capacity nothing is waited for: pairs has `capacity` rows of which the first `total` are written, and total is a 0-d
+        int64 tensor (offsets is an int64 tensor too: the same bits); capacity=None reads the count back first, and total is an int."""
+        margin = float(margin)
+        if margin != margin:
+            raise ValueError("margin must not be NaN")
+        if capacity is not None:
+            capacity = int(capacity)
+            if not 0 <= capacity <= 0x7FFFFFFF:
+                raise ValueError("capacity must be None or 0 .. 2^31 - 1, not %d" % capacity)
+        R = _real(self.scene.precision)
+        n = self.scene.items.shape[0]
+        st = capi.Stats()
+        stp = C.byref(st) if stats else None
+        if device:
+            import torch
+            tdt = torch.float32 if R == np.float32 else torch.float64
+            dev = torch.device("cuda", self.device)
+            qs, cur = self._device_stream(torch, stream)
+            if qs != cur:
+                qs.wait_stream(cur)
+            ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
+            with torch.cuda.stream(qs):
+                total = torch.zeros((), dtype=torch.int64, device=dev)
+                off = torch.empty(n + 1, dtype=torch.int64, device=dev) if offsets else None
+                counted = capacity is None
+                if counted:
+                    capi.check(capi.lib.rt_scene_contacts_device(self._h, margin, 0, None, None, None, ptr(total), None, C.c_void_p(qs.cuda_stream)),
+                               "rt_scene_contacts_device")
+                    capacity = int(total.item())
+                    if capacity > 0x7FFFFFFF:
+                        raise ValueError("the scene has %d contacts, more than one call can list: pass a capacity" % capacity)
+                pairs = torch.empty((capacity, 2), dtype=torch.int32, device=dev)
+                gap = torch.empty(capacity, dtype=tdt, device=dev) if gaps else None
+                rc = capi.lib.rt_scene_contacts_device(self._h, margin, capacity, ptr(pairs) if capacity else None, ptr(gap) if capacity else None, ptr(off), ptr(total), stp,
+                                                       C.c_void_p(qs.cuda_stream))
+            capi.check(rc, "rt_scene_contacts_device")
+            total = int(total.item()) if counted else total
+        else:
+            total = C.c_uint64(0)
+            off = np.empty(n + 1, dtype=np.uint64) if offsets else None
+            ptr = lambda x: None if x is None else x.ctypes.data
+            if capacity is None:
+                capi.check(capi.lib.rt_scene_contacts(self._h, margin, 0, None, None, None, C.byref(total), None), "rt_scene_contacts")
+                capacity = int(total.value)
+                if capacity > 0x7FFFFFFF:
+                    raise ValueError("the scene has %d contacts, more than one call can list: pass a capacity" % capacity)
+            pairs = np.empty((capacity, 2), dtype=np.int32)
+            gap = np.empty(capacity, dtype=R) if gaps else None
+            capi.check(capi.lib.rt_scene_contacts(self._h, margin, capacity, ptr(pairs) if capacity else None, ptr(gap) if capacity else None, ptr(off),
+                                                  C.byref(total), stp), "rt_scene_contacts")
+            total = int(total.value)
+            m = min(capacity, total)
+            pairs, gap = pairs[:m], (gap[:m] if gaps else None)
+        res = (pairs,) + ((gap,) if gaps else ()) + ((off,) if offsets else ()) + (total,)
+        return res + ((st.as_dict(),) if stats else ())
 
     @staticmethod
     def _radius_array(radius, R, n):
