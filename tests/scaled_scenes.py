@@ -14,7 +14,13 @@ base_scenes() -> [(name, items, bounds, ranges)]: random_nested_scene(31) and th
 answers), and the same items with no bounds at all: the flat walk.
 
 case(precision, placement) -> [Case]: every base scene placed, with its oracle, 84 rays (ray_families, n_each = 12: one full wave and a
-partly filled one) and 80 query points (query_families, n_each = 20).  Made once per process; nothing in a Case is written to."""
+partly filled one) and 80 query points (query_families, n_each = 20).  Made once per process; nothing in a Case is written to.
+
+casts(c) -> (rays, radius, which, tmax): the 80 sphere casts of a Case (cast_families and cutoffs of tests/test_gpu_sweep.py, n_each = 20: one
+full wave and a partly filled one; radii 0, a quarter of the median, 0.5 - 2 medians, half the root and three roots), and margins(c): the
+contact margins (0, r, -0.25 r, 4 r, +inf, -inf) with r the median placed item radius; ray_casts(c) -> (rays, zeros, tmax): the casts from
+outside the root with radius 0 and cutoffs of their own (default_rng(400 + k)), which are ray queries.  Made on first use, once per process, for the
+cast and contact tests (tests/test_scales_contact_host.py, tests/test_gpu_scales_contact.py); the other tests pay nothing for them."""
 import functools
 
 import numpy as np
@@ -29,6 +35,7 @@ SCALES = (1e-20, 1e-10, 1e6, 5e13)
 EYE = (0.07, -0.12, -3.1)                    # the scaled frame tests' eye
 LIGHT = (-1.0, -3.0, 2.0)
 N_EACH_RAYS, N_EACH_POINTS = 12, 20
+N_EACH_CASTS = 20
 AIMED_FAMILIES = (0, 4)                      # ray_families: "outside the root, aimed at items" and "inside the root, aimed at items"
 
 
@@ -107,6 +114,47 @@ def case(precision, placement):
         c.points, c.radius = query_families(c.scene, np.random.default_rng(200 + k), N_EACH_POINTS)
         out.append(c)
     return tuple(out)
+
+
+_CASTS = {}
+
+
+def casts(c):
+    """(rays REAL[80, 6], radius REAL[80], which int[80], tmax REAL[80]) of Case c; family f in rows [20 f, 20 (f + 1))."""
+    from tests.test_gpu_sweep import cast_families, cutoffs
+    key = (c.precision, c.placement, c.name)
+    if key not in _CASTS:
+        k = [b[0] for b in base_scenes()].index(c.name)
+        rng = np.random.default_rng(300 + k)
+        rays, radius, which = cast_families(c.scene, rng, N_EACH_CASTS)
+        tmax = cutoffs(rays, radius, c.scene.items, rng)
+        for a in (rays, radius, which, tmax):
+            a.setflags(write=False)
+        _CASTS[key] = (rays, radius, which, tmax)
+    return _CASTS[key]
+
+
+def ray_casts(c):
+    """(rays REAL[40, 6], zeros REAL[40], tmax REAL[40]): the casts of families 0 and 3 of Case c (from outside the root, aimed at items and aimed
+    away) with radius 0 and cutoffs of their own: the casts that are ray queries."""
+    from tests.test_gpu_sweep import cutoffs
+    key = (c.precision, c.placement, c.name, "rays")
+    if key not in _CASTS:
+        k = [b[0] for b in base_scenes()].index(c.name)
+        rays = casts(c)[0]
+        rays = np.ascontiguousarray(np.concatenate([rays[:N_EACH_CASTS], rays[3 * N_EACH_CASTS:]]))
+        zeros = np.zeros(len(rays), rays.dtype)
+        tmax = cutoffs(rays, zeros, c.scene.items, np.random.default_rng(400 + k))
+        for a in (rays, zeros, tmax):
+            a.setflags(write=False)
+        _CASTS[key] = (rays, zeros, tmax)
+    return _CASTS[key]
+
+
+def margins(c):
+    """The contact margins of Case c: (0, r, -0.25 r, 4 r, +inf, -inf), r the median placed item radius."""
+    r = float(np.median(c.scene.items[:, 3]))
+    return (0.0, r, -0.25 * r, 4.0 * r, np.inf, -np.inf)
 
 
 def oracle_nearest(c, rays=None, tmax=None):
