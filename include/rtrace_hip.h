@@ -675,6 +675,59 @@ rt_status rt_scene_contacts(rt_scene *scene, double margin, uint32_t capacity, i
 rt_status rt_scene_contacts_device(rt_scene *scene, double margin, uint32_t capacity, int32_t *pairs_out, void *gap_out, uint64_t *offsets_out,
                                    uint64_t *total_out, rt_stats *stats, void *hip_stream);
 
+/* ---- overlap lists (additive to ABI 5): every sphere of the scene within a margin of each query sphere ----
+ * The question of a sphere that is NOT an item of the scene: which spheres of the scene does it touch?  A second set of bodies against a
+ * resident world, a sensor or trigger volume, a sphere about to be spawned.  rt_near_spheres takes outside queries but keeps at most
+ * RT_NEAR_MAX_K slots per query; rt_scene_contacts has no cap but its queries are the scene's own records.  This entry takes outside
+ * queries and gives a list as long as the data makes it.
+ *   Query g is queries[4g .. 4g+4] = {p.x, p.y, p.z, q} in REAL: a centre and a radius, the layout of a scene's sphere array -- a second
+ * scene's spheres go in as they are.  For a record {c, rr} of the scene's stream -- rr is the radius squared, rounded once -- in REAL,
+ * every operation rounded once, no FMA, every root the IEEE one:
+ *   v   = c - p                                       component-wise
+ *   vv  = (v.x*v.x + v.y*v.y) + v.z*v.z
+ *   gap = rr > 0 ? (sqrt(vv) - sqrt(rr)) - q : +inf
+ * the proximity queries' gap minus the query's radius: the contact pairs' gap with q given by the caller instead of taken from the
+ * stream.  With q = 0 it is the proximity queries' gap bit for bit (x - 0 == x).  An item is LISTED when !(gap >= margin): margin = 0
+ * gives the spheres the query overlaps, a positive margin is a skin, a negative one asks for that much overlap, +inf lists every live
+ * sphere.  A query whose q is not >= 0 (negative, NaN) carries no query: it makes no test and lists nothing.  A dead item (rr = -inf,
+ * "live and dead slots" above) is at +inf and never listed, at margin = +inf too; a sphere whose rr is 0 behaves like one.
+ * rust_tracer_amd.overlap_gaps restates the gap in numpy, bit for bit.
+ *   The walk is the proximity queries' RT_NEAR_ALL walk over the whole stream: a bound culls when its gap >= margin (a bound without a
+ * positive rr: always), an item with !(gap >= margin) is listed.  The result is the walk's, as for every query here: a bound encloses its
+ * items, so a list can differ from brute force over all items only where a gap lies within a few ulp of the margin.  exclude and order
+ * mean what they mean for rt_near_spheres: exclude (int32[n] or NULL) is the item slot query g never lists -- it is tested and counted as
+ * a test, never listed or counted as found; order (uint32[n] or NULL): thread j carries query order[j], and the bytes and counters are
+ * the same in every order.
+ *   The list is made as the contact pairs' is, in two passes and without an atomic append, so it is the same bytes every time: the walk
+ * counts the entries of every query, an exclusive scan of the counts gives offsets[n + 1], and the walk runs again -- only for the
+ * queries that counted something -- and writes entry offsets[g] + (rank within g).  The entries are sorted by (g, item slot).  items_out
+ * (int32[capacity] or NULL): the item slot of every entry; gap_out (REAL[capacity] or NULL; needs items_out): its gap.  Only entries
+ * e < min(capacity, total) are written -- a capacity that is too small gets the exact prefix of the list, and nothing behind it is
+ * touched.  *total_out is always the full count: size a buffer from it and call again.  capacity == 0 or items_out == NULL skips the
+ * second pass: the cheap "how many".  offsets_out (uint64[n + 1] or NULL): query g owns entries offsets_out[g] .. offsets_out[g + 1], and
+ * offsets_out[n] == *total_out.  stats (may be NULL): the counters of ONE walk, the counting pass -- primary = queries carried, hits =
+ * queries with at least one entry, sphere_tests / bound_tests / tests_executed, every other counter 0; asking for it runs the counting
+ * flavour (same bytes).
+ *   The workspace of the two passes (counts, offsets, the scan's block sums) belongs to the scene: the first call makes it, and it grows
+ * only when n exceeds the largest n any call on the scene has brought so far.  Growing is the one allocation a call can make, and it
+ * waits for the overlap call before it.  The workspace is freed with the scene.  Calls on one scene are put in a row. */
+/* Host memory.  RT_ERR_INVALID_ARGUMENT before the device is touched for a NULL scene, queries or total_out, n == 0, a NaN margin, a
+ * misaligned buffer (items_out, exclude, order 4 bytes, queries and gap_out REAL, offsets_out and total_out 8 bytes), gap_out without
+ * items_out, capacity > 2^31 - 1, a buffer in device memory, a centre coordinate that is not finite or beyond +-1e15, a q that is NaN,
+ * negative, infinite or above 1e15 (the radius of rt_sweep_spheres) and an order that is no permutation of 0 .. n-1.  Pinned memory is
+ * used in place, pageable memory goes through the call's device workspace.  Returns when the results are in place.  The call is a READ
+ * in the sense of ORDER above, on static, dynamic, live and flat scenes alike. */
+rt_status rt_overlap_spheres(rt_scene *scene, const void *queries, uint32_t n, double margin, const int32_t *exclude, const uint32_t *order,
+                             uint32_t capacity, int32_t *items_out, void *gap_out, uint64_t *offsets_out, uint64_t *total_out, rt_stats *stats);
+/* The same over DEVICE memory (total_out too), enqueued on `hip_stream` without a host synchronisation (but see the workspace above):
+ * only pointers, alignment, n, the margin and the capacity are checked.  An order entry >= n carries no query, and a query that no
+ * thread carries has count 0; any input bits end the walk without a fault.  A call goes behind the overlap call before it, whichever
+ * stream that was on.  Entries e >= *total_out keep the caller's bytes.  stats != NULL: filled after an internal synchronisation of
+ * hip_stream. */
+rt_status rt_overlap_spheres_device(rt_scene *scene, const void *queries, uint32_t n, double margin, const int32_t *exclude, const uint32_t *order,
+                                    uint32_t capacity, int32_t *items_out, void *gap_out, uint64_t *offsets_out, uint64_t *total_out, rt_stats *stats,
+                                    void *hip_stream);
+
 /* Bytes rt_render_tiles writes for this tile list (4 * total area), or 0 on an invalid list. */
 uint64_t rt_tiles_rgba_bytes(const rt_region *tiles, uint32_t n_tiles);
 

@@ -21,6 +21,7 @@
 #include "rt_near.hpp"
 #include "rt_sweep.hpp"
 #include "rt_contacts.hpp"
+#include "rt_overlap.hpp"
 #include "rt_order.hpp"
 #include "rt_dynamic.hpp"
 #include "rt_rebuild.hpp"
@@ -291,6 +292,18 @@ struct rt_scene {
     hipEvent_t contacts_ev = nullptr;
     uint64_t *h_contacts_total = nullptr, *d_contacts_total = nullptr;      // one pinned word and its device alias: the host entry reads the total here (no copy into a caller's stack)
     bool contacts_recorded = false;
+    // ---- overlap lists (rt_overlap_spheres*, rt_overlap.hpp): the workspace of the two passes -- counts, offsets and the scan's block sums
+    // for overlap_cap queries -- made by the first call, grown when a call brings more queries than any before it (behind overlap_ev: the
+    // one allocation) and shared by all: a call enqueues under overlap_mu and behind overlap_ev, which the call before it recorded on its
+    // own stream
+    std::mutex overlap_mu;
+    void *d_overlap = nullptr;
+    size_t overlap_cap = 0;
+    uint32_t *d_overlap_counts = nullptr;
+    uint64_t *d_overlap_offsets = nullptr, *d_overlap_sums = nullptr;
+    hipEvent_t overlap_ev = nullptr;
+    uint64_t *h_overlap_total = nullptr, *d_overlap_total = nullptr;        // one pinned word and its device alias, as h_contacts_total
+    bool overlap_recorded = false;
 };
 
 namespace {

@@ -1046,6 +1046,130 @@ rt_status enqueue_contacts_fill(const rt_scene *s, const void *nodes, uint32_t n
                                   : enqueue_contacts_fill<double>(s, nodes, n_nodes, margin, capacity, pairs, gap, stream);
 }
 
+// ---- overlap lists (rt_overlap_spheres*, rt_overlap.hpp) ----
+
+// What both overlap entries check (device pointers are not dereferenced here).
+bool overlap_args_ok(const rt_scene *s, const void *queries, uint32_t n, double margin, const int32_t *exclude, const uint32_t *order, uint32_t capacity,
+                     const int32_t *items, const void *gap, const uint64_t *offsets, const uint64_t *total, const char *what)
+{
+    if (!s || !queries || !total || n == 0) { snprintf(g_err, sizeof g_err, "%s: NULL scene, queries or total_out, or n == 0", what); return false; }
+    if (std::isnan(margin)) { snprintf(g_err, sizeof g_err, "%s: margin is NaN", what); return false; }
+    if (capacity > 0x7FFFFFFFu) { snprintf(g_err, sizeof g_err, "%s: capacity %u is above 2^31 - 1", what, capacity); return false; }
+    if (gap && !items) { snprintf(g_err, sizeof g_err, "%s: gap_out without items_out", what); return false; }
+    const struct { const void *p; const char *name; } words[] = { { items, "items_out" }, { exclude, "exclude" }, { order, "order" } };
+    for (const auto &w : words)
+        if ((reinterpret_cast<uintptr_t>(w.p) & 3u) != 0) { snprintf(g_err, sizeof g_err, "%s: %s must be 4-byte aligned", what, w.name); return false; }
+    const struct { const void *p; const char *name; } longs[] = { { offsets, "offsets_out" }, { total, "total_out" } };
+    for (const auto &w : longs)
+        if ((reinterpret_cast<uintptr_t>(w.p) & 7u) != 0) { snprintf(g_err, sizeof g_err, "%s: %s must be 8-byte aligned", what, w.name); return false; }
+    const uintptr_t esz = s->precision == RT_F32 ? sizeof(float) : sizeof(double);
+    const struct { const void *p; const char *name; } reals[] = { { queries, "queries" }, { gap, "gap_out" } };
+    for (const auto &w : reals)
+        if ((reinterpret_cast<uintptr_t>(w.p) % esz) != 0) { snprintf(g_err, sizeof g_err, "%s: %s must be %u-byte aligned", what, w.name, (unsigned)esz); return false; }
+    return true;
+}
+
+// The host entry's domain: centres finite with |coordinate| <= 1e15 (rt_near_spheres's points) and a radius in 0 .. 1e15 (rt_sweep_spheres's).
+template <typename T>
+bool overlap_queries_valid(const T *queries, uint32_t n, const char *what)
+{
+    for (uint32_t i = 0; i < n; ++i) {
+        const T *rec = queries + 4 * (size_t)i;
+        for (int c = 0; c < 3; ++c)
+            if (!std::isfinite(rec[c]) || std::fabs((double)rec[c]) > 1e15) {
+                snprintf(g_err, sizeof g_err, "%s: query %u has a non-finite coordinate or one beyond +-1e15", what, i);
+                return false;
+            }
+        if (!(rec[3] >= T(0.0) && (double)rec[3] <= 1e15)) {         // (NaN fails the first comparison)
+            snprintf(g_err, sizeof g_err, "%s: query %u's radius %g is not in 0 .. 1e15", what, i, (double)rec[3]);
+            return false;
+        }
+    }
+    return true;
+}
+
+// The scene's overlap workspace for `n` queries, and this call's place behind the one before it.  Under s->overlap_mu.  The first call
+// makes the workspace; a call with more queries than any before it makes a larger one, once the call before it is through with the old.
+rt_status overlap_begin(rt_scene *s, uint32_t n, hipStream_t stream)
+{
+    if (!s->overlap_ev) HIP_TRY(hipEventCreateWithFlags(&s->overlap_ev, hipEventDisableTiming));
+    if (!s->h_overlap_total) {
+        void *h = nullptr, *alias = nullptr;
+        HIP_TRY(hipHostMalloc(&h, 64, hipHostMallocDefault));
+        if (const hipError_t e = hipHostGetDevicePointer(&alias, h, 0); e != hipSuccess) { (void)hipHostFree(h); return hip_fail(e, "hipHostGetDevicePointer(total)", __LINE__); }
+        s->h_overlap_total = static_cast<uint64_t *>(h);
+        s->d_overlap_total = static_cast<uint64_t *>(alias);
+    }
+    if (n > s->overlap_cap) {
+        if (s->overlap_recorded) HIP_TRY(hipEventSynchronize(s->overlap_ev));
+        if (s->d_overlap) HIP_TRY(hipFree(s->d_overlap));
+        s->d_overlap = nullptr; s->overlap_cap = 0;
+        const size_t n_sums = ((size_t)n + rt::kScanBlock - 1) / rt::kScanBlock;
+        const size_t o_offsets = (sizeof(uint32_t) * (size_t)n + 255) & ~(size_t)255;
+        const size_t o_sums = o_offsets + ((sizeof(uint64_t) * ((size_t)n + 1) + 255) & ~(size_t)255);
+        void *p = nullptr;
+        HIP_TRY(hipMalloc(&p, o_sums + ((sizeof(uint64_t) * (n_sums + 1) + 255) & ~(size_t)255)));
+        uint8_t *const d = static_cast<uint8_t *>(p);
+        s->d_overlap = p;
+        s->overlap_cap = n;
+        s->d_overlap_counts = reinterpret_cast<uint32_t *>(d);
+        s->d_overlap_offsets = reinterpret_cast<uint64_t *>(d + o_offsets);
+        s->d_overlap_sums = reinterpret_cast<uint64_t *>(d + o_sums);
+    }
+    if (s->overlap_recorded) HIP_TRY(hipStreamWaitEvent(stream, s->overlap_ev, 0));
+    return RT_OK;
+}
+
+// The first pass and the scan on `stream`: counts, then offsets[n + 1] in the workspace and, where given, in the caller's device memory.
+// counters != NULL runs the counting flavour (same counts).  With an order a query that no thread carries keeps the count 0.
+template <typename T>
+rt_status enqueue_overlap_count(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *queries, uint32_t n, double margin, const int32_t *exclude,
+                                const uint32_t *order, uint64_t *offsets_out, uint64_t *total_out, rt::Counters *counters, hipStream_t stream)
+{
+    const rt::OverlapArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), static_cast<const T *>(queries), exclude, order, s->d_overlap_counts, nullptr, nullptr, nullptr,
+                                counters, (T)margin, n_nodes, n, 0u };
+    if (order) HIP_TRY(hipMemsetAsync(s->d_overlap_counts, 0, sizeof(uint32_t) * (size_t)n, stream));
+    const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
+    if (counters) hipLaunchKernelGGL((rt::k_overlap_spheres<T, true, false>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((rt::k_overlap_spheres<T, false, false>), grid, block, 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    const unsigned n_sums = (unsigned)(((uint64_t)n + rt::kScanBlock - 1) / rt::kScanBlock);
+    const dim3 sgrid(n_sums), sblock(rt::kScanBlock);
+    hipLaunchKernelGGL(rt::k_contact_scan_sums, sgrid, sblock, 0, stream, s->d_overlap_counts, n, s->d_overlap_sums);
+    hipLaunchKernelGGL(rt::k_contact_scan_spine, dim3(1), sblock, 0, stream, s->d_overlap_sums, n_sums, s->d_overlap_offsets + n, offsets_out ? offsets_out + n : nullptr, total_out);
+    hipLaunchKernelGGL(rt::k_contact_scan_offsets, sgrid, sblock, 0, stream, s->d_overlap_counts, n, s->d_overlap_sums, s->d_overlap_offsets, offsets_out);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+rt_status enqueue_overlap_count(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *queries, uint32_t n, double margin, const int32_t *exclude,
+                                const uint32_t *order, uint64_t *offsets_out, uint64_t *total_out, rt::Counters *counters, hipStream_t stream)
+{
+    return s->precision == RT_F32 ? enqueue_overlap_count<float>(s, nodes, n_nodes, queries, n, margin, exclude, order, offsets_out, total_out, counters, stream)
+                                  : enqueue_overlap_count<double>(s, nodes, n_nodes, queries, n, margin, exclude, order, offsets_out, total_out, counters, stream);
+}
+
+// The second pass on `stream`: the same walk by the queries that counted something, entry offsets[g] + rank written where it lies below
+// `capacity`.
+template <typename T>
+rt_status enqueue_overlap_fill(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *queries, uint32_t n, double margin, const int32_t *exclude,
+                               const uint32_t *order, uint32_t capacity, int32_t *items, void *gap, hipStream_t stream)
+{
+    const rt::OverlapArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), static_cast<const T *>(queries), exclude, order, s->d_overlap_counts, s->d_overlap_offsets, items,
+                                static_cast<T *>(gap), nullptr, (T)margin, n_nodes, n, capacity };
+    const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
+    hipLaunchKernelGGL((rt::k_overlap_spheres<T, false, true>), grid, block, 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+rt_status enqueue_overlap_fill(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *queries, uint32_t n, double margin, const int32_t *exclude,
+                               const uint32_t *order, uint32_t capacity, int32_t *items, void *gap, hipStream_t stream)
+{
+    return s->precision == RT_F32 ? enqueue_overlap_fill<float>(s, nodes, n_nodes, queries, n, margin, exclude, order, capacity, items, gap, stream)
+                                  : enqueue_overlap_fill<double>(s, nodes, n_nodes, queries, n, margin, exclude, order, capacity, items, gap, stream);
+}
+
 // ---- traced rays and camera frames (rt_trace_rays*, rt_render_camera*, rt_trace.hpp) ----
 
 // The camera domain both rt_render_camera entries check (in double, before the device is touched): 12 finite values, |eye coordinate|

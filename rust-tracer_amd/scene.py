@@ -125,6 +125,26 @@ def pair_gaps(spheres, i, j):
     return np.where(solid, gap, R(np.inf)).astype(R, copy=False)
 
 
+def overlap_gaps(queries, spheres):
+    """The gap between every query sphere of `queries` (n x 4: px, py, pz, q) and every sphere of `spheres` (m x 4: cx, cy, cz, r) ->
+    REAL[n, m], the metric of rt_overlap_spheres restated in numpy bit for bit (include/rtrace_hip.h states it), in the arrays' dtype
+    (float32 or float64, the same for both), every operation rounded once:  rr = r * r;  v = c - p;  vv = (v.x*v.x + v.y*v.y) + v.z*v.z;
+    gap = (sqrt(vv) - sqrt(rr)) - q where rr > 0, else +inf: sphere_gaps from the query's centre, minus the query's radius.  With q = 0 it
+    is sphere_gaps; with a scene's own spheres as the queries and q = sqrt(r * r) it is pair_gaps.  A record without a positive rr --
+    radius 0: a dead slot -- is at +inf from every query.  DeviceScene.overlaps lists, per query with q >= 0, the spheres with
+    !(gap >= margin); a query whose q is not >= 0 carries no query there, and its row here is whatever the arithmetic gives."""
+    qs, s = np.asarray(queries), np.asarray(spheres)
+    if qs.dtype not in (np.float32, np.float64) or s.dtype != qs.dtype or qs.ndim != 2 or qs.shape[1] != 4 or s.ndim != 2 or s.shape[1] != 4:
+        raise ValueError("queries must be (n, 4) and spheres (m, 4), both float32 or both float64")
+    R = qs.dtype.type
+    rr = s[:, 3] * s[:, 3]
+    with np.errstate(invalid="ignore", over="ignore"):
+        v = s[None, :, :3] - qs[:, None, :3]
+        vv = (v[..., 0] * v[..., 0] + v[..., 1] * v[..., 1]) + v[..., 2] * v[..., 2]
+        gap = (np.sqrt(vv) - np.sqrt(np.where(rr > 0, rr, R(1.0)))[None, :]) - qs[:, 3][:, None]
+    return np.where((rr > 0)[None, :], gap, R(np.inf)).astype(R, copy=False)
+
+
 def sweep_distances(rays, radius, spheres):
     """The cast distance of every cast of `rays` (n x 6: pos.xyz, dir.xyz, dir a unit vector) with `radius` (REAL[n], one value, or None: 0)
     against every sphere of `spheres` (m x 4: cx, cy, cz, r) -> REAL[n, m], the metric of rt_sweep_spheres restated in numpy bit for bit
@@ -1155,6 +1175,111 @@ class DeviceScene:
             m = min(capacity, total)
             pairs, gap = pairs[:m], (gap[:m] if gaps else None)
         res = (pairs,) + ((gap,) if gaps else ()) + ((off,) if offsets else ()) + (total,)
+        return res + ((st.as_dict(),) if stats else ())
+
+    def overlaps(self, queries, margin=0.0, exclude=None, order=None, capacity=None, gaps=False, offsets=False, stats=False, stream=None):
+        """rt_overlap_spheres / rt_overlap_spheres_device: every sphere of the scene within `margin` of each query sphere of `queries`
+        (n x 4: px, py, pz, q, the scene's REAL dtype -- the layout of a sphere array; overlap_gaps is the metric; margin 0: the spheres a
+        query overlaps, a positive margin is a skin, a negative one asks for that much overlap, +inf lists every live sphere) ->
+        (items[, gap][, offsets], total[, stats dict]).  items: int32[m], the DFS slots of the listed spheres, query after query, ascending
+        within a query, the same bytes every time; a dead slot of a dynamic scene is never listed.  gaps=True: REAL[m], each entry's gap.
+        offsets=True: uint64[n + 1], query g owns entries offsets[g] .. offsets[g + 1].  total: how many entries there are.
+        capacity=None counts first and then allocates exactly (m = total); with a capacity, m = min(capacity, total) and the list is the
+        exact prefix of the full one; capacity=0 only counts.  exclude (int32[n]): the item slot each query never lists (-1 or a slot
+        outside the scene: none).  order (uint32[n]): thread j carries query order[j] -- the same bytes and counters in every order; True
+        asks sphere_order for a coherent one (by centre).  numpy arrays go through the host entry and give numpy results.  A torch
+        tensor on this scene's device goes through the device entry on `stream` (a torch stream or a hipStream_t as int; default the current
+        torch stream) and gives torch tensors -- with a capacity nothing is waited for: items has `capacity` entries of which the first
+        `total` are written, and total is a 0-d int64 tensor (offsets is an int64 tensor too: the same bits); capacity=None reads the
+        count back first, and total is an int.  Through the device entry an order entry >= n carries no query, and a query that no
+        thread carries, or whose q is not >= 0, has an empty row."""
+        margin = float(margin)
+        if margin != margin:
+            raise ValueError("margin must not be NaN")
+        if capacity is not None:
+            capacity = int(capacity)
+            if not 0 <= capacity <= 0x7FFFFFFF:
+                raise ValueError("capacity must be None or 0 .. 2^31 - 1, not %d" % capacity)
+        R = _real(self.scene.precision)
+        st = capi.Stats()
+        stp = C.byref(st) if stats else None
+        torch = sys.modules.get("torch")
+        if torch is not None and isinstance(queries, torch.Tensor):
+            tdt = torch.float32 if R == np.float32 else torch.float64
+            dev = torch.device("cuda", self.device)
+            if queries.dtype != tdt or queries.dim() != 2 or queries.shape[1] != 4 or queries.shape[0] == 0:
+                raise ValueError("queries must be a non-empty (n, 4) %s tensor" % tdt)
+            if queries.device != dev:
+                raise ValueError("queries must be on %s, not %s" % (dev, queries.device))
+            n = queries.shape[0]
+            if exclude is not None and (not isinstance(exclude, torch.Tensor) or exclude.dtype != torch.int32 or exclude.shape != (n,) or exclude.device != dev):
+                raise ValueError("exclude must be None or an (n,) int32 tensor on %s" % dev)
+            if order is not None and order is not True:
+                order = self._order_torch(torch, order, n, dev)
+            qs, cur = self._device_stream(torch, stream)
+            if qs != cur:
+                qs.wait_stream(cur)
+            ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
+            with torch.cuda.stream(qs):
+                qt = queries.contiguous()
+                if order is True:
+                    unit = qt.clone()
+                    unit[:, 3] = 1                                               # (the radii take no part in the order, and q = 0 is no sphere)
+                    order = self.sphere_order(unit, stream=qs)
+                ex = None if exclude is None else exclude.contiguous()
+                total = torch.zeros((), dtype=torch.int64, device=dev)
+                off = torch.empty(n + 1, dtype=torch.int64, device=dev) if offsets else None
+                counted = capacity is None
+                if counted:
+                    capi.check(capi.lib.rt_overlap_spheres_device(self._h, ptr(qt), n, margin, ptr(ex), ptr(order), 0, None, None, None, ptr(total), None,
+                                                                  C.c_void_p(qs.cuda_stream)), "rt_overlap_spheres_device")
+                    capacity = int(total.item())
+                    if capacity > 0x7FFFFFFF:
+                        raise ValueError("the queries have %d entries, more than one call can list: pass a capacity" % capacity)
+                items = torch.empty(capacity, dtype=torch.int32, device=dev)
+                gap = torch.empty(capacity, dtype=tdt, device=dev) if gaps else None
+                rc = capi.lib.rt_overlap_spheres_device(self._h, ptr(qt), n, margin, ptr(ex), ptr(order), capacity, ptr(items) if capacity else None,
+                                                        ptr(gap) if capacity else None, ptr(off), ptr(total), stp, C.c_void_p(qs.cuda_stream))
+            if qs != cur:
+                for x in (queries, qt, exclude, ex, order):
+                    if isinstance(x, torch.Tensor) and x.is_cuda:
+                        x.record_stream(qs)
+            capi.check(rc, "rt_overlap_spheres_device")
+            total = int(total.item()) if counted else total
+        else:
+            if not isinstance(queries, np.ndarray) or queries.dtype != R or queries.ndim != 2 or queries.shape[1] != 4 or queries.shape[0] == 0:
+                raise ValueError("queries must be a non-empty (n, 4) numpy array of %s (or a torch tensor on the scene's device)" % np.dtype(R).name)
+            n = queries.shape[0]
+            qa = np.ascontiguousarray(queries)
+            ex = None
+            if exclude is not None:
+                ex = np.asarray(exclude)
+                if ex.dtype != np.int32 or ex.shape != (n,):
+                    raise ValueError("exclude must be None or an (n,) int32 array")
+                ex = np.ascontiguousarray(ex)
+            o = None
+            if order is True:
+                unit = qa.copy()
+                unit[:, 3] = 1                                                   # (the radii take no part in the order, and q = 0 is no sphere)
+                o = self.sphere_order(unit)
+            elif order is not None:
+                o = self._order_numpy(order, n)
+            total = C.c_uint64(0)
+            off = np.empty(n + 1, dtype=np.uint64) if offsets else None
+            ptr = lambda x: None if x is None else x.ctypes.data
+            if capacity is None:
+                capi.check(capi.lib.rt_overlap_spheres(self._h, ptr(qa), n, margin, ptr(ex), ptr(o), 0, None, None, None, C.byref(total), None), "rt_overlap_spheres")
+                capacity = int(total.value)
+                if capacity > 0x7FFFFFFF:
+                    raise ValueError("the queries have %d entries, more than one call can list: pass a capacity" % capacity)
+            items = np.empty(capacity, dtype=np.int32)
+            gap = np.empty(capacity, dtype=R) if gaps else None
+            capi.check(capi.lib.rt_overlap_spheres(self._h, ptr(qa), n, margin, ptr(ex), ptr(o), capacity, ptr(items) if capacity else None,
+                                                   ptr(gap) if capacity else None, ptr(off), C.byref(total), stp), "rt_overlap_spheres")
+            total = int(total.value)
+            m = min(capacity, total)
+            items, gap = items[:m], (gap[:m] if gaps else None)
+        res = (items,) + ((gap,) if gaps else ()) + ((off,) if offsets else ()) + (total,)
         return res + ((st.as_dict(),) if stats else ())
 
     @staticmethod
