@@ -750,9 +750,10 @@ int rt_abi_version(void);
  *   RT_LAUNCH_ORDERED          blocks dispatched most-expensive-first from the scene's cost map (else: through the tile table)
  *   RT_LAUNCH_FLAT_PIPELINE    RT_TRAVERSAL_FLAT's wavefront pipeline
  *   RT_LAUNCH_COUNTING         the counting flavour of the kernels (the call asked for rt_stats)
- *   RT_LAUNCH_FAST_KERNEL      the single-pass kernel of steady-state frames (f32, one sample per pixel, ordered: k_render_skip_fast) */
+ *   RT_LAUNCH_FAST_KERNEL      the single-pass kernel of steady-state frames (f32, one sample per pixel, ordered: k_render_skip_fast)
+ *   RT_LAUNCH_TIGHT_BOUNDS     the walk read the scene's tight streams: bounds shrunk around their items at no change to any byte */
 enum { RT_LAUNCH_TWO_RAYS = 1u, RT_LAUNCH_COOPERATIVE = 2u, RT_LAUNCH_SAMPLE_PARALLEL = 4u, RT_LAUNCH_ORDERED = 8u, RT_LAUNCH_FLAT_PIPELINE = 16u,
-       RT_LAUNCH_COUNTING = 32u, RT_LAUNCH_FAST_KERNEL = 64u };
+       RT_LAUNCH_COUNTING = 32u, RT_LAUNCH_FAST_KERNEL = 64u, RT_LAUNCH_TIGHT_BOUNDS = 128u };
 uint32_t rt_last_launch_flags(void);
 
 /* The toolchain this library was built with, e.g. "hipcc: HIP version: 7.2.x ... | clang ... | kernels <sha1 of the kernel sources>"

@@ -45,7 +45,7 @@ SYMBOLS = ("rt_abi_version", "rt_build_hierarchy", "rt_device_count", "rt_scene_
            "rt_scene_contacts", "rt_scene_contacts_device", "rt_overlap_spheres", "rt_overlap_spheres_device")
 # csrc/rt_debug.h: only in the -DRT_TEST_HOOKS build
 DEBUG_SYMBOLS = ("rt_debug_set", "rt_debug_count", "rt_debug_wave_trace", "rt_debug_flat_filter_check", "rt_debug_gang_layout", "rt_debug_rccl_library",
-                 "rt_debug_shard_costs")
+                 "rt_debug_shard_costs", "rt_debug_tight_bounds")
 
 
 class Options(C.Structure):      # rt_options / RenderOptions render.rs:33-38
@@ -182,6 +182,7 @@ lib.rt_last_error_message.restype = C.c_char_p
 lib.rt_last_launch_flags.restype = C.c_uint32
 lib.rt_build_info.restype = C.c_char_p
 RT_LAUNCH_TWO_RAYS, RT_LAUNCH_COOPERATIVE, RT_LAUNCH_SAMPLE_PARALLEL, RT_LAUNCH_ORDERED, RT_LAUNCH_FLAT_PIPELINE, RT_LAUNCH_COUNTING, RT_LAUNCH_FAST_KERNEL = 1, 2, 4, 8, 16, 32, 64
+RT_LAUNCH_TIGHT_BOUNDS = 128
 HAVE_TEST_HOOKS = hasattr(lib, "rt_debug_set")
 
 if lib.rt_abi_version() != ABI_VERSION:
@@ -206,7 +207,8 @@ def last_launch():
     """rt_last_launch_flags of the calling thread as a set of names."""
     f = lib.rt_last_launch_flags()
     names = (("two_rays", RT_LAUNCH_TWO_RAYS), ("cooperative", RT_LAUNCH_COOPERATIVE), ("sample_parallel", RT_LAUNCH_SAMPLE_PARALLEL),
-             ("ordered", RT_LAUNCH_ORDERED), ("flat_pipeline", RT_LAUNCH_FLAT_PIPELINE), ("counting", RT_LAUNCH_COUNTING), ("fast_kernel", RT_LAUNCH_FAST_KERNEL))
+             ("ordered", RT_LAUNCH_ORDERED), ("flat_pipeline", RT_LAUNCH_FLAT_PIPELINE), ("counting", RT_LAUNCH_COUNTING), ("fast_kernel", RT_LAUNCH_FAST_KERNEL),
+             ("tight_bounds", RT_LAUNCH_TIGHT_BOUNDS))
     return {n for n, bit in names if f & bit}
 
 
@@ -258,7 +260,7 @@ def selftest_rcp(device=0):
 (DEBUG_SKIP_VARIANT, DEBUG_BLOCK_ORDER, DEBUG_NARROW_MAX, DEBUG_PACKED_SAMPLES, DEBUG_PRINT_STEPS, DEBUG_PRINT_COSTS,
  DEBUG_HOST_COPY, DEBUG_COALESCE, DEBUG_LDS_BYTES, DEBUG_WG_POLICY, DEBUG_NARROW_L2, DEBUG_FLAT_KERNELS, DEBUG_SKIP_RAYS,
  DEBUG_FRAME_AHEAD, DEBUG_FILTER_RO_PERCENT, DEBUG_COOP, DEBUG_COOP_THR, DEBUG_COOP_MAX, DEBUG_COOP_LEVEL, DEBUG_COOP_REST, DEBUG_ASYNC_ORDERS,
- DEBUG_FAST_KERNEL, DEBUG_EXACT_COSTS, DEBUG_MULTIHIT_BUCKET) = range(24)
+ DEBUG_FAST_KERNEL, DEBUG_EXACT_COSTS, DEBUG_MULTIHIT_BUCKET, DEBUG_TIGHT_BOUNDS) = range(25)
 if HAVE_TEST_HOOKS:
     lib.rt_debug_set.argtypes = [C.c_int, C.c_longlong]
     lib.rt_debug_wave_trace.argtypes = [C.c_char_p]
@@ -268,6 +270,7 @@ if HAVE_TEST_HOOKS:
     lib.rt_debug_gang_layout.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
     lib.rt_debug_shard_costs.argtypes = [C.c_void_p, C.POINTER(Options), C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     lib.rt_debug_rccl_library.argtypes = [C.c_char_p]
+    lib.rt_debug_tight_bounds.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
 
 
 def _need_hooks(what):
@@ -281,7 +284,7 @@ def debug_count(counter):
     _need_hooks("rt_debug_count")
     return lib.rt_debug_count(counter)
 (DEBUG_COUNT_REGION_CALLS, DEBUG_COUNT_REGION_PASSES, DEBUG_COUNT_FILTER_PASS, DEBUG_COUNT_FILTER_VIOLATIONS, DEBUG_COUNT_PRIMARY_TESTS,
- DEBUG_COUNT_FRAME_AHEAD_PASSES, DEBUG_COUNT_TWO_RAY_LAUNCHES, DEBUG_COUNT_COOP_LAUNCHES) = range(8)
+ DEBUG_COUNT_FRAME_AHEAD_PASSES, DEBUG_COUNT_TWO_RAY_LAUNCHES, DEBUG_COUNT_COOP_LAUNCHES, DEBUG_COUNT_TIGHT_VIOLATIONS) = range(9)
 
 
 def debug_set(key, value=-1):
@@ -309,6 +312,24 @@ def flat_filter_check(scene_handle, width, height, spp):
     check(lib.rt_debug_flat_filter_check(scene_handle, width, height, spp, C.byref(counts)), "rt_debug_flat_filter_check")
     return tuple(int(c) for c in counts)
 
+
+
+def tight_bounds(items, light_unit, eye, bounds, ranges):
+    """rt_debug_tight_bounds (no device needed) -> (float32[n_bounds, 4] spheres of the tight streams, uint8[n_bounds] 1 where tight,
+    {S, eta, volume_ratio, by_rule, rule: 0 never / 1 every launch that can / 2 large one-sample passes only})."""
+    import numpy as np
+    _need_hooks("rt_debug_tight_bounds")
+    items = np.ascontiguousarray(items, dtype=np.float32).reshape(-1, 4)
+    bounds = np.ascontiguousarray(bounds, dtype=np.float32).reshape(-1, 4)
+    light = np.ascontiguousarray(light_unit, dtype=np.float32)
+    eye = np.ascontiguousarray(eye, dtype=np.float32)
+    arr = (Range * len(ranges))(*[Range(int(f), int(c)) for f, c in ranges])
+    out = np.zeros((len(bounds), 4), dtype=np.float32)
+    tight = np.zeros(len(bounds), dtype=np.uint8)
+    consts = np.zeros(4, dtype=np.float64)
+    check(lib.rt_debug_tight_bounds(items.ctypes.data, len(items), light.ctypes.data, eye.ctypes.data, bounds.ctypes.data, arr, len(bounds),
+                                    out.ctypes.data, tight.ctypes.data, consts.ctypes.data), "rt_debug_tight_bounds")
+    return out, tight, {"S": consts[0], "eta": consts[1], "volume_ratio": consts[2], "by_rule": bool(consts[3]), "rule": int(consts[3])}
 
 
 def gang_layout(regions, n_devices):

@@ -180,6 +180,17 @@ struct rt_scene {
     rt::FilterConsts fc{};
     void *d_fc = nullptr;          // device copy of fc
     uint32_t n_nodes = 0, n_fnodes = 0;
+    // TIGHT streams (f32 scenes from rt_scene_create; rt_tight.hpp): the plain streams once more with every BOUND that qualifies
+    // carrying a smaller sphere around its subtree's items, and their FNode copies -- what the un-fused filtered loops walk where walks_tight
+    // (rt_capi_launch.hpp) says so.  Made once, by the scene's worker next to the cost map (ensure_tight); ONE allocation.
+    std::vector<rt::RawNode<float>> raw_given;     // the given raw stream, kept for that day
+    double fc_rc = 0.0;                            // max |centre - m0| over the given nodes (filter_constants)
+    std::mutex tight_mu;
+    bool tight_tried = false;
+    int tight_by_rule = 0;                         // tight_rule: 0 never, 1 every launch that can, 2 large one-sample passes only
+    std::atomic<bool> tight_ready{ false };
+    void *d_tight = nullptr, *d_tprim = nullptr, *d_tshad = nullptr, *d_txprim = nullptr, *d_txshad = nullptr;
+    uint32_t n_tight = 0;
     bool fused = false;            // every BOUND is followed by an ITEM with the same centre (rt_skip.hpp, Node)
     // the hierarchy once more in sibling-contiguous order for the lane-cooperative walk (rt_coop.hpp; f64: CNode64); coop.fanout == 0: none
     void *d_coop_prim = nullptr, *d_coop_shad = nullptr;
@@ -212,6 +223,7 @@ struct rt_scene {
                    // (slot = count % kOrderTrialSamples; a sample whose events could not be read is LOST and issued again)
                    hipEvent_t e0[3] = { nullptr, nullptr, nullptr }, e1[3] = { nullptr, nullptr, nullptr }; int issued = 0, harvested = 0, good = 0; float best_ms = 1e30f; };
     struct CachedTable { std::vector<rt::TileDev> host; unsigned w = 0, h = 0, passes = 0; rt::TileDev *dev = nullptr; std::vector<Order> orders; int chosen = 0; unsigned turn = 0; bool building = false;
+                         bool retrial = false;             // the scene's tight streams arrived after this list's trial had begun: time the orders once more (pick_order)
                          void *order_arena = nullptr;      // ONE device allocation holds every order's arrays (allocation calls wait for a busy device)
                          long long coop_key = 0;
                          // a table uploaded asynchronously on its first caller's stream (device_table): until `landed` has completed, launches on
@@ -305,6 +317,8 @@ struct rt_scene {
     uint64_t *h_overlap_total = nullptr, *d_overlap_total = nullptr;        // one pinned word and its device alias, as h_contacts_total
     bool overlap_recorded = false;
 };
+
+#include "rt_tight.hpp"
 
 namespace {
 #include "rt_capi_scene.hpp"

@@ -458,9 +458,7 @@ rt::BlockList pick_order(rt_scene::CachedTable &t, bool will_be_timed)      // w
         l.plain_d = t.orders[0].dev_order; l.plain_n = t.orders[0].n_order; l.plain_wg_first = t.orders[0].dev_wg; l.plain_n_wg = t.orders[0].n_wg;
         return l;
     };
-    if (t.chosen >= 0) return list_of(t.orders[(size_t)t.chosen]);
-    bool all_done = true;
-    for (auto &od : t.orders) {
+    auto harvest = [](rt_scene::Order &od) {
         while (od.harvested < od.issued && hipEventQuery(od.e1[od.harvested % kOrderTrialSamples]) == hipSuccess) {
             float ms = 0.f;
             const int slot = od.harvested % kOrderTrialSamples;
@@ -468,6 +466,21 @@ rt::BlockList pick_order(rt_scene::CachedTable &t, bool will_be_timed)      // w
             ++od.harvested;
         }
         (void)hipGetLastError();                         // hipErrorNotReady is not an error here
+    };
+    if (t.retrial) {
+        // the launches of this list walk other streams now than the ones its orders were timed on (build_orders_async): once no timed launch
+        // is in flight any more, the trial starts again from nothing
+        bool idle = true;
+        for (auto &od : t.orders) { harvest(od); idle = idle && od.harvested >= od.issued; }
+        if (idle) {
+            for (auto &od : t.orders) { od.issued = od.harvested = od.good = 0; od.best_ms = 1e30f; }
+            t.chosen = -1; t.retrial = false;
+        }
+    }
+    if (t.chosen >= 0) return list_of(t.orders[(size_t)t.chosen]);
+    bool all_done = true;
+    for (auto &od : t.orders) {
+        harvest(od);
         all_done = all_done && od.good >= kOrderTrialSamples;
     }
     auto best_known = [&t] {
@@ -701,10 +714,22 @@ void build_orders_async(rt_scene *s, size_t index, std::vector<rt::TileDev> tab,
         ok = build_orders(s, map, tab, w, h, passes, orders, chosen, &arena) == RT_OK;
     }
     (void)hipGetLastError();
-    std::lock_guard<std::mutex> lk(s->mu);
-    rt_scene::CachedTable &t = s->tables[index];
-    if (ok) { t.orders = std::move(orders); t.chosen = chosen; t.order_arena = arena; }
-    t.building = false;
+    {
+        std::lock_guard<std::mutex> lk(s->mu);
+        rt_scene::CachedTable &t = s->tables[index];
+        if (ok) { t.orders = std::move(orders); t.chosen = chosen; t.order_arena = arena; }
+        t.building = false;
+    }
+    // The tight streams (rt_capi_scene.hpp ensure_tight) behind the orders -- those are what the caller's next frames wait for, and a deep
+    // scene's tight spheres take the host a few tenths of a second.  Lists whose orders are being tried, or were, on the given streams are
+    // tried once more on the streams their frames walk from now on.
+    const bool had = s->tight_ready.load(std::memory_order_acquire);
+    if (ok && !had && ensure_tight(s) && s->tight_by_rule) {
+        std::lock_guard<std::mutex> lk(s->mu);
+        for (auto &t : s->tables)
+            if (t.orders.size() > 1 && t.orders[0].e0[0]) t.retrial = true;
+    }
+    (void)hipGetLastError();
 }
 
 rt_status device_table(rt_scene *s, Context *c, const std::vector<rt::TileDev> &tab, hipStream_t stream, const rt::TileDev **out, int slot,
@@ -770,6 +795,8 @@ rt_status device_table(rt_scene *s, Context *c, const std::vector<rt::TileDev> &
                 rt_status bst = build_orders(s, map, tab, w, h, passes, t.orders, t.chosen, &t.order_arena);
                 clk.lap("dispatch orders");
                 if (bst != RT_OK) { drop(); return bst; }
+                (void)ensure_tight(s);
+                clk.lap("tight streams (1st list only)");
             }
             // The copies above are blocking for the host, but the render kernel runs on another (non-blocking) stream: make sure
             // the tables have landed in device memory before anything can be launched against them (once per tile list).

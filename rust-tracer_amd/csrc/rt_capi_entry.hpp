@@ -200,6 +200,41 @@ static rt_status scene_items_ok(const char *what, rt_precision precision, const 
     return RT_OK;
 }
 
+#ifdef RT_TEST_HOOKS
+// Test infrastructure (csrc/rt_debug.h): the tight spheres rt_scene_create's scene would get (rt_tight.hpp), on the host alone.
+rt_status rt_debug_tight_bounds(const float *dfs_items, uint32_t n_items, const float *light_unit, const float *eye, const float *bounds, const rt_range *ranges,
+                                uint32_t n_bounds, float *spheres_out, uint8_t *tight_out, double consts_out[4])
+{
+    rt_scene *none = nullptr;
+    if (rt_status ast = scene_items_ok("rt_debug_tight_bounds", RT_F32, dfs_items, n_items, light_unit, eye, bounds, ranges, n_bounds, false, &none); ast != RT_OK) return ast;
+    if (!n_bounds || !spheres_out || !tight_out) { snprintf(g_err, sizeof g_err, "rt_debug_tight_bounds: no bounds or no output"); return RT_ERR_INVALID_ARGUMENT; }
+    std::unique_ptr<rt_scene> s(new (std::nothrow) rt_scene());      // (host fields only: nothing of it ever reaches a device)
+    if (!s) return RT_ERR_OUT_OF_MEMORY;
+    s->precision = RT_F32; s->n_items = n_items; s->n_bounds = n_bounds;
+    if (rt_status vst = scene_view_ok("rt_debug_tight_bounds", s.get(), light_unit, eye); vst != RT_OK) return vst;
+    std::vector<rt::RawNode<float>> raw;
+    if (rt_status st = build_raw_stream<float>(dfs_items, n_items, bounds, ranges, n_bounds, raw); st != RT_OK) return st;
+    filter_constants<float>(s.get(), raw, dfs_items);
+    rt_tight::Result tr;
+    tight_spheres_of(s.get(), raw, tr);
+    memcpy(spheres_out, bounds, sizeof(float) * 4 * n_bounds);
+    memset(tight_out, 0, n_bounds);
+    uint32_t b = 0;
+    for (size_t i = 0; i < raw.size(); ++i) {
+        if (raw[i].skip == 0u) continue;
+        while (b < n_bounds && ranges[b].count == 0) ++b;                // (groups without items have no node)
+        if (b >= n_bounds) break;
+        memcpy(spheres_out + 4 * b, &tr.sphere[4 * i], sizeof(float) * 4);
+        tight_out[b++] = tr.tight[i];
+    }
+    if (consts_out) {
+        const rt_tight::Params p = tight_params(s.get());
+        consts_out[0] = p.S; consts_out[1] = p.eta; consts_out[2] = tr.volume_ratio; consts_out[3] = (double)tight_rule(tr, raw_is_fused<float>(raw));
+    }
+    return RT_OK;
+}
+#endif  // RT_TEST_HOOKS
+
 rt_status rt_scene_create(int device, rt_precision precision, const void *dfs_items, uint32_t n_items,
                           const void *light_unit, const void *eye, const void *bounds, const rt_range *ranges,
                           uint32_t n_bounds, rt_scene **out)
@@ -309,7 +344,7 @@ rt_status rt_scene_destroy(rt_scene *s)
     if (s->h_overlap_total) (void)hipHostFree(s->h_overlap_total);
     if (s->d_cprim) (void)hipFree(s->d_cprim);
     if (s->d_cshad) (void)hipFree(s->d_cshad);
-    for (void *p : { s->d_xprim, s->d_xshad, s->d_xcprim, s->d_xcshad, s->d_xown, s->d_fc, s->d_coop_prim, s->d_coop_shad, s->d_cost_arena }) if (p) (void)hipFree(p);
+    for (void *p : { s->d_xprim, s->d_xshad, s->d_xcprim, s->d_xcshad, s->d_xown, s->d_fc, s->d_coop_prim, s->d_coop_shad, s->d_cost_arena, s->d_tight }) if (p) (void)hipFree(p);
     if (s->cost_stream) { (void)hipStreamSynchronize(s->cost_stream); (void)hipStreamDestroy(s->cost_stream); }
     if (s->h_cost) (void)hipHostFree(s->h_cost);
     if (s->h_up) (void)hipHostFree(s->h_up);

@@ -150,10 +150,25 @@ rt::Fast2Args fast2_args(const rt_scene *s, const rt::BlockList &order, unsigned
     return a;
 }
 
+// Does this launch walk the scene's TIGHT streams (rt_tight.hpp)?  Launches of the filtered assembly loops of an f32 scene that neither
+// count nor take two rays per lane -- then the un-fused loops (VAR 19) over the tight streams, whatever the scene's own flavour is.
+// RT_DEBUG_TIGHT_BOUNDS: 0 never, 1 the rule, 2 wherever a scene has tight streams; default: the rule.  A question only: whoever wants the streams
+// made at the launch (the control at 1 or 2: tests, tools) calls ensure_tight first -- launch_render does.
+bool walks_tight(const rt_scene *s, int v, uint64_t total_px, unsigned spp)
+{
+    const long long tb = knob(RT_DEBUG_TIGHT_BOUNDS);
+    if (tb == 0 || s->precision != RT_F32 || s->dynamic || ((v & ~8) != 19 && (v & ~8) != 23)) return false;
+    if (!s->tight_ready.load(std::memory_order_acquire)) return false;
+    if (tb != 2 && (s->tight_by_rule == 0 || (s->tight_by_rule == 2 && !(spp == 1 && total_px >= kTightPartialMinPx)))) return false;
+    const long long k = knob(RT_DEBUG_SKIP_RAYS);      // the two-ray kernels keep the given streams: launch_skip_one's question, asked first
+    const bool two_rays = (k < 0 ? skip2_by_default(total_px, spp, (v & 4) ? s->n_fnodes : s->n_nodes) : k == 2) && (spp == 1 || (use_split(spp) && packed_samples(spp)));
+    return !two_rays;
+}
+
 template <typename T, bool COUNT, int VAR>
 rt_status launch_skip_one(const rt_scene *s, Context *c, dim3 grid, hipStream_t stream, unsigned w, unsigned h, unsigned spp,
                           const rt::TileDev *d_tab, unsigned nt, uint64_t total_px, uint8_t *d_out, rt::Counters *cnt, unsigned frame_w,
-                          rt::BlockList order)
+                          rt::BlockList order, [[maybe_unused]] bool tight = false)
 {
     // two rays per lane (rt_skip2.hpp): f32, fused assembly loops, launches that neither count nor trace
     bool two_rays = false;
@@ -162,7 +177,7 @@ rt_status launch_skip_one(const rt_scene *s, Context *c, dim3 grid, hipStream_t 
     if constexpr (kTwoRayFlavour) {
         const long long k = knob(RT_DEBUG_SKIP_RAYS);
         two_rays = k < 0 ? skip2_by_default(total_px, spp, (VAR & 4) ? s->n_fnodes : s->n_nodes) : k == 2;
-        two_rays = two_rays && (spp == 1 || (use_split(spp) && packed_samples(spp)));
+        two_rays = two_rays && (spp == 1 || (use_split(spp) && packed_samples(spp))) && !tight;      // (walks_tight has asked the same question)
     }
     // an order with cooperative quads needs the COOP flavour of k_render_skip: everything else renders the plain order of the same list
     constexpr bool kCoopFlavour = !COUNT && (VAR == 19 || VAR == 23 || VAR == 31);       // (f32, and since round 6 f64: the filtered assembly loops)
@@ -227,7 +242,7 @@ rt_status launch_skip_one(const rt_scene *s, Context *c, dim3 grid, hipStream_t 
             const long long fk = knob(RT_DEBUG_FAST_KERNEL);
             if (spp == 1 && order.d && !order.wg_first && lds == 0 && fk != 0 && (order.holes || fk == 2)) {
                 rt::FastArgs fa{};
-                const rt::SkipView<float> sv = skip_view_of<float>(s);
+                const rt::SkipView<float> sv = skip_view_of<float>(s, tight);
                 constexpr bool kFused = (VAR & 4) != 0;
                 fa.order = order.d;
                 fa.walk_prim = kFused ? sv.xfprim : sv.xprim;
@@ -275,16 +290,16 @@ rt_status launch_skip_one(const rt_scene *s, Context *c, dim3 grid, hipStream_t 
             if (spp == 1 && order.d && order.holes && !order.wg_first) {        // some quads of the pass are walked cooperatively (rt_coop.hpp)
                 count_event(RT_DEBUG_COUNT_COOP_LAUNCHES); g_launch_flags |= RT_LAUNCH_COOPERATIVE;
                 hipLaunchKernelGGL((skip_kernel<T, COUNT, VAR, rt::kSkipOne, true>()), rgrid, b, lds, stream, 
-                                   skip_args<T>(s, order.d, order.wg_first, w, h, frame_w, d_out, d_tab, nt, spp, cnt, no_cost, sb, s->coop, order.holes, order.n_holes));
+                                   skip_args_of<T>(s, tight, order.d, order.wg_first, w, h, frame_w, d_out, d_tab, nt, spp, cnt, no_cost, sb, s->coop, order.holes, order.n_holes));
                 return RT_OK;
             }
         }
         if (spp == 1)
             hipLaunchKernelGGL((skip_kernel<T, COUNT, VAR, rt::kSkipOne>()), rgrid, b, lds, stream, 
-                               skip_args<T>(s, order.d, order.wg_first, w, h, frame_w, d_out, d_tab, nt, spp, cnt, no_cost, sb));
+                               skip_args_of<T>(s, tight, order.d, order.wg_first, w, h, frame_w, d_out, d_tab, nt, spp, cnt, no_cost, sb));
         else
             hipLaunchKernelGGL((skip_kernel<T, COUNT, VAR, rt::kSkipLoop>()), rgrid, b, lds, stream, 
-                               skip_args<T>(s, order.d, order.wg_first, w, h, frame_w, d_out, d_tab, nt, spp, cnt, no_cost, sb));
+                               skip_args_of<T>(s, tight, order.d, order.wg_first, w, h, frame_w, d_out, d_tab, nt, spp, cnt, no_cost, sb));
         return RT_OK;
     }
     const size_t ns = (size_t)spp * spp;
@@ -321,10 +336,10 @@ rt_status launch_skip_one(const rt_scene *s, Context *c, dim3 grid, hipStream_t 
     if (done2) {
     } else if (packed)
         hipLaunchKernelGGL((skip_kernel<T, COUNT, VAR, rt::kSkipPacked>()), dim3(rgrid.x, (unsigned)ns), b, lds, stream, 
-                           skip_args<T>(s, order.d, order.wg_first, w, h, frame_w, d_out, d_tab, nt, spp, cnt, no_cost, sb));
+                           skip_args_of<T>(s, tight, order.d, order.wg_first, w, h, frame_w, d_out, d_tab, nt, spp, cnt, no_cost, sb));
     else
         hipLaunchKernelGGL((skip_kernel<T, COUNT, VAR, rt::kSkipSplit>()), dim3(rgrid.x, (unsigned)ns), b, lds, stream, 
-                           skip_args<T>(s, order.d, order.wg_first, w, h, frame_w, d_out, d_tab, nt, spp, cnt, no_cost, sb));
+                           skip_args_of<T>(s, tight, order.d, order.wg_first, w, h, frame_w, d_out, d_tab, nt, spp, cnt, no_cost, sb));
     HIP_TRY(hipGetLastError());
     if constexpr (sizeof(T) == 4) {
         if (packed) {        // one word per sample, [pixel][sample] (rt_kernels.hpp sample_word)
@@ -352,6 +367,15 @@ rt_status launch_skip_var(const rt_scene *s, Context *c, dim3 grid, hipStream_t 
 #endif
         return launch_skip_one<T, true, 1>(s, c, grid, stream, w, h, spp, d_tab, nt, total_px, d_out, cnt, frame_w, order);
     } else {
+        if constexpr (sizeof(T) == 4) {
+            if (walks_tight(s, v, total_px, spp)) {
+                g_launch_flags |= RT_LAUNCH_TIGHT_BOUNDS;
+#ifdef RT_TEST_HOOKS
+                if (v & 8) return launch_skip_one<T, false, 27>(s, c, grid, stream, w, h, spp, d_tab, nt, total_px, d_out, cnt, frame_w, order, true);
+#endif
+                return launch_skip_one<T, false, 19>(s, c, grid, stream, w, h, spp, d_tab, nt, total_px, d_out, cnt, frame_w, order, true);
+            }
+        }
         switch (v) {
         // what a scene gets by itself: the filtered assembly loops, fused where the scene is concentric (f64 scenes too large for the
         // filter streams' 32-bit offsets: the unfiltered ones)
@@ -436,6 +460,8 @@ rt_status launch_render(rt_scene *s, Context *c, const rt_options *o, rt_travers
 {
     const dim3 grid(total_blocks);
     const unsigned w = o->width, h = o->height, spp = o->samples_per_pixel;
+    // RT_DEBUG_TIGHT_BOUNDS 1 / 2 (tests, tools): the tight streams are made here and now if the scene's worker has not made them yet
+    if (trav == RT_TRAVERSAL_SKIP && !cnt && knob(RT_DEBUG_TIGHT_BOUNDS) >= 1) (void)ensure_tight(s);
     if (spp == 0) {
         // render.rs:219-250 with no sample to take: 0 * inf = NaN in every channel, and `NaN as u8` is 0 (set_pixel_from_vector, render.rs:96-108)
         g_launch_flags = cnt ? RT_LAUNCH_COUNTING : 0u;
@@ -510,9 +536,12 @@ rt_status read_stats(rt_scene *s, Context *c, hipStream_t stream, rt_traversal t
         h.max_wave_ref100mhz = std::max(h.max_wave_ref100mhz, k.max_wave_ref100mhz);
         h.wave_item_steps += k.wave_item_steps;
         h.filter_pass += k.filter_pass; h.filter_violations += k.filter_violations; h.primary_tests += k.primary_tests;
+        h.tight_violations += k.tight_violations;
     }
     count_event(RT_DEBUG_COUNT_FILTER_PASS, (long long)h.filter_pass);
-    count_event(RT_DEBUG_COUNT_FILTER_VIOLATIONS, (long long)h.filter_violations);
+    // (a tight-stream violation is a bound's verdict violated like the others: it counts there too, so that whoever asserts that counter asserts this one)
+    count_event(RT_DEBUG_COUNT_FILTER_VIOLATIONS, (long long)(h.filter_violations + h.tight_violations));
+    count_event(RT_DEBUG_COUNT_TIGHT_VIOLATIONS, (long long)h.tight_violations);
     count_store(RT_DEBUG_COUNT_PRIMARY_TESTS, (long long)h.primary_tests);
     float ms = 0.f;
     HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));

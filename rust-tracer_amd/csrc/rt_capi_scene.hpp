@@ -230,12 +230,13 @@ rt::FlatScView flat_sc_view_of(const rt_scene *s)
     return v;
 }
 
+// tight: the tight streams in the places of the plain ones (f32 scenes whose tight_ready is set; the un-fused loops only)
 template <typename T>
-rt::SkipView<T> skip_view_of(const rt_scene *s)
+rt::SkipView<T> skip_view_of(const rt_scene *s, bool tight = false)
 {
     rt::SkipView<T> v;
-    v.prim = static_cast<const rt::Node<T> *>(s->d_prim);
-    v.shad = static_cast<const rt::Node<T> *>(s->d_shad);
+    v.prim = static_cast<const rt::Node<T> *>(tight ? s->d_tprim : s->d_prim);
+    v.shad = static_cast<const rt::Node<T> *>(tight ? s->d_tshad : s->d_shad);
     v.fprim = static_cast<const rt::Node<T> *>(s->d_cprim);
     v.fshad = static_cast<const rt::Node<T> *>(s->d_cshad);
     v.items = static_cast<const rt::Item<T> *>(s->d_items);
@@ -243,8 +244,8 @@ rt::SkipView<T> skip_view_of(const rt_scene *s)
     v.n_fnodes = s->n_fnodes;
     v.light = { (T)s->light[0], (T)s->light[1], (T)s->light[2] };
     v.eye = { (T)s->eye[0], (T)s->eye[1], (T)s->eye[2] };
-    v.xprim = static_cast<const rt::FNode *>(s->d_xprim);
-    v.xshad = static_cast<const rt::FNodeS *>(s->d_xshad);
+    v.xprim = static_cast<const rt::FNode *>(tight ? s->d_txprim : s->d_xprim);
+    v.xshad = static_cast<const rt::FNodeS *>(tight ? s->d_txshad : s->d_xshad);
     v.xfprim = static_cast<const rt::FNode *>(s->d_xcprim);
     v.xfshad = static_cast<const rt::FNodeS *>(s->d_xcshad);
     v.xown = static_cast<const uint32_t *>(s->d_xown);
@@ -254,15 +255,21 @@ rt::SkipView<T> skip_view_of(const rt_scene *s)
 
 // The one argument of the render kernels (rt_skip.hpp SkipArgs: what a wave needs first lies first).
 template <typename T>
-rt::SkipArgs<T> skip_args(const rt_scene *s, const rt::BlockDesc *order, const uint32_t *wg_first, unsigned w, unsigned h, unsigned frame_w, uint8_t *out,
-                          const rt::TileDev *tiles, unsigned n_tiles, unsigned spp, rt::Counters *counters, uint32_t *lane_cost, rt::SampleBuf<T> sb,
-                          rt::CoopView cv = rt::CoopView{}, const uint64_t *holes = nullptr, unsigned n_holes = 0)
+rt::SkipArgs<T> skip_args_of(const rt_scene *s, bool tight, const rt::BlockDesc *order, const uint32_t *wg_first, unsigned w, unsigned h, unsigned frame_w, uint8_t *out,
+                             const rt::TileDev *tiles, unsigned n_tiles, unsigned spp, rt::Counters *counters, uint32_t *lane_cost, rt::SampleBuf<T> sb,
+                             rt::CoopView cv = rt::CoopView{}, const uint64_t *holes = nullptr, unsigned n_holes = 0)
 {
     rt::SkipArgs<T> a{};
     a.order = order; a.wg_first = wg_first; a.width = w; a.height = h; a.frame_w = frame_w; a.out = out; a.tiles = tiles; a.n_tiles = n_tiles;
-    a.spp_arg = spp; a.sc = skip_view_of<T>(s); a.counters = counters; a.lane_cost = lane_cost; a.holes = holes; a.n_holes = n_holes; a.sb = sb; a.cv = cv;
+    a.spp_arg = spp; a.sc = skip_view_of<T>(s, tight); a.counters = counters; a.lane_cost = lane_cost; a.holes = holes; a.n_holes = n_holes; a.sb = sb; a.cv = cv;
+    // a counting launch walks the given streams and holds every ITEM test that counts against the tight ones, where the scene has them
+    if (counters && !tight && sizeof(T) == 4 && s->tight_ready.load(std::memory_order_acquire)) {
+        a.tprim = static_cast<const rt::Node<T> *>(s->d_tprim); a.tshad = static_cast<const rt::Node<T> *>(s->d_tshad);
+    }
     return a;
 }
+template <typename T, typename... A>
+rt::SkipArgs<T> skip_args(const rt_scene *s, const rt::BlockDesc *order, A... rest) { return skip_args_of<T>(s, false, order, rest...); }      // (the given streams)
 
 
 // Constants of the filtered loops' shadow bounds (rt_skip.hpp FilterConsts, shadow_filter_bounds; derivation in DESIGN.md 4.1).
@@ -304,6 +311,7 @@ void filter_constants(rt_scene *s, const std::vector<rt::RawNode<T>> &raw, const
     for (int k = 0; k < 3; ++k) { fc.e1[k] = (float)e1[k]; fc.e2[k] = (float)e2[k]; }
     for (int k = 0; k < 3; ++k) fc.l[k] = (float)l[k];
     fc.eta = std::fabs(l2 - 1.0);
+    s->fc_rc = rc;
     fc.S = (rc + ro * (1.0 + 4.0 * eps)) * (1.0 + 1e-9);
     auto up = [](double v) { float f = (float)v; if ((double)f < v) f = std::nextafterf(f, INFINITY); return std::nextafterf(f, INFINITY); };
     fc.a0 = up(11.0 * eps * fc.S + 1e-37);
@@ -397,6 +405,17 @@ rt_status derive_streams(const rt_scene *s, const std::vector<rt::RawNode<T>> &r
     return RT_OK;
 }
 
+// fused: every BOUND directly followed by an ITEM with the same centre, bit for bit (then the values v, b, b*b - vv a ray forms for the two are the same bits)
+template <typename T>
+bool raw_is_fused(const std::vector<rt::RawNode<T>> &raw)
+{
+    bool fused = !raw.empty();
+    for (size_t i = 0; fused && i < raw.size(); ++i)
+        if (raw[i].skip != 0u)
+            fused = i + 1 < raw.size() && raw[i + 1].skip == 0u && memcmp(&raw[i].cx, &raw[i + 1].cx, 3 * sizeof(T)) == 0;
+    return fused;
+}
+
 template <typename T> rt_status upload_coop(rt_scene *s, const std::vector<rt::RawNode<T>> &raw);
 
 template <typename T>
@@ -411,12 +430,7 @@ rt_status upload_streams(rt_scene *s, const void *items, const void *bounds, con
         return RT_ERR_UNSUPPORTED;
     }
     s->n_nodes = (uint32_t)raw.size();
-    // fused: every BOUND directly followed by an ITEM with the same centre, bit for bit (then the values v, b, b*b - vv a
-    // ray forms for the two are the same bits).
-    bool fused = !raw.empty();
-    for (size_t i = 0; fused && i < raw.size(); ++i)
-        if (raw[i].skip != 0u)
-            fused = i + 1 < raw.size() && raw[i + 1].skip == 0u && memcmp(&raw[i].cx, &raw[i + 1].cx, 3 * sizeof(T)) == 0;
+    const bool fused = raw_is_fused<T>(raw);
     s->fused = fused;
     StageClock clk;
     if ((st = derive_streams<T>(s, raw, false, &s->d_prim, &s->d_shad)) != RT_OK) return st;
@@ -480,8 +494,84 @@ rt_status upload_streams(rt_scene *s, const void *items, const void *bounds, con
         clk.lap("  streams: filtered");
         if ((st = upload_coop<T>(s, raw)) != RT_OK) return st;
         clk.lap("  streams: cooperative copy");
+        // (ensure_tight, on the worker: 36 bytes per node of host memory until the first tile list has its dispatch orders -- a scene that
+        // never renders through the hierarchy walk keeps them as it keeps h_items for the flat scan)
+        s->raw_given = std::move(raw);
     }
     return RT_OK;
+}
+
+// What rt_tight::build needs to know of an f32 scene whose filter constants are made.  S covers the eye as well as the shadow origins; eta the
+// primary directions (| |d|^2 - 1 | <= 16 eps) as well as the shadow direction.
+rt_tight::Params tight_params(const rt_scene *s)
+{
+    rt_tight::Params p{};
+    for (int k = 0; k < 3; ++k) { p.eye[k] = s->eye[k]; p.m0[k] = (double)s->fc.m0[k]; }
+    p.rc = s->fc_rc;
+    p.S = std::max(s->fc.S, (s->fc_rc + rt_tight::dist3(p.eye, p.m0)) * (1.0 + 1e-9));
+    p.eta = std::max(16.0 * rt_tight::kEps, s->fc.eta);
+    return p;
+}
+
+void tight_spheres_of(const rt_scene *s, const std::vector<rt::RawNode<float>> &raw, rt_tight::Result &out)
+{
+    std::vector<float> sph(4 * raw.size());
+    std::vector<uint32_t> skip(raw.size());
+    for (size_t i = 0; i < raw.size(); ++i) { sph[4 * i] = raw[i].cx; sph[4 * i + 1] = raw[i].cy; sph[4 * i + 2] = raw[i].cz; sph[4 * i + 3] = raw[i].r; skip[i] = raw[i].skip; }
+    rt_tight::build(sph.data(), skip.data(), (uint32_t)raw.size(), tight_params(s), out);
+}
+
+// The selection rule (measured: profiles/t01_rule.log).  0: the scene keeps its given streams -- no BOUND qualified, or the summed
+// volume of the bounds drops by less than a quarter (a guess on the safe side: no scene between 0.56 and 1 was measured; a hierarchy from
+// rt_build_hierarchy qualifies nowhere).  1: every launch that can walks the tight streams.  2: a FUSED scene on which fewer than nine in ten
+// bounds qualified gives up its compacted streams -- an ITEM step more for EVERY entered group -- for a gain on some groups only: the level-9
+// pyramid (a quarter qualify) measured 50.1 -> 41.3 us at 1080p and 30.9 -> 31.7 at 800x600, so such a scene walks them in one-sample passes of
+// a million pixels or more and nowhere else.
+constexpr double kTightVolumeRatio = 0.75;
+constexpr uint64_t kTightPartialMinPx = 1000000u;
+inline int tight_rule(const rt_tight::Result &tr, bool fused)
+{
+    if (tr.n_tight == 0 || !(tr.volume_ratio <= kTightVolumeRatio)) return 0;
+    return (!fused || (uint64_t)tr.n_tight * 10u >= (uint64_t)tr.n_bounds * 9u) ? 1 : 2;
+}
+// Makes the tight streams of an f32 scene (once; whoever comes first, normally the scene's worker behind the cost map).  true: they are there.
+bool ensure_tight(rt_scene *s)
+{
+    if (s->tight_ready.load(std::memory_order_acquire)) return true;
+    std::lock_guard<std::mutex> lk(s->tight_mu);
+    if (s->tight_tried) return s->tight_ready.load(std::memory_order_acquire);
+    s->tight_tried = true;
+    if (s->precision != RT_F32 || s->dynamic || s->raw_given.empty() || !s->d_fc) return false;
+    std::vector<rt::RawNode<float>> raw;
+    raw.swap(s->raw_given);
+    rt_tight::Result tr;
+    tight_spheres_of(s, raw, tr);
+    if (tr.n_tight == 0) return false;
+    for (size_t i = 0; i < raw.size(); ++i)
+        if (tr.tight[i]) { raw[i].cx = tr.sphere[4 * i]; raw[i].cy = tr.sphere[4 * i + 1]; raw[i].cz = tr.sphere[4 * i + 2]; raw[i].r = tr.sphere[4 * i + 3]; }
+    const size_t n = raw.size(), total = n + rt::kNodePad;
+    static_assert(sizeof(rt::Node<float>) == 32 && sizeof(rt::FNode) == 32 && sizeof(rt::FNodeS) == 32, "one block of 32-byte records");
+    char *d = nullptr;
+    if (hipMalloc(&d, 128 * total + sizeof(rt::RawNode<float>) * n) != hipSuccess) { (void)hipGetLastError(); return false; }
+    rt::RawNode<float> *d_raw = reinterpret_cast<rt::RawNode<float> *>(d + 128 * total);
+    hipError_t e = hipMemcpy(d_raw, raw.data(), sizeof(rt::RawNode<float>) * n, hipMemcpyHostToDevice);      // (blocking: in device memory when it returns)
+    if (e == hipSuccess) {
+        const rt::V3<float> eye = { (float)s->eye[0], (float)s->eye[1], (float)s->eye[2] };
+        rt::Node<float> *tp = reinterpret_cast<rt::Node<float> *>(d), *ts = reinterpret_cast<rt::Node<float> *>(d + 32 * total);
+        const dim3 grid((unsigned)((total + 255) / 256));
+        hipLaunchKernelGGL((rt::k_build_streams<float>), grid, dim3(256), 0, s->cost_stream, d_raw, (unsigned)n, eye, false, tp, ts);
+        hipLaunchKernelGGL(rt::k_build_fstreams, grid, dim3(256), 0, s->cost_stream, tp, ts, (unsigned)total, false, s->fc, reinterpret_cast<rt::FNode *>(d + 64 * total),
+                           reinterpret_cast<rt::FNodeS *>(d + 96 * total), static_cast<uint32_t *>(nullptr));
+        e = hipGetLastError();
+        const hipError_t se = hipStreamSynchronize(s->cost_stream);
+        if (e == hipSuccess) e = se;
+    }
+    if (e != hipSuccess) { (void)hipGetLastError(); (void)hipFree(d); return false; }
+    s->d_tight = d; s->d_tprim = d; s->d_tshad = d + 32 * total; s->d_txprim = d + 64 * total; s->d_txshad = d + 96 * total;
+    s->n_tight = tr.n_tight;
+    s->tight_by_rule = tight_rule(tr, s->fused);
+    s->tight_ready.store(true, std::memory_order_release);
+    return true;
 }
 
 // The lane-cooperative walk's copy of the hierarchy (rt_coop.hpp): the nodes of the plain stream in breadth-first order, so that the

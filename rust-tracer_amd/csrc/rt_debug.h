@@ -62,7 +62,10 @@ typedef enum rt_debug_key {
                                     blocks again at the frame's own resolution (rt_capi.hip exact_block_costs).  Default 1 (read when a tile list is first seen) */
     RT_DEBUG_MULTIHIT_BUCKET = 23, /* the list capacity of rt_intersect_rays_multi* and rt_near_spheres* (rt_multihit.hpp, rt_near.hpp: 1, 4, 8 or 16) when it is >= k; default (and any
                                     other value): the smallest one >= k.  Every capacity must give the same bytes */
-    RT_DEBUG_KEYS = 24
+    RT_DEBUG_TIGHT_BOUNDS = 24,  /* the tight streams of an f32 scene (rt_tight.hpp: BOUND nodes carry a smaller sphere around their subtree's items; the un-fused filtered
+                                    loops walk them): 0 never, 1 the library's rule, 2 wherever a scene has tight streams -- 1 and 2 make them at the launch if
+                                    the scene's worker has not yet; default: the rule, from the launch on that finds them made.  All must render the same bytes */
+    RT_DEBUG_KEYS = 25
 } rt_debug_key;
 
 /* value < 0 restores the default. */
@@ -79,7 +82,9 @@ typedef enum rt_debug_counter {
     RT_DEBUG_COUNT_FRAME_AHEAD_PASSES = 5,  /* whole-grid passes rendered for rt_render_region's frame-ahead */
     RT_DEBUG_COUNT_TWO_RAY_LAUNCHES = 6,    /* hierarchy-walk passes that ran k_render_skip2 (two rays per lane) instead of k_render_skip */
     RT_DEBUG_COUNT_COOP_LAUNCHES = 7,       /* hierarchy-walk passes whose launch carried cooperative quads (k_render_skip<..., COOP>) */
-    RT_DEBUG_COUNTERS = 8
+    RT_DEBUG_COUNT_TIGHT_VIOLATIONS = 8,    /* counting launches of an f32 scene that has tight streams: ITEM tests that counted where a tight bound would have put the
+                                               lane to sleep (also added to RT_DEBUG_COUNT_FILTER_VIOLATIONS): must stay 0 */
+    RT_DEBUG_COUNTERS = 9
 } rt_debug_counter;
 long long rt_debug_count(int counter);
 
@@ -92,6 +97,12 @@ rt_status rt_debug_wave_trace(const char *path);
  * counts = { pairs with disc >= 0, pairs with bound >= 0, pairs with disc >= 0 but bound < 0 } for the primary filter, then the same
  * three for the shadow filter on rays from a point of each primary ray towards the light: counts[2] and counts[5] must be 0. */
 rt_status rt_debug_flat_filter_check(rt_scene *scene, uint32_t width, uint32_t height, uint32_t spp, unsigned long long counts[6]);
+
+/* Test infrastructure for the tight streams (rt_tight.hpp), host only -- no device is looked for: the sphere every bound of an f32 scene with these
+ * arguments (rt_scene_create's) carries in the tight streams, spheres_out[4 * n_bounds], and whether it is a tight one (1) or the given one, bit
+ * for bit (0), tight_out[n_bounds].  consts_out (optional): { S, eta, summed-volume ratio tight / given, the selection rule's verdict: 0 never, 1 every launch that can, 2 one-sample passes of a million pixels or more }. */
+rt_status rt_debug_tight_bounds(const float *dfs_items, uint32_t n_items, const float *light_unit, const float *eye, const float *bounds, const rt_range *ranges,
+                                uint32_t n_bounds, float *spheres_out, uint8_t *tight_out, double consts_out[4]);
 
 /* Test infrastructure for the multi-GPU paths.  rt_debug_gang_layout: the sharding arithmetic of rt_gang_render_frame(s) without a
  * device -- for bucket i its device (i % n_devices) and its first pixel inside that device's tile-major shard; per device the pixels

@@ -100,6 +100,9 @@ struct Counters {          // same meaning as the reference-side ray statistics
     // the bound would have ruled out (must be 0: rt_debug_count(RT_DEBUG_COUNT_FILTER_VIOLATIONS))
     unsigned long long filter_pass, filter_violations;
     unsigned long long primary_tests;                         // SKIP: the part of sphere_tests + bound_tests made for primary rays
+    // SKIP, f32 scenes with tight streams, counting launches: ITEM tests that count (primary: a distance below hit.distance; shadow: a hit) at a
+    // stream position a tight BOUND (rt_tight.hpp) would have put the lane to sleep over (must be 0: RT_DEBUG_COUNT_TIGHT_VIOLATIONS)
+    unsigned long long tight_violations;
 };
 
 __device__ __forceinline__ unsigned long long wave_sum(unsigned v)

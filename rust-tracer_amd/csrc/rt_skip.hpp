@@ -422,6 +422,7 @@ template <typename T> struct SkipArgs {
     unsigned n_tiles, pad_;
     SkipView<T> sc;
     Counters *counters; uint32_t *lane_cost; const uint64_t *holes; unsigned n_holes; SampleBuf<T> sb; CoopView cv;
+    const Node<T> *tprim, *tshad;       // counting launches: the scene's TIGHT plain streams (rt_tight.hpp) to hold the walk against, or NULL
 };
 typedef unsigned rt_u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned rt_u32x4 __attribute__((ext_vector_type(4)));
@@ -462,7 +463,8 @@ __device__ __forceinline__ void render_skip_body(const BlockDesc *__restrict__ o
                                                  const TileDev *__restrict__ tiles, unsigned n_tiles, unsigned spp_arg,
                                                  Counters *__restrict__ counters, uint32_t *__restrict__ lane_cost,
                                                  const uint64_t *__restrict__ holes, unsigned n_holes, SampleBuf<T> sb, SkipView<T> sc, CoopView cv,
-                                                 [[maybe_unused]] unsigned long long r_entry)      // (wave trace: the wave's very first instruction)
+                                                 [[maybe_unused]] unsigned long long r_entry,      // (wave trace: the wave's very first instruction)
+                                                 [[maybe_unused]] const Node<T> *__restrict__ tprim = nullptr, [[maybe_unused]] const Node<T> *__restrict__ tshad = nullptr)
 {
     constexpr bool PACKED = MODE == kSkipPacked, SPLIT = MODE == kSkipSplit || PACKED, ONE = MODE == kSkipOne;
     static_assert(!COOP || (!COUNT && ONE && (VAR & 2) != 0 && (sizeof(T) == 4 || (VAR & 16) != 0)), "the cooperative walk serves spp-1 passes of the assembly loops (f64: the filtered ones)");
@@ -554,7 +556,7 @@ __device__ __forceinline__ void render_skip_body(const BlockDesc *__restrict__ o
     V3<T> g = { T(0.0), T(0.0), T(0.0) };
     T alpha = T(0.0);
     unsigned c_hits = 0, c_shadow = 0, c_occ = 0, c_items = 0, c_bounds = 0, c_steps = 0, c_isteps = 0;
-    [[maybe_unused]] unsigned c_fpass = 0, c_fviol = 0, c_ptotal = 0;
+    [[maybe_unused]] unsigned c_fpass = 0, c_fviol = 0, c_ptotal = 0, c_tviol = 0;
 
     const unsigned ss_first = SPLIT ? sample / spp : 0u, ss_last = SPLIT ? ss_first + 1 : spp;
     for (unsigned ssx = ss_first; ssx < ss_last; ++ssx) {
@@ -613,6 +615,9 @@ __device__ __forceinline__ void render_skip_body(const BlockDesc *__restrict__ o
                 }
             } else {
             Node<T> nd = sc.prim[0];                                    // wave-uniform record -> SGPRs
+            // (counting launches, tight streams: the stream position up to which a tight BOUND would have put this lane to sleep -- the walk
+            // itself stays on the given streams, so that its counters are the CPU path's)
+            [[maybe_unused]] unsigned tsleep = 0u;
             for (;;) {
                 const bool active = i >= resume;
                 // Sphere::distance_from_ray with the ray-independent parts pre-formed (primitive.rs:55-72)
@@ -663,6 +668,21 @@ __device__ __forceinline__ void render_skip_body(const BlockDesc *__restrict__ o
                                 const int v = bound_shortcut_verdict((float)b, (float)disc, (float)best);
                                 c_fviol += ((v == 2 && !(d < best)) || (v == 0 && d < best)) ? 1u : 0u;
                             }
+                        }
+                    }
+                    if constexpr (COUNT && sizeof(T) == 4) {
+                        if (tprim) {
+                            if (nd.is_bound()) {
+                                const Node<T> tn = tprim[i];            // the same test on the tight record
+                                const T tb = (tn.a0 * dir.x + tn.a1 * dir.y) + tn.a2 * dir.z;
+                                const T tdisc = (tb * tb - tn.a3) + tn.a4;
+                                T td = inf<T>();
+                                if (!(tdisc < T(0.0))) {
+                                    const T ts = (VAR & 1) ? sqrt_rn_lean(tdisc) : rsqrt_exact(tdisc);
+                                    if (!((tb + ts) < T(0.0))) td = (tb - ts) > T(0.0) ? tb - ts : tb + ts;
+                                }
+                                if (active && i >= tsleep && td >= best) tsleep = nd.skip();
+                            } else if (active && i < tsleep && !(d >= best)) ++c_tviol;
                         }
                     }
                     if (nd.is_bound()) {                                // BOUND  group.rs:73
@@ -770,6 +790,7 @@ __device__ __forceinline__ void render_skip_body(const BlockDesc *__restrict__ o
                 if constexpr (COUNT && sizeof(T) == 4) { if (sc.xshad) { cfc = *sc.fc; shadow_filter_origin(cfc, sp.x, sp.y, sp.z, fq1, fq2, fql); } }
                 if constexpr (COUNT && sizeof(T) == 8) { if (sc.xshad) { cfc = *sc.fc; shadow_filter_origin64(cfc, sp.x, sp.y, sp.z, fq1, fq2, fql); } }
                 Node<T> nd = sc.shad[0];
+                [[maybe_unused]] unsigned tsleep = 0u;                  // (as in the primary walk)
                 for (;;) {
                     const bool active = i >= resume;
                     const V3<T> v = { nd.a0 - sp.x, nd.a1 - sp.y, nd.a2 - sp.z };
@@ -794,6 +815,19 @@ __device__ __forceinline__ void render_skip_body(const BlockDesc *__restrict__ o
                             c_fpass += verdict == 1 ? 1u : 0u;              // tests the bounds leave to the reference's arithmetic
                             c_fviol += ((verdict == 0 && hit) || (verdict == 2 && !hit)) ? 1u : 0u;
                             c_fviol += ((verdict2 == 0 && hit) || (verdict2 == 2 && !hit)) ? 1u : 0u;
+                        }
+                    }
+                    if constexpr (COUNT && sizeof(T) == 4) {
+                        if (tshad) {
+                            if (nd.is_bound()) {
+                                const Node<T> tn = tshad[i];
+                                const V3<T> tv = { tn.a0 - sp.x, tn.a1 - sp.y, tn.a2 - sp.z };
+                                const T tb = dot(tv, sdir);
+                                const T tdisc = (tb * tb - dot(tv, tv)) + tn.a3;
+                                bool thit = false;
+                                if (!(tdisc < T(0.0))) thit = !((tb + ((VAR & 1) ? sqrt_rn_lean(tdisc) : rsqrt_exact(tdisc))) < T(0.0));
+                                if (active && i >= tsleep && !thit) tsleep = nd.skip();
+                            } else if (active && i < tsleep && hit) ++c_tviol;
                         }
                     }
                     unsigned ni;
@@ -877,7 +911,7 @@ __device__ __forceinline__ void render_skip_body(const BlockDesc *__restrict__ o
         const unsigned long long prim = wave_sum(inside ? (SPLIT ? 1u : spp * spp) : 0u);
         const unsigned long long hits = wave_sum(c_hits), sh = wave_sum(c_shadow), oc = wave_sum(c_occ);
         const unsigned long long its = wave_sum(c_items), bds = wave_sum(c_bounds);
-        const unsigned long long fpass = wave_sum(c_fpass), fviol = wave_sum(c_fviol), ptot = wave_sum(c_ptotal);
+        const unsigned long long fpass = wave_sum(c_fpass), fviol = wave_sum(c_fviol), ptot = wave_sum(c_ptotal), tviol = wave_sum(c_tviol);
         if (lane == 0) {
             atomicAdd(&stripe->primary, prim);
             atomicAdd(&stripe->hits, hits);
@@ -890,6 +924,7 @@ __device__ __forceinline__ void render_skip_body(const BlockDesc *__restrict__ o
             atomicAdd(&stripe->primary_tests, ptot);
             if (fpass) atomicAdd(&stripe->filter_pass, fpass);
             if (fviol) atomicAdd(&stripe->filter_violations, fviol);
+            if (tviol) atomicAdd(&stripe->tight_violations, tviol);
             atomicMax(&stripe->max_wave_steps, (unsigned long long)c_steps);
             atomicMax(&stripe->max_wave_cycles, (unsigned long long)(__builtin_amdgcn_s_memtime() - t_start));
             atomicMax(&stripe->max_wave_ref100mhz, (unsigned long long)(__builtin_amdgcn_s_memrealtime() - r_start));
@@ -912,7 +947,7 @@ __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(6
     if constexpr (!COUNT && (VAR & 8) != 0) r_entry = __builtin_amdgcn_s_memrealtime();
     const SkipArgs<T> &a = args;
     render_skip_body<T, COUNT, VAR, MODE, COOP>(a.order, a.wg_first, a.width, a.height, a.frame_w, a.out, a.tiles, a.n_tiles, a.spp_arg, a.counters, a.lane_cost, a.holes,
-                     a.n_holes, a.sb, a.sc, a.cv, r_entry);
+                     a.n_holes, a.sb, a.sc, a.cv, r_entry, a.tprim, a.tshad);
 }
 
 // The same kernel for f32 launches that do not count, held to 74 scalar registers -- 80 with the hardware's six, and 80 is what a CU admits

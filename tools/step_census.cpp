@@ -6,13 +6,18 @@
 // decision of round 4 settles (rt_skip.hpp bound_shortcut_verdict: b <= 0, b < hit.distance, disc (1 + 2^-20) <= RN(b - hit.distance)^2) --
 // checking on the way that the verdict never contradicts the reference's `d >= hit.distance`.
 //
-//   g++ -O2 -ffp-contract=off -o /tmp/step_census tools/step_census.cpp && /tmp/step_census [w h]
+// --tight: the un-fused walk over the tight bounds of rt_tight.hpp (a BOUND's own sphere is the ITEM step behind it), the prediction the
+// GPU numbers of the tight streams are read against; the hash of every pixel's hit item and shadow verdict must equal the plain run's.
+//
+//   g++ -O2 -ffp-contract=off -o /tmp/step_census tools/step_census.cpp && /tmp/step_census [w h [level]] [--tight]
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
+#include "../rust-tracer_amd/csrc/rt_tight.hpp"
 struct V3 { float x, y, z; };
 static inline V3 add(V3 a, V3 b) { return { a.x + b.x, a.y + b.y, a.z + b.z }; }
 static inline V3 sub(V3 a, V3 b) { return { a.x - b.x, a.y - b.y, a.z - b.z }; }
@@ -39,11 +44,40 @@ static inline float dist(V3 c, float r, V3 o, V3 d, float *disc_out)
 }
 int main(int argc, char **argv)
 {
-    const unsigned W = argc > 1 ? atoi(argv[1]) : 1920, H = argc > 2 ? atoi(argv[2]) : 1080;
-    pyramid(8, { 0, -1, 0 }, 1.0f);
+    bool tight = false;
+    std::vector<char *> pos;
+    for (int a = 1; a < argc; ++a) { if (!strcmp(argv[a], "--tight")) tight = true; else pos.push_back(argv[a]); }
+    const unsigned W = pos.size() > 0 ? atoi(pos[0]) : 1920, H = pos.size() > 1 ? atoi(pos[1]) : 1080, level = pos.size() > 2 ? atoi(pos[2]) : 8;
+    pyramid(level, { 0, -1, 0 }, 1.0f);
     const size_t n = nodes.size();
     const V3 eye = { 0, 0, -4 }, light = normalized({ -1, -3, 2 }), sdir = mulf(light, -1.0f);
-    uint64_t pQ = 0, pB0 = 0, pB1 = 0, pB2 = 0, pI = 0, pLeafQ = 0, sQ = 0, sH = 0, waves = 0, swaves = 0;
+    if (tight) {
+        // the constants rt_scene_create hands rt_tight::build (rt_capi_scene.hpp filter_constants, tight_params)
+        std::vector<float> sph(4 * n); std::vector<uint32_t> skip(n);
+        double m0[3] = { 0, 0, 0 }; size_t n_items = 0;
+        for (size_t i = 0; i < n; ++i) {
+            sph[4 * i] = nodes[i].c.x; sph[4 * i + 1] = nodes[i].c.y; sph[4 * i + 2] = nodes[i].c.z; sph[4 * i + 3] = nodes[i].r; skip[i] = nodes[i].item ? 0u : nodes[i].skip;
+            if (nodes[i].item) { m0[0] += nodes[i].c.x; m0[1] += nodes[i].c.y; m0[2] += nodes[i].c.z; ++n_items; }
+        }
+        rt_tight::Params p{};
+        for (int k = 0; k < 3; ++k) p.m0[k] = (double)(float)(m0[k] / (double)n_items);
+        p.eye[0] = eye.x; p.eye[1] = eye.y; p.eye[2] = eye.z;
+        double rc = 0, rit = 0;
+        for (size_t i = 0; i < n; ++i) {
+            const double c[3] = { nodes[i].c.x, nodes[i].c.y, nodes[i].c.z }, d = rt_tight::dist3(c, p.m0);
+            rc = std::max(rc, d); if (nodes[i].item) rit = std::max(rit, d + nodes[i].r);
+        }
+        const double eye_d = rt_tight::dist3(p.eye, p.m0);
+        const double ro = 1.01 * rit + 1e-3 * (eye_d + rit) + 1e-5 * (fabs(p.eye[0]) + fabs(p.eye[1]) + fabs(p.eye[2]) + fabs(p.m0[0]) + fabs(p.m0[1]) + fabs(p.m0[2]));
+        const double l2 = (double)sdir.x * sdir.x + (double)sdir.y * sdir.y + (double)sdir.z * sdir.z;
+        p.rc = rc; p.S = std::max(rc + ro * (1.0 + 4.0 * rt_tight::kEps), rc + eye_d) * (1.0 + 1e-9); p.eta = std::max(16.0 * rt_tight::kEps, fabs(l2 - 1.0));
+        rt_tight::Result tr;
+        rt_tight::build(sph.data(), skip.data(), (uint32_t)n, p, tr);
+        for (size_t i = 0; i < n; ++i) if (tr.tight[i]) { nodes[i].c = { tr.sphere[4 * i], tr.sphere[4 * i + 1], tr.sphere[4 * i + 2] }; nodes[i].r = tr.sphere[4 * i + 3]; }
+        printf("tight: %u of %u bounds carry a tight sphere, volume ratio %.4f (S %.4f)\n", tr.n_tight, tr.n_bounds, tr.volume_ratio, p.S);
+    }
+    uint64_t hash = 1469598103934665603ull;
+    uint64_t pQ = 0, pB0 = 0, pB1 = 0, pB2 = 0, pI = 0, pLeafQ = 0, sQ = 0, sH = 0, sEnt = 0, waves = 0, swaves = 0;
     uint64_t dec1 = 0, dec2 = 0, dec1_b0 = 0;    // B0 steps in which every candidate lane has b >= best (root-free "no" possible) 
     for (unsigned y0 = 0; y0 < H; y0 += 8) for (unsigned x0 = 0; x0 < W; x0 += 8) {
         V3 dir[64]; bool in[64]; float best[64]; int bi[64]; uint32_t res[64];
@@ -77,6 +111,7 @@ int main(int argc, char **argv)
             if (!cand) { ++pQ; i = nd.skip; continue; }
             if (!undecided) ++dec1; if (!undecided2) ++dec2;
             if (!enter) { ++pB0; if (!undecided) ++dec1_b0; i = nd.skip; continue; }
+            if (tight) { ++pB1; ++i; continue; }      // un-fused: the own sphere is the ITEM step behind the BOUND
             // fused: the own sphere (next node) for the lanes that entered
             const Node &own = nodes[i + 1];
             bool ocand = false;
@@ -89,6 +124,7 @@ int main(int argc, char **argv)
             if (ocand) ++pB2; else ++pB1;
             i += 2;
         }
+        for (unsigned l = 0; l < 64; ++l) if (in[l]) hash = (hash ^ (uint64_t)(uint32_t)bi[l]) * 1099511628211ull;
         // shadow
         V3 sp[64]; bool need[64]; unsigned nn = 0;
         for (unsigned l = 0; l < 64; ++l) { need[l] = false; if (!in[l] || best[l] == INFINITY) continue; const Node &it = nodes[bi[l]]; const V3 nrm = normalized(add(eye, sub(mulf(dir[l], best[l]), it.c))); if (dot(nrm, light) >= 0) continue; sp[l] = add(add(eye, mulf(dir[l], best[l])), mulf(nrm, best[l] * sqrtf(1.1920929e-7f))); need[l] = true; ++nn; }
@@ -106,10 +142,12 @@ int main(int argc, char **argv)
                 else if (hit) { res[l] = 0xFFFFFFFFu; fin = true; }
             }
             if (cand) ++sH; else ++sQ;
+            if (!nd.item && enter) ++sEnt;      // (the fused walk tests the own sphere in this step: it saves the ITEM step behind it)
             size_t ni = (nd.item || enter) ? i + 1 : nd.skip;
             if (fin) { uint32_t m = 0xFFFFFFFFu; for (unsigned l = 0; l < 64; ++l) m = std::min(m, res[l] == 0xFFFFFFFFu ? 0xFFFFFFFFu : std::max<uint32_t>(res[l], (uint32_t)i + 1)); ni = m == 0xFFFFFFFFu ? n : m; }
             i = ni;
         }
+        for (unsigned l = 0; l < 64; ++l) if (need[l]) hash = (hash ^ (res[l] == 0xFFFFFFFFu ? 1u : 2u)) * 1099511628211ull;
     }
     printf("%ux%u: %llu waves (%llu with shadow rays)\n", W, H, (unsigned long long)waves, (unsigned long long)swaves);
     printf("primary: quiet BOUND %llu, quiet ITEM %llu, BOUND cand/no enter %llu, BOUND enter/own quiet %llu, BOUND enter/own cand %llu, ITEM cand %llu\n", (unsigned long long)pQ, (unsigned long long)pLeafQ,
@@ -117,6 +155,9 @@ int main(int argc, char **argv)
     const double valu = 5.0 * (pQ + pLeafQ) + 25.0 * pB0 + 28.0 * pB1 + 42.0 * pB2 + 27.0 * pI;
     printf("primary VALU estimate: %.2f M (quiet %.2f, B0 %.2f, B1 %.2f, B2 %.2f, I %.2f)\n", valu / 1e6, 5.0 * (pQ + pLeafQ) / 1e6, 25.0 * pB0 / 1e6, 28.0 * pB1 / 1e6, 42.0 * pB2 / 1e6, 27.0 * pI / 1e6);
     printf("BOUND-cand steps decided by A/N alone: %llu (of which no-enter %llu), by A/N/G: %llu, of %llu\n", (unsigned long long)dec1, (unsigned long long)dec1_b0, (unsigned long long)dec2, (unsigned long long)(pB0 + pB1 + pB2));
+    printf("steps: primary %llu, shadow %llu; hash of hit items and shadow verdicts %016llx\n", (unsigned long long)(pQ + pLeafQ + pB0 + pB1 + pB2 + pI), (unsigned long long)(sQ + sH), (unsigned long long)hash);
+    // the shadow walk here always takes every node as a step of its own (the UN-FUSED walk); today's fused walk over the given bounds saves one per entered group
+    if (!tight) printf("shadow steps of the FUSED walk (an entered group's own sphere tested in its BOUND step): %llu\n", (unsigned long long)(sQ + sH - sEnt));
     printf("shadow: quiet %llu, hit %llu -> VALU estimate %.2f M (6 / ~14)\n", (unsigned long long)sQ, (unsigned long long)sH, (6.0 * sQ + 14.0 * sH) / 1e6);
     return 0;
 }
