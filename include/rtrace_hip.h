@@ -728,6 +728,55 @@ rt_status rt_overlap_spheres_device(rt_scene *scene, const void *queries, uint32
                                     uint32_t capacity, int32_t *items_out, void *gap_out, uint64_t *offsets_out, uint64_t *total_out, rt_stats *stats,
                                     void *hip_stream);
 
+/* ---- impact pairs (additive to ABI 5): which spheres of the scene come into contact during one step, and when ----
+ * The continuous form of rt_scene_contacts.  A contacts call sees one pose: a pair that is apart at the start of a step and apart at its
+ * end but passes through each other in between is in neither list.  rt_sweep_spheres moves one sphere against a scene that stands still.
+ * This entry takes one displacement per item slot for the step and lists every pair i < j that comes into contact at some t in [0, 1],
+ * with that t: the contact pairs' self-join with the sphere cast as its metric, both spheres moving.
+ *   disp is REAL[3 n_items]: sphere k is at c_k + t d_k for t in [0, 1], d_k = disp[3k .. 3k+3].  On a dynamic scene with live and dead
+ * slots it covers the capacity; a dead slot's value is not used.  For two item slots i < j with stream records {c_i, rr_i} and {c_j, rr_j}
+ * -- rr is the radius squared, rounded once -- in REAL, every operation rounded once, no FMA, every root the IEEE one, every dot product
+ * (x*x' + y*y') + z*z':
+ *   v = c_j - c_i            w = d_i - d_j                     the lower slot is the query, as for the contact pairs
+ *   R = (sqrt(rr_j) + E) + sqrt(rr_i)       RR = R * R         E = 0 for an item; see the bounds below
+ *   a = dot(w, w)    b = dot(v, w)    c = dot(v, v) - RR       disc = b*b - a*c
+ *   t = +inf                     if !(rr_i > 0 && rr_j > 0)
+ *     = 0                        else if !(c > 0)              in contact at the start (the sphere cast's rule)
+ *     = +inf                     else if !(b > 0) or disc < 0  not approaching (this covers w = 0), or passing by
+ *     = c / (b + sqrt(disc))     otherwise                     the smaller root; no division by a
+ * The pair (i, j) is an IMPACT when t <= 1.  The root form never divides by a, so equal displacements need no special case, and it does
+ * not cancel for slow relative motion.  A dead item (rr = -inf) is never part of a pair, as i or as j; a sphere whose rr is 0 behaves
+ * like one.  rust_tracer_amd.pair_impacts restates t in numpy, bit for bit.
+ *   A bound {C, RRn} that encloses its items at the start encloses them during the whole step once it is inflated by the largest
+ * displacement below it.  Every call therefore first makes a MOTION TABLE parallel to the stream, one record {e.x, e.y, e.z, E} per node:
+ * the ITEM node of slot j holds {d_j, 0}; a BOUND node holds {0, 0, 0, D}, D = max m_j * (1 + 8 EPSILON) over the live items of its
+ * subtree, m_j = s >= TINY ? sqrt(s) : (|dx| + |dy|) + |dz| with s = dot(d_j, d_j) and TINY = MIN_NORMAL / EPSILON^2 (the refit's rule
+ * for a length), m_j = 0 for a record without a positive rr.  max is exact: the table's bytes do not depend on how the reduction is
+ * split.  The walk is the contact pairs' -- item i walks the stream BEHIND its own node -- and applies the ONE formula above to every
+ * node with w = d_i - e and E as stored: for an item that is the definition bit for bit; for a bound it is the cast of sphere i, with
+ * its own motion, against a standing sphere of radius r + D, and the subtree is culled when !(t <= 1).  In exact arithmetic a bound's t
+ * is no later than that of any item below it and is 0 whenever the query starts inside.  The result is the walk's, as for every query
+ * here: it can differ from the definition over all i < j only where t lies within rounding of 1 or the pair grazes (disc within
+ * rounding of 0).  A group whose live items all stand still has D = 0: its bound is the contact pairs' bound at margin 0.
+ *   The list is made as the contact pairs' is -- count, exclusive scan, fill -- so it is sorted by (i, j) and the same bytes every time.
+ * pairs_out (int32[2 capacity] or NULL): pair p is pairs_out[2p] = i, pairs_out[2p + 1] = j; time_out (REAL[capacity] or NULL; needs
+ * pairs_out): its t.  capacity, the prefix, *total_out, offsets_out (uint64[n_items + 1] or NULL) and stats behave exactly as for
+ * rt_scene_contacts.  The motion table lives in the scene's contacts workspace (made by the first impacts call, freed with the scene),
+ * and impacts calls take their turn with contacts calls: they share the counts and the offsets. */
+/* Host memory.  RT_ERR_INVALID_ARGUMENT before the device is touched for a NULL scene, disp or total_out, a misaligned buffer (pairs_out
+ * 4 bytes, disp and time_out REAL, offsets_out and total_out 8 bytes), time_out without pairs_out, capacity > 2^31 - 1, a buffer in
+ * device memory and a displacement component that is not finite or beyond +-1e15 (the scene's own bound on a length; dead slots
+ * included).  Pinned memory is used in place, pageable memory goes through the call's device workspace.  Returns when the results are
+ * in place.  The call is a READ in the sense of ORDER above, on static, dynamic, live and flat scenes alike. */
+rt_status rt_scene_impacts(rt_scene *scene, const void *disp, uint32_t capacity, int32_t *pairs_out, void *time_out, uint64_t *offsets_out,
+                           uint64_t *total_out, rt_stats *stats);
+/* The same over DEVICE memory (disp and total_out too), enqueued on `hip_stream` without a host synchronisation: only pointers,
+ * alignment and the capacity are checked.  Displacements outside the host entry's domain give unspecified values, never a fault: the
+ * stream index only grows.  A call goes behind the contacts or impacts call before it, whichever stream that was on.  Pairs
+ * p >= *total_out keep the caller's bytes.  stats != NULL: filled after an internal synchronisation of hip_stream. */
+rt_status rt_scene_impacts_device(rt_scene *scene, const void *disp, uint32_t capacity, int32_t *pairs_out, void *time_out, uint64_t *offsets_out,
+                                  uint64_t *total_out, rt_stats *stats, void *hip_stream);
+
 /* Bytes rt_render_tiles writes for this tile list (4 * total area), or 0 on an invalid list. */
 uint64_t rt_tiles_rgba_bytes(const rt_region *tiles, uint32_t n_tiles);
 

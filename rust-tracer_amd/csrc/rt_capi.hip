@@ -22,6 +22,7 @@
 #include "rt_sweep.hpp"
 #include "rt_contacts.hpp"
 #include "rt_overlap.hpp"
+#include "rt_impacts.hpp"
 #include "rt_order.hpp"
 #include "rt_dynamic.hpp"
 #include "rt_rebuild.hpp"
@@ -304,6 +305,10 @@ struct rt_scene {
     hipEvent_t contacts_ev = nullptr;
     uint64_t *h_contacts_total = nullptr, *d_contacts_total = nullptr;      // one pinned word and its device alias: the host entry reads the total here (no copy into a caller's stack)
     bool contacts_recorded = false;
+    // ---- impact pairs (rt_scene_impacts*, rt_impacts.hpp): the motion table -- one record per stream node -- with the nodes' lengths and their
+    // chunk maxima behind it, made by the first impacts call under contacts_mu; impacts calls share the counts, offsets and sums above
+    void *d_impacts = nullptr;
+    uint32_t impacts_cap = 0;          // nodes d_impacts has room for
     // ---- overlap lists (rt_overlap_spheres*, rt_overlap.hpp): the workspace of the two passes -- counts, offsets and the scan's block sums
     // for overlap_cap queries -- made by the first call, grown when a call brings more queries than any before it (behind overlap_ev: the
     // one allocation) and shared by all: a call enqueues under overlap_mu and behind overlap_ev, which the call before it recorded on its

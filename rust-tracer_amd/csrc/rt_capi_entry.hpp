@@ -337,6 +337,7 @@ rt_status rt_scene_destroy(rt_scene *s)
     if (s->d_query_items) (void)hipFree(s->d_query_items);
     if (s->query_items_ev) (void)hipEventDestroy(s->query_items_ev);
     if (s->d_contacts) (void)hipFree(s->d_contacts);
+    if (s->d_impacts) (void)hipFree(s->d_impacts);
     if (s->contacts_ev) (void)hipEventDestroy(s->contacts_ev);
     if (s->h_contacts_total) (void)hipHostFree(s->h_contacts_total);
     if (s->d_overlap) (void)hipFree(s->d_overlap);
@@ -1543,6 +1544,134 @@ rt_status rt_scene_contacts(rt_scene *s, double margin, uint32_t capacity, int32
         st = enqueue_contacts_fill(s, nodes, n_nodes, margin, capacity, reinterpret_cast<int32_t *>(b[0].dev), b[1].dev, c->stream);
         if (st != RT_OK) { (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return st; }
         for (int k = 0; k < 2; ++k)                                  // (only what was written: the caller's bytes behind it stay)
+            if (b[k].staged && b[k].host) HIP_DRAIN(hipMemcpyAsync(b[k].host, b[k].dev, b[k].unit * written, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (stats) {
+        HIP_DRAIN(hipEventRecord(c->ev1, c->stream));
+        return read_query_stats(c, c->stream, stats);                // synchronises the stream
+    }
+    HIP_DRAIN(hipStreamSynchronize(c->stream));
+#undef HIP_DRAIN
+    return RT_OK;
+}
+
+// ---- impact pairs: every pair of spheres of the scene that comes into contact during one step, and when (rt_impacts.hpp) ----
+
+rt_status rt_scene_impacts_device(rt_scene *s, const void *disp, uint32_t capacity, int32_t *pairs_out, void *time_out, uint64_t *offsets_out, uint64_t *total_out,
+                                  rt_stats *stats, void *hip_stream)
+{
+    const char *const what = "rt_scene_impacts_device";
+    if (!impacts_args_ok(s, disp, capacity, pairs_out, time_out, offsets_out, total_out, what)) return RT_ERR_INVALID_ARGUMENT;
+    const ReadLock rl(s);
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    const void *nodes = nullptr;
+    uint32_t n_nodes = 0;
+    rt_status st = query_stream(s, stream, &nodes, &n_nodes);
+    if (st != RT_OK) return st;
+    Context *c = nullptr;
+    Lease lease{ s, nullptr };
+    if (stats) {
+        if ((st = acquire(s, &c)) != RT_OK) return st;
+        lease.c = c;
+    }
+    {
+        // impacts calls take their turn with contacts calls: they share the counts and the offsets
+        std::lock_guard<std::mutex> lk(s->contacts_mu);
+        if ((st = impacts_begin(s, nodes, n_nodes, stream)) != RT_OK) return st;
+        if (stats) {
+            HIP_TRY(hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, stream));
+            HIP_TRY(hipEventRecord(c->ev0, stream));
+        }
+        st = enqueue_impacts_count(s, nodes, n_nodes, disp, offsets_out, total_out, stats ? c->d_counters : nullptr, stream);
+        if (st == RT_OK && capacity != 0u && pairs_out) st = enqueue_impacts_fill(s, nodes, n_nodes, capacity, pairs_out, time_out, stream);
+        // whatever was enqueued uses the workspace: the next call goes behind it
+        if (hipEventRecord(s->contacts_ev, stream) == hipSuccess) s->contacts_recorded = true;
+        else { (void)hipGetLastError(); (void)hipStreamSynchronize(stream); }
+    }
+    if (!stats) return st;
+    (void)hipEventRecord(c->ev1, stream);
+    if (st != RT_OK) { (void)hipGetLastError(); lease.inflight = true; return st; }      // (the context goes back behind what is enqueued)
+    return read_query_stats(c, stream, stats);
+}
+
+rt_status rt_scene_impacts(rt_scene *s, const void *disp, uint32_t capacity, int32_t *pairs_out, void *time_out, uint64_t *offsets_out, uint64_t *total_out,
+                           rt_stats *stats)
+{
+    const char *const what = "rt_scene_impacts";
+    if (!impacts_args_ok(s, disp, capacity, pairs_out, time_out, offsets_out, total_out, what)) return RT_ERR_INVALID_ARGUMENT;
+    const bool f32 = s->precision == RT_F32;
+    const bool fill = capacity != 0u && pairs_out;
+    // pinned buffers are read and written by the kernels in place, pageable ones go through the call's workspace (as rt_overlap_spheres)
+    const size_t esz = f32 ? sizeof(float) : sizeof(double);
+    struct Buf { void *host; size_t bytes, unit; bool out; uint8_t *dev; size_t off; bool staged; };
+    Buf b[4] = { { const_cast<void *>(disp), 3 * esz * (size_t)s->n_items, 0, false, nullptr, 0, false },
+                 { fill ? pairs_out : nullptr, 2 * sizeof(int32_t) * (size_t)capacity, 2 * sizeof(int32_t), true, nullptr, 0, false },
+                 { fill ? time_out : nullptr, esz * (size_t)capacity, esz, true, nullptr, 0, false },
+                 { offsets_out, sizeof(uint64_t) * ((size_t)s->n_items + 1), 0, true, nullptr, 0, false } };
+    size_t need = 0;
+    for (Buf &x : b) {
+        if (!x.host) continue;
+        const HostDest d = classify_host_pointer(x.host);
+        if (d.bad) {
+            snprintf(g_err, sizeof g_err, "%s: a buffer is device memory; use %s_device", what, what);
+            return RT_ERR_INVALID_ARGUMENT;
+        }
+        if (d.pinned && d.dev_alias && d.room >= x.bytes) { x.dev = d.dev_alias; continue; }
+        x.staged = true;
+        x.off = need;
+        need += (x.bytes + 255) & ~(size_t)255;
+    }
+    if (classify_host_pointer(total_out).bad) {
+        snprintf(g_err, sizeof g_err, "%s: a buffer is device memory; use %s_device", what, what);
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    if (!(f32 ? impacts_disp_valid(static_cast<const float *>(disp), s->n_items, what) : impacts_disp_valid(static_cast<const double *>(disp), s->n_items, what)))
+        return RT_ERR_INVALID_ARGUMENT;
+    const ReadLock rl(s);
+    HIP_TRY(hipSetDevice(s->device));
+    rt_status st = RT_OK;
+    Context *c = nullptr;
+    if ((st = acquire(s, &c)) != RT_OK) return st;
+    Lease lease{ s, c };
+    const void *nodes = nullptr;
+    uint32_t n_nodes = 0;
+    if ((st = query_stream(s, c->stream, &nodes, &n_nodes)) != RT_OK) return st;
+    if (need > c->query_cap) {
+        if (c->d_query) HIP_TRY(hipFree(c->d_query));
+        c->d_query = nullptr; c->query_cap = 0;
+        HIP_TRY(hipMalloc(&c->d_query, need));
+        c->query_cap = need;
+    }
+    for (Buf &x : b)
+        if (x.staged) x.dev = static_cast<uint8_t *>(c->d_query) + x.off;
+    // the two passes share the scene's contacts workspace and this call reads the total between them: host calls on one scene take turns,
+    // contacts and impacts alike
+    std::lock_guard<std::mutex> lk(s->contacts_mu);
+    if ((st = impacts_begin(s, nodes, n_nodes, c->stream)) != RT_OK) return st;
+    // from here on work of this call may be queued: an error return first waits for it
+#define HIP_DRAIN(expr)                                                                                                   \
+    do {                                                                                                                  \
+        hipError_t e__ = (expr);                                                                                          \
+        if (e__ != hipSuccess) { (void)hipStreamSynchronize(c->stream); return hip_fail(e__, #expr, __LINE__); }          \
+    } while (0)
+    if (b[0].staged) HIP_DRAIN(hipMemcpyAsync(b[0].dev, b[0].host, b[0].bytes, hipMemcpyHostToDevice, c->stream));
+    if (stats) {
+        HIP_DRAIN(hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, c->stream));
+        HIP_DRAIN(hipEventRecord(c->ev0, c->stream));
+    }
+    // the scan writes the total into the scene's pinned word, as rt_scene_contacts has it
+    st = enqueue_impacts_count(s, nodes, n_nodes, b[0].dev, reinterpret_cast<uint64_t *>(b[3].dev), s->d_contacts_total, stats ? c->d_counters : nullptr, c->stream);
+    if (st != RT_OK) { (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return st; }
+    if (b[3].staged) HIP_DRAIN(hipMemcpyAsync(b[3].host, b[3].dev, b[3].bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_DRAIN(hipStreamSynchronize(c->stream));
+    const uint64_t total = *static_cast<volatile uint64_t *>(s->h_contacts_total);
+    *total_out = total;
+    const size_t written = (size_t)std::min<uint64_t>(total, capacity);
+    if (fill && written) {
+        st = enqueue_impacts_fill(s, nodes, n_nodes, capacity, reinterpret_cast<int32_t *>(b[1].dev), b[2].dev, c->stream);
+        if (st != RT_OK) { (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return st; }
+        for (int k = 1; k < 3; ++k)                                  // (only what was written: the caller's bytes behind it stay)
             if (b[k].staged && b[k].host) HIP_DRAIN(hipMemcpyAsync(b[k].host, b[k].dev, b[k].unit * written, hipMemcpyDeviceToHost, c->stream));
     }
     if (stats) {

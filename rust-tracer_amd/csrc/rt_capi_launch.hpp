@@ -1075,6 +1075,123 @@ rt_status enqueue_contacts_fill(const rt_scene *s, const void *nodes, uint32_t n
                                   : enqueue_contacts_fill<double>(s, nodes, n_nodes, margin, capacity, pairs, gap, stream);
 }
 
+// ---- impact pairs (rt_scene_impacts*, rt_impacts.hpp) ----
+
+// What both impacts entries check (device pointers are not dereferenced here).
+bool impacts_args_ok(const rt_scene *s, const void *disp, uint32_t capacity, const int32_t *pairs, const void *time, const uint64_t *offsets, const uint64_t *total,
+                     const char *what)
+{
+    if (!s || !disp || !total) { snprintf(g_err, sizeof g_err, "%s: NULL scene, disp or total_out", what); return false; }
+    if (capacity > 0x7FFFFFFFu) { snprintf(g_err, sizeof g_err, "%s: capacity %u is above 2^31 - 1", what, capacity); return false; }
+    if (time && !pairs) { snprintf(g_err, sizeof g_err, "%s: time_out without pairs_out", what); return false; }
+    if ((reinterpret_cast<uintptr_t>(pairs) & 3u) != 0) { snprintf(g_err, sizeof g_err, "%s: pairs_out must be 4-byte aligned", what); return false; }
+    const struct { const void *p; const char *name; } longs[] = { { offsets, "offsets_out" }, { total, "total_out" } };
+    for (const auto &w : longs)
+        if ((reinterpret_cast<uintptr_t>(w.p) & 7u) != 0) { snprintf(g_err, sizeof g_err, "%s: %s must be 8-byte aligned", what, w.name); return false; }
+    const uintptr_t esz = s->precision == RT_F32 ? sizeof(float) : sizeof(double);
+    const struct { const void *p; const char *name; } reals[] = { { disp, "disp" }, { time, "time_out" } };
+    for (const auto &w : reals)
+        if ((reinterpret_cast<uintptr_t>(w.p) % esz) != 0) { snprintf(g_err, sizeof g_err, "%s: %s must be %u-byte aligned", what, w.name, (unsigned)esz); return false; }
+    return true;
+}
+
+// The host entry's domain: every component finite and within +-1e15, the scene's own bound on a length.
+template <typename T>
+bool impacts_disp_valid(const T *disp, uint32_t n_items, const char *what)
+{
+    for (size_t k = 0; k < 3 * (size_t)n_items; ++k)
+        if (!std::isfinite(disp[k]) || std::fabs((double)disp[k]) > 1e15) {
+            snprintf(g_err, sizeof g_err, "%s: disp of slot %u has a non-finite component or one beyond +-1e15", what, (unsigned)(k / 3));
+            return false;
+        }
+    return true;
+}
+
+// contacts_begin, and room for the motion table of `n_nodes` nodes.  Under s->contacts_mu.
+rt_status impacts_begin(rt_scene *s, const void *nodes, uint32_t n_nodes, hipStream_t stream)
+{
+    const rt_status st = contacts_begin(s, nodes, n_nodes, stream);
+    if (st != RT_OK) return st;
+    if (n_nodes <= s->impacts_cap && s->d_impacts) return RT_OK;
+    if (s->d_impacts) {
+        if (s->contacts_recorded) HIP_TRY(hipEventSynchronize(s->contacts_ev));
+        HIP_TRY(hipFree(s->d_impacts));
+        s->d_impacts = nullptr; s->impacts_cap = 0;
+    }
+    const size_t esz = s->precision == RT_F32 ? sizeof(float) : sizeof(double);
+    const size_t n = n_nodes ? n_nodes : 1, n_chunks = (n + rt::kMotionChunk - 1) / rt::kMotionChunk;
+    const size_t o_length = (4 * esz * n + 255) & ~(size_t)255, o_chunk = o_length + ((esz * n + 255) & ~(size_t)255);
+    HIP_TRY(hipMalloc(&s->d_impacts, o_chunk + ((esz * n_chunks + 255) & ~(size_t)255)));
+    s->impacts_cap = n_nodes;
+    return RT_OK;
+}
+
+template <typename T> struct ImpactsSpace { rt::Motion<T> *motion; T *length, *chunk; };
+template <typename T>
+ImpactsSpace<T> impacts_space(const rt_scene *s)
+{
+    const size_t n = s->impacts_cap ? s->impacts_cap : 1;
+    const size_t o_length = (4 * sizeof(T) * n + 255) & ~(size_t)255, o_chunk = o_length + ((sizeof(T) * n + 255) & ~(size_t)255);
+    uint8_t *const d = static_cast<uint8_t *>(s->d_impacts);
+    return { reinterpret_cast<rt::Motion<T> *>(d), reinterpret_cast<T *>(d + o_length), reinterpret_cast<T *>(d + o_chunk) };
+}
+
+// The motion table, the first pass and the scan on `stream`.  counters != NULL runs the counting flavour (same counts).
+template <typename T>
+rt_status enqueue_impacts_count(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *disp, uint64_t *offsets_out, uint64_t *total_out,
+                                rt::Counters *counters, hipStream_t stream)
+{
+    const uint32_t n = s->n_items;
+    const ImpactsSpace<T> w = impacts_space<T>(s);
+    const rt::Node<T> *const st = static_cast<const rt::Node<T> *>(nodes);
+    if (n_nodes != 0u) {
+        const unsigned n_chunks = (n_nodes + rt::kMotionChunk - 1) / rt::kMotionChunk;
+        hipLaunchKernelGGL(rt::k_impact_motion_items<T>, dim3(n_chunks), dim3(rt::kMotionChunk), 0, stream, st, static_cast<const T *>(disp), n_nodes, n, w.motion, w.length, w.chunk);
+        hipLaunchKernelGGL(rt::k_impact_motion_bounds<T>, dim3((n_nodes + 255) / 256), dim3(256), 0, stream, st, n_nodes, w.length, w.chunk, w.motion);
+        HIP_TRY(hipGetLastError());
+    }
+    const uint32_t *const item_node = s->n_nodes ? (s->d_item_node ? s->d_item_node : s->d_contacts_item_node) : nullptr;
+    const rt::ImpactArgs<T> a{ st, w.motion, item_node, s->d_contacts_counts, nullptr, nullptr, nullptr, counters, n_nodes, n, 0u };
+    const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
+    if (counters) hipLaunchKernelGGL((rt::k_impact_pairs<T, true, false>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((rt::k_impact_pairs<T, false, false>), grid, block, 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    const unsigned n_sums = (n + rt::kScanBlock - 1) / rt::kScanBlock;
+    const dim3 sgrid(n_sums), sblock(rt::kScanBlock);
+    hipLaunchKernelGGL(rt::k_contact_scan_sums, sgrid, sblock, 0, stream, s->d_contacts_counts, n, s->d_contacts_sums);
+    hipLaunchKernelGGL(rt::k_contact_scan_spine, dim3(1), sblock, 0, stream, s->d_contacts_sums, n_sums, s->d_contacts_offsets + n, offsets_out ? offsets_out + n : nullptr, total_out);
+    hipLaunchKernelGGL(rt::k_contact_scan_offsets, sgrid, sblock, 0, stream, s->d_contacts_counts, n, s->d_contacts_sums, s->d_contacts_offsets, offsets_out);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+rt_status enqueue_impacts_count(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *disp, uint64_t *offsets_out, uint64_t *total_out,
+                                rt::Counters *counters, hipStream_t stream)
+{
+    return s->precision == RT_F32 ? enqueue_impacts_count<float>(s, nodes, n_nodes, disp, offsets_out, total_out, counters, stream)
+                                  : enqueue_impacts_count<double>(s, nodes, n_nodes, disp, offsets_out, total_out, counters, stream);
+}
+
+// The second pass on `stream`: the same walk over the motion table the first pass left, pair offsets[i] + rank written below `capacity`.
+template <typename T>
+rt_status enqueue_impacts_fill(const rt_scene *s, const void *nodes, uint32_t n_nodes, uint32_t capacity, int32_t *pairs, void *time, hipStream_t stream)
+{
+    const uint32_t n = s->n_items;
+    const uint32_t *const item_node = s->n_nodes ? (s->d_item_node ? s->d_item_node : s->d_contacts_item_node) : nullptr;
+    const rt::ImpactArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), impacts_space<T>(s).motion, item_node, nullptr, s->d_contacts_offsets, pairs, static_cast<T *>(time), nullptr,
+                               n_nodes, n, capacity };
+    const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
+    hipLaunchKernelGGL((rt::k_impact_pairs<T, false, true>), grid, block, 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+rt_status enqueue_impacts_fill(const rt_scene *s, const void *nodes, uint32_t n_nodes, uint32_t capacity, int32_t *pairs, void *time, hipStream_t stream)
+{
+    return s->precision == RT_F32 ? enqueue_impacts_fill<float>(s, nodes, n_nodes, capacity, pairs, time, stream)
+                                  : enqueue_impacts_fill<double>(s, nodes, n_nodes, capacity, pairs, time, stream);
+}
+
 // ---- overlap lists (rt_overlap_spheres*, rt_overlap.hpp) ----
 
 // What both overlap entries check (device pointers are not dereferenced here).

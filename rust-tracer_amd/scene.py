@@ -145,6 +145,48 @@ def overlap_gaps(queries, spheres):
     return np.where((rr > 0)[None, :], gap, R(np.inf)).astype(R, copy=False)
 
 
+def pair_impacts(spheres, disp, i, j, inflate=None):
+    """The time of impact of the pairs (i[k], j[k]) of `spheres` (m x 4: cx, cy, cz, r) that move by `disp` (m x 3) during one step -- sphere
+    k is at c_k + t d_k for t in [0, 1] -> REAL[len(i)], the metric of rt_scene_impacts restated in numpy bit for bit (include/rtrace_hip.h
+    states it), in the arrays' dtype (float32 or float64), every operation rounded once:
+    rr = r * r;  v = c_j - c_i;  w = d_i - d_j;  R = (sqrt(rr_j) + E_j) + sqrt(rr_i);  a = dot(w, w), b = dot(v, w), c = dot(v, v) - R * R,
+    disc = b*b - a*c;  t = +inf where not (rr_i > 0 and rr_j > 0), else 0 where not c > 0 (in contact at the start), else +inf where
+    not b > 0 or disc < 0 (not approaching, or passing by), else c / (b + sqrt(disc)).  The library always takes the lower slot as i.
+    `inflate` (REAL[m] or None: 0) is E, what the walk adds to the radius of a BOUND record: 0 for every item.  A record without a
+    positive rr -- radius 0: a dead slot -- is at +inf, in either place.  DeviceScene.impacts lists the pairs i < j with t <= 1."""
+    s, d = np.asarray(spheres), np.asarray(disp)
+    if s.dtype not in (np.float32, np.float64) or s.ndim != 2 or s.shape[1] != 4:
+        raise ValueError("spheres must be an (m, 4) array of float32 or float64")
+    if d.dtype != s.dtype or d.shape != (s.shape[0], 3):
+        raise ValueError("disp must be an (m, 3) array of the spheres' dtype")
+    R = s.dtype.type
+    E = np.zeros(s.shape[0], R) if inflate is None else np.asarray(inflate)
+    if E.dtype != s.dtype or E.shape != (s.shape[0],):
+        raise ValueError("inflate must be None or an (m,) array of the spheres' dtype")
+    i, j = np.asarray(i), np.asarray(j)
+    if i.dtype.kind not in "iu" or j.dtype.kind not in "iu" or i.ndim != 1 or i.shape != j.shape:
+        raise ValueError("i and j must be integer arrays of one shape, (k,)")
+    if i.size and (min(int(i.min()), int(j.min())) < 0 or max(int(i.max()), int(j.max())) >= s.shape[0]):
+        raise ValueError("i and j must be rows of spheres")
+    rr = s[:, 3] * s[:, 3]
+    rri, rrj = rr[i], rr[j]
+    solid = (rri > 0) & (rrj > 0)
+    one = R(1.0)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore", under="ignore"):
+        v = s[j, :3] - s[i, :3]
+        w = d[i] - d[j]
+        rad = (np.sqrt(np.where(rrj > 0, rrj, one)) + E[j]) + np.sqrt(np.where(rri > 0, rri, one))
+        RR = rad * rad
+        a = (w[:, 0] * w[:, 0] + w[:, 1] * w[:, 1]) + w[:, 2] * w[:, 2]
+        b = (v[:, 0] * w[:, 0] + v[:, 1] * w[:, 1]) + v[:, 2] * w[:, 2]
+        c = ((v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1]) + v[:, 2] * v[:, 2]) - RR
+        disc = b * b - a * c
+        root = (b > 0) & ~(disc < 0)
+        t = np.where(root, c / (b + np.sqrt(np.where(root, disc, one))), R(np.inf))
+        t = np.where(c > 0, t, R(0.0))
+    return np.where(solid, t, R(np.inf)).astype(R, copy=False)
+
+
 def sweep_distances(rays, radius, spheres):
     """The cast distance of every cast of `rays` (n x 6: pos.xyz, dir.xyz, dir a unit vector) with `radius` (REAL[n], one value, or None: 0)
     against every sphere of `spheres` (m x 4: cx, cy, cz, r) -> REAL[n, m], the metric of rt_sweep_spheres restated in numpy bit for bit
@@ -1280,6 +1322,83 @@ class DeviceScene:
             m = min(capacity, total)
             items, gap = items[:m], (gap[:m] if gaps else None)
         res = (items,) + ((gap,) if gaps else ()) + ((off,) if offsets else ()) + (total,)
+        return res + ((st.as_dict(),) if stats else ())
+
+    def impacts(self, disp, capacity=None, times=False, offsets=False, stats=False, stream=None):
+        """rt_scene_impacts / rt_scene_impacts_device: every pair of spheres of the scene that comes into contact while sphere k moves from
+        c_k to c_k + disp[k] (`disp`: n_items x 3, the scene's REAL dtype, one row per item slot -- on a live scene per slot of the capacity;
+        a dead slot's row is not used; pair_impacts is the metric) -> (pairs[, time][, offsets], total[, stats dict]).  pairs: int32[m, 2],
+        the DFS slots i < j of every impact, sorted by (i, j), the same bytes every time.  times=True: REAL[m], each pair's t in [0, 1] (0:
+        in contact at the start).  offsets=True: uint64[n_items + 1], item i is the lower slot of pairs offsets[i] .. offsets[i + 1].
+        capacity=None counts first and then allocates exactly (m = total); with a capacity, m = min(capacity, total) and the list is the
+        exact prefix of the full one; capacity=0 only counts (times needs pairs: times=True with capacity=0 is an error).  A numpy array
+        goes through the host entry and gives numpy results; its components must be finite and within +-1e15.  A torch tensor on this
+        scene's device goes through the device entry on `stream` (a torch stream or a hipStream_t as int; default the current torch
+        stream) and gives torch tensors -- with a capacity nothing is waited for: pairs has `capacity` rows of which the first `total` are
+        written, and total is a 0-d int64 tensor (offsets is an int64 tensor too: the same bits); capacity=None reads the count back
+        first, and total is an int."""
+        if capacity is not None:
+            capacity = int(capacity)
+            if not 0 <= capacity <= 0x7FFFFFFF:
+                raise ValueError("capacity must be None or 0 .. 2^31 - 1, not %d" % capacity)
+            if times and capacity == 0:
+                raise ValueError("times needs pairs: capacity must not be 0")
+        R = _real(self.scene.precision)
+        n = self.scene.items.shape[0]
+        st = capi.Stats()
+        stp = C.byref(st) if stats else None
+        torch = sys.modules.get("torch")
+        if torch is not None and isinstance(disp, torch.Tensor):
+            tdt = torch.float32 if R == np.float32 else torch.float64
+            dev = torch.device("cuda", self.device)
+            if disp.dtype != tdt or tuple(disp.shape) != (n, 3):
+                raise ValueError("disp must be an (%d, 3) %s tensor" % (n, tdt))
+            if disp.device != dev:
+                raise ValueError("disp must be on %s, not %s" % (dev, disp.device))
+            qs, cur = self._device_stream(torch, stream)
+            if qs != cur:
+                qs.wait_stream(cur)
+            ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
+            with torch.cuda.stream(qs):
+                dt = disp.contiguous()
+                total = torch.zeros((), dtype=torch.int64, device=dev)
+                off = torch.empty(n + 1, dtype=torch.int64, device=dev) if offsets else None
+                counted = capacity is None
+                if counted:
+                    capi.check(capi.lib.rt_scene_impacts_device(self._h, ptr(dt), 0, None, None, None, ptr(total), None, C.c_void_p(qs.cuda_stream)),
+                               "rt_scene_impacts_device")
+                    capacity = int(total.item())
+                    if capacity > 0x7FFFFFFF:
+                        raise ValueError("the step has %d impacts, more than one call can list: pass a capacity" % capacity)
+                pairs = torch.empty((capacity, 2), dtype=torch.int32, device=dev)
+                time = torch.empty(capacity, dtype=tdt, device=dev) if times else None
+                rc = capi.lib.rt_scene_impacts_device(self._h, ptr(dt), capacity, ptr(pairs) if capacity else None, ptr(time) if capacity else None, ptr(off),
+                                                      ptr(total), stp, C.c_void_p(qs.cuda_stream))
+            if qs != cur:
+                for x in (disp, dt):
+                    x.record_stream(qs)
+            capi.check(rc, "rt_scene_impacts_device")
+            total = int(total.item()) if counted else total
+        else:
+            if not isinstance(disp, np.ndarray) or disp.dtype != R or disp.shape != (n, 3):
+                raise ValueError("disp must be an (%d, 3) numpy array of %s (or a torch tensor on the scene's device)" % (n, np.dtype(R).name))
+            da = np.ascontiguousarray(disp)
+            total = C.c_uint64(0)
+            off = np.empty(n + 1, dtype=np.uint64) if offsets else None
+            ptr = lambda x: None if x is None else x.ctypes.data
+            if capacity is None:
+                capi.check(capi.lib.rt_scene_impacts(self._h, ptr(da), 0, None, None, None, C.byref(total), None), "rt_scene_impacts")
+                capacity = int(total.value)
+                if capacity > 0x7FFFFFFF:
+                    raise ValueError("the step has %d impacts, more than one call can list: pass a capacity" % capacity)
+            pairs = np.empty((capacity, 2), dtype=np.int32)
+            time = np.empty(capacity, dtype=R) if times else None
+            capi.check(capi.lib.rt_scene_impacts(self._h, ptr(da), capacity, ptr(pairs) if capacity else None, ptr(time) if capacity else None, ptr(off),
+                                                 C.byref(total), stp), "rt_scene_impacts")
+            total = int(total.value)
+            m = min(capacity, total)
+            pairs, time = pairs[:m], (time[:m] if times else None)
+        res = (pairs,) + ((time,) if times else ()) + ((off,) if offsets else ()) + (total,)
         return res + ((st.as_dict(),) if stats else ())
 
     @staticmethod
