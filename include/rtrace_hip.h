@@ -737,8 +737,9 @@ rt_status rt_overlap_spheres_device(rt_scene *scene, const void *queries, uint32
  * slots it covers the capacity; a dead slot's value is not used.  For two item slots i < j with stream records {c_i, rr_i} and {c_j, rr_j}
  * -- rr is the radius squared, rounded once -- in REAL, every operation rounded once, no FMA, every root the IEEE one, every dot product
  * (x*x' + y*y') + z*z':
- *   v = c_j - c_i            w = d_i - d_j                     the lower slot is the query, as for the contact pairs
- *   R = (sqrt(rr_j) + E) + sqrt(rr_i)       RR = R * R         E = 0 for an item; see the bounds below
+ *   c' = c S    r' = r S           d' = d S    E' = E S       S: the call's power of two, r: the record's radius, see below
+ *   v = c_j' - c_i'          w = d_i' - d_j'                   the lower slot is the query, as for the contact pairs
+ *   R = (r_j' + E') + r_i'                  RR = R * R         E = 0 for an item; see the bounds below
  *   a = dot(w, w)    b = dot(v, w)    c = dot(v, v) - RR       disc = b*b - a*c
  *   t = +inf                     if !(rr_i > 0 && rr_j > 0)
  *     = 0                        else if !(c > 0)              in contact at the start (the sphere cast's rule)
@@ -747,13 +748,25 @@ rt_status rt_overlap_spheres_device(rt_scene *scene, const void *queries, uint32
  * The pair (i, j) is an IMPACT when t <= 1.  The root form never divides by a, so equal displacements need no special case, and it does
  * not cancel for slow relative motion.  A dead item (rr = -inf) is never part of a pair, as i or as j; a sphere whose rr is 0 behaves
  * like one.  rust_tracer_amd.pair_impacts restates t in numpy, bit for bit.
+ *   S.  a, b and c are of the second degree in a length and disc of the fourth; t has none.  So that b*b and a*c stay normal numbers
+ * wherever the scene is -- coordinates and displacements up to 1e15, no lower bound -- every input is first multiplied by S = 2^-e, which
+ * is exact: M is the largest of |C.x|, |C.y|, |C.z| and r over the nodes {C, RRn} of THE SCENE'S STREAM that have RRn > 0 -- its
+ * items and its bounds, as the call finds them -- and of |d.x|, |d.y|, |d.z| over its items with rr > 0; M = f 2^e with 0.5 <= f < 1, e
+ * held to [MIN_EXP + 1, MAX_EXP - 2] of REAL so that S is a normal number, and S = 1 when M = 0.  A dead record contributes nothing, as
+ * for D below.  Every scaled magnitude is below 1, and lengths down to 2^-31 M (f64: 2^-255 M) keep their fourth powers normal.  Wherever
+ * nothing leaves the normal range S changes no bit of t: a scene and its displacements times a power of two have the same times.
+ *   r.  rr decides whether a record is alive (rr > 0); the radius is the scene's own |r|, not sqrt(rr): the item's radius as the scene
+ * holds it (rt_scene_create, rt_scene_update*, rt_scene_rebuild*), and a bound's as it was given or as the refit left it (rt_scene_bounds).
+ * The two are the same number wherever r * r is a normal number; where it is a denormal (f32: r below 2^-63) sqrt(rr) keeps a few bits
+ * of r and r keeps them all.
+ * rust_tracer_amd.impact_scale restates S; pair_impacts takes it as `scale`, or computes it from the records it is given.
  *   A bound {C, RRn} that encloses its items at the start encloses them during the whole step once it is inflated by the largest
  * displacement below it.  Every call therefore first makes a MOTION TABLE parallel to the stream, one record {e.x, e.y, e.z, E} per node:
- * the ITEM node of slot j holds {d_j, 0}; a BOUND node holds {0, 0, 0, D}, D = max m_j * (1 + 8 EPSILON) over the live items of its
+ * the ITEM node of slot j holds {d_j, 0}; a BOUND node holds {0, 0, 0, D} (stored times S, with r' added to the last field), D = max m_j * (1 + 8 EPSILON) over the live items of its
  * subtree, m_j = s >= TINY ? sqrt(s) : (|dx| + |dy|) + |dz| with s = dot(d_j, d_j) and TINY = MIN_NORMAL / EPSILON^2 (the refit's rule
  * for a length), m_j = 0 for a record without a positive rr.  max is exact: the table's bytes do not depend on how the reduction is
  * split.  The walk is the contact pairs' -- item i walks the stream BEHIND its own node -- and applies the ONE formula above to every
- * node with w = d_i - e and E as stored: for an item that is the definition bit for bit; for a bound it is the cast of sphere i, with
+ * node with w = d_i' - e' and E' as stored: for an item that is the definition bit for bit; for a bound it is the cast of sphere i, with
  * its own motion, against a standing sphere of radius r + D, and the subtree is culled when !(t <= 1).  In exact arithmetic a bound's t
  * is no later than that of any item below it and is 0 whenever the query starts inside.  The result is the walk's, as for every query
  * here: it can differ from the definition over all i < j only where t lies within rounding of 1 or the pair grazes (disc within

@@ -278,6 +278,8 @@ struct rt_scene {
     int comb_leaders = 0;              // passes being led right now (<= kMaxRegionLeaders)
     // rt_scene_bounds of a scene from rt_scene_create: the bounds it was created with
     std::vector<unsigned char> h_bounds;
+    // ... and the radius of every node of its stream, REAL[n_nodes], as given (the stream holds its square): the impacts calls' bound radii
+    std::vector<unsigned char> h_node_radius;
     // ---- a DYNAMIC scene (rt_scene_create_dynamic, rt_dynamic.hpp): the items, ONE stream (d_shad, or d_query_items without bounds), and
     // what an update needs, resident -- nothing of the render path (no filtered / compacted / cooperative / flat data, no cost map, no worker)
     bool dynamic = false;

@@ -1121,19 +1121,31 @@ rt_status impacts_begin(rt_scene *s, const void *nodes, uint32_t n_nodes, hipStr
     const size_t esz = s->precision == RT_F32 ? sizeof(float) : sizeof(double);
     const size_t n = n_nodes ? n_nodes : 1, n_chunks = (n + rt::kMotionChunk - 1) / rt::kMotionChunk;
     const size_t o_length = (4 * esz * n + 255) & ~(size_t)255, o_chunk = o_length + ((esz * n + 255) & ~(size_t)255);
-    HIP_TRY(hipMalloc(&s->d_impacts, o_chunk + ((esz * n_chunks + 255) & ~(size_t)255)));
+    const size_t o_radius = o_chunk + ((esz * n_chunks + 255) & ~(size_t)255) + 256;                   // (+ the call's magnitude, a word of its own)
+    HIP_TRY(hipMalloc(&s->d_impacts, o_radius + ((esz * n + 255) & ~(size_t)255)));
     s->impacts_cap = n_nodes;
+    // the radii of the bound nodes: a static scene's never change and go up once; a dynamic scene's are gathered per call
+    if (!s->dynamic && s->n_nodes != 0u) {
+        if (s->h_node_radius.size() != esz * (size_t)s->n_nodes || n_nodes != s->n_nodes) {
+            snprintf(g_err, sizeof g_err, "rt_scene_impacts: internal: the scene kept no radii for its %u nodes", s->n_nodes);
+            return RT_ERR_INVALID_ARGUMENT;
+        }
+        HIP_TRY(hipMemcpy(static_cast<uint8_t *>(s->d_impacts) + o_radius, s->h_node_radius.data(), s->h_node_radius.size(), hipMemcpyHostToDevice));
+    }
     return RT_OK;
 }
 
-template <typename T> struct ImpactsSpace { rt::Motion<T> *motion; T *length, *chunk; };
+template <typename T> struct ImpactsSpace { rt::Motion<T> *motion; T *length, *chunk, *magnitude, *radius; };
 template <typename T>
 ImpactsSpace<T> impacts_space(const rt_scene *s)
 {
     const size_t n = s->impacts_cap ? s->impacts_cap : 1;
+    const size_t n_chunks = (n + rt::kMotionChunk - 1) / rt::kMotionChunk;
     const size_t o_length = (4 * sizeof(T) * n + 255) & ~(size_t)255, o_chunk = o_length + ((sizeof(T) * n + 255) & ~(size_t)255);
+    const size_t o_magnitude = o_chunk + ((sizeof(T) * n_chunks + 255) & ~(size_t)255);
     uint8_t *const d = static_cast<uint8_t *>(s->d_impacts);
-    return { reinterpret_cast<rt::Motion<T> *>(d), reinterpret_cast<T *>(d + o_length), reinterpret_cast<T *>(d + o_chunk) };
+    return { reinterpret_cast<rt::Motion<T> *>(d), reinterpret_cast<T *>(d + o_length), reinterpret_cast<T *>(d + o_chunk), reinterpret_cast<T *>(d + o_magnitude),
+             reinterpret_cast<T *>(d + o_magnitude + 256) };
 }
 
 // The motion table, the first pass and the scan on `stream`.  counters != NULL runs the counting flavour (same counts).
@@ -1144,14 +1156,19 @@ rt_status enqueue_impacts_count(const rt_scene *s, const void *nodes, uint32_t n
     const uint32_t n = s->n_items;
     const ImpactsSpace<T> w = impacts_space<T>(s);
     const rt::Node<T> *const st = static_cast<const rt::Node<T> *>(nodes);
+    HIP_TRY(hipMemsetAsync(w.magnitude, 0, sizeof(T), stream));
     if (n_nodes != 0u) {
         const unsigned n_chunks = (n_nodes + rt::kMotionChunk - 1) / rt::kMotionChunk;
-        hipLaunchKernelGGL(rt::k_impact_motion_items<T>, dim3(n_chunks), dim3(rt::kMotionChunk), 0, stream, st, static_cast<const T *>(disp), n_nodes, n, w.motion, w.length, w.chunk);
-        hipLaunchKernelGGL(rt::k_impact_motion_bounds<T>, dim3((n_nodes + 255) / 256), dim3(256), 0, stream, st, n_nodes, w.length, w.chunk, w.motion);
+        if (s->dynamic && s->n_nodes != 0u && s->n_bounds != 0u)
+            hipLaunchKernelGGL(rt::k_impact_bound_radii<T>, dim3((s->n_bounds + 255) / 256), dim3(256), 0, stream, static_cast<const rt::Item<T> *>(s->d_bounds), s->d_bound_node,
+                               s->n_bounds, n_nodes, w.radius);
+        hipLaunchKernelGGL(rt::k_impact_motion_items<T>, dim3(n_chunks), dim3(rt::kMotionChunk), 0, stream, st, static_cast<const rt::Item<T> *>(s->d_items),
+                           s->n_nodes != 0u ? w.radius : nullptr, static_cast<const T *>(disp), n_nodes, n, w.motion, w.length, w.chunk, w.magnitude);
+        hipLaunchKernelGGL(rt::k_impact_motion_bounds<T>, dim3((n_nodes + 255) / 256), dim3(256), 0, stream, st, n_nodes, w.length, w.chunk, w.magnitude, w.motion);
         HIP_TRY(hipGetLastError());
     }
     const uint32_t *const item_node = s->n_nodes ? (s->d_item_node ? s->d_item_node : s->d_contacts_item_node) : nullptr;
-    const rt::ImpactArgs<T> a{ st, w.motion, item_node, s->d_contacts_counts, nullptr, nullptr, nullptr, counters, n_nodes, n, 0u };
+    const rt::ImpactArgs<T> a{ st, w.motion, w.magnitude, item_node, s->d_contacts_counts, nullptr, nullptr, nullptr, counters, n_nodes, n, 0u };
     const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
     if (counters) hipLaunchKernelGGL((rt::k_impact_pairs<T, true, false>), grid, block, 0, stream, a);
     else hipLaunchKernelGGL((rt::k_impact_pairs<T, false, false>), grid, block, 0, stream, a);
@@ -1178,7 +1195,8 @@ rt_status enqueue_impacts_fill(const rt_scene *s, const void *nodes, uint32_t n_
 {
     const uint32_t n = s->n_items;
     const uint32_t *const item_node = s->n_nodes ? (s->d_item_node ? s->d_item_node : s->d_contacts_item_node) : nullptr;
-    const rt::ImpactArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), impacts_space<T>(s).motion, item_node, nullptr, s->d_contacts_offsets, pairs, static_cast<T *>(time), nullptr,
+    const ImpactsSpace<T> w = impacts_space<T>(s);
+    const rt::ImpactArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), w.motion, w.magnitude, item_node, nullptr, s->d_contacts_offsets, pairs, static_cast<T *>(time), nullptr,
                                n_nodes, n, capacity };
     const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
     hipLaunchKernelGGL((rt::k_impact_pairs<T, false, true>), grid, block, 0, stream, a);

@@ -430,6 +430,8 @@ rt_status upload_streams(rt_scene *s, const void *items, const void *bounds, con
         return RT_ERR_UNSUPPORTED;
     }
     s->n_nodes = (uint32_t)raw.size();
+    s->h_node_radius.resize(sizeof(T) * raw.size());
+    for (size_t i = 0; i < raw.size(); ++i) memcpy(s->h_node_radius.data() + sizeof(T) * i, &raw[i].r, sizeof(T));
     const bool fused = raw_is_fused<T>(raw);
     s->fused = fused;
     StageClock clk;

@@ -145,15 +145,40 @@ def overlap_gaps(queries, spheres):
     return np.where((rr > 0)[None, :], gap, R(np.inf)).astype(R, copy=False)
 
 
-def pair_impacts(spheres, disp, i, j, inflate=None):
+def impact_scale(spheres, disp):
+    """S of rt_scene_impacts (include/rtrace_hip.h) for the records `spheres` (m x 4: cx, cy, cz, r) and their motion-table rows `disp`
+    (m x 3) -> a power of two in the arrays' dtype.  M is the largest of |cx|, |cy|, |cz|, r, |dx|, |dy|, |dz| over the records
+    with a positive rr -- the library takes it over the nodes of the scene's stream, bounds included (a bound's row is 0) -- and
+    S = 2^-e, M = f 2^e with 0.5 <= f < 1, e held to [MIN_EXP + 1, MAX_EXP - 2] so that S is a normal number; S = 1 when M is 0.
+    Every scaled magnitude is then below 1."""
+    s, d = np.asarray(spheres), np.asarray(disp)
+    R = s.dtype.type
+    with np.errstate(over="ignore", under="ignore"):
+        rr = s[:, 3] * s[:, 3]
+    solid = rr > 0
+    if not solid.any():
+        return R(1.0)
+    M = R(max(float(np.abs(s[solid, :3]).max()), float(np.abs(s[solid, 3]).max()), float(np.abs(d[solid]).max())))
+    if not M > 0:
+        return R(1.0)
+    fi = np.finfo(R)
+    e = min(max(int(np.frexp(M)[1]), fi.minexp + 1), fi.maxexp - 2)
+    return R(np.ldexp(1.0, -e))
+
+
+def pair_impacts(spheres, disp, i, j, inflate=None, scale=None):
     """The time of impact of the pairs (i[k], j[k]) of `spheres` (m x 4: cx, cy, cz, r) that move by `disp` (m x 3) during one step -- sphere
     k is at c_k + t d_k for t in [0, 1] -> REAL[len(i)], the metric of rt_scene_impacts restated in numpy bit for bit (include/rtrace_hip.h
-    states it), in the arrays' dtype (float32 or float64), every operation rounded once:
-    rr = r * r;  v = c_j - c_i;  w = d_i - d_j;  R = (sqrt(rr_j) + E_j) + sqrt(rr_i);  a = dot(w, w), b = dot(v, w), c = dot(v, v) - R * R,
-    disc = b*b - a*c;  t = +inf where not (rr_i > 0 and rr_j > 0), else 0 where not c > 0 (in contact at the start), else +inf where
-    not b > 0 or disc < 0 (not approaching, or passing by), else c / (b + sqrt(disc)).  The library always takes the lower slot as i.
-    `inflate` (REAL[m] or None: 0) is E, what the walk adds to the radius of a BOUND record: 0 for every item.  A record without a
-    positive rr -- radius 0: a dead slot -- is at +inf, in either place.  DeviceScene.impacts lists the pairs i < j with t <= 1."""
+    states it), in the arrays' dtype (float32 or float64), every operation rounded once.  Every input is first multiplied by S, a power
+    of two that brings the whole scene below 1 (impact_scale; `scale`: that of another set of records, None: impact_scale(spheres, disp)):
+    rr = r * r;  c' = c S;  r' = r S;  d' = d S;  E' = E S;  v = c_j' - c_i';  w = d_i' - d_j';  R = (r_j' + E_j') + r_i';
+    a = dot(w, w), b = dot(v, w), c = dot(v, v) - R * R, disc = b*b - a*c;  t = +inf where not (rr_i > 0 and rr_j > 0), else 0 where
+    not c > 0 (in contact at the start), else +inf where not b > 0 or disc < 0 (not approaching, or passing by), else
+    c / (b + sqrt(disc)).  t has no dimension and the products with S are exact, so S changes no bit of t as long as nothing leaves the
+    normal range -- which is what S is for: a, b and c are of the second degree in a length, disc of the fourth.  The library always
+    takes the lower slot as i.  `inflate` (REAL[m] or None: 0) is E, what the walk adds to the radius of a BOUND record: 0 for every item.
+    A record without a positive rr -- radius 0: a dead slot -- is at +inf, in either place, and does not contribute to S.
+    DeviceScene.impacts lists the pairs i < j with t <= 1."""
     s, d = np.asarray(spheres), np.asarray(disp)
     if s.dtype not in (np.float32, np.float64) or s.ndim != 2 or s.shape[1] != 4:
         raise ValueError("spheres must be an (m, 4) array of float32 or float64")
@@ -168,14 +193,20 @@ def pair_impacts(spheres, disp, i, j, inflate=None):
         raise ValueError("i and j must be integer arrays of one shape, (k,)")
     if i.size and (min(int(i.min()), int(j.min())) < 0 or max(int(i.max()), int(j.max())) >= s.shape[0]):
         raise ValueError("i and j must be rows of spheres")
-    rr = s[:, 3] * s[:, 3]
+    S = impact_scale(s, d) if scale is None else R(scale)
+    if not (S > 0 and np.isfinite(S) and np.frexp(S)[0] == 0.5):
+        raise ValueError("scale must be a positive power of two")
+    with np.errstate(over="ignore", under="ignore"):
+        rr = s[:, 3] * s[:, 3]
     rri, rrj = rr[i], rr[j]
     solid = (rri > 0) & (rrj > 0)
     one = R(1.0)
     with np.errstate(invalid="ignore", over="ignore", divide="ignore", under="ignore"):
-        v = s[j, :3] - s[i, :3]
+        cs, d, E = s[:, :3] * S, d * S, E * S
+        v = cs[j] - cs[i]
         w = d[i] - d[j]
-        rad = (np.sqrt(np.where(rrj > 0, rrj, one)) + E[j]) + np.sqrt(np.where(rri > 0, rri, one))
+        r = np.abs(s[:, 3]) * S
+        rad = (r[j] + E[j]) + r[i]
         RR = rad * rad
         a = (w[:, 0] * w[:, 0] + w[:, 1] * w[:, 1]) + w[:, 2] * w[:, 2]
         b = (v[:, 0] * w[:, 0] + v[:, 1] * w[:, 1]) + v[:, 2] * w[:, 2]

@@ -20,7 +20,14 @@ casts(c) -> (rays, radius, which, tmax): the 80 sphere casts of a Case (cast_fam
 full wave and a partly filled one; radii 0, a quarter of the median, 0.5 - 2 medians, half the root and three roots), and margins(c): the
 contact margins (0, r, -0.25 r, 4 r, +inf, -inf) with r the median placed item radius; ray_casts(c) -> (rays, zeros, tmax): the casts from
 outside the root with radius 0 and cutoffs of their own (default_rng(400 + k)), which are ray queries.  Made on first use, once per process, for the
-cast and contact tests (tests/test_scales_contact_host.py, tests/test_gpu_scales_contact.py); the other tests pay nothing for them."""
+cast and contact tests (tests/test_scales_contact_host.py, tests/test_gpu_scales_contact.py); the other tests pay nothing for them.
+
+overlap_queries(c) -> REAL[80, 4]: the query spheres of a Case for the overlap lists, drawn in the base scene's own frame and placed with
+the scene, so that under the translations c - p cancels as c - o does for rays; displacements(c, family) -> REAL[n, 3]: the "slow" and
+"fast" displacements of tests/test_gpu_impacts.py for the placed items; refit_twin(c) -> rta.Scene: the placed items under the case's
+ranges with refit bounds, which enclose (brute force applies); POW2 and pow2_scaled(items0, disp0, k, R): exact power-of-two scalings of a
+unit-scale scene and its displacements, under which the time of impact may not change a bit.  Made on first use, once per process, for
+tests/test_scales_overlap_host.py and tests/test_gpu_scales_overlap.py."""
 import functools
 
 import numpy as np
@@ -179,3 +186,65 @@ def sort_inputs(precision, n=300001, duplicates=1000, seed=41):
     s = np.concatenate([rng.uniform([-3.0, -2.0, 0.0], [3.0, 2.0, 6.0], (n, 3)), rng.uniform(0.01, 0.03, (n, 1))], axis=1)
     s[n - duplicates:, :3] = s[rng.choice(n - duplicates, duplicates, replace=False), :3]
     return np.ascontiguousarray(s[rng.permutation(n)].astype(R))
+
+
+N_OVERLAP_QUERIES = 80                       # one full wave and a partly filled one
+POW2 = (-66, -40, -33, 33, 45)               # exponents k of the exact scalings by 2^k of pow2_scaled
+
+
+def _index(c):
+    return [b[0] for b in base_scenes()].index(c.name)
+
+
+def overlap_queries(c):
+    """REAL[80, 4] of Case c: centres uniform in 1.2 times the base items' box about its centre, q uniform in [0, 0.3 extent] with every
+    tenth q = 0, drawn from default_rng(800 + k) in the base scene's frame and mapped through the case's placement, rounded once."""
+    from tests.test_gpu_impacts import extent
+    key = (c.precision, c.placement, c.name, "overlap queries")
+    if key not in _CASTS:
+        rng = np.random.default_rng(800 + _index(c))
+        it = np.asarray(c.items0, dtype=np.float64).reshape(-1, 4)
+        lo, hi = (it[:, :3] - it[:, 3:]).min(axis=0), (it[:, :3] + it[:, 3:]).max(axis=0)
+        mid, half = 0.5 * (lo + hi), 0.5 * (hi - lo)
+        centres = mid + rng.uniform(-1.2, 1.2, (N_OVERLAP_QUERIES, 3)) * half
+        q = rng.uniform(0.0, 0.3 * extent(it), N_OVERLAP_QUERIES)
+        q[::10] = 0.0
+        f = dict(placements(c.precision))[c.placement]
+        placed = f(np.concatenate([centres, q[:, None]], axis=1), None, EYE)[0]
+        queries = np.ascontiguousarray(placed.astype(REAL[c.precision]))
+        queries.setflags(write=False)
+        _CASTS[key] = queries
+    return _CASTS[key]
+
+
+def displacements(c, family):
+    """REAL[n, 3] of Case c: tests/test_gpu_impacts.py's displacements of the placed items, seed 900 + k; family "slow" (factors of the placed
+    median radius) or "fast" (of the placed extent)."""
+    from tests.test_gpu_impacts import displacements as make
+    key = (c.precision, c.placement, c.name, "displacements", family)
+    if key not in _CASTS:
+        disp = make(c.scene.items, 900 + _index(c), family, REAL[c.precision])
+        disp.setflags(write=False)
+        _CASTS[key] = disp
+    return _CASTS[key]
+
+
+def refit_twin(c):
+    """rta.Scene (host side): the items of Case c under its ranges -- the bounded twin's for a scene without bounds -- with
+    rta.refit_bounds, which enclose their items."""
+    key = (c.precision, c.placement, c.name, "refit twin")
+    if key not in _CASTS:
+        R = REAL[c.precision]
+        name = c.name[:-len("_flat")] if c.name.endswith("_flat") else c.name
+        ranges = next(b[3] for b in base_scenes() if b[0] == name)
+        items = np.ascontiguousarray(c.scene.items.astype(R))
+        bounds = rta.refit_bounds(items, ranges, c.precision)
+        _CASTS[key] = rta.Scene(items, rta.normalized(LIGHT, c.precision), c.eye, bounds, ranges, c.precision)
+    return _CASTS[key]
+
+
+def pow2_scaled(items0, disp0, k, R):
+    """(items REAL[n, 4], disp REAL[n, 3]): items0 and disp0, both already REAL, times 2^k -- exact as long as nothing leaves the normal range."""
+    items = np.ascontiguousarray(np.ldexp(np.asarray(items0, dtype=R), k).astype(R))
+    disp = np.ascontiguousarray(np.ldexp(np.asarray(disp0, dtype=R), k).astype(R))
+    return items, disp

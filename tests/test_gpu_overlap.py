@@ -414,16 +414,18 @@ def test_exclude_and_any_order_give_the_same_bytes(precision):
     d.close()
 
 
-def check_dynamic(d, items, live, ranges, precision, what):
+def check_dynamic(d, items, live, ranges, precision, what, queries=None):
     """overlaps() on dynamic scene d, which holds `items` with `live`, against the Walker over a fresh static scene (host side only) made
-    from the live items -- a dead slot is {0, 0, 0, 0}, which overlap_gaps puts at +inf as the walk does the dead record -- and bounds()."""
+    from the live items -- a dead slot is {0, 0, 0, 0}, which overlap_gaps puts at +inf as the walk does the dead record -- and bounds().
+    queries: REAL[n, 4], or None: 120 query spheres around a scene of unit size at the origin."""
     R = REAL[precision]
     live = np.asarray(live) != 0
     it = np.where(live[:, None], items, 0).astype(R)
     fresh = scene_of(it, d.bounds() if ranges is not None else None, ranges, precision)
-    rng = np.random.default_rng(78)
-    queries = np.concatenate([rng.uniform(-1.2, 1.2, (120, 3)), rng.uniform(0.0, 0.3, (120, 1))], axis=1).astype(R)
-    queries[::10, 3] = 0
+    if queries is None:
+        rng = np.random.default_rng(78)
+        queries = np.concatenate([rng.uniform(-1.2, 1.2, (120, 3)), rng.uniform(0.0, 0.3, (120, 1))], axis=1).astype(R)
+        queries[::10, 3] = 0
     w = Walker(fresh, queries)
     dead = np.flatnonzero(~live)
     r = float(np.median(it[live, 3])) if live.any() else 0.1
