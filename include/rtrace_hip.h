@@ -790,6 +790,70 @@ rt_status rt_scene_impacts(rt_scene *scene, const void *disp, uint32_t capacity,
 rt_status rt_scene_impacts_device(rt_scene *scene, const void *disp, uint32_t capacity, int32_t *pairs_out, void *time_out, uint64_t *offsets_out,
                                   uint64_t *total_out, rt_stats *stats, void *hip_stream);
 
+/* ---- swept overlap lists (additive to ABI 5): what moving spheres from OUTSIDE the scene come into contact with during one step ----
+ * rt_sweep_spheres moves an outside sphere against a standing scene and returns the first contact only.  rt_overlap_spheres lists every
+ * item an outside sphere touches, at one pose.  rt_scene_impacts covers a whole step with both bodies moving, but its queries are the
+ * scene's own items.  This entry takes a second set of bodies that moves during the step -- particles against level geometry, another
+ * scene's spheres, a projectile, a swept trigger volume -- while the resident scene may move too, and lists for every body every item it
+ * comes into contact with at some t in [0, 1], with that t and the contact normal.  The overlap lists' walk and list with the impact
+ * pairs' metric, scale and motion table.
+ *   queries is REAL[4n]: query g is {p.x, p.y, p.z, q}, the layout of a sphere array.  qdisp is REAL[3n]: query g is at p + t dq for t in
+ * [0, 1], dq = qdisp[3g .. 3g+3].  disp is REAL[3 n_items] or NULL: the items' displacements exactly as rt_scene_impacts takes them (a
+ * dead slot's row is not used); NULL means the scene stands still.  For a query and a node of the scene's stream with record {c, rr} and
+ * motion record {e', r' + E'} (the impact pairs' motion table, below), in REAL, every operation rounded once, no FMA, every root the IEEE
+ * one, every dot product (x*x' + y*y') + z*z':
+ *   p' = p S    q' = q S    dq' = dq S                         c', r', d', E' as for the impact pairs
+ *   v = c' - p'        w = dq' - e'         R = (r' + E') + q'      RR = R * R
+ *   a = dot(w, w)   b = dot(v, w)   cc = dot(v, v) - RR   disc = b*b - a*cc
+ *   t = +inf                       if !(rr > 0)
+ *     = 0                          else if !(cc > 0)              in contact at the start
+ *     = +inf                       else if !(b > 0) or disc < 0   not approaching (w = 0 too), or passing by
+ *     = cc / (b + sqrt(disc))      otherwise
+ * the impact pairs' formula with the query in the place of item i.  An item is LISTED when t <= 1; a bound CULLS when !(t <= 1).  A
+ * query whose q is not >= 0 (negative, NaN) carries no query: it makes no test and its row is empty.  q = 0 is a valid query, a moving
+ * point.  The excluded slot (exclude, as for rt_overlap_spheres) is tested and counted as a test, never listed and never counted as
+ * found.  A dead item (rr = -inf) is never listed whatever its disp row holds, a dead bound culls at its one test, and neither adds to S
+ * or to a bound's D.  rust_tracer_amd.swept_times restates t in numpy, bit for bit.
+ *   The normal of an entry (normal_out) is normalized(u), u = {w.x*t - v.x, w.y*t - v.y, w.z*t - v.z}, each product and each difference
+ * rounded once, normalized as everywhere here: u * (1 / sqrt(dot(u, u))).  u is the query's centre minus the touched sphere's centre at
+ * time t (times S): the normal points from the touched sphere to the query, the direction rt_sweep_spheres uses.  Centres that coincide
+ * at t = 0 give u = 0; the normal is then 0 * (1 / 0) = NaN in all three components -- there is no direction to report, and no special
+ * case.  rust_tracer_amd.swept_normals restates it.
+ *   S is the impact pairs' with the queries folded in: M is the largest of |C.x|, |C.y|, |C.z| and r over the stream's nodes with
+ * RRn > 0, of |d.x|, |d.y|, |d.z| over the items with rr > 0 (absent when disp is NULL), and of |p.x|, |p.y|, |p.z|, q, |dq.x|, |dq.y|,
+ * |dq.z| over ALL n queries with q >= 0 -- by query index, not through `order`, so S is the same in every order; S = 2^-e from M as
+ * for the impact pairs.  A query far from the scene therefore raises M, and the floor of 2^-31 M (f64: 2^-255 M) below which a length
+ * loses its fourth power counts from there: keep far-away bodies out of a batch whose scene is small.
+ *   The MOTION TABLE is the impact pairs', byte for byte, for the same disp and the same S; with disp == NULL every e and D is 0 and a
+ * bound is the static bound.  The walk is the overlap lists': every query walks the whole stream from node 0.  For an item the formula
+ * is the definition; for a bound it is the cast of the moving query against a standing sphere of radius r + D.  The result is the
+ * walk's: it differs from the definition over all items only where t lies within rounding of 1 or the pair grazes.
+ *   items_out (int32[capacity] or NULL): the item slot of every entry; time_out (REAL[capacity] or NULL; needs items_out): its t;
+ * normal_out (REAL[3 capacity] or NULL; needs items_out): its normal.  capacity, the exact prefix ("nothing behind it is touched"),
+ * capacity == 0 or items_out == NULL (the second walk is skipped), the order of the entries -- sorted by (g, item slot) --, the same
+ * bytes every time and in every order, offsets_out (uint64[n + 1] or NULL), *total_out (always the full count) and stats (primary =
+ * queries carried, hits = queries with an entry, the tests of the counting pass) behave exactly as for rt_overlap_spheres.
+ *   The counts, offsets and block sums are the overlap lists' workspace (it grows with the largest n seen); this entry's motion table is
+ * a second table of that workspace, sized as the impact pairs', made by the first swept call and freed with the scene.  A swept call
+ * takes its turn with overlap calls only and never waits for a contacts or impacts call. */
+/* Host memory.  RT_ERR_INVALID_ARGUMENT before the device is touched for a NULL scene, queries, qdisp or total_out, n == 0, a
+ * misaligned buffer (items_out, exclude, order 4 bytes; queries, qdisp, disp, time_out, normal_out REAL; offsets_out and total_out 8
+ * bytes), time_out or normal_out without items_out, capacity > 2^31 - 1, a buffer in device memory, a centre, qdisp or disp component
+ * that is not finite or beyond +-1e15, a q that is NaN, negative, infinite or above 1e15, and an order that is no permutation of
+ * 0 .. n-1.  Pinned memory is used in place, pageable memory goes through the call's device workspace.  Returns when the results are
+ * in place.  The call is a READ in the sense of ORDER above, on static, dynamic, live and flat scenes alike. */
+rt_status rt_swept_overlaps(rt_scene *scene, const void *queries, const void *qdisp, uint32_t n, const void *disp, const int32_t *exclude,
+                            const uint32_t *order, uint32_t capacity, int32_t *items_out, void *time_out, void *normal_out, uint64_t *offsets_out,
+                            uint64_t *total_out, rt_stats *stats);
+/* The same over DEVICE memory (total_out too), enqueued on `hip_stream` without a host synchronisation (but see the workspace above):
+ * only pointers, alignment, n and the capacity are checked.  An order entry >= n carries no query, and a query that no thread carries
+ * has count 0; any input bits give unspecified values, never a fault.  A call goes behind the overlap or swept call before it, whichever
+ * stream that was on.  Entries e >= *total_out keep the caller's bytes.  stats != NULL: filled after an internal synchronisation of
+ * hip_stream. */
+rt_status rt_swept_overlaps_device(rt_scene *scene, const void *queries, const void *qdisp, uint32_t n, const void *disp, const int32_t *exclude,
+                                   const uint32_t *order, uint32_t capacity, int32_t *items_out, void *time_out, void *normal_out,
+                                   uint64_t *offsets_out, uint64_t *total_out, rt_stats *stats, void *hip_stream);
+
 /* Bytes rt_render_tiles writes for this tile list (4 * total area), or 0 on an invalid list. */
 uint64_t rt_tiles_rgba_bytes(const rt_region *tiles, uint32_t n_tiles);
 

@@ -23,6 +23,7 @@
 #include "rt_contacts.hpp"
 #include "rt_overlap.hpp"
 #include "rt_impacts.hpp"
+#include "rt_swept.hpp"
 #include "rt_order.hpp"
 #include "rt_dynamic.hpp"
 #include "rt_rebuild.hpp"
@@ -323,6 +324,10 @@ struct rt_scene {
     hipEvent_t overlap_ev = nullptr;
     uint64_t *h_overlap_total = nullptr, *d_overlap_total = nullptr;        // one pinned word and its device alias, as h_contacts_total
     bool overlap_recorded = false;
+    // ---- swept overlap lists (rt_swept_overlaps*, rt_swept.hpp): a motion table of their own -- laid out as d_impacts -- that belongs to the
+    // overlap workspace: made by the first swept call under overlap_mu, used behind overlap_ev; counts, offsets and sums are the ones above
+    void *d_swept = nullptr;
+    uint32_t swept_cap = 0;            // nodes d_swept has room for
 };
 
 #include "rt_tight.hpp"

@@ -341,6 +341,7 @@ rt_status rt_scene_destroy(rt_scene *s)
     if (s->contacts_ev) (void)hipEventDestroy(s->contacts_ev);
     if (s->h_contacts_total) (void)hipHostFree(s->h_contacts_total);
     if (s->d_overlap) (void)hipFree(s->d_overlap);
+    if (s->d_swept) (void)hipFree(s->d_swept);
     if (s->overlap_ev) (void)hipEventDestroy(s->overlap_ev);
     if (s->h_overlap_total) (void)hipHostFree(s->h_overlap_total);
     if (s->d_cprim) (void)hipFree(s->d_cprim);
@@ -1807,6 +1808,151 @@ rt_status rt_overlap_spheres(rt_scene *s, const void *queries, uint32_t n, doubl
         st = enqueue_overlap_fill(s, nodes, n_nodes, b[0].dev, n, margin, d_exclude, d_order, capacity, reinterpret_cast<int32_t *>(b[3].dev), b[4].dev, c->stream);
         if (st != RT_OK) { (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return st; }
         for (int k = 3; k < 5; ++k)                                  // (only what was written: the caller's bytes behind it stay)
+            if (b[k].staged && b[k].host) HIP_DRAIN(hipMemcpyAsync(b[k].host, b[k].dev, b[k].unit * written, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (stats) {
+        HIP_DRAIN(hipEventRecord(c->ev1, c->stream));
+        return read_query_stats(c, c->stream, stats);                // synchronises the stream
+    }
+    HIP_DRAIN(hipStreamSynchronize(c->stream));
+#undef HIP_DRAIN
+    return RT_OK;
+}
+
+// ---- swept overlap lists: every sphere of the scene a moving outside sphere comes into contact with during one step (rt_swept.hpp) ----
+
+rt_status rt_swept_overlaps_device(rt_scene *s, const void *queries, const void *qdisp, uint32_t n, const void *disp, const int32_t *exclude, const uint32_t *order,
+                                   uint32_t capacity, int32_t *items_out, void *time_out, void *normal_out, uint64_t *offsets_out, uint64_t *total_out, rt_stats *stats,
+                                   void *hip_stream)
+{
+    const char *const what = "rt_swept_overlaps_device";
+    if (!swept_args_ok(s, queries, qdisp, n, disp, exclude, order, capacity, items_out, time_out, normal_out, offsets_out, total_out, what)) return RT_ERR_INVALID_ARGUMENT;
+    const ReadLock rl(s);
+    HIP_TRY(hipSetDevice(s->device));
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    const void *nodes = nullptr;
+    uint32_t n_nodes = 0;
+    rt_status st = query_stream(s, stream, &nodes, &n_nodes);
+    if (st != RT_OK) return st;
+    Context *c = nullptr;
+    Lease lease{ s, nullptr };
+    if (stats) {
+        if ((st = acquire(s, &c)) != RT_OK) return st;
+        lease.c = c;
+    }
+    {
+        // swept calls take their turn with overlap calls: they share the counts and the offsets
+        std::lock_guard<std::mutex> lk(s->overlap_mu);
+        if ((st = swept_begin(s, n, n_nodes, stream)) != RT_OK) return st;
+        if (stats) {
+            HIP_TRY(hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, stream));
+            HIP_TRY(hipEventRecord(c->ev0, stream));
+        }
+        st = enqueue_swept_count(s, nodes, n_nodes, queries, qdisp, n, disp, exclude, order, offsets_out, total_out, stats ? c->d_counters : nullptr, stream);
+        if (st == RT_OK && capacity != 0u && items_out)
+            st = enqueue_swept_fill(s, nodes, n_nodes, queries, qdisp, n, exclude, order, capacity, items_out, time_out, normal_out, stream);
+        // whatever was enqueued uses the workspace: the next call goes behind it
+        if (hipEventRecord(s->overlap_ev, stream) == hipSuccess) s->overlap_recorded = true;
+        else { (void)hipGetLastError(); (void)hipStreamSynchronize(stream); }
+    }
+    if (!stats) return st;
+    (void)hipEventRecord(c->ev1, stream);
+    if (st != RT_OK) { (void)hipGetLastError(); lease.inflight = true; return st; }      // (the context goes back behind what is enqueued)
+    return read_query_stats(c, stream, stats);
+}
+
+rt_status rt_swept_overlaps(rt_scene *s, const void *queries, const void *qdisp, uint32_t n, const void *disp, const int32_t *exclude, const uint32_t *order,
+                            uint32_t capacity, int32_t *items_out, void *time_out, void *normal_out, uint64_t *offsets_out, uint64_t *total_out, rt_stats *stats)
+{
+    const char *const what = "rt_swept_overlaps";
+    if (!swept_args_ok(s, queries, qdisp, n, disp, exclude, order, capacity, items_out, time_out, normal_out, offsets_out, total_out, what)) return RT_ERR_INVALID_ARGUMENT;
+    const bool f32 = s->precision == RT_F32;
+    if (!(f32 ? overlap_queries_valid(static_cast<const float *>(queries), n, what) : overlap_queries_valid(static_cast<const double *>(queries), n, what)))
+        return RT_ERR_INVALID_ARGUMENT;
+    if (!(f32 ? swept_qdisp_valid(static_cast<const float *>(qdisp), n, what) : swept_qdisp_valid(static_cast<const double *>(qdisp), n, what)))
+        return RT_ERR_INVALID_ARGUMENT;
+    if (order && !order_is_permutation(order, n, what)) return RT_ERR_INVALID_ARGUMENT;
+    // pinned buffers are read and written by the kernels in place, pageable ones go through the call's workspace (as rt_overlap_spheres)
+    const bool fill = capacity != 0u && items_out;
+    const size_t esz = f32 ? sizeof(float) : sizeof(double);
+    struct Buf { void *host; size_t bytes, unit; bool out; uint8_t *dev; size_t off; bool staged; };
+    Buf b[9] = { { const_cast<void *>(queries), 4 * esz * (size_t)n, 0, false, nullptr, 0, false },
+                 { const_cast<void *>(qdisp), 3 * esz * (size_t)n, 0, false, nullptr, 0, false },
+                 { const_cast<void *>(disp), 3 * esz * (size_t)s->n_items, 0, false, nullptr, 0, false },
+                 { const_cast<int32_t *>(exclude), sizeof(int32_t) * (size_t)n, 0, false, nullptr, 0, false },
+                 { const_cast<uint32_t *>(order), sizeof(uint32_t) * (size_t)n, 0, false, nullptr, 0, false },
+                 { fill ? items_out : nullptr, sizeof(int32_t) * (size_t)capacity, sizeof(int32_t), true, nullptr, 0, false },
+                 { fill ? time_out : nullptr, esz * (size_t)capacity, esz, true, nullptr, 0, false },
+                 { fill ? normal_out : nullptr, 3 * esz * (size_t)capacity, 3 * esz, true, nullptr, 0, false },
+                 { offsets_out, sizeof(uint64_t) * ((size_t)n + 1), 0, true, nullptr, 0, false } };
+    size_t need = 0;
+    for (Buf &x : b) {
+        if (!x.host) continue;
+        const HostDest d = classify_host_pointer(x.host);
+        if (d.bad) {
+            snprintf(g_err, sizeof g_err, "%s: a buffer is device memory; use %s_device", what, what);
+            return RT_ERR_INVALID_ARGUMENT;
+        }
+        if (d.pinned && d.dev_alias && d.room >= x.bytes) { x.dev = d.dev_alias; continue; }
+        x.staged = true;
+        x.off = need;
+        need += (x.bytes + 255) & ~(size_t)255;
+    }
+    if (classify_host_pointer(total_out).bad) {
+        snprintf(g_err, sizeof g_err, "%s: a buffer is device memory; use %s_device", what, what);
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    if (disp && !(f32 ? impacts_disp_valid(static_cast<const float *>(disp), s->n_items, what) : impacts_disp_valid(static_cast<const double *>(disp), s->n_items, what)))
+        return RT_ERR_INVALID_ARGUMENT;
+    const ReadLock rl(s);
+    HIP_TRY(hipSetDevice(s->device));
+    rt_status st = RT_OK;
+    Context *c = nullptr;
+    if ((st = acquire(s, &c)) != RT_OK) return st;
+    Lease lease{ s, c };
+    const void *nodes = nullptr;
+    uint32_t n_nodes = 0;
+    if ((st = query_stream(s, c->stream, &nodes, &n_nodes)) != RT_OK) return st;
+    if (need > c->query_cap) {
+        if (c->d_query) HIP_TRY(hipFree(c->d_query));
+        c->d_query = nullptr; c->query_cap = 0;
+        HIP_TRY(hipMalloc(&c->d_query, need));
+        c->query_cap = need;
+    }
+    for (Buf &x : b)
+        if (x.staged) x.dev = static_cast<uint8_t *>(c->d_query) + x.off;
+    // the two passes share the scene's overlap workspace and this call reads the total between them: host calls on one scene take turns,
+    // overlap and swept alike
+    std::lock_guard<std::mutex> lk(s->overlap_mu);
+    if ((st = swept_begin(s, n, n_nodes, c->stream)) != RT_OK) return st;
+    // from here on work of this call may be queued: an error return first waits for it
+#define HIP_DRAIN(expr)                                                                                                   \
+    do {                                                                                                                  \
+        hipError_t e__ = (expr);                                                                                          \
+        if (e__ != hipSuccess) { (void)hipStreamSynchronize(c->stream); return hip_fail(e__, #expr, __LINE__); }          \
+    } while (0)
+    for (const Buf &x : b)
+        if (x.staged && !x.out)
+            HIP_DRAIN(hipMemcpyAsync(x.dev, x.host, x.bytes, hipMemcpyHostToDevice, c->stream));
+    if (stats) {
+        HIP_DRAIN(hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, c->stream));
+        HIP_DRAIN(hipEventRecord(c->ev0, c->stream));
+    }
+    const int32_t *const d_exclude = reinterpret_cast<const int32_t *>(b[3].dev);
+    const uint32_t *const d_order = reinterpret_cast<const uint32_t *>(b[4].dev);
+    // the scan writes the total into the scene's pinned word, as rt_overlap_spheres has it
+    st = enqueue_swept_count(s, nodes, n_nodes, b[0].dev, b[1].dev, n, b[2].dev, d_exclude, d_order, reinterpret_cast<uint64_t *>(b[8].dev), s->d_overlap_total,
+                             stats ? c->d_counters : nullptr, c->stream);
+    if (st != RT_OK) { (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return st; }
+    if (b[8].staged) HIP_DRAIN(hipMemcpyAsync(b[8].host, b[8].dev, b[8].bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_DRAIN(hipStreamSynchronize(c->stream));
+    const uint64_t total = *static_cast<volatile uint64_t *>(s->h_overlap_total);
+    *total_out = total;
+    const size_t written = (size_t)std::min<uint64_t>(total, capacity);
+    if (fill && written) {
+        st = enqueue_swept_fill(s, nodes, n_nodes, b[0].dev, b[1].dev, n, d_exclude, d_order, capacity, reinterpret_cast<int32_t *>(b[5].dev), b[6].dev, b[7].dev, c->stream);
+        if (st != RT_OK) { (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return st; }
+        for (int k = 5; k < 8; ++k)                                  // (only what was written: the caller's bytes behind it stay)
             if (b[k].staged && b[k].host) HIP_DRAIN(hipMemcpyAsync(b[k].host, b[k].dev, b[k].unit * written, hipMemcpyDeviceToHost, c->stream));
     }
     if (stats) {

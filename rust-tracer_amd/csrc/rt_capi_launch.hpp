@@ -1107,45 +1107,71 @@ bool impacts_disp_valid(const T *disp, uint32_t n_items, const char *what)
     return true;
 }
 
-// contacts_begin, and room for the motion table of `n_nodes` nodes.  Under s->contacts_mu.
-rt_status impacts_begin(rt_scene *s, const void *nodes, uint32_t n_nodes, hipStream_t stream)
+// Room for a motion table of `n_nodes` nodes in *table (its nodes' lengths, their chunk maxima, the call's magnitude and the bound nodes'
+// radii behind it).  `ev` / `recorded`: the event behind which the calls that use this table run -- a table that has to grow waits for it.
+rt_status motion_table_begin(rt_scene *s, void **table, uint32_t *cap, uint32_t n_nodes, hipEvent_t ev, bool recorded, const char *what)
 {
-    const rt_status st = contacts_begin(s, nodes, n_nodes, stream);
-    if (st != RT_OK) return st;
-    if (n_nodes <= s->impacts_cap && s->d_impacts) return RT_OK;
-    if (s->d_impacts) {
-        if (s->contacts_recorded) HIP_TRY(hipEventSynchronize(s->contacts_ev));
-        HIP_TRY(hipFree(s->d_impacts));
-        s->d_impacts = nullptr; s->impacts_cap = 0;
+    if (n_nodes <= *cap && *table) return RT_OK;
+    if (*table) {
+        if (recorded) HIP_TRY(hipEventSynchronize(ev));
+        HIP_TRY(hipFree(*table));
+        *table = nullptr; *cap = 0;
     }
     const size_t esz = s->precision == RT_F32 ? sizeof(float) : sizeof(double);
     const size_t n = n_nodes ? n_nodes : 1, n_chunks = (n + rt::kMotionChunk - 1) / rt::kMotionChunk;
     const size_t o_length = (4 * esz * n + 255) & ~(size_t)255, o_chunk = o_length + ((esz * n + 255) & ~(size_t)255);
     const size_t o_radius = o_chunk + ((esz * n_chunks + 255) & ~(size_t)255) + 256;                   // (+ the call's magnitude, a word of its own)
-    HIP_TRY(hipMalloc(&s->d_impacts, o_radius + ((esz * n + 255) & ~(size_t)255)));
-    s->impacts_cap = n_nodes;
+    HIP_TRY(hipMalloc(table, o_radius + ((esz * n + 255) & ~(size_t)255)));
+    *cap = n_nodes;
     // the radii of the bound nodes: a static scene's never change and go up once; a dynamic scene's are gathered per call
     if (!s->dynamic && s->n_nodes != 0u) {
         if (s->h_node_radius.size() != esz * (size_t)s->n_nodes || n_nodes != s->n_nodes) {
-            snprintf(g_err, sizeof g_err, "rt_scene_impacts: internal: the scene kept no radii for its %u nodes", s->n_nodes);
+            snprintf(g_err, sizeof g_err, "%s: internal: the scene kept no radii for its %u nodes", what, s->n_nodes);
             return RT_ERR_INVALID_ARGUMENT;
         }
-        HIP_TRY(hipMemcpy(static_cast<uint8_t *>(s->d_impacts) + o_radius, s->h_node_radius.data(), s->h_node_radius.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(static_cast<uint8_t *>(*table) + o_radius, s->h_node_radius.data(), s->h_node_radius.size(), hipMemcpyHostToDevice));
     }
     return RT_OK;
 }
 
+// contacts_begin, and room for the motion table of `n_nodes` nodes.  Under s->contacts_mu.
+rt_status impacts_begin(rt_scene *s, const void *nodes, uint32_t n_nodes, hipStream_t stream)
+{
+    const rt_status st = contacts_begin(s, nodes, n_nodes, stream);
+    if (st != RT_OK) return st;
+    return motion_table_begin(s, &s->d_impacts, &s->impacts_cap, n_nodes, s->contacts_ev, s->contacts_recorded, "rt_scene_impacts");
+}
+
 template <typename T> struct ImpactsSpace { rt::Motion<T> *motion; T *length, *chunk, *magnitude, *radius; };
 template <typename T>
-ImpactsSpace<T> impacts_space(const rt_scene *s)
+ImpactsSpace<T> motion_table_space(void *table, uint32_t cap)
 {
-    const size_t n = s->impacts_cap ? s->impacts_cap : 1;
+    const size_t n = cap ? cap : 1;
     const size_t n_chunks = (n + rt::kMotionChunk - 1) / rt::kMotionChunk;
     const size_t o_length = (4 * sizeof(T) * n + 255) & ~(size_t)255, o_chunk = o_length + ((sizeof(T) * n + 255) & ~(size_t)255);
     const size_t o_magnitude = o_chunk + ((sizeof(T) * n_chunks + 255) & ~(size_t)255);
-    uint8_t *const d = static_cast<uint8_t *>(s->d_impacts);
+    uint8_t *const d = static_cast<uint8_t *>(table);
     return { reinterpret_cast<rt::Motion<T> *>(d), reinterpret_cast<T *>(d + o_length), reinterpret_cast<T *>(d + o_chunk), reinterpret_cast<T *>(d + o_magnitude),
              reinterpret_cast<T *>(d + o_magnitude + 256) };
+}
+template <typename T>
+ImpactsSpace<T> impacts_space(const rt_scene *s) { return motion_table_space<T>(s->d_impacts, s->impacts_cap); }
+
+// The motion table of one call into `w`, on `stream`: *w.magnitude must already be 0 or hold what the call folds in besides the scene.
+// disp == NULL: the scene stands still (every e and D is 0).
+template <typename T>
+rt_status enqueue_motion_table(const rt_scene *s, const rt::Node<T> *st, uint32_t n_nodes, const T *disp, const ImpactsSpace<T> &w, hipStream_t stream)
+{
+    if (n_nodes == 0u) return RT_OK;
+    const unsigned n_chunks = (n_nodes + rt::kMotionChunk - 1) / rt::kMotionChunk;
+    if (s->dynamic && s->n_nodes != 0u && s->n_bounds != 0u)
+        hipLaunchKernelGGL(rt::k_impact_bound_radii<T>, dim3((s->n_bounds + 255) / 256), dim3(256), 0, stream, static_cast<const rt::Item<T> *>(s->d_bounds), s->d_bound_node,
+                           s->n_bounds, n_nodes, w.radius);
+    hipLaunchKernelGGL(rt::k_impact_motion_items<T>, dim3(n_chunks), dim3(rt::kMotionChunk), 0, stream, st, static_cast<const rt::Item<T> *>(s->d_items),
+                       s->n_nodes != 0u ? w.radius : nullptr, disp, n_nodes, s->n_items, w.motion, w.length, w.chunk, w.magnitude);
+    hipLaunchKernelGGL(rt::k_impact_motion_bounds<T>, dim3((n_nodes + 255) / 256), dim3(256), 0, stream, st, n_nodes, w.length, w.chunk, w.magnitude, w.motion);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
 }
 
 // The motion table, the first pass and the scan on `stream`.  counters != NULL runs the counting flavour (same counts).
@@ -1157,16 +1183,7 @@ rt_status enqueue_impacts_count(const rt_scene *s, const void *nodes, uint32_t n
     const ImpactsSpace<T> w = impacts_space<T>(s);
     const rt::Node<T> *const st = static_cast<const rt::Node<T> *>(nodes);
     HIP_TRY(hipMemsetAsync(w.magnitude, 0, sizeof(T), stream));
-    if (n_nodes != 0u) {
-        const unsigned n_chunks = (n_nodes + rt::kMotionChunk - 1) / rt::kMotionChunk;
-        if (s->dynamic && s->n_nodes != 0u && s->n_bounds != 0u)
-            hipLaunchKernelGGL(rt::k_impact_bound_radii<T>, dim3((s->n_bounds + 255) / 256), dim3(256), 0, stream, static_cast<const rt::Item<T> *>(s->d_bounds), s->d_bound_node,
-                               s->n_bounds, n_nodes, w.radius);
-        hipLaunchKernelGGL(rt::k_impact_motion_items<T>, dim3(n_chunks), dim3(rt::kMotionChunk), 0, stream, st, static_cast<const rt::Item<T> *>(s->d_items),
-                           s->n_nodes != 0u ? w.radius : nullptr, static_cast<const T *>(disp), n_nodes, n, w.motion, w.length, w.chunk, w.magnitude);
-        hipLaunchKernelGGL(rt::k_impact_motion_bounds<T>, dim3((n_nodes + 255) / 256), dim3(256), 0, stream, st, n_nodes, w.length, w.chunk, w.magnitude, w.motion);
-        HIP_TRY(hipGetLastError());
-    }
+    if (const rt_status mt = enqueue_motion_table<T>(s, st, n_nodes, static_cast<const T *>(disp), w, stream); mt != RT_OK) return mt;
     const uint32_t *const item_node = s->n_nodes ? (s->d_item_node ? s->d_item_node : s->d_contacts_item_node) : nullptr;
     const rt::ImpactArgs<T> a{ st, w.motion, w.magnitude, item_node, s->d_contacts_counts, nullptr, nullptr, nullptr, counters, n_nodes, n, 0u };
     const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
@@ -1332,6 +1349,111 @@ rt_status enqueue_overlap_fill(const rt_scene *s, const void *nodes, uint32_t n_
 {
     return s->precision == RT_F32 ? enqueue_overlap_fill<float>(s, nodes, n_nodes, queries, n, margin, exclude, order, capacity, items, gap, stream)
                                   : enqueue_overlap_fill<double>(s, nodes, n_nodes, queries, n, margin, exclude, order, capacity, items, gap, stream);
+}
+
+// ---- swept overlap lists (rt_swept_overlaps*, rt_swept.hpp) ----
+
+// What both swept entries check (device pointers are not dereferenced here).
+bool swept_args_ok(const rt_scene *s, const void *queries, const void *qdisp, uint32_t n, const void *disp, const int32_t *exclude, const uint32_t *order,
+                   uint32_t capacity, const int32_t *items, const void *time, const void *normal, const uint64_t *offsets, const uint64_t *total, const char *what)
+{
+    if (!s) { snprintf(g_err, sizeof g_err, "%s: NULL scene", what); return false; }
+    if (!queries) { snprintf(g_err, sizeof g_err, "%s: NULL queries", what); return false; }
+    if (!qdisp) { snprintf(g_err, sizeof g_err, "%s: NULL qdisp", what); return false; }
+    if (!total) { snprintf(g_err, sizeof g_err, "%s: NULL total_out", what); return false; }
+    if (n == 0) { snprintf(g_err, sizeof g_err, "%s: n == 0", what); return false; }
+    if (capacity > 0x7FFFFFFFu) { snprintf(g_err, sizeof g_err, "%s: capacity %u is above 2^31 - 1", what, capacity); return false; }
+    if (time && !items) { snprintf(g_err, sizeof g_err, "%s: time_out without items_out", what); return false; }
+    if (normal && !items) { snprintf(g_err, sizeof g_err, "%s: normal_out without items_out", what); return false; }
+    const struct { const void *p; const char *name; } words[] = { { items, "items_out" }, { exclude, "exclude" }, { order, "order" } };
+    for (const auto &w : words)
+        if ((reinterpret_cast<uintptr_t>(w.p) & 3u) != 0) { snprintf(g_err, sizeof g_err, "%s: %s must be 4-byte aligned", what, w.name); return false; }
+    const struct { const void *p; const char *name; } longs[] = { { offsets, "offsets_out" }, { total, "total_out" } };
+    for (const auto &w : longs)
+        if ((reinterpret_cast<uintptr_t>(w.p) & 7u) != 0) { snprintf(g_err, sizeof g_err, "%s: %s must be 8-byte aligned", what, w.name); return false; }
+    const uintptr_t esz = s->precision == RT_F32 ? sizeof(float) : sizeof(double);
+    const struct { const void *p; const char *name; } reals[] = { { queries, "queries" }, { qdisp, "qdisp" }, { disp, "disp" }, { time, "time_out" }, { normal, "normal_out" } };
+    for (const auto &w : reals)
+        if ((reinterpret_cast<uintptr_t>(w.p) % esz) != 0) { snprintf(g_err, sizeof g_err, "%s: %s must be %u-byte aligned", what, w.name, (unsigned)esz); return false; }
+    return true;
+}
+
+// The host entry's domain for the queries' displacements: every component finite and within +-1e15, as a scene's own.
+template <typename T>
+bool swept_qdisp_valid(const T *qdisp, uint32_t n, const char *what)
+{
+    for (size_t k = 0; k < 3 * (size_t)n; ++k)
+        if (!std::isfinite(qdisp[k]) || std::fabs((double)qdisp[k]) > 1e15) {
+            snprintf(g_err, sizeof g_err, "%s: qdisp of query %u has a non-finite component or one beyond +-1e15", what, (unsigned)(k / 3));
+            return false;
+        }
+    return true;
+}
+
+// overlap_begin, and room for this entry's motion table of `n_nodes` nodes.  Under s->overlap_mu.
+rt_status swept_begin(rt_scene *s, uint32_t n, uint32_t n_nodes, hipStream_t stream)
+{
+    const rt_status st = overlap_begin(s, n, stream);
+    if (st != RT_OK) return st;
+    return motion_table_begin(s, &s->d_swept, &s->swept_cap, n_nodes, s->overlap_ev, s->overlap_recorded, "rt_swept_overlaps");
+}
+
+// The queries' magnitude, the motion table, the first pass and the scan on `stream`.  counters != NULL runs the counting flavour (same
+// counts).  With an order a query that no thread carries keeps the count 0.
+template <typename T>
+rt_status enqueue_swept_count(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *queries, const void *qdisp, uint32_t n, const void *disp,
+                              const int32_t *exclude, const uint32_t *order, uint64_t *offsets_out, uint64_t *total_out, rt::Counters *counters, hipStream_t stream)
+{
+    const ImpactsSpace<T> w = motion_table_space<T>(s->d_swept, s->swept_cap);
+    const rt::Node<T> *const st = static_cast<const rt::Node<T> *>(nodes);
+    HIP_TRY(hipMemsetAsync(w.magnitude, 0, sizeof(T), stream));
+    hipLaunchKernelGGL(rt::k_swept_query_magnitude<T>, dim3((unsigned)(((uint64_t)n + 255) / 256)), dim3(256), 0, stream, static_cast<const T *>(queries),
+                       static_cast<const T *>(qdisp), n, w.magnitude);
+    HIP_TRY(hipGetLastError());
+    if (const rt_status mt = enqueue_motion_table<T>(s, st, n_nodes, static_cast<const T *>(disp), w, stream); mt != RT_OK) return mt;
+    const rt::SweptArgs<T> a{ st, w.motion, w.magnitude, static_cast<const T *>(queries), static_cast<const T *>(qdisp), exclude, order, s->d_overlap_counts, nullptr,
+                              nullptr, nullptr, nullptr, counters, n_nodes, n, 0u };
+    if (order) HIP_TRY(hipMemsetAsync(s->d_overlap_counts, 0, sizeof(uint32_t) * (size_t)n, stream));
+    const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
+    if (counters) hipLaunchKernelGGL((rt::k_swept_overlaps<T, true, false>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((rt::k_swept_overlaps<T, false, false>), grid, block, 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    const unsigned n_sums = (unsigned)(((uint64_t)n + rt::kScanBlock - 1) / rt::kScanBlock);
+    const dim3 sgrid(n_sums), sblock(rt::kScanBlock);
+    hipLaunchKernelGGL(rt::k_contact_scan_sums, sgrid, sblock, 0, stream, s->d_overlap_counts, n, s->d_overlap_sums);
+    hipLaunchKernelGGL(rt::k_contact_scan_spine, dim3(1), sblock, 0, stream, s->d_overlap_sums, n_sums, s->d_overlap_offsets + n, offsets_out ? offsets_out + n : nullptr, total_out);
+    hipLaunchKernelGGL(rt::k_contact_scan_offsets, sgrid, sblock, 0, stream, s->d_overlap_counts, n, s->d_overlap_sums, s->d_overlap_offsets, offsets_out);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+rt_status enqueue_swept_count(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *queries, const void *qdisp, uint32_t n, const void *disp,
+                              const int32_t *exclude, const uint32_t *order, uint64_t *offsets_out, uint64_t *total_out, rt::Counters *counters, hipStream_t stream)
+{
+    return s->precision == RT_F32 ? enqueue_swept_count<float>(s, nodes, n_nodes, queries, qdisp, n, disp, exclude, order, offsets_out, total_out, counters, stream)
+                                  : enqueue_swept_count<double>(s, nodes, n_nodes, queries, qdisp, n, disp, exclude, order, offsets_out, total_out, counters, stream);
+}
+
+// The second pass on `stream`: the same walk over the motion table the first pass left, by the queries that counted something; entry
+// offsets[g] + rank written where it lies below `capacity`.
+template <typename T>
+rt_status enqueue_swept_fill(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *queries, const void *qdisp, uint32_t n, const int32_t *exclude,
+                             const uint32_t *order, uint32_t capacity, int32_t *items, void *time, void *normal, hipStream_t stream)
+{
+    const ImpactsSpace<T> w = motion_table_space<T>(s->d_swept, s->swept_cap);
+    const rt::SweptArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), w.motion, w.magnitude, static_cast<const T *>(queries), static_cast<const T *>(qdisp), exclude, order,
+                              s->d_overlap_counts, s->d_overlap_offsets, items, static_cast<T *>(time), static_cast<T *>(normal), nullptr, n_nodes, n, capacity };
+    const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
+    hipLaunchKernelGGL((rt::k_swept_overlaps<T, false, true>), grid, block, 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+rt_status enqueue_swept_fill(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *queries, const void *qdisp, uint32_t n, const int32_t *exclude,
+                             const uint32_t *order, uint32_t capacity, int32_t *items, void *time, void *normal, hipStream_t stream)
+{
+    return s->precision == RT_F32 ? enqueue_swept_fill<float>(s, nodes, n_nodes, queries, qdisp, n, exclude, order, capacity, items, time, normal, stream)
+                                  : enqueue_swept_fill<double>(s, nodes, n_nodes, queries, qdisp, n, exclude, order, capacity, items, time, normal, stream);
 }
 
 // ---- traced rays and camera frames (rt_trace_rays*, rt_render_camera*, rt_trace.hpp) ----

@@ -204,7 +204,8 @@ __global__ __launch_bounds__(256) void k_impact_bound_radii(const Item<T> *__res
 
 // Thread i looks at node i: an ITEM node of slot j takes {d_j, r_j} (k_impact_motion_bounds scales it) and the length m_j (radius and
 // length 0 without a positive rr), a BOUND node {0, 0, 0, r} and the length 0 (k_impact_motion_bounds finishes its record).  Block b leaves the largest length of its kMotionChunk
-// nodes in chunk[b] and folds the largest magnitude of its nodes into *magnitude, which the caller has set to 0.
+// nodes in chunk[b] and folds the largest magnitude of its nodes into *magnitude, which the caller has set to 0.  disp == NULL (rt_swept.hpp:
+// the scene stands still) is a displacement of 0 for every slot.
 template <typename T>
 __global__ __launch_bounds__(kMotionChunk) void k_impact_motion_items(const Node<T> *__restrict__ stream, const Item<T> *__restrict__ items,
                                                                       const T *__restrict__ bound_radius, const T *__restrict__ disp, unsigned n_nodes, unsigned n_items,
@@ -226,7 +227,7 @@ __global__ __launch_bounds__(kMotionChunk) void k_impact_motion_items(const Node
             g = max_rn(max_rn(abs_rn(stream[i].a0), abs_rn(stream[i].a1)), max_rn(abs_rn(stream[i].a2), r));
         }
         if (item) {
-            const T dx = disp[3 * (size_t)slot], dy = disp[3 * (size_t)slot + 1], dz = disp[3 * (size_t)slot + 2];
+            const T dx = disp ? disp[3 * (size_t)slot] : T(0.0), dy = disp ? disp[3 * (size_t)slot + 1] : T(0.0), dz = disp ? disp[3 * (size_t)slot + 2] : T(0.0);
             motion[i] = { dx, dy, dz, r };
             if (alive) {
                 const T s = (dx * dx + dy * dy) + dz * dz;

@@ -145,20 +145,29 @@ def overlap_gaps(queries, spheres):
     return np.where((rr > 0)[None, :], gap, R(np.inf)).astype(R, copy=False)
 
 
-def impact_scale(spheres, disp):
+def impact_scale(spheres, disp, queries=None, qdisp=None):
     """S of rt_scene_impacts (include/rtrace_hip.h) for the records `spheres` (m x 4: cx, cy, cz, r) and their motion-table rows `disp`
-    (m x 3) -> a power of two in the arrays' dtype.  M is the largest of |cx|, |cy|, |cz|, r, |dx|, |dy|, |dz| over the records
+    (m x 3, or None: 0) -> a power of two in the arrays' dtype.  M is the largest of |cx|, |cy|, |cz|, r, |dx|, |dy|, |dz| over the records
     with a positive rr -- the library takes it over the nodes of the scene's stream, bounds included (a bound's row is 0) -- and
     S = 2^-e, M = f 2^e with 0.5 <= f < 1, e held to [MIN_EXP + 1, MAX_EXP - 2] so that S is a normal number; S = 1 when M is 0.
-    Every scaled magnitude is then below 1."""
-    s, d = np.asarray(spheres), np.asarray(disp)
+    Every scaled magnitude is then below 1.  `queries` (n x 4: px, py, pz, q) with `qdisp` (n x 3) gives S of rt_swept_overlaps: M also
+    covers |px|, |py|, |pz|, q, |dqx|, |dqy|, |dqz| over the queries with q >= 0."""
+    s = np.asarray(spheres)
     R = s.dtype.type
+    d = np.zeros((s.shape[0], 3), R) if disp is None else np.asarray(disp)
     with np.errstate(over="ignore", under="ignore"):
         rr = s[:, 3] * s[:, 3]
     solid = rr > 0
-    if not solid.any():
-        return R(1.0)
-    M = R(max(float(np.abs(s[solid, :3]).max()), float(np.abs(s[solid, 3]).max()), float(np.abs(d[solid]).max())))
+    M = 0.0
+    if solid.any():
+        M = max(float(np.abs(s[solid, :3]).max()), float(np.abs(s[solid, 3]).max()), float(np.abs(d[solid]).max()))
+    if queries is not None:
+        qs, qd = np.asarray(queries), np.asarray(qdisp)
+        with np.errstate(invalid="ignore"):
+            carried = qs[:, 3] >= 0
+        if carried.any():
+            M = max(M, float(np.abs(qs[carried, :3]).max()), float(qs[carried, 3].max()), float(np.abs(qd[carried]).max()))
+    M = R(M)
     if not M > 0:
         return R(1.0)
     fi = np.finfo(R)
@@ -216,6 +225,74 @@ def pair_impacts(spheres, disp, i, j, inflate=None, scale=None):
         t = np.where(root, c / (b + np.sqrt(np.where(root, disc, one))), R(np.inf))
         t = np.where(c > 0, t, R(0.0))
     return np.where(solid, t, R(np.inf)).astype(R, copy=False)
+
+
+def _swept_terms(queries, qdisp, spheres, disp, inflate, scale):
+    """(t, v, w) of swept_times: REAL[n, m], REAL[n, m, 3], REAL[n, m, 3]."""
+    qs, qd, s = np.asarray(queries), np.asarray(qdisp), np.asarray(spheres)
+    if qs.dtype not in (np.float32, np.float64) or qs.ndim != 2 or qs.shape[1] != 4:
+        raise ValueError("queries must be an (n, 4) array of float32 or float64")
+    if qd.dtype != qs.dtype or qd.shape != (qs.shape[0], 3):
+        raise ValueError("qdisp must be an (n, 3) array of the queries' dtype")
+    if s.dtype != qs.dtype or s.ndim != 2 or s.shape[1] != 4:
+        raise ValueError("spheres must be an (m, 4) array of the queries' dtype")
+    R = qs.dtype.type
+    d = np.zeros((s.shape[0], 3), R) if disp is None else np.asarray(disp)
+    if d.dtype != s.dtype or d.shape != (s.shape[0], 3):
+        raise ValueError("disp must be None or an (m, 3) array of the queries' dtype")
+    E = np.zeros(s.shape[0], R) if inflate is None else np.asarray(inflate)
+    if E.dtype != s.dtype or E.shape != (s.shape[0],):
+        raise ValueError("inflate must be None or an (m,) array of the queries' dtype")
+    S = impact_scale(s, d, qs, qd) if scale is None else R(scale)
+    if not (S > 0 and np.isfinite(S) and np.frexp(S)[0] == 0.5):
+        raise ValueError("scale must be a positive power of two")
+    one = R(1.0)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore", under="ignore"):
+        rr = s[:, 3] * s[:, 3]
+        cs, ds, Es, r = s[:, :3] * S, d * S, E * S, np.abs(s[:, 3]) * S
+        ps, dqs, q = qs[:, :3] * S, qd * S, qs[:, 3] * S
+        v = cs[None, :, :] - ps[:, None, :]
+        w = dqs[:, None, :] - ds[None, :, :]
+        rad = (r + Es)[None, :] + q[:, None]
+        RR = rad * rad
+        a = (w[..., 0] * w[..., 0] + w[..., 1] * w[..., 1]) + w[..., 2] * w[..., 2]
+        b = (v[..., 0] * w[..., 0] + v[..., 1] * w[..., 1]) + v[..., 2] * w[..., 2]
+        c = ((v[..., 0] * v[..., 0] + v[..., 1] * v[..., 1]) + v[..., 2] * v[..., 2]) - RR
+        disc = b * b - a * c
+        root = (b > 0) & ~(disc < 0)
+        t = np.where(root, c / (b + np.sqrt(np.where(root, disc, one))), R(np.inf))
+        t = np.where(c > 0, t, R(0.0))
+    return np.where((rr > 0)[None, :], t, R(np.inf)).astype(R, copy=False), v, w
+
+
+def swept_times(queries, qdisp, spheres, disp=None, inflate=None, scale=None):
+    """The time at which every moving query sphere of `queries` (n x 4: px, py, pz, q; query g is at p + t qdisp[g] for t in [0, 1]) first
+    touches every sphere of `spheres` (m x 4: cx, cy, cz, r) that moves by `disp` (m x 3, or None: it stands still) -> REAL[n, m], the metric
+    of rt_swept_overlaps restated in numpy bit for bit (include/rtrace_hip.h states it), in the arrays' dtype (float32 or float64, the same
+    for all), every operation rounded once.  Every input is first multiplied by S, a power of two (`scale`, or None: impact_scale over
+    everything given here -- spheres, disp, queries and qdisp): rr = r * r;  p' = p S, q' = q S, dq' = dq S, c' = c S, r' = |r| S, d' = d S,
+    E' = E S;  v = c' - p';  w = dq' - d';  R = (r' + E') + q';  a = dot(w, w), b = dot(v, w), cc = dot(v, v) - R * R, disc = b*b - a*cc;
+    t = +inf where not rr > 0, else 0 where not cc > 0 (in contact at the start), else +inf where not b > 0 or disc < 0 (not
+    approaching, or passing by), else cc / (b + sqrt(disc)).  pair_impacts with the query in the place of sphere i -- for q > 0 the
+    same bits as pair_impacts over the concatenated records -- but q = 0 is a query here: a moving point.  `inflate` (REAL[m] or None: 0)
+    is E, what the walk adds to the radius of a BOUND record.  A record without a positive rr -- radius 0: a dead slot -- is at +inf and
+    does not contribute to S.  DeviceScene.swept_overlaps lists, per query with q >= 0, the spheres with t <= 1; a query whose q is not
+    >= 0 carries no query there and does not contribute to S; its row here is whatever the arithmetic gives."""
+    return _swept_terms(queries, qdisp, spheres, disp, inflate, scale)[0]
+
+
+def swept_normals(queries, qdisp, spheres, disp=None, inflate=None, scale=None):
+    """The contact normal rt_swept_overlaps reports for every (query, sphere) of swept_times -> REAL[n, m, 3], bit for bit: u = w * t - v
+    (each product and difference rounded once) -- the query's centre minus the sphere's centre at time t, in the scaled frame --
+    then u * (1 / sqrt(dot(u, u))): from the touched sphere to the query.  NaN where t is not finite, and where the centres coincide
+    (u = 0)."""
+    t, v, w = _swept_terms(queries, qdisp, spheres, disp, inflate, scale)
+    R = t.dtype.type
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore", under="ignore"):
+        u = w * t[..., None] - v
+        ln = np.sqrt((u[..., 0] * u[..., 0] + u[..., 1] * u[..., 1]) + u[..., 2] * u[..., 2])
+        rc = R(1.0) / ln
+        return (u * rc[..., None]).astype(R, copy=False)
 
 
 def sweep_distances(rays, radius, spheres):
@@ -1430,6 +1507,122 @@ class DeviceScene:
             m = min(capacity, total)
             pairs, time = pairs[:m], (time[:m] if times else None)
         res = (pairs,) + ((time,) if times else ()) + ((off,) if offsets else ()) + (total,)
+        return res + ((st.as_dict(),) if stats else ())
+
+    def swept_overlaps(self, queries, qdisp, disp=None, exclude=None, order=None, capacity=None, times=False, normals=False, offsets=False, stats=False,
+                       stream=None):
+        """rt_swept_overlaps / rt_swept_overlaps_device: every sphere of the scene that each moving query sphere of `queries` (n x 4: px, py,
+        pz, q, the scene's REAL dtype; query g is at p + t qdisp[g] for t in [0, 1], `qdisp`: n x 3) comes into contact with while sphere k of
+        the scene moves from c_k to c_k + disp[k] (`disp`: n_items x 3 as impacts() takes it, or None: the scene stands still; swept_times is
+        the metric) -> (items[, time][, normal][, offsets], total[, stats dict]).  items: int32[m], the DFS slots of the touched spheres,
+        query after query, ascending within a query, the same bytes every time; a dead slot is never listed.  times=True: REAL[m], each
+        entry's t in [0, 1] (0: in contact at the start).  normals=True: REAL[m, 3], the unit vector from the touched sphere's centre to the
+        query's at contact (swept_normals; NaN where the centres coincide).  offsets=True: uint64[n + 1], query g owns entries offsets[g]
+        .. offsets[g + 1].  total: how many entries there are.  capacity, exclude, order (True: sphere_order of the start poses), numpy and
+        torch arguments, `stream` and the results' types are overlaps()'s; times and normals need items (not capacity=0).  A query whose q
+        is not >= 0 has an empty row; q = 0 is a moving point."""
+        if capacity is not None:
+            capacity = int(capacity)
+            if not 0 <= capacity <= 0x7FFFFFFF:
+                raise ValueError("capacity must be None or 0 .. 2^31 - 1, not %d" % capacity)
+            if (times or normals) and capacity == 0:
+                raise ValueError("times and normals need items: capacity must not be 0")
+        R = _real(self.scene.precision)
+        n_items = self.scene.items.shape[0]
+        st = capi.Stats()
+        stp = C.byref(st) if stats else None
+        torch = sys.modules.get("torch")
+        if torch is not None and isinstance(queries, torch.Tensor):
+            tdt = torch.float32 if R == np.float32 else torch.float64
+            dev = torch.device("cuda", self.device)
+            if queries.dtype != tdt or queries.dim() != 2 or queries.shape[1] != 4 or queries.shape[0] == 0:
+                raise ValueError("queries must be a non-empty (n, 4) %s tensor" % tdt)
+            if queries.device != dev:
+                raise ValueError("queries must be on %s, not %s" % (dev, queries.device))
+            n = queries.shape[0]
+            if not isinstance(qdisp, torch.Tensor) or qdisp.dtype != tdt or tuple(qdisp.shape) != (n, 3) or qdisp.device != dev:
+                raise ValueError("qdisp must be an (n, 3) %s tensor on %s" % (tdt, dev))
+            if disp is not None and (not isinstance(disp, torch.Tensor) or disp.dtype != tdt or tuple(disp.shape) != (n_items, 3) or disp.device != dev):
+                raise ValueError("disp must be None or an (%d, 3) %s tensor on %s" % (n_items, tdt, dev))
+            if exclude is not None and (not isinstance(exclude, torch.Tensor) or exclude.dtype != torch.int32 or exclude.shape != (n,) or exclude.device != dev):
+                raise ValueError("exclude must be None or an (n,) int32 tensor on %s" % dev)
+            if order is not None and order is not True:
+                order = self._order_torch(torch, order, n, dev)
+            qs, cur = self._device_stream(torch, stream)
+            if qs != cur:
+                qs.wait_stream(cur)
+            ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
+            with torch.cuda.stream(qs):
+                qt, qd = queries.contiguous(), qdisp.contiguous()
+                dt = None if disp is None else disp.contiguous()
+                if order is True:
+                    unit = qt.clone()
+                    unit[:, 3] = 1                                               # (the radii take no part in the order, and q = 0 is no sphere)
+                    order = self.sphere_order(unit, stream=qs)
+                ex = None if exclude is None else exclude.contiguous()
+                total = torch.zeros((), dtype=torch.int64, device=dev)
+                off = torch.empty(n + 1, dtype=torch.int64, device=dev) if offsets else None
+                counted = capacity is None
+                if counted:
+                    capi.check(capi.lib.rt_swept_overlaps_device(self._h, ptr(qt), ptr(qd), n, ptr(dt), ptr(ex), ptr(order), 0, None, None, None, None, ptr(total),
+                                                                 None, C.c_void_p(qs.cuda_stream)), "rt_swept_overlaps_device")
+                    capacity = int(total.item())
+                    if capacity > 0x7FFFFFFF:
+                        raise ValueError("the queries have %d entries, more than one call can list: pass a capacity" % capacity)
+                items = torch.empty(capacity, dtype=torch.int32, device=dev)
+                time = torch.empty(capacity, dtype=tdt, device=dev) if times else None
+                normal = torch.empty((capacity, 3), dtype=tdt, device=dev) if normals else None
+                rc = capi.lib.rt_swept_overlaps_device(self._h, ptr(qt), ptr(qd), n, ptr(dt), ptr(ex), ptr(order), capacity, ptr(items) if capacity else None,
+                                                       ptr(time) if capacity else None, ptr(normal) if capacity else None, ptr(off), ptr(total), stp,
+                                                       C.c_void_p(qs.cuda_stream))
+            if qs != cur:
+                for x in (queries, qt, qdisp, qd, disp, dt, exclude, ex, order):
+                    if isinstance(x, torch.Tensor) and x.is_cuda:
+                        x.record_stream(qs)
+            capi.check(rc, "rt_swept_overlaps_device")
+            total = int(total.item()) if counted else total
+        else:
+            if not isinstance(queries, np.ndarray) or queries.dtype != R or queries.ndim != 2 or queries.shape[1] != 4 or queries.shape[0] == 0:
+                raise ValueError("queries must be a non-empty (n, 4) numpy array of %s (or a torch tensor on the scene's device)" % np.dtype(R).name)
+            n = queries.shape[0]
+            if not isinstance(qdisp, np.ndarray) or qdisp.dtype != R or qdisp.shape != (n, 3):
+                raise ValueError("qdisp must be an (n, 3) numpy array of %s" % np.dtype(R).name)
+            if disp is not None and (not isinstance(disp, np.ndarray) or disp.dtype != R or disp.shape != (n_items, 3)):
+                raise ValueError("disp must be None or an (%d, 3) numpy array of %s" % (n_items, np.dtype(R).name))
+            qa, qd = np.ascontiguousarray(queries), np.ascontiguousarray(qdisp)
+            da = None if disp is None else np.ascontiguousarray(disp)
+            ex = None
+            if exclude is not None:
+                ex = np.asarray(exclude)
+                if ex.dtype != np.int32 or ex.shape != (n,):
+                    raise ValueError("exclude must be None or an (n,) int32 array")
+                ex = np.ascontiguousarray(ex)
+            o = None
+            if order is True:
+                unit = qa.copy()
+                unit[:, 3] = 1                                                   # (the radii take no part in the order, and q = 0 is no sphere)
+                o = self.sphere_order(unit)
+            elif order is not None:
+                o = self._order_numpy(order, n)
+            total = C.c_uint64(0)
+            off = np.empty(n + 1, dtype=np.uint64) if offsets else None
+            ptr = lambda x: None if x is None else x.ctypes.data
+            if capacity is None:
+                capi.check(capi.lib.rt_swept_overlaps(self._h, ptr(qa), ptr(qd), n, ptr(da), ptr(ex), ptr(o), 0, None, None, None, None, C.byref(total), None),
+                           "rt_swept_overlaps")
+                capacity = int(total.value)
+                if capacity > 0x7FFFFFFF:
+                    raise ValueError("the queries have %d entries, more than one call can list: pass a capacity" % capacity)
+            items = np.empty(capacity, dtype=np.int32)
+            time = np.empty(capacity, dtype=R) if times else None
+            normal = np.empty((capacity, 3), dtype=R) if normals else None
+            capi.check(capi.lib.rt_swept_overlaps(self._h, ptr(qa), ptr(qd), n, ptr(da), ptr(ex), ptr(o), capacity, ptr(items) if capacity else None,
+                                                  ptr(time) if capacity else None, ptr(normal) if capacity else None, ptr(off), C.byref(total), stp),
+                       "rt_swept_overlaps")
+            total = int(total.value)
+            m = min(capacity, total)
+            items, time, normal = items[:m], (time[:m] if times else None), (normal[:m] if normals else None)
+        res = (items,) + ((time,) if times else ()) + ((normal,) if normals else ()) + ((off,) if offsets else ()) + (total,)
         return res + ((st.as_dict(),) if stats else ())
 
     @staticmethod
