@@ -1,6 +1,7 @@
 """The tight streams (rust-tracer_amd/csrc/rt_tight.hpp) on the GPU: frames walked over the tight bounds (RT_DEBUG_TIGHT_BOUNDS 2) and over the
 given ones (0) against the oracle byte for byte, through the generic kernel, the lean kernel, cooperative quads and a sample-parallel pass;
-and the launch flag that says which streams a launch walked."""
+and the launch flag that says which streams a launch walked.  tests/test_gpu_tight_poses.py does the same away from the home pose: every
+light, eye and placement of the frame tests, the edge scenes, and rim fixtures with an item on the tight ball's rim."""
 import functools
 import os
 
@@ -39,39 +40,16 @@ def _ref(key, w, h, spp):
 
 
 def _frames(s, ref, opts, regs, expect_tight=True, controls=()):
-    """Renders `regs` with the given and with the tight streams under `controls`; both must equal the oracle's frame where a tile covers it."""
-    covered = np.zeros(ref.shape[:2], dtype=bool)
-    for (l, t, r, b) in regs:
-        covered[b:t, l:r] = True
-    for tb in (0, 2):
-        with capi.debug(capi.DEBUG_TIGHT_BOUNDS, tb):
-            for key, value in controls:
-                capi.debug_set(key, value)
-            try:
-                data, st = s.device().render_tiles(opts, regs, SKIP, want_stats=False)
-                flags = capi.last_launch()
-            finally:
-                for key, _ in controls:
-                    capi.debug_set(key, -1)
-        frame = util.stitch(opts, regs, data)
-        np.testing.assert_array_equal(frame[covered], ref[covered], err_msg="RT_DEBUG_TIGHT_BOUNDS %d" % tb)
-        assert ("tight_bounds" in flags) == (tb == 2 and expect_tight), (tb, flags)
-    # ... and the counting launch (the given streams, the C++ loops): the same bytes, no bound's verdict violated (tests/conftest.py asserts the counter)
-    data, st = s.device().render_tiles(opts, regs, SKIP, want_stats=True)
-    np.testing.assert_array_equal(util.stitch(opts, regs, data)[covered], ref[covered])
-    # ... and no ITEM test of it counted where a tight bound would have put its lane to sleep
-    assert capi.debug_count(capi.DEBUG_COUNT_TIGHT_VIOLATIONS) == 0
+    """Renders `regs` with the given and with the tight streams under `controls`; both must equal the oracle's frame where a tile covers it
+    (tests/tight_scenes.py frames, shared with tests/test_gpu_tight_poses.py)."""
+    ts.frames(s.device(), ref, opts, regs, expect_tight=expect_tight, controls=controls)
 
 
 def _buckets(w, h, spp=1):
     return (w, h, spp), [tuple(r) for r in rta.buckets(rta.RenderOptions(w, h, spp))]
 
 
-MODES = {"generic": ((capi.DEBUG_FAST_KERNEL, 0), (capi.DEBUG_COOP, 0)),
-         "lean": ((capi.DEBUG_FAST_KERNEL, 2), (capi.DEBUG_COOP, 0)),
-         "lean_coop": ((capi.DEBUG_FAST_KERNEL, 2), (capi.DEBUG_COOP, 2)),
-         "generic_coop": ((capi.DEBUG_FAST_KERNEL, 0), (capi.DEBUG_COOP, 2)),
-         "one_ray": ((capi.DEBUG_SKIP_RAYS, 1),)}
+MODES = ts.MODES
 
 
 @pytest.mark.parametrize("mode", sorted(MODES))

@@ -1,5 +1,7 @@
 """The tight spheres of the filtered f32 walks (rust-tracer_amd/csrc/rt_tight.hpp) on the host: every one encloses its subtree's items with the
-stated inflation, and a bound that leaves an item outside or holds the eye keeps the sphere it was given, bit for bit.  No GPU."""
+stated inflation, and a bound that leaves an item outside or holds the eye keeps the sphere it was given, bit for bit.
+tests/test_tight_poses_host.py holds the same, and the theorem behind the inflation, on every light, eye and placement of the frame tests.
+No GPU."""
 import numpy as np
 import pytest
 
