@@ -46,7 +46,7 @@ SYMBOLS = ("rt_abi_version", "rt_build_hierarchy", "rt_device_count", "rt_scene_
            "rt_scene_impacts", "rt_scene_impacts_device", "rt_swept_overlaps", "rt_swept_overlaps_device")
 # csrc/rt_debug.h: only in the -DRT_TEST_HOOKS build
 DEBUG_SYMBOLS = ("rt_debug_set", "rt_debug_count", "rt_debug_wave_trace", "rt_debug_flat_filter_check", "rt_debug_gang_layout", "rt_debug_rccl_library",
-                 "rt_debug_shard_costs", "rt_debug_tight_bounds")
+                 "rt_debug_shard_costs", "rt_debug_tight_bounds", "rt_debug_cost_map")
 
 
 class Options(C.Structure):      # rt_options / RenderOptions render.rs:33-38
@@ -192,6 +192,7 @@ lib.rt_last_launch_flags.restype = C.c_uint32
 lib.rt_build_info.restype = C.c_char_p
 RT_LAUNCH_TWO_RAYS, RT_LAUNCH_COOPERATIVE, RT_LAUNCH_SAMPLE_PARALLEL, RT_LAUNCH_ORDERED, RT_LAUNCH_FLAT_PIPELINE, RT_LAUNCH_COUNTING, RT_LAUNCH_FAST_KERNEL = 1, 2, 4, 8, 16, 32, 64
 RT_LAUNCH_TIGHT_BOUNDS = 128
+RT_LAUNCH_TIGHT_COSTS = 256
 HAVE_TEST_HOOKS = hasattr(lib, "rt_debug_set")
 
 if lib.rt_abi_version() != ABI_VERSION:
@@ -217,7 +218,7 @@ def last_launch():
     f = lib.rt_last_launch_flags()
     names = (("two_rays", RT_LAUNCH_TWO_RAYS), ("cooperative", RT_LAUNCH_COOPERATIVE), ("sample_parallel", RT_LAUNCH_SAMPLE_PARALLEL),
              ("ordered", RT_LAUNCH_ORDERED), ("flat_pipeline", RT_LAUNCH_FLAT_PIPELINE), ("counting", RT_LAUNCH_COUNTING), ("fast_kernel", RT_LAUNCH_FAST_KERNEL),
-             ("tight_bounds", RT_LAUNCH_TIGHT_BOUNDS))
+             ("tight_bounds", RT_LAUNCH_TIGHT_BOUNDS), ("tight_costs", RT_LAUNCH_TIGHT_COSTS))
     return {n for n, bit in names if f & bit}
 
 
@@ -269,7 +270,7 @@ def selftest_rcp(device=0):
 (DEBUG_SKIP_VARIANT, DEBUG_BLOCK_ORDER, DEBUG_NARROW_MAX, DEBUG_PACKED_SAMPLES, DEBUG_PRINT_STEPS, DEBUG_PRINT_COSTS,
  DEBUG_HOST_COPY, DEBUG_COALESCE, DEBUG_LDS_BYTES, DEBUG_WG_POLICY, DEBUG_NARROW_L2, DEBUG_FLAT_KERNELS, DEBUG_SKIP_RAYS,
  DEBUG_FRAME_AHEAD, DEBUG_FILTER_RO_PERCENT, DEBUG_COOP, DEBUG_COOP_THR, DEBUG_COOP_MAX, DEBUG_COOP_LEVEL, DEBUG_COOP_REST, DEBUG_ASYNC_ORDERS,
- DEBUG_FAST_KERNEL, DEBUG_EXACT_COSTS, DEBUG_MULTIHIT_BUCKET, DEBUG_TIGHT_BOUNDS) = range(25)
+ DEBUG_FAST_KERNEL, DEBUG_EXACT_COSTS, DEBUG_MULTIHIT_BUCKET, DEBUG_TIGHT_BOUNDS, DEBUG_TIGHT_COSTS) = range(26)
 if HAVE_TEST_HOOKS:
     lib.rt_debug_set.argtypes = [C.c_int, C.c_longlong]
     lib.rt_debug_wave_trace.argtypes = [C.c_char_p]
@@ -279,6 +280,7 @@ if HAVE_TEST_HOOKS:
     lib.rt_debug_gang_layout.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
     lib.rt_debug_shard_costs.argtypes = [C.c_void_p, C.POINTER(Options), C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
     lib.rt_debug_rccl_library.argtypes = [C.c_char_p]
+    lib.rt_debug_cost_map.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     lib.rt_debug_tight_bounds.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
 
 
@@ -293,7 +295,7 @@ def debug_count(counter):
     _need_hooks("rt_debug_count")
     return lib.rt_debug_count(counter)
 (DEBUG_COUNT_REGION_CALLS, DEBUG_COUNT_REGION_PASSES, DEBUG_COUNT_FILTER_PASS, DEBUG_COUNT_FILTER_VIOLATIONS, DEBUG_COUNT_PRIMARY_TESTS,
- DEBUG_COUNT_FRAME_AHEAD_PASSES, DEBUG_COUNT_TWO_RAY_LAUNCHES, DEBUG_COUNT_COOP_LAUNCHES, DEBUG_COUNT_TIGHT_VIOLATIONS) = range(9)
+ DEBUG_COUNT_FRAME_AHEAD_PASSES, DEBUG_COUNT_TWO_RAY_LAUNCHES, DEBUG_COUNT_COOP_LAUNCHES, DEBUG_COUNT_TIGHT_VIOLATIONS, DEBUG_COUNT_TIGHT_RECOUNTS) = range(10)
 
 
 def debug_set(key, value=-1):
@@ -364,6 +366,16 @@ def shard_costs(scene_handle, options, regions, n_devices):
     o = Options(*options)
     check(lib.rt_debug_shard_costs(scene_handle, C.byref(o), arr, len(regions), n_devices, cost.ctypes.data), "rt_debug_shard_costs")
     return cost
+
+
+def cost_map(scene_handle, tight):
+    """rt_debug_cost_map -> uint32[256, 256]: tests per primary ray (its shadow ray included) on the scene's given streams (tight=False) or
+    its tight streams (tight=True; made if needed)."""
+    import numpy as np
+    _need_hooks("rt_debug_cost_map")
+    out = np.zeros((256, 256), dtype=np.uint32)
+    check(lib.rt_debug_cost_map(scene_handle, 1 if tight else 0, out.ctypes.data), "rt_debug_cost_map")
+    return out
 
 
 FAKE_RCCL = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "c", "libfake_rccl.so")

@@ -75,11 +75,13 @@ std::string g_trace_path;
 // (a background builder of dispatch orders works for a caller that had no control set: it must not see one that is set meanwhile)
 thread_local bool g_knobs_at_default = false;
 inline long long knob(int key) { return g_knobs_at_default ? -1 : g_knob[key].load(std::memory_order_relaxed); }
+inline long long print_knob(int key) { return g_knob[key].load(std::memory_order_relaxed); }      // (printing controls: also on a background builder)
 inline void count_event(int counter, long long n = 1) { g_count[counter].fetch_add(n, std::memory_order_relaxed); }
 inline void count_store(int counter, long long v) { g_count[counter].store(v, std::memory_order_relaxed); }
 inline void knobs_at_default() { g_knobs_at_default = true; }
 #else
 constexpr long long knob(int) { return -1; }
+constexpr long long print_knob(int) { return -1; }
 inline void count_event(int, long long = 1) {}
 inline void count_store(int, long long) {}
 inline void knobs_at_default() {}
@@ -101,9 +103,10 @@ rt_status hip_fail(hipError_t e, const char *what, int line, const char *file = 
 // RT_DEBUG_PRINT_COSTS: where rt_scene_create and the first use of a tile list spend their host time
 struct StageClock {
     std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+    bool on = knob(RT_DEBUG_PRINT_COSTS) > 0;
     void lap(const char *what)
     {
-        if (knob(RT_DEBUG_PRINT_COSTS) <= 0) return;
+        if (!on) return;
         const auto n = std::chrono::steady_clock::now();
         fprintf(stderr, "[rtrace_hip] %-28s %8.1f us\n", what, std::chrono::duration<double, std::micro>(n - t).count());
         t = n;
@@ -227,6 +230,17 @@ struct rt_scene {
     struct CachedTable { std::vector<rt::TileDev> host; unsigned w = 0, h = 0, passes = 0; rt::TileDev *dev = nullptr; std::vector<Order> orders; int chosen = 0; unsigned turn = 0; bool building = false;
                          bool retrial = false;             // the scene's tight streams arrived after this list's trial had begun: time the orders once more (pick_order)
                          void *order_arena = nullptr;      // ONE device allocation holds every order's arrays (allocation calls wait for a busy device)
+                         // the orders were built from costs counted on the TIGHT streams (build_orders: a table whose launches walk them)
+                         bool tight_costs = false;
+                         bool tight_pending = false;       // ... are being built right now (build_orders_async)
+                         bool from_worker = false;         // the list's orders are the background's to make: it was first seen with no dispatch control set
+                         long long tight_knob = -1;        // RT_DEBUG_TIGHT_BOUNDS when the list was first seen: part of what its launches walk
+                         long long tight_costs_knob = -1;  // RT_DEBUG_TIGHT_COSTS, likewise
+                         // orders built from the given-stream costs that the tight-cost ones replaced (build_orders_async): launches enqueued before
+                         // the swap may still read their arrays or record their events, so they stay until the table goes
+                         std::vector<Order> retired_orders; std::vector<void *> retired_arenas;
+                         // quads each cooperative candidate of the given-stream build picked: the budget the tight-cost thresholds are quantiles for
+                         std::vector<uint32_t> coop_quads;
                          long long coop_key = 0;
                          // a table uploaded asynchronously on its first caller's stream (device_table): until `landed` has completed, launches on
                          // OTHER streams wait for it
@@ -254,6 +268,10 @@ struct rt_scene {
     bool cost_started = false;
     bool main_stream_taken = false;        // cost_stream doubles as the first context's stream (acquire)
     std::vector<uint32_t> cost_map;
+    // ... and the same map counted on the tight streams, for the lists whose frames walk those (tight_cost_map_of; made once, behind the
+    // tight streams, through the same arena)
+    std::once_flag tight_cost_once;
+    std::vector<uint32_t> tight_cost_map;
     // Concurrent rt_render_region callers (the reference's pool threads, render.rs:283-294) are merged into shared passes:
     // whoever finds no pass running becomes its leader and renders every request that is waiting at that moment.
     struct RegionReq { rt_options o; rt_traversal trav; rt_region region; uint8_t *out; rt_status st = RT_OK; bool taken = false, done = false; char err[256] = "";

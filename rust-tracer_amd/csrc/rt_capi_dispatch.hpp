@@ -94,15 +94,18 @@ rt_status alloc_cost_host(rt_scene *s)
 
 // Enqueues the counting render of the cost map on the scene's own stream (by whoever first asks for the map: cost_map_of, normally the
 // scene's worker thread).  No copy engine: the one tile is read from pinned memory, the lanes store their counts into the pinned map.
+// tight: the same counting loops over the scene's TIGHT plain streams (skip_view_of<T>(s, true); the caller has seen tight_ready) -- what the
+// frames of a list that walks_tight says yes to will walk.  Its counters stay in the arena like the given-stream map's: nothing of it
+// reaches rt_stats or the tight-violation check (skip_args_of hands the tight records to hold against to given-stream launches only).
 template <typename T>
-rt_status start_cost_map(rt_scene *s)
+rt_status start_cost_map(rt_scene *s, bool tight = false)
 {
     constexpr unsigned R = kCostRes;
     const rt::TileDev tile{ 0, (uint16_t)R, (uint16_t)R, 0, 0u, 0u, R / rt::kBlockW };
     if (!s->h_cost) return RT_ERR_OUT_OF_MEMORY;
     // ONE device allocation, kept until the scene goes (hipMalloc / hipFree wait for a busy device): tile | frame | costs | counters
     constexpr size_t kTileBytes = kCostTileBytes, kPx = kCostArenaPx * 4, kCnt = sizeof(rt::Counters) * rt::kCounterStripes;
-    HIP_TRY(hipMalloc(&s->d_cost_arena, kTileBytes + 2 * kPx + kCnt));
+    if (!s->d_cost_arena) HIP_TRY(hipMalloc(&s->d_cost_arena, kTileBytes + 2 * kPx + kCnt));
     hipStream_t stream = s->cost_stream;
     char *base = static_cast<char *>(s->d_cost_arena);
     uint8_t *d_out = reinterpret_cast<uint8_t *>(base + kTileBytes);
@@ -114,7 +117,7 @@ rt_status start_cost_map(rt_scene *s)
     hipLaunchKernelGGL(rt::k_zero_words, dim3(64), dim3(256), 0, stream, reinterpret_cast<uint32_t *>(d_cnt), kCnt / 4);
     rt::SampleBuf<T> sb{ nullptr, nullptr, R * R };
     hipLaunchKernelGGL((rt::k_render_skip<T, true, 1, rt::kSkipLoop>), dim3((R / rt::kBlockW) * (R / rt::kBlockH)), dim3(rt::kBlockThreads), 0, stream,
-                       skip_args<T>(s, nullptr, nullptr, R, R, 0u, d_out, tile_alias, 1u, 1u, d_cnt, static_cast<uint32_t *>(h_alias), sb));
+                       skip_args_of<T>(s, tight, nullptr, nullptr, R, R, 0u, d_out, tile_alias, 1u, 1u, d_cnt, static_cast<uint32_t *>(h_alias), sb));
     HIP_TRY(hipGetLastError());
     s->cost_started = true;
     return RT_OK;
@@ -125,12 +128,28 @@ const std::vector<uint32_t> *cost_map_of(rt_scene *s)
 {
     std::call_once(s->cost_once, [s] {
         if (s->n_nodes == 0) return;
+        std::lock_guard<std::mutex> lk(s->exact_mu);                 // one counting launch at a time through the scene's arena
         if ((s->precision == RT_F32 ? start_cost_map<float>(s) : start_cost_map<double>(s)) != RT_OK) { s->cost_started = false; (void)hipGetLastError(); return; }
         if (hipStreamSynchronize(s->cost_stream) != hipSuccess) { (void)hipGetLastError(); return; }
         const uint32_t *h = static_cast<const uint32_t *>(s->h_cost);
         s->cost_map.assign(h, h + (size_t)kCostRes * kCostRes);
     });
     return s->cost_map.empty() ? nullptr : &s->cost_map;
+}
+
+// The second map, beside the first: counted on the tight streams once the scene has them (NULL before, and for every scene that gets none:
+// f64, dynamic, no bound qualified).  The given-stream map goes first -- it owns the arena's allocation.
+const std::vector<uint32_t> *tight_cost_map_of(rt_scene *s)
+{
+    if (s->precision != RT_F32 || !s->tight_ready.load(std::memory_order_acquire) || !cost_map_of(s)) return nullptr;
+    std::call_once(s->tight_cost_once, [s] {
+        std::lock_guard<std::mutex> lk(s->exact_mu);
+        if (start_cost_map<float>(s, true) != RT_OK) { (void)hipGetLastError(); return; }
+        if (hipStreamSynchronize(s->cost_stream) != hipSuccess) { (void)hipGetLastError(); return; }
+        const uint32_t *h = static_cast<const uint32_t *>(s->h_cost);
+        s->tight_cost_map.assign(h, h + (size_t)kCostRes * kCostRes);
+    });
+    return s->tight_cost_map.empty() ? nullptr : &s->tight_cost_map;
 }
 
 // Tests per pixel at the FRAME's resolution for a few blocks of a tile list (round 6).  The scene's cost map has one cell per 7.5 pixels of
@@ -141,7 +160,7 @@ const std::vector<uint32_t> *cost_map_of(rt_scene *s)
 // stream), each lane storing the number of tests its pixel took.  px[i * 256 + (y - y0) * 16 + (x - x0)] for block i of `blocks`.
 struct ExactCosts { std::vector<uint32_t> block; std::vector<uint32_t> px; uint32_t top = 0; };      // block: raster index of the counted blocks
 template <typename T>
-rt_status exact_block_costs(rt_scene *s, const std::vector<rt::BlockDesc> &raster, const std::vector<uint32_t> &blocks, unsigned w, unsigned h, ExactCosts &out)
+rt_status exact_block_costs(rt_scene *s, const std::vector<rt::BlockDesc> &raster, const std::vector<uint32_t> &blocks, unsigned w, unsigned h, ExactCosts &out, bool tight = false)
 {
     out = ExactCosts{};
     if (blocks.empty() || blocks.size() > kExactBlocks || !s->d_cost_arena || !s->h_cost) return RT_OK;
@@ -170,9 +189,10 @@ rt_status exact_block_costs(rt_scene *s, const std::vector<rt::BlockDesc> &raste
     hipLaunchKernelGGL(rt::k_zero_words, dim3(64), dim3(256), 0, stream, reinterpret_cast<uint32_t *>(d_cnt), kCnt / 4);
     rt::SampleBuf<T> sb{ nullptr, nullptr, (unsigned)(blocks.size() * rt::kBlockW * rt::kBlockH) };
     hipLaunchKernelGGL((rt::k_render_skip<T, true, 1, rt::kSkipLoop>), dim3((unsigned)blocks.size()), dim3(rt::kBlockThreads), 0, stream,
-                       skip_args<T>(s, nullptr, nullptr, w, h, 0u, d_out, tile_alias, (unsigned)tiles.size(), 1u, d_cnt, static_cast<uint32_t *>(h_alias), sb));
+                       skip_args_of<T>(s, tight, nullptr, nullptr, w, h, 0u, d_out, tile_alias, (unsigned)tiles.size(), 1u, d_cnt, static_cast<uint32_t *>(h_alias), sb));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(stream));
+    if (tight) count_event(RT_DEBUG_COUNT_TIGHT_RECOUNTS);
     const std::vector<uint32_t> raw(h_counts, h_counts + blocks.size() * rt::kBlockW * rt::kBlockH);
     // the kernel stores tile-major with the tile's own pitch (its clipped width): re-pitch to 16
     out.block = blocks;
@@ -215,7 +235,8 @@ void block_order(const std::vector<uint32_t> *map, const std::vector<rt::TileDev
                  std::vector<rt::BlockDesc> &descs, std::vector<uint32_t> &wg_first, const rt::CoopView *coop = nullptr, std::vector<uint64_t> *holes = nullptr,
                  int coop_percent = -1,            // 0: no cooperative quads; > 0: from that share of the pass's largest estimate; -1: as rt_debug.h says (default share)
                  const ExactCosts *exact = nullptr, uint32_t exact_thr = 0,      // cooperative quads by EXACT tests per pixel (exact_block_costs) from exact_thr on, instead
-                 std::vector<uint32_t> *heaviest = nullptr)                      // out: the raster indices of the heaviest blocks (what exact_block_costs is asked for); descs is not made
+                 std::vector<uint32_t> *heaviest = nullptr,                      // out: the raster indices of the heaviest blocks (what exact_block_costs is asked for); descs is not made
+                 int cost_grow = 0)                                              // a block's estimate: the map cells under it, grown by so many cells on every side
 {
     wg_first.clear();
     if (holes) holes->clear();
@@ -239,7 +260,7 @@ void block_order(const std::vector<uint32_t> *map, const std::vector<rt::TileDev
                 const unsigned x0 = t.l + bx * rt::kBlockW, y0 = t.b + by * rt::kBlockH;
                 raster.push_back(rt::BlockDesc{ (uint16_t)x0, (uint16_t)y0, t.r, t.t, pitch, t.out_px - t.b * pitch - t.l });
                 uint32_t m = 0;
-                if (map) m = map_max(x0, y0, std::min<unsigned>(x0 + rt::kBlockW, t.r) - 1, std::min<unsigned>(y0 + rt::kBlockH, t.t) - 1, 0);
+                if (map) m = map_max(x0, y0, std::min<unsigned>(x0 + rt::kBlockW, t.r) - 1, std::min<unsigned>(y0 + rt::kBlockH, t.t) - 1, cost_grow);
                 cost.push_back(m);
             }
     }
@@ -456,6 +477,7 @@ rt::BlockList pick_order(rt_scene::CachedTable &t, bool will_be_timed)      // w
     auto list_of = [&t](const rt_scene::Order &od) {
         rt::BlockList l{ od.dev_order, od.n_order, od.dev_wg, od.n_wg, od.dev_holes, od.n_holes };
         l.plain_d = t.orders[0].dev_order; l.plain_n = t.orders[0].n_order; l.plain_wg_first = t.orders[0].dev_wg; l.plain_n_wg = t.orders[0].n_wg;
+        l.tight_costs = t.tight_costs;
         return l;
     };
     auto harvest = [](rt_scene::Order &od) {
@@ -493,8 +515,8 @@ rt::BlockList pick_order(rt_scene::CachedTable &t, bool will_be_timed)      // w
         t.chosen = (int)best;
         if (knob(RT_DEBUG_PRINT_STEPS) > 0) {
             fprintf(stderr, "[rtrace_hip] dispatch orders of a %zu-tile list, ms:", t.host.size());
-            for (const auto &od : t.orders) fprintf(stderr, " %.4f%s", od.best_ms, od.dev_holes ? "c" : "");
-            fprintf(stderr, " -> #%zu\n", best);
+            for (const auto &od : t.orders) fprintf(stderr, " %.4f%s/%u", od.best_ms, od.dev_holes ? "c" : "", od.n_order);      // (time / descriptors)
+            fprintf(stderr, " -> #%zu%s\n", best, t.tight_costs ? " (tight costs)" : "");
         }
         return list_of(t.orders[best]);
     }
@@ -521,11 +543,79 @@ bool order_knobs_set()
     return knob(RT_DEBUG_ASYNC_ORDERS) == 0;
 }
 
+// Does a launch walk the scene's TIGHT streams (rt_tight.hpp)?  Launches of the filtered assembly loops of an f32 scene that neither
+// count nor take two rays per lane -- then the un-fused loops (VAR 19) over the tight streams, whatever the scene's own flavour is.
+// tb, RT_DEBUG_TIGHT_BOUNDS: 0 never, 1 the rule, 2 wherever a scene has tight streams; default: the rule.  (walks_tight, rt_capi_launch.hpp,
+// asks it for a launch; table_walks_tight below for a cached list, whose dispatch orders are built from the costs of the streams it walks)
+int skip_variant(const rt_scene *s);
+bool walks_tight_with(const rt_scene *s, int v, uint64_t total_px, unsigned spp, long long tb)
+{
+    if (tb == 0 || s->precision != RT_F32 || s->dynamic || ((v & ~8) != 19 && (v & ~8) != 23)) return false;
+    if (!s->tight_ready.load(std::memory_order_acquire)) return false;
+    if (tb != 2 && (s->tight_by_rule == 0 || (s->tight_by_rule == 2 && !(spp == 1 && total_px >= kTightPartialMinPx)))) return false;
+    const long long k = knob(RT_DEBUG_SKIP_RAYS);      // the two-ray kernels keep the given streams: launch_skip_one's question, asked first
+    const bool two_rays = (k < 0 ? skip2_by_default(total_px, spp, (v & 4) ? s->n_fnodes : s->n_nodes) : k == 2) && (spp == 1 || (use_split(spp) && packed_samples(spp)));
+    return !two_rays;
+}
+
+// The same question for every non-counting launch of a cached tile list (its width, height and passes are part of its identity, and so is
+// the RT_DEBUG_TIGHT_BOUNDS it was first seen with): passes is spp^2 in the sample-parallel path and 1 otherwise.
+bool table_walks_tight(const rt_scene *s, const std::vector<rt::TileDev> &tab, unsigned passes, long long tb)
+{
+    uint64_t total_px = 0;
+    for (const rt::TileDev &td : tab) total_px += (uint64_t)(td.r - td.l) * (td.t - td.b);
+    unsigned spp = 1;
+    while (spp * spp < passes) ++spp;
+    return walks_tight_with(s, skip_variant(s), total_px, spp, tb);
+}
+
+// Quads (2x2 pixels) of the counted blocks, each by the largest exact count of its four pixels: what a cooperative threshold picks from.
+std::vector<uint32_t> exact_quad_costs(const ExactCosts &ex)
+{
+    std::vector<uint32_t> q;
+    q.reserve(ex.block.size() * 64);
+    for (size_t k = 0; k < ex.block.size(); ++k) {
+        const uint32_t *px = &ex.px[k * 256];
+        for (unsigned qy = 0; qy < 8; ++qy)
+            for (unsigned qx = 0; qx < 8; ++qx)
+                q.push_back(std::max(std::max(px[(2 * qy) * 16 + 2 * qx], px[(2 * qy) * 16 + 2 * qx + 1]), std::max(px[(2 * qy + 1) * 16 + 2 * qx], px[(2 * qy + 1) * 16 + 2 * qx + 1])));
+    }
+    return q;
+}
+
+// A list's heaviest blocks by `map`, counted again at the frame's own resolution on the given or the tight streams (exact_block_costs).
+void recount_heaviest(rt_scene *s, const std::vector<uint32_t> *map, const std::vector<rt::TileDev> &tab, unsigned w, unsigned h, unsigned passes, bool tight, ExactCosts &exact, int cost_grow = 0)
+{
+    std::vector<rt::BlockDesc> none; std::vector<uint32_t> none_wg, heaviest;
+    block_order(map, tab, w, h, passes, none, none_wg, nullptr, nullptr, 0, nullptr, 0, &heaviest, cost_grow);
+    std::vector<rt::BlockDesc> raster;
+    for (const rt::TileDev &t : tab) {          // (block_order's raster enumeration: the indices `heaviest` holds)
+        const unsigned bys = ((unsigned)(t.t - t.b) + rt::kBlockH - 1) / rt::kBlockH;
+        const uint32_t pitch = (uint32_t)t.r - t.l;
+        for (unsigned by = 0; by < bys; ++by)
+            for (unsigned bx = 0; bx < t.blks_x; ++bx)
+                raster.push_back(rt::BlockDesc{ (uint16_t)(t.l + bx * rt::kBlockW), (uint16_t)(t.b + by * rt::kBlockH), t.r, t.t, pitch, 0u });
+    }
+    if ((s->precision == RT_F32 ? exact_block_costs<float>(s, raster, heaviest, w, h, exact, tight) : exact_block_costs<double>(s, raster, heaviest, w, h, exact, tight)) != RT_OK) {
+        (void)hipGetLastError(); exact = ExactCosts{};
+    }
+}
+
 // The candidate dispatch orders of one tile list: the plain one first; where the cooperative walk could serve the pass and nothing was
 // asked for explicitly, a few thresholds in percent of the pass's largest estimate (pick_order tries them: chosen = -1).
+// tight: `map` is the scene's TIGHT cost map (tight_cost_map_of) and the exact recount walks the tight streams too -- for a list whose
+// launches walk them (table_walks_tight).  coop_quads (optional): how many quads each cooperative threshold of the given-stream build
+// picked -- written by such a build, read by a tight one (see the thresholds below).
+// The tight map's blocks are estimated from one map cell more on every side (kTightCostGrow).  Measured at 1080p, one box, the same tight
+// walk (profiles/c01_cost_sources.log, ms per frame): orders from the given map 0.0307 - 0.0311; from the tight map, cells under the block
+// only, 0.0329 - 0.0336 -- its PLAIN order alone 0.045 against 0.035: the tight bounds make the silhouettes that carry the long chains
+// thinner than a map cell (7.5 pixels there), a heavy block whose cells miss them is dispatched late and un-narrowed, and the frame waits
+// for it --; from the tight map with the neighbouring cells 0.0293 - 0.0295 (two cells: 0.0296).
+constexpr int kTightCostGrow = 1;
 rt_status build_orders(rt_scene *s, const std::vector<uint32_t> *map, const std::vector<rt::TileDev> &tab, unsigned w, unsigned h, unsigned passes,
-                       std::vector<rt_scene::Order> &orders, int &chosen, void **arena_out)
+                       std::vector<rt_scene::Order> &orders, int &chosen, void **arena_out, bool tight = false, std::vector<uint32_t> *coop_quads = nullptr)
 {
+    const int cost_grow = tight ? kTightCostGrow : 0;
     const bool coop_pass = s->coop.fanout != 0u && passes == 1;       // (f32; f64 scenes whose filtered streams exist)
     uint64_t total_px = 0, total_blocks = 0;
     for (const rt::TileDev &td : tab) {
@@ -544,21 +634,8 @@ rt_status build_orders(rt_scene *s, const std::vector<uint32_t> *map, const std:
     std::vector<Want> wants;
     ExactCosts exact;
     const bool knobs = knob(RT_DEBUG_COOP) >= 0 || knob(RT_DEBUG_COOP_THR) >= 0 || knob(RT_DEBUG_COOP_MAX) >= 0;
-    if (coop_pass && map && !two_rays && !knobs && knob(RT_DEBUG_EXACT_COSTS) != 0) {
-        std::vector<rt::BlockDesc> none; std::vector<uint32_t> none_wg, heaviest;
-        block_order(map, tab, w, h, passes, none, none_wg, nullptr, nullptr, 0, nullptr, 0, &heaviest);
-        std::vector<rt::BlockDesc> raster;
-        for (const rt::TileDev &t : tab) {          // (block_order's raster enumeration: the indices `heaviest` holds)
-            const unsigned bys = ((unsigned)(t.t - t.b) + rt::kBlockH - 1) / rt::kBlockH;
-            const uint32_t pitch = (uint32_t)t.r - t.l;
-            for (unsigned by = 0; by < bys; ++by)
-                for (unsigned bx = 0; bx < t.blks_x; ++bx)
-                    raster.push_back(rt::BlockDesc{ (uint16_t)(t.l + bx * rt::kBlockW), (uint16_t)(t.b + by * rt::kBlockH), t.r, t.t, pitch, 0u });
-        }
-        if ((s->precision == RT_F32 ? exact_block_costs<float>(s, raster, heaviest, w, h, exact) : exact_block_costs<double>(s, raster, heaviest, w, h, exact)) != RT_OK) {
-            (void)hipGetLastError(); exact = ExactCosts{};
-        }
-    }
+    const bool recount = coop_pass && map && !two_rays && !knobs && knob(RT_DEBUG_EXACT_COSTS) != 0;
+    if (recount) recount_heaviest(s, map, tab, w, h, passes, tight, exact, cost_grow);
     bool asked = false;
     if (!exact.block.empty() && exact.top >= kCoopMinCost) {
         wants.push_back({ 0, 0u });
@@ -568,8 +645,37 @@ rt_status build_orders(rt_scene *s, const std::vector<uint32_t> *map, const std:
         const bool small = total_blocks <= kCoopPassBlocks;
         // (round 6, the trial's own times: the best candidate was the HIGHEST threshold of the five at 1024x768, 1280x720, 1080p and in f64
         // everywhere -- profiles/r06_order_trials.log --, so the range now reaches further up, at both sizes)
-        for (unsigned pc : { small ? 85u : 95u, small ? 70u : 88u, small ? 58u : 80u, small ? 48u : 70u, small ? 40u : 58u, small ? 33u : 48u })
-            wants.push_back({ 0, std::max<uint32_t>((uint32_t)kCoopMinCost, exact.top * pc / 100u) });
+        const unsigned shares[6] = { small ? 85u : 95u, small ? 70u : 88u, small ? 58u : 80u, small ? 48u : 70u, small ? 40u : 58u, small ? 33u : 48u };
+        auto given_thr = [&shares](const ExactCosts &ex, size_t k) { return std::max<uint32_t>((uint32_t)kCoopMinCost, ex.top * shares[k] / 100u); };
+        auto quads_from = [](const std::vector<uint32_t> &q, uint32_t thr) { return (uint32_t)std::count_if(q.begin(), q.end(), [thr](uint32_t v) { return v >= thr; }); };
+        if (!tight) {
+            const std::vector<uint32_t> q = coop_quads ? exact_quad_costs(exact) : std::vector<uint32_t>();
+            if (coop_quads) coop_quads->clear();
+            for (size_t k = 0; k < 6; ++k) {
+                wants.push_back({ 0, given_thr(exact, k) });
+                if (coop_quads) coop_quads->push_back(quads_from(q, given_thr(exact, k)));
+            }
+        } else {
+            // Those shares were tuned on given-stream counts, and the tight streams shorten the heavy walks most (about 0.7 of the given counts
+            // at the heavy end, less further down): a share of the tight top means another budget.  What the trial tuned is how many quads
+            // leave their waves -- every one costs a wave of its own --, so each tight threshold is the quantile of the TIGHT recount that
+            // picks as many quads as the given-stream threshold in its place picked of the given recount (taken from this list's given-stream
+            // build, or counted here when there was none: a list first seen with the tight streams there).
+            std::vector<uint32_t> budget;
+            if (coop_quads && coop_quads->size() == 6) budget = *coop_quads;
+            else {
+                ExactCosts given;
+                recount_heaviest(s, cost_map_of(s), tab, w, h, passes, false, given);
+                const std::vector<uint32_t> gq = exact_quad_costs(given);
+                for (size_t k = 0; k < 6; ++k) budget.push_back(given.block.empty() ? 0u : quads_from(gq, given_thr(given, k)));
+            }
+            std::vector<uint32_t> q = exact_quad_costs(exact);
+            std::sort(q.begin(), q.end(), std::greater<uint32_t>());
+            for (size_t k = 0; k < 6; ++k) {
+                const size_t rank = std::min<size_t>(std::max<uint32_t>(budget[k], 1u), q.size());       // (q holds 64 quads per counted block: never empty here)
+                wants.push_back({ 0, std::max<uint32_t>((uint32_t)kCoopMinCost, q[rank - 1]) });
+            }
+        }
     } else if (coop_pass && map && !two_rays && total_blocks <= kCoopPassBlocks && !knobs)
         wants = { { 0, 0u }, { 28, 0u }, { 34, 0u }, { 40, 0u }, { 48, 0u }, { 58, 0u } };
     else if (coop_pass && !two_rays && knobs && (knob(RT_DEBUG_COOP) > 0 || knob(RT_DEBUG_COOP_THR) >= 0 || knob(RT_DEBUG_COOP_MAX) >= 0)) { wants = { { 0, 0u }, { -1, 0u } }; asked = true; }       // as asked, behind the plain one
@@ -581,7 +687,7 @@ rt_status build_orders(rt_scene *s, const std::vector<uint32_t> *map, const std:
     std::vector<Host> cand;
     for (const Want &wt : wants) {
         Host c;
-        block_order(map, tab, w, h, passes, c.order, c.wg_first, coop_pass ? &s->coop : nullptr, &c.holes, wt.pc, wt.exact_thr ? &exact : nullptr, wt.exact_thr);
+        block_order(map, tab, w, h, passes, c.order, c.wg_first, coop_pass ? &s->coop : nullptr, &c.holes, wt.pc, wt.exact_thr ? &exact : nullptr, wt.exact_thr, nullptr, cost_grow);
         c.any_hole = std::any_of(c.holes.begin(), c.holes.end(), [](uint64_t v) { return v != 0; });
         if (&wt != &wants[0] && !c.any_hole) continue;     // the same dispatch as the plain one
         if (!cand.empty() && wt.exact_thr && cand.back().any_hole && cand.back().holes == c.holes && cand.back().order.size() == c.order.size()) continue;   // (two thresholds, the same quads)
@@ -704,6 +810,7 @@ void build_orders_async(rt_scene *s, size_t index, std::vector<rt::TileDev> tab,
 {
     knobs_at_default();                           // this thread only exists because no dispatch control was set when the list was first seen
     std::vector<rt_scene::Order> orders;
+    std::vector<uint32_t> quads;
     int chosen = 0;
     void *arena = nullptr;
     bool ok = hipSetDevice(s->device) == hipSuccess;
@@ -711,24 +818,61 @@ void build_orders_async(rt_scene *s, size_t index, std::vector<rt::TileDev> tab,
         const std::vector<uint32_t> *map = cost_map_of(s);
         // (the uploads are blocking copies: the data is in device memory when they return.  No device-wide synchronise here -- the caller's
         // own launches keep the device busy and it would wait for all of them)
-        ok = build_orders(s, map, tab, w, h, passes, orders, chosen, &arena) == RT_OK;
+        ok = build_orders(s, map, tab, w, h, passes, orders, chosen, &arena, false, &quads) == RT_OK;
     }
     (void)hipGetLastError();
     {
         std::lock_guard<std::mutex> lk(s->mu);
         rt_scene::CachedTable &t = s->tables[index];
-        if (ok) { t.orders = std::move(orders); t.chosen = chosen; t.order_arena = arena; }
+        if (ok) { t.orders = std::move(orders); t.chosen = chosen; t.order_arena = arena; t.coop_quads = std::move(quads); }
         t.building = false;
     }
     // The tight streams (rt_capi_scene.hpp ensure_tight) behind the orders -- those are what the caller's next frames wait for, and a deep
-    // scene's tight spheres take the host a few tenths of a second.  Lists whose orders are being tried, or were, on the given streams are
-    // tried once more on the streams their frames walk from now on.
+    // scene's tight spheres take the host a few tenths of a second.  Then, for every list whose launches walk them (table_walks_tight), what
+    // its orders are made from once more, COUNTED ON THEM: the tight cost map (once per scene), the list's exact recount, a fresh set of
+    // orders -- swapped in under the scene's lock, tried by pick_order like the first set.  The first set stays where it is until the table
+    // goes: launches enqueued before the swap may still be reading it.  (A list first seen later, with the tight streams there, takes the
+    // same two steps: its given-stream orders come a cost map sooner.)
     const bool had = s->tight_ready.load(std::memory_order_acquire);
-    if (ok && !had && ensure_tight(s) && s->tight_by_rule) {
+    // (RT_DEBUG_PRINT_STEPS, hooks build: what this second pass costs the worker -- the control leaves a list in the background)
+    StageClock clk;
+    clk.on = print_knob(RT_DEBUG_PRINT_STEPS) > 0;
+    if (!ok || !ensure_tight(s)) { (void)hipGetLastError(); return; }
+    clk.lap("worker: tight streams");
+    struct Todo { size_t index; std::vector<rt::TileDev> tab; unsigned w, h, passes; std::vector<uint32_t> quads; };
+    std::vector<Todo> todo;
+    {
         std::lock_guard<std::mutex> lk(s->mu);
-        for (auto &t : s->tables)
-            if (t.orders.size() > 1 && t.orders[0].e0[0]) t.retrial = true;
+        for (size_t i = 0; i < s->tables.size(); ++i) {
+            rt_scene::CachedTable &t = s->tables[i];
+            // (only lists the background was given: one first seen under a dispatch control got what it asked for from its caller)
+            if (!t.from_worker || t.building || t.tight_costs || t.tight_pending || t.orders.empty() || !table_walks_tight(s, t.host, t.passes, t.tight_knob)) continue;
+            if (t.tight_costs_knob == 0) {       // (A/B: the given-stream orders stay, tried once more on the streams walked from now on)
+                if (!had && t.orders.size() > 1 && t.orders[0].e0[0]) t.retrial = true;
+                continue;
+            }
+            t.tight_pending = true;
+            todo.push_back(Todo{ i, t.host, t.w, t.h, t.passes, t.coop_quads });
+        }
     }
+    const std::vector<uint32_t> *tmap = todo.empty() ? nullptr : tight_cost_map_of(s);
+    clk.lap("worker: tight cost map");
+    for (Todo &td : todo) {
+        std::vector<rt_scene::Order> fresh;
+        int fresh_chosen = 0;
+        void *fresh_arena = nullptr;
+        const bool built = tmap && build_orders(s, tmap, td.tab, td.w, td.h, td.passes, fresh, fresh_chosen, &fresh_arena, true, &td.quads) == RT_OK;
+        (void)hipGetLastError();
+        std::lock_guard<std::mutex> lk(s->mu);
+        rt_scene::CachedTable &t = s->tables[td.index];
+        t.tight_pending = false;
+        if (built) {
+            for (auto &od : t.orders) t.retired_orders.push_back(od);
+            if (t.order_arena) t.retired_arenas.push_back(t.order_arena);
+            t.orders = std::move(fresh); t.chosen = fresh_chosen; t.order_arena = fresh_arena; t.turn = 0; t.retrial = false; t.tight_costs = true;
+        } else if (!had && t.orders.size() > 1 && t.orders[0].e0[0]) t.retrial = true;      // (no tight costs: at least time the given-stream orders on the streams walked now)
+    }
+    clk.lap("worker: tight dispatch orders");
     (void)hipGetLastError();
 }
 
@@ -741,9 +885,11 @@ rt_status device_table(rt_scene *s, Context *c, const std::vector<rt::TileDev> &
     if (order_out) *order_out = rt::BlockList{};
     StageClock clk;
     // the cooperative walk's controls (rt_debug.h) are part of a dispatch table's identity: tests render one tile list with and without
+    // (and RT_DEBUG_TIGHT_BOUNDS: which streams a list's launches walk decides which costs its orders are built from)
     long long coop_key = 0;
     if (o && order_out)
-        for (int k : { RT_DEBUG_COOP, RT_DEBUG_COOP_THR, RT_DEBUG_COOP_MAX, RT_DEBUG_COOP_LEVEL, RT_DEBUG_COOP_REST, RT_DEBUG_NARROW_MAX, RT_DEBUG_NARROW_L2, RT_DEBUG_SKIP_RAYS, RT_DEBUG_EXACT_COSTS })
+        for (int k : { RT_DEBUG_COOP, RT_DEBUG_COOP_THR, RT_DEBUG_COOP_MAX, RT_DEBUG_COOP_LEVEL, RT_DEBUG_COOP_REST, RT_DEBUG_NARROW_MAX, RT_DEBUG_NARROW_L2, RT_DEBUG_SKIP_RAYS, RT_DEBUG_EXACT_COSTS,
+                       RT_DEBUG_TIGHT_BOUNDS, RT_DEBUG_TIGHT_COSTS })
             coop_key = coop_key * 1000003ll + (knob(k) + 2);
     if (cacheable) {
         std::lock_guard<std::mutex> lk(s->mu);
@@ -789,14 +935,20 @@ rt_status device_table(rt_scene *s, Context *c, const std::vector<rt::TileDev> &
             hipError_t e = async_copy ? hipSuccess : hipMemcpy(t.dev, tab.data(), bytes, hipMemcpyHostToDevice);    // blocking, once per table
             clk.lap("tile table upload");
             if (e != hipSuccess) { drop(); return hip_fail(e, "hipMemcpy(tile table)", __LINE__); }
+            t.tight_knob = knob(RT_DEBUG_TIGHT_BOUNDS); t.tight_costs_knob = knob(RT_DEBUG_TIGHT_COSTS);
             if (want_orders && !in_background) {
+                // (the caller waits for all of it: the tight streams first, so that a list whose launches walk them gets its orders from
+                // their costs at once)
                 const std::vector<uint32_t> *map = cost_map_of(s);
                 clk.lap("cost map (cached after 1st)");
-                rt_status bst = build_orders(s, map, tab, w, h, passes, t.orders, t.chosen, &t.order_arena);
-                clk.lap("dispatch orders");
-                if (bst != RT_OK) { drop(); return bst; }
                 (void)ensure_tight(s);
                 clk.lap("tight streams (1st list only)");
+                if (t.tight_costs_knob != 0 && table_walks_tight(s, tab, passes, t.tight_knob))
+                    if (const std::vector<uint32_t> *tmap = tight_cost_map_of(s)) { map = tmap; t.tight_costs = true; }
+                clk.lap("tight cost map (cached after 1st)");
+                rt_status bst = build_orders(s, map, tab, w, h, passes, t.orders, t.chosen, &t.order_arena, t.tight_costs);
+                clk.lap("dispatch orders");
+                if (bst != RT_OK) { drop(); return bst; }
             }
             // The copies above are blocking for the host, but the render kernel runs on another (non-blocking) stream: make sure
             // the tables have landed in device memory before anything can be launched against them (once per tile list).
@@ -805,7 +957,7 @@ rt_status device_table(rt_scene *s, Context *c, const std::vector<rt::TileDev> &
                 if (e != hipSuccess) { drop(); return hip_fail(e, "hipDeviceSynchronize(tile tables)", __LINE__); }
             }
             clk.lap("device sync");
-            t.building = in_background;
+            t.building = in_background; t.from_worker = in_background;
             t.host = tab; t.w = w; t.h = h; t.passes = passes; t.coop_key = coop_key;
             *out = t.dev;
             s->tables.push_back(std::move(t));

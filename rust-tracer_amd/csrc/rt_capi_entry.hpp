@@ -323,7 +323,14 @@ rt_status rt_scene_destroy(rt_scene *s)
     forget_scene(s);
     if (s->ahead.stream) { (void)hipStreamSynchronize(s->ahead.stream); (void)hipStreamDestroy(s->ahead.stream); }      // a pass rendered ahead may still be running
     s->pool.clear();
-    for (auto &t : s->tables) { (void)hipFree(t.dev); for (auto &od : t.orders) release_order(od); if (t.order_arena) (void)hipFree(t.order_arena); if (t.landed) (void)hipEventDestroy(t.landed); }
+    for (auto &t : s->tables) {
+        (void)hipFree(t.dev);
+        for (auto &od : t.orders) release_order(od);
+        for (auto &od : t.retired_orders) release_order(od);
+        if (t.order_arena) (void)hipFree(t.order_arena);
+        for (void *a : t.retired_arenas) (void)hipFree(a);
+        if (t.landed) (void)hipEventDestroy(t.landed);
+    }
     if (s->dynamic) {                                      // (its stream is part of d_dyn)
         s->d_shad = s->d_query_items = nullptr;
         if (s->cost_stream) (void)hipStreamSynchronize(s->cost_stream);

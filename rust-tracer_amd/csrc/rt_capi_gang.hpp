@@ -420,6 +420,14 @@ rt_status rt_debug_shard_costs(rt_scene *s, const rt_options *o, const rt_region
     if (!map) { snprintf(g_err, sizeof g_err, "rt_debug_shard_costs: the scene has no cost map (no hierarchy)"); return RT_ERR_UNSUPPORTED; }
     constexpr int R = (int)kCostRes;
     const unsigned w = o->width, h = o->height;
+    // (the costs of the streams a launch of these buckets walks, like the dispatch orders of their tile list: build_orders)
+    {
+        uint64_t total_px = 0;
+        for (uint32_t i = 0; i < n; ++i) total_px += (uint64_t)(tiles[i].r - tiles[i].l) * (tiles[i].t - tiles[i].b);
+        (void)ensure_tight(s);      // (made here if nobody has yet: the answer does not depend on when the scene's worker ran)
+        if (walks_tight(s, skip_variant(s), total_px, o->samples_per_pixel))
+            if (const std::vector<uint32_t> *tmap = tight_cost_map_of(s)) map = tmap;
+    }
     for (uint32_t d = 0; d < n_devices; ++d) cost[d] = 0.0;
     for (uint32_t i = 0; i < n; ++i) {
         double c = 0.0;
@@ -431,6 +439,21 @@ rt_status rt_debug_shard_costs(rt_scene *s, const rt_options *o, const rt_region
             }
         cost[i % n_devices] += c;
     }
+    return RT_OK;
+}
+
+// Test infrastructure (rt_debug.h): either cost map of the scene, made if needed.
+rt_status rt_debug_cost_map(rt_scene *s, int tight, uint32_t *out)
+{
+    if (!s || !out) { snprintf(g_err, sizeof g_err, "rt_debug_cost_map: NULL argument"); return RT_ERR_INVALID_ARGUMENT; }
+    HIP_TRY(hipSetDevice(s->device));
+    if (tight) (void)ensure_tight(s);
+    const std::vector<uint32_t> *map = tight ? tight_cost_map_of(s) : cost_map_of(s);
+    if (!map) {
+        snprintf(g_err, sizeof g_err, tight ? "rt_debug_cost_map: the scene has no tight streams to count on" : "rt_debug_cost_map: the scene has no cost map (no hierarchy)");
+        return RT_ERR_UNSUPPORTED;
+    }
+    memcpy(out, map->data(), sizeof(uint32_t) * (size_t)kCostRes * kCostRes);
     return RT_OK;
 }
 #endif  // RT_TEST_HOOKS

@@ -150,20 +150,9 @@ rt::Fast2Args fast2_args(const rt_scene *s, const rt::BlockList &order, unsigned
     return a;
 }
 
-// Does this launch walk the scene's TIGHT streams (rt_tight.hpp)?  Launches of the filtered assembly loops of an f32 scene that neither
-// count nor take two rays per lane -- then the un-fused loops (VAR 19) over the tight streams, whatever the scene's own flavour is.
-// RT_DEBUG_TIGHT_BOUNDS: 0 never, 1 the rule, 2 wherever a scene has tight streams; default: the rule.  A question only: whoever wants the streams
-// made at the launch (the control at 1 or 2: tests, tools) calls ensure_tight first -- launch_render does.
-bool walks_tight(const rt_scene *s, int v, uint64_t total_px, unsigned spp)
-{
-    const long long tb = knob(RT_DEBUG_TIGHT_BOUNDS);
-    if (tb == 0 || s->precision != RT_F32 || s->dynamic || ((v & ~8) != 19 && (v & ~8) != 23)) return false;
-    if (!s->tight_ready.load(std::memory_order_acquire)) return false;
-    if (tb != 2 && (s->tight_by_rule == 0 || (s->tight_by_rule == 2 && !(spp == 1 && total_px >= kTightPartialMinPx)))) return false;
-    const long long k = knob(RT_DEBUG_SKIP_RAYS);      // the two-ray kernels keep the given streams: launch_skip_one's question, asked first
-    const bool two_rays = (k < 0 ? skip2_by_default(total_px, spp, (v & 4) ? s->n_fnodes : s->n_nodes) : k == 2) && (spp == 1 || (use_split(spp) && packed_samples(spp)));
-    return !two_rays;
-}
+// Does this launch walk the scene's TIGHT streams (walks_tight_with, rt_capi_dispatch.hpp)?  A question only: whoever wants the streams
+// made at the launch (RT_DEBUG_TIGHT_BOUNDS at 1 or 2: tests, tools) calls ensure_tight first -- launch_render does.
+bool walks_tight(const rt_scene *s, int v, uint64_t total_px, unsigned spp) { return walks_tight_with(s, v, total_px, spp, knob(RT_DEBUG_TIGHT_BOUNDS)); }
 
 template <typename T, bool COUNT, int VAR>
 rt_status launch_skip_one(const rt_scene *s, Context *c, dim3 grid, hipStream_t stream, unsigned w, unsigned h, unsigned spp,
@@ -370,6 +359,7 @@ rt_status launch_skip_var(const rt_scene *s, Context *c, dim3 grid, hipStream_t 
         if constexpr (sizeof(T) == 4) {
             if (walks_tight(s, v, total_px, spp)) {
                 g_launch_flags |= RT_LAUNCH_TIGHT_BOUNDS;
+                if (order.d && order.tight_costs) g_launch_flags |= RT_LAUNCH_TIGHT_COSTS;
 #ifdef RT_TEST_HOOKS
                 if (v & 8) return launch_skip_one<T, false, 27>(s, c, grid, stream, w, h, spp, d_tab, nt, total_px, d_out, cnt, frame_w, order, true);
 #endif

@@ -65,7 +65,9 @@ typedef enum rt_debug_key {
     RT_DEBUG_TIGHT_BOUNDS = 24,  /* the tight streams of an f32 scene (rt_tight.hpp: BOUND nodes carry a smaller sphere around their subtree's items; the un-fused filtered
                                     loops walk them): 0 never, 1 the library's rule, 2 wherever a scene has tight streams -- 1 and 2 make them at the launch if
                                     the scene's worker has not yet; default: the rule, from the launch on that finds them made.  All must render the same bytes */
-    RT_DEBUG_KEYS = 25
+    RT_DEBUG_TIGHT_COSTS = 25,   /* which costs the dispatch orders of a list whose launches walk the tight streams are built from (read when a tile list is first
+                                    seen): 0 the given streams' (what every other list gets; A/B runs); default: the tight streams' */
+    RT_DEBUG_KEYS = 26
 } rt_debug_key;
 
 /* value < 0 restores the default. */
@@ -84,7 +86,8 @@ typedef enum rt_debug_counter {
     RT_DEBUG_COUNT_COOP_LAUNCHES = 7,       /* hierarchy-walk passes whose launch carried cooperative quads (k_render_skip<..., COOP>) */
     RT_DEBUG_COUNT_TIGHT_VIOLATIONS = 8,    /* counting launches of an f32 scene that has tight streams: ITEM tests that counted where a tight bound would have put the
                                                lane to sleep (also added to RT_DEBUG_COUNT_FILTER_VIOLATIONS): must stay 0 */
-    RT_DEBUG_COUNTERS = 9
+    RT_DEBUG_COUNT_TIGHT_RECOUNTS = 9,      /* exact recounts of a tile list's heaviest blocks that walked the scene's TIGHT streams (exact_block_costs) */
+    RT_DEBUG_COUNTERS = 10
 } rt_debug_counter;
 long long rt_debug_count(int counter);
 
@@ -115,6 +118,10 @@ rt_status rt_debug_gang_layout(const rt_region *tiles, uint32_t n_tiles, uint32_
  * executed on a one-GPU box.  NULL: librccl.so again.  A gang keeps the library it was created with. */
 rt_status rt_debug_rccl_library(const char *path);
 rt_status rt_debug_shard_costs(rt_scene *scene, const rt_options *options, const rt_region *tiles, uint32_t n_tiles, uint32_t n_devices, double *cost);
+/* The scene's 256 x 256 cost map (tests per primary ray, its shadow ray included), out[65536]: tight = 0 counted on the scene's given streams,
+ * tight = 1 on its tight streams (made here if nobody made them yet; RT_ERR_UNSUPPORTED for a scene that gets none).  Either map is counted
+ * once per scene, by whoever asks first. */
+rt_status rt_debug_cost_map(rt_scene *scene, int tight, uint32_t *out);
 
 #ifdef __cplusplus
 }

@@ -55,7 +55,8 @@ constexpr uint32_t kBlockCoopShift = 20;
 struct BlockList { const BlockDesc *d = nullptr; uint32_t n = 0; const uint32_t *wg_first = nullptr; uint32_t n_wg = 0; const uint64_t *holes = nullptr; uint32_t n_holes = 0;
                    hipEvent_t ev0 = nullptr, ev1 = nullptr;
                    // the same list without cooperative quads (for launches that cannot walk them)
-                   const BlockDesc *plain_d = nullptr; uint32_t plain_n = 0; const uint32_t *plain_wg_first = nullptr; uint32_t plain_n_wg = 0; };
+                   const BlockDesc *plain_d = nullptr; uint32_t plain_n = 0; const uint32_t *plain_wg_first = nullptr; uint32_t plain_n_wg = 0;
+                   bool tight_costs = false; };      // built from costs counted on the scene's tight streams (RT_LAUNCH_TIGHT_COSTS)
 
 // Outcome of one sample, stored by the sample-parallel paths and consumed by k_resolve_samples in the reference's
 // accumulation order: the four exits of Renderer::raytrace (render.rs:190-213) and n.light where it is needed.
