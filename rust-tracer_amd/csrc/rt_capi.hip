@@ -170,6 +170,56 @@ struct Context {
     }
 };
 
+// The workspace of a two-pass list query (count, scan, fill): counts for `cap` lists, their offsets and the scan's block sums in ONE
+// allocation, shared by every call on the scene.  A call enqueues under `mu` and behind `ev`, which the call before it recorded on its
+// own stream.
+struct ListSpace {
+    std::mutex mu;
+    hipEvent_t ev = nullptr;
+    bool recorded = false;
+    void *d = nullptr;
+    uint32_t *counts = nullptr;
+    uint64_t *offsets = nullptr, *sums = nullptr;
+    uint64_t *h_total = nullptr, *d_total = nullptr;      // one pinned word and its device alias: the host entries read the total here (no copy into a caller's stack)
+    size_t cap = 0;
+
+    rt_status make_total()
+    {
+        if (h_total) return RT_OK;
+        void *h = nullptr, *alias = nullptr;
+        HIP_TRY(hipHostMalloc(&h, 64, hipHostMallocDefault));
+        if (const hipError_t e = hipHostGetDevicePointer(&alias, h, 0); e != hipSuccess) { (void)hipHostFree(h); return hip_fail(e, "hipHostGetDevicePointer(total)", __LINE__); }
+        h_total = static_cast<uint64_t *>(h);
+        d_total = static_cast<uint64_t *>(alias);
+        return RT_OK;
+    }
+
+    // Room for n lists and `extra` bytes behind them, which *extra_out points at (nothing may be using what it replaces).
+    rt_status make_room(size_t n, size_t extra, uint8_t **extra_out)
+    {
+        if (d) HIP_TRY(hipFree(d));
+        d = nullptr; cap = 0;
+        const size_t n_sums = (n + rt::kScanBlock - 1) / rt::kScanBlock;
+        const size_t o_offsets = (sizeof(uint32_t) * n + 255) & ~(size_t)255, o_sums = o_offsets + ((sizeof(uint64_t) * (n + 1) + 255) & ~(size_t)255);
+        const size_t o_extra = o_sums + ((sizeof(uint64_t) * (n_sums + 1) + 255) & ~(size_t)255);
+        HIP_TRY(hipMalloc(&d, o_extra + extra));
+        uint8_t *const p = static_cast<uint8_t *>(d);
+        cap = n;
+        counts = reinterpret_cast<uint32_t *>(p);
+        offsets = reinterpret_cast<uint64_t *>(p + o_offsets);
+        sums = reinterpret_cast<uint64_t *>(p + o_sums);
+        if (extra_out) *extra_out = p + o_extra;
+        return RT_OK;
+    }
+
+    void free_all()
+    {
+        if (d) (void)hipFree(d);
+        if (ev) (void)hipEventDestroy(ev);
+        if (h_total) (void)hipHostFree(h_total);
+    }
+};
+
 }  // namespace
 
 struct rt_scene {
@@ -316,34 +366,19 @@ struct rt_scene {
     hipEvent_t upd_ev = nullptr;       // behind the last update
     void *d_rebuild = nullptr;         // rt_scene_rebuild*: the sort's workspace for n_items keys and the gathered items behind it (rt_rebuild.hpp), made by the first rebuild
     std::mutex rebuild_mu;             // (two first rebuilds at once make it once)
-    // ---- contact pairs (rt_scene_contacts*, rt_contacts.hpp): the workspace of the two passes -- counts, offsets, the scan's block sums and,
-    // on a scene that is not dynamic, the item-to-node table -- made by the first call and shared by all: a call enqueues under contacts_mu
-    // and behind contacts_ev, which the call before it recorded on its own stream
-    std::mutex contacts_mu;
-    void *d_contacts = nullptr;
-    uint32_t *d_contacts_counts = nullptr, *d_contacts_item_node = nullptr;
-    uint64_t *d_contacts_offsets = nullptr, *d_contacts_sums = nullptr;
-    hipEvent_t contacts_ev = nullptr;
-    uint64_t *h_contacts_total = nullptr, *d_contacts_total = nullptr;      // one pinned word and its device alias: the host entry reads the total here (no copy into a caller's stack)
-    bool contacts_recorded = false;
+    // ---- contact pairs (rt_scene_contacts*, rt_contacts.hpp): the workspace of the two passes, for n_items lists, and -- on a scene that is not
+    // dynamic -- the item-to-node table behind it, made by the first call
+    ListSpace contacts;
+    uint32_t *d_contacts_item_node = nullptr;
     // ---- impact pairs (rt_scene_impacts*, rt_impacts.hpp): the motion table -- one record per stream node -- with the nodes' lengths and their
-    // chunk maxima behind it, made by the first impacts call under contacts_mu; impacts calls share the counts, offsets and sums above
+    // chunk maxima behind it, made by the first impacts call under contacts.mu; impacts calls share the contacts workspace
     void *d_impacts = nullptr;
     uint32_t impacts_cap = 0;          // nodes d_impacts has room for
-    // ---- overlap lists (rt_overlap_spheres*, rt_overlap.hpp): the workspace of the two passes -- counts, offsets and the scan's block sums
-    // for overlap_cap queries -- made by the first call, grown when a call brings more queries than any before it (behind overlap_ev: the
-    // one allocation) and shared by all: a call enqueues under overlap_mu and behind overlap_ev, which the call before it recorded on its
-    // own stream
-    std::mutex overlap_mu;
-    void *d_overlap = nullptr;
-    size_t overlap_cap = 0;
-    uint32_t *d_overlap_counts = nullptr;
-    uint64_t *d_overlap_offsets = nullptr, *d_overlap_sums = nullptr;
-    hipEvent_t overlap_ev = nullptr;
-    uint64_t *h_overlap_total = nullptr, *d_overlap_total = nullptr;        // one pinned word and its device alias, as h_contacts_total
-    bool overlap_recorded = false;
+    // ---- overlap lists (rt_overlap_spheres*, rt_overlap.hpp): the workspace of the two passes, for overlap.cap queries: made by the first call,
+    // grown when a call brings more queries than any before it (behind overlap.ev)
+    ListSpace overlap;
     // ---- swept overlap lists (rt_swept_overlaps*, rt_swept.hpp): a motion table of their own -- laid out as d_impacts -- that belongs to the
-    // overlap workspace: made by the first swept call under overlap_mu, used behind overlap_ev; counts, offsets and sums are the ones above
+    // overlap workspace: made by the first swept call under overlap.mu, used behind overlap.ev
     void *d_swept = nullptr;
     uint32_t swept_cap = 0;            // nodes d_swept has room for
 };
@@ -354,6 +389,7 @@ namespace {
 #include "rt_capi_scene.hpp"
 #include "rt_capi_dispatch.hpp"
 #include "rt_capi_launch.hpp"
+#include "rt_capi_query.hpp"
 }  // namespace
 
 extern "C" {

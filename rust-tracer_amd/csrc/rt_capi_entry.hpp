@@ -343,14 +343,10 @@ rt_status rt_scene_destroy(rt_scene *s)
     if (s->d_shad) (void)hipFree(s->d_shad);
     if (s->d_query_items) (void)hipFree(s->d_query_items);
     if (s->query_items_ev) (void)hipEventDestroy(s->query_items_ev);
-    if (s->d_contacts) (void)hipFree(s->d_contacts);
+    s->contacts.free_all();
     if (s->d_impacts) (void)hipFree(s->d_impacts);
-    if (s->contacts_ev) (void)hipEventDestroy(s->contacts_ev);
-    if (s->h_contacts_total) (void)hipHostFree(s->h_contacts_total);
-    if (s->d_overlap) (void)hipFree(s->d_overlap);
+    s->overlap.free_all();
     if (s->d_swept) (void)hipFree(s->d_swept);
-    if (s->overlap_ev) (void)hipEventDestroy(s->overlap_ev);
-    if (s->h_overlap_total) (void)hipHostFree(s->h_overlap_total);
     if (s->d_cprim) (void)hipFree(s->d_cprim);
     if (s->d_cshad) (void)hipFree(s->d_cshad);
     for (void *p : { s->d_xprim, s->d_xshad, s->d_xcprim, s->d_xcshad, s->d_xown, s->d_fc, s->d_coop_prim, s->d_coop_shad, s->d_cost_arena, s->d_tight }) if (p) (void)hipFree(p);
@@ -597,38 +593,7 @@ rt_status rt_render_frame_device(rt_scene *s, const rt_options *o, rt_traversal 
 //            pinned staging and the CPU hands each caller its 16 KB.
 enum HostCopy { kCopyAuto = 0, kCopyDirect = 1, kCopyStaged = 2, kCopyZero = 3, kCopyZeroStaged = 4 };
 
-struct HostDest { bool pinned = false; uint8_t *dev_alias = nullptr; bool bad = false; size_t room = 0; };
-
-// Host ranges this library pinned itself (rt_host_alloc / rt_host_register), base -> {bytes, device alias}.  Only these are
-// written by the render kernel directly.  Asking the runtime instead (hipPointerGetAttributes) is not safe: it also reports
-// ranges it locked on its own for an earlier pageable copy, and such a record can outlive the caller's buffer -- a kernel
-// store to it is a GPU memory fault (seen as an intermittent fault on freshly allocated numpy buffers).
-struct PinnedRange { size_t bytes; uint8_t *alias; };
-static std::mutex g_pinned_mu;
-static std::map<uintptr_t, PinnedRange> g_pinned;
-
-static HostDest classify_host_pointer(const void *p)
-{
-    HostDest d;
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p);
-    {
-        std::lock_guard<std::mutex> lk(g_pinned_mu);
-        auto it = g_pinned.upper_bound(a);
-        if (it != g_pinned.begin()) {
-            --it;
-            if (a - it->first < it->second.bytes) {
-                d.pinned = true;
-                d.dev_alias = it->second.alias ? it->second.alias + (a - it->first) : nullptr;
-                d.room = it->second.bytes - (a - it->first);
-                return d;
-            }
-        }
-    }
-    hipPointerAttribute_t at{};
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return d; }      // plain pageable memory
-    if (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeArray) d.bad = true;            // a device pointer is a caller error here
-    return d;
-}
+// (HostDest and classify_host_pointer, which tell the three apart: rt_capi_query.hpp)
 
 constexpr size_t kStageChunk = 1u << 20;
 
@@ -1009,76 +974,21 @@ static rt_status intersect_rays_host(rt_scene *s, rt_query mode, const void *ray
     if (!query_args_ok(s, mode, rays, tmax, n, distance_out, normal_out, item_out, what)) return RT_ERR_INVALID_ARGUMENT;
     if (ordered && !device_order_ok(order, what)) return RT_ERR_INVALID_ARGUMENT;
     const bool f32 = s->precision == RT_F32;
+    const size_t esz = f32 ? sizeof(float) : sizeof(double);
+    HostStaging::Row rows[] = { { rays, 6 * esz * n, kStageIn }, { tmax, esz * n, kStageIn }, { distance_out, esz * n, kStageOut },
+                                { normal_out, 3 * esz * n, kStageOut }, { item_out, sizeof(int32_t) * n, kStageOut }, { order, sizeof(uint32_t) * n, kStageIn } };
+    HostStaging hs(rows);
+    if (rt_status pst = hs.plan(what); pst != RT_OK) return pst;
     if (!(f32 ? query_rays_valid(static_cast<const float *>(rays), static_cast<const float *>(tmax), n)
               : query_rays_valid(static_cast<const double *>(rays), static_cast<const double *>(tmax), n)))
         return RT_ERR_INVALID_ARGUMENT;
     if (order && !order_is_permutation(order, n, what)) return RT_ERR_INVALID_ARGUMENT;
-    const ReadLock rl(s);
-    HIP_TRY(hipSetDevice(s->device));
-    rt_status st = RT_OK;
-    // Every buffer is either the caller's own memory, read and written by the kernel directly (rt_host_alloc / rt_host_register), or a
-    // device copy in the call's workspace (pageable memory: the copies go through the runtime's staging).
-    const size_t esz = f32 ? sizeof(float) : sizeof(double);
-    struct Buf { void *host; size_t bytes; bool out; uint8_t *dev; size_t off; bool staged; };
-    Buf b[6] = { { const_cast<void *>(rays), 6 * esz * n, false, nullptr, 0, false }, { const_cast<void *>(tmax), esz * n, false, nullptr, 0, false },
-                 { distance_out, esz * n, true, nullptr, 0, false }, { normal_out, 3 * esz * n, true, nullptr, 0, false },
-                 { item_out, sizeof(int32_t) * n, true, nullptr, 0, false },
-                 { const_cast<uint32_t *>(order), sizeof(uint32_t) * n, false, nullptr, 0, false } };
-    size_t need = 0;
-    for (Buf &x : b) {
-        if (!x.host) continue;
-        const HostDest d = classify_host_pointer(x.host);
-        if (d.bad) {
-            snprintf(g_err, sizeof g_err, "%s: a buffer is device memory; use %s_device", what, what);
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-        if (d.pinned && d.dev_alias && d.room >= x.bytes) { x.dev = d.dev_alias; continue; }
-        x.staged = true;
-        x.off = need;
-        need += (x.bytes + 255) & ~(size_t)255;
-    }
-    Context *c = nullptr;
-    if ((st = acquire(s, &c)) != RT_OK) return st;
-    Lease lease{ s, c };
-    const void *nodes = nullptr;
-    uint32_t n_nodes = 0;
-    if ((st = query_stream(s, c->stream, &nodes, &n_nodes)) != RT_OK) return st;
-    if (need > c->query_cap) {
-        if (c->d_query) HIP_TRY(hipFree(c->d_query));
-        c->d_query = nullptr; c->query_cap = 0;
-        HIP_TRY(hipMalloc(&c->d_query, need));
-        c->query_cap = need;
-    }
-    for (Buf &x : b)
-        if (x.staged) x.dev = static_cast<uint8_t *>(c->d_query) + x.off;
-    // from the first copy on, work of this call may be queued: an error return first waits for it
-#define HIP_DRAIN(expr)                                                                                                   \
-    do {                                                                                                                  \
-        hipError_t e__ = (expr);                                                                                          \
-        if (e__ != hipSuccess) { (void)hipStreamSynchronize(c->stream); return hip_fail(e__, #expr, __LINE__); }          \
-    } while (0)
-    for (const Buf &x : b)
-        if (x.staged && !x.out)
-            HIP_DRAIN(hipMemcpyAsync(x.dev, x.host, x.bytes, hipMemcpyHostToDevice, c->stream));
-    const uint32_t *d_order = reinterpret_cast<const uint32_t *>(b[5].dev);
-    if (ordered && !order && (st = enqueue_ray_order(s, c, b[0].dev, n, nullptr, c->stream, &d_order)) != RT_OK) {
-        (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return st;
-    }
-    if (stats) {
-        HIP_DRAIN(hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, c->stream));
-        HIP_DRAIN(hipEventRecord(c->ev0, c->stream));
-    }
-    st = enqueue_query(s, nodes, n_nodes, mode, b[0].dev, b[1].dev, n, b[2].dev, b[3].dev, reinterpret_cast<int32_t *>(b[4].dev),
-                       stats ? c->d_counters : nullptr, c->stream, d_order);
-    if (st != RT_OK) { (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return st; }
-    if (stats) HIP_DRAIN(hipEventRecord(c->ev1, c->stream));
-    for (const Buf &x : b)
-        if (x.staged && x.out)
-            HIP_DRAIN(hipMemcpyAsync(x.host, x.dev, x.bytes, hipMemcpyDeviceToHost, c->stream));
-    if (stats) return read_query_stats(c, c->stream, stats);          // synchronises the stream
-    HIP_DRAIN(hipStreamSynchronize(c->stream));
-#undef HIP_DRAIN
-    return RT_OK;
+    const uint32_t *d_order = nullptr;
+    return host_query(s, hs, stats, read_query_stats,
+                      [&](Context *c) { d_order = hs.dev<const uint32_t>(5); return ordered && !order ? enqueue_ray_order(s, c, hs.dev(0), n, nullptr, c->stream, &d_order) : RT_OK; },
+                      [&](const void *nodes, uint32_t n_nodes, rt::Counters *counters, hipStream_t stream) {
+                          return enqueue_query(s, nodes, n_nodes, mode, hs.dev(0), hs.dev(1), n, hs.dev(2), hs.dev(3), hs.dev<int32_t>(4), counters, stream, d_order);
+                      });
 }
 
 rt_status rt_intersect_rays(rt_scene *s, rt_query mode, const void *rays, const void *tmax, uint32_t n, void *distance_out, void *normal_out,
@@ -1154,75 +1064,22 @@ static rt_status intersect_rays_multi_host(rt_scene *s, rt_multihit mode, uint32
         return RT_ERR_INVALID_ARGUMENT;
     if (ordered && !device_order_ok(order, what)) return RT_ERR_INVALID_ARGUMENT;
     const bool f32 = s->precision == RT_F32;
+    const size_t esz = f32 ? sizeof(float) : sizeof(double), nk = (size_t)n * k;
+    HostStaging::Row rows[] = { { rays, 6 * esz * n, kStageIn }, { tmax, esz * n, kStageIn }, { distance_out, esz * nk, kStageOut }, { normal_out, 3 * esz * nk, kStageOut },
+                                { item_out, sizeof(int32_t) * nk, kStageOut }, { hits_out, sizeof(uint32_t) * n, kStageOut }, { order, sizeof(uint32_t) * n, kStageIn } };
+    HostStaging hs(rows);
+    if (rt_status pst = hs.plan(what); pst != RT_OK) return pst;
     if (!(f32 ? query_rays_valid(static_cast<const float *>(rays), static_cast<const float *>(tmax), n)
               : query_rays_valid(static_cast<const double *>(rays), static_cast<const double *>(tmax), n)))
         return RT_ERR_INVALID_ARGUMENT;
     if (order && !order_is_permutation(order, n, what)) return RT_ERR_INVALID_ARGUMENT;
-    const ReadLock rl(s);
-    HIP_TRY(hipSetDevice(s->device));
-    rt_status st = RT_OK;
-    // pinned buffers are read and written by the kernel in place, pageable ones go through the call's workspace (as rt_intersect_rays)
-    const size_t esz = f32 ? sizeof(float) : sizeof(double), nk = (size_t)n * k;
-    struct Buf { void *host; size_t bytes; bool out; uint8_t *dev; size_t off; bool staged; };
-    Buf b[7] = { { const_cast<void *>(rays), 6 * esz * n, false, nullptr, 0, false }, { const_cast<void *>(tmax), esz * n, false, nullptr, 0, false },
-                 { distance_out, esz * nk, true, nullptr, 0, false }, { normal_out, 3 * esz * nk, true, nullptr, 0, false },
-                 { item_out, sizeof(int32_t) * nk, true, nullptr, 0, false }, { hits_out, sizeof(uint32_t) * n, true, nullptr, 0, false },
-                 { const_cast<uint32_t *>(order), sizeof(uint32_t) * n, false, nullptr, 0, false } };
-    size_t need = 0;
-    for (Buf &x : b) {
-        if (!x.host) continue;
-        const HostDest d = classify_host_pointer(x.host);
-        if (d.bad) {
-            snprintf(g_err, sizeof g_err, "%s: a buffer is device memory; use %s_device", what, what);
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-        if (d.pinned && d.dev_alias && d.room >= x.bytes) { x.dev = d.dev_alias; continue; }
-        x.staged = true;
-        x.off = need;
-        need += (x.bytes + 255) & ~(size_t)255;
-    }
-    Context *c = nullptr;
-    if ((st = acquire(s, &c)) != RT_OK) return st;
-    Lease lease{ s, c };
-    const void *nodes = nullptr;
-    uint32_t n_nodes = 0;
-    if ((st = query_stream(s, c->stream, &nodes, &n_nodes)) != RT_OK) return st;
-    if (need > c->query_cap) {
-        if (c->d_query) HIP_TRY(hipFree(c->d_query));
-        c->d_query = nullptr; c->query_cap = 0;
-        HIP_TRY(hipMalloc(&c->d_query, need));
-        c->query_cap = need;
-    }
-    for (Buf &x : b)
-        if (x.staged) x.dev = static_cast<uint8_t *>(c->d_query) + x.off;
-    // from the first copy on, work of this call may be queued: an error return first waits for it
-#define HIP_DRAIN(expr)                                                                                                   \
-    do {                                                                                                                  \
-        hipError_t e__ = (expr);                                                                                          \
-        if (e__ != hipSuccess) { (void)hipStreamSynchronize(c->stream); return hip_fail(e__, #expr, __LINE__); }          \
-    } while (0)
-    for (const Buf &x : b)
-        if (x.staged && !x.out)
-            HIP_DRAIN(hipMemcpyAsync(x.dev, x.host, x.bytes, hipMemcpyHostToDevice, c->stream));
-    const uint32_t *d_order = reinterpret_cast<const uint32_t *>(b[6].dev);
-    if (ordered && !order && (st = enqueue_ray_order(s, c, b[0].dev, n, nullptr, c->stream, &d_order)) != RT_OK) {
-        (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return st;
-    }
-    if (stats) {
-        HIP_DRAIN(hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, c->stream));
-        HIP_DRAIN(hipEventRecord(c->ev0, c->stream));
-    }
-    st = enqueue_multihit(s, nodes, n_nodes, mode, k, b[0].dev, b[1].dev, n, b[2].dev, b[3].dev, reinterpret_cast<int32_t *>(b[4].dev),
-                          reinterpret_cast<uint32_t *>(b[5].dev), stats ? c->d_counters : nullptr, c->stream, d_order);
-    if (st != RT_OK) { (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return st; }
-    if (stats) HIP_DRAIN(hipEventRecord(c->ev1, c->stream));
-    for (const Buf &x : b)
-        if (x.staged && x.out)
-            HIP_DRAIN(hipMemcpyAsync(x.host, x.dev, x.bytes, hipMemcpyDeviceToHost, c->stream));
-    if (stats) return read_query_stats(c, c->stream, stats);          // synchronises the stream
-    HIP_DRAIN(hipStreamSynchronize(c->stream));
-#undef HIP_DRAIN
-    return RT_OK;
+    const uint32_t *d_order = nullptr;
+    return host_query(s, hs, stats, read_query_stats,
+                      [&](Context *c) { d_order = hs.dev<const uint32_t>(6); return ordered && !order ? enqueue_ray_order(s, c, hs.dev(0), n, nullptr, c->stream, &d_order) : RT_OK; },
+                      [&](const void *nodes, uint32_t n_nodes, rt::Counters *counters, hipStream_t stream) {
+                          return enqueue_multihit(s, nodes, n_nodes, mode, k, hs.dev(0), hs.dev(1), n, hs.dev(2), hs.dev(3), hs.dev<int32_t>(4), hs.dev<uint32_t>(5), counters,
+                                                  stream, d_order);
+                      });
 }
 
 rt_status rt_intersect_rays_multi(rt_scene *s, rt_multihit mode, uint32_t k, const void *rays, const void *tmax, uint32_t n, void *distance_out,
@@ -1245,23 +1102,9 @@ rt_status rt_near_spheres_device(rt_scene *s, rt_near mode, uint32_t k, const vo
 {
     const char *const what = "rt_near_spheres_device";
     if (!near_args_ok(s, mode, k, points, radius, n, exclude, order, gap_out, item_out, found_out, what)) return RT_ERR_INVALID_ARGUMENT;
-    const ReadLock rl(s);
-    HIP_TRY(hipSetDevice(s->device));
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    const void *nodes = nullptr;
-    uint32_t n_nodes = 0;
-    rt_status st = query_stream(s, stream, &nodes, &n_nodes);
-    if (st != RT_OK) return st;
-    if (!stats) return enqueue_near(s, nodes, n_nodes, mode, k, points, radius, n, exclude, order, gap_out, item_out, found_out, nullptr, stream);
-    Context *c = nullptr;
-    if ((st = acquire(s, &c)) != RT_OK) return st;
-    Lease lease{ s, c };
-    HIP_TRY(hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, stream));
-    HIP_TRY(hipEventRecord(c->ev0, stream));
-    st = enqueue_near(s, nodes, n_nodes, mode, k, points, radius, n, exclude, order, gap_out, item_out, found_out, c->d_counters, stream);
-    (void)hipEventRecord(c->ev1, stream);
-    if (st != RT_OK) { (void)hipGetLastError(); lease.inflight = true; return st; }      // (the context goes back behind what is enqueued)
-    return read_query_stats(c, stream, stats);
+    return device_query(s, stats, static_cast<hipStream_t>(hip_stream), [&](const void *nodes, uint32_t n_nodes, rt::Counters *counters, hipStream_t stream) {
+        return enqueue_near(s, nodes, n_nodes, mode, k, points, radius, n, exclude, order, gap_out, item_out, found_out, counters, stream);
+    });
 }
 
 rt_status rt_near_spheres(rt_scene *s, rt_near mode, uint32_t k, const void *points, const void *radius, uint32_t n, const int32_t *exclude,
@@ -1270,73 +1113,19 @@ rt_status rt_near_spheres(rt_scene *s, rt_near mode, uint32_t k, const void *poi
     const char *const what = "rt_near_spheres";
     if (!near_args_ok(s, mode, k, points, radius, n, exclude, order, gap_out, item_out, found_out, what)) return RT_ERR_INVALID_ARGUMENT;
     const bool f32 = s->precision == RT_F32;
+    const size_t esz = f32 ? sizeof(float) : sizeof(double), nk = (size_t)n * k;
+    HostStaging::Row rows[] = { { points, 3 * esz * n, kStageIn }, { radius, esz * n, kStageIn }, { exclude, sizeof(int32_t) * n, kStageIn }, { order, sizeof(uint32_t) * n, kStageIn },
+                                { gap_out, esz * nk, kStageOut }, { item_out, sizeof(int32_t) * nk, kStageOut }, { found_out, sizeof(uint32_t) * n, kStageOut } };
+    HostStaging hs(rows);
+    if (rt_status pst = hs.plan(what); pst != RT_OK) return pst;
     if (!(f32 ? near_points_valid(static_cast<const float *>(points), static_cast<const float *>(radius), n, what)
               : near_points_valid(static_cast<const double *>(points), static_cast<const double *>(radius), n, what)))
         return RT_ERR_INVALID_ARGUMENT;
     if (order && !order_is_permutation(order, n, what)) return RT_ERR_INVALID_ARGUMENT;
-    const ReadLock rl(s);
-    HIP_TRY(hipSetDevice(s->device));
-    rt_status st = RT_OK;
-    // pinned buffers are read and written by the kernel in place, pageable ones go through the call's workspace (as rt_intersect_rays_multi)
-    const size_t esz = f32 ? sizeof(float) : sizeof(double), nk = (size_t)n * k;
-    struct Buf { void *host; size_t bytes; bool out; uint8_t *dev; size_t off; bool staged; };
-    Buf b[7] = { { const_cast<void *>(points), 3 * esz * n, false, nullptr, 0, false }, { const_cast<void *>(radius), esz * n, false, nullptr, 0, false },
-                 { const_cast<int32_t *>(exclude), sizeof(int32_t) * n, false, nullptr, 0, false },
-                 { const_cast<uint32_t *>(order), sizeof(uint32_t) * n, false, nullptr, 0, false },
-                 { gap_out, esz * nk, true, nullptr, 0, false }, { item_out, sizeof(int32_t) * nk, true, nullptr, 0, false },
-                 { found_out, sizeof(uint32_t) * n, true, nullptr, 0, false } };
-    size_t need = 0;
-    for (Buf &x : b) {
-        if (!x.host) continue;
-        const HostDest d = classify_host_pointer(x.host);
-        if (d.bad) {
-            snprintf(g_err, sizeof g_err, "%s: a buffer is device memory; use %s_device", what, what);
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-        if (d.pinned && d.dev_alias && d.room >= x.bytes) { x.dev = d.dev_alias; continue; }
-        x.staged = true;
-        x.off = need;
-        need += (x.bytes + 255) & ~(size_t)255;
-    }
-    Context *c = nullptr;
-    if ((st = acquire(s, &c)) != RT_OK) return st;
-    Lease lease{ s, c };
-    const void *nodes = nullptr;
-    uint32_t n_nodes = 0;
-    if ((st = query_stream(s, c->stream, &nodes, &n_nodes)) != RT_OK) return st;
-    if (need > c->query_cap) {
-        if (c->d_query) HIP_TRY(hipFree(c->d_query));
-        c->d_query = nullptr; c->query_cap = 0;
-        HIP_TRY(hipMalloc(&c->d_query, need));
-        c->query_cap = need;
-    }
-    for (Buf &x : b)
-        if (x.staged) x.dev = static_cast<uint8_t *>(c->d_query) + x.off;
-    // from the first copy on, work of this call may be queued: an error return first waits for it
-#define HIP_DRAIN(expr)                                                                                                   \
-    do {                                                                                                                  \
-        hipError_t e__ = (expr);                                                                                          \
-        if (e__ != hipSuccess) { (void)hipStreamSynchronize(c->stream); return hip_fail(e__, #expr, __LINE__); }          \
-    } while (0)
-    for (const Buf &x : b)
-        if (x.staged && !x.out)
-            HIP_DRAIN(hipMemcpyAsync(x.dev, x.host, x.bytes, hipMemcpyHostToDevice, c->stream));
-    if (stats) {
-        HIP_DRAIN(hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, c->stream));
-        HIP_DRAIN(hipEventRecord(c->ev0, c->stream));
-    }
-    st = enqueue_near(s, nodes, n_nodes, mode, k, b[0].dev, b[1].dev, n, reinterpret_cast<const int32_t *>(b[2].dev),
-                      reinterpret_cast<const uint32_t *>(b[3].dev), b[4].dev, reinterpret_cast<int32_t *>(b[5].dev), reinterpret_cast<uint32_t *>(b[6].dev),
-                      stats ? c->d_counters : nullptr, c->stream);
-    if (st != RT_OK) { (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return st; }
-    if (stats) HIP_DRAIN(hipEventRecord(c->ev1, c->stream));
-    for (const Buf &x : b)
-        if (x.staged && x.out)
-            HIP_DRAIN(hipMemcpyAsync(x.host, x.dev, x.bytes, hipMemcpyDeviceToHost, c->stream));
-    if (stats) return read_query_stats(c, c->stream, stats);          // synchronises the stream
-    HIP_DRAIN(hipStreamSynchronize(c->stream));
-#undef HIP_DRAIN
-    return RT_OK;
+    return host_query(s, hs, stats, read_query_stats, no_pre_step, [&](const void *nodes, uint32_t n_nodes, rt::Counters *counters, hipStream_t stream) {
+        return enqueue_near(s, nodes, n_nodes, mode, k, hs.dev(0), hs.dev(1), n, hs.dev<const int32_t>(2), hs.dev<const uint32_t>(3), hs.dev(4), hs.dev<int32_t>(5),
+                            hs.dev<uint32_t>(6), counters, stream);
+    });
 }
 
 // ---- sphere casts: the first contact of a moving sphere with the scene (rt_sweep.hpp) ----
@@ -1346,23 +1135,9 @@ rt_status rt_sweep_spheres_device(rt_scene *s, rt_sweep mode, const void *rays, 
 {
     const char *const what = "rt_sweep_spheres_device";
     if (!sweep_args_ok(s, mode, rays, radius, tmax, n, exclude, order, distance_out, normal_out, item_out, what)) return RT_ERR_INVALID_ARGUMENT;
-    const ReadLock rl(s);
-    HIP_TRY(hipSetDevice(s->device));
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    const void *nodes = nullptr;
-    uint32_t n_nodes = 0;
-    rt_status st = query_stream(s, stream, &nodes, &n_nodes);
-    if (st != RT_OK) return st;
-    if (!stats) return enqueue_sweep(s, nodes, n_nodes, mode, rays, radius, tmax, n, exclude, order, distance_out, normal_out, item_out, nullptr, stream);
-    Context *c = nullptr;
-    if ((st = acquire(s, &c)) != RT_OK) return st;
-    Lease lease{ s, c };
-    HIP_TRY(hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, stream));
-    HIP_TRY(hipEventRecord(c->ev0, stream));
-    st = enqueue_sweep(s, nodes, n_nodes, mode, rays, radius, tmax, n, exclude, order, distance_out, normal_out, item_out, c->d_counters, stream);
-    (void)hipEventRecord(c->ev1, stream);
-    if (st != RT_OK) { (void)hipGetLastError(); lease.inflight = true; return st; }      // (the context goes back behind what is enqueued)
-    return read_query_stats(c, stream, stats);
+    return device_query(s, stats, static_cast<hipStream_t>(hip_stream), [&](const void *nodes, uint32_t n_nodes, rt::Counters *counters, hipStream_t stream) {
+        return enqueue_sweep(s, nodes, n_nodes, mode, rays, radius, tmax, n, exclude, order, distance_out, normal_out, item_out, counters, stream);
+    });
 }
 
 rt_status rt_sweep_spheres(rt_scene *s, rt_sweep mode, const void *rays, const void *radius, const void *tmax, uint32_t n, const int32_t *exclude,
@@ -1371,74 +1146,20 @@ rt_status rt_sweep_spheres(rt_scene *s, rt_sweep mode, const void *rays, const v
     const char *const what = "rt_sweep_spheres";
     if (!sweep_args_ok(s, mode, rays, radius, tmax, n, exclude, order, distance_out, normal_out, item_out, what)) return RT_ERR_INVALID_ARGUMENT;
     const bool f32 = s->precision == RT_F32;
+    const size_t esz = f32 ? sizeof(float) : sizeof(double);
+    HostStaging::Row rows[] = { { rays, 6 * esz * n, kStageIn }, { radius, esz * n, kStageIn }, { tmax, esz * n, kStageIn }, { exclude, sizeof(int32_t) * n, kStageIn },
+                                { order, sizeof(uint32_t) * n, kStageIn }, { distance_out, esz * n, kStageOut }, { normal_out, 3 * esz * n, kStageOut },
+                                { item_out, sizeof(int32_t) * n, kStageOut } };
+    HostStaging hs(rows);
+    if (rt_status pst = hs.plan(what); pst != RT_OK) return pst;
     if (!(f32 ? sweep_casts_valid(static_cast<const float *>(rays), static_cast<const float *>(radius), static_cast<const float *>(tmax), n, what)
               : sweep_casts_valid(static_cast<const double *>(rays), static_cast<const double *>(radius), static_cast<const double *>(tmax), n, what)))
         return RT_ERR_INVALID_ARGUMENT;
     if (order && !order_is_permutation(order, n, what)) return RT_ERR_INVALID_ARGUMENT;
-    const ReadLock rl(s);
-    HIP_TRY(hipSetDevice(s->device));
-    rt_status st = RT_OK;
-    // pinned buffers are read and written by the kernel in place, pageable ones go through the call's workspace (as rt_intersect_rays)
-    const size_t esz = f32 ? sizeof(float) : sizeof(double);
-    struct Buf { void *host; size_t bytes; bool out; uint8_t *dev; size_t off; bool staged; };
-    Buf b[8] = { { const_cast<void *>(rays), 6 * esz * n, false, nullptr, 0, false }, { const_cast<void *>(radius), esz * n, false, nullptr, 0, false },
-                 { const_cast<void *>(tmax), esz * n, false, nullptr, 0, false },
-                 { const_cast<int32_t *>(exclude), sizeof(int32_t) * n, false, nullptr, 0, false },
-                 { const_cast<uint32_t *>(order), sizeof(uint32_t) * n, false, nullptr, 0, false },
-                 { distance_out, esz * n, true, nullptr, 0, false }, { normal_out, 3 * esz * n, true, nullptr, 0, false },
-                 { item_out, sizeof(int32_t) * n, true, nullptr, 0, false } };
-    size_t need = 0;
-    for (Buf &x : b) {
-        if (!x.host) continue;
-        const HostDest d = classify_host_pointer(x.host);
-        if (d.bad) {
-            snprintf(g_err, sizeof g_err, "%s: a buffer is device memory; use %s_device", what, what);
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-        if (d.pinned && d.dev_alias && d.room >= x.bytes) { x.dev = d.dev_alias; continue; }
-        x.staged = true;
-        x.off = need;
-        need += (x.bytes + 255) & ~(size_t)255;
-    }
-    Context *c = nullptr;
-    if ((st = acquire(s, &c)) != RT_OK) return st;
-    Lease lease{ s, c };
-    const void *nodes = nullptr;
-    uint32_t n_nodes = 0;
-    if ((st = query_stream(s, c->stream, &nodes, &n_nodes)) != RT_OK) return st;
-    if (need > c->query_cap) {
-        if (c->d_query) HIP_TRY(hipFree(c->d_query));
-        c->d_query = nullptr; c->query_cap = 0;
-        HIP_TRY(hipMalloc(&c->d_query, need));
-        c->query_cap = need;
-    }
-    for (Buf &x : b)
-        if (x.staged) x.dev = static_cast<uint8_t *>(c->d_query) + x.off;
-    // from the first copy on, work of this call may be queued: an error return first waits for it
-#define HIP_DRAIN(expr)                                                                                                   \
-    do {                                                                                                                  \
-        hipError_t e__ = (expr);                                                                                          \
-        if (e__ != hipSuccess) { (void)hipStreamSynchronize(c->stream); return hip_fail(e__, #expr, __LINE__); }          \
-    } while (0)
-    for (const Buf &x : b)
-        if (x.staged && !x.out)
-            HIP_DRAIN(hipMemcpyAsync(x.dev, x.host, x.bytes, hipMemcpyHostToDevice, c->stream));
-    if (stats) {
-        HIP_DRAIN(hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, c->stream));
-        HIP_DRAIN(hipEventRecord(c->ev0, c->stream));
-    }
-    st = enqueue_sweep(s, nodes, n_nodes, mode, b[0].dev, b[1].dev, b[2].dev, n, reinterpret_cast<const int32_t *>(b[3].dev),
-                       reinterpret_cast<const uint32_t *>(b[4].dev), b[5].dev, b[6].dev, reinterpret_cast<int32_t *>(b[7].dev),
-                       stats ? c->d_counters : nullptr, c->stream);
-    if (st != RT_OK) { (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return st; }
-    if (stats) HIP_DRAIN(hipEventRecord(c->ev1, c->stream));
-    for (const Buf &x : b)
-        if (x.staged && x.out)
-            HIP_DRAIN(hipMemcpyAsync(x.host, x.dev, x.bytes, hipMemcpyDeviceToHost, c->stream));
-    if (stats) return read_query_stats(c, c->stream, stats);          // synchronises the stream
-    HIP_DRAIN(hipStreamSynchronize(c->stream));
-#undef HIP_DRAIN
-    return RT_OK;
+    return host_query(s, hs, stats, read_query_stats, no_pre_step, [&](const void *nodes, uint32_t n_nodes, rt::Counters *counters, hipStream_t stream) {
+        return enqueue_sweep(s, nodes, n_nodes, mode, hs.dev(0), hs.dev(1), hs.dev(2), n, hs.dev<const int32_t>(3), hs.dev<const uint32_t>(4), hs.dev(5), hs.dev(6),
+                             hs.dev<int32_t>(7), counters, stream);
+    });
 }
 
 // ---- contact pairs: every pair of spheres of the scene closer than a margin (rt_contacts.hpp) ----
@@ -1448,36 +1169,13 @@ rt_status rt_scene_contacts_device(rt_scene *s, double margin, uint32_t capacity
 {
     const char *const what = "rt_scene_contacts_device";
     if (!contacts_args_ok(s, margin, capacity, pairs_out, gap_out, offsets_out, total_out, what)) return RT_ERR_INVALID_ARGUMENT;
-    const ReadLock rl(s);
-    HIP_TRY(hipSetDevice(s->device));
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    const void *nodes = nullptr;
-    uint32_t n_nodes = 0;
-    rt_status st = query_stream(s, stream, &nodes, &n_nodes);
-    if (st != RT_OK) return st;
-    Context *c = nullptr;
-    Lease lease{ s, nullptr };
-    if (stats) {
-        if ((st = acquire(s, &c)) != RT_OK) return st;
-        lease.c = c;
-    }
-    {
-        std::lock_guard<std::mutex> lk(s->contacts_mu);
-        if ((st = contacts_begin(s, nodes, n_nodes, stream)) != RT_OK) return st;
-        if (stats) {
-            HIP_TRY(hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, stream));
-            HIP_TRY(hipEventRecord(c->ev0, stream));
-        }
-        st = enqueue_contacts_count(s, nodes, n_nodes, margin, offsets_out, total_out, stats ? c->d_counters : nullptr, stream);
-        if (st == RT_OK && capacity != 0u && pairs_out) st = enqueue_contacts_fill(s, nodes, n_nodes, margin, capacity, pairs_out, gap_out, stream);
-        // whatever was enqueued uses the workspace: the next call goes behind it
-        if (hipEventRecord(s->contacts_ev, stream) == hipSuccess) s->contacts_recorded = true;
-        else { (void)hipGetLastError(); (void)hipStreamSynchronize(stream); }
-    }
-    if (!stats) return st;
-    (void)hipEventRecord(c->ev1, stream);
-    if (st != RT_OK) { (void)hipGetLastError(); lease.inflight = true; return st; }      // (the context goes back behind what is enqueued)
-    return read_query_stats(c, stream, stats);
+    return device_list_query(
+        s, s->contacts, capacity != 0u && pairs_out, stats, static_cast<hipStream_t>(hip_stream),
+        [&](const void *nodes, uint32_t n_nodes, hipStream_t stream) { return contacts_begin(s, nodes, n_nodes, stream); },
+        [&](const void *nodes, uint32_t n_nodes, rt::Counters *counters, hipStream_t stream) {
+            return enqueue_contacts_count(s, nodes, n_nodes, margin, offsets_out, total_out, counters, stream);
+        },
+        [&](const void *nodes, uint32_t n_nodes, hipStream_t stream) { return enqueue_contacts_fill(s, nodes, n_nodes, margin, capacity, pairs_out, gap_out, stream); });
 }
 
 rt_status rt_scene_contacts(rt_scene *s, double margin, uint32_t capacity, int32_t *pairs_out, void *gap_out, uint64_t *offsets_out, uint64_t *total_out,
@@ -1485,82 +1183,22 @@ rt_status rt_scene_contacts(rt_scene *s, double margin, uint32_t capacity, int32
 {
     const char *const what = "rt_scene_contacts";
     if (!contacts_args_ok(s, margin, capacity, pairs_out, gap_out, offsets_out, total_out, what)) return RT_ERR_INVALID_ARGUMENT;
-    const ReadLock rl(s);
-    HIP_TRY(hipSetDevice(s->device));
-    rt_status st = RT_OK;
     const bool fill = capacity != 0u && pairs_out;
-    // pinned buffers are written by the kernels in place, pageable ones go through the call's workspace (as rt_near_spheres)
     const size_t esz = s->precision == RT_F32 ? sizeof(float) : sizeof(double);
-    struct Buf { void *host; size_t bytes, unit; uint8_t *dev; size_t off; bool staged; };
-    Buf b[3] = { { fill ? pairs_out : nullptr, 2 * sizeof(int32_t) * (size_t)capacity, 2 * sizeof(int32_t), nullptr, 0, false },
-                 { fill ? gap_out : nullptr, esz * (size_t)capacity, esz, nullptr, 0, false },
-                 { offsets_out, sizeof(uint64_t) * ((size_t)s->n_items + 1), 0, nullptr, 0, false } };
-    size_t need = 0;
-    for (Buf &x : b) {
-        if (!x.host) continue;
-        const HostDest d = classify_host_pointer(x.host);
-        if (d.bad) {
-            snprintf(g_err, sizeof g_err, "%s: a buffer is device memory; use %s_device", what, what);
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-        if (d.pinned && d.dev_alias && d.room >= x.bytes) { x.dev = d.dev_alias; continue; }
-        x.staged = true;
-        x.off = need;
-        need += (x.bytes + 255) & ~(size_t)255;
-    }
-    if (classify_host_pointer(total_out).bad) {
-        snprintf(g_err, sizeof g_err, "%s: a buffer is device memory; use %s_device", what, what);
-        return RT_ERR_INVALID_ARGUMENT;
-    }
-    Context *c = nullptr;
-    if ((st = acquire(s, &c)) != RT_OK) return st;
-    Lease lease{ s, c };
-    const void *nodes = nullptr;
-    uint32_t n_nodes = 0;
-    if ((st = query_stream(s, c->stream, &nodes, &n_nodes)) != RT_OK) return st;
-    if (need > c->query_cap) {
-        if (c->d_query) HIP_TRY(hipFree(c->d_query));
-        c->d_query = nullptr; c->query_cap = 0;
-        HIP_TRY(hipMalloc(&c->d_query, need));
-        c->query_cap = need;
-    }
-    for (Buf &x : b)
-        if (x.staged) x.dev = static_cast<uint8_t *>(c->d_query) + x.off;
-    // the two passes share the scene's workspace and this call reads the total between them: host calls on one scene take turns
-    std::lock_guard<std::mutex> lk(s->contacts_mu);
-    if ((st = contacts_begin(s, nodes, n_nodes, c->stream)) != RT_OK) return st;
-    // from here on work of this call may be queued: an error return first waits for it
-#define HIP_DRAIN(expr)                                                                                                   \
-    do {                                                                                                                  \
-        hipError_t e__ = (expr);                                                                                          \
-        if (e__ != hipSuccess) { (void)hipStreamSynchronize(c->stream); return hip_fail(e__, #expr, __LINE__); }          \
-    } while (0)
-    if (stats) {
-        HIP_DRAIN(hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, c->stream));
-        HIP_DRAIN(hipEventRecord(c->ev0, c->stream));
-    }
-    // the scan writes the total into the scene's pinned word: an asynchronous copy into this frame would have the runtime lock a page of
-    // the caller's stack, and keep its record of it when the thread and its stack are gone
-    st = enqueue_contacts_count(s, nodes, n_nodes, margin, reinterpret_cast<uint64_t *>(b[2].dev), s->d_contacts_total, stats ? c->d_counters : nullptr, c->stream);
-    if (st != RT_OK) { (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return st; }
-    if (b[2].staged) HIP_DRAIN(hipMemcpyAsync(b[2].host, b[2].dev, b[2].bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_DRAIN(hipStreamSynchronize(c->stream));
-    const uint64_t total = *static_cast<volatile uint64_t *>(s->h_contacts_total);
-    *total_out = total;
-    const size_t written = (size_t)std::min<uint64_t>(total, capacity);
-    if (fill && written) {
-        st = enqueue_contacts_fill(s, nodes, n_nodes, margin, capacity, reinterpret_cast<int32_t *>(b[0].dev), b[1].dev, c->stream);
-        if (st != RT_OK) { (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return st; }
-        for (int k = 0; k < 2; ++k)                                  // (only what was written: the caller's bytes behind it stay)
-            if (b[k].staged && b[k].host) HIP_DRAIN(hipMemcpyAsync(b[k].host, b[k].dev, b[k].unit * written, hipMemcpyDeviceToHost, c->stream));
-    }
-    if (stats) {
-        HIP_DRAIN(hipEventRecord(c->ev1, c->stream));
-        return read_query_stats(c, c->stream, stats);                // synchronises the stream
-    }
-    HIP_DRAIN(hipStreamSynchronize(c->stream));
-#undef HIP_DRAIN
-    return RT_OK;
+    HostStaging::Row rows[] = { { fill ? pairs_out : nullptr, 2 * sizeof(int32_t) * (size_t)capacity, kStageOut, 2 * sizeof(int32_t) },
+                                { fill ? gap_out : nullptr, esz * (size_t)capacity, kStageOut, esz },
+                                { offsets_out, sizeof(uint64_t) * ((size_t)s->n_items + 1), kStageOut } };
+    HostStaging hs(rows);
+    if (rt_status pst = hs.plan(what, total_out); pst != RT_OK) return pst;
+    return host_list_query(
+        s, s->contacts, hs, capacity, fill, total_out, stats,
+        [&](const void *nodes, uint32_t n_nodes, hipStream_t stream) { return contacts_begin(s, nodes, n_nodes, stream); },
+        [&](const void *nodes, uint32_t n_nodes, rt::Counters *counters, hipStream_t stream) {
+            return enqueue_contacts_count(s, nodes, n_nodes, margin, hs.dev<uint64_t>(2), s->contacts.d_total, counters, stream);
+        },
+        [&](const void *nodes, uint32_t n_nodes, hipStream_t stream) {
+            return enqueue_contacts_fill(s, nodes, n_nodes, margin, capacity, hs.dev<int32_t>(0), hs.dev(1), stream);
+        });
 }
 
 // ---- impact pairs: every pair of spheres of the scene that comes into contact during one step, and when (rt_impacts.hpp) ----
@@ -1570,37 +1208,14 @@ rt_status rt_scene_impacts_device(rt_scene *s, const void *disp, uint32_t capaci
 {
     const char *const what = "rt_scene_impacts_device";
     if (!impacts_args_ok(s, disp, capacity, pairs_out, time_out, offsets_out, total_out, what)) return RT_ERR_INVALID_ARGUMENT;
-    const ReadLock rl(s);
-    HIP_TRY(hipSetDevice(s->device));
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    const void *nodes = nullptr;
-    uint32_t n_nodes = 0;
-    rt_status st = query_stream(s, stream, &nodes, &n_nodes);
-    if (st != RT_OK) return st;
-    Context *c = nullptr;
-    Lease lease{ s, nullptr };
-    if (stats) {
-        if ((st = acquire(s, &c)) != RT_OK) return st;
-        lease.c = c;
-    }
-    {
-        // impacts calls take their turn with contacts calls: they share the counts and the offsets
-        std::lock_guard<std::mutex> lk(s->contacts_mu);
-        if ((st = impacts_begin(s, nodes, n_nodes, stream)) != RT_OK) return st;
-        if (stats) {
-            HIP_TRY(hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, stream));
-            HIP_TRY(hipEventRecord(c->ev0, stream));
-        }
-        st = enqueue_impacts_count(s, nodes, n_nodes, disp, offsets_out, total_out, stats ? c->d_counters : nullptr, stream);
-        if (st == RT_OK && capacity != 0u && pairs_out) st = enqueue_impacts_fill(s, nodes, n_nodes, capacity, pairs_out, time_out, stream);
-        // whatever was enqueued uses the workspace: the next call goes behind it
-        if (hipEventRecord(s->contacts_ev, stream) == hipSuccess) s->contacts_recorded = true;
-        else { (void)hipGetLastError(); (void)hipStreamSynchronize(stream); }
-    }
-    if (!stats) return st;
-    (void)hipEventRecord(c->ev1, stream);
-    if (st != RT_OK) { (void)hipGetLastError(); lease.inflight = true; return st; }      // (the context goes back behind what is enqueued)
-    return read_query_stats(c, stream, stats);
+    // impacts calls take their turn with contacts calls: they share the counts and the offsets
+    return device_list_query(
+        s, s->contacts, capacity != 0u && pairs_out, stats, static_cast<hipStream_t>(hip_stream),
+        [&](const void *nodes, uint32_t n_nodes, hipStream_t stream) { return impacts_begin(s, nodes, n_nodes, stream); },
+        [&](const void *nodes, uint32_t n_nodes, rt::Counters *counters, hipStream_t stream) {
+            return enqueue_impacts_count(s, nodes, n_nodes, disp, offsets_out, total_out, counters, stream);
+        },
+        [&](const void *nodes, uint32_t n_nodes, hipStream_t stream) { return enqueue_impacts_fill(s, nodes, n_nodes, capacity, pairs_out, time_out, stream); });
 }
 
 rt_status rt_scene_impacts(rt_scene *s, const void *disp, uint32_t capacity, int32_t *pairs_out, void *time_out, uint64_t *offsets_out, uint64_t *total_out,
@@ -1610,85 +1225,25 @@ rt_status rt_scene_impacts(rt_scene *s, const void *disp, uint32_t capacity, int
     if (!impacts_args_ok(s, disp, capacity, pairs_out, time_out, offsets_out, total_out, what)) return RT_ERR_INVALID_ARGUMENT;
     const bool f32 = s->precision == RT_F32;
     const bool fill = capacity != 0u && pairs_out;
-    // pinned buffers are read and written by the kernels in place, pageable ones go through the call's workspace (as rt_overlap_spheres)
     const size_t esz = f32 ? sizeof(float) : sizeof(double);
-    struct Buf { void *host; size_t bytes, unit; bool out; uint8_t *dev; size_t off; bool staged; };
-    Buf b[4] = { { const_cast<void *>(disp), 3 * esz * (size_t)s->n_items, 0, false, nullptr, 0, false },
-                 { fill ? pairs_out : nullptr, 2 * sizeof(int32_t) * (size_t)capacity, 2 * sizeof(int32_t), true, nullptr, 0, false },
-                 { fill ? time_out : nullptr, esz * (size_t)capacity, esz, true, nullptr, 0, false },
-                 { offsets_out, sizeof(uint64_t) * ((size_t)s->n_items + 1), 0, true, nullptr, 0, false } };
-    size_t need = 0;
-    for (Buf &x : b) {
-        if (!x.host) continue;
-        const HostDest d = classify_host_pointer(x.host);
-        if (d.bad) {
-            snprintf(g_err, sizeof g_err, "%s: a buffer is device memory; use %s_device", what, what);
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-        if (d.pinned && d.dev_alias && d.room >= x.bytes) { x.dev = d.dev_alias; continue; }
-        x.staged = true;
-        x.off = need;
-        need += (x.bytes + 255) & ~(size_t)255;
-    }
-    if (classify_host_pointer(total_out).bad) {
-        snprintf(g_err, sizeof g_err, "%s: a buffer is device memory; use %s_device", what, what);
-        return RT_ERR_INVALID_ARGUMENT;
-    }
+    HostStaging::Row rows[] = { { disp, 3 * esz * (size_t)s->n_items, kStageIn },
+                                { fill ? pairs_out : nullptr, 2 * sizeof(int32_t) * (size_t)capacity, kStageOut, 2 * sizeof(int32_t) },
+                                { fill ? time_out : nullptr, esz * (size_t)capacity, kStageOut, esz },
+                                { offsets_out, sizeof(uint64_t) * ((size_t)s->n_items + 1), kStageOut } };
+    HostStaging hs(rows);
+    if (rt_status pst = hs.plan(what, total_out); pst != RT_OK) return pst;
     if (!(f32 ? impacts_disp_valid(static_cast<const float *>(disp), s->n_items, what) : impacts_disp_valid(static_cast<const double *>(disp), s->n_items, what)))
         return RT_ERR_INVALID_ARGUMENT;
-    const ReadLock rl(s);
-    HIP_TRY(hipSetDevice(s->device));
-    rt_status st = RT_OK;
-    Context *c = nullptr;
-    if ((st = acquire(s, &c)) != RT_OK) return st;
-    Lease lease{ s, c };
-    const void *nodes = nullptr;
-    uint32_t n_nodes = 0;
-    if ((st = query_stream(s, c->stream, &nodes, &n_nodes)) != RT_OK) return st;
-    if (need > c->query_cap) {
-        if (c->d_query) HIP_TRY(hipFree(c->d_query));
-        c->d_query = nullptr; c->query_cap = 0;
-        HIP_TRY(hipMalloc(&c->d_query, need));
-        c->query_cap = need;
-    }
-    for (Buf &x : b)
-        if (x.staged) x.dev = static_cast<uint8_t *>(c->d_query) + x.off;
-    // the two passes share the scene's contacts workspace and this call reads the total between them: host calls on one scene take turns,
-    // contacts and impacts alike
-    std::lock_guard<std::mutex> lk(s->contacts_mu);
-    if ((st = impacts_begin(s, nodes, n_nodes, c->stream)) != RT_OK) return st;
-    // from here on work of this call may be queued: an error return first waits for it
-#define HIP_DRAIN(expr)                                                                                                   \
-    do {                                                                                                                  \
-        hipError_t e__ = (expr);                                                                                          \
-        if (e__ != hipSuccess) { (void)hipStreamSynchronize(c->stream); return hip_fail(e__, #expr, __LINE__); }          \
-    } while (0)
-    if (b[0].staged) HIP_DRAIN(hipMemcpyAsync(b[0].dev, b[0].host, b[0].bytes, hipMemcpyHostToDevice, c->stream));
-    if (stats) {
-        HIP_DRAIN(hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, c->stream));
-        HIP_DRAIN(hipEventRecord(c->ev0, c->stream));
-    }
-    // the scan writes the total into the scene's pinned word, as rt_scene_contacts has it
-    st = enqueue_impacts_count(s, nodes, n_nodes, b[0].dev, reinterpret_cast<uint64_t *>(b[3].dev), s->d_contacts_total, stats ? c->d_counters : nullptr, c->stream);
-    if (st != RT_OK) { (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return st; }
-    if (b[3].staged) HIP_DRAIN(hipMemcpyAsync(b[3].host, b[3].dev, b[3].bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_DRAIN(hipStreamSynchronize(c->stream));
-    const uint64_t total = *static_cast<volatile uint64_t *>(s->h_contacts_total);
-    *total_out = total;
-    const size_t written = (size_t)std::min<uint64_t>(total, capacity);
-    if (fill && written) {
-        st = enqueue_impacts_fill(s, nodes, n_nodes, capacity, reinterpret_cast<int32_t *>(b[1].dev), b[2].dev, c->stream);
-        if (st != RT_OK) { (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return st; }
-        for (int k = 1; k < 3; ++k)                                  // (only what was written: the caller's bytes behind it stay)
-            if (b[k].staged && b[k].host) HIP_DRAIN(hipMemcpyAsync(b[k].host, b[k].dev, b[k].unit * written, hipMemcpyDeviceToHost, c->stream));
-    }
-    if (stats) {
-        HIP_DRAIN(hipEventRecord(c->ev1, c->stream));
-        return read_query_stats(c, c->stream, stats);                // synchronises the stream
-    }
-    HIP_DRAIN(hipStreamSynchronize(c->stream));
-#undef HIP_DRAIN
-    return RT_OK;
+    // (the contacts workspace: host calls on one scene take turns, contacts and impacts alike)
+    return host_list_query(
+        s, s->contacts, hs, capacity, fill, total_out, stats,
+        [&](const void *nodes, uint32_t n_nodes, hipStream_t stream) { return impacts_begin(s, nodes, n_nodes, stream); },
+        [&](const void *nodes, uint32_t n_nodes, rt::Counters *counters, hipStream_t stream) {
+            return enqueue_impacts_count(s, nodes, n_nodes, hs.dev(0), hs.dev<uint64_t>(3), s->contacts.d_total, counters, stream);
+        },
+        [&](const void *nodes, uint32_t n_nodes, hipStream_t stream) {
+            return enqueue_impacts_fill(s, nodes, n_nodes, capacity, hs.dev<int32_t>(1), hs.dev(2), stream);
+        });
 }
 
 // ---- overlap lists: every sphere of the scene within a margin of each query sphere (rt_overlap.hpp) ----
@@ -1698,37 +1253,15 @@ rt_status rt_overlap_spheres_device(rt_scene *s, const void *queries, uint32_t n
 {
     const char *const what = "rt_overlap_spheres_device";
     if (!overlap_args_ok(s, queries, n, margin, exclude, order, capacity, items_out, gap_out, offsets_out, total_out, what)) return RT_ERR_INVALID_ARGUMENT;
-    const ReadLock rl(s);
-    HIP_TRY(hipSetDevice(s->device));
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    const void *nodes = nullptr;
-    uint32_t n_nodes = 0;
-    rt_status st = query_stream(s, stream, &nodes, &n_nodes);
-    if (st != RT_OK) return st;
-    Context *c = nullptr;
-    Lease lease{ s, nullptr };
-    if (stats) {
-        if ((st = acquire(s, &c)) != RT_OK) return st;
-        lease.c = c;
-    }
-    {
-        std::lock_guard<std::mutex> lk(s->overlap_mu);
-        if ((st = overlap_begin(s, n, stream)) != RT_OK) return st;
-        if (stats) {
-            HIP_TRY(hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, stream));
-            HIP_TRY(hipEventRecord(c->ev0, stream));
-        }
-        st = enqueue_overlap_count(s, nodes, n_nodes, queries, n, margin, exclude, order, offsets_out, total_out, stats ? c->d_counters : nullptr, stream);
-        if (st == RT_OK && capacity != 0u && items_out)
-            st = enqueue_overlap_fill(s, nodes, n_nodes, queries, n, margin, exclude, order, capacity, items_out, gap_out, stream);
-        // whatever was enqueued uses the workspace: the next call goes behind it
-        if (hipEventRecord(s->overlap_ev, stream) == hipSuccess) s->overlap_recorded = true;
-        else { (void)hipGetLastError(); (void)hipStreamSynchronize(stream); }
-    }
-    if (!stats) return st;
-    (void)hipEventRecord(c->ev1, stream);
-    if (st != RT_OK) { (void)hipGetLastError(); lease.inflight = true; return st; }      // (the context goes back behind what is enqueued)
-    return read_query_stats(c, stream, stats);
+    return device_list_query(
+        s, s->overlap, capacity != 0u && items_out, stats, static_cast<hipStream_t>(hip_stream),
+        [&](const void *, uint32_t, hipStream_t stream) { return overlap_begin(s, n, stream); },
+        [&](const void *nodes, uint32_t n_nodes, rt::Counters *counters, hipStream_t stream) {
+            return enqueue_overlap_count(s, nodes, n_nodes, queries, n, margin, exclude, order, offsets_out, total_out, counters, stream);
+        },
+        [&](const void *nodes, uint32_t n_nodes, hipStream_t stream) {
+            return enqueue_overlap_fill(s, nodes, n_nodes, queries, n, margin, exclude, order, capacity, items_out, gap_out, stream);
+        });
 }
 
 rt_status rt_overlap_spheres(rt_scene *s, const void *queries, uint32_t n, double margin, const int32_t *exclude, const uint32_t *order, uint32_t capacity,
@@ -1737,93 +1270,27 @@ rt_status rt_overlap_spheres(rt_scene *s, const void *queries, uint32_t n, doubl
     const char *const what = "rt_overlap_spheres";
     if (!overlap_args_ok(s, queries, n, margin, exclude, order, capacity, items_out, gap_out, offsets_out, total_out, what)) return RT_ERR_INVALID_ARGUMENT;
     const bool f32 = s->precision == RT_F32;
+    const bool fill = capacity != 0u && items_out;
+    const size_t esz = f32 ? sizeof(float) : sizeof(double);
+    HostStaging::Row rows[] = { { queries, 4 * esz * (size_t)n, kStageIn }, { exclude, sizeof(int32_t) * (size_t)n, kStageIn }, { order, sizeof(uint32_t) * (size_t)n, kStageIn },
+                                { fill ? items_out : nullptr, sizeof(int32_t) * (size_t)capacity, kStageOut, sizeof(int32_t) },
+                                { fill ? gap_out : nullptr, esz * (size_t)capacity, kStageOut, esz },
+                                { offsets_out, sizeof(uint64_t) * ((size_t)n + 1), kStageOut } };
+    HostStaging hs(rows);
+    if (rt_status pst = hs.plan(what, total_out); pst != RT_OK) return pst;
     if (!(f32 ? overlap_queries_valid(static_cast<const float *>(queries), n, what) : overlap_queries_valid(static_cast<const double *>(queries), n, what)))
         return RT_ERR_INVALID_ARGUMENT;
     if (order && !order_is_permutation(order, n, what)) return RT_ERR_INVALID_ARGUMENT;
-    // pinned buffers are read and written by the kernels in place, pageable ones go through the call's workspace (as rt_near_spheres)
-    const bool fill = capacity != 0u && items_out;
-    const size_t esz = f32 ? sizeof(float) : sizeof(double);
-    struct Buf { void *host; size_t bytes, unit; bool out; uint8_t *dev; size_t off; bool staged; };
-    Buf b[6] = { { const_cast<void *>(queries), 4 * esz * (size_t)n, 0, false, nullptr, 0, false },
-                 { const_cast<int32_t *>(exclude), sizeof(int32_t) * (size_t)n, 0, false, nullptr, 0, false },
-                 { const_cast<uint32_t *>(order), sizeof(uint32_t) * (size_t)n, 0, false, nullptr, 0, false },
-                 { fill ? items_out : nullptr, sizeof(int32_t) * (size_t)capacity, sizeof(int32_t), true, nullptr, 0, false },
-                 { fill ? gap_out : nullptr, esz * (size_t)capacity, esz, true, nullptr, 0, false },
-                 { offsets_out, sizeof(uint64_t) * ((size_t)n + 1), 0, true, nullptr, 0, false } };
-    size_t need = 0;
-    for (Buf &x : b) {
-        if (!x.host) continue;
-        const HostDest d = classify_host_pointer(x.host);
-        if (d.bad) {
-            snprintf(g_err, sizeof g_err, "%s: a buffer is device memory; use %s_device", what, what);
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-        if (d.pinned && d.dev_alias && d.room >= x.bytes) { x.dev = d.dev_alias; continue; }
-        x.staged = true;
-        x.off = need;
-        need += (x.bytes + 255) & ~(size_t)255;
-    }
-    if (classify_host_pointer(total_out).bad) {
-        snprintf(g_err, sizeof g_err, "%s: a buffer is device memory; use %s_device", what, what);
-        return RT_ERR_INVALID_ARGUMENT;
-    }
-    const ReadLock rl(s);
-    HIP_TRY(hipSetDevice(s->device));
-    rt_status st = RT_OK;
-    Context *c = nullptr;
-    if ((st = acquire(s, &c)) != RT_OK) return st;
-    Lease lease{ s, c };
-    const void *nodes = nullptr;
-    uint32_t n_nodes = 0;
-    if ((st = query_stream(s, c->stream, &nodes, &n_nodes)) != RT_OK) return st;
-    if (need > c->query_cap) {
-        if (c->d_query) HIP_TRY(hipFree(c->d_query));
-        c->d_query = nullptr; c->query_cap = 0;
-        HIP_TRY(hipMalloc(&c->d_query, need));
-        c->query_cap = need;
-    }
-    for (Buf &x : b)
-        if (x.staged) x.dev = static_cast<uint8_t *>(c->d_query) + x.off;
-    // the two passes share the scene's workspace and this call reads the total between them: host calls on one scene take turns
-    std::lock_guard<std::mutex> lk(s->overlap_mu);
-    if ((st = overlap_begin(s, n, c->stream)) != RT_OK) return st;
-    // from here on work of this call may be queued: an error return first waits for it
-#define HIP_DRAIN(expr)                                                                                                   \
-    do {                                                                                                                  \
-        hipError_t e__ = (expr);                                                                                          \
-        if (e__ != hipSuccess) { (void)hipStreamSynchronize(c->stream); return hip_fail(e__, #expr, __LINE__); }          \
-    } while (0)
-    for (const Buf &x : b)
-        if (x.staged && !x.out)
-            HIP_DRAIN(hipMemcpyAsync(x.dev, x.host, x.bytes, hipMemcpyHostToDevice, c->stream));
-    if (stats) {
-        HIP_DRAIN(hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, c->stream));
-        HIP_DRAIN(hipEventRecord(c->ev0, c->stream));
-    }
-    const int32_t *const d_exclude = reinterpret_cast<const int32_t *>(b[1].dev);
-    const uint32_t *const d_order = reinterpret_cast<const uint32_t *>(b[2].dev);
-    // the scan writes the total into the scene's pinned word, as rt_scene_contacts has it
-    st = enqueue_overlap_count(s, nodes, n_nodes, b[0].dev, n, margin, d_exclude, d_order, reinterpret_cast<uint64_t *>(b[5].dev), s->d_overlap_total,
-                               stats ? c->d_counters : nullptr, c->stream);
-    if (st != RT_OK) { (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return st; }
-    if (b[5].staged) HIP_DRAIN(hipMemcpyAsync(b[5].host, b[5].dev, b[5].bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_DRAIN(hipStreamSynchronize(c->stream));
-    const uint64_t total = *static_cast<volatile uint64_t *>(s->h_overlap_total);
-    *total_out = total;
-    const size_t written = (size_t)std::min<uint64_t>(total, capacity);
-    if (fill && written) {
-        st = enqueue_overlap_fill(s, nodes, n_nodes, b[0].dev, n, margin, d_exclude, d_order, capacity, reinterpret_cast<int32_t *>(b[3].dev), b[4].dev, c->stream);
-        if (st != RT_OK) { (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return st; }
-        for (int k = 3; k < 5; ++k)                                  // (only what was written: the caller's bytes behind it stay)
-            if (b[k].staged && b[k].host) HIP_DRAIN(hipMemcpyAsync(b[k].host, b[k].dev, b[k].unit * written, hipMemcpyDeviceToHost, c->stream));
-    }
-    if (stats) {
-        HIP_DRAIN(hipEventRecord(c->ev1, c->stream));
-        return read_query_stats(c, c->stream, stats);                // synchronises the stream
-    }
-    HIP_DRAIN(hipStreamSynchronize(c->stream));
-#undef HIP_DRAIN
-    return RT_OK;
+    return host_list_query(
+        s, s->overlap, hs, capacity, fill, total_out, stats,
+        [&](const void *, uint32_t, hipStream_t stream) { return overlap_begin(s, n, stream); },
+        [&](const void *nodes, uint32_t n_nodes, rt::Counters *counters, hipStream_t stream) {
+            return enqueue_overlap_count(s, nodes, n_nodes, hs.dev(0), n, margin, hs.dev<const int32_t>(1), hs.dev<const uint32_t>(2), hs.dev<uint64_t>(5), s->overlap.d_total,
+                                         counters, stream);
+        },
+        [&](const void *nodes, uint32_t n_nodes, hipStream_t stream) {
+            return enqueue_overlap_fill(s, nodes, n_nodes, hs.dev(0), n, margin, hs.dev<const int32_t>(1), hs.dev<const uint32_t>(2), capacity, hs.dev<int32_t>(3), hs.dev(4), stream);
+        });
 }
 
 // ---- swept overlap lists: every sphere of the scene a moving outside sphere comes into contact with during one step (rt_swept.hpp) ----
@@ -1834,38 +1301,16 @@ rt_status rt_swept_overlaps_device(rt_scene *s, const void *queries, const void 
 {
     const char *const what = "rt_swept_overlaps_device";
     if (!swept_args_ok(s, queries, qdisp, n, disp, exclude, order, capacity, items_out, time_out, normal_out, offsets_out, total_out, what)) return RT_ERR_INVALID_ARGUMENT;
-    const ReadLock rl(s);
-    HIP_TRY(hipSetDevice(s->device));
-    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-    const void *nodes = nullptr;
-    uint32_t n_nodes = 0;
-    rt_status st = query_stream(s, stream, &nodes, &n_nodes);
-    if (st != RT_OK) return st;
-    Context *c = nullptr;
-    Lease lease{ s, nullptr };
-    if (stats) {
-        if ((st = acquire(s, &c)) != RT_OK) return st;
-        lease.c = c;
-    }
-    {
-        // swept calls take their turn with overlap calls: they share the counts and the offsets
-        std::lock_guard<std::mutex> lk(s->overlap_mu);
-        if ((st = swept_begin(s, n, n_nodes, stream)) != RT_OK) return st;
-        if (stats) {
-            HIP_TRY(hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, stream));
-            HIP_TRY(hipEventRecord(c->ev0, stream));
-        }
-        st = enqueue_swept_count(s, nodes, n_nodes, queries, qdisp, n, disp, exclude, order, offsets_out, total_out, stats ? c->d_counters : nullptr, stream);
-        if (st == RT_OK && capacity != 0u && items_out)
-            st = enqueue_swept_fill(s, nodes, n_nodes, queries, qdisp, n, exclude, order, capacity, items_out, time_out, normal_out, stream);
-        // whatever was enqueued uses the workspace: the next call goes behind it
-        if (hipEventRecord(s->overlap_ev, stream) == hipSuccess) s->overlap_recorded = true;
-        else { (void)hipGetLastError(); (void)hipStreamSynchronize(stream); }
-    }
-    if (!stats) return st;
-    (void)hipEventRecord(c->ev1, stream);
-    if (st != RT_OK) { (void)hipGetLastError(); lease.inflight = true; return st; }      // (the context goes back behind what is enqueued)
-    return read_query_stats(c, stream, stats);
+    // swept calls take their turn with overlap calls: they share the counts and the offsets
+    return device_list_query(
+        s, s->overlap, capacity != 0u && items_out, stats, static_cast<hipStream_t>(hip_stream),
+        [&](const void *, uint32_t n_nodes, hipStream_t stream) { return swept_begin(s, n, n_nodes, stream); },
+        [&](const void *nodes, uint32_t n_nodes, rt::Counters *counters, hipStream_t stream) {
+            return enqueue_swept_count(s, nodes, n_nodes, queries, qdisp, n, disp, exclude, order, offsets_out, total_out, counters, stream);
+        },
+        [&](const void *nodes, uint32_t n_nodes, hipStream_t stream) {
+            return enqueue_swept_fill(s, nodes, n_nodes, queries, qdisp, n, exclude, order, capacity, items_out, time_out, normal_out, stream);
+        });
 }
 
 rt_status rt_swept_overlaps(rt_scene *s, const void *queries, const void *qdisp, uint32_t n, const void *disp, const int32_t *exclude, const uint32_t *order,
@@ -1874,101 +1319,35 @@ rt_status rt_swept_overlaps(rt_scene *s, const void *queries, const void *qdisp,
     const char *const what = "rt_swept_overlaps";
     if (!swept_args_ok(s, queries, qdisp, n, disp, exclude, order, capacity, items_out, time_out, normal_out, offsets_out, total_out, what)) return RT_ERR_INVALID_ARGUMENT;
     const bool f32 = s->precision == RT_F32;
+    const bool fill = capacity != 0u && items_out;
+    const size_t esz = f32 ? sizeof(float) : sizeof(double);
+    HostStaging::Row rows[] = { { queries, 4 * esz * (size_t)n, kStageIn }, { qdisp, 3 * esz * (size_t)n, kStageIn }, { disp, 3 * esz * (size_t)s->n_items, kStageIn },
+                                { exclude, sizeof(int32_t) * (size_t)n, kStageIn }, { order, sizeof(uint32_t) * (size_t)n, kStageIn },
+                                { fill ? items_out : nullptr, sizeof(int32_t) * (size_t)capacity, kStageOut, sizeof(int32_t) },
+                                { fill ? time_out : nullptr, esz * (size_t)capacity, kStageOut, esz },
+                                { fill ? normal_out : nullptr, 3 * esz * (size_t)capacity, kStageOut, 3 * esz },
+                                { offsets_out, sizeof(uint64_t) * ((size_t)n + 1), kStageOut } };
+    HostStaging hs(rows);
+    if (rt_status pst = hs.plan(what, total_out); pst != RT_OK) return pst;
     if (!(f32 ? overlap_queries_valid(static_cast<const float *>(queries), n, what) : overlap_queries_valid(static_cast<const double *>(queries), n, what)))
         return RT_ERR_INVALID_ARGUMENT;
     if (!(f32 ? swept_qdisp_valid(static_cast<const float *>(qdisp), n, what) : swept_qdisp_valid(static_cast<const double *>(qdisp), n, what)))
         return RT_ERR_INVALID_ARGUMENT;
     if (order && !order_is_permutation(order, n, what)) return RT_ERR_INVALID_ARGUMENT;
-    // pinned buffers are read and written by the kernels in place, pageable ones go through the call's workspace (as rt_overlap_spheres)
-    const bool fill = capacity != 0u && items_out;
-    const size_t esz = f32 ? sizeof(float) : sizeof(double);
-    struct Buf { void *host; size_t bytes, unit; bool out; uint8_t *dev; size_t off; bool staged; };
-    Buf b[9] = { { const_cast<void *>(queries), 4 * esz * (size_t)n, 0, false, nullptr, 0, false },
-                 { const_cast<void *>(qdisp), 3 * esz * (size_t)n, 0, false, nullptr, 0, false },
-                 { const_cast<void *>(disp), 3 * esz * (size_t)s->n_items, 0, false, nullptr, 0, false },
-                 { const_cast<int32_t *>(exclude), sizeof(int32_t) * (size_t)n, 0, false, nullptr, 0, false },
-                 { const_cast<uint32_t *>(order), sizeof(uint32_t) * (size_t)n, 0, false, nullptr, 0, false },
-                 { fill ? items_out : nullptr, sizeof(int32_t) * (size_t)capacity, sizeof(int32_t), true, nullptr, 0, false },
-                 { fill ? time_out : nullptr, esz * (size_t)capacity, esz, true, nullptr, 0, false },
-                 { fill ? normal_out : nullptr, 3 * esz * (size_t)capacity, 3 * esz, true, nullptr, 0, false },
-                 { offsets_out, sizeof(uint64_t) * ((size_t)n + 1), 0, true, nullptr, 0, false } };
-    size_t need = 0;
-    for (Buf &x : b) {
-        if (!x.host) continue;
-        const HostDest d = classify_host_pointer(x.host);
-        if (d.bad) {
-            snprintf(g_err, sizeof g_err, "%s: a buffer is device memory; use %s_device", what, what);
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-        if (d.pinned && d.dev_alias && d.room >= x.bytes) { x.dev = d.dev_alias; continue; }
-        x.staged = true;
-        x.off = need;
-        need += (x.bytes + 255) & ~(size_t)255;
-    }
-    if (classify_host_pointer(total_out).bad) {
-        snprintf(g_err, sizeof g_err, "%s: a buffer is device memory; use %s_device", what, what);
-        return RT_ERR_INVALID_ARGUMENT;
-    }
     if (disp && !(f32 ? impacts_disp_valid(static_cast<const float *>(disp), s->n_items, what) : impacts_disp_valid(static_cast<const double *>(disp), s->n_items, what)))
         return RT_ERR_INVALID_ARGUMENT;
-    const ReadLock rl(s);
-    HIP_TRY(hipSetDevice(s->device));
-    rt_status st = RT_OK;
-    Context *c = nullptr;
-    if ((st = acquire(s, &c)) != RT_OK) return st;
-    Lease lease{ s, c };
-    const void *nodes = nullptr;
-    uint32_t n_nodes = 0;
-    if ((st = query_stream(s, c->stream, &nodes, &n_nodes)) != RT_OK) return st;
-    if (need > c->query_cap) {
-        if (c->d_query) HIP_TRY(hipFree(c->d_query));
-        c->d_query = nullptr; c->query_cap = 0;
-        HIP_TRY(hipMalloc(&c->d_query, need));
-        c->query_cap = need;
-    }
-    for (Buf &x : b)
-        if (x.staged) x.dev = static_cast<uint8_t *>(c->d_query) + x.off;
-    // the two passes share the scene's overlap workspace and this call reads the total between them: host calls on one scene take turns,
-    // overlap and swept alike
-    std::lock_guard<std::mutex> lk(s->overlap_mu);
-    if ((st = swept_begin(s, n, n_nodes, c->stream)) != RT_OK) return st;
-    // from here on work of this call may be queued: an error return first waits for it
-#define HIP_DRAIN(expr)                                                                                                   \
-    do {                                                                                                                  \
-        hipError_t e__ = (expr);                                                                                          \
-        if (e__ != hipSuccess) { (void)hipStreamSynchronize(c->stream); return hip_fail(e__, #expr, __LINE__); }          \
-    } while (0)
-    for (const Buf &x : b)
-        if (x.staged && !x.out)
-            HIP_DRAIN(hipMemcpyAsync(x.dev, x.host, x.bytes, hipMemcpyHostToDevice, c->stream));
-    if (stats) {
-        HIP_DRAIN(hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, c->stream));
-        HIP_DRAIN(hipEventRecord(c->ev0, c->stream));
-    }
-    const int32_t *const d_exclude = reinterpret_cast<const int32_t *>(b[3].dev);
-    const uint32_t *const d_order = reinterpret_cast<const uint32_t *>(b[4].dev);
-    // the scan writes the total into the scene's pinned word, as rt_overlap_spheres has it
-    st = enqueue_swept_count(s, nodes, n_nodes, b[0].dev, b[1].dev, n, b[2].dev, d_exclude, d_order, reinterpret_cast<uint64_t *>(b[8].dev), s->d_overlap_total,
-                             stats ? c->d_counters : nullptr, c->stream);
-    if (st != RT_OK) { (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return st; }
-    if (b[8].staged) HIP_DRAIN(hipMemcpyAsync(b[8].host, b[8].dev, b[8].bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_DRAIN(hipStreamSynchronize(c->stream));
-    const uint64_t total = *static_cast<volatile uint64_t *>(s->h_overlap_total);
-    *total_out = total;
-    const size_t written = (size_t)std::min<uint64_t>(total, capacity);
-    if (fill && written) {
-        st = enqueue_swept_fill(s, nodes, n_nodes, b[0].dev, b[1].dev, n, d_exclude, d_order, capacity, reinterpret_cast<int32_t *>(b[5].dev), b[6].dev, b[7].dev, c->stream);
-        if (st != RT_OK) { (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return st; }
-        for (int k = 5; k < 8; ++k)                                  // (only what was written: the caller's bytes behind it stay)
-            if (b[k].staged && b[k].host) HIP_DRAIN(hipMemcpyAsync(b[k].host, b[k].dev, b[k].unit * written, hipMemcpyDeviceToHost, c->stream));
-    }
-    if (stats) {
-        HIP_DRAIN(hipEventRecord(c->ev1, c->stream));
-        return read_query_stats(c, c->stream, stats);                // synchronises the stream
-    }
-    HIP_DRAIN(hipStreamSynchronize(c->stream));
-#undef HIP_DRAIN
-    return RT_OK;
+    // (the overlap workspace: host calls on one scene take turns, overlap and swept alike)
+    return host_list_query(
+        s, s->overlap, hs, capacity, fill, total_out, stats,
+        [&](const void *, uint32_t n_nodes, hipStream_t stream) { return swept_begin(s, n, n_nodes, stream); },
+        [&](const void *nodes, uint32_t n_nodes, rt::Counters *counters, hipStream_t stream) {
+            return enqueue_swept_count(s, nodes, n_nodes, hs.dev(0), hs.dev(1), n, hs.dev(2), hs.dev<const int32_t>(3), hs.dev<const uint32_t>(4), hs.dev<uint64_t>(8),
+                                       s->overlap.d_total, counters, stream);
+        },
+        [&](const void *nodes, uint32_t n_nodes, hipStream_t stream) {
+            return enqueue_swept_fill(s, nodes, n_nodes, hs.dev(0), hs.dev(1), n, hs.dev<const int32_t>(3), hs.dev<const uint32_t>(4), capacity, hs.dev<int32_t>(5), hs.dev(6),
+                                      hs.dev(7), stream);
+        });
 }
 
 // ---- traced rays and camera frames: Renderer::raytrace for any ray, render_region for any pinhole camera (rt_trace.hpp) ----
@@ -2024,73 +1403,20 @@ static rt_status trace_rays_host(rt_scene *s, const void *rays, uint32_t n, void
     if (!trace_args_ok(s, rays, n, color_out, alpha_out, what)) return RT_ERR_INVALID_ARGUMENT;
     if (ordered && !device_order_ok(order, what)) return RT_ERR_INVALID_ARGUMENT;
     const bool f32 = s->precision == RT_F32;
+    const size_t esz = f32 ? sizeof(float) : sizeof(double);
+    HostStaging::Row rows[] = { { rays, 6 * esz * n, kStageIn }, { color_out, 3 * esz * n, kStageOut }, { alpha_out, esz * n, kStageOut }, { order, sizeof(uint32_t) * n, kStageIn } };
+    HostStaging hs(rows);
+    if (rt_status pst = hs.plan(what); pst != RT_OK) return pst;
     if (!(f32 ? query_rays_valid(static_cast<const float *>(rays), static_cast<const float *>(nullptr), n)
               : query_rays_valid(static_cast<const double *>(rays), static_cast<const double *>(nullptr), n)))
         return RT_ERR_INVALID_ARGUMENT;
     if (order && !order_is_permutation(order, n, what)) return RT_ERR_INVALID_ARGUMENT;
-    const ReadLock rl(s);
-    HIP_TRY(hipSetDevice(s->device));
-    rt_status st = RT_OK;
-    // pinned buffers are read and written by the kernel in place, pageable ones go through the call's workspace (as rt_intersect_rays)
-    const size_t esz = f32 ? sizeof(float) : sizeof(double);
-    struct Buf { void *host; size_t bytes; bool out; uint8_t *dev; size_t off; bool staged; };
-    Buf b[4] = { { const_cast<void *>(rays), 6 * esz * n, false, nullptr, 0, false }, { color_out, 3 * esz * n, true, nullptr, 0, false },
-                 { alpha_out, esz * n, true, nullptr, 0, false }, { const_cast<uint32_t *>(order), sizeof(uint32_t) * n, false, nullptr, 0, false } };
-    size_t need = 0;
-    for (Buf &x : b) {
-        if (!x.host) continue;
-        const HostDest d = classify_host_pointer(x.host);
-        if (d.bad) {
-            snprintf(g_err, sizeof g_err, "%s: a buffer is device memory; use %s_device", what, what);
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-        if (d.pinned && d.dev_alias && d.room >= x.bytes) { x.dev = d.dev_alias; continue; }
-        x.staged = true;
-        x.off = need;
-        need += (x.bytes + 255) & ~(size_t)255;
-    }
-    Context *c = nullptr;
-    if ((st = acquire(s, &c)) != RT_OK) return st;
-    Lease lease{ s, c };
-    const void *nodes = nullptr;
-    uint32_t n_nodes = 0;
-    if ((st = query_stream(s, c->stream, &nodes, &n_nodes)) != RT_OK) return st;
-    if (need > c->query_cap) {
-        if (c->d_query) HIP_TRY(hipFree(c->d_query));
-        c->d_query = nullptr; c->query_cap = 0;
-        HIP_TRY(hipMalloc(&c->d_query, need));
-        c->query_cap = need;
-    }
-    for (Buf &x : b)
-        if (x.staged) x.dev = static_cast<uint8_t *>(c->d_query) + x.off;
-    // from the first copy on, work of this call may be queued: an error return first waits for it
-#define HIP_DRAIN(expr)                                                                                                   \
-    do {                                                                                                                  \
-        hipError_t e__ = (expr);                                                                                          \
-        if (e__ != hipSuccess) { (void)hipStreamSynchronize(c->stream); return hip_fail(e__, #expr, __LINE__); }          \
-    } while (0)
-    for (const Buf &x : b)
-        if (x.staged && !x.out)
-            HIP_DRAIN(hipMemcpyAsync(x.dev, x.host, x.bytes, hipMemcpyHostToDevice, c->stream));
-    const uint32_t *d_order = reinterpret_cast<const uint32_t *>(b[3].dev);
-    if (ordered && !order && (st = enqueue_ray_order(s, c, b[0].dev, n, nullptr, c->stream, &d_order)) != RT_OK) {
-        (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return st;
-    }
-    if (stats) {
-        HIP_DRAIN(hipMemsetAsync(c->d_counters, 0, sizeof(rt::Counters) * rt::kCounterStripes, c->stream));
-        HIP_DRAIN(hipEventRecord(c->ev0, c->stream));
-    }
-    st = enqueue_trace(s, nodes, n_nodes, b[0].dev, n, b[1].dev, b[2].dev, nullptr, nullptr, nullptr, 0, 0, nullptr, stats ? c->d_counters : nullptr, c->stream,
-                       d_order);
-    if (st != RT_OK) { (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return st; }
-    if (stats) HIP_DRAIN(hipEventRecord(c->ev1, c->stream));
-    for (const Buf &x : b)
-        if (x.staged && x.out)
-            HIP_DRAIN(hipMemcpyAsync(x.host, x.dev, x.bytes, hipMemcpyDeviceToHost, c->stream));
-    if (stats) return read_trace_stats(c, c->stream, stats);          // synchronises the stream
-    HIP_DRAIN(hipStreamSynchronize(c->stream));
-#undef HIP_DRAIN
-    return RT_OK;
+    const uint32_t *d_order = nullptr;
+    return host_query(s, hs, stats, read_trace_stats,
+                      [&](Context *c) { d_order = hs.dev<const uint32_t>(3); return ordered && !order ? enqueue_ray_order(s, c, hs.dev(0), n, nullptr, c->stream, &d_order) : RT_OK; },
+                      [&](const void *nodes, uint32_t n_nodes, rt::Counters *counters, hipStream_t stream) {
+                          return enqueue_trace(s, nodes, n_nodes, hs.dev(0), n, hs.dev(1), hs.dev(2), nullptr, nullptr, nullptr, 0, 0, nullptr, counters, stream, d_order);
+                      });
 }
 
 rt_status rt_trace_rays(rt_scene *s, const void *rays, uint32_t n, void *color_out, void *alpha_out, rt_stats *stats)
@@ -2122,53 +1448,35 @@ rt_status rt_ray_order_device(rt_scene *s, const void *rays, uint32_t n, uint32_
     return st;
 }
 
-rt_status rt_ray_order(rt_scene *s, const void *rays, uint32_t n, uint32_t *order_out)
+// Shared body of rt_ray_order and rt_sphere_order, `hs` planned: row 0 up, the order `enqueue` makes of it into row 1, and that back.
+static rt_status order_host(rt_scene *s, HostStaging &hs, uint32_t n,
+                            rt_status (*enqueue)(const rt_scene *, Context *, const void *, uint32_t, uint32_t *, hipStream_t, const uint32_t **))
 {
-    if (!order_args_ok(s, rays, n, order_out, "rt_ray_order")) return RT_ERR_INVALID_ARGUMENT;
-    const bool f32 = s->precision == RT_F32;
-    if (!(f32 ? query_rays_valid(static_cast<const float *>(rays), static_cast<const float *>(nullptr), n)
-              : query_rays_valid(static_cast<const double *>(rays), static_cast<const double *>(nullptr), n)))
-        return RT_ERR_INVALID_ARGUMENT;
     HIP_TRY(hipSetDevice(s->device));
-    // pinned buffers are read and written by the kernels in place, pageable ones go through the call's workspace (as rt_intersect_rays)
-    const size_t esz = f32 ? sizeof(float) : sizeof(double);
-    struct Buf { void *host; size_t bytes; bool out; uint8_t *dev; size_t off; bool staged; };
-    Buf b[2] = { { const_cast<void *>(rays), 6 * esz * n, false, nullptr, 0, false }, { order_out, sizeof(uint32_t) * n, true, nullptr, 0, false } };
-    size_t need = 0;
-    for (Buf &x : b) {
-        const HostDest d = classify_host_pointer(x.host);
-        if (d.bad) {
-            snprintf(g_err, sizeof g_err, "rt_ray_order: a buffer is device memory; use rt_ray_order_device");
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-        if (d.pinned && d.dev_alias && d.room >= x.bytes) { x.dev = d.dev_alias; continue; }
-        x.staged = true;
-        x.off = need;
-        need += (x.bytes + 255) & ~(size_t)255;
-    }
     Context *c = nullptr;
     rt_status st = acquire(s, &c);
     if (st != RT_OK) return st;
     Lease lease{ s, c };
-    if (need > c->query_cap) {
-        if (c->d_query) HIP_TRY(hipFree(c->d_query));
-        c->d_query = nullptr; c->query_cap = 0;
-        HIP_TRY(hipMalloc(&c->d_query, need));
-        c->query_cap = need;
-    }
-    for (Buf &x : b)
-        if (x.staged) x.dev = static_cast<uint8_t *>(c->d_query) + x.off;
-    // from the first copy on, work of this call may be queued: an error return first waits for it
-    auto drain = [&](rt_status code) { (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return code; };
-    hipError_t e = hipSuccess;
-    if (b[0].staged && (e = hipMemcpyAsync(b[0].dev, b[0].host, b[0].bytes, hipMemcpyHostToDevice, c->stream)) != hipSuccess)
-        return drain(hip_fail(e, "hipMemcpyAsync", __LINE__));
+    if ((st = hs.bind(c)) != RT_OK) return st;
+    if ((st = hs.upload(c)) != RT_OK) return st;
     const uint32_t *used = nullptr;
-    if ((st = enqueue_ray_order(s, c, b[0].dev, n, reinterpret_cast<uint32_t *>(b[1].dev), c->stream, &used)) != RT_OK) return drain(st);
-    if (b[1].staged && (e = hipMemcpyAsync(b[1].host, b[1].dev, b[1].bytes, hipMemcpyDeviceToHost, c->stream)) != hipSuccess)
-        return drain(hip_fail(e, "hipMemcpyAsync", __LINE__));
-    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize", __LINE__);
+    if ((st = enqueue(s, c, hs.dev(0), n, hs.dev<uint32_t>(1), c->stream, &used)) != RT_OK) return drain(c, st);
+    if ((st = hs.download(c)) != RT_OK) return st;
+    HIP_TRY_DRAIN(c, hipStreamSynchronize(c->stream));
     return RT_OK;
+}
+
+rt_status rt_ray_order(rt_scene *s, const void *rays, uint32_t n, uint32_t *order_out)
+{
+    if (!order_args_ok(s, rays, n, order_out, "rt_ray_order")) return RT_ERR_INVALID_ARGUMENT;
+    const bool f32 = s->precision == RT_F32;
+    HostStaging::Row rows[] = { { rays, 6 * (f32 ? sizeof(float) : sizeof(double)) * n, kStageIn }, { order_out, sizeof(uint32_t) * n, kStageOut } };
+    HostStaging hs(rows);
+    if (rt_status pst = hs.plan("rt_ray_order"); pst != RT_OK) return pst;
+    if (!(f32 ? query_rays_valid(static_cast<const float *>(rays), static_cast<const float *>(nullptr), n)
+              : query_rays_valid(static_cast<const double *>(rays), static_cast<const double *>(nullptr), n)))
+        return RT_ERR_INVALID_ARGUMENT;
+    return order_host(s, hs, n, enqueue_ray_order);
 }
 
 // ---- sphere orders, balanced ranges and rebuilds: a dynamic scene's hierarchy rebuilt on the device (rt_rebuild.hpp) ----
@@ -2228,37 +1536,16 @@ rt_status rt_sphere_order(rt_scene *s, const void *spheres, uint32_t n, uint32_t
 {
     const uintptr_t esz = s && s->precision == RT_F64 ? sizeof(double) : sizeof(float);
     if (!sphere_order_args_ok(s, spheres, n, order_out, esz, "rt_sphere_order")) return RT_ERR_INVALID_ARGUMENT;
+    // both buffers go through the call's workspace, whatever memory they are: the kernels load a sphere whole, and a host pointer need
+    // only be aligned to one of its elements
+    HostStaging::Row rows[] = { { spheres, 4 * esz * n, kStageIn }, { order_out, sizeof(uint32_t) * n, kStageOut } };
+    HostStaging hs(rows);
+    if (rt_status pst = hs.plan("rt_sphere_order", nullptr, false); pst != RT_OK) return pst;
     if (!(s->precision == RT_F32 ? items_valid<float>(spheres, n, true) : items_valid<double>(spheres, n, true))) {
         snprintf(g_err, sizeof g_err, "rt_sphere_order: spheres must be finite, |v| <= 1e15, radius > 0");
         return RT_ERR_INVALID_ARGUMENT;
     }
-    HIP_TRY(hipSetDevice(s->device));
-    if (classify_host_pointer(spheres).bad || classify_host_pointer(order_out).bad) {
-        snprintf(g_err, sizeof g_err, "rt_sphere_order: a buffer is device memory; use rt_sphere_order_device");
-        return RT_ERR_INVALID_ARGUMENT;
-    }
-    // both buffers go through the call's workspace: the spheres up, the order back
-    const size_t in_bytes = 4 * esz * n, out_off = (in_bytes + 255) & ~(size_t)255, need = out_off + ((sizeof(uint32_t) * n + 255) & ~(size_t)255);
-    Context *c = nullptr;
-    rt_status st = acquire(s, &c);
-    if (st != RT_OK) return st;
-    Lease lease{ s, c };
-    if (need > c->query_cap) {
-        if (c->d_query) HIP_TRY(hipFree(c->d_query));
-        c->d_query = nullptr; c->query_cap = 0;
-        HIP_TRY(hipMalloc(&c->d_query, need));
-        c->query_cap = need;
-    }
-    uint8_t *const d_in = static_cast<uint8_t *>(c->d_query), *const d_out = d_in + out_off;
-    // from the first copy on, work of this call may be queued: an error return first waits for it
-    auto drain = [&](rt_status code) { (void)hipStreamSynchronize(c->stream); (void)hipGetLastError(); return code; };
-    hipError_t e = hipSuccess;
-    if ((e = hipMemcpyAsync(d_in, spheres, in_bytes, hipMemcpyHostToDevice, c->stream)) != hipSuccess) return drain(hip_fail(e, "hipMemcpyAsync", __LINE__));
-    const uint32_t *used = nullptr;
-    if ((st = enqueue_sphere_order(s, c, d_in, n, reinterpret_cast<uint32_t *>(d_out), c->stream, &used)) != RT_OK) return drain(st);
-    if ((e = hipMemcpyAsync(order_out, d_out, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, c->stream)) != hipSuccess) return drain(hip_fail(e, "hipMemcpyAsync", __LINE__));
-    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return hip_fail(e, "hipStreamSynchronize", __LINE__);
-    return RT_OK;
+    return order_host(s, hs, n, enqueue_sphere_order);
 }
 
 rt_status rt_scene_rebuild(rt_scene *s, const void *spheres, uint32_t *order_out)

@@ -980,40 +980,42 @@ bool contacts_args_ok(const rt_scene *s, double margin, uint32_t capacity, const
     return true;
 }
 
-// The scene's contacts workspace, made by the first call, and this call's place behind the one before it.  Under s->contacts_mu.  A scene
-// that is not dynamic gets its item-to-node table here, on `stream`: every later call waits for contacts_ev, so for it too.
+// The three launches of the scan on `stream`: the counts of `n` lists into offsets[n + 1] in the workspace and, where given, in the caller's
+// device memory; the total also into *total_out.
+rt_status enqueue_list_scan(const ListSpace &w, uint32_t n, uint64_t *offsets_out, uint64_t *total_out, hipStream_t stream)
+{
+    const unsigned n_sums = (unsigned)(((uint64_t)n + rt::kScanBlock - 1) / rt::kScanBlock);
+    const dim3 sgrid(n_sums), sblock(rt::kScanBlock);
+    hipLaunchKernelGGL(rt::k_contact_scan_sums, sgrid, sblock, 0, stream, w.counts, n, w.sums);
+    hipLaunchKernelGGL(rt::k_contact_scan_spine, dim3(1), sblock, 0, stream, w.sums, n_sums, w.offsets + n, offsets_out ? offsets_out + n : nullptr, total_out);
+    hipLaunchKernelGGL(rt::k_contact_scan_offsets, sgrid, sblock, 0, stream, w.counts, n, w.sums, w.offsets, offsets_out);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+// The scene's contacts workspace, made by the first call, and this call's place behind the one before it.  Under s->contacts.mu.  A scene
+// that is not dynamic gets its item-to-node table here, on `stream`: every later call waits for contacts.ev, so for it too.
 rt_status contacts_begin(rt_scene *s, const void *nodes, uint32_t n_nodes, hipStream_t stream)
 {
-    if (!s->contacts_ev) HIP_TRY(hipEventCreateWithFlags(&s->contacts_ev, hipEventDisableTiming));
-    if (s->contacts_recorded) HIP_TRY(hipStreamWaitEvent(stream, s->contacts_ev, 0));
-    if (s->d_contacts) return RT_OK;
-    const size_t n = s->n_items, n_sums = (n + rt::kScanBlock - 1) / rt::kScanBlock;
+    ListSpace &w = s->contacts;
+    if (!w.ev) HIP_TRY(hipEventCreateWithFlags(&w.ev, hipEventDisableTiming));
+    if (w.recorded) HIP_TRY(hipStreamWaitEvent(stream, w.ev, 0));
+    if (w.d) return RT_OK;
+    const size_t n = s->n_items;
     const bool table = s->n_nodes != 0 && !s->d_item_node;
-    const size_t o_offsets = (sizeof(uint32_t) * n + 255) & ~(size_t)255, o_sums = o_offsets + ((sizeof(uint64_t) * (n + 1) + 255) & ~(size_t)255);
-    const size_t o_table = o_sums + ((sizeof(uint64_t) * (n_sums + 1) + 255) & ~(size_t)255);
-    if (!s->h_contacts_total) {
-        void *h = nullptr, *alias = nullptr;
-        HIP_TRY(hipHostMalloc(&h, 64, hipHostMallocDefault));
-        if (const hipError_t e = hipHostGetDevicePointer(&alias, h, 0); e != hipSuccess) { (void)hipHostFree(h); return hip_fail(e, "hipHostGetDevicePointer(total)", __LINE__); }
-        s->h_contacts_total = static_cast<uint64_t *>(h);
-        s->d_contacts_total = static_cast<uint64_t *>(alias);
-    }
-    void *p = nullptr;
-    HIP_TRY(hipMalloc(&p, o_table + (table ? sizeof(uint32_t) * n : 0) + 256));
-    uint8_t *const d = static_cast<uint8_t *>(p);
+    if (const rt_status st = w.make_total(); st != RT_OK) return st;
+    uint8_t *behind = nullptr;
+    if (const rt_status st = w.make_room(n, (table ? sizeof(uint32_t) * n : 0) + 256, &behind); st != RT_OK) return st;
     if (table) {
-        uint32_t *const item_node = reinterpret_cast<uint32_t *>(d + o_table);
+        uint32_t *const item_node = reinterpret_cast<uint32_t *>(behind);
         const dim3 grid((n_nodes + 255) / 256), block(256);
-        if (const hipError_t e = hipMemsetAsync(item_node, 0xFF, sizeof(uint32_t) * n, stream); e != hipSuccess) { (void)hipFree(p); return hip_fail(e, "hipMemsetAsync(item_node)", __LINE__); }
+        hipError_t e = hipMemsetAsync(item_node, 0xFF, sizeof(uint32_t) * n, stream);
+        if (e != hipSuccess) { (void)hipFree(w.d); w.d = nullptr; return hip_fail(e, "hipMemsetAsync(item_node)", __LINE__); }
         if (s->precision == RT_F32) hipLaunchKernelGGL(rt::k_contact_item_nodes<float>, grid, block, 0, stream, static_cast<const rt::Node<float> *>(nodes), n_nodes, s->n_items, item_node);
         else hipLaunchKernelGGL(rt::k_contact_item_nodes<double>, grid, block, 0, stream, static_cast<const rt::Node<double> *>(nodes), n_nodes, s->n_items, item_node);
-        if (const hipError_t e = hipGetLastError(); e != hipSuccess) { (void)hipFree(p); return hip_fail(e, "k_contact_item_nodes", __LINE__); }
+        if ((e = hipGetLastError()) != hipSuccess) { (void)hipFree(w.d); w.d = nullptr; return hip_fail(e, "k_contact_item_nodes", __LINE__); }
         s->d_contacts_item_node = item_node;
     }
-    s->d_contacts = p;
-    s->d_contacts_counts = reinterpret_cast<uint32_t *>(d);
-    s->d_contacts_offsets = reinterpret_cast<uint64_t *>(d + o_offsets);
-    s->d_contacts_sums = reinterpret_cast<uint64_t *>(d + o_sums);
     return RT_OK;
 }
 
@@ -1025,18 +1027,12 @@ rt_status enqueue_contacts_count(const rt_scene *s, const void *nodes, uint32_t 
 {
     const uint32_t n = s->n_items;
     const uint32_t *const item_node = s->n_nodes ? (s->d_item_node ? s->d_item_node : s->d_contacts_item_node) : nullptr;
-    const rt::ContactArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), item_node, s->d_contacts_counts, nullptr, nullptr, nullptr, counters, (T)margin, n_nodes, n, 0u };
+    const rt::ContactArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), item_node, s->contacts.counts, nullptr, nullptr, nullptr, counters, (T)margin, n_nodes, n, 0u };
     const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
     if (counters) hipLaunchKernelGGL((rt::k_contact_pairs<T, true, false>), grid, block, 0, stream, a);
     else hipLaunchKernelGGL((rt::k_contact_pairs<T, false, false>), grid, block, 0, stream, a);
     HIP_TRY(hipGetLastError());
-    const unsigned n_sums = (n + rt::kScanBlock - 1) / rt::kScanBlock;
-    const dim3 sgrid(n_sums), sblock(rt::kScanBlock);
-    hipLaunchKernelGGL(rt::k_contact_scan_sums, sgrid, sblock, 0, stream, s->d_contacts_counts, n, s->d_contacts_sums);
-    hipLaunchKernelGGL(rt::k_contact_scan_spine, dim3(1), sblock, 0, stream, s->d_contacts_sums, n_sums, s->d_contacts_offsets + n, offsets_out ? offsets_out + n : nullptr, total_out);
-    hipLaunchKernelGGL(rt::k_contact_scan_offsets, sgrid, sblock, 0, stream, s->d_contacts_counts, n, s->d_contacts_sums, s->d_contacts_offsets, offsets_out);
-    HIP_TRY(hipGetLastError());
-    return RT_OK;
+    return enqueue_list_scan(s->contacts, n, offsets_out, total_out, stream);
 }
 
 rt_status enqueue_contacts_count(const rt_scene *s, const void *nodes, uint32_t n_nodes, double margin, uint64_t *offsets_out, uint64_t *total_out,
@@ -1052,7 +1048,7 @@ rt_status enqueue_contacts_fill(const rt_scene *s, const void *nodes, uint32_t n
 {
     const uint32_t n = s->n_items;
     const uint32_t *const item_node = s->n_nodes ? (s->d_item_node ? s->d_item_node : s->d_contacts_item_node) : nullptr;
-    const rt::ContactArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), item_node, nullptr, s->d_contacts_offsets, pairs, static_cast<T *>(gap), nullptr, (T)margin, n_nodes, n, capacity };
+    const rt::ContactArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), item_node, nullptr, s->contacts.offsets, pairs, static_cast<T *>(gap), nullptr, (T)margin, n_nodes, n, capacity };
     const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
     hipLaunchKernelGGL((rt::k_contact_pairs<T, false, true>), grid, block, 0, stream, a);
     HIP_TRY(hipGetLastError());
@@ -1098,12 +1094,12 @@ bool impacts_disp_valid(const T *disp, uint32_t n_items, const char *what)
 }
 
 // Room for a motion table of `n_nodes` nodes in *table (its nodes' lengths, their chunk maxima, the call's magnitude and the bound nodes'
-// radii behind it).  `ev` / `recorded`: the event behind which the calls that use this table run -- a table that has to grow waits for it.
-rt_status motion_table_begin(rt_scene *s, void **table, uint32_t *cap, uint32_t n_nodes, hipEvent_t ev, bool recorded, const char *what)
+// radii behind it).  `w`: the workspace behind whose event the calls that use this table run -- a table that has to grow waits for it.
+rt_status motion_table_begin(rt_scene *s, const ListSpace &w, void **table, uint32_t *cap, uint32_t n_nodes, const char *what)
 {
     if (n_nodes <= *cap && *table) return RT_OK;
     if (*table) {
-        if (recorded) HIP_TRY(hipEventSynchronize(ev));
+        if (w.recorded) HIP_TRY(hipEventSynchronize(w.ev));
         HIP_TRY(hipFree(*table));
         *table = nullptr; *cap = 0;
     }
@@ -1124,12 +1120,12 @@ rt_status motion_table_begin(rt_scene *s, void **table, uint32_t *cap, uint32_t 
     return RT_OK;
 }
 
-// contacts_begin, and room for the motion table of `n_nodes` nodes.  Under s->contacts_mu.
+// contacts_begin, and room for the motion table of `n_nodes` nodes.  Under s->contacts.mu.
 rt_status impacts_begin(rt_scene *s, const void *nodes, uint32_t n_nodes, hipStream_t stream)
 {
     const rt_status st = contacts_begin(s, nodes, n_nodes, stream);
     if (st != RT_OK) return st;
-    return motion_table_begin(s, &s->d_impacts, &s->impacts_cap, n_nodes, s->contacts_ev, s->contacts_recorded, "rt_scene_impacts");
+    return motion_table_begin(s, s->contacts, &s->d_impacts, &s->impacts_cap, n_nodes, "rt_scene_impacts");
 }
 
 template <typename T> struct ImpactsSpace { rt::Motion<T> *motion; T *length, *chunk, *magnitude, *radius; };
@@ -1175,18 +1171,12 @@ rt_status enqueue_impacts_count(const rt_scene *s, const void *nodes, uint32_t n
     HIP_TRY(hipMemsetAsync(w.magnitude, 0, sizeof(T), stream));
     if (const rt_status mt = enqueue_motion_table<T>(s, st, n_nodes, static_cast<const T *>(disp), w, stream); mt != RT_OK) return mt;
     const uint32_t *const item_node = s->n_nodes ? (s->d_item_node ? s->d_item_node : s->d_contacts_item_node) : nullptr;
-    const rt::ImpactArgs<T> a{ st, w.motion, w.magnitude, item_node, s->d_contacts_counts, nullptr, nullptr, nullptr, counters, n_nodes, n, 0u };
+    const rt::ImpactArgs<T> a{ st, w.motion, w.magnitude, item_node, s->contacts.counts, nullptr, nullptr, nullptr, counters, n_nodes, n, 0u };
     const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
     if (counters) hipLaunchKernelGGL((rt::k_impact_pairs<T, true, false>), grid, block, 0, stream, a);
     else hipLaunchKernelGGL((rt::k_impact_pairs<T, false, false>), grid, block, 0, stream, a);
     HIP_TRY(hipGetLastError());
-    const unsigned n_sums = (n + rt::kScanBlock - 1) / rt::kScanBlock;
-    const dim3 sgrid(n_sums), sblock(rt::kScanBlock);
-    hipLaunchKernelGGL(rt::k_contact_scan_sums, sgrid, sblock, 0, stream, s->d_contacts_counts, n, s->d_contacts_sums);
-    hipLaunchKernelGGL(rt::k_contact_scan_spine, dim3(1), sblock, 0, stream, s->d_contacts_sums, n_sums, s->d_contacts_offsets + n, offsets_out ? offsets_out + n : nullptr, total_out);
-    hipLaunchKernelGGL(rt::k_contact_scan_offsets, sgrid, sblock, 0, stream, s->d_contacts_counts, n, s->d_contacts_sums, s->d_contacts_offsets, offsets_out);
-    HIP_TRY(hipGetLastError());
-    return RT_OK;
+    return enqueue_list_scan(s->contacts, n, offsets_out, total_out, stream);
 }
 
 rt_status enqueue_impacts_count(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *disp, uint64_t *offsets_out, uint64_t *total_out,
@@ -1203,7 +1193,7 @@ rt_status enqueue_impacts_fill(const rt_scene *s, const void *nodes, uint32_t n_
     const uint32_t n = s->n_items;
     const uint32_t *const item_node = s->n_nodes ? (s->d_item_node ? s->d_item_node : s->d_contacts_item_node) : nullptr;
     const ImpactsSpace<T> w = impacts_space<T>(s);
-    const rt::ImpactArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), w.motion, w.magnitude, item_node, nullptr, s->d_contacts_offsets, pairs, static_cast<T *>(time), nullptr,
+    const rt::ImpactArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), w.motion, w.magnitude, item_node, nullptr, s->contacts.offsets, pairs, static_cast<T *>(time), nullptr,
                                n_nodes, n, capacity };
     const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
     hipLaunchKernelGGL((rt::k_impact_pairs<T, false, true>), grid, block, 0, stream, a);
@@ -1259,35 +1249,18 @@ bool overlap_queries_valid(const T *queries, uint32_t n, const char *what)
     return true;
 }
 
-// The scene's overlap workspace for `n` queries, and this call's place behind the one before it.  Under s->overlap_mu.  The first call
+// The scene's overlap workspace for `n` queries, and this call's place behind the one before it.  Under s->overlap.mu.  The first call
 // makes the workspace; a call with more queries than any before it makes a larger one, once the call before it is through with the old.
 rt_status overlap_begin(rt_scene *s, uint32_t n, hipStream_t stream)
 {
-    if (!s->overlap_ev) HIP_TRY(hipEventCreateWithFlags(&s->overlap_ev, hipEventDisableTiming));
-    if (!s->h_overlap_total) {
-        void *h = nullptr, *alias = nullptr;
-        HIP_TRY(hipHostMalloc(&h, 64, hipHostMallocDefault));
-        if (const hipError_t e = hipHostGetDevicePointer(&alias, h, 0); e != hipSuccess) { (void)hipHostFree(h); return hip_fail(e, "hipHostGetDevicePointer(total)", __LINE__); }
-        s->h_overlap_total = static_cast<uint64_t *>(h);
-        s->d_overlap_total = static_cast<uint64_t *>(alias);
+    ListSpace &w = s->overlap;
+    if (!w.ev) HIP_TRY(hipEventCreateWithFlags(&w.ev, hipEventDisableTiming));
+    if (const rt_status st = w.make_total(); st != RT_OK) return st;
+    if (n > w.cap) {
+        if (w.recorded) HIP_TRY(hipEventSynchronize(w.ev));
+        if (const rt_status st = w.make_room(n, 0, nullptr); st != RT_OK) return st;
     }
-    if (n > s->overlap_cap) {
-        if (s->overlap_recorded) HIP_TRY(hipEventSynchronize(s->overlap_ev));
-        if (s->d_overlap) HIP_TRY(hipFree(s->d_overlap));
-        s->d_overlap = nullptr; s->overlap_cap = 0;
-        const size_t n_sums = ((size_t)n + rt::kScanBlock - 1) / rt::kScanBlock;
-        const size_t o_offsets = (sizeof(uint32_t) * (size_t)n + 255) & ~(size_t)255;
-        const size_t o_sums = o_offsets + ((sizeof(uint64_t) * ((size_t)n + 1) + 255) & ~(size_t)255);
-        void *p = nullptr;
-        HIP_TRY(hipMalloc(&p, o_sums + ((sizeof(uint64_t) * (n_sums + 1) + 255) & ~(size_t)255)));
-        uint8_t *const d = static_cast<uint8_t *>(p);
-        s->d_overlap = p;
-        s->overlap_cap = n;
-        s->d_overlap_counts = reinterpret_cast<uint32_t *>(d);
-        s->d_overlap_offsets = reinterpret_cast<uint64_t *>(d + o_offsets);
-        s->d_overlap_sums = reinterpret_cast<uint64_t *>(d + o_sums);
-    }
-    if (s->overlap_recorded) HIP_TRY(hipStreamWaitEvent(stream, s->overlap_ev, 0));
+    if (w.recorded) HIP_TRY(hipStreamWaitEvent(stream, w.ev, 0));
     return RT_OK;
 }
 
@@ -1297,20 +1270,14 @@ template <typename T>
 rt_status enqueue_overlap_count(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *queries, uint32_t n, double margin, const int32_t *exclude,
                                 const uint32_t *order, uint64_t *offsets_out, uint64_t *total_out, rt::Counters *counters, hipStream_t stream)
 {
-    const rt::OverlapArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), static_cast<const T *>(queries), exclude, order, s->d_overlap_counts, nullptr, nullptr, nullptr,
+    const rt::OverlapArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), static_cast<const T *>(queries), exclude, order, s->overlap.counts, nullptr, nullptr, nullptr,
                                 counters, (T)margin, n_nodes, n, 0u };
-    if (order) HIP_TRY(hipMemsetAsync(s->d_overlap_counts, 0, sizeof(uint32_t) * (size_t)n, stream));
+    if (order) HIP_TRY(hipMemsetAsync(s->overlap.counts, 0, sizeof(uint32_t) * (size_t)n, stream));
     const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
     if (counters) hipLaunchKernelGGL((rt::k_overlap_spheres<T, true, false>), grid, block, 0, stream, a);
     else hipLaunchKernelGGL((rt::k_overlap_spheres<T, false, false>), grid, block, 0, stream, a);
     HIP_TRY(hipGetLastError());
-    const unsigned n_sums = (unsigned)(((uint64_t)n + rt::kScanBlock - 1) / rt::kScanBlock);
-    const dim3 sgrid(n_sums), sblock(rt::kScanBlock);
-    hipLaunchKernelGGL(rt::k_contact_scan_sums, sgrid, sblock, 0, stream, s->d_overlap_counts, n, s->d_overlap_sums);
-    hipLaunchKernelGGL(rt::k_contact_scan_spine, dim3(1), sblock, 0, stream, s->d_overlap_sums, n_sums, s->d_overlap_offsets + n, offsets_out ? offsets_out + n : nullptr, total_out);
-    hipLaunchKernelGGL(rt::k_contact_scan_offsets, sgrid, sblock, 0, stream, s->d_overlap_counts, n, s->d_overlap_sums, s->d_overlap_offsets, offsets_out);
-    HIP_TRY(hipGetLastError());
-    return RT_OK;
+    return enqueue_list_scan(s->overlap, n, offsets_out, total_out, stream);
 }
 
 rt_status enqueue_overlap_count(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *queries, uint32_t n, double margin, const int32_t *exclude,
@@ -1326,7 +1293,7 @@ template <typename T>
 rt_status enqueue_overlap_fill(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *queries, uint32_t n, double margin, const int32_t *exclude,
                                const uint32_t *order, uint32_t capacity, int32_t *items, void *gap, hipStream_t stream)
 {
-    const rt::OverlapArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), static_cast<const T *>(queries), exclude, order, s->d_overlap_counts, s->d_overlap_offsets, items,
+    const rt::OverlapArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), static_cast<const T *>(queries), exclude, order, s->overlap.counts, s->overlap.offsets, items,
                                 static_cast<T *>(gap), nullptr, (T)margin, n_nodes, n, capacity };
     const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
     hipLaunchKernelGGL((rt::k_overlap_spheres<T, false, true>), grid, block, 0, stream, a);
@@ -1380,12 +1347,12 @@ bool swept_qdisp_valid(const T *qdisp, uint32_t n, const char *what)
     return true;
 }
 
-// overlap_begin, and room for this entry's motion table of `n_nodes` nodes.  Under s->overlap_mu.
+// overlap_begin, and room for this entry's motion table of `n_nodes` nodes.  Under s->overlap.mu.
 rt_status swept_begin(rt_scene *s, uint32_t n, uint32_t n_nodes, hipStream_t stream)
 {
     const rt_status st = overlap_begin(s, n, stream);
     if (st != RT_OK) return st;
-    return motion_table_begin(s, &s->d_swept, &s->swept_cap, n_nodes, s->overlap_ev, s->overlap_recorded, "rt_swept_overlaps");
+    return motion_table_begin(s, s->overlap, &s->d_swept, &s->swept_cap, n_nodes, "rt_swept_overlaps");
 }
 
 // The queries' magnitude, the motion table, the first pass and the scan on `stream`.  counters != NULL runs the counting flavour (same
@@ -1401,20 +1368,14 @@ rt_status enqueue_swept_count(const rt_scene *s, const void *nodes, uint32_t n_n
                        static_cast<const T *>(qdisp), n, w.magnitude);
     HIP_TRY(hipGetLastError());
     if (const rt_status mt = enqueue_motion_table<T>(s, st, n_nodes, static_cast<const T *>(disp), w, stream); mt != RT_OK) return mt;
-    const rt::SweptArgs<T> a{ st, w.motion, w.magnitude, static_cast<const T *>(queries), static_cast<const T *>(qdisp), exclude, order, s->d_overlap_counts, nullptr,
+    const rt::SweptArgs<T> a{ st, w.motion, w.magnitude, static_cast<const T *>(queries), static_cast<const T *>(qdisp), exclude, order, s->overlap.counts, nullptr,
                               nullptr, nullptr, nullptr, counters, n_nodes, n, 0u };
-    if (order) HIP_TRY(hipMemsetAsync(s->d_overlap_counts, 0, sizeof(uint32_t) * (size_t)n, stream));
+    if (order) HIP_TRY(hipMemsetAsync(s->overlap.counts, 0, sizeof(uint32_t) * (size_t)n, stream));
     const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
     if (counters) hipLaunchKernelGGL((rt::k_swept_overlaps<T, true, false>), grid, block, 0, stream, a);
     else hipLaunchKernelGGL((rt::k_swept_overlaps<T, false, false>), grid, block, 0, stream, a);
     HIP_TRY(hipGetLastError());
-    const unsigned n_sums = (unsigned)(((uint64_t)n + rt::kScanBlock - 1) / rt::kScanBlock);
-    const dim3 sgrid(n_sums), sblock(rt::kScanBlock);
-    hipLaunchKernelGGL(rt::k_contact_scan_sums, sgrid, sblock, 0, stream, s->d_overlap_counts, n, s->d_overlap_sums);
-    hipLaunchKernelGGL(rt::k_contact_scan_spine, dim3(1), sblock, 0, stream, s->d_overlap_sums, n_sums, s->d_overlap_offsets + n, offsets_out ? offsets_out + n : nullptr, total_out);
-    hipLaunchKernelGGL(rt::k_contact_scan_offsets, sgrid, sblock, 0, stream, s->d_overlap_counts, n, s->d_overlap_sums, s->d_overlap_offsets, offsets_out);
-    HIP_TRY(hipGetLastError());
-    return RT_OK;
+    return enqueue_list_scan(s->overlap, n, offsets_out, total_out, stream);
 }
 
 rt_status enqueue_swept_count(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *queries, const void *qdisp, uint32_t n, const void *disp,
@@ -1432,7 +1393,7 @@ rt_status enqueue_swept_fill(const rt_scene *s, const void *nodes, uint32_t n_no
 {
     const ImpactsSpace<T> w = motion_table_space<T>(s->d_swept, s->swept_cap);
     const rt::SweptArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), w.motion, w.magnitude, static_cast<const T *>(queries), static_cast<const T *>(qdisp), exclude, order,
-                              s->d_overlap_counts, s->d_overlap_offsets, items, static_cast<T *>(time), static_cast<T *>(normal), nullptr, n_nodes, n, capacity };
+                              s->overlap.counts, s->overlap.offsets, items, static_cast<T *>(time), static_cast<T *>(normal), nullptr, n_nodes, n, capacity };
     const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
     hipLaunchKernelGGL((rt::k_swept_overlaps<T, false, true>), grid, block, 0, stream, a);
     HIP_TRY(hipGetLastError());
