@@ -4,6 +4,7 @@ reference (render.rs:138-167, group.rs:27-66), kept as the flat DFS arrays the C
 All scene arithmetic is done in the scene's REAL type with numpy scalars (IEEE, one rounding per operation,
 reference operation order) -- centres accumulate rounding level by level, so the builder replays the
 recursion instead of using a closed form.  Rendering never happens here; see render.py / capi.py."""
+import contextlib
 import ctypes as C
 import sys
 
@@ -16,14 +17,175 @@ def _real(precision):
     return np.float32 if precision == capi.RT_F32 else np.float64
 
 
-def _tmax_array(tmax, R, n):
-    """A query's tmax as a contiguous REAL[n]: one value (a Python float, a 0-d array) is rounded to REAL; an array must already be REAL."""
+def _tmax_array(tmax, R, n, name="tmax"):
+    """A query's tmax (or radius: `name`) as a contiguous REAL[n]: one value (a Python float, a 0-d array) is rounded to REAL; an array
+    must already be REAL."""
     t = np.asarray(tmax)
     if t.ndim == 0 and t.dtype.kind in "fiu":
         t = t.astype(R)
     if t.dtype != R or t.size not in (1, n):
-        raise ValueError("tmax must be one value or an (n,) array of %s" % np.dtype(R).name)
+        raise ValueError("%s must be one value or an (n,) array of %s" % (name, np.dtype(R).name))
     return np.ascontiguousarray(np.broadcast_to(t.reshape(-1), (n,)))
+
+
+def _rows_text(cols, rows, optional):
+    return ("None or " if optional else "") + ("a non-empty (n, %d)" % cols if rows is None else "a (%d, %d)" % (rows, cols))
+
+
+_N, _ITEMS = object(), object()              # _list_query: an input with as many rows as there are queries / as the scene has items
+_NO_STREAM = contextlib.nullcontext(())      # the host side's scope: a host entry takes no stream and returns when it is done
+
+
+class _HostSide:
+    """A call's arguments and results as numpy arrays, for a scene of REAL `R`: what the host entries take.  The checks raise ValueError
+    and hand back what the entry can read: contiguous arrays.  _DeviceSide has the same methods; a dtype is named "R", np.int32,
+    np.uint32 or np.uint64 on both sides."""
+    suffix, trims = "", True
+
+    def __init__(self, R):
+        self.R, self.real = R, np.dtype(R).name
+        self.types = {"R": R, np.int32: np.int32, np.uint32: np.uint32, np.uint64: np.uint64}
+
+    def scope(self, scene, stream, tensors):
+        return _NO_STREAM
+
+    def real_rows(self, x, name, cols, rows=None, optional=False):
+        """x: (n, cols) of REAL -- n > 0, or n = rows; None passes where optional."""
+        if x is None and optional:
+            return None
+        if not isinstance(x, np.ndarray) or x.dtype != self.R or x.ndim != 2 or x.shape[1] != cols or x.shape[0] == 0 or (rows is not None and x.shape[0] != rows):
+            raise ValueError("%s must be %s numpy array of %s (or a torch tensor on the scene's device)" % (name, _rows_text(cols, rows, optional), self.real))
+        return np.ascontiguousarray(x)
+
+    def per_query(self, x, name, n):
+        """x: None, one value (rounded to REAL) or (n,) of REAL -> REAL[n]."""
+        return None if x is None else _tmax_array(x, self.R, n, name)
+
+    def exclude(self, x, n):
+        if x is None:
+            return None
+        ex = np.asarray(x)
+        if ex.dtype != np.int32 or ex.shape != (n,):
+            raise ValueError("exclude must be None or an (n,) int32 array")
+        return np.ascontiguousarray(ex)
+
+    def order(self, x, n):
+        """An index array: contiguous uint32[n] (whether it is a permutation is the library's check)."""
+        o = np.asarray(x)
+        if o.dtype.kind not in "iu" or o.shape != (n,):
+            raise ValueError("order must be None, True or an (n,) integer array")
+        if o.dtype != np.uint32 and n and (int(o.min()) < 0 or int(o.max()) > 0xFFFFFFFF):      # (the cast below would wrap it into range)
+            raise ValueError("order holds an index outside 0 .. 2^32 - 1")
+        return np.ascontiguousarray(o, dtype=np.uint32)
+
+    def empty(self, shape, dt):
+        return np.empty(shape, dtype=self.types[dt])
+
+    def copy(self, x):
+        return x.copy()
+
+    def check_out(self, out, specs):
+        res = tuple(out)
+        if len(res) != len(specs) or any(not isinstance(a, np.ndarray) or a.dtype != self.types[dt] or a.shape != shape or not a.flags.c_contiguous
+                                         for a, (shape, dt) in zip(res, specs)):
+            raise ValueError("out: contiguous arrays of " + ", ".join("%s %s" % (np.dtype(self.types[dt]).name, shape) for shape, dt in specs))
+        return res
+
+    @staticmethod
+    def ptr(x):
+        if x is None:
+            return None
+        try:
+            return C.addressof(C.c_char.from_buffer(x))                          # a third of the time x.ctypes.data takes
+        except (TypeError, ValueError):                                          # (a read-only or an empty array)
+            return x.ctypes.data
+
+    @staticmethod
+    def total_cell():
+        """(where a list entry writes its total, the pointer to it)."""
+        total = C.c_uint64(0)
+        return total, C.byref(total)
+
+    @staticmethod
+    def read_total(total):
+        return int(total.value)
+
+
+class _DeviceSide:
+    """A call's arguments and results as torch tensors on one device, for a scene of REAL `R`: what the _device entries take.  Made once
+    per (precision, device); use it inside its scope, where what it allocates belongs to the call's stream.  Offsets and totals are
+    int64 here: the same bits as the host side's uint64."""
+    suffix, trims = "_device", False
+
+    def __init__(self, torch, R, device):
+        self.torch, self.R, self.dev = torch, R, torch.device("cuda", device)
+        self.real = torch.float32 if R == np.float32 else torch.float64
+        self.types = {"R": self.real, np.int32: torch.int32, np.uint32: torch.uint32, np.uint64: torch.int64}
+
+    def scope(self, scene, stream, tensors):
+        return scene._stream_scope(self.torch, stream, tensors)
+
+    def real_rows(self, x, name, cols, rows=None, optional=False):
+        if x is None and optional:
+            return None
+        if not isinstance(x, self.torch.Tensor) or x.dtype != self.real or x.dim() != 2 or x.shape[1] != cols or x.shape[0] == 0 or x.device != self.dev \
+                or (rows is not None and x.shape[0] != rows):
+            raise ValueError("%s must be %s %s tensor on %s" % (name, _rows_text(cols, rows, optional), self.real, self.dev))
+        return x.contiguous()
+
+    def per_query(self, x, name, n):
+        if x is None:
+            return None
+        if not isinstance(x, self.torch.Tensor):
+            return self.torch.from_numpy(_tmax_array(x, self.R, n, name).copy()).to(self.dev)     # (a broadcast view is read-only)
+        if x.dim() == 0 and x.dtype.is_floating_point:
+            x = x.to(self.real)                                              # one value: rounded to the scene's REAL
+        if x.dtype != self.real or x.numel() not in (1, n):
+            raise ValueError("%s must be a %s value or (n,) tensor" % (name, self.real))
+        return x.to(self.dev).reshape(-1).expand(n).contiguous()
+
+    def exclude(self, x, n):
+        if x is None:
+            return None
+        if not isinstance(x, self.torch.Tensor) or x.dtype != self.torch.int32 or x.shape != (n,) or x.device != self.dev:
+            raise ValueError("exclude must be None or an (n,) int32 tensor on %s" % self.dev)
+        return x.contiguous()
+
+    def order(self, x, n):
+        """An index tensor: contiguous uint32 / int32 [n] on the scene's device."""
+        if not isinstance(x, self.torch.Tensor) or x.dtype not in (self.torch.uint32, self.torch.int32) or x.shape != (n,) or x.device != self.dev:
+            raise ValueError("order must be None, True or an (n,) uint32 / int32 tensor on %s" % self.dev)
+        return x.contiguous()
+
+    def empty(self, shape, dt):
+        return self.torch.empty(shape, dtype=self.types[dt], device=self.dev)
+
+    def copy(self, x):
+        return x.clone()
+
+    def check_out(self, out, specs):
+        res = tuple(out)
+        specs = [(shape, self.types[dt]) for shape, dt in specs]
+        if len(res) != len(specs) or any(not isinstance(a, self.torch.Tensor) or a.dtype != dt or tuple(a.shape) != shape or a.device != self.dev or not a.is_contiguous()
+                                         for a, (shape, dt) in zip(res, specs)):
+            raise ValueError("out: contiguous tensors on %s of %s" % (self.dev, ", ".join("%s %s" % (dt, shape) for shape, dt in specs)))
+        return res
+
+    @staticmethod
+    def ptr(x):
+        return None if x is None else x.data_ptr()
+
+    def total_cell(self):
+        total = self.torch.zeros((), dtype=self.torch.int64, device=self.dev)
+        return total, total.data_ptr()
+
+    @staticmethod
+    def read_total(total):
+        return int(total.item())
+
+
+_HOST_SIDES = {capi.RT_F32: _HostSide(np.float32), capi.RT_F64: _HostSide(np.float64)}
+_DEVICE_SIDES = {}                           # (precision, device) -> _DeviceSide, made on first use
 
 
 def ray_keys(rays):
@@ -732,28 +894,13 @@ class DeviceScene:
                     raise ValueError("%s must be a (%d, 4) %s tensor on %s" % (what, rows, tdt, dev))
             if is_t(live) and (live.dtype not in (torch.uint8, torch.bool) or live.device != dev or live.numel() != n):
                 raise ValueError("live must be a (%d,) uint8 or bool tensor on %s" % (n, dev))
-            cur = torch.cuda.current_stream(dev)
-            if stream is None:
-                qs = cur
-            elif isinstance(stream, torch.cuda.Stream):
-                qs = stream
-            else:
-                hs = int(stream)
-                qs = torch.cuda.default_stream(dev) if hs == 0 else torch.cuda.ExternalStream(hs, device=dev)
-            if qs != cur:
-                qs.wait_stream(cur)
-            with torch.cuda.stream(qs):
-                it = items.contiguous() if is_t(items) else items
-                bd = bounds.contiguous() if is_t(bounds) else bounds
+            with self._stream_scope(torch, stream, (items, bounds, live)) as tail:
+                it, bd, lv = (x.contiguous() if is_t(x) else x for x in (items, bounds, live))
                 ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr() if is_t(x) else x)
-                lv = live.contiguous() if is_t(live) else live
                 if lv is None:
-                    rc = capi.lib.rt_scene_update_device(self._h, ptr(it), ptr(bd), C.c_void_p(qs.cuda_stream))
+                    rc = capi.lib.rt_scene_update_device(self._h, ptr(it), ptr(bd), *tail)
                 else:
-                    rc = capi.lib.rt_scene_update_live_device(self._h, ptr(it), ptr(bd), ptr(lv), C.c_void_p(qs.cuda_stream))
-            for x in (it, bd, lv, items, bounds, live):
-                if is_t(x):
-                    x.record_stream(qs)
+                    rc = capi.lib.rt_scene_update_live_device(self._h, ptr(it), ptr(bd), ptr(lv), *tail)
             capi.check(rc, "rt_scene_update_device" if lv is None else "rt_scene_update_live_device")
             return
         it = np.asarray(items)
@@ -787,53 +934,54 @@ class DeviceScene:
         hs = int(stream)
         return (torch.cuda.default_stream(dev) if hs == 0 else torch.cuda.ExternalStream(hs, device=dev)), cur
 
-    def _spheres_arg(self, spheres, n, what, at_least=None):
-        """`spheres` for a sphere order or a rebuild: (True, contiguous tensor) for a torch tensor on this scene's device, (False, contiguous
-        numpy array) otherwise; n: the number of rows it must have, or None for any; at_least: a rebuild of that many takes its first rows."""
-        if at_least is not None:
-            ok = hasattr(spheres, "shape") and len(spheres.shape) == 2 and at_least <= spheres.shape[0]
-            if not ok:
-                raise ValueError("%s: spheres must have at least n = %d rows" % (what, at_least))
-            if spheres.shape[0] == 0:                                # (n = 0: nothing to read; a tensor still goes through the device entry, on its stream)
-                torch = sys.modules.get("torch")
-                if torch is not None and isinstance(spheres, torch.Tensor):
-                    return True, spheres
-                return False, np.zeros((0, 4), dtype=_real(self.scene.precision))
-            n = None
-        R = _real(self.scene.precision)
+    @contextlib.contextmanager
+    def _stream_scope(self, torch, stream, tensors):
+        """The scope a device entry is called in -> the entry's stream argument, as a 1-tuple.  The call runs on `qs`, the stream `stream`
+        names.  It first waits for what the caller has queued on the current stream (the inputs were made there), and everything
+        allocated inside the scope -- copies of the inputs, the results -- comes from qs's pool, so no allocation of another stream can
+        reuse that memory while the call still uses it.  The caller's own tensors among `tensors`, inputs and outputs alike, are marked
+        as used on qs when the scope is left."""
+        qs, cur = self._device_stream(torch, stream)
+        if qs != cur:
+            qs.wait_stream(cur)
+        with torch.cuda.stream(qs):
+            yield (qs.cuda_stream,)
+        if qs != cur:
+            for x in tensors:
+                if isinstance(x, torch.Tensor) and x.is_cuda:
+                    x.record_stream(qs)
+
+    def _side(self, x=None, device=False):
+        """The argument side of a call: the device side for a torch tensor `x` (or device=True), the host side otherwise."""
         torch = sys.modules.get("torch")
-        if torch is not None and isinstance(spheres, torch.Tensor):
-            tdt = torch.float32 if R == np.float32 else torch.float64
-            dev = torch.device("cuda", self.device)
-            if spheres.dtype != tdt or spheres.dim() != 2 or spheres.shape[1] != 4 or spheres.shape[0] == 0 or spheres.device != dev or (n is not None and spheres.shape[0] != n):
-                raise ValueError("%s: spheres must be a (%s, 4) %s tensor on %s" % (what, "n" if n is None else n, tdt, dev))
-            return True, spheres
-        if not isinstance(spheres, np.ndarray) or spheres.dtype != R or spheres.ndim != 2 or spheres.shape[1] != 4 or spheres.shape[0] == 0 or (n is not None and spheres.shape[0] != n):
-            raise ValueError("%s: spheres must be a (%s, 4) numpy array of %s (or a torch tensor on the scene's device)" % (what, "n" if n is None else n, np.dtype(R).name))
-        return False, np.ascontiguousarray(spheres)
+        if not device and (torch is None or not isinstance(x, torch.Tensor)):
+            return _HOST_SIDES[self.scene.precision]
+        key = (self.scene.precision, self.device)
+        side = _DEVICE_SIDES.get(key)
+        if side is None:
+            import torch
+            side = _DEVICE_SIDES[key] = _DeviceSide(torch, _real(self.scene.precision), self.device)
+        return side
+
+    def _order_query(self, entry, x, name, cols, rows, stream, n=None, with_n=True):
+        """The body of ray_order, sphere_order and the rebuilds: entry(scene, x[, n], order_out[, stream]) -> uint32[n].  n: None -- every
+        row of x; else that many of them (0: nothing is read or written, and x may be empty)."""
+        side = self._side(x)
+        with side.scope(self, stream, (x,)) as tail:
+            if not (n == 0 and x.shape[0] == 0):
+                x = side.real_rows(x, name, cols, rows)
+            m = x.shape[0] if n is None else n
+            order = side.empty((m,), np.uint32)
+            args = (side.ptr(x) if m else None,) + ((m,) if with_n else ()) + (side.ptr(order) if m else None,)
+            rc = getattr(capi.lib, entry + side.suffix)(self._h, *args, *tail)
+        capi.check(rc, entry + side.suffix)
+        return order
 
     def sphere_order(self, spheres, stream=None):
         """rt_sphere_order / rt_sphere_order_device: the Morton order of `spheres` (n x 4, the scene's REAL dtype; any n), computed on the
         device -> uint32[n]: np.argsort(sphere_keys(spheres), kind="stable").  numpy in, numpy out; a torch tensor on this scene's device goes
         through the device entry on `stream` (as ray_order routes) and gives a torch.uint32 tensor."""
-        is_t, sp = self._spheres_arg(spheres, None, "sphere_order")
-        n = sp.shape[0]
-        if not is_t:
-            order = np.empty(n, dtype=np.uint32)
-            capi.check(capi.lib.rt_sphere_order(self._h, sp.ctypes.data, n, order.ctypes.data), "rt_sphere_order")
-            return order
-        import torch
-        qs, cur = self._device_stream(torch, stream)
-        if qs != cur:
-            qs.wait_stream(cur)
-        with torch.cuda.stream(qs):
-            t = sp.contiguous()
-            order = torch.empty(n, dtype=torch.uint32, device=t.device)
-            rc = capi.lib.rt_sphere_order_device(self._h, C.c_void_p(t.data_ptr()), n, C.c_void_p(order.data_ptr()), C.c_void_p(qs.cuda_stream))
-        if qs != cur:
-            spheres.record_stream(qs)
-        capi.check(rc, "rt_sphere_order_device")
-        return order
+        return self._order_query("rt_sphere_order", spheres, "spheres", 4, None, stream)
 
     def rebuild(self, spheres, stream=None, n=None):
         """rt_scene_rebuild / rt_scene_rebuild_device: the hierarchy of a dynamic scene rebuilt from `spheres` (n_items x 4, the scene's REAL
@@ -843,48 +991,15 @@ class DeviceScene:
         a torch tensor on this scene's device goes through the device entry, enqueued on `stream` with the discipline of update().
         n (rt_scene_rebuild_n*; None: all n_items): the first n rows of `spheres`, 0 <= n <= n_items, into slots 0 .. n-1 in their own
         sphere order -> uint32[n]; every slot from n on is dead, n = 0 empties the scene."""
-        if n is not None:
-            return self._rebuild_n(spheres, int(n), stream)
-        n = self.scene.items.shape[0]
-        is_t, sp = self._spheres_arg(spheres, n, "rebuild")
-        if not is_t:
-            order = np.empty(n, dtype=np.uint32)
-            capi.check(capi.lib.rt_scene_rebuild(self._h, sp.ctypes.data, order.ctypes.data), "rt_scene_rebuild")
-            return order
-        import torch
-        qs, cur = self._device_stream(torch, stream)
-        if qs != cur:
-            qs.wait_stream(cur)
-        with torch.cuda.stream(qs):
-            t = sp.contiguous()
-            order = torch.empty(n, dtype=torch.uint32, device=t.device)
-            rc = capi.lib.rt_scene_rebuild_device(self._h, C.c_void_p(t.data_ptr()), C.c_void_p(order.data_ptr()), C.c_void_p(qs.cuda_stream))
-        for x in (t, spheres):
-            x.record_stream(qs)
-        capi.check(rc, "rt_scene_rebuild_device")
-        return order
-
-    def _rebuild_n(self, spheres, n, stream):
         cap = self.scene.items.shape[0]
+        if n is None:
+            return self._order_query("rt_scene_rebuild", spheres, "spheres", 4, cap, stream, with_n=False)
+        n = int(n)
         if not 0 <= n <= cap:
             raise capi.RtError(capi.RT_ERR_INVALID_ARGUMENT, "rt_scene_rebuild_n", "n = %d is outside 0 .. %d, the scene's capacity" % (n, cap))
-        is_t, sp = self._spheres_arg(spheres, None, "rebuild", at_least=n)
-        if not is_t:
-            order = np.empty(n, dtype=np.uint32)
-            capi.check(capi.lib.rt_scene_rebuild_n(self._h, sp.ctypes.data if n else None, n, order.ctypes.data if n else None), "rt_scene_rebuild_n")
-            return order
-        import torch
-        qs, cur = self._device_stream(torch, stream)
-        if qs != cur:
-            qs.wait_stream(cur)
-        with torch.cuda.stream(qs):
-            t = sp.contiguous()
-            order = torch.empty(n, dtype=torch.uint32, device=t.device)
-            rc = capi.lib.rt_scene_rebuild_n_device(self._h, C.c_void_p(t.data_ptr()) if n else None, n, C.c_void_p(order.data_ptr()) if n else None, C.c_void_p(qs.cuda_stream))
-        for x in (t, spheres):
-            x.record_stream(qs)
-        capi.check(rc, "rt_scene_rebuild_n_device")
-        return order
+        if not (hasattr(spheres, "shape") and len(spheres.shape) == 2 and n <= spheres.shape[0]):
+            raise ValueError("rebuild: spheres must have at least n = %d rows" % n)
+        return self._order_query("rt_scene_rebuild_n", spheres, "spheres", 4, None, stream, n=n)
 
     def live(self):
         """rt_scene_live -> uint8[n_items] of 0 / 1: which slots are live (after the last update or rebuild; an immutable scene: all ones)."""
@@ -1036,6 +1151,96 @@ class DeviceScene:
         capi.check(rc, "rt_render_frame_device")
         return st.as_dict() if want_stats else None
 
+    def _fixed_query(self, entry, x, name, cols, names, values, exclude, order, true_ok, specs, out, want_stats, stream, layout):
+        """The body of every query with one fixed-size result per query: `entry` (host side) or `entry`_device is called with the scene and
+        layout(x, reals, n, exclude, order, results, stats, stream) -- pointers, or NULL for None; reals and results are lists; stream is
+        () on the host side and the 1-tuple of the stream on the device side -- and the results come back as a tuple[, stats dict].
+        x: the main input, `name`, n x cols of the scene's REAL, whose memory kind chooses the side.  names, values: the per-query reals,
+        each one value, (n,) REAL or None.  exclude: int32[n] or None.  order: None or uint32[n]; True passes as NULL where true_ok.
+        specs: (shape behind n, dtype) of each result, "R" for the scene's REAL; out: such arrays or tensors to fill, or None."""
+        side = self._side(x)
+        st = capi.Stats()
+        stp = C.byref(st) if want_stats else None
+        with side.scope(self, stream, (x, exclude, order, *values, *(() if out is None else out))) as tail:
+            x = side.real_rows(x, name, cols)
+            n = x.shape[0]
+            reals = [side.per_query(v, what, n) for what, v in zip(names, values)]
+            ex = side.exclude(exclude, n)
+            o = None if order is None or (order is True and true_ok) else side.order(order, n)
+            if out is None:
+                res = tuple([side.empty((n,) + shape, dt) for shape, dt in specs])
+            else:
+                res = side.check_out(out, [((n,) + shape, dt) for shape, dt in specs])
+            ptr = side.ptr
+            rc = getattr(capi.lib, entry + side.suffix)(
+                self._h, *layout(ptr(x), [ptr(r) for r in reals], n, ptr(ex), ptr(o), [ptr(a) for a in res], stp, tail))
+        capi.check(rc, entry + side.suffix)
+        return res + (st.as_dict(),) if want_stats else res
+
+    def _ray_query(self, entry, head, rays, values, order, specs, out, want_stats, stream):
+        """_fixed_query for the ray entries: entry(scene, *head, rays[, tmax], n, results...[, stream], stats), which with an order (True or
+        indices) is `entry`_ordered, whose order pointer follows n.  values: (tmax,) or ().  Known gap: with tensors `out` is ignored."""
+        ordered = order is not None
+        return self._fixed_query(entry + "_ordered" if ordered else entry, rays, "rays", 6, ("tmax",), values, None, order, True, specs,
+                                 out if isinstance(rays, np.ndarray) else None, want_stats, stream,
+                                 lambda x, t, n, ex, o, res, stats, stream: (*head, x, *t, n, *((o,) if ordered else ()), *res, *stream, stats))
+
+    def _list_query(self, entry, side, xs, shapes, exclude, order, capacity, wanted, columns, offsets, stats, stream, what, head):
+        """The body of every query that lists: `entry` + side.suffix is called with the scene, head(inputs, n, exclude, order) -- pointers, or
+        NULL for None -- and then capacity, a pointer per column, offsets, total, stats[, stream]; -> (columns..., [offsets,] total[, stats
+        dict]).  xs: the inputs, each with its (name, cols, rows, optional) in shapes for side.real_rows -- rows None: any n > 0, which
+        exclude, order and the offsets then go by; _N: n rows; _ITEMS: one per item of the scene (without an n the offsets go by the
+        items too).  order=True: the sphere order of the first input with unit radii, on the same stream.  capacity=None: a counting call
+        first, then exactly that many entries (`what` % count names them when there are too many).  columns: (shape behind the entry
+        count, dtype) each, made where `wanted`.  The host side trims the columns to min(capacity, total) and gives total as an int; the
+        device side waits for nothing unless it had to count: total is then a 0-d int64 tensor."""
+        if capacity is not None:
+            capacity = int(capacity)
+            if not 0 <= capacity <= 0x7FFFFFFF:
+                raise ValueError("capacity must be None or 0 .. 2^31 - 1, not %d" % capacity)
+        st = capi.Stats()
+        stp = C.byref(st) if stats else None
+        ptr = side.ptr
+        with side.scope(self, stream, (*xs, exclude, order)) as tail:
+            n, n_items, staged, ptrs = None, self.scene.items.shape[0], [], []
+            for x, (name, cols, rows, optional) in zip(xs, shapes):
+                x = side.real_rows(x, name, cols, n if rows is _N else n_items if rows is _ITEMS else None, optional)
+                if rows is None:
+                    n = x.shape[0]
+                staged.append(x)
+                ptrs.append(ptr(x))
+            ex = side.exclude(exclude, n)
+            if order is True:
+                unit = side.copy(staged[0])
+                unit[:, 3] = 1                                                   # (the radii take no part in the order, and q = 0 is no sphere)
+                o = self.sphere_order(unit)                                      # (on the scope's stream: it is the current one)
+            else:
+                o = None if order is None else side.order(order, n)
+            total, totp = side.total_cell()
+            off = side.empty(((n_items if n is None else n) + 1,), np.uint64) if offsets else None
+            f = getattr(capi.lib, entry + side.suffix)
+            args = head(ptrs, n, ptr(ex), ptr(o))
+            counted = capacity is None
+            if counted:
+                capi.check(f(self._h, *args, 0, *[None] * len(columns), None, totp, None, *tail), entry + side.suffix)
+                capacity = side.read_total(total)
+                if capacity > 0x7FFFFFFF:
+                    raise ValueError("%s, more than one call can list: pass a capacity" % (what % capacity))
+            listed = [side.empty((capacity,) + shape, dt) if w else None for w, (shape, dt) in zip(wanted, columns)]
+            rc = f(self._h, *args, capacity, *[ptr(c) if capacity else None for c in listed], ptr(off), totp, stp, *tail)
+        capi.check(rc, entry + side.suffix)
+        if side.trims or counted:
+            total = side.read_total(total)
+        m = min(capacity, total) if side.trims else None
+        res = [c if m is None else c[:m] for c in listed if c is not None]
+        if offsets:
+            res.append(off)
+        res.append(total)
+        if stats:
+            res.append(st.as_dict())
+        return tuple(res)
+
+
     def intersect(self, rays, tmax=None, any_hit=False, want_stats=False, stream=None, out=None, order=None):
         """rt_intersect_rays / rt_intersect_rays_device: TypedGroup::intersect for every ray of `rays` (n x 6: pos.xyz, dir.xyz, the scene's REAL
         dtype) -> (distance[n], normal[n, 3], item[n] (DFS index or -1)[, stats dict]).  tmax: hit.distance going in, per ray (an array of
@@ -1048,8 +1253,7 @@ class DeviceScene:
         (ray_order) and walks in that order; or an index array / tensor (uint32[n], a permutation: lane j carries ray order[j]).  The results
         and counters are the same bytes whatever the order; only the time differs."""
         mode = capi.RT_QUERY_ANY if any_hit else capi.RT_QUERY_NEAREST
-        return self._ray_query("rt_intersect_rays", lambda f, r, t, n, *rest: f(self._h, mode, r, t, n, *rest),
-                               (((), "R"), ((3,), "R"), ((), np.int32)), rays, tmax, want_stats, stream, out, order)
+        return self._ray_query("rt_intersect_rays", (mode,), rays, (tmax,), order, (((), "R"), ((3,), "R"), ((), np.int32)), out, want_stats, stream)
 
     def intersect_multi(self, rays, k, tmax=None, all_hits=False, want_stats=False, stream=None, out=None, order=None):
         """rt_intersect_rays_multi / rt_intersect_rays_multi_device: the k closest hits of every ray, nearest first, equal distances in DFS
@@ -1061,8 +1265,8 @@ class DeviceScene:
         if not 1 <= k <= capi.RT_MULTIHIT_MAX_K:
             raise ValueError("k must be 1 .. %d, not %d" % (capi.RT_MULTIHIT_MAX_K, k))
         mode = capi.RT_MULTIHIT_ALL if all_hits else capi.RT_MULTIHIT_CLOSEST
-        return self._ray_query("rt_intersect_rays_multi", lambda f, r, t, n, *rest: f(self._h, mode, k, r, t, n, *rest),
-                               (((k,), "R"), ((k, 3), "R"), ((k,), np.int32), ((), np.uint32)), rays, tmax, want_stats, stream, out, order)
+        return self._ray_query("rt_intersect_rays_multi", (mode, k), rays, (tmax,), order,
+                               (((k,), "R"), ((k, 3), "R"), ((k,), np.int32), ((), np.uint32)), out, want_stats, stream)
 
     def near(self, points, k, radius=None, all_within=False, exclude=None, want_stats=False, stream=None, out=None, order=None):
         """rt_near_spheres / rt_near_spheres_device: the k nearest spheres of every point of `points` (n x 3, the scene's REAL dtype), by
@@ -1082,85 +1286,9 @@ class DeviceScene:
         if not 1 <= k <= capi.RT_NEAR_MAX_K:
             raise ValueError("k must be 1 .. %d, not %d" % (capi.RT_NEAR_MAX_K, k))
         mode = capi.RT_NEAR_ALL if all_within else capi.RT_NEAR_CLOSEST
-        R = _real(self.scene.precision)
-        st = capi.Stats()
-        stp = C.byref(st) if want_stats else None
-        torch = sys.modules.get("torch")
-        if torch is not None and isinstance(points, torch.Tensor):
-            tdt = torch.float32 if R == np.float32 else torch.float64
-            dev = torch.device("cuda", self.device)
-            if points.dtype != tdt or points.dim() != 2 or points.shape[1] != 3 or points.shape[0] == 0:
-                raise ValueError("points must be a non-empty (n, 3) %s tensor" % tdt)
-            if points.device != dev:
-                raise ValueError("points must be on %s, not %s" % (dev, points.device))
-            n = points.shape[0]
-            if isinstance(radius, torch.Tensor):
-                if radius.dim() == 0 and radius.dtype.is_floating_point:
-                    radius = radius.to(tdt)                              # one value: rounded to the scene's REAL
-                if radius.dtype != tdt or radius.numel() not in (1, n):
-                    raise ValueError("radius must be a %s value or (n,) tensor" % tdt)
-            elif radius is not None:
-                radius = self._radius_array(radius, R, n)
-            if exclude is not None and (not isinstance(exclude, torch.Tensor) or exclude.dtype != torch.int32 or exclude.shape != (n,) or exclude.device != dev):
-                raise ValueError("exclude must be None or an (n,) int32 tensor on %s" % dev)
-            if order is not None:
-                try:
-                    order = self._order_torch(torch, order, n, dev)
-                except ValueError:
-                    raise ValueError("order must be None or an (n,) uint32 / int32 tensor on %s" % dev) from None
-            specs = (((n, k), tdt), ((n, k), torch.int32), ((n,), torch.uint32))
-            if out is not None:
-                out = tuple(out)
-                if len(out) != 3 or any(not isinstance(a, torch.Tensor) or a.dtype != dt or tuple(a.shape) != shape or a.device != dev or not a.is_contiguous()
-                                        for a, (shape, dt) in zip(out, specs)):
-                    raise ValueError("out: contiguous tensors on %s of %s" % (dev, ", ".join("%s %s" % (dt, shape) for shape, dt in specs)))
-            qs, cur = self._device_stream(torch, stream)
-            if qs != cur:
-                qs.wait_stream(cur)
-            with torch.cuda.stream(qs):
-                p = points.contiguous()
-                r = None
-                if isinstance(radius, torch.Tensor):
-                    r = radius.to(dev).reshape(-1).expand(n).contiguous()
-                elif radius is not None:
-                    r = torch.from_numpy(radius.copy()).to(dev)              # (a broadcast view is read-only)
-                ex = None if exclude is None else exclude.contiguous()
-                res = out if out is not None else tuple(torch.empty(shape, dtype=dt, device=dev) for shape, dt in specs)
-                ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
-                rc = capi.lib.rt_near_spheres_device(self._h, mode, k, ptr(p), ptr(r), n, ptr(ex), ptr(order), ptr(res[0]), ptr(res[1]), ptr(res[2]),
-                                                     stp, C.c_void_p(qs.cuda_stream))
-            if qs != cur:
-                for x in (points, radius, exclude, order) + tuple(res if out is not None else ()):
-                    if isinstance(x, torch.Tensor) and x.is_cuda:
-                        x.record_stream(qs)
-            capi.check(rc, "rt_near_spheres_device")
-        else:
-            if not isinstance(points, np.ndarray) or points.dtype != R or points.ndim != 2 or points.shape[1] != 3 or points.shape[0] == 0:
-                raise ValueError("points must be a non-empty (n, 3) numpy array of %s (or a torch tensor on the scene's device)" % np.dtype(R).name)
-            n = points.shape[0]
-            p = np.ascontiguousarray(points)
-            r = None if radius is None else self._radius_array(radius, R, n)
-            ex = None
-            if exclude is not None:
-                ex = np.asarray(exclude)
-                if ex.dtype != np.int32 or ex.shape != (n,):
-                    raise ValueError("exclude must be None or an (n,) int32 array")
-                ex = np.ascontiguousarray(ex)
-            o = None if order is None else self._order_numpy(order, n)
-            specs = (((n, k), R), ((n, k), np.int32), ((n,), np.uint32))
-            if out is None:
-                res = tuple(np.empty(shape, dtype=dt) for shape, dt in specs)
-            else:
-                res = tuple(out)
-                if len(res) != 3 or any(not isinstance(a, np.ndarray) or a.dtype != dt or a.shape != shape or not a.flags.c_contiguous
-                                        for a, (shape, dt) in zip(res, specs)):
-                    raise ValueError("out: contiguous arrays of " + ", ".join("%s %s" % (np.dtype(dt).name, shape) for shape, dt in specs))
-            ptr = lambda x: None if x is None else x.ctypes.data
-            rc = capi.lib.rt_near_spheres(self._h, mode, k, ptr(p), ptr(r), n, ptr(ex), ptr(o), ptr(res[0]), ptr(res[1]), ptr(res[2]), stp)
-            capi.check(rc, "rt_near_spheres")
-        if want_stats:
-            return tuple(res) + (st.as_dict(),)
-        return tuple(res)
+        return self._fixed_query("rt_near_spheres", points, "points", 3, ("radius",), (radius,), exclude, order, False,
+                                 (((k,), "R"), ((k,), np.int32), ((), np.uint32)), out, want_stats, stream,
+                                 lambda p, r, n, ex, o, res, stats, stream: (mode, k, p, r[0], n, ex, o, *res, stats, *stream))
 
     def sweep(self, rays, radius=None, tmax=None, any_hit=False, exclude=None, order=None, want_stats=False, stream=None, out=None):
         """rt_sweep_spheres / rt_sweep_spheres_device: the first contact of a moving sphere with the scene, for every cast of `rays` (n x 6:
@@ -1177,90 +1305,9 @@ class DeviceScene:
         the time differs.  The host entry wants a permutation; through the device entry an index >= n carries no cast and leaves that
         thread's outputs alone."""
         mode = capi.RT_SWEEP_ANY if any_hit else capi.RT_SWEEP_NEAREST
-        R = _real(self.scene.precision)
-        st = capi.Stats()
-        stp = C.byref(st) if want_stats else None
-        torch = sys.modules.get("torch")
-        if torch is not None and isinstance(rays, torch.Tensor):
-            tdt = torch.float32 if R == np.float32 else torch.float64
-            dev = torch.device("cuda", self.device)
-            if rays.dtype != tdt or rays.dim() != 2 or rays.shape[1] != 6 or rays.shape[0] == 0:
-                raise ValueError("rays must be a non-empty (n, 6) %s tensor" % tdt)
-            if rays.device != dev:
-                raise ValueError("rays must be on %s, not %s" % (dev, rays.device))
-            n = rays.shape[0]
-            reals = {"radius": radius, "tmax": tmax}
-            for name, x in reals.items():
-                if isinstance(x, torch.Tensor):
-                    if x.dim() == 0 and x.dtype.is_floating_point:
-                        x = x.to(tdt)                                    # one value: rounded to the scene's REAL
-                    if x.dtype != tdt or x.numel() not in (1, n):
-                        raise ValueError("%s must be a %s value or (n,) tensor" % (name, tdt))
-                elif x is not None:
-                    x = self._radius_array(x, R, n) if name == "radius" else _tmax_array(x, R, n)
-                reals[name] = x
-            if exclude is not None and (not isinstance(exclude, torch.Tensor) or exclude.dtype != torch.int32 or exclude.shape != (n,) or exclude.device != dev):
-                raise ValueError("exclude must be None or an (n,) int32 tensor on %s" % dev)
-            if order is not None:
-                try:
-                    order = self._order_torch(torch, order, n, dev)
-                except ValueError:
-                    raise ValueError("order must be None or an (n,) uint32 / int32 tensor on %s" % dev) from None
-            specs = (((n,), tdt), ((n, 3), tdt), ((n,), torch.int32))
-            if out is not None:
-                out = tuple(out)
-                if len(out) != 3 or any(not isinstance(a, torch.Tensor) or a.dtype != dt or tuple(a.shape) != shape or a.device != dev or not a.is_contiguous()
-                                        for a, (shape, dt) in zip(out, specs)):
-                    raise ValueError("out: contiguous tensors on %s of %s" % (dev, ", ".join("%s %s" % (dt, shape) for shape, dt in specs)))
-            qs, cur = self._device_stream(torch, stream)
-            if qs != cur:
-                qs.wait_stream(cur)
-            with torch.cuda.stream(qs):
-                r = rays.contiguous()
-                staged = {}
-                for name, x in reals.items():
-                    if isinstance(x, torch.Tensor):
-                        staged[name] = x.to(dev).reshape(-1).expand(n).contiguous()
-                    else:
-                        staged[name] = None if x is None else torch.from_numpy(x.copy()).to(dev)     # (a broadcast view is read-only)
-                ex = None if exclude is None else exclude.contiguous()
-                res = out if out is not None else tuple(torch.empty(shape, dtype=dt, device=dev) for shape, dt in specs)
-                ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
-                rc = capi.lib.rt_sweep_spheres_device(self._h, mode, ptr(r), ptr(staged["radius"]), ptr(staged["tmax"]), n, ptr(ex), ptr(order),
-                                                      ptr(res[0]), ptr(res[1]), ptr(res[2]), stp, C.c_void_p(qs.cuda_stream))
-            if qs != cur:
-                for x in (rays, reals["radius"], reals["tmax"], exclude, order) + tuple(res if out is not None else ()):
-                    if isinstance(x, torch.Tensor) and x.is_cuda:
-                        x.record_stream(qs)
-            capi.check(rc, "rt_sweep_spheres_device")
-        else:
-            if not isinstance(rays, np.ndarray) or rays.dtype != R or rays.ndim != 2 or rays.shape[1] != 6 or rays.shape[0] == 0:
-                raise ValueError("rays must be a non-empty (n, 6) numpy array of %s (or a torch tensor on the scene's device)" % np.dtype(R).name)
-            n = rays.shape[0]
-            r = np.ascontiguousarray(rays)
-            q = None if radius is None else self._radius_array(radius, R, n)
-            t = None if tmax is None else _tmax_array(tmax, R, n)
-            ex = None
-            if exclude is not None:
-                ex = np.asarray(exclude)
-                if ex.dtype != np.int32 or ex.shape != (n,):
-                    raise ValueError("exclude must be None or an (n,) int32 array")
-                ex = np.ascontiguousarray(ex)
-            o = None if order is None else self._order_numpy(order, n)
-            specs = (((n,), R), ((n, 3), R), ((n,), np.int32))
-            if out is None:
-                res = tuple(np.empty(shape, dtype=dt) for shape, dt in specs)
-            else:
-                res = tuple(out)
-                if len(res) != 3 or any(not isinstance(a, np.ndarray) or a.dtype != dt or a.shape != shape or not a.flags.c_contiguous
-                                        for a, (shape, dt) in zip(res, specs)):
-                    raise ValueError("out: contiguous arrays of " + ", ".join("%s %s" % (np.dtype(dt).name, shape) for shape, dt in specs))
-            ptr = lambda x: None if x is None else x.ctypes.data
-            rc = capi.lib.rt_sweep_spheres(self._h, mode, ptr(r), ptr(q), ptr(t), n, ptr(ex), ptr(o), ptr(res[0]), ptr(res[1]), ptr(res[2]), stp)
-            capi.check(rc, "rt_sweep_spheres")
-        if want_stats:
-            return tuple(res) + (st.as_dict(),)
-        return tuple(res)
+        return self._fixed_query("rt_sweep_spheres", rays, "rays", 6, ("radius", "tmax"), (radius, tmax), exclude, order, False,
+                                 (((), "R"), ((3,), "R"), ((), np.int32)), out, want_stats, stream,
+                                 lambda y, qt, n, ex, o, res, stats, stream: (mode, y, qt[0], qt[1], n, ex, o, *res, stats, *stream))
 
     def contacts(self, margin=0.0, capacity=None, gaps=False, offsets=False, stats=False, device=False, stream=None):
         """rt_scene_contacts / rt_scene_contacts_device: every pair of spheres of the scene that is closer than `margin` (pair_gaps is the
@@ -1276,56 +1323,8 @@ class DeviceScene:
         margin = float(margin)
         if margin != margin:
             raise ValueError("margin must not be NaN")
-        if capacity is not None:
-            capacity = int(capacity)
-            if not 0 <= capacity <= 0x7FFFFFFF:
-                raise ValueError("capacity must be None or 0 .. 2^31 - 1, not %d" % capacity)
-        R = _real(self.scene.precision)
-        n = self.scene.items.shape[0]
-        st = capi.Stats()
-        stp = C.byref(st) if stats else None
-        if device:
-            import torch
-            tdt = torch.float32 if R == np.float32 else torch.float64
-            dev = torch.device("cuda", self.device)
-            qs, cur = self._device_stream(torch, stream)
-            if qs != cur:
-                qs.wait_stream(cur)
-            ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
-            with torch.cuda.stream(qs):
-                total = torch.zeros((), dtype=torch.int64, device=dev)
-                off = torch.empty(n + 1, dtype=torch.int64, device=dev) if offsets else None
-                counted = capacity is None
-                if counted:
-                    capi.check(capi.lib.rt_scene_contacts_device(self._h, margin, 0, None, None, None, ptr(total), None, C.c_void_p(qs.cuda_stream)),
-                               "rt_scene_contacts_device")
-                    capacity = int(total.item())
-                    if capacity > 0x7FFFFFFF:
-                        raise ValueError("the scene has %d contacts, more than one call can list: pass a capacity" % capacity)
-                pairs = torch.empty((capacity, 2), dtype=torch.int32, device=dev)
-                gap = torch.empty(capacity, dtype=tdt, device=dev) if gaps else None
-                rc = capi.lib.rt_scene_contacts_device(self._h, margin, capacity, ptr(pairs) if capacity else None, ptr(gap) if capacity else None, ptr(off), ptr(total), stp,
-                                                       C.c_void_p(qs.cuda_stream))
-            capi.check(rc, "rt_scene_contacts_device")
-            total = int(total.item()) if counted else total
-        else:
-            total = C.c_uint64(0)
-            off = np.empty(n + 1, dtype=np.uint64) if offsets else None
-            ptr = lambda x: None if x is None else x.ctypes.data
-            if capacity is None:
-                capi.check(capi.lib.rt_scene_contacts(self._h, margin, 0, None, None, None, C.byref(total), None), "rt_scene_contacts")
-                capacity = int(total.value)
-                if capacity > 0x7FFFFFFF:
-                    raise ValueError("the scene has %d contacts, more than one call can list: pass a capacity" % capacity)
-            pairs = np.empty((capacity, 2), dtype=np.int32)
-            gap = np.empty(capacity, dtype=R) if gaps else None
-            capi.check(capi.lib.rt_scene_contacts(self._h, margin, capacity, ptr(pairs) if capacity else None, ptr(gap) if capacity else None, ptr(off),
-                                                  C.byref(total), stp), "rt_scene_contacts")
-            total = int(total.value)
-            m = min(capacity, total)
-            pairs, gap = pairs[:m], (gap[:m] if gaps else None)
-        res = (pairs,) + ((gap,) if gaps else ()) + ((off,) if offsets else ()) + (total,)
-        return res + ((st.as_dict(),) if stats else ())
+        return self._list_query("rt_scene_contacts", self._side(device=device), (), (), None, None, capacity, (True, gaps), (((2,), np.int32), ((), "R")),
+                                offsets, stats, stream, "the scene has %d contacts", lambda xs, n, ex, o: (margin,))
 
     def overlaps(self, queries, margin=0.0, exclude=None, order=None, capacity=None, gaps=False, offsets=False, stats=False, stream=None):
         """rt_overlap_spheres / rt_overlap_spheres_device: every sphere of the scene within `margin` of each query sphere of `queries`
@@ -1346,91 +1345,9 @@ class DeviceScene:
         margin = float(margin)
         if margin != margin:
             raise ValueError("margin must not be NaN")
-        if capacity is not None:
-            capacity = int(capacity)
-            if not 0 <= capacity <= 0x7FFFFFFF:
-                raise ValueError("capacity must be None or 0 .. 2^31 - 1, not %d" % capacity)
-        R = _real(self.scene.precision)
-        st = capi.Stats()
-        stp = C.byref(st) if stats else None
-        torch = sys.modules.get("torch")
-        if torch is not None and isinstance(queries, torch.Tensor):
-            tdt = torch.float32 if R == np.float32 else torch.float64
-            dev = torch.device("cuda", self.device)
-            if queries.dtype != tdt or queries.dim() != 2 or queries.shape[1] != 4 or queries.shape[0] == 0:
-                raise ValueError("queries must be a non-empty (n, 4) %s tensor" % tdt)
-            if queries.device != dev:
-                raise ValueError("queries must be on %s, not %s" % (dev, queries.device))
-            n = queries.shape[0]
-            if exclude is not None and (not isinstance(exclude, torch.Tensor) or exclude.dtype != torch.int32 or exclude.shape != (n,) or exclude.device != dev):
-                raise ValueError("exclude must be None or an (n,) int32 tensor on %s" % dev)
-            if order is not None and order is not True:
-                order = self._order_torch(torch, order, n, dev)
-            qs, cur = self._device_stream(torch, stream)
-            if qs != cur:
-                qs.wait_stream(cur)
-            ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
-            with torch.cuda.stream(qs):
-                qt = queries.contiguous()
-                if order is True:
-                    unit = qt.clone()
-                    unit[:, 3] = 1                                               # (the radii take no part in the order, and q = 0 is no sphere)
-                    order = self.sphere_order(unit, stream=qs)
-                ex = None if exclude is None else exclude.contiguous()
-                total = torch.zeros((), dtype=torch.int64, device=dev)
-                off = torch.empty(n + 1, dtype=torch.int64, device=dev) if offsets else None
-                counted = capacity is None
-                if counted:
-                    capi.check(capi.lib.rt_overlap_spheres_device(self._h, ptr(qt), n, margin, ptr(ex), ptr(order), 0, None, None, None, ptr(total), None,
-                                                                  C.c_void_p(qs.cuda_stream)), "rt_overlap_spheres_device")
-                    capacity = int(total.item())
-                    if capacity > 0x7FFFFFFF:
-                        raise ValueError("the queries have %d entries, more than one call can list: pass a capacity" % capacity)
-                items = torch.empty(capacity, dtype=torch.int32, device=dev)
-                gap = torch.empty(capacity, dtype=tdt, device=dev) if gaps else None
-                rc = capi.lib.rt_overlap_spheres_device(self._h, ptr(qt), n, margin, ptr(ex), ptr(order), capacity, ptr(items) if capacity else None,
-                                                        ptr(gap) if capacity else None, ptr(off), ptr(total), stp, C.c_void_p(qs.cuda_stream))
-            if qs != cur:
-                for x in (queries, qt, exclude, ex, order):
-                    if isinstance(x, torch.Tensor) and x.is_cuda:
-                        x.record_stream(qs)
-            capi.check(rc, "rt_overlap_spheres_device")
-            total = int(total.item()) if counted else total
-        else:
-            if not isinstance(queries, np.ndarray) or queries.dtype != R or queries.ndim != 2 or queries.shape[1] != 4 or queries.shape[0] == 0:
-                raise ValueError("queries must be a non-empty (n, 4) numpy array of %s (or a torch tensor on the scene's device)" % np.dtype(R).name)
-            n = queries.shape[0]
-            qa = np.ascontiguousarray(queries)
-            ex = None
-            if exclude is not None:
-                ex = np.asarray(exclude)
-                if ex.dtype != np.int32 or ex.shape != (n,):
-                    raise ValueError("exclude must be None or an (n,) int32 array")
-                ex = np.ascontiguousarray(ex)
-            o = None
-            if order is True:
-                unit = qa.copy()
-                unit[:, 3] = 1                                                   # (the radii take no part in the order, and q = 0 is no sphere)
-                o = self.sphere_order(unit)
-            elif order is not None:
-                o = self._order_numpy(order, n)
-            total = C.c_uint64(0)
-            off = np.empty(n + 1, dtype=np.uint64) if offsets else None
-            ptr = lambda x: None if x is None else x.ctypes.data
-            if capacity is None:
-                capi.check(capi.lib.rt_overlap_spheres(self._h, ptr(qa), n, margin, ptr(ex), ptr(o), 0, None, None, None, C.byref(total), None), "rt_overlap_spheres")
-                capacity = int(total.value)
-                if capacity > 0x7FFFFFFF:
-                    raise ValueError("the queries have %d entries, more than one call can list: pass a capacity" % capacity)
-            items = np.empty(capacity, dtype=np.int32)
-            gap = np.empty(capacity, dtype=R) if gaps else None
-            capi.check(capi.lib.rt_overlap_spheres(self._h, ptr(qa), n, margin, ptr(ex), ptr(o), capacity, ptr(items) if capacity else None,
-                                                   ptr(gap) if capacity else None, ptr(off), C.byref(total), stp), "rt_overlap_spheres")
-            total = int(total.value)
-            m = min(capacity, total)
-            items, gap = items[:m], (gap[:m] if gaps else None)
-        res = (items,) + ((gap,) if gaps else ()) + ((off,) if offsets else ()) + (total,)
-        return res + ((st.as_dict(),) if stats else ())
+        return self._list_query("rt_overlap_spheres", self._side(queries), (queries,), (("queries", 4, None, False),), exclude, order, capacity,
+                                (True, gaps), (((), np.int32), ((), "R")), offsets, stats, stream, "the queries have %d entries",
+                                lambda xs, n, ex, o: (xs[0], n, margin, ex, o))
 
     def impacts(self, disp, capacity=None, times=False, offsets=False, stats=False, stream=None):
         """rt_scene_impacts / rt_scene_impacts_device: every pair of spheres of the scene that comes into contact while sphere k moves from
@@ -1445,69 +1362,11 @@ class DeviceScene:
         stream) and gives torch tensors -- with a capacity nothing is waited for: pairs has `capacity` rows of which the first `total` are
         written, and total is a 0-d int64 tensor (offsets is an int64 tensor too: the same bits); capacity=None reads the count back
         first, and total is an int."""
-        if capacity is not None:
-            capacity = int(capacity)
-            if not 0 <= capacity <= 0x7FFFFFFF:
-                raise ValueError("capacity must be None or 0 .. 2^31 - 1, not %d" % capacity)
-            if times and capacity == 0:
-                raise ValueError("times needs pairs: capacity must not be 0")
-        R = _real(self.scene.precision)
-        n = self.scene.items.shape[0]
-        st = capi.Stats()
-        stp = C.byref(st) if stats else None
-        torch = sys.modules.get("torch")
-        if torch is not None and isinstance(disp, torch.Tensor):
-            tdt = torch.float32 if R == np.float32 else torch.float64
-            dev = torch.device("cuda", self.device)
-            if disp.dtype != tdt or tuple(disp.shape) != (n, 3):
-                raise ValueError("disp must be an (%d, 3) %s tensor" % (n, tdt))
-            if disp.device != dev:
-                raise ValueError("disp must be on %s, not %s" % (dev, disp.device))
-            qs, cur = self._device_stream(torch, stream)
-            if qs != cur:
-                qs.wait_stream(cur)
-            ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
-            with torch.cuda.stream(qs):
-                dt = disp.contiguous()
-                total = torch.zeros((), dtype=torch.int64, device=dev)
-                off = torch.empty(n + 1, dtype=torch.int64, device=dev) if offsets else None
-                counted = capacity is None
-                if counted:
-                    capi.check(capi.lib.rt_scene_impacts_device(self._h, ptr(dt), 0, None, None, None, ptr(total), None, C.c_void_p(qs.cuda_stream)),
-                               "rt_scene_impacts_device")
-                    capacity = int(total.item())
-                    if capacity > 0x7FFFFFFF:
-                        raise ValueError("the step has %d impacts, more than one call can list: pass a capacity" % capacity)
-                pairs = torch.empty((capacity, 2), dtype=torch.int32, device=dev)
-                time = torch.empty(capacity, dtype=tdt, device=dev) if times else None
-                rc = capi.lib.rt_scene_impacts_device(self._h, ptr(dt), capacity, ptr(pairs) if capacity else None, ptr(time) if capacity else None, ptr(off),
-                                                      ptr(total), stp, C.c_void_p(qs.cuda_stream))
-            if qs != cur:
-                for x in (disp, dt):
-                    x.record_stream(qs)
-            capi.check(rc, "rt_scene_impacts_device")
-            total = int(total.item()) if counted else total
-        else:
-            if not isinstance(disp, np.ndarray) or disp.dtype != R or disp.shape != (n, 3):
-                raise ValueError("disp must be an (%d, 3) numpy array of %s (or a torch tensor on the scene's device)" % (n, np.dtype(R).name))
-            da = np.ascontiguousarray(disp)
-            total = C.c_uint64(0)
-            off = np.empty(n + 1, dtype=np.uint64) if offsets else None
-            ptr = lambda x: None if x is None else x.ctypes.data
-            if capacity is None:
-                capi.check(capi.lib.rt_scene_impacts(self._h, ptr(da), 0, None, None, None, C.byref(total), None), "rt_scene_impacts")
-                capacity = int(total.value)
-                if capacity > 0x7FFFFFFF:
-                    raise ValueError("the step has %d impacts, more than one call can list: pass a capacity" % capacity)
-            pairs = np.empty((capacity, 2), dtype=np.int32)
-            time = np.empty(capacity, dtype=R) if times else None
-            capi.check(capi.lib.rt_scene_impacts(self._h, ptr(da), capacity, ptr(pairs) if capacity else None, ptr(time) if capacity else None, ptr(off),
-                                                 C.byref(total), stp), "rt_scene_impacts")
-            total = int(total.value)
-            m = min(capacity, total)
-            pairs, time = pairs[:m], (time[:m] if times else None)
-        res = (pairs,) + ((time,) if times else ()) + ((off,) if offsets else ()) + (total,)
-        return res + ((st.as_dict(),) if stats else ())
+        if times and capacity is not None and int(capacity) == 0:
+            raise ValueError("times needs pairs: capacity must not be 0")
+        return self._list_query("rt_scene_impacts", self._side(disp), (disp,), (("disp", 3, _ITEMS, False),), None, None, capacity,
+                                (True, times), (((2,), np.int32), ((), "R")), offsets, stats, stream, "the step has %d impacts",
+                                lambda xs, n, ex, o: (xs[0],))
 
     def swept_overlaps(self, queries, qdisp, disp=None, exclude=None, order=None, capacity=None, times=False, normals=False, offsets=False, stats=False,
                        stream=None):
@@ -1521,255 +1380,18 @@ class DeviceScene:
         .. offsets[g + 1].  total: how many entries there are.  capacity, exclude, order (True: sphere_order of the start poses), numpy and
         torch arguments, `stream` and the results' types are overlaps()'s; times and normals need items (not capacity=0).  A query whose q
         is not >= 0 has an empty row; q = 0 is a moving point."""
-        if capacity is not None:
-            capacity = int(capacity)
-            if not 0 <= capacity <= 0x7FFFFFFF:
-                raise ValueError("capacity must be None or 0 .. 2^31 - 1, not %d" % capacity)
-            if (times or normals) and capacity == 0:
-                raise ValueError("times and normals need items: capacity must not be 0")
-        R = _real(self.scene.precision)
-        n_items = self.scene.items.shape[0]
-        st = capi.Stats()
-        stp = C.byref(st) if stats else None
-        torch = sys.modules.get("torch")
-        if torch is not None and isinstance(queries, torch.Tensor):
-            tdt = torch.float32 if R == np.float32 else torch.float64
-            dev = torch.device("cuda", self.device)
-            if queries.dtype != tdt or queries.dim() != 2 or queries.shape[1] != 4 or queries.shape[0] == 0:
-                raise ValueError("queries must be a non-empty (n, 4) %s tensor" % tdt)
-            if queries.device != dev:
-                raise ValueError("queries must be on %s, not %s" % (dev, queries.device))
-            n = queries.shape[0]
-            if not isinstance(qdisp, torch.Tensor) or qdisp.dtype != tdt or tuple(qdisp.shape) != (n, 3) or qdisp.device != dev:
-                raise ValueError("qdisp must be an (n, 3) %s tensor on %s" % (tdt, dev))
-            if disp is not None and (not isinstance(disp, torch.Tensor) or disp.dtype != tdt or tuple(disp.shape) != (n_items, 3) or disp.device != dev):
-                raise ValueError("disp must be None or an (%d, 3) %s tensor on %s" % (n_items, tdt, dev))
-            if exclude is not None and (not isinstance(exclude, torch.Tensor) or exclude.dtype != torch.int32 or exclude.shape != (n,) or exclude.device != dev):
-                raise ValueError("exclude must be None or an (n,) int32 tensor on %s" % dev)
-            if order is not None and order is not True:
-                order = self._order_torch(torch, order, n, dev)
-            qs, cur = self._device_stream(torch, stream)
-            if qs != cur:
-                qs.wait_stream(cur)
-            ptr = lambda x: None if x is None else C.c_void_p(x.data_ptr())
-            with torch.cuda.stream(qs):
-                qt, qd = queries.contiguous(), qdisp.contiguous()
-                dt = None if disp is None else disp.contiguous()
-                if order is True:
-                    unit = qt.clone()
-                    unit[:, 3] = 1                                               # (the radii take no part in the order, and q = 0 is no sphere)
-                    order = self.sphere_order(unit, stream=qs)
-                ex = None if exclude is None else exclude.contiguous()
-                total = torch.zeros((), dtype=torch.int64, device=dev)
-                off = torch.empty(n + 1, dtype=torch.int64, device=dev) if offsets else None
-                counted = capacity is None
-                if counted:
-                    capi.check(capi.lib.rt_swept_overlaps_device(self._h, ptr(qt), ptr(qd), n, ptr(dt), ptr(ex), ptr(order), 0, None, None, None, None, ptr(total),
-                                                                 None, C.c_void_p(qs.cuda_stream)), "rt_swept_overlaps_device")
-                    capacity = int(total.item())
-                    if capacity > 0x7FFFFFFF:
-                        raise ValueError("the queries have %d entries, more than one call can list: pass a capacity" % capacity)
-                items = torch.empty(capacity, dtype=torch.int32, device=dev)
-                time = torch.empty(capacity, dtype=tdt, device=dev) if times else None
-                normal = torch.empty((capacity, 3), dtype=tdt, device=dev) if normals else None
-                rc = capi.lib.rt_swept_overlaps_device(self._h, ptr(qt), ptr(qd), n, ptr(dt), ptr(ex), ptr(order), capacity, ptr(items) if capacity else None,
-                                                       ptr(time) if capacity else None, ptr(normal) if capacity else None, ptr(off), ptr(total), stp,
-                                                       C.c_void_p(qs.cuda_stream))
-            if qs != cur:
-                for x in (queries, qt, qdisp, qd, disp, dt, exclude, ex, order):
-                    if isinstance(x, torch.Tensor) and x.is_cuda:
-                        x.record_stream(qs)
-            capi.check(rc, "rt_swept_overlaps_device")
-            total = int(total.item()) if counted else total
-        else:
-            if not isinstance(queries, np.ndarray) or queries.dtype != R or queries.ndim != 2 or queries.shape[1] != 4 or queries.shape[0] == 0:
-                raise ValueError("queries must be a non-empty (n, 4) numpy array of %s (or a torch tensor on the scene's device)" % np.dtype(R).name)
-            n = queries.shape[0]
-            if not isinstance(qdisp, np.ndarray) or qdisp.dtype != R or qdisp.shape != (n, 3):
-                raise ValueError("qdisp must be an (n, 3) numpy array of %s" % np.dtype(R).name)
-            if disp is not None and (not isinstance(disp, np.ndarray) or disp.dtype != R or disp.shape != (n_items, 3)):
-                raise ValueError("disp must be None or an (%d, 3) numpy array of %s" % (n_items, np.dtype(R).name))
-            qa, qd = np.ascontiguousarray(queries), np.ascontiguousarray(qdisp)
-            da = None if disp is None else np.ascontiguousarray(disp)
-            ex = None
-            if exclude is not None:
-                ex = np.asarray(exclude)
-                if ex.dtype != np.int32 or ex.shape != (n,):
-                    raise ValueError("exclude must be None or an (n,) int32 array")
-                ex = np.ascontiguousarray(ex)
-            o = None
-            if order is True:
-                unit = qa.copy()
-                unit[:, 3] = 1                                                   # (the radii take no part in the order, and q = 0 is no sphere)
-                o = self.sphere_order(unit)
-            elif order is not None:
-                o = self._order_numpy(order, n)
-            total = C.c_uint64(0)
-            off = np.empty(n + 1, dtype=np.uint64) if offsets else None
-            ptr = lambda x: None if x is None else x.ctypes.data
-            if capacity is None:
-                capi.check(capi.lib.rt_swept_overlaps(self._h, ptr(qa), ptr(qd), n, ptr(da), ptr(ex), ptr(o), 0, None, None, None, None, C.byref(total), None),
-                           "rt_swept_overlaps")
-                capacity = int(total.value)
-                if capacity > 0x7FFFFFFF:
-                    raise ValueError("the queries have %d entries, more than one call can list: pass a capacity" % capacity)
-            items = np.empty(capacity, dtype=np.int32)
-            time = np.empty(capacity, dtype=R) if times else None
-            normal = np.empty((capacity, 3), dtype=R) if normals else None
-            capi.check(capi.lib.rt_swept_overlaps(self._h, ptr(qa), ptr(qd), n, ptr(da), ptr(ex), ptr(o), capacity, ptr(items) if capacity else None,
-                                                  ptr(time) if capacity else None, ptr(normal) if capacity else None, ptr(off), C.byref(total), stp),
-                       "rt_swept_overlaps")
-            total = int(total.value)
-            m = min(capacity, total)
-            items, time, normal = items[:m], (time[:m] if times else None), (normal[:m] if normals else None)
-        res = (items,) + ((time,) if times else ()) + ((normal,) if normals else ()) + ((off,) if offsets else ()) + (total,)
-        return res + ((st.as_dict(),) if stats else ())
-
-    @staticmethod
-    def _radius_array(radius, R, n):
-        """near()'s and sweep()'s radius as a contiguous REAL[n] (one value is rounded to REAL; an array must already be REAL)."""
-        try:
-            return _tmax_array(radius, R, n)
-        except ValueError:
-            raise ValueError("radius must be one value or an (n,) array of %s" % np.dtype(R).name) from None
-
-    @staticmethod
-    def _order_numpy(order, n):
-        """An index array for a host entry: contiguous uint32[n] (whether it is a permutation is the library's check)."""
-        o = np.asarray(order)
-        if o.dtype.kind not in "iu" or o.shape != (n,):
-            raise ValueError("order must be None, True or an (n,) integer array")
-        if o.dtype != np.uint32 and n and (int(o.min()) < 0 or int(o.max()) > 0xFFFFFFFF):      # (the cast below would wrap it into range)
-            raise ValueError("order holds an index outside 0 .. 2^32 - 1")
-        return np.ascontiguousarray(o, dtype=np.uint32)
-
-    @staticmethod
-    def _order_torch(torch, order, n, dev):
-        """An index tensor for a device entry: contiguous uint32 / int32 [n] on the scene's device."""
-        if not isinstance(order, torch.Tensor) or order.dtype not in (torch.uint32, torch.int32) or order.shape != (n,) or order.device != dev:
-            raise ValueError("order must be None, True or an (n,) uint32 / int32 tensor on %s" % dev)
-        return order.contiguous()
+        if (times or normals) and capacity is not None and int(capacity) == 0:
+            raise ValueError("times and normals need items: capacity must not be 0")
+        return self._list_query("rt_swept_overlaps", self._side(queries), (queries, qdisp, disp),
+                                (("queries", 4, None, False), ("qdisp", 3, _N, False), ("disp", 3, _ITEMS, True)), exclude, order, capacity,
+                                (True, times, normals), (((), np.int32), ((), "R"), ((3,), "R")), offsets, stats, stream,
+                                "the queries have %d entries", lambda xs, n, ex, o: (xs[0], xs[1], n, xs[2], ex, o))
 
     def ray_order(self, rays, stream=None):
         """rt_ray_order / rt_ray_order_device: the coherent order of `rays` (n x 6, the scene's REAL dtype), computed on the device -> uint32[n],
         order[j] = the ray lane j should carry: np.argsort(ray_keys(rays), kind="stable").  numpy in, numpy out; a torch tensor on this
         scene's device goes through the device entry on `stream` (as intersect() routes) and gives a torch.uint32 tensor."""
-        R = _real(self.scene.precision)
-        torch = sys.modules.get("torch")
-        if torch is not None and isinstance(rays, torch.Tensor):
-            tdt = torch.float32 if R == np.float32 else torch.float64
-            dev = torch.device("cuda", self.device)
-            if rays.dtype != tdt or rays.dim() != 2 or rays.shape[1] != 6 or rays.shape[0] == 0:
-                raise ValueError("rays must be a non-empty (n, 6) %s tensor" % tdt)
-            if rays.device != dev:
-                raise ValueError("rays must be on %s, not %s" % (dev, rays.device))
-            n = rays.shape[0]
-            cur = torch.cuda.current_stream(dev)
-            if stream is None:
-                qs = cur
-            elif isinstance(stream, torch.cuda.Stream):
-                qs = stream
-            else:
-                h = int(stream)
-                qs = torch.cuda.default_stream(dev) if h == 0 else torch.cuda.ExternalStream(h, device=dev)
-            if qs != cur:
-                qs.wait_stream(cur)
-            with torch.cuda.stream(qs):
-                r = rays.contiguous()
-                order = torch.empty(n, dtype=torch.uint32, device=dev)
-                rc = capi.lib.rt_ray_order_device(self._h, C.c_void_p(r.data_ptr()), n, C.c_void_p(order.data_ptr()), C.c_void_p(qs.cuda_stream))
-            if qs != cur:
-                rays.record_stream(qs)
-            capi.check(rc, "rt_ray_order_device")
-            return order
-        if not isinstance(rays, np.ndarray) or rays.dtype != R or rays.ndim != 2 or rays.shape[1] != 6 or rays.shape[0] == 0:
-            raise ValueError("rays must be a non-empty (n, 6) numpy array of %s (or a torch tensor on the scene's device)" % np.dtype(R).name)
-        rays = np.ascontiguousarray(rays)
-        order = np.empty(rays.shape[0], dtype=np.uint32)
-        capi.check(capi.lib.rt_ray_order(self._h, rays.ctypes.data, rays.shape[0], order.ctypes.data), "rt_ray_order")
-        return order
-
-    def _ray_query(self, entry, call, results, rays, tmax, want_stats, stream, out, order=None):
-        """The body every ray query shares: checks rays and tmax, makes the results -- (shape behind n, dtype) each, "R" for the scene's
-        REAL -- and calls `entry` (numpy) or `entry`_device (torch) as call(f, rays, tmax, n, *result pointers[, stream], stats).  With an
-        order (True or indices) it is `entry`_ordered[_device], whose order pointer (NULL for True) follows n."""
-        if order is not None:
-            entry += "_ordered"
-        R = _real(self.scene.precision)
-        st = capi.Stats()
-        stp = C.byref(st) if want_stats else None
-        torch = sys.modules.get("torch")
-        if torch is not None and isinstance(rays, torch.Tensor):
-            tdt = torch.float32 if R == np.float32 else torch.float64
-            tdts = {"R": tdt, np.int32: torch.int32, np.uint32: torch.uint32}
-            dev = torch.device("cuda", self.device)
-            if rays.dtype != tdt or rays.dim() != 2 or rays.shape[1] != 6 or rays.shape[0] == 0:
-                raise ValueError("rays must be a non-empty (n, 6) %s tensor" % tdt)
-            if rays.device != dev:
-                raise ValueError("rays must be on %s, not %s" % (dev, rays.device))
-            n = rays.shape[0]
-            if isinstance(tmax, torch.Tensor):
-                if tmax.dim() == 0 and tmax.dtype.is_floating_point:
-                    tmax = tmax.to(tdt)                                  # one value: rounded to the scene's REAL
-                if tmax.dtype != tdt or tmax.numel() not in (1, n):
-                    raise ValueError("tmax must be a %s value or (n,) tensor" % tdt)
-            elif tmax is not None:
-                tmax = _tmax_array(tmax, R, n)
-            # The query runs on `qs`.  It first waits for what the caller has queued on the current stream (the inputs were made there),
-            # and everything this call allocates -- copies of the inputs, the results -- comes from qs's pool, so no allocation of another
-            # stream can reuse that memory while the query still uses it.  The caller's own input tensors are marked as used on qs.
-            cur = torch.cuda.current_stream(dev)
-            if stream is None:
-                qs = cur
-            elif isinstance(stream, torch.cuda.Stream):
-                qs = stream
-            else:
-                h = int(stream)
-                qs = torch.cuda.default_stream(dev) if h == 0 else torch.cuda.ExternalStream(h, device=dev)
-            if qs != cur:
-                qs.wait_stream(cur)
-            with torch.cuda.stream(qs):
-                r = rays.contiguous()
-                t = None
-                if isinstance(tmax, torch.Tensor):
-                    t = tmax.to(dev).reshape(-1).expand(n).contiguous()
-                elif tmax is not None:
-                    t = torch.from_numpy(tmax).to(dev)
-                res = tuple(torch.empty((n,) + shape, dtype=tdts[dt], device=dev) for shape, dt in results)
-                ordp = ()
-                if order is not None:
-                    if order is not True:
-                        order = self._order_torch(torch, order, n, dev)
-                    ordp = (None if order is True else C.c_void_p(order.data_ptr()),)
-                rc = call(getattr(capi.lib, entry + "_device"), C.c_void_p(r.data_ptr()), C.c_void_p(t.data_ptr()) if t is not None else None, n,
-                          *ordp, *[C.c_void_p(x.data_ptr()) for x in res], C.c_void_p(qs.cuda_stream), stp)
-            if qs != cur:
-                for x in (rays, tmax, order):
-                    if isinstance(x, torch.Tensor) and x.is_cuda:
-                        x.record_stream(qs)
-            capi.check(rc, entry + "_device")
-        else:
-            if not isinstance(rays, np.ndarray) or rays.dtype != R or rays.ndim != 2 or rays.shape[1] != 6 or rays.shape[0] == 0:
-                raise ValueError("rays must be a non-empty (n, 6) numpy array of %s (or a torch tensor on the scene's device)" % np.dtype(R).name)
-            n = rays.shape[0]
-            rays = np.ascontiguousarray(rays)
-            t = None if tmax is None else _tmax_array(tmax, R, n)
-            specs = [((n,) + shape, R if dt == "R" else dt) for shape, dt in results]
-            if out is None:
-                res = tuple(np.empty(shape, dtype=dt) for shape, dt in specs)
-            else:
-                res = tuple(out)
-                if len(res) != len(specs) or any(a.dtype != dt or a.shape != shape or not a.flags.c_contiguous for a, (shape, dt) in zip(res, specs)):
-                    raise ValueError("out: contiguous arrays of " + ", ".join("%s %s" % (np.dtype(dt).name, shape) for shape, dt in specs))
-            ordp = ()
-            if order is not None:
-                o = None if order is True else self._order_numpy(order, n)
-                ordp = (None if o is None else o.ctypes.data,)
-            rc = call(getattr(capi.lib, entry), rays.ctypes.data, t.ctypes.data if t is not None else None, n, *ordp, *[a.ctypes.data for a in res], stp)
-            capi.check(rc, entry)
-        if want_stats:
-            return res + (st.as_dict(),)
-        return res
+        return self._order_query("rt_ray_order", rays, "rays", 6, None, stream)
 
     def _camera(self, camera):
         cam = np.asarray(camera)
@@ -1784,67 +1406,7 @@ class DeviceScene:
         numpy arrays go through the host entry (out: optional (color, alpha) arrays to fill, e.g. from capi.HostBuffer); a torch tensor on
         this scene's device goes through the device entry on `stream`, with the stream discipline of intersect().  order (None, True or
         indices; rt_trace_rays_ordered*): as for intersect()."""
-        R = _real(self.scene.precision)
-        st = capi.Stats()
-        stp = C.byref(st) if want_stats else None
-        torch = sys.modules.get("torch")
-        if torch is not None and isinstance(rays, torch.Tensor):
-            tdt = torch.float32 if R == np.float32 else torch.float64
-            dev = torch.device("cuda", self.device)
-            if rays.dtype != tdt or rays.dim() != 2 or rays.shape[1] != 6 or rays.shape[0] == 0:
-                raise ValueError("rays must be a non-empty (n, 6) %s tensor" % tdt)
-            if rays.device != dev:
-                raise ValueError("rays must be on %s, not %s" % (dev, rays.device))
-            n = rays.shape[0]
-            cur = torch.cuda.current_stream(dev)
-            if stream is None:
-                qs = cur
-            elif isinstance(stream, torch.cuda.Stream):
-                qs = stream
-            else:
-                h = int(stream)
-                qs = torch.cuda.default_stream(dev) if h == 0 else torch.cuda.ExternalStream(h, device=dev)
-            if qs != cur:
-                qs.wait_stream(cur)
-            with torch.cuda.stream(qs):
-                r = rays.contiguous()
-                color = torch.empty((n, 3), dtype=tdt, device=dev)
-                alpha = torch.empty(n, dtype=tdt, device=dev)
-                if order is None:
-                    rc = capi.lib.rt_trace_rays_device(self._h, C.c_void_p(r.data_ptr()), n, C.c_void_p(color.data_ptr()), C.c_void_p(alpha.data_ptr()),
-                                                       C.c_void_p(qs.cuda_stream), stp)
-                else:
-                    if order is not True:
-                        order = self._order_torch(torch, order, n, dev)
-                    rc = capi.lib.rt_trace_rays_ordered_device(self._h, C.c_void_p(r.data_ptr()), n, None if order is True else C.c_void_p(order.data_ptr()),
-                                                               C.c_void_p(color.data_ptr()), C.c_void_p(alpha.data_ptr()), C.c_void_p(qs.cuda_stream), stp)
-            if qs != cur:
-                rays.record_stream(qs)
-                if isinstance(order, torch.Tensor):
-                    order.record_stream(qs)
-            capi.check(rc, "rt_trace_rays_device" if order is None else "rt_trace_rays_ordered_device")
-        else:
-            if not isinstance(rays, np.ndarray) or rays.dtype != R or rays.ndim != 2 or rays.shape[1] != 6 or rays.shape[0] == 0:
-                raise ValueError("rays must be a non-empty (n, 6) numpy array of %s (or a torch tensor on the scene's device)" % np.dtype(R).name)
-            n = rays.shape[0]
-            rays = np.ascontiguousarray(rays)
-            if out is None:
-                color, alpha = np.empty((n, 3), dtype=R), np.empty(n, dtype=R)
-            else:
-                color, alpha = out
-                for a, shape in ((color, (n, 3)), (alpha, (n,))):
-                    if a.dtype != R or a.shape != shape or not a.flags.c_contiguous:
-                        raise ValueError("out: contiguous %s arrays of shapes (n, 3) and (n,)" % np.dtype(R).name)
-            if order is None:
-                rc = capi.lib.rt_trace_rays(self._h, rays.ctypes.data, n, color.ctypes.data, alpha.ctypes.data, stp)
-            else:
-                o = None if order is True else self._order_numpy(order, n)
-                rc = capi.lib.rt_trace_rays_ordered(self._h, rays.ctypes.data, n, None if o is None else o.ctypes.data, color.ctypes.data,
-                                                    alpha.ctypes.data, stp)
-            capi.check(rc, "rt_trace_rays" if order is None else "rt_trace_rays_ordered")
-        if want_stats:
-            return color, alpha, st.as_dict()
-        return color, alpha
+        return self._ray_query("rt_trace_rays", (), rays, (), order, (((3,), "R"), ((), "R")), out, want_stats, stream)
 
     def render_camera(self, options, camera, regions, want_stats=True, out=None):
         """rt_render_camera: render_tiles through a pinhole camera (REAL[12] = eye, right, up, forward; see look_at) -> (uint8[total_px*4]

@@ -301,6 +301,30 @@ def test_trace_entries_buffers_streams_and_threads_agree():
             np.testing.assert_array_equal(a.view(np.uint8), b.view(np.uint8))
 
 
+@pytest.mark.parametrize("precision", [rta.RT_F32, rta.RT_F64], ids=["f32", "f64"])
+def test_trace_on_a_side_stream_and_on_its_handle_is_the_default_stream_trace(precision):
+    import torch
+    R = np.float32 if precision == rta.RT_F32 else np.float64
+    s = rta.Scene.three_spheres(precision)
+    d = s.device()
+    rng = np.random.default_rng(65)
+    rays = np.concatenate([np.tile(s.eye.astype(np.float64), (65, 1)), rng.normal(size=(65, 3)) * (0.3, 0.3, 0.0) + (0.0, -0.1, 1.0)], axis=1)      # one wave and one lane
+    rays[:, 3:] /= np.linalg.norm(rays[:, 3:], axis=1, keepdims=True)
+    tr = torch.from_numpy(rays.astype(R)).cuda()
+    order = torch.from_numpy(rng.permutation(65).astype(np.int32)).cuda()
+    side = torch.cuda.Stream()
+    assert side != torch.cuda.current_stream()
+    for o in (None, True, order):
+        ref = [a.cpu().numpy().view(np.uint8) for a in d.trace(tr, order=o)]
+        assert ref[1].any()                                                          # some ray hits
+        for stream in (side, side.cuda_stream):
+            got = d.trace(tr * 1.0, stream=stream, order=None if o is None else (o if o is True else o.clone()))      # inputs made on the current stream
+            side.synchronize()
+            for a, b in zip(ref, got):
+                assert b.device.type == "cuda"
+                np.testing.assert_array_equal(a, b.cpu().numpy().view(np.uint8))
+
+
 def test_trace_host_entry_rejects_rays_outside_the_domain():
     d = rta.Scene.three_spheres().device()
     good = np.array([[0, 0, -4, 0, 0, 1]] * 4, dtype=np.float32)

@@ -277,6 +277,37 @@ def test_a_device_update_orders_the_queries_behind_it_on_its_stream(precision):
     host.close(); dev.close()
 
 
+@PRECISIONS
+def test_an_update_on_a_side_stream_and_on_its_handle_is_the_default_stream_update(precision):
+    import torch
+    R = REAL[precision]
+    it0, bd0, rg = rta.pyramid(2, (0.0, -1.0, 0.0), 1.0, precision)
+    rng = np.random.default_rng(65)
+    rays = np.concatenate([np.tile(np.asarray(EYE), (65, 1)), rng.normal(size=(65, 3)) * (0.3, 0.3, 0.0) + (0.0, -0.15, 1.0)], axis=1)      # one wave and one lane
+    rays[:, 3:] /= np.linalg.norm(rays[:, 3:], axis=1, keepdims=True)
+    trays = torch.from_numpy(rays.astype(R)).cuda()
+    d = rta.DeviceScene(scene_of(it0, bd0, rg, precision), dynamic=True)
+    side = torch.cuda.Stream()
+    assert side != torch.cuda.current_stream()
+    it, other = animate(it0, 1, R), animate(it0, 2, R)
+    live = np.array([1, 1, 0, 1, 1], np.uint8)
+    for lv in (None, live):
+        tit, tlv = torch.from_numpy(it).cuda(), None if lv is None else torch.from_numpy(lv).cuda()
+        d.update(tit, live=tlv)
+        ref = [as_bits(a.cpu().numpy()) for a in d.intersect(trays)]
+        ref_bounds = d.bounds()
+        assert (d.intersect(trays)[2] >= 0).any()
+        for stream in (side, side.cuda_stream):
+            d.update(other)
+            d.update(tit * 1.0, live=None if lv is None else tlv.clone(), stream=stream)      # inputs made on the current stream and dropped at once
+            got = d.intersect(trays, stream=stream)
+            side.synchronize()
+            for a, b in zip(ref, got):
+                np.testing.assert_array_equal(a, as_bits(b.cpu().numpy()))
+            np.testing.assert_array_equal(as_bits(d.bounds()), as_bits(ref_bounds))
+    d.close()
+
+
 # ---- 8: status codes ----
 
 def test_status_codes_and_a_refused_update_leaves_the_scene_alone():

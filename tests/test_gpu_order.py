@@ -58,6 +58,24 @@ def check_order(d, rays, what):
 
 
 @pytest.mark.parametrize("precision", [rta.RT_F32, rta.RT_F64], ids=["f32", "f64"])
+def test_ray_order_on_a_side_stream_and_on_its_handle_is_the_default_stream_order(precision):
+    import torch
+    d = rta.Scene.three_spheres(precision).device()
+    rng = np.random.default_rng(65)
+    rays = np.concatenate([rng.normal(size=(65, 3)) * 0.5 + (0.0, 0.0, -4.0), rng.normal(size=(65, 3))], axis=1).astype(REAL[precision])      # one wave and one lane
+    tr = torch.from_numpy(rays).cuda()
+    ref = d.ray_order(tr)
+    torch.cuda.current_stream().synchronize()
+    assert np.array_equal(ref.cpu().numpy(), np.argsort(rta.ray_keys(rays), kind="stable"))
+    side = torch.cuda.Stream()
+    assert side != torch.cuda.current_stream()
+    for stream in (side, side.cuda_stream):
+        got = d.ray_order(tr * 1.0, stream=stream)                             # an input made on the current stream and dropped at once
+        side.synchronize()
+        assert got.dtype == torch.uint32 and got.device.type == "cuda" and np.array_equal(raw(got), raw(ref)), stream
+
+
+@pytest.mark.parametrize("precision", [rta.RT_F32, rta.RT_F64], ids=["f32", "f64"])
 def test_ray_order_is_the_stable_argsort_of_the_key(precision):
     R = REAL[precision]
     s = rta.Scene.default(precision=precision)

@@ -85,6 +85,40 @@ def test_the_sphere_order_is_the_stable_sort_of_the_numpy_keys(precision):
             np.testing.assert_array_equal(t.cpu().numpy().view(np.uint32), want, err_msg="device entry, n = %d" % n)
 
 
+@PRECISIONS
+def test_the_order_and_the_rebuild_on_a_side_stream_and_on_its_handle_are_the_default_stream_ones(precision):
+    import torch
+    side = torch.cuda.Stream()
+    assert side != torch.cuda.current_stream()
+    static = rta.Scene.three_spheres(precision).device()
+    s = spheres_of(65, precision)                                                    # one wave and one lane
+    ts = torch.from_numpy(s).cuda()
+    ref = static.sphere_order(ts)
+    torch.cuda.current_stream().synchronize()
+    np.testing.assert_array_equal(ref.cpu().numpy().view(np.uint32), expected_order(s))
+    for stream in (side, side.cuda_stream):
+        got = static.sphere_order(ts * 1.0, stream=stream)                           # an input made on the current stream and dropped at once
+        side.synchronize()
+        assert got.dtype == torch.uint32 and got.device.type == "cuda"
+        np.testing.assert_array_equal(as_bits(got.cpu().numpy()), as_bits(ref.cpu().numpy()))
+    # a rebuild of the level-2 pyramid from its own spheres, reversed
+    items = rta.pyramid(2, (0.0, -1.0, 0.0), 1.0, precision)[0]
+    back = np.ascontiguousarray(items[::-1])
+    tb = torch.from_numpy(back).cuda()
+    d = dynamic_scene(items, rta.balanced_ranges(len(items), LEAF), precision)
+    ref = d.rebuild(tb)
+    ref_bounds = d.bounds()
+    np.testing.assert_array_equal(ref.cpu().numpy().view(np.uint32), expected_order(back))
+    for stream in (side, side.cuda_stream):
+        d.update(items)                                                              # the caller's order again
+        got = d.rebuild(tb * 1.0, stream=stream)
+        side.synchronize()
+        assert got.dtype == torch.uint32 and got.device.type == "cuda"
+        np.testing.assert_array_equal(as_bits(got.cpu().numpy()), as_bits(ref.cpu().numpy()))
+        np.testing.assert_array_equal(as_bits(d.bounds()), as_bits(ref_bounds))
+    d.close()
+
+
 # ---- 2: a rebuild is the update with the permuted spheres ----
 
 @PRECISIONS
