@@ -854,6 +854,48 @@ rt_status rt_swept_overlaps_device(rt_scene *scene, const void *queries, const v
                                    const uint32_t *order, uint32_t capacity, int32_t *items_out, void *time_out, void *normal_out,
                                    uint64_t *offsets_out, uint64_t *total_out, rt_stats *stats, void *hip_stream);
 
+/* ---- first contacts (additive to ABI 5): each moving outside sphere's EARLIEST contact with the scene during one step ----
+ * rt_swept_overlaps lists every contact of the step: a count walk, a scan and a fill walk.  A caller that steps bodies asks first how far
+ * each body can go before it touches anything, and what it touches -- conservative advancement, a projectile, a particle that stops or
+ * bounces at its first hit, time-of-impact ordering.  rt_sweep_spheres answers that only against a scene that stands still.  This entry
+ * is one walk with one fixed-size result per query: rt_sweep_spheres's shrinking window on rt_swept_overlaps's metric.
+ *   queries (REAL[4n]), qdisp (REAL[3n]), disp (REAL[3 n_items] or NULL: the scene stands still), exclude (int32[n] or NULL) and order
+ * (uint32[n] or NULL) are rt_swept_overlaps's, in layout, rules and meaning.  mode is rt_sweep_spheres's.  The time t of a query against
+ * a stream node is rt_swept_overlaps's, bit for bit: the same formula, the same S -- the queries folded in by index whatever the order --,
+ * the same motion table, the same dead records; q = 0 is a moving point, and a query whose q is not >= 0 carries no query: no test, no
+ * result.
+ *   The walk is rt_swept_overlaps's: from node 0, in stream order.  Every query carries best = 1, found = false, and one predicate serves
+ * both kinds of node:  beats(t) = found ? t < best : t <= best.  A BOUND is entered when its t beats, else its subtree is culled.  An ITEM
+ * whose slot is not the query's exclude and whose t beats becomes the result: best = t, found = true.  The excluded item is tested and
+ * counted as a test, and never becomes the result.  The query is finished as soon as found && best == 0 (a start in contact: nothing
+ * beats it) and, RT_SWEEP_ANY, as soon as found -- some contact of the step, found sooner; its t is that item's, not the earliest.  On
+ * a tie the first item in stream order wins, which is the lowest slot; a contact at exactly t = 1 is found, and a later one at t = 1
+ * does not replace it.  The result is the walk's, as for every query here.  In RT_SWEEP_NEAREST it is the smallest t of the query's
+ * rt_swept_overlaps row at its lowest slot wherever no bound's t lies within rounding of an item's below it; a result exists exactly
+ * where that row is not empty.
+ *   time_out (REAL[n]): best, or +inf when nothing was found or no query was carried.  item_out (int32[n] or NULL): the slot, or -1.
+ * normal_out (REAL[3n] or NULL): rt_swept_overlaps's normal of that (query, item) at best -- rust_tracer_amd.swept_normals restates it,
+ * NaN where the centres coincide at t = 0 -- and {0, 0, 0} when there is no result.  The bytes and the counters are the same in every
+ * order.  stats (may be NULL): primary = queries carried, hits = queries with a result, sphere_tests / bound_tests / tests_executed,
+ * every other counter 0; asking for it runs the counting flavour (same bytes).
+ *   The motion table and the magnitude word are rt_swept_overlaps's: a first-contacts call takes its turn with the overlap and swept
+ * calls on its scene (and never waits for a contacts or impacts call); it brings no counts, and the list workspace does not grow for it. */
+/* Host memory.  RT_ERR_INVALID_ARGUMENT before the device is touched for a NULL scene, queries, qdisp or time_out, an unknown mode,
+ * n == 0, a misaligned buffer (item_out, exclude, order 4 bytes; queries, qdisp, disp, time_out, normal_out REAL), a buffer in device
+ * memory, a centre, qdisp or disp component that is not finite or beyond +-1e15, a q that is NaN, negative, infinite or above 1e15, and
+ * an order that is no permutation of 0 .. n-1.  Pinned memory is used in place, pageable memory goes through the call's device
+ * workspace.  Returns when the results are in place.  The call is a READ in the sense of ORDER above, on static, dynamic, live and flat
+ * scenes alike. */
+rt_status rt_first_contacts(rt_scene *scene, rt_sweep mode, const void *queries, const void *qdisp, uint32_t n, const void *disp, const int32_t *exclude,
+                            const uint32_t *order, void *time_out, int32_t *item_out, void *normal_out, rt_stats *stats);
+/* The same over DEVICE memory, enqueued on `hip_stream` without a host synchronisation: only pointers, alignment, n and the mode are
+ * checked.  An order entry >= n carries no query and leaves that thread's outputs alone; a query that no thread carries keeps the
+ * caller's bytes, and still counts for S.  Any input bits end the walk without a fault.  A call goes behind the overlap, swept or
+ * first-contacts call before it, whichever stream that was on.  stats != NULL: filled after an internal synchronisation of hip_stream. */
+rt_status rt_first_contacts_device(rt_scene *scene, rt_sweep mode, const void *queries, const void *qdisp, uint32_t n, const void *disp,
+                                   const int32_t *exclude, const uint32_t *order, void *time_out, int32_t *item_out, void *normal_out, rt_stats *stats,
+                                   void *hip_stream);
+
 /* Bytes rt_render_tiles writes for this tile list (4 * total area), or 0 on an invalid list. */
 uint64_t rt_tiles_rgba_bytes(const rt_region *tiles, uint32_t n_tiles);
 

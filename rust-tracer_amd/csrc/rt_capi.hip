@@ -24,6 +24,7 @@
 #include "rt_overlap.hpp"
 #include "rt_impacts.hpp"
 #include "rt_swept.hpp"
+#include "rt_first.hpp"
 #include "rt_order.hpp"
 #include "rt_dynamic.hpp"
 #include "rt_rebuild.hpp"

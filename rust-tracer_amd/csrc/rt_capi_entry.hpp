@@ -1350,6 +1350,45 @@ rt_status rt_swept_overlaps(rt_scene *s, const void *queries, const void *qdisp,
         });
 }
 
+// ---- first contacts: the earliest contact of each moving outside sphere with the scene during one step (rt_first.hpp) ----
+
+rt_status rt_first_contacts_device(rt_scene *s, rt_sweep mode, const void *queries, const void *qdisp, uint32_t n, const void *disp, const int32_t *exclude,
+                                   const uint32_t *order, void *time_out, int32_t *item_out, void *normal_out, rt_stats *stats, void *hip_stream)
+{
+    const char *const what = "rt_first_contacts_device";
+    if (!first_args_ok(s, mode, queries, qdisp, n, disp, exclude, order, time_out, item_out, normal_out, what)) return RT_ERR_INVALID_ARGUMENT;
+    // first-contact calls take their turn with overlap and swept calls: they use the swept entry's motion table
+    return device_query(s, stats, static_cast<hipStream_t>(hip_stream), [&](const void *nodes, uint32_t n_nodes, rt::Counters *counters, hipStream_t stream) {
+        return enqueue_first(s, nodes, n_nodes, mode, queries, qdisp, n, disp, exclude, order, time_out, item_out, normal_out, counters, stream);
+    });
+}
+
+rt_status rt_first_contacts(rt_scene *s, rt_sweep mode, const void *queries, const void *qdisp, uint32_t n, const void *disp, const int32_t *exclude,
+                            const uint32_t *order, void *time_out, int32_t *item_out, void *normal_out, rt_stats *stats)
+{
+    const char *const what = "rt_first_contacts";
+    if (!first_args_ok(s, mode, queries, qdisp, n, disp, exclude, order, time_out, item_out, normal_out, what)) return RT_ERR_INVALID_ARGUMENT;
+    const bool f32 = s->precision == RT_F32;
+    const size_t esz = f32 ? sizeof(float) : sizeof(double);
+    HostStaging::Row rows[] = { { queries, 4 * esz * (size_t)n, kStageIn }, { qdisp, 3 * esz * (size_t)n, kStageIn }, { disp, 3 * esz * (size_t)s->n_items, kStageIn },
+                                { exclude, sizeof(int32_t) * (size_t)n, kStageIn }, { order, sizeof(uint32_t) * (size_t)n, kStageIn },
+                                { time_out, esz * (size_t)n, kStageOut }, { item_out, sizeof(int32_t) * (size_t)n, kStageOut },
+                                { normal_out, 3 * esz * (size_t)n, kStageOut } };
+    HostStaging hs(rows);
+    if (rt_status pst = hs.plan(what); pst != RT_OK) return pst;
+    if (!(f32 ? overlap_queries_valid(static_cast<const float *>(queries), n, what) : overlap_queries_valid(static_cast<const double *>(queries), n, what)))
+        return RT_ERR_INVALID_ARGUMENT;
+    if (!(f32 ? swept_qdisp_valid(static_cast<const float *>(qdisp), n, what) : swept_qdisp_valid(static_cast<const double *>(qdisp), n, what)))
+        return RT_ERR_INVALID_ARGUMENT;
+    if (order && !order_is_permutation(order, n, what)) return RT_ERR_INVALID_ARGUMENT;
+    if (disp && !(f32 ? impacts_disp_valid(static_cast<const float *>(disp), s->n_items, what) : impacts_disp_valid(static_cast<const double *>(disp), s->n_items, what)))
+        return RT_ERR_INVALID_ARGUMENT;
+    return host_query(s, hs, stats, read_query_stats, no_pre_step, [&](const void *nodes, uint32_t n_nodes, rt::Counters *counters, hipStream_t stream) {
+        return enqueue_first(s, nodes, n_nodes, mode, hs.dev(0), hs.dev(1), n, hs.dev(2), hs.dev<const int32_t>(3), hs.dev<const uint32_t>(4), hs.dev(5),
+                             hs.dev<int32_t>(6), hs.dev(7), counters, stream);
+    });
+}
+
 // ---- traced rays and camera frames: Renderer::raytrace for any ray, render_region for any pinhole camera (rt_trace.hpp) ----
 
 static rt_status trace_rays_device(rt_scene *s, const void *rays, uint32_t n, void *color_out, void *alpha_out, bool ordered, const uint32_t *order,

@@ -1407,6 +1407,75 @@ rt_status enqueue_swept_fill(const rt_scene *s, const void *nodes, uint32_t n_no
                                   : enqueue_swept_fill<double>(s, nodes, n_nodes, queries, qdisp, n, exclude, order, capacity, items, time, normal, stream);
 }
 
+// ---- first contacts (rt_first_contacts*, rt_first.hpp) ----
+
+// What both first-contact entries check (device pointers are not dereferenced here).
+bool first_args_ok(const rt_scene *s, rt_sweep mode, const void *queries, const void *qdisp, uint32_t n, const void *disp, const int32_t *exclude,
+                   const uint32_t *order, const void *time, const int32_t *item, const void *normal, const char *what)
+{
+    if (!s) { snprintf(g_err, sizeof g_err, "%s: NULL scene", what); return false; }
+    if (mode != RT_SWEEP_NEAREST && mode != RT_SWEEP_ANY) { snprintf(g_err, sizeof g_err, "%s: unknown mode %d (nearest is 0, any is 1)", what, (int)mode); return false; }
+    if (!queries) { snprintf(g_err, sizeof g_err, "%s: NULL queries", what); return false; }
+    if (!qdisp) { snprintf(g_err, sizeof g_err, "%s: NULL qdisp", what); return false; }
+    if (!time) { snprintf(g_err, sizeof g_err, "%s: NULL time_out", what); return false; }
+    if (n == 0) { snprintf(g_err, sizeof g_err, "%s: n == 0", what); return false; }
+    const struct { const void *p; const char *name; } words[] = { { item, "item_out" }, { exclude, "exclude" }, { order, "order" } };
+    for (const auto &w : words)
+        if ((reinterpret_cast<uintptr_t>(w.p) & 3u) != 0) { snprintf(g_err, sizeof g_err, "%s: %s must be 4-byte aligned", what, w.name); return false; }
+    const uintptr_t esz = s->precision == RT_F32 ? sizeof(float) : sizeof(double);
+    const struct { const void *p; const char *name; } reals[] = { { queries, "queries" }, { qdisp, "qdisp" }, { disp, "disp" }, { time, "time_out" }, { normal, "normal_out" } };
+    for (const auto &w : reals)
+        if ((reinterpret_cast<uintptr_t>(w.p) % esz) != 0) { snprintf(g_err, sizeof g_err, "%s: %s must be %u-byte aligned", what, w.name, (unsigned)esz); return false; }
+    return true;
+}
+
+template <typename T, bool COUNT>
+void launch_first(dim3 grid, dim3 block, hipStream_t stream, bool any, const rt::FirstArgs<T> &a)
+{
+    if (any) hipLaunchKernelGGL((rt::k_first_contacts<T, COUNT, true>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((rt::k_first_contacts<T, COUNT, false>), grid, block, 0, stream, a);
+}
+
+// The queries' magnitude, the motion table and the one walk on `stream`, in the swept entry's table.  counters != NULL runs the counting
+// flavour (same bytes).  Under s->overlap.mu, behind swept_begin.
+template <typename T>
+rt_status enqueue_first(const rt_scene *s, const void *nodes, uint32_t n_nodes, rt_sweep mode, const void *queries, const void *qdisp, uint32_t n, const void *disp,
+                        const int32_t *exclude, const uint32_t *order, void *time, int32_t *item, void *normal, rt::Counters *counters, hipStream_t stream)
+{
+    const ImpactsSpace<T> w = motion_table_space<T>(s->d_swept, s->swept_cap);
+    const rt::Node<T> *const st = static_cast<const rt::Node<T> *>(nodes);
+    HIP_TRY(hipMemsetAsync(w.magnitude, 0, sizeof(T), stream));
+    hipLaunchKernelGGL(rt::k_swept_query_magnitude<T>, dim3((unsigned)(((uint64_t)n + 255) / 256)), dim3(256), 0, stream, static_cast<const T *>(queries),
+                       static_cast<const T *>(qdisp), n, w.magnitude);
+    HIP_TRY(hipGetLastError());
+    if (const rt_status mt = enqueue_motion_table<T>(s, st, n_nodes, static_cast<const T *>(disp), w, stream); mt != RT_OK) return mt;
+    const rt::FirstArgs<T> a{ st, w.motion, w.magnitude, static_cast<const T *>(queries), static_cast<const T *>(qdisp), exclude, order, static_cast<T *>(time), item,
+                              static_cast<T *>(normal), counters, n_nodes, n };
+    const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
+    if (counters) launch_first<T, true>(grid, block, stream, mode == RT_SWEEP_ANY, a);
+    else launch_first<T, false>(grid, block, stream, mode == RT_SWEEP_ANY, a);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+// One first-contacts call's place among the overlap and swept calls of its scene, and its kernels: under s->overlap.mu it goes behind
+// the call before it (swept_begin; it brings no counts, so the list workspace does not grow for it), uses the swept entry's motion table,
+// and leaves the event the next call waits for -- host calls too: the outputs are the call's own, only the table is shared, so the call
+// need not hold the mutex until its stream is drained.
+rt_status enqueue_first(rt_scene *s, const void *nodes, uint32_t n_nodes, rt_sweep mode, const void *queries, const void *qdisp, uint32_t n, const void *disp,
+                        const int32_t *exclude, const uint32_t *order, void *time, int32_t *item, void *normal, rt::Counters *counters, hipStream_t stream)
+{
+    std::lock_guard<std::mutex> lk(s->overlap.mu);
+    rt_status st = swept_begin(s, 0u, n_nodes, stream);
+    if (st != RT_OK) return st;
+    st = s->precision == RT_F32 ? enqueue_first<float>(s, nodes, n_nodes, mode, queries, qdisp, n, disp, exclude, order, time, item, normal, counters, stream)
+                                : enqueue_first<double>(s, nodes, n_nodes, mode, queries, qdisp, n, disp, exclude, order, time, item, normal, counters, stream);
+    // whatever was enqueued uses the table: the next call goes behind it
+    if (hipEventRecord(s->overlap.ev, stream) == hipSuccess) s->overlap.recorded = true;
+    else { (void)hipGetLastError(); (void)hipStreamSynchronize(stream); }
+    return st;
+}
+
 // ---- traced rays and camera frames (rt_trace_rays*, rt_render_camera*, rt_trace.hpp) ----
 
 // The camera domain both rt_render_camera entries check (in double, before the device is touched): 12 finite values, |eye coordinate|

@@ -1151,20 +1151,23 @@ class DeviceScene:
         capi.check(rc, "rt_render_frame_device")
         return st.as_dict() if want_stats else None
 
-    def _fixed_query(self, entry, x, name, cols, names, values, exclude, order, true_ok, specs, out, want_stats, stream, layout):
+    def _fixed_query(self, entry, x, name, cols, names, values, exclude, order, true_ok, specs, out, want_stats, stream, layout, rows=()):
         """The body of every query with one fixed-size result per query: `entry` (host side) or `entry`_device is called with the scene and
         layout(x, reals, n, exclude, order, results, stats, stream) -- pointers, or NULL for None; reals and results are lists; stream is
         () on the host side and the 1-tuple of the stream on the device side -- and the results come back as a tuple[, stats dict].
         x: the main input, `name`, n x cols of the scene's REAL, whose memory kind chooses the side.  names, values: the per-query reals,
-        each one value, (n,) REAL or None.  exclude: int32[n] or None.  order: None or uint32[n]; True passes as NULL where true_ok.
-        specs: (shape behind n, dtype) of each result, "R" for the scene's REAL; out: such arrays or tensors to fill, or None."""
+        each one value, (n,) REAL or None.  rows: further inputs with rows of REAL, each (array, name, cols, _N or _ITEMS, optional) as
+        _list_query takes them; their pointers follow the per-query reals' in `reals`.  exclude: int32[n] or None.  order: None or
+        uint32[n]; True passes as NULL where true_ok.  specs: (shape behind n, dtype) of each result, "R" for the scene's REAL; out: such
+        arrays or tensors to fill, or None."""
         side = self._side(x)
         st = capi.Stats()
         stp = C.byref(st) if want_stats else None
-        with side.scope(self, stream, (x, exclude, order, *values, *(() if out is None else out))) as tail:
+        with side.scope(self, stream, (x, exclude, order, *values, *[r[0] for r in rows], *(() if out is None else out))) as tail:
             x = side.real_rows(x, name, cols)
             n = x.shape[0]
             reals = [side.per_query(v, what, n) for what, v in zip(names, values)]
+            reals += [side.real_rows(y, what, c, n if count is _N else self.scene.items.shape[0], optional) for y, what, c, count, optional in rows]
             ex = side.exclude(exclude, n)
             o = None if order is None or (order is True and true_ok) else side.order(order, n)
             if out is None:
@@ -1386,6 +1389,28 @@ class DeviceScene:
                                 (("queries", 4, None, False), ("qdisp", 3, _N, False), ("disp", 3, _ITEMS, True)), exclude, order, capacity,
                                 (True, times, normals), (((), np.int32), ((), "R"), ((3,), "R")), offsets, stats, stream,
                                 "the queries have %d entries", lambda xs, n, ex, o: (xs[0], xs[1], n, xs[2], ex, o))
+
+    def first_contacts(self, queries, qdisp, disp=None, any_hit=False, exclude=None, order=None, normals=False, stats=False, stream=None, out=None):
+        """rt_first_contacts / rt_first_contacts_device: the earliest contact of each moving query sphere of `queries` (n x 4: px, py, pz, q;
+        query g is at p + t qdisp[g] for t in [0, 1], `qdisp`: n x 3) with the scene while sphere k of the scene moves from c_k to c_k +
+        disp[k] (`disp`: n_items x 3, or None: the scene stands still) -- all as swept_overlaps() takes them -> (time[n], item[n][,
+        normal[n, 3]][, stats dict]).  There is no metric of its own: swept_times and swept_normals already are the definition -- time is
+        swept_times of the (query, item) returned, normal (normals=True) its swept_normals (NaN where the centres coincide at t = 0) --
+        and the result is the smallest time of the query's swept_overlaps row, at its lowest slot.  A query that touches nothing during
+        the step, or whose q is not >= 0, reads +inf, -1 and a zero normal; q = 0 is a moving point.  any_hit=False (RT_SWEEP_NEAREST):
+        the earliest contact, equal times to the first item in DFS order; a query in contact at its start reads 0 and ends its walk
+        there.  any_hit=True (RT_SWEEP_ANY): some contact of the step, found sooner.  exclude (int32[n]): the item slot each query never
+        returns -- np.arange(n) with the scene's own items, their `disp` as `qdisp`, for the scene against itself; -1 or a slot outside
+        the scene excludes nothing.  A dead slot of a dynamic scene is never returned.  numpy arrays go through the host entry, a torch
+        tensor on this scene's device through the device entry on `stream`, with the stream discipline of intersect(); out: optional
+        (time, item[, normal]) arrays / tensors to fill.  order (uint32[n]): lane j carries query order[j]; the results and counters are
+        the same bytes whatever the order, only the time differs.  The host entry wants a permutation; through the device entry an index
+        >= n carries no query and leaves that thread's outputs alone."""
+        mode = capi.RT_SWEEP_ANY if any_hit else capi.RT_SWEEP_NEAREST
+        specs = (((), "R"), ((), np.int32)) + ((((3,), "R"),) if normals else ())
+        return self._fixed_query("rt_first_contacts", queries, "queries", 4, (), (), exclude, order, False, specs, out, stats, stream,
+                                 lambda x, r, n, ex, o, res, st, stream: (mode, x, r[0], n, r[1], ex, o, *res, *((None,) if not normals else ()), st, *stream),
+                                 rows=((qdisp, "qdisp", 3, _N, False), (disp, "disp", 3, _ITEMS, True)))
 
     def ray_order(self, rays, stream=None):
         """rt_ray_order / rt_ray_order_device: the coherent order of `rays` (n x 6, the scene's REAL dtype), computed on the device -> uint32[n],
