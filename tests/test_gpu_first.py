@@ -29,8 +29,9 @@ class FirstWalker(Walker):
     metric (rta.swept_times / rta.swept_normals over the node records), with the window that shrinks -- best = 1, found = False, and
     beats(t) = t < best if found else t <= best for bounds and items alike."""
 
-    def first(self, queries, qdisp, disp=None, exclude=None, any_hit=False, table=None):
-        """(time REAL[n], item int32[n], normal REAL[n, 3], counters); table: motion()'s, or another."""
+    def first(self, queries, qdisp, disp=None, exclude=None, any_hit=False, table=None, S=None):
+        """(time REAL[n], item int32[n], normal REAL[n, 3], counters); table: motion()'s, or another; S: the call's scale where it is not
+        scale() of the queries given -- queries that count for S and that nobody carries."""
         R = self.R
         queries, qdisp = np.asarray(queries, R), np.asarray(qdisp, R)
         n, n_nodes = len(queries), len(self.bound)
@@ -41,7 +42,7 @@ class FirstWalker(Walker):
         time, item, normal = np.full(n, np.inf, R), np.full(n, -1, np.int32), np.zeros((n, 3), R)
         tests_items = tests_bounds = 0
         if n_nodes:
-            S = self.scale(queries, qdisp, disp, (e, E))
+            S = self.scale(queries, qdisp, disp, (e, E)) if S is None else S
             tm = rta.swept_times(queries, qdisp, records, e, E, S)
             nm = rta.swept_normals(queries, qdisp, records, e, E, S)
         for g in range(n):
@@ -538,3 +539,142 @@ def test_the_host_entry_refuses_motions_outside_its_domain_and_a_short_disp():
     assert err.value.status == capi.RT_ERR_INVALID_ARGUMENT and "mode" in str(err.value)
     assert (d.first_contacts(queries, qdisp)[1] >= 0).any()                       # ... and the scene answers the next call
     d.close()
+
+
+FAR = (1e15, 2.0 ** 72)
+
+
+@PRECISIONS
+@ANY
+def test_a_far_query_that_nobody_carries_still_sets_the_scale(precision, any_hit):
+    """S is folded by query index, whatever the order (tests/test_gpu_swept.py's test of the same name, for this entry): the last query
+    lies far away, the device entry's `order` has a hole exactly for it, and the other queries get the bytes of the walk at the far S.
+    At 1e15 (S = 2^-50) that changes one entry of the swept lists of these inputs in f32 and none that is a row's first or smallest, so
+    only the counters tell the far S from the near one; at 2^72 -- the device entry checks no values, and the walk is defined for any
+    bits -- seven of the 79 results are other items in f32, and the test requires that the GPU's are not the near ones.  (f64: both are
+    exact scalings of a unit scene, the same bits.)  The same query with q = -1 neither counts nor walks: the near bytes come back."""
+    import torch
+    from tests.test_gpu_swept import far_query_inputs
+    for x in FAR:
+        s, far, far_d, disp, sub, S_far, S_near = far_query_inputs(precision, x)
+        d = rta.DeviceScene(s)
+        w = FirstWalker(s)
+        n = len(far)
+        want, near = w.first(sub, far_d, disp, any_hit=any_hit, S=S_far), w.first(sub, far_d, disp, any_hit=any_hit)
+        differ = bool((want[1] != near[1]).any() or (bits(want[0], w.R) != bits(near[0], w.R)).any())
+        assert differ == (precision == rta.RT_F32 and x != 1e15), (x, differ)
+        assert (want[3] != near[3]) == (precision == rta.RT_F32), x              # (f32: the two walks differ in their tests at 1e15 already)
+        order = np.arange(n, dtype=np.int32)
+        order[n - 1] = n                                                         # nobody carries the far query
+        dev = [torch.from_numpy(a).cuda() for a in (far, far_d, disp)]
+        got = d.first_contacts(*dev, any_hit=any_hit, order=torch.from_numpy(order).cuda(), normals=True, stats=True)
+        time, item, normal = (a.cpu().numpy()[:n - 1] for a in got[:3])          # (the thread without a query leaves its outputs alone)
+        same_bytes((want[0][:n - 1], want[1][:n - 1], want[2][:n - 1]), (time, item, normal))
+        assert counters(got[3]) == want[3] and want[3]["primary"] == n - 1 and want[3]["hits"] > 0, x
+        if differ:
+            assert not (np.array_equal(item, near[1][:n - 1]) and np.array_equal(bits(time, w.R), bits(near[0][:n - 1], w.R))), x
+        gone = d.first_contacts(*(torch.from_numpy(a).cuda() for a in (sub, far_d, disp)), any_hit=any_hit, normals=True, stats=True)
+        same_bytes(near[:3], gone[:3])
+        assert counters(gone[3]) == near[3] and gone[1].cpu().numpy()[-1] == -1, x
+        d.close()
+
+
+LINES = [(rta.RT_F32, 65537), (rta.RT_F64, 1025)]
+
+
+@pytest.mark.parametrize("precision,n", LINES, ids=["f32-65537", "f64-1025"])
+def test_a_line_of_spheres_under_as_many_queries(precision, n):
+    """tests/test_gpu_swept.py's line under from_spheres_balanced(leaf_size=4), as a dynamic scene -- whose bounds are refit from the items:
+    the topology alone has none, and a static scene made from it is walked flat -- so the winning node's index passes 2^16 in a real
+    hierarchy and the root's subtree spans hundreds of chunks of the motion table.  Every coordinate is a multiple of 0.5 below 2^17, so
+    all differences are exact and a query meets only the spheres within two places of its own.  Standing scene: query g touches item g at R(3) / R(4.5) with the normal (0, 1, 0) -- v = (0, -2),
+    w = (0, -1.5): a = 2.25, b = 3, cc = 3, disc = 2.25, all exact.  Moving scene: rta.swept_times over each query's five neighbours, the
+    smallest time at the lowest slot (ANY: the lowest slot that touches), with rta.swept_normals' normal; no result where none touches."""
+    from tests.test_gpu_swept import line
+    R = REAL[precision]
+    sp, disp, queries, qdisp = line(n, precision)
+    d = rta.DeviceScene(rta.Scene.from_spheres_balanced(sp, leaf_size=4, precision=precision), 0, True)
+    assert len(d.bounds()) > n // 4 and (d.bounds()[:, 3] > 0).all()
+    for any_hit in (False, True):
+        time, item, normal = d.first_contacts(queries, qdisp, None, any_hit=any_hit, normals=True)
+        assert (item == np.arange(n)).all() and (bits(time, R) == bits(R(3.0) / R(4.5), R)).all() and (normal == np.array([0, 1, 0], R)).all(), any_hit
+        S = rta.impact_scale(sp, disp, queries, qdisp)
+        want_t, want_i, want_n = np.empty(n, R), np.empty(n, np.int32), np.empty((n, 3), R)
+        for lo in range(0, n, 256):
+            hi = min(n, lo + 256)
+            a, b = max(0, lo - 2), min(n, hi + 2)
+            t = rta.swept_times(queries[lo:hi], qdisp[lo:hi], sp[a:b], disp[a:b], None, S)
+            nm = rta.swept_normals(queries[lo:hi], qdisp[lo:hi], sp[a:b], disp[a:b], None, S)
+            k = np.argmax(t <= 1, axis=1) if any_hit else np.argmin(t, axis=1)  # (both: the first of equals)
+            rows = np.arange(hi - lo)
+            some = t[rows, k] <= 1
+            want_t[lo:hi], want_i[lo:hi], want_n[lo:hi] = np.where(some, t[rows, k], R(np.inf)), np.where(some, k + a, -1), np.where(some[:, None], nm[rows, k], R(0.0))
+        time, item, normal = d.first_contacts(queries, qdisp, disp, any_hit=any_hit, normals=True)
+        np.testing.assert_array_equal(item, want_i, err_msg=str(any_hit))
+        np.testing.assert_array_equal(bits(time, R), bits(want_t, R), err_msg=str(any_hit))
+        np.testing.assert_array_equal(bits(normal, R), bits(want_n, R), err_msg=str(any_hit))
+        assert (want_i < 0).any() and (want_i >= 0).any()                        # (an odd sphere leaves before its query arrives)
+        if n <= 1025:                                                            # ... and the walker over the refit bounds: the counters too
+            ranges = rta.balanced_ranges(n, 4)
+            w = FirstWalker(scene_of(sp, d.bounds(), ranges, precision))
+            for moving in (None, disp):
+                assert_first(d, w, queries, qdisp, moving, (n, any_hit, moving is not None), any_hit)
+    d.close()
+
+
+def hand_waves(R):
+    """name -> (queries, qdisp, balanced, sphere_tests (NEAREST, ANY) or None) over 300 spheres of radius 1 at (10 k, 0, 0) -- but item 101,
+    which is a copy of item 100 --, for one wave of 64 queries of radius 0.25 that move by (0.5, 0, 0): towards the items behind them,
+    away from those in front, whose tm is +inf."""
+    lane = np.arange(64)
+    col = lambda x, y: np.stack([x, y, np.zeros(64), np.full(64, 0.25)], axis=1).astype(R)
+    qdisp = np.tile(np.array([0.5, 0.0, 0.0], R), (64, 1))
+    at_zero = col(0.1 + 0.01 * lane, 0.01 * lane)                                # all in contact with item 0 at the start
+    own = col(10.0 * lane + 0.1, 0.01 * lane)                                    # lane k in contact with item k only
+    alone = at_zero.copy()
+    alone[63] = (2985.0, 5.0, 0.0, 0.25)                                         # beside the far end of the line ...
+    away = qdisp.copy()
+    away[63] = (0.0, 1.0, 0.0)                                                   # ... and leaving: it touches nothing
+    twins = col(996.0 - 0.01 * lane, 0.01 * lane)                                # 4 in front of items 100 and 101, which are one sphere ...
+    reach = np.tile(np.array([6.0, 0.0, 0.0], R), (64, 1))                       # ... met at the same time inside the step: the lower slot
+    every = sum(k + 1 for k in range(64))
+    return {"all at item 0": (at_zero, qdisp, False, (64, 64)), "lane k at item k": (own, qdisp, False, (every, every)),
+            "one lane awake": (alone, away, False, (63 + 300, 63 + 300)), "one lane awake, balanced": (alone, away, True, None),
+            "twins": (twins, reach, False, (64 * 300, 64 * 101))}
+
+
+@PRECISIONS
+@ANY
+def test_hand_built_waves_finish_where_the_walk_says(precision, any_hit):
+    """One wave on a scene of 300 items without bounds, FirstWalker the reference and the counters in closed form: (a) 64 queries that all
+    start in contact with item 0 -- the whole wave finishes at node 0 after 64 tests; (b) lane k in contact with item k only, +inf against
+    the items before it -- sum (k + 1) tests, the wave loses a lane at every node; (c) 63 lanes as in (a) and one that touches nothing --
+    one lane awake among 63 finished, 63 + 300 tests; (d) as (c) under balanced ranges with refit bounds, where the lone lane culls and its
+    `resume` lies behind the node the others finish on (it stands inside the root, culls the half the others walk down, and walks the
+    other half alone): the walker's counters; (e) 64 lanes that move by (6, 0, 0) and meet items 100 and 101, two copies of one sphere,
+    at the same time inside the step -- the lower slot is the result, NEAREST tests all 300 items and ANY stops at the first.  The
+    flavour without counters gives the same bytes."""
+    R = REAL[precision]
+    items = np.zeros((300, 4), R)
+    items[:, 0], items[:, 3] = 10.0 * np.arange(300), 1.0
+    items[101] = items[100]
+    flat = rta.Scene(items, rta.normalized(LIGHT, precision), EYE, precision=precision)
+    ranges = rta.balanced_ranges(len(items), 4)
+    balanced = scene_of(items, rta.refit_bounds(items, ranges, precision), ranges, precision)
+    for name, (queries, qdisp, tree, tests) in hand_waves(R).items():
+        s = balanced if tree else flat
+        d = rta.DeviceScene(s)
+        w = FirstWalker(s)
+        time, item, normal, st = assert_first(d, w, queries, qdisp, None, (name, any_hit), any_hit)
+        if tests is not None:
+            assert st["sphere_tests"] == tests[any_hit] and st["bound_tests"] == 0, (name, st)
+        else:
+            assert 0 < st["bound_tests"] and st["sphere_tests"] < 63 + 300, (name, st)
+        if name == "lane k at item k":
+            assert (item == np.arange(64)).all() and (time == 0).all(), name
+        elif name == "twins":
+            assert (item == 100).all() and (time > 0).all() and (time < 1).all(), name
+        else:
+            assert (item[:63] == 0).all() and (time[:63] == 0).all() and (item[63] == (0 if name == "all at item 0" else -1)), name
+        same_bytes((time, item, normal), d.first_contacts(queries, qdisp, None, any_hit=any_hit, normals=True))
+        d.close()

@@ -37,8 +37,9 @@ class Walker(ImpactWalker):
         e, _ = self.table(disp) if table is None else table
         return rta.impact_scale(self.spheres[self.n_items:], e, queries, qdisp)
 
-    def all(self, queries, qdisp, disp=None, exclude=None, table=None):
-        """(items int32[m], times REAL[m], normals REAL[m, 3], offsets uint64[n + 1], counters); table: motion()'s, or another."""
+    def all(self, queries, qdisp, disp=None, exclude=None, table=None, S=None):
+        """(items int32[m], times REAL[m], normals REAL[m, 3], offsets uint64[n + 1], counters); table: motion()'s, or another; S: the
+        call's scale where it is not scale() of the queries given -- queries that count for S and that nobody carries."""
         R = self.R
         queries, qdisp = np.asarray(queries, R), np.asarray(qdisp, R)
         n, n_nodes = len(queries), len(self.bound)
@@ -49,7 +50,7 @@ class Walker(ImpactWalker):
         items, times, normals, counts = [], [], [], np.zeros(n, np.uint64)
         tests_items = tests_bounds = 0
         if n_nodes:
-            S = self.scale(queries, qdisp, disp, (e, E))
+            S = self.scale(queries, qdisp, disp, (e, E)) if S is None else S
             tm = rta.swept_times(queries, qdisp, records, e, E, S)
             nm = rta.swept_normals(queries, qdisp, records, e, E, S)
         for g in range(n):
@@ -703,6 +704,52 @@ def test_a_lone_far_query_sets_the_scale(precision):
     assert gone[4] == len(want[0]) and counters(gone[5]) == want[4]
     same_bytes(ref[:3], want[:3])                                                # the last row was empty before, too
     assert rows[-1] == 0
+    d.close()
+
+
+def far_query_inputs(precision, x=1e15):
+    """(Scene, queries, qdisp, disp, sub, S_far, S_near) for the tests of "S counts a query nobody carries": refit0 with its slow inputs and
+    the last query at (x, 0, 0, 0.25); sub is the walker's way to say that nobody carries that query (q = -1), S_far the scale with it
+    counted (2^-50 for 1e15) and S_near the scale without it."""
+    R = REAL[precision]
+    s, seed = scenes(precision)["refit0"]
+    w = Walker(s)
+    queries, qdisp = queries_of(s, seed, "slow")
+    disp = scene_disp(s, seed, "slow")
+    far, far_d = queries.copy(), qdisp.copy()
+    far[-1] = (x, 0.0, 0.0, 0.25)
+    far_d[-1] = (-0.5, 0.0, 0.0)
+    sub = far.copy()
+    sub[-1, 3] = -1
+    S_far, S_near = w.scale(far, far_d, disp), w.scale(sub, far_d, disp)
+    assert (S_far == R(2.0 ** -50) or x != 1e15) and S_far < R(2.0 ** -49) and S_near >= R(0.125) and S_near == w.scale(queries, qdisp, disp)
+    return s, far, far_d, disp, sub, S_far, S_near
+
+
+@PRECISIONS
+def test_a_far_query_that_nobody_carries_still_sets_the_scale(precision):
+    """S is folded by query index, whatever the order: the last query lies at 1e15 and the device entry's `order` has a hole exactly for
+    it.  It walks nowhere and lists nothing, and every other row is the walk's at S = 2^-50 -- in f32 other bytes than at the near S, which
+    a magnitude kernel that folded only the carried queries would give."""
+    import torch
+    s, far, far_d, disp, sub, S_far, S_near = far_query_inputs(precision)
+    d = rta.DeviceScene(s)
+    w = Walker(s)
+    n = len(far)
+    want, near = w.all(sub, far_d, disp, S=S_far), w.all(sub, far_d, disp, S=S_near)
+    differ = len(want[0]) != len(near[0]) or (want[0] != near[0]).any() or (bits(want[1], w.R) != bits(near[1], w.R)).any()
+    if precision == rta.RT_F32:                                                   # (f64: 2^-50 is an exact scaling of a unit scene, the same bits)
+        assert differ
+    order = np.arange(n, dtype=np.int32)
+    order[n - 1] = n                                                             # nobody carries the far query
+    kw = dict(times=True, normals=True, offsets=True, stats=True)
+    dev = [torch.from_numpy(x).cuda() for x in (far, far_d, disp)]
+    got = d.swept_overlaps(*dev, order=torch.from_numpy(order).cuda(), **kw)
+    same_bytes(want[:4], got[:4])
+    assert got[4] == len(want[0]) > 0 and counters(got[5]) == want[4] and want[4]["primary"] == n - 1
+    if differ:
+        assert not (len(got[0]) == len(near[0]) and np.array_equal(got[0].cpu().numpy(), near[0]) and
+                    np.array_equal(bits(got[1].cpu().numpy(), w.R), bits(near[1], w.R)))
     d.close()
 
 
