@@ -10,18 +10,18 @@
 // rounding of a pair is defined once.  The pair is a CONTACT when !(gap >= margin).  The dead record of DESIGN.md 4.13 is {0, 0, 0, -inf}:
 // a dead item carries no query and, as a record, is at +inf -- never part of a pair; a dead BOUND culls for every query.
 //
-// The walk is k_near_spheres's in ALL mode (rt_near.hpp) with the scene's items as the queries: lane t carries item slot t, reads its own
-// record from the stream and walks only the part of the stream BEHIND its own node.  Items appear in the stream in ascending slot order, so
-// these are exactly the items j > t: every pair is tested once, from its lower slot.  The stream index is wave-uniform (node records arrive
-// through the scalar cache); a lane sleeps while i < resume, and a lane whose own bound test culls a subtree sets resume = skip.  The wave
-// starts at the smallest resume of its lanes; when no awake lane enters a bound it continues at the smallest resume again -- the skip
-// target, or the first node behind a lane that still sleeps inside that subtree.  The index only grows, so the walk ends.
+// The walk is made of rt_walk.hpp's pieces (centre_gap, bound_step_min) with the scene's items as the queries: lane t carries item slot t,
+// reads its own record from the stream and walks only the part of the stream BEHIND its own node.  Items appear in the stream in ascending
+// slot order, so these are exactly the items j > t: every pair is tested once, from its lower slot.  A lane sleeps while i < resume, and a
+// lane whose own bound test culls a subtree sets resume = skip.  The wave starts at the smallest resume of its lanes; when no awake lane
+// enters a bound it continues at the smallest resume again -- the skip target, or the first node behind a lane that still sleeps inside
+// that subtree.
 //
 // The list is deterministic and compact without an atomic append: the walk runs twice.  The first pass writes one count per item; an
 // exclusive scan turns the counts into offsets; the second pass repeats the walk and writes pair offsets[t] + (rank within t) where that
 // lies below the capacity.  The pairs are sorted by (i, j) by construction, and a capacity that is too small gets the exact prefix.
 #pragma once
-#include "rt_skip.hpp"
+#include "rt_walk.hpp"
 
 namespace rt {
 
@@ -43,7 +43,7 @@ template <typename T, bool COUNT, bool FILL>
 __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(8))) void k_contact_pairs(ContactArgs<T> a)
 {
     static_assert(!(COUNT && FILL), "the counters are the first pass's");
-    const unsigned t = blockIdx.x * kBlockThreads + threadIdx.x;
+    const unsigned t = lane_query(false, nullptr, a.n_items);
     const bool in = t < a.n_items;
     V3<T> p = { T(0.0), T(0.0), T(0.0) };
     T q = T(0.0);
@@ -71,18 +71,11 @@ __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(8
         Node<T> nd = a.stream[i];
         for (;;) {
             const bool active = i >= resume;
-            // rt_near.hpp's gap of the record from the lane's centre, minus the lane's own radius; every operation rounded once
-            const V3<T> v = { nd.a0 - p.x, nd.a1 - p.y, nd.a2 - p.z };
-            const T vv = dot(v, v);
-            T g = inf<T>();
-            if (nd.a3 > T(0.0)) g = (sqrt_rn_lean(vv) - sqrt_rn_lean(nd.a3)) - q;
+            const T g = centre_gap(nd, p, q);                        // the gap above: the lane's own radius comes off
             unsigned ni;
             if (nd.is_bound()) {                                     // BOUND  against the margin
                 const bool cull = active && (g >= margin);
-                if (cull) resume = nd.skip();
-                if (COUNT) c_bounds += active ? 1u : 0u;
-                // nobody enters: every lane's resume now lies behind i -- the skip target, or a sleeping lane's own start inside the subtree
-                ni = (__ballot(active && !cull) == 0) ? wave_min_u32(resume) : i + 1;
+                ni = bound_step_min<COUNT>(active, cull, nd, i, resume, c_bounds);
             } else {                                                 // ITEM   a contact of the lane's item with a later one
                 const bool hit = active && !(g >= margin);
                 if (FILL) {
@@ -103,17 +96,8 @@ __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(8
         }
     }
     if (!FILL && in) a.counts[t] = found;
-    if constexpr (COUNT) {
-        const unsigned long long prim = wave_sum(live ? 1u : 0u), nhit = wave_sum((live && found > 0u) ? 1u : 0u);
-        const unsigned long long its = wave_sum(c_items), bds = wave_sum(c_bounds);
-        if ((threadIdx.x & 63u) == 0u) {
-            Counters *const stripe = a.counters + blockIdx.x % kCounterStripes;
-            atomicAdd(&stripe->primary, prim);
-            atomicAdd(&stripe->hits, nhit);
-            atomicAdd(&stripe->sphere_tests, its);
-            atomicAdd(&stripe->bound_tests, bds);
-        }
-    }
+    if constexpr (COUNT)
+        flush_counters(a.counters, wave_sum(live ? 1u : 0u), wave_sum((live && found > 0u) ? 1u : 0u), wave_sum(c_items), wave_sum(c_bounds));
 }
 
 // The item-to-node table of a scene that was not created dynamic: thread i looks at node i, an ITEM node writes its index.

@@ -7,8 +7,9 @@
 // folds the queries in by index, whatever the order), the same motion table (enqueue_motion_table), the same dead records, q = 0 a moving
 // point, a query whose q is not >= 0 no query at all.
 //
-// The walk is k_swept_overlaps's loop: thread j carries query order[j] from node 0 in stream order, the node index is wave-uniform (stream
-// and motion record arrive through the scalar cache), a lane sleeps while i < resume.  Per lane best = 1, found = false, item = none, and
+// The walk is built as k_swept_overlaps's is, from rt_walk.hpp's pieces (lane_query, swept_time, bound_step_min, and item_step_retire for
+// a lane that is finished): thread j carries query order[j] from node 0 in stream order, stream and motion record arrive through the
+// scalar cache, a lane sleeps while i < resume.  Per lane best = 1, found = false, item = none, and
 // ONE predicate serves both kinds of node:
 //     beats(tm) = found ? tm < best : tm <= best
 // A BOUND is entered when beats, else culled to its skip.  An ITEM whose slot is not the lane's `exclude` and that beats becomes the
@@ -61,15 +62,13 @@ __device__ __forceinline__ Motion<T> motion_alongside(const Motion<T> *motion, u
 template <typename T, bool COUNT, bool ANY>
 __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(8))) void k_first_contacts(FirstArgs<T> a)
 {
-    unsigned gid = blockIdx.x * kBlockThreads + threadIdx.x;
-    if (a.order) gid = gid < a.n ? a.order[gid] : kNever;
+    const unsigned gid = lane_query(a.order != nullptr, a.order, a.n);
     const bool in = gid < a.n;
     const size_t g = in ? gid : 0u;
     const T S = impact_scale(*a.magnitude);      // (wave-uniform)
     V3<T> p = { T(0.0), T(0.0), T(0.0) }, dq = { T(0.0), T(0.0), T(0.0) };
     T q = T(0.0);
-    constexpr unsigned kNone = 0xFFFFFFFFu;
-    unsigned excl = kNone;                       // (an item word's index has 30 bits: kNone and every negative slot match no item)
+    unsigned excl = kNone;
     unsigned resume = kNever;                    // a lane without a query never wakes
     if (in) {
         const T *const rec = a.queries + 4 * g;
@@ -96,33 +95,19 @@ __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(8
         Motion<T> mo = motion_alongside(a.motion, i);
         for (;;) {
             const bool active = i >= resume;
-            // k_swept_overlaps's arithmetic; every operation rounded once
-            const V3<T> v = { nd.a0 * S - p.x, nd.a1 * S - p.y, nd.a2 * S - p.z };
-            const V3<T> w = { dq.x - mo.x, dq.y - mo.y, dq.z - mo.z };
-            const T R = mo.E + q;                                    // ((r' + E') + q')
-            const T RR = R * R;
-            const T qa = dot(w, w), qb = dot(v, w), qc = dot(v, v) - RR;
-            const T disc = qb * qb - qa * qc;
-            T tm = inf<T>();
-            if (nd.a3 > T(0.0)) {
-                if (!(qc > T(0.0))) tm = T(0.0);
-                else if (qb > T(0.0) && !(disc < T(0.0))) tm = qc / (qb + sqrt_rn_lean(disc));
-            }
+            V3<T> v, w;
+            const T tm = swept_time(nd, mo, S, p, dq, q, v, w);      // k_swept_overlaps's
             const bool beats = found ? tm < best : tm <= best;       // (NaN and +inf never do)
             unsigned ni;
             if (nd.is_bound()) {                                     // BOUND  inflated by the largest displacement below it
                 const bool cull = active && !beats;
-                if (cull) resume = nd.skip();
-                if (COUNT) c_bounds += active ? 1u : 0u;
-                // nobody enters: every lane's resume now lies behind i
-                ni = (__ballot(active && !cull) == 0) ? wave_min_u32(resume) : i + 1;
+                ni = bound_step_min<COUNT>(active, cull, nd, i, resume, c_bounds);
             } else {                                                 // ITEM   the earliest so far
                 const bool hit = active && nd.index() != excl && beats;
                 if (COUNT) c_items += active ? 1u : 0u;
                 if (hit) { best = tm; found = true; win = i; }
                 const bool fin = hit && (ANY || tm == T(0.0));       // nothing can beat it (ANY: nothing has to)
-                if (fin) resume = kNever;
-                ni = (__ballot(fin) != 0) ? wave_min_u32(resume == kNever ? kNever : (resume > i ? resume : i + 1)) : i + 1;
+                ni = item_step_retire(fin, i, resume);
             }
             if (ni >= n) break;                                      // also kNever: every lane is done
             i = (unsigned)__builtin_amdgcn_readfirstlane((int)ni);
@@ -138,10 +123,9 @@ __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(8
             const Node<T> nd = a.stream[win];
             slot = nd.index();
             if (a.normal) {                                          // the loop's v and w of that node, then rt_swept.hpp's normal
-                const Motion<T> mo = a.motion[win];
-                const V3<T> v = { nd.a0 * S - p.x, nd.a1 * S - p.y, nd.a2 * S - p.z };
-                const V3<T> w = { dq.x - mo.x, dq.y - mo.y, dq.z - mo.z };
-                u = normalized(V3<T>{ w.x * best - v.x, w.y * best - v.y, w.z * best - v.z });
+                V3<T> v, w;
+                swept_frame(nd, a.motion[win], S, p, dq, v, w);
+                u = swept_normal(v, w, best);
             }
         }
         if (a.item) a.item[g] = slot != kNone ? (int32_t)slot : -1;
@@ -150,17 +134,8 @@ __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(8
             out[0] = u.x; out[1] = u.y; out[2] = u.z;
         }
     }
-    if constexpr (COUNT) {
-        const unsigned long long prim = wave_sum(live ? 1u : 0u), nhit = wave_sum(found ? 1u : 0u);
-        const unsigned long long its = wave_sum(c_items), bds = wave_sum(c_bounds);
-        if ((threadIdx.x & 63u) == 0u) {
-            Counters *const stripe = a.counters + blockIdx.x % kCounterStripes;
-            atomicAdd(&stripe->primary, prim);
-            atomicAdd(&stripe->hits, nhit);
-            atomicAdd(&stripe->sphere_tests, its);
-            atomicAdd(&stripe->bound_tests, bds);
-        }
-    }
+    if constexpr (COUNT)
+        flush_counters(a.counters, wave_sum(live ? 1u : 0u), wave_sum(found ? 1u : 0u), wave_sum(c_items), wave_sum(c_bounds));
 }
 
 }  // namespace rt

@@ -43,9 +43,10 @@
 // single lengths up to the first chunk boundary, whole chunks, single lengths behind the last boundary.  max is exact, so the split cannot
 // show in the bytes.
 //
-// The walk is k_contact_pairs's (rt_contacts.hpp): lane t carries item slot t and walks only the stream behind its own node, the node index
-// is wave-uniform (node and motion record arrive through the scalar cache), and the wave continues at the smallest resume when nobody
-// enters.  Count pass, rt_contacts.hpp's scan, fill pass: the list is sorted by (i, j) and the same bytes every time.
+// The walk is built as k_contact_pairs's is (rt_contacts.hpp) from rt_walk.hpp's pieces -- swept_time is the formula above, bound_step_min
+// the wave's step: lane t carries item slot t and walks only the stream behind its own node, the node's motion record arrives through the
+// scalar cache next to its stream record, and the wave continues at the smallest resume when nobody enters.  Count pass,
+// rt_contacts.hpp's scan, fill pass: the list is sorted by (i, j) and the same bytes every time.
 #pragma once
 #include "rt_contacts.hpp"
 #include "rt_dynamic.hpp"
@@ -91,7 +92,7 @@ template <typename T, bool COUNT, bool FILL>
 __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(8))) void k_impact_pairs(ImpactArgs<T> a)
 {
     static_assert(!(COUNT && FILL), "the counters are the first pass's");
-    const unsigned t = blockIdx.x * kBlockThreads + threadIdx.x;
+    const unsigned t = lane_query(false, nullptr, a.n_items);
     const bool in = t < a.n_items;
     const T S = impact_scale(*a.magnitude);      // (wave-uniform)
     V3<T> p = { T(0.0), T(0.0), T(0.0) }, d = { T(0.0), T(0.0), T(0.0) };
@@ -123,26 +124,13 @@ __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(8
         Motion<T> mo = a.motion[i];
         for (;;) {
             const bool active = i >= resume;
-            // the definition above, one formula for both kinds of node; every operation rounded once
-            const V3<T> v = { nd.a0 * S - p.x, nd.a1 * S - p.y, nd.a2 * S - p.z };
-            const V3<T> w = { d.x - mo.x, d.y - mo.y, d.z - mo.z };
-            const T R = mo.E + q;                                    // ((r_j' + E') + r_i')
-            const T RR = R * R;
-            const T qa = dot(w, w), qb = dot(v, w), qc = dot(v, v) - RR;
-            const T disc = qb * qb - qa * qc;
-            T tm = inf<T>();
-            if (nd.a3 > T(0.0)) {
-                if (!(qc > T(0.0))) tm = T(0.0);
-                else if (qb > T(0.0) && !(disc < T(0.0))) tm = qc / (qb + sqrt_rn_lean(disc));
-            }
+            V3<T> v, w;
+            const T tm = swept_time(nd, mo, S, p, d, q, v, w);       // the definition above, one formula for both kinds of node
             const bool within = tm <= T(1.0);
             unsigned ni;
             if (nd.is_bound()) {                                     // BOUND  inflated by the largest displacement below it
                 const bool cull = active && !within;
-                if (cull) resume = nd.skip();
-                if (COUNT) c_bounds += active ? 1u : 0u;
-                // nobody enters: every lane's resume now lies behind i -- the skip target, or a sleeping lane's own start inside the subtree
-                ni = (__ballot(active && !cull) == 0) ? wave_min_u32(resume) : i + 1;
+                ni = bound_step_min<COUNT>(active, cull, nd, i, resume, c_bounds);
             } else {                                                 // ITEM   an impact of the lane's item with a later one
                 const bool hit = active && within;
                 if (FILL) {
@@ -164,17 +152,8 @@ __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(8
         }
     }
     if (!FILL && in) a.counts[t] = found;
-    if constexpr (COUNT) {
-        const unsigned long long prim = wave_sum(live ? 1u : 0u), nhit = wave_sum((live && found > 0u) ? 1u : 0u);
-        const unsigned long long its = wave_sum(c_items), bds = wave_sum(c_bounds);
-        if ((threadIdx.x & 63u) == 0u) {
-            Counters *const stripe = a.counters + blockIdx.x % kCounterStripes;
-            atomicAdd(&stripe->primary, prim);
-            atomicAdd(&stripe->hits, nhit);
-            atomicAdd(&stripe->sphere_tests, its);
-            atomicAdd(&stripe->bound_tests, bds);
-        }
-    }
+    if constexpr (COUNT)
+        flush_counters(a.counters, wave_sum(live ? 1u : 0u), wave_sum((live && found > 0u) ? 1u : 0u), wave_sum(c_items), wave_sum(c_bounds));
 }
 
 // ---- the motion table ----

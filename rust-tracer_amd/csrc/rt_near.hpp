@@ -10,11 +10,13 @@
 // is to the ray queries.  The guard belongs to the definition: the dead record of DESIGN.md 4.13 is {0, 0, 0, -inf}, whose root would be
 // NaN; with the guard a dead ITEM has gap +inf (never below a cutoff: never listed, never counted) and a dead BOUND culls for every query.
 //
-// The walk is k_multihit_rays's (rt_multihit.hpp) over the same plain per-origin stream: one query per lane, a wave-uniform stream index
-// (node records arrive through the scalar cache), a per-lane `resume`, a jump to the skip target once no live lane wants to enter.  Every
-// slot starts as (rho, -1).  A BOUND culls when gap >= cut: the last slot's gap (CLOSEST) or rho (ALL).  An ITEM with !(gap >= last slot)
-// is inserted behind every slot whose gap is <= its own, so equal gaps keep DFS order; ALL also counts every ITEM with !(gap >= rho).  The
-// query's `exclude` slot is tested and counted as a test, but neither inserted nor counted as found.
+// The walk is k_multihit_rays's (rt_multihit.hpp; the shared pieces are rt_walk.hpp's) over the same plain per-origin stream: one query
+// per lane, a per-lane `resume`, a jump to the skip target once no live lane wants to enter.  The gap and the BOUND step stand in this
+// kernel's own text -- rt_walk.hpp's centre_gap with q = 0 and bound_step_skip, which made the f64 B = 4 flavours 30 to 40 instructions
+// longer when called from here.  Every slot starts as (rho, -1).  A BOUND culls when gap >= cut: the last slot's gap (CLOSEST) or rho
+// (ALL).  An ITEM with !(gap >= last slot) is inserted behind every slot whose gap is <= its own, so equal gaps keep DFS order; ALL also
+// counts every ITEM with !(gap >= rho).  The query's `exclude` slot is tested and counted as a test, but neither inserted nor counted as
+// found.
 //
 // The list lives in registers as multihit's does: capacity B is a template parameter (kMultiBuckets), a runtime k < B leaves the first
 // B - k slots at -inf, every access has a compile-time index and the insertion is the branch-free compare-and-shift.
@@ -41,14 +43,12 @@ template <typename T> struct NearArgs {
 template <typename T, bool COUNT, bool ALL, bool ORDERED, int B>
 __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(B <= 4 ? 8 : 4))) void k_near_spheres(NearArgs<T> a)
 {
-    unsigned gid = blockIdx.x * kBlockThreads + threadIdx.x;
-    if (ORDERED) gid = gid < a.n ? a.order[gid] : kNever;
+    const unsigned gid = lane_query(ORDERED, a.order, a.n);
     const bool live = gid < a.n;
     const size_t g = live ? gid : 0u;
     V3<T> p = { T(0.0), T(0.0), T(0.0) };
     T rho = inf<T>();
-    constexpr unsigned kNone = 0xFFFFFFFFu;
-    unsigned excl = kNone;                       // (an item word's index has 30 bits: kNone and every negative slot match no item)
+    unsigned excl = kNone;
     if (live) {
         const T *q = a.points + 3 * g;
         p = { q[0], q[1], q[2] };
@@ -118,17 +118,8 @@ __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(B
         }
         if (a.found) a.found[g] = found;
     }
-    if constexpr (COUNT) {
-        const unsigned long long prim = wave_sum(live ? 1u : 0u), nhit = wave_sum((live && found > 0u) ? 1u : 0u);
-        const unsigned long long its = wave_sum(c_items), bds = wave_sum(c_bounds);
-        if ((threadIdx.x & 63u) == 0u) {
-            Counters *const stripe = a.counters + blockIdx.x % kCounterStripes;
-            atomicAdd(&stripe->primary, prim);
-            atomicAdd(&stripe->hits, nhit);
-            atomicAdd(&stripe->sphere_tests, its);
-            atomicAdd(&stripe->bound_tests, bds);
-        }
-    }
+    if constexpr (COUNT)
+        flush_counters(a.counters, wave_sum(live ? 1u : 0u), wave_sum((live && found > 0u) ? 1u : 0u), wave_sum(c_items), wave_sum(c_bounds));
 }
 
 }  // namespace rt

@@ -12,11 +12,10 @@
 // without a positive rr: always).  A query whose q is not >= 0 (negative, NaN) carries no query: no test, nothing listed.  The dead record
 // of DESIGN.md 4.13 is {0, 0, 0, -inf}: a dead item is at +inf -- never listed -- and a dead BOUND culls for every query.
 //
-// The walk is k_near_spheres's in ALL mode (rt_near.hpp) over the whole stream from node 0: one query per lane, a wave-uniform stream
-// index (node records arrive through the scalar cache), a lane sleeps while i < resume, a lane whose own bound test culls a subtree sets
-// resume = skip.  When no awake lane enters a bound the wave continues at the smallest resume of its lanes, as k_contact_pairs does; a
-// wave none of whose lanes carries a query never enters the loop.  The query's `exclude` slot is tested and counted as a test, but never
-// listed.  The index only grows, so the walk ends.
+// The walk is made of rt_walk.hpp's pieces (lane_query, centre_gap, bound_step_min) over the whole stream from node 0: one query per lane,
+// a lane sleeps while i < resume, a lane whose own bound test culls a subtree sets resume = skip.  When no awake lane enters a bound the
+// wave continues at the smallest resume of its lanes, as k_contact_pairs does; a wave none of whose lanes carries a query never enters
+// the loop.  The query's `exclude` slot is tested and counted as a test, but never listed.
 //
 // The list is rt_contacts.hpp's: the walk runs twice.  The first pass writes one count per query; the exclusive scan of rt_contacts.hpp
 // turns the counts into offsets; the second pass repeats the walk and writes entry offsets[g] + (rank within g) where that lies below the
@@ -48,14 +47,12 @@ template <typename T, bool COUNT, bool FILL>
 __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(8))) void k_overlap_spheres(OverlapArgs<T> a)
 {
     static_assert(!(COUNT && FILL), "the counters are the first pass's");
-    unsigned gid = blockIdx.x * kBlockThreads + threadIdx.x;
-    if (a.order) gid = gid < a.n ? a.order[gid] : kNever;
+    const unsigned gid = lane_query(a.order != nullptr, a.order, a.n);
     const bool in = gid < a.n;
     const size_t g = in ? gid : 0u;
     V3<T> p = { T(0.0), T(0.0), T(0.0) };
     T q = T(0.0);
-    constexpr unsigned kNone = 0xFFFFFFFFu;
-    unsigned excl = kNone;                       // (an item word's index has 30 bits: kNone and every negative slot match no item)
+    unsigned excl = kNone;
     unsigned resume = kNever;                    // a lane without a query never wakes
     unsigned long long at = 0;                   // FILL: where query g's entries start
     if (in) {
@@ -81,18 +78,11 @@ __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(8
         Node<T> nd = a.stream[i];
         for (;;) {
             const bool active = i >= resume;
-            // rt_near.hpp's gap of the record from the lane's centre, minus the lane's radius; every operation rounded once
-            const V3<T> v = { nd.a0 - p.x, nd.a1 - p.y, nd.a2 - p.z };
-            const T vv = dot(v, v);
-            T t = inf<T>();
-            if (nd.a3 > T(0.0)) t = (sqrt_rn_lean(vv) - sqrt_rn_lean(nd.a3)) - q;
+            const T t = centre_gap(nd, p, q);                        // the gap above
             unsigned ni;
             if (nd.is_bound()) {                                     // BOUND  against the margin
                 const bool cull = active && (t >= margin);
-                if (cull) resume = nd.skip();
-                if (COUNT) c_bounds += active ? 1u : 0u;
-                // nobody enters: every lane's resume now lies behind i
-                ni = (__ballot(active && !cull) == 0) ? wave_min_u32(resume) : i + 1;
+                ni = bound_step_min<COUNT>(active, cull, nd, i, resume, c_bounds);
             } else {                                                 // ITEM   within the margin of the lane's sphere
                 const unsigned it = nd.index();
                 const bool hit = active && it != excl && !(t >= margin);
@@ -113,17 +103,8 @@ __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(8
         }
     }
     if (!FILL && in) a.counts[g] = found;
-    if constexpr (COUNT) {
-        const unsigned long long prim = wave_sum(live ? 1u : 0u), nhit = wave_sum((live && found > 0u) ? 1u : 0u);
-        const unsigned long long its = wave_sum(c_items), bds = wave_sum(c_bounds);
-        if ((threadIdx.x & 63u) == 0u) {
-            Counters *const stripe = a.counters + blockIdx.x % kCounterStripes;
-            atomicAdd(&stripe->primary, prim);
-            atomicAdd(&stripe->hits, nhit);
-            atomicAdd(&stripe->sphere_tests, its);
-            atomicAdd(&stripe->bound_tests, bds);
-        }
-    }
+    if constexpr (COUNT)
+        flush_counters(a.counters, wave_sum(live ? 1u : 0u), wave_sum((live && found > 0u) ? 1u : 0u), wave_sum(c_items), wave_sum(c_bounds));
 }
 
 }  // namespace rt

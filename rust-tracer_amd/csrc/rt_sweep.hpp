@@ -16,14 +16,14 @@
 // 4.13 is {0, 0, 0, -inf}, whose root would be NaN; with the guard a dead ITEM is at +inf (never below a cutoff) and a dead BOUND culls
 // for every cast.
 //
-// The walk is k_query_rays's (rt_query.hpp) over the same plain per-origin stream: one cast per lane, a wave-uniform stream index (node
-// records arrive through the scalar cache), a per-lane `resume`, a jump to the skip target once no live lane wants to enter.  `best` starts
-// at tmax.  A BOUND culls when t >= best.  NEAREST: an ITEM with !(t >= best) becomes the result (the first item in DFS order wins a tie,
-// several items at 0 included).  ANY: the first ITEM with !(t >= tmax) retires the lane, and the wave goes to the smallest `resume` still
-// wanted.  The cast's `exclude` slot is tested and counted as a test, but can never win or retire the lane.  The index only grows, so the
-// walk ends whatever bits the casts carry.
+// The walk is made of k_query_rays's pieces (rt_walk.hpp: bound_step_skip, item_step_retire) over the same plain per-origin stream: one
+// cast per lane, a per-lane `resume`, a jump to the skip target once no live lane wants to enter; the metric above has its one copy in
+// the loop below.  `best` starts at tmax.  A BOUND culls when t >= best.  NEAREST: an ITEM with !(t >= best) becomes the result (the
+// first item in DFS order wins a tie, several items at 0 included).  ANY: the first ITEM with !(t >= tmax) retires the lane, and the wave
+// goes to the smallest `resume` still wanted.  The cast's `exclude` slot is tested and counted as a test, but can never win or retire
+// the lane.  The index only grows, so the walk ends whatever bits the casts carry.
 #pragma once
-#include "rt_skip.hpp"
+#include "rt_walk.hpp"
 
 namespace rt {
 
@@ -46,14 +46,12 @@ template <typename T> struct SweepArgs {
 template <typename T, bool COUNT, bool ANY, bool ORDERED>
 __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(8))) void k_sweep_spheres(SweepArgs<T> a)
 {
-    unsigned gid = blockIdx.x * kBlockThreads + threadIdx.x;
-    if (ORDERED) gid = gid < a.n ? a.order[gid] : kNever;
+    const unsigned gid = lane_query(ORDERED, a.order, a.n);
     const bool live = gid < a.n;
     const size_t g = live ? gid : 0u;
     V3<T> o = { T(0.0), T(0.0), T(0.0) }, d = { T(0.0), T(0.0), T(0.0) };
     T best = inf<T>(), q = T(0.0);
-    constexpr unsigned kNone = 0xFFFFFFFFu;
-    unsigned excl = kNone;                       // (an item word's index has 30 bits: kNone and every negative slot match no item)
+    unsigned excl = kNone;
     if (live) {
         const T *r = a.rays + 6 * g;
         o = { r[0], r[1], r[2] };
@@ -88,9 +86,7 @@ __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(8
             unsigned ni;
             if (nd.is_bound()) {                                     // BOUND
                 const bool cull = active && (t >= best);
-                if (cull) resume = nd.skip();
-                if (COUNT) c_bounds += active ? 1u : 0u;
-                ni = (__ballot(active && !cull) == 0) ? nd.skip() : i + 1;
+                ni = bound_step_skip<COUNT>(active, cull, nd, i, resume, c_bounds);
             } else if constexpr (!ANY) {                             // ITEM, the nearest so far
                 const unsigned it = nd.index();
                 if (active && it != excl && !(t >= best)) { best = t; best_item = it; }
@@ -100,8 +96,8 @@ __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(8
                 const unsigned it = nd.index();
                 const bool fin = active && it != excl && !(t >= best);
                 if (COUNT) c_items += active ? 1u : 0u;
-                if (fin) { best = t; best_item = it; resume = kNever; }
-                ni = (__ballot(fin) != 0) ? wave_min_u32(resume == kNever ? kNever : (resume > i ? resume : i + 1)) : i + 1;
+                if (fin) { best = t; best_item = it; }
+                ni = item_step_retire(fin, i, resume);
             }
             if (ni >= n) break;                                      // also kNever: every lane retired
             i = (unsigned)__builtin_amdgcn_readfirstlane((int)ni);
@@ -121,17 +117,8 @@ __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(8
             p[0] = nrm.x; p[1] = nrm.y; p[2] = nrm.z;
         }
     }
-    if constexpr (COUNT) {
-        const unsigned long long prim = wave_sum(live ? 1u : 0u), hits = wave_sum((live && best_item != kNone) ? 1u : 0u);
-        const unsigned long long its = wave_sum(c_items), bds = wave_sum(c_bounds);
-        if ((threadIdx.x & 63u) == 0u) {
-            Counters *const stripe = a.counters + blockIdx.x % kCounterStripes;
-            atomicAdd(&stripe->primary, prim);
-            atomicAdd(&stripe->hits, hits);
-            atomicAdd(&stripe->sphere_tests, its);
-            atomicAdd(&stripe->bound_tests, bds);
-        }
-    }
+    if constexpr (COUNT)
+        flush_counters(a.counters, wave_sum(live ? 1u : 0u), wave_sum((live && best_item != kNone) ? 1u : 0u), wave_sum(c_items), wave_sum(c_bounds));
 }
 
 }  // namespace rt

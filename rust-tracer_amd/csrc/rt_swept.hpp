@@ -23,9 +23,11 @@
 // |dq.z| over every query with q >= 0 -- by query index, whatever the order -- into the magnitude word the motion kernels fold the scene
 // into (atomic_max_bits: max is exact, the word is the same every time).  It runs before k_impact_motion_bounds, which reads S.
 //
-// The walk is k_overlap_spheres's: thread j carries query order[j] from node 0, the node index is wave-uniform (stream and motion record
-// arrive through the scalar cache), a lane sleeps while i < resume, the wave goes to the smallest resume when nobody enters, a wave
-// without a query returns before the loop, and in the FILL pass a query whose count is 0 carries no query.  Count pass, rt_contacts.hpp's
+// The walk is built as k_overlap_spheres's is, from rt_walk.hpp's pieces (lane_query; swept_time, the formula above): thread j carries
+// query order[j] from node 0, stream and motion record arrive through the scalar cache, a lane sleeps while i < resume, the wave goes to
+// the smallest resume when nobody enters, a wave without a query returns before the loop, and in the FILL pass a query whose count is 0
+// carries no query.  The BOUND step and the normal stand in this kernel's own text: called from here, rt_walk.hpp's bound_step_min and
+// swept_normal made the counting and the FILL flavours two to three instructions longer.  Count pass, rt_contacts.hpp's
 // scan, fill pass: the list is sorted by (g, item slot) and the same bytes every time.
 #pragma once
 #include "rt_impacts.hpp"
@@ -79,15 +81,13 @@ template <typename T, bool COUNT, bool FILL>
 __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(8))) void k_swept_overlaps(SweptArgs<T> a)
 {
     static_assert(!(COUNT && FILL), "the counters are the first pass's");
-    unsigned gid = blockIdx.x * kBlockThreads + threadIdx.x;
-    if (a.order) gid = gid < a.n ? a.order[gid] : kNever;
+    const unsigned gid = lane_query(a.order != nullptr, a.order, a.n);
     const bool in = gid < a.n;
     const size_t g = in ? gid : 0u;
     const T S = impact_scale(*a.magnitude);      // (wave-uniform)
     V3<T> p = { T(0.0), T(0.0), T(0.0) }, dq = { T(0.0), T(0.0), T(0.0) };
     T q = T(0.0);
-    constexpr unsigned kNone = 0xFFFFFFFFu;
-    unsigned excl = kNone;                       // (an item word's index has 30 bits: kNone and every negative slot match no item)
+    unsigned excl = kNone;
     unsigned resume = kNever;                    // a lane without a query never wakes
     unsigned long long at = 0;                   // FILL: where query g's entries start
     if (in) {
@@ -116,18 +116,8 @@ __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(8
         Motion<T> mo = a.motion[i];
         for (;;) {
             const bool active = i >= resume;
-            // k_impact_pairs's arithmetic with the lane's query in the place of item i; every operation rounded once
-            const V3<T> v = { nd.a0 * S - p.x, nd.a1 * S - p.y, nd.a2 * S - p.z };
-            const V3<T> w = { dq.x - mo.x, dq.y - mo.y, dq.z - mo.z };
-            const T R = mo.E + q;                                    // ((r' + E') + q')
-            const T RR = R * R;
-            const T qa = dot(w, w), qb = dot(v, w), qc = dot(v, v) - RR;
-            const T disc = qb * qb - qa * qc;
-            T tm = inf<T>();
-            if (nd.a3 > T(0.0)) {
-                if (!(qc > T(0.0))) tm = T(0.0);
-                else if (qb > T(0.0) && !(disc < T(0.0))) tm = qc / (qb + sqrt_rn_lean(disc));
-            }
+            V3<T> v, w;
+            const T tm = swept_time(nd, mo, S, p, dq, q, v, w);      // k_impact_pairs's, with the lane's query in the place of item i
             const bool within = tm <= T(1.0);
             unsigned ni;
             if (nd.is_bound()) {                                     // BOUND  inflated by the largest displacement below it
@@ -162,17 +152,8 @@ __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(8
         }
     }
     if (!FILL && in) a.counts[g] = found;
-    if constexpr (COUNT) {
-        const unsigned long long prim = wave_sum(live ? 1u : 0u), nhit = wave_sum((live && found > 0u) ? 1u : 0u);
-        const unsigned long long its = wave_sum(c_items), bds = wave_sum(c_bounds);
-        if ((threadIdx.x & 63u) == 0u) {
-            Counters *const stripe = a.counters + blockIdx.x % kCounterStripes;
-            atomicAdd(&stripe->primary, prim);
-            atomicAdd(&stripe->hits, nhit);
-            atomicAdd(&stripe->sphere_tests, its);
-            atomicAdd(&stripe->bound_tests, bds);
-        }
-    }
+    if constexpr (COUNT)
+        flush_counters(a.counters, wave_sum(live ? 1u : 0u), wave_sum((live && found > 0u) ? 1u : 0u), wave_sum(c_items), wave_sum(c_bounds));
 }
 
 }  // namespace rt

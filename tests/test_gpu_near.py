@@ -335,6 +335,24 @@ def test_any_order_gives_the_same_bytes_and_counters():
         same_bytes(ref[:3], full[:3])
         assert counters(full[3]) == counters(ref[3])
     d.close()
+    # every flavour of the walk -- precision, list capacity, mode, in an order or not, counting or not -- on 65 queries: two waves, the
+    # second with one live lane.  The counting unordered call is held to the host walker, the other three to its bytes and counters.
+    for precision in (rta.RT_F32, rta.RT_F64):
+        s = cases(precision)["refit"]
+        d = rta.DeviceScene(s)
+        points, radius = (np.ascontiguousarray(x[:65]) for x in query_families(s, np.random.default_rng(13), 80))
+        perm = np.random.default_rng(14).permutation(65).astype(np.uint32)
+        w = Walker(s, points)
+        for k in (1, 4, 8, 16):
+            for all_within in (False, True):
+                ref = d.near(points, k, radius, all_within=all_within, want_stats=True)
+                assert_walk(ref, w.all(radius, k, all_within), REAL[precision], ("refit, 65 queries", precision, k, all_within))
+                same_bytes(ref[:3], d.near(points, k, radius, all_within=all_within))
+                same_bytes(ref[:3], d.near(points, k, radius, all_within=all_within, order=perm))
+                got = d.near(points, k, radius, all_within=all_within, want_stats=True, order=perm)
+                same_bytes(ref[:3], got[:3])
+                assert counters(got[3]) == counters(ref[3]), (precision, k, all_within)
+        d.close()
 
 
 @PRECISIONS

@@ -131,11 +131,12 @@ def test_walks_in_any_order_write_the_same_bytes_and_count_the_same_tests(precis
                  ("nearest, tmax inf", lambda **kw: d.intersect(rays, want_stats=True, **kw)),
                  ("trace", lambda **kw: d.trace(rays, want_stats=True, **kw)),
                  ("trace, no stats", lambda **kw: d.trace(rays, **kw))]
-        for k in (1, 4, 16):
+        for k in (1, 4, 8, 16):                                                 # every list capacity, both modes, with and without counters
             for all_hits in (False, True):
                 calls.append(("multi k=%d all=%d" % (k, all_hits), lambda k=k, all_hits=all_hits, **kw:
                               d.intersect_multi(rays, k, tmax, all_hits=all_hits, want_stats=True, **kw)))
-        calls.append(("multi k=8, no stats", lambda **kw: d.intersect_multi(rays, 8, tmax, **kw)))
+                calls.append(("multi k=%d all=%d, no stats" % (k, all_hits), lambda k=k, all_hits=all_hits, **kw:
+                              d.intersect_multi(rays, k, tmax, all_hits=all_hits, **kw)))
         orders = orders_of(d, rays, rng)
         for what, call in calls:
             ref = call()

@@ -358,6 +358,26 @@ def test_any_order_gives_the_same_bytes_and_counters():
         same_bytes(ref[:3], full[:3])
         assert counters(full[3]) == counters(ref[3])
     d.close()
+    # every flavour of the walk -- precision, mode, in an order or not, counting or not -- on 65 casts: two waves, the second with one live
+    # lane.  The counting unordered call is held to the host walker, the other three to its bytes and counters.
+    for precision in (rta.RT_F32, rta.RT_F64):
+        s = cases(precision)["refit"]
+        d = rta.DeviceScene(s)
+        rng = np.random.default_rng(13)
+        rays, radius, _ = cast_families(s, rng, 80)
+        tmax = cutoffs(rays, radius, s.items, rng)
+        rays, radius, tmax = (np.ascontiguousarray(x[:65]) for x in (rays, radius, tmax))
+        perm = np.random.default_rng(14).permutation(65).astype(np.uint32)
+        w = Walker(s, rays, radius)
+        for any_hit in (False, True):
+            ref = d.sweep(rays, radius, tmax, any_hit=any_hit, want_stats=True)
+            assert_walk(ref, w.all(tmax, any_hit), w, REAL[precision], ("refit, 65 casts", precision, any_hit))
+            same_bytes(ref[:3], d.sweep(rays, radius, tmax, any_hit=any_hit))
+            same_bytes(ref[:3], d.sweep(rays, radius, tmax, any_hit=any_hit, order=perm))
+            got = d.sweep(rays, radius, tmax, any_hit=any_hit, want_stats=True, order=perm)
+            same_bytes(ref[:3], got[:3])
+            assert counters(got[3]) == counters(ref[3]), (precision, any_hit)
+        d.close()
 
 
 @PRECISIONS
