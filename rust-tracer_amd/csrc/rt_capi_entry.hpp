@@ -973,15 +973,12 @@ static rt_status intersect_rays_host(rt_scene *s, rt_query mode, const void *ray
 {
     if (!query_args_ok(s, mode, rays, tmax, n, distance_out, normal_out, item_out, what)) return RT_ERR_INVALID_ARGUMENT;
     if (ordered && !device_order_ok(order, what)) return RT_ERR_INVALID_ARGUMENT;
-    const bool f32 = s->precision == RT_F32;
-    const size_t esz = f32 ? sizeof(float) : sizeof(double);
+    const size_t esz = real_size(s);
     HostStaging::Row rows[] = { { rays, 6 * esz * n, kStageIn }, { tmax, esz * n, kStageIn }, { distance_out, esz * n, kStageOut },
                                 { normal_out, 3 * esz * n, kStageOut }, { item_out, sizeof(int32_t) * n, kStageOut }, { order, sizeof(uint32_t) * n, kStageIn } };
     HostStaging hs(rows);
     if (rt_status pst = hs.plan(what); pst != RT_OK) return pst;
-    if (!(f32 ? query_rays_valid(static_cast<const float *>(rays), static_cast<const float *>(tmax), n)
-              : query_rays_valid(static_cast<const double *>(rays), static_cast<const double *>(tmax), n)))
-        return RT_ERR_INVALID_ARGUMENT;
+    if (!query_rays_valid(s, rays, tmax, n)) return RT_ERR_INVALID_ARGUMENT;
     if (order && !order_is_permutation(order, n, what)) return RT_ERR_INVALID_ARGUMENT;
     const uint32_t *d_order = nullptr;
     return host_query(s, hs, stats, read_query_stats,
@@ -1063,15 +1060,12 @@ static rt_status intersect_rays_multi_host(rt_scene *s, rt_multihit mode, uint32
     if (!query_args_ok(s, RT_QUERY_NEAREST, rays, tmax, n, distance_out, normal_out, item_out, what) || !multihit_args_ok(mode, k, hits_out, what))
         return RT_ERR_INVALID_ARGUMENT;
     if (ordered && !device_order_ok(order, what)) return RT_ERR_INVALID_ARGUMENT;
-    const bool f32 = s->precision == RT_F32;
-    const size_t esz = f32 ? sizeof(float) : sizeof(double), nk = (size_t)n * k;
+    const size_t esz = real_size(s), nk = (size_t)n * k;
     HostStaging::Row rows[] = { { rays, 6 * esz * n, kStageIn }, { tmax, esz * n, kStageIn }, { distance_out, esz * nk, kStageOut }, { normal_out, 3 * esz * nk, kStageOut },
                                 { item_out, sizeof(int32_t) * nk, kStageOut }, { hits_out, sizeof(uint32_t) * n, kStageOut }, { order, sizeof(uint32_t) * n, kStageIn } };
     HostStaging hs(rows);
     if (rt_status pst = hs.plan(what); pst != RT_OK) return pst;
-    if (!(f32 ? query_rays_valid(static_cast<const float *>(rays), static_cast<const float *>(tmax), n)
-              : query_rays_valid(static_cast<const double *>(rays), static_cast<const double *>(tmax), n)))
-        return RT_ERR_INVALID_ARGUMENT;
+    if (!query_rays_valid(s, rays, tmax, n)) return RT_ERR_INVALID_ARGUMENT;
     if (order && !order_is_permutation(order, n, what)) return RT_ERR_INVALID_ARGUMENT;
     const uint32_t *d_order = nullptr;
     return host_query(s, hs, stats, read_query_stats,
@@ -1112,15 +1106,12 @@ rt_status rt_near_spheres(rt_scene *s, rt_near mode, uint32_t k, const void *poi
 {
     const char *const what = "rt_near_spheres";
     if (!near_args_ok(s, mode, k, points, radius, n, exclude, order, gap_out, item_out, found_out, what)) return RT_ERR_INVALID_ARGUMENT;
-    const bool f32 = s->precision == RT_F32;
-    const size_t esz = f32 ? sizeof(float) : sizeof(double), nk = (size_t)n * k;
+    const size_t esz = real_size(s), nk = (size_t)n * k;
     HostStaging::Row rows[] = { { points, 3 * esz * n, kStageIn }, { radius, esz * n, kStageIn }, { exclude, sizeof(int32_t) * n, kStageIn }, { order, sizeof(uint32_t) * n, kStageIn },
                                 { gap_out, esz * nk, kStageOut }, { item_out, sizeof(int32_t) * nk, kStageOut }, { found_out, sizeof(uint32_t) * n, kStageOut } };
     HostStaging hs(rows);
     if (rt_status pst = hs.plan(what); pst != RT_OK) return pst;
-    if (!(f32 ? near_points_valid(static_cast<const float *>(points), static_cast<const float *>(radius), n, what)
-              : near_points_valid(static_cast<const double *>(points), static_cast<const double *>(radius), n, what)))
-        return RT_ERR_INVALID_ARGUMENT;
+    if (!near_points_valid(s, points, radius, n, what)) return RT_ERR_INVALID_ARGUMENT;
     if (order && !order_is_permutation(order, n, what)) return RT_ERR_INVALID_ARGUMENT;
     return host_query(s, hs, stats, read_query_stats, no_pre_step, [&](const void *nodes, uint32_t n_nodes, rt::Counters *counters, hipStream_t stream) {
         return enqueue_near(s, nodes, n_nodes, mode, k, hs.dev(0), hs.dev(1), n, hs.dev<const int32_t>(2), hs.dev<const uint32_t>(3), hs.dev(4), hs.dev<int32_t>(5),
@@ -1145,16 +1136,13 @@ rt_status rt_sweep_spheres(rt_scene *s, rt_sweep mode, const void *rays, const v
 {
     const char *const what = "rt_sweep_spheres";
     if (!sweep_args_ok(s, mode, rays, radius, tmax, n, exclude, order, distance_out, normal_out, item_out, what)) return RT_ERR_INVALID_ARGUMENT;
-    const bool f32 = s->precision == RT_F32;
-    const size_t esz = f32 ? sizeof(float) : sizeof(double);
+    const size_t esz = real_size(s);
     HostStaging::Row rows[] = { { rays, 6 * esz * n, kStageIn }, { radius, esz * n, kStageIn }, { tmax, esz * n, kStageIn }, { exclude, sizeof(int32_t) * n, kStageIn },
                                 { order, sizeof(uint32_t) * n, kStageIn }, { distance_out, esz * n, kStageOut }, { normal_out, 3 * esz * n, kStageOut },
                                 { item_out, sizeof(int32_t) * n, kStageOut } };
     HostStaging hs(rows);
     if (rt_status pst = hs.plan(what); pst != RT_OK) return pst;
-    if (!(f32 ? sweep_casts_valid(static_cast<const float *>(rays), static_cast<const float *>(radius), static_cast<const float *>(tmax), n, what)
-              : sweep_casts_valid(static_cast<const double *>(rays), static_cast<const double *>(radius), static_cast<const double *>(tmax), n, what)))
-        return RT_ERR_INVALID_ARGUMENT;
+    if (!sweep_casts_valid(s, rays, radius, tmax, n, what)) return RT_ERR_INVALID_ARGUMENT;
     if (order && !order_is_permutation(order, n, what)) return RT_ERR_INVALID_ARGUMENT;
     return host_query(s, hs, stats, read_query_stats, no_pre_step, [&](const void *nodes, uint32_t n_nodes, rt::Counters *counters, hipStream_t stream) {
         return enqueue_sweep(s, nodes, n_nodes, mode, hs.dev(0), hs.dev(1), hs.dev(2), n, hs.dev<const int32_t>(3), hs.dev<const uint32_t>(4), hs.dev(5), hs.dev(6),
@@ -1184,7 +1172,7 @@ rt_status rt_scene_contacts(rt_scene *s, double margin, uint32_t capacity, int32
     const char *const what = "rt_scene_contacts";
     if (!contacts_args_ok(s, margin, capacity, pairs_out, gap_out, offsets_out, total_out, what)) return RT_ERR_INVALID_ARGUMENT;
     const bool fill = capacity != 0u && pairs_out;
-    const size_t esz = s->precision == RT_F32 ? sizeof(float) : sizeof(double);
+    const size_t esz = real_size(s);
     HostStaging::Row rows[] = { { fill ? pairs_out : nullptr, 2 * sizeof(int32_t) * (size_t)capacity, kStageOut, 2 * sizeof(int32_t) },
                                 { fill ? gap_out : nullptr, esz * (size_t)capacity, kStageOut, esz },
                                 { offsets_out, sizeof(uint64_t) * ((size_t)s->n_items + 1), kStageOut } };
@@ -1223,17 +1211,15 @@ rt_status rt_scene_impacts(rt_scene *s, const void *disp, uint32_t capacity, int
 {
     const char *const what = "rt_scene_impacts";
     if (!impacts_args_ok(s, disp, capacity, pairs_out, time_out, offsets_out, total_out, what)) return RT_ERR_INVALID_ARGUMENT;
-    const bool f32 = s->precision == RT_F32;
     const bool fill = capacity != 0u && pairs_out;
-    const size_t esz = f32 ? sizeof(float) : sizeof(double);
+    const size_t esz = real_size(s);
     HostStaging::Row rows[] = { { disp, 3 * esz * (size_t)s->n_items, kStageIn },
                                 { fill ? pairs_out : nullptr, 2 * sizeof(int32_t) * (size_t)capacity, kStageOut, 2 * sizeof(int32_t) },
                                 { fill ? time_out : nullptr, esz * (size_t)capacity, kStageOut, esz },
                                 { offsets_out, sizeof(uint64_t) * ((size_t)s->n_items + 1), kStageOut } };
     HostStaging hs(rows);
     if (rt_status pst = hs.plan(what, total_out); pst != RT_OK) return pst;
-    if (!(f32 ? impacts_disp_valid(static_cast<const float *>(disp), s->n_items, what) : impacts_disp_valid(static_cast<const double *>(disp), s->n_items, what)))
-        return RT_ERR_INVALID_ARGUMENT;
+    if (!impacts_disp_valid(s, disp, s->n_items, what)) return RT_ERR_INVALID_ARGUMENT;
     // (the contacts workspace: host calls on one scene take turns, contacts and impacts alike)
     return host_list_query(
         s, s->contacts, hs, capacity, fill, total_out, stats,
@@ -1269,17 +1255,15 @@ rt_status rt_overlap_spheres(rt_scene *s, const void *queries, uint32_t n, doubl
 {
     const char *const what = "rt_overlap_spheres";
     if (!overlap_args_ok(s, queries, n, margin, exclude, order, capacity, items_out, gap_out, offsets_out, total_out, what)) return RT_ERR_INVALID_ARGUMENT;
-    const bool f32 = s->precision == RT_F32;
     const bool fill = capacity != 0u && items_out;
-    const size_t esz = f32 ? sizeof(float) : sizeof(double);
+    const size_t esz = real_size(s);
     HostStaging::Row rows[] = { { queries, 4 * esz * (size_t)n, kStageIn }, { exclude, sizeof(int32_t) * (size_t)n, kStageIn }, { order, sizeof(uint32_t) * (size_t)n, kStageIn },
                                 { fill ? items_out : nullptr, sizeof(int32_t) * (size_t)capacity, kStageOut, sizeof(int32_t) },
                                 { fill ? gap_out : nullptr, esz * (size_t)capacity, kStageOut, esz },
                                 { offsets_out, sizeof(uint64_t) * ((size_t)n + 1), kStageOut } };
     HostStaging hs(rows);
     if (rt_status pst = hs.plan(what, total_out); pst != RT_OK) return pst;
-    if (!(f32 ? overlap_queries_valid(static_cast<const float *>(queries), n, what) : overlap_queries_valid(static_cast<const double *>(queries), n, what)))
-        return RT_ERR_INVALID_ARGUMENT;
+    if (!overlap_queries_valid(s, queries, n, what)) return RT_ERR_INVALID_ARGUMENT;
     if (order && !order_is_permutation(order, n, what)) return RT_ERR_INVALID_ARGUMENT;
     return host_list_query(
         s, s->overlap, hs, capacity, fill, total_out, stats,
@@ -1318,9 +1302,8 @@ rt_status rt_swept_overlaps(rt_scene *s, const void *queries, const void *qdisp,
 {
     const char *const what = "rt_swept_overlaps";
     if (!swept_args_ok(s, queries, qdisp, n, disp, exclude, order, capacity, items_out, time_out, normal_out, offsets_out, total_out, what)) return RT_ERR_INVALID_ARGUMENT;
-    const bool f32 = s->precision == RT_F32;
     const bool fill = capacity != 0u && items_out;
-    const size_t esz = f32 ? sizeof(float) : sizeof(double);
+    const size_t esz = real_size(s);
     HostStaging::Row rows[] = { { queries, 4 * esz * (size_t)n, kStageIn }, { qdisp, 3 * esz * (size_t)n, kStageIn }, { disp, 3 * esz * (size_t)s->n_items, kStageIn },
                                 { exclude, sizeof(int32_t) * (size_t)n, kStageIn }, { order, sizeof(uint32_t) * (size_t)n, kStageIn },
                                 { fill ? items_out : nullptr, sizeof(int32_t) * (size_t)capacity, kStageOut, sizeof(int32_t) },
@@ -1329,13 +1312,10 @@ rt_status rt_swept_overlaps(rt_scene *s, const void *queries, const void *qdisp,
                                 { offsets_out, sizeof(uint64_t) * ((size_t)n + 1), kStageOut } };
     HostStaging hs(rows);
     if (rt_status pst = hs.plan(what, total_out); pst != RT_OK) return pst;
-    if (!(f32 ? overlap_queries_valid(static_cast<const float *>(queries), n, what) : overlap_queries_valid(static_cast<const double *>(queries), n, what)))
-        return RT_ERR_INVALID_ARGUMENT;
-    if (!(f32 ? swept_qdisp_valid(static_cast<const float *>(qdisp), n, what) : swept_qdisp_valid(static_cast<const double *>(qdisp), n, what)))
-        return RT_ERR_INVALID_ARGUMENT;
+    if (!overlap_queries_valid(s, queries, n, what)) return RT_ERR_INVALID_ARGUMENT;
+    if (!swept_qdisp_valid(s, qdisp, n, what)) return RT_ERR_INVALID_ARGUMENT;
     if (order && !order_is_permutation(order, n, what)) return RT_ERR_INVALID_ARGUMENT;
-    if (disp && !(f32 ? impacts_disp_valid(static_cast<const float *>(disp), s->n_items, what) : impacts_disp_valid(static_cast<const double *>(disp), s->n_items, what)))
-        return RT_ERR_INVALID_ARGUMENT;
+    if (disp && !impacts_disp_valid(s, disp, s->n_items, what)) return RT_ERR_INVALID_ARGUMENT;
     // (the overlap workspace: host calls on one scene take turns, overlap and swept alike)
     return host_list_query(
         s, s->overlap, hs, capacity, fill, total_out, stats,
@@ -1368,21 +1348,17 @@ rt_status rt_first_contacts(rt_scene *s, rt_sweep mode, const void *queries, con
 {
     const char *const what = "rt_first_contacts";
     if (!first_args_ok(s, mode, queries, qdisp, n, disp, exclude, order, time_out, item_out, normal_out, what)) return RT_ERR_INVALID_ARGUMENT;
-    const bool f32 = s->precision == RT_F32;
-    const size_t esz = f32 ? sizeof(float) : sizeof(double);
+    const size_t esz = real_size(s);
     HostStaging::Row rows[] = { { queries, 4 * esz * (size_t)n, kStageIn }, { qdisp, 3 * esz * (size_t)n, kStageIn }, { disp, 3 * esz * (size_t)s->n_items, kStageIn },
                                 { exclude, sizeof(int32_t) * (size_t)n, kStageIn }, { order, sizeof(uint32_t) * (size_t)n, kStageIn },
                                 { time_out, esz * (size_t)n, kStageOut }, { item_out, sizeof(int32_t) * (size_t)n, kStageOut },
                                 { normal_out, 3 * esz * (size_t)n, kStageOut } };
     HostStaging hs(rows);
     if (rt_status pst = hs.plan(what); pst != RT_OK) return pst;
-    if (!(f32 ? overlap_queries_valid(static_cast<const float *>(queries), n, what) : overlap_queries_valid(static_cast<const double *>(queries), n, what)))
-        return RT_ERR_INVALID_ARGUMENT;
-    if (!(f32 ? swept_qdisp_valid(static_cast<const float *>(qdisp), n, what) : swept_qdisp_valid(static_cast<const double *>(qdisp), n, what)))
-        return RT_ERR_INVALID_ARGUMENT;
+    if (!overlap_queries_valid(s, queries, n, what)) return RT_ERR_INVALID_ARGUMENT;
+    if (!swept_qdisp_valid(s, qdisp, n, what)) return RT_ERR_INVALID_ARGUMENT;
     if (order && !order_is_permutation(order, n, what)) return RT_ERR_INVALID_ARGUMENT;
-    if (disp && !(f32 ? impacts_disp_valid(static_cast<const float *>(disp), s->n_items, what) : impacts_disp_valid(static_cast<const double *>(disp), s->n_items, what)))
-        return RT_ERR_INVALID_ARGUMENT;
+    if (disp && !impacts_disp_valid(s, disp, s->n_items, what)) return RT_ERR_INVALID_ARGUMENT;
     return host_query(s, hs, stats, read_query_stats, no_pre_step, [&](const void *nodes, uint32_t n_nodes, rt::Counters *counters, hipStream_t stream) {
         return enqueue_first(s, nodes, n_nodes, mode, hs.dev(0), hs.dev(1), n, hs.dev(2), hs.dev<const int32_t>(3), hs.dev<const uint32_t>(4), hs.dev(5),
                              hs.dev<int32_t>(6), hs.dev(7), counters, stream);
@@ -1441,14 +1417,11 @@ static rt_status trace_rays_host(rt_scene *s, const void *rays, uint32_t n, void
 {
     if (!trace_args_ok(s, rays, n, color_out, alpha_out, what)) return RT_ERR_INVALID_ARGUMENT;
     if (ordered && !device_order_ok(order, what)) return RT_ERR_INVALID_ARGUMENT;
-    const bool f32 = s->precision == RT_F32;
-    const size_t esz = f32 ? sizeof(float) : sizeof(double);
+    const size_t esz = real_size(s);
     HostStaging::Row rows[] = { { rays, 6 * esz * n, kStageIn }, { color_out, 3 * esz * n, kStageOut }, { alpha_out, esz * n, kStageOut }, { order, sizeof(uint32_t) * n, kStageIn } };
     HostStaging hs(rows);
     if (rt_status pst = hs.plan(what); pst != RT_OK) return pst;
-    if (!(f32 ? query_rays_valid(static_cast<const float *>(rays), static_cast<const float *>(nullptr), n)
-              : query_rays_valid(static_cast<const double *>(rays), static_cast<const double *>(nullptr), n)))
-        return RT_ERR_INVALID_ARGUMENT;
+    if (!query_rays_valid(s, rays, nullptr, n)) return RT_ERR_INVALID_ARGUMENT;
     if (order && !order_is_permutation(order, n, what)) return RT_ERR_INVALID_ARGUMENT;
     const uint32_t *d_order = nullptr;
     return host_query(s, hs, stats, read_trace_stats,
@@ -1508,13 +1481,10 @@ static rt_status order_host(rt_scene *s, HostStaging &hs, uint32_t n,
 rt_status rt_ray_order(rt_scene *s, const void *rays, uint32_t n, uint32_t *order_out)
 {
     if (!order_args_ok(s, rays, n, order_out, "rt_ray_order")) return RT_ERR_INVALID_ARGUMENT;
-    const bool f32 = s->precision == RT_F32;
-    HostStaging::Row rows[] = { { rays, 6 * (f32 ? sizeof(float) : sizeof(double)) * n, kStageIn }, { order_out, sizeof(uint32_t) * n, kStageOut } };
+    HostStaging::Row rows[] = { { rays, 6 * real_size(s) * n, kStageIn }, { order_out, sizeof(uint32_t) * n, kStageOut } };
     HostStaging hs(rows);
     if (rt_status pst = hs.plan("rt_ray_order"); pst != RT_OK) return pst;
-    if (!(f32 ? query_rays_valid(static_cast<const float *>(rays), static_cast<const float *>(nullptr), n)
-              : query_rays_valid(static_cast<const double *>(rays), static_cast<const double *>(nullptr), n)))
-        return RT_ERR_INVALID_ARGUMENT;
+    if (!query_rays_valid(s, rays, nullptr, n)) return RT_ERR_INVALID_ARGUMENT;
     return order_host(s, hs, n, enqueue_ray_order);
 }
 

@@ -590,6 +590,129 @@ bool live_items_valid(const void *items, const uint8_t *live, uint32_t n)
     return true;
 }
 
+// ---- what the queries' checks and launches share: one precision switch, one flavour switch, one alignment check, three
+// domain predicates.  A query brings its argument struct, its NULL / mode / capacity rules, its table of pointers, its composition of the
+// predicates and one launch lambda per kernel ----
+
+inline size_t real_size(const rt_scene *s) { return s->precision == RT_F32 ? sizeof(float) : sizeof(double); }
+
+// The precision switch: f(float{}) or f(double{}) by the scene's REAL, and what it returns.  Inside, `using T = decltype(real)`.
+template <typename F>
+auto by_precision(const rt_scene *s, F &&f) { return s->precision == RT_F32 ? f(float{}) : f(double{}); }
+
+// The flavour switch: runtime flags as template arguments.  with_flags(f, a, b) calls f(std::bool_constant<a>{}, std::bool_constant<b>{});
+// a generic lambda that launches kernel<T, a(), b()> is instantiated for every combination of its flags.  So this is for kernels that
+// exist in every combination: where only some do (the list queries' <COUNT, false> and <false, true>), spell those.
+template <typename F>
+void with_flags(F &&f) { f(); }
+template <typename F, typename... Rest>
+void with_flags(F &&f, bool first, Rest... rest)
+{
+    if (first) with_flags([&](auto... r) { f(std::true_type{}, r...); }, rest...);
+    else with_flags([&](auto... r) { f(std::false_type{}, r...); }, rest...);
+}
+
+// ... and the capacity of a k-list kernel's lists: f(std::integral_constant<int, B>{}), B the smallest bucket >= k
+// (RT_DEBUG_MULTIHIT_BUCKET: a larger one).
+template <typename F>
+void with_list_bucket(uint32_t k, F &&f)
+{
+    static_assert(sizeof rt::kMultiBuckets == 4 * sizeof(unsigned) && rt::kMultiBuckets[3] == 16u, "the cases below are rt::kMultiBuckets");
+    unsigned bucket = 0;
+    for (unsigned b : rt::kMultiBuckets)
+        if (bucket == 0 && b >= k) bucket = b;
+    const long long forced = knob(RT_DEBUG_MULTIHIT_BUCKET);
+    for (unsigned b : rt::kMultiBuckets)
+        if (forced == (long long)b && b >= k) bucket = b;
+    switch (bucket) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 8: f(std::integral_constant<int, 8>{}); break;
+    default: f(std::integral_constant<int, 16>{}); break;
+    }
+}
+
+// One thread per query, in blocks of rt::kBlockThreads.
+inline dim3 query_grid(uint32_t n) { return dim3((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)); }
+inline dim3 query_block() { return dim3(rt::kBlockThreads); }
+
+// The alignment check: the first pointer of the table that is not `alignment`-byte aligned is named (NULL is aligned).
+struct NamedPointer { const void *p; const char *name; };
+bool aligned_ok(const char *what, size_t alignment, std::initializer_list<NamedPointer> table)
+{
+    for (const NamedPointer &x : table)
+        if ((reinterpret_cast<uintptr_t>(x.p) % alignment) != 0) {
+            snprintf(g_err, sizeof g_err, "%s: %s must be %u-byte aligned", what, x.name, (unsigned)alignment);
+            return false;
+        }
+    return true;
+}
+
+// The domain predicates of the host entries, each for element i of a REAL array, with the variable parts of its message passed in.  A
+// query's *_valid composes them element by element (each_valid): of two violations the one at the lower index is reported.
+// 1. a ray {pos, dir}: finite, |pos| <= 1e15 and a unit direction (squared length within 2e-3 of 1) -- the bounds rt_scene_create puts on
+//    the light and the eye: no intermediate of the walk overflows.  `infix`: what stands between `what` and ": ray i"
+template <typename T>
+bool ray_ok(const T *rays, uint32_t i, const char *what, const char *infix)
+{
+    const T *r = rays + 6 * (size_t)i;
+    for (int k = 0; k < 6; ++k)
+        if (!std::isfinite(r[k]) || (k < 3 && std::fabs((double)r[k]) > 1e15)) {
+            snprintf(g_err, sizeof g_err, "%s%s: ray %u has a non-finite component or |pos| > 1e15", what, infix, i);
+            return false;
+        }
+    const double d2 = (double)r[3] * r[3] + (double)r[4] * r[4] + (double)r[5] * r[5];
+    if (std::fabs(d2 - 1.0) > 2e-3) {
+        snprintf(g_err, sizeof g_err, "%s%s: ray %u's direction is not a unit vector (its squared length is %.6g)", what, infix, i, d2);
+        return false;
+    }
+    return true;
+}
+
+// ... with a tmax that is not NaN; a proximity radius is held to no more.  v == NULL: none was given
+template <typename T>
+bool not_nan_ok(const T *v, uint32_t i, const char *what, const char *name)
+{
+    if (v && std::isnan(v[i])) { snprintf(g_err, sizeof g_err, "%s: %s[%u] is NaN", what, name, i); return false; }
+    return true;
+}
+
+// 2. a triple: every component finite and within +-1e15, the scene's own bound on a length (vv stays finite).  `subject`, `noun`: "point"
+//    and "coordinate", "disp of slot" and "component"
+template <typename T>
+bool triple_ok(const T *v, uint32_t i, const char *what, const char *subject, const char *noun)
+{
+    for (int c = 0; c < 3; ++c)
+        if (!std::isfinite(v[c]) || std::fabs((double)v[c]) > 1e15) {
+            snprintf(g_err, sizeof g_err, "%s: %s %u has a non-finite %s or one beyond +-1e15", what, subject, i, noun);
+            return false;
+        }
+    return true;
+}
+
+// 3. a radius in 0 .. 1e15, the scene's own bound on a radius: no intermediate of the inflated test overflows.  `before`, `after`: what
+//    stands around i, "radius[" and "] =" or "query " and "'s radius"
+template <typename T>
+bool radius_ok(T r, uint32_t i, const char *what, const char *before, const char *after)
+{
+    if (!(r >= T(0.0) && (double)r <= 1e15)) {                     // (NaN fails the first comparison)
+        snprintf(g_err, sizeof g_err, "%s: %s%u%s %g is not in 0 .. 1e15", what, before, i, after, (double)r);
+        return false;
+    }
+    return true;
+}
+
+// ok(real, i) for every element 0 .. n-1, in the scene's REAL
+template <typename F>
+bool each_valid(const rt_scene *s, uint32_t n, F &&ok)
+{
+    return by_precision(s, [&](auto real) {
+        for (uint32_t i = 0; i < n; ++i)
+            if (!ok(real, i)) return false;
+        return true;
+    });
+}
+
 // ---- ray queries (rt_intersect_rays*, rt_query.hpp) ----
 
 // The stream a ray query walks: the scene's plain per-origin stream, or -- for a scene created without bounds -- its items as a stream of
@@ -607,9 +730,11 @@ rt_status query_stream(rt_scene *s, hipStream_t stream, const void **nodes, uint
         HIP_TRY(hipMalloc(&p, (f32 ? sizeof(rt::Node<float>) : sizeof(rt::Node<double>)) * total));
         hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
         if (e == hipSuccess) {
-            const dim3 grid((total + 255) / 256), block(256);
-            if (f32) hipLaunchKernelGGL(rt::k_items_stream<float>, grid, block, 0, stream, static_cast<const rt::Item<float> *>(s->d_items), s->n_items, static_cast<rt::Node<float> *>(p));
-            else hipLaunchKernelGGL(rt::k_items_stream<double>, grid, block, 0, stream, static_cast<const rt::Item<double> *>(s->d_items), s->n_items, static_cast<rt::Node<double> *>(p));
+            by_precision(s, [&](auto real) {
+                using T = decltype(real);
+                hipLaunchKernelGGL(rt::k_items_stream<T>, dim3((total + 255) / 256), dim3(256), 0, stream, static_cast<const rt::Item<T> *>(s->d_items), s->n_items,
+                                   static_cast<rt::Node<T> *>(p));
+            });
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipEventRecord(ev, stream);
@@ -640,89 +765,62 @@ bool query_args_ok(const rt_scene *s, rt_query mode, const void *rays, const voi
         snprintf(g_err, sizeof g_err, "%s: NULL scene, rays or distance_out, n == 0 or unknown mode", what);
         return false;
     }
-    const uintptr_t esz = s->precision == RT_F32 ? sizeof(float) : sizeof(double);
-    for (const void *p : { rays, tmax, dist, normal })
-        if ((reinterpret_cast<uintptr_t>(p) % esz) != 0) { snprintf(g_err, sizeof g_err, "%s: REAL buffers must be %u-byte aligned", what, (unsigned)esz); return false; }
-    if ((reinterpret_cast<uintptr_t>(item) & 3u) != 0) { snprintf(g_err, sizeof g_err, "%s: item_out must be 4-byte aligned", what); return false; }
-    return true;
+    return aligned_ok(what, real_size(s), { { rays, "REAL buffers" }, { tmax, "REAL buffers" }, { dist, "REAL buffers" }, { normal, "REAL buffers" } })
+           && aligned_ok(what, 4, { { item, "item_out" } });
 }
 
-// The host entry's domain, the bounds rt_scene_create puts on the light and the eye: finite, |pos| <= 1e15, a unit direction (squared
-// length within 2e-3 of 1) and a tmax that is not NaN -- no intermediate of the walk overflows.
-template <typename T>
-bool query_rays_valid(const T *rays, const T *tmax, uint32_t n)
+// The host entry's domain: rays, and a tmax that is not NaN.  (The multi-hit, trace and order entries share it, message and all.)
+bool query_rays_valid(const rt_scene *s, const void *rays, const void *tmax, uint32_t n)
 {
-    for (uint32_t i = 0; i < n; ++i) {
-        const T *r = rays + 6 * (size_t)i;
-        for (int k = 0; k < 6; ++k) {
-            if (!std::isfinite(r[k]) || (k < 3 && std::fabs((double)r[k]) > 1e15)) {
-                snprintf(g_err, sizeof g_err, "rt_intersect_rays: ray %u has a non-finite component or |pos| > 1e15", i);
-                return false;
-            }
-        }
-        const double d2 = (double)r[3] * r[3] + (double)r[4] * r[4] + (double)r[5] * r[5];
-        if (std::fabs(d2 - 1.0) > 2e-3) {
-            snprintf(g_err, sizeof g_err, "rt_intersect_rays: ray %u's direction is not a unit vector (its squared length is %.6g)", i, d2);
-            return false;
-        }
-        if (tmax && std::isnan(tmax[i])) {
-            snprintf(g_err, sizeof g_err, "rt_intersect_rays: tmax[%u] is NaN", i);
-            return false;
-        }
-    }
-    return true;
+    return each_valid(s, n, [&](auto real, uint32_t i) {
+        using T = decltype(real);
+        return ray_ok(static_cast<const T *>(rays), i, "rt_intersect_rays", "") && not_nan_ok(static_cast<const T *>(tmax), i, "rt_intersect_rays", "tmax");
+    });
 }
 
-// One query launch on `stream`: counters != NULL runs the counting flavour (same bytes).
-template <typename T>
+// One query launch on `stream`: counters != NULL runs the counting flavour (same bytes); with an order, the rays in that order
+// (rt_order.hpp): the same walk, ray order[j] in lane j.
 rt_status enqueue_query(const rt_scene *s, const void *nodes, uint32_t n_nodes, rt_query mode, const void *rays, const void *tmax, uint32_t n,
-                        void *dist, void *normal, int32_t *item, rt::Counters *counters, hipStream_t stream, const uint32_t *order)
+                        void *dist, void *normal, int32_t *item, rt::Counters *counters, hipStream_t stream, const uint32_t *order = nullptr)
 {
-    const rt::QueryArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), static_cast<const rt::Item<T> *>(s->d_items), static_cast<const T *>(rays),
-                              static_cast<const T *>(tmax), static_cast<T *>(dist), static_cast<T *>(normal), item, counters, n_nodes, n };
-    const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
-    const bool any = mode == RT_QUERY_ANY;
-    if (order) {                                                     // the rays in a given order (rt_order.hpp): the same walk, ray order[j] in lane j
-        if (counters) {
-            if (any) hipLaunchKernelGGL((rt::k_query_rays_ordered<T, true, true>), grid, block, 0, stream, a, order);
-            else hipLaunchKernelGGL((rt::k_query_rays_ordered<T, true, false>), grid, block, 0, stream, a, order);
-        } else {
-            if (any) hipLaunchKernelGGL((rt::k_query_rays_ordered<T, false, true>), grid, block, 0, stream, a, order);
-            else hipLaunchKernelGGL((rt::k_query_rays_ordered<T, false, false>), grid, block, 0, stream, a, order);
-        }
-    } else if (counters) {
-        if (any) hipLaunchKernelGGL((rt::k_query_rays<T, true, true>), grid, block, 0, stream, a);
-        else hipLaunchKernelGGL((rt::k_query_rays<T, true, false>), grid, block, 0, stream, a);
-    } else {
-        if (any) hipLaunchKernelGGL((rt::k_query_rays<T, false, true>), grid, block, 0, stream, a);
-        else hipLaunchKernelGGL((rt::k_query_rays<T, false, false>), grid, block, 0, stream, a);
-    }
+    by_precision(s, [&](auto real) {
+        using T = decltype(real);
+        const rt::QueryArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), static_cast<const rt::Item<T> *>(s->d_items), static_cast<const T *>(rays),
+                                  static_cast<const T *>(tmax), static_cast<T *>(dist), static_cast<T *>(normal), item, counters, n_nodes, n };
+        with_flags([&](auto count, auto any, auto ordered) {
+            if constexpr (ordered()) hipLaunchKernelGGL((rt::k_query_rays_ordered<T, count(), any()>), query_grid(n), query_block(), 0, stream, a, order);
+            else hipLaunchKernelGGL((rt::k_query_rays<T, count(), any()>), query_grid(n), query_block(), 0, stream, a);
+        }, counters != nullptr, mode == RT_QUERY_ANY, order != nullptr);
+    });
     HIP_TRY(hipGetLastError());
     return RT_OK;
 }
 
-rt_status enqueue_query(const rt_scene *s, const void *nodes, uint32_t n_nodes, rt_query mode, const void *rays, const void *tmax, uint32_t n,
-                        void *dist, void *normal, int32_t *item, rt::Counters *counters, hipStream_t stream, const uint32_t *order = nullptr)
-{
-    return s->precision == RT_F32 ? enqueue_query<float>(s, nodes, n_nodes, mode, rays, tmax, n, dist, normal, item, counters, stream, order)
-                                  : enqueue_query<double>(s, nodes, n_nodes, mode, rays, tmax, n, dist, normal, item, counters, stream, order);
-}
-
-// A counting query's rt_stats: primary = rays, hits = results below tmax, the tests; every other counter 0.  Synchronises `stream`.
-rt_status read_query_stats(Context *c, hipStream_t stream, rt_stats *st)
+// A counting call's counters, their stripes summed into *h, and what every query reports of them in *st: primary = rays, hits = results
+// below tmax, the tests, the interval; every other field 0.  Synchronises `stream`.
+rt_status read_counters(Context *c, hipStream_t stream, rt::Counters *h, rt_stats *st)
 {
     std::vector<rt::Counters> stripes(rt::kCounterStripes);
     HIP_TRY(hipMemcpyAsync(stripes.data(), c->d_counters, sizeof(rt::Counters) * rt::kCounterStripes, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
-    rt::Counters h{};
-    for (const rt::Counters &k : stripes) { h.primary += k.primary; h.hits += k.hits; h.sphere_tests += k.sphere_tests; h.bound_tests += k.bound_tests; }
+    *h = rt::Counters{};
+    for (const rt::Counters &k : stripes) {
+        h->primary += k.primary; h->hits += k.hits; h->shadow += k.shadow; h->occluded += k.occluded;
+        h->sphere_tests += k.sphere_tests; h->bound_tests += k.bound_tests; h->primary_tests += k.primary_tests;
+    }
     float ms = 0.f;
     HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
     *st = rt_stats{};
-    st->primary = h.primary; st->hits = h.hits;
-    st->sphere_tests = h.sphere_tests; st->bound_tests = h.bound_tests; st->tests_executed = h.sphere_tests + h.bound_tests;
+    st->primary = h->primary; st->hits = h->hits;
+    st->sphere_tests = h->sphere_tests; st->bound_tests = h->bound_tests; st->tests_executed = h->sphere_tests + h->bound_tests;
     st->device_ms = ms;
     return RT_OK;
+}
+
+rt_status read_query_stats(Context *c, hipStream_t stream, rt_stats *st)
+{
+    rt::Counters h;
+    return read_counters(c, stream, &h, st);
 }
 
 // ---- multi-hit ray queries (rt_intersect_rays_multi*, rt_multihit.hpp) ----
@@ -734,64 +832,29 @@ bool multihit_args_ok(rt_multihit mode, uint32_t k, const uint32_t *hits, const 
         snprintf(g_err, sizeof g_err, "%s: k must be 1 .. %d and the mode closest (0) or all (1)", what, RT_MULTIHIT_MAX_K);
         return false;
     }
-    if ((reinterpret_cast<uintptr_t>(hits) & 3u) != 0) { snprintf(g_err, sizeof g_err, "%s: hits_out must be 4-byte aligned", what); return false; }
-    return true;
+    return aligned_ok(what, 4, { { hits, "hits_out" } });
 }
 
-template <typename T, bool COUNT, bool ALL>
-void launch_multihit(unsigned bucket, dim3 grid, dim3 block, hipStream_t stream, const rt::MultiArgs<T> &a, const uint32_t *order)
-{
-    if (order) {                                                     // the rays in a given order (rt_order.hpp)
-        switch (bucket) {
-        case 1: hipLaunchKernelGGL((rt::k_multihit_rays_ordered<T, COUNT, ALL, 1>), grid, block, 0, stream, a, order); break;
-        case 4: hipLaunchKernelGGL((rt::k_multihit_rays_ordered<T, COUNT, ALL, 4>), grid, block, 0, stream, a, order); break;
-        case 8: hipLaunchKernelGGL((rt::k_multihit_rays_ordered<T, COUNT, ALL, 8>), grid, block, 0, stream, a, order); break;
-        default: hipLaunchKernelGGL((rt::k_multihit_rays_ordered<T, COUNT, ALL, 16>), grid, block, 0, stream, a, order); break;
-        }
-        return;
-    }
-    switch (bucket) {
-    case 1: hipLaunchKernelGGL((rt::k_multihit_rays<T, COUNT, ALL, 1>), grid, block, 0, stream, a); break;
-    case 4: hipLaunchKernelGGL((rt::k_multihit_rays<T, COUNT, ALL, 4>), grid, block, 0, stream, a); break;
-    case 8: hipLaunchKernelGGL((rt::k_multihit_rays<T, COUNT, ALL, 8>), grid, block, 0, stream, a); break;
-    default: hipLaunchKernelGGL((rt::k_multihit_rays<T, COUNT, ALL, 16>), grid, block, 0, stream, a); break;
-    }
-}
-
-// One multi-hit launch on `stream`: the list capacity is the smallest bucket >= k (RT_DEBUG_MULTIHIT_BUCKET: a larger one); counters
-// != NULL runs the counting flavour (same bytes).
-template <typename T>
-rt_status enqueue_multihit(const rt_scene *s, const void *nodes, uint32_t n_nodes, rt_multihit mode, uint32_t k, const void *rays, const void *tmax,
-                           uint32_t n, void *dist, void *normal, int32_t *item, uint32_t *hits, rt::Counters *counters, hipStream_t stream,
-                           const uint32_t *order)
-{
-    const rt::MultiArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), static_cast<const rt::Item<T> *>(s->d_items), static_cast<const T *>(rays),
-                              static_cast<const T *>(tmax), static_cast<T *>(dist), static_cast<T *>(normal), item, hits, counters, n_nodes, n, k };
-    unsigned bucket = 0;
-    for (unsigned b : rt::kMultiBuckets)
-        if (bucket == 0 && b >= k) bucket = b;
-    const long long forced = knob(RT_DEBUG_MULTIHIT_BUCKET);
-    for (unsigned b : rt::kMultiBuckets)
-        if (forced == (long long)b && b >= k) bucket = b;
-    const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
-    const bool all = mode == RT_MULTIHIT_ALL;
-    if (counters) {
-        if (all) launch_multihit<T, true, true>(bucket, grid, block, stream, a, order);
-        else launch_multihit<T, true, false>(bucket, grid, block, stream, a, order);
-    } else {
-        if (all) launch_multihit<T, false, true>(bucket, grid, block, stream, a, order);
-        else launch_multihit<T, false, false>(bucket, grid, block, stream, a, order);
-    }
-    HIP_TRY(hipGetLastError());
-    return RT_OK;
-}
-
+// One multi-hit launch on `stream`: the list capacity is the smallest bucket >= k; counters != NULL runs the counting flavour (same
+// bytes); with an order, the rays in that order (rt_order.hpp).
 rt_status enqueue_multihit(const rt_scene *s, const void *nodes, uint32_t n_nodes, rt_multihit mode, uint32_t k, const void *rays, const void *tmax,
                            uint32_t n, void *dist, void *normal, int32_t *item, uint32_t *hits, rt::Counters *counters, hipStream_t stream,
                            const uint32_t *order = nullptr)
 {
-    return s->precision == RT_F32 ? enqueue_multihit<float>(s, nodes, n_nodes, mode, k, rays, tmax, n, dist, normal, item, hits, counters, stream, order)
-                                  : enqueue_multihit<double>(s, nodes, n_nodes, mode, k, rays, tmax, n, dist, normal, item, hits, counters, stream, order);
+    by_precision(s, [&](auto real) {
+        using T = decltype(real);
+        const rt::MultiArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), static_cast<const rt::Item<T> *>(s->d_items), static_cast<const T *>(rays),
+                                  static_cast<const T *>(tmax), static_cast<T *>(dist), static_cast<T *>(normal), item, hits, counters, n_nodes, n, k };
+        with_list_bucket(k, [&](auto bucket) {
+            constexpr int B = bucket();
+            with_flags([&](auto count, auto all, auto ordered) {
+                if constexpr (ordered()) hipLaunchKernelGGL((rt::k_multihit_rays_ordered<T, count(), all(), B>), query_grid(n), query_block(), 0, stream, a, order);
+                else hipLaunchKernelGGL((rt::k_multihit_rays<T, count(), all(), B>), query_grid(n), query_block(), 0, stream, a);
+            }, counters != nullptr, mode == RT_MULTIHIT_ALL, order != nullptr);
+        });
+    });
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
 }
 
 // ---- proximity queries (rt_near_spheres*, rt_near.hpp) ----
@@ -803,82 +866,36 @@ bool near_args_ok(const rt_scene *s, rt_near mode, uint32_t k, const void *point
     if (!s || !points || !gap || n == 0) { snprintf(g_err, sizeof g_err, "%s: NULL scene, points or gap_out, or n == 0", what); return false; }
     if (k == 0 || k > RT_NEAR_MAX_K) { snprintf(g_err, sizeof g_err, "%s: k must be 1 .. %d, not %u", what, RT_NEAR_MAX_K, k); return false; }
     if (mode != RT_NEAR_CLOSEST && mode != RT_NEAR_ALL) { snprintf(g_err, sizeof g_err, "%s: unknown mode %d (closest is 0, all is 1)", what, (int)mode); return false; }
-    const struct { const void *p; const char *name; } words[] = { { item, "item_out" }, { found, "found_out" }, { exclude, "exclude" }, { order, "order" } };
-    for (const auto &w : words)
-        if ((reinterpret_cast<uintptr_t>(w.p) & 3u) != 0) { snprintf(g_err, sizeof g_err, "%s: %s must be 4-byte aligned", what, w.name); return false; }
-    const uintptr_t esz = s->precision == RT_F32 ? sizeof(float) : sizeof(double);
-    for (const void *p : { points, radius, gap })
-        if ((reinterpret_cast<uintptr_t>(p) % esz) != 0) { snprintf(g_err, sizeof g_err, "%s: REAL buffers must be %u-byte aligned", what, (unsigned)esz); return false; }
-    return true;
+    return aligned_ok(what, 4, { { item, "item_out" }, { found, "found_out" }, { exclude, "exclude" }, { order, "order" } })
+           && aligned_ok(what, real_size(s), { { points, "REAL buffers" }, { radius, "REAL buffers" }, { gap, "REAL buffers" } });
 }
 
-// The host entry's domain: points finite with |coordinate| <= 1e15 (the scene's own domain: vv stays finite), a radius that is not NaN.
-template <typename T>
-bool near_points_valid(const T *points, const T *radius, uint32_t n, const char *what)
+// The host entry's domain: points, and a radius that is not NaN.
+bool near_points_valid(const rt_scene *s, const void *points, const void *radius, uint32_t n, const char *what)
 {
-    for (uint32_t i = 0; i < n; ++i) {
-        for (int c = 0; c < 3; ++c) {
-            const T v = points[3 * (size_t)i + c];
-            if (!std::isfinite(v) || std::fabs((double)v) > 1e15) {
-                snprintf(g_err, sizeof g_err, "%s: point %u has a non-finite coordinate or one beyond +-1e15", what, i);
-                return false;
-            }
-        }
-        if (radius && std::isnan(radius[i])) { snprintf(g_err, sizeof g_err, "%s: radius[%u] is NaN", what, i); return false; }
-    }
-    return true;
+    return each_valid(s, n, [&](auto real, uint32_t i) {
+        using T = decltype(real);
+        return triple_ok(static_cast<const T *>(points) + 3 * (size_t)i, i, what, "point", "coordinate") && not_nan_ok(static_cast<const T *>(radius), i, what, "radius");
+    });
 }
 
-template <typename T, bool COUNT, bool ALL, bool ORDERED>
-void launch_near(unsigned bucket, dim3 grid, dim3 block, hipStream_t stream, const rt::NearArgs<T> &a)
-{
-    switch (bucket) {
-    case 1: hipLaunchKernelGGL((rt::k_near_spheres<T, COUNT, ALL, ORDERED, 1>), grid, block, 0, stream, a); break;
-    case 4: hipLaunchKernelGGL((rt::k_near_spheres<T, COUNT, ALL, ORDERED, 4>), grid, block, 0, stream, a); break;
-    case 8: hipLaunchKernelGGL((rt::k_near_spheres<T, COUNT, ALL, ORDERED, 8>), grid, block, 0, stream, a); break;
-    default: hipLaunchKernelGGL((rt::k_near_spheres<T, COUNT, ALL, ORDERED, 16>), grid, block, 0, stream, a); break;
-    }
-}
-
-template <typename T, bool COUNT, bool ALL>
-void launch_near(unsigned bucket, dim3 grid, dim3 block, hipStream_t stream, const rt::NearArgs<T> &a)
-{
-    if (a.order) launch_near<T, COUNT, ALL, true>(bucket, grid, block, stream, a);
-    else launch_near<T, COUNT, ALL, false>(bucket, grid, block, stream, a);
-}
-
-// One proximity launch on `stream`: the list capacity is the smallest bucket >= k (RT_DEBUG_MULTIHIT_BUCKET: a larger one, as for the
-// multi-hit lists); counters != NULL runs the counting flavour (same bytes).
-template <typename T>
-rt_status enqueue_near(const void *nodes, uint32_t n_nodes, rt_near mode, uint32_t k, const void *points, const void *radius, uint32_t n,
-                       const int32_t *exclude, const uint32_t *order, void *gap, int32_t *item, uint32_t *found, rt::Counters *counters, hipStream_t stream)
-{
-    const rt::NearArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), static_cast<const T *>(points), static_cast<const T *>(radius), exclude, order,
-                             static_cast<T *>(gap), item, found, counters, n_nodes, n, k };
-    unsigned bucket = 0;
-    for (unsigned b : rt::kMultiBuckets)
-        if (bucket == 0 && b >= k) bucket = b;
-    const long long forced = knob(RT_DEBUG_MULTIHIT_BUCKET);
-    for (unsigned b : rt::kMultiBuckets)
-        if (forced == (long long)b && b >= k) bucket = b;
-    const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
-    const bool all = mode == RT_NEAR_ALL;
-    if (counters) {
-        if (all) launch_near<T, true, true>(bucket, grid, block, stream, a);
-        else launch_near<T, true, false>(bucket, grid, block, stream, a);
-    } else {
-        if (all) launch_near<T, false, true>(bucket, grid, block, stream, a);
-        else launch_near<T, false, false>(bucket, grid, block, stream, a);
-    }
-    HIP_TRY(hipGetLastError());
-    return RT_OK;
-}
-
+// One proximity launch on `stream`: the list capacity as for the multi-hit lists; counters != NULL runs the counting flavour (same bytes).
 rt_status enqueue_near(const rt_scene *s, const void *nodes, uint32_t n_nodes, rt_near mode, uint32_t k, const void *points, const void *radius, uint32_t n,
                        const int32_t *exclude, const uint32_t *order, void *gap, int32_t *item, uint32_t *found, rt::Counters *counters, hipStream_t stream)
 {
-    return s->precision == RT_F32 ? enqueue_near<float>(nodes, n_nodes, mode, k, points, radius, n, exclude, order, gap, item, found, counters, stream)
-                                  : enqueue_near<double>(nodes, n_nodes, mode, k, points, radius, n, exclude, order, gap, item, found, counters, stream);
+    by_precision(s, [&](auto real) {
+        using T = decltype(real);
+        const rt::NearArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), static_cast<const T *>(points), static_cast<const T *>(radius), exclude, order,
+                                 static_cast<T *>(gap), item, found, counters, n_nodes, n, k };
+        with_list_bucket(k, [&](auto bucket) {
+            constexpr int B = bucket();
+            with_flags([&](auto count, auto all, auto ordered) {
+                hipLaunchKernelGGL((rt::k_near_spheres<T, count(), all(), ordered(), B>), query_grid(n), query_block(), 0, stream, a);
+            }, counters != nullptr, mode == RT_NEAR_ALL, order != nullptr);
+        });
+    });
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
 }
 
 // ---- sphere casts (rt_sweep_spheres*, rt_sweep.hpp) ----
@@ -889,76 +906,35 @@ bool sweep_args_ok(const rt_scene *s, rt_sweep mode, const void *rays, const voi
 {
     if (!s || !rays || !dist || n == 0) { snprintf(g_err, sizeof g_err, "%s: NULL scene, rays or distance_out, or n == 0", what); return false; }
     if (mode != RT_SWEEP_NEAREST && mode != RT_SWEEP_ANY) { snprintf(g_err, sizeof g_err, "%s: unknown mode %d (nearest is 0, any is 1)", what, (int)mode); return false; }
-    const struct { const void *p; const char *name; } words[] = { { item, "item_out" }, { exclude, "exclude" }, { order, "order" } };
-    for (const auto &w : words)
-        if ((reinterpret_cast<uintptr_t>(w.p) & 3u) != 0) { snprintf(g_err, sizeof g_err, "%s: %s must be 4-byte aligned", what, w.name); return false; }
-    const uintptr_t esz = s->precision == RT_F32 ? sizeof(float) : sizeof(double);
-    const struct { const void *p; const char *name; } reals[] = { { rays, "rays" }, { radius, "radius" }, { tmax, "tmax" }, { dist, "distance_out" }, { normal, "normal_out" } };
-    for (const auto &w : reals)
-        if ((reinterpret_cast<uintptr_t>(w.p) % esz) != 0) { snprintf(g_err, sizeof g_err, "%s: %s must be %u-byte aligned", what, w.name, (unsigned)esz); return false; }
-    return true;
+    return aligned_ok(what, 4, { { item, "item_out" }, { exclude, "exclude" }, { order, "order" } })
+           && aligned_ok(what, real_size(s), { { rays, "rays" }, { radius, "radius" }, { tmax, "tmax" }, { dist, "distance_out" }, { normal, "normal_out" } });
 }
 
-// The host entry's domain: the rays and tmax of rt_intersect_rays (finite, |pos| <= 1e15, a unit direction, a tmax that is not NaN) and a
-// radius in 0 .. 1e15 -- the scene's own bound on a radius, so that no intermediate of the inflated test overflows.
-template <typename T>
-bool sweep_casts_valid(const T *rays, const T *radius, const T *tmax, uint32_t n, const char *what)
+// The host entry's domain: per cast the ray, a radius in 0 .. 1e15 and a tmax that is not NaN.
+bool sweep_casts_valid(const rt_scene *s, const void *rays, const void *radius, const void *tmax, uint32_t n, const char *what)
 {
-    for (uint32_t i = 0; i < n; ++i) {
-        const T *r = rays + 6 * (size_t)i;
-        for (int k = 0; k < 6; ++k) {
-            if (!std::isfinite(r[k]) || (k < 3 && std::fabs((double)r[k]) > 1e15)) {
-                snprintf(g_err, sizeof g_err, "%s: rays: ray %u has a non-finite component or |pos| > 1e15", what, i);
-                return false;
-            }
-        }
-        const double d2 = (double)r[3] * r[3] + (double)r[4] * r[4] + (double)r[5] * r[5];
-        if (std::fabs(d2 - 1.0) > 2e-3) {
-            snprintf(g_err, sizeof g_err, "%s: rays: ray %u's direction is not a unit vector (its squared length is %.6g)", what, i, d2);
-            return false;
-        }
-        if (radius && !(radius[i] >= T(0.0) && (double)radius[i] <= 1e15)) {         // (NaN fails the first comparison)
-            snprintf(g_err, sizeof g_err, "%s: radius[%u] = %g is not in 0 .. 1e15", what, i, (double)radius[i]);
-            return false;
-        }
-        if (tmax && std::isnan(tmax[i])) { snprintf(g_err, sizeof g_err, "%s: tmax[%u] is NaN", what, i); return false; }
-    }
-    return true;
-}
-
-template <typename T, bool COUNT, bool ANY>
-void launch_sweep(dim3 grid, dim3 block, hipStream_t stream, const rt::SweepArgs<T> &a)
-{
-    if (a.order) hipLaunchKernelGGL((rt::k_sweep_spheres<T, COUNT, ANY, true>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((rt::k_sweep_spheres<T, COUNT, ANY, false>), grid, block, 0, stream, a);
+    return each_valid(s, n, [&](auto real, uint32_t i) {
+        using T = decltype(real);
+        return ray_ok(static_cast<const T *>(rays), i, what, ": rays") && (!radius || radius_ok(static_cast<const T *>(radius)[i], i, what, "radius[", "] ="))
+               && not_nan_ok(static_cast<const T *>(tmax), i, what, "tmax");
+    });
 }
 
 // One cast launch on `stream`: counters != NULL runs the counting flavour (same bytes).
-template <typename T>
 rt_status enqueue_sweep(const rt_scene *s, const void *nodes, uint32_t n_nodes, rt_sweep mode, const void *rays, const void *radius, const void *tmax, uint32_t n,
                         const int32_t *exclude, const uint32_t *order, void *dist, void *normal, int32_t *item, rt::Counters *counters, hipStream_t stream)
 {
-    const rt::SweepArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), static_cast<const rt::Item<T> *>(s->d_items), static_cast<const T *>(rays),
-                              static_cast<const T *>(radius), static_cast<const T *>(tmax), exclude, order, static_cast<T *>(dist), static_cast<T *>(normal),
-                              item, counters, n_nodes, n };
-    const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
-    const bool any = mode == RT_SWEEP_ANY;
-    if (counters) {
-        if (any) launch_sweep<T, true, true>(grid, block, stream, a);
-        else launch_sweep<T, true, false>(grid, block, stream, a);
-    } else {
-        if (any) launch_sweep<T, false, true>(grid, block, stream, a);
-        else launch_sweep<T, false, false>(grid, block, stream, a);
-    }
+    by_precision(s, [&](auto real) {
+        using T = decltype(real);
+        const rt::SweepArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), static_cast<const rt::Item<T> *>(s->d_items), static_cast<const T *>(rays),
+                                  static_cast<const T *>(radius), static_cast<const T *>(tmax), exclude, order, static_cast<T *>(dist), static_cast<T *>(normal),
+                                  item, counters, n_nodes, n };
+        with_flags([&](auto count, auto any, auto ordered) {
+            hipLaunchKernelGGL((rt::k_sweep_spheres<T, count(), any(), ordered()>), query_grid(n), query_block(), 0, stream, a);
+        }, counters != nullptr, mode == RT_SWEEP_ANY, order != nullptr);
+    });
     HIP_TRY(hipGetLastError());
     return RT_OK;
-}
-
-rt_status enqueue_sweep(const rt_scene *s, const void *nodes, uint32_t n_nodes, rt_sweep mode, const void *rays, const void *radius, const void *tmax, uint32_t n,
-                        const int32_t *exclude, const uint32_t *order, void *dist, void *normal, int32_t *item, rt::Counters *counters, hipStream_t stream)
-{
-    return s->precision == RT_F32 ? enqueue_sweep<float>(s, nodes, n_nodes, mode, rays, radius, tmax, n, exclude, order, dist, normal, item, counters, stream)
-                                  : enqueue_sweep<double>(s, nodes, n_nodes, mode, rays, radius, tmax, n, exclude, order, dist, normal, item, counters, stream);
 }
 
 // ---- contact pairs (rt_scene_contacts*, rt_contacts.hpp) ----
@@ -971,13 +947,8 @@ bool contacts_args_ok(const rt_scene *s, double margin, uint32_t capacity, const
     if (std::isnan(margin)) { snprintf(g_err, sizeof g_err, "%s: margin is NaN", what); return false; }
     if (capacity > 0x7FFFFFFFu) { snprintf(g_err, sizeof g_err, "%s: capacity %u is above 2^31 - 1", what, capacity); return false; }
     if (gap && !pairs) { snprintf(g_err, sizeof g_err, "%s: gap_out without pairs_out", what); return false; }
-    if ((reinterpret_cast<uintptr_t>(pairs) & 3u) != 0) { snprintf(g_err, sizeof g_err, "%s: pairs_out must be 4-byte aligned", what); return false; }
-    const struct { const void *p; const char *name; } longs[] = { { offsets, "offsets_out" }, { total, "total_out" } };
-    for (const auto &w : longs)
-        if ((reinterpret_cast<uintptr_t>(w.p) & 7u) != 0) { snprintf(g_err, sizeof g_err, "%s: %s must be 8-byte aligned", what, w.name); return false; }
-    const uintptr_t esz = s->precision == RT_F32 ? sizeof(float) : sizeof(double);
-    if ((reinterpret_cast<uintptr_t>(gap) % esz) != 0) { snprintf(g_err, sizeof g_err, "%s: gap_out must be %u-byte aligned", what, (unsigned)esz); return false; }
-    return true;
+    return aligned_ok(what, 4, { { pairs, "pairs_out" } }) && aligned_ok(what, 8, { { offsets, "offsets_out" }, { total, "total_out" } })
+           && aligned_ok(what, real_size(s), { { gap, "gap_out" } });
 }
 
 // The three launches of the scan on `stream`: the counts of `n` lists into offsets[n + 1] in the workspace and, where given, in the caller's
@@ -1008,57 +979,49 @@ rt_status contacts_begin(rt_scene *s, const void *nodes, uint32_t n_nodes, hipSt
     if (const rt_status st = w.make_room(n, (table ? sizeof(uint32_t) * n : 0) + 256, &behind); st != RT_OK) return st;
     if (table) {
         uint32_t *const item_node = reinterpret_cast<uint32_t *>(behind);
-        const dim3 grid((n_nodes + 255) / 256), block(256);
         hipError_t e = hipMemsetAsync(item_node, 0xFF, sizeof(uint32_t) * n, stream);
         if (e != hipSuccess) { (void)hipFree(w.d); w.d = nullptr; return hip_fail(e, "hipMemsetAsync(item_node)", __LINE__); }
-        if (s->precision == RT_F32) hipLaunchKernelGGL(rt::k_contact_item_nodes<float>, grid, block, 0, stream, static_cast<const rt::Node<float> *>(nodes), n_nodes, s->n_items, item_node);
-        else hipLaunchKernelGGL(rt::k_contact_item_nodes<double>, grid, block, 0, stream, static_cast<const rt::Node<double> *>(nodes), n_nodes, s->n_items, item_node);
+        by_precision(s, [&](auto real) {
+            using T = decltype(real);
+            hipLaunchKernelGGL(rt::k_contact_item_nodes<T>, dim3((n_nodes + 255) / 256), dim3(256), 0, stream, static_cast<const rt::Node<T> *>(nodes), n_nodes, s->n_items, item_node);
+        });
         if ((e = hipGetLastError()) != hipSuccess) { (void)hipFree(w.d); w.d = nullptr; return hip_fail(e, "k_contact_item_nodes", __LINE__); }
         s->d_contacts_item_node = item_node;
     }
     return RT_OK;
 }
 
-// The first pass and the scan on `stream`: counts, then offsets[n_items + 1] in the workspace and, where given, in the caller's device
-// memory.  counters != NULL runs the counting flavour (same counts).
-template <typename T>
-rt_status enqueue_contacts_count(const rt_scene *s, const void *nodes, uint32_t n_nodes, double margin, uint64_t *offsets_out, uint64_t *total_out,
-                                 rt::Counters *counters, hipStream_t stream)
-{
-    const uint32_t n = s->n_items;
-    const uint32_t *const item_node = s->n_nodes ? (s->d_item_node ? s->d_item_node : s->d_contacts_item_node) : nullptr;
-    const rt::ContactArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), item_node, s->contacts.counts, nullptr, nullptr, nullptr, counters, (T)margin, n_nodes, n, 0u };
-    const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
-    if (counters) hipLaunchKernelGGL((rt::k_contact_pairs<T, true, false>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((rt::k_contact_pairs<T, false, false>), grid, block, 0, stream, a);
-    HIP_TRY(hipGetLastError());
-    return enqueue_list_scan(s->contacts, n, offsets_out, total_out, stream);
-}
+// Where item i's own node lies in the stream the contacts and impacts walks skip from: the dynamic scene's table, or contacts_begin's.
+inline const uint32_t *contact_item_node(const rt_scene *s) { return s->n_nodes ? (s->d_item_node ? s->d_item_node : s->d_contacts_item_node) : nullptr; }
 
-rt_status enqueue_contacts_count(const rt_scene *s, const void *nodes, uint32_t n_nodes, double margin, uint64_t *offsets_out, uint64_t *total_out,
-                                 rt::Counters *counters, hipStream_t stream)
+// One pass of the walk on `stream`.  The first (fill == false) counts; counters != NULL runs its counting flavour (same counts).  The
+// second is the same walk, pair offsets[i] + rank written where it lies below `capacity`.
+rt_status enqueue_contacts_pass(const rt_scene *s, const void *nodes, uint32_t n_nodes, double margin, bool fill, uint32_t capacity, int32_t *pairs, void *gap,
+                                rt::Counters *counters, hipStream_t stream)
 {
-    return s->precision == RT_F32 ? enqueue_contacts_count<float>(s, nodes, n_nodes, margin, offsets_out, total_out, counters, stream)
-                                  : enqueue_contacts_count<double>(s, nodes, n_nodes, margin, offsets_out, total_out, counters, stream);
-}
-
-// The second pass on `stream`: the same walk, pair offsets[i] + rank written where it lies below `capacity`.
-template <typename T>
-rt_status enqueue_contacts_fill(const rt_scene *s, const void *nodes, uint32_t n_nodes, double margin, uint32_t capacity, int32_t *pairs, void *gap, hipStream_t stream)
-{
-    const uint32_t n = s->n_items;
-    const uint32_t *const item_node = s->n_nodes ? (s->d_item_node ? s->d_item_node : s->d_contacts_item_node) : nullptr;
-    const rt::ContactArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), item_node, nullptr, s->contacts.offsets, pairs, static_cast<T *>(gap), nullptr, (T)margin, n_nodes, n, capacity };
-    const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
-    hipLaunchKernelGGL((rt::k_contact_pairs<T, false, true>), grid, block, 0, stream, a);
+    by_precision(s, [&](auto real) {
+        using T = decltype(real);
+        const ListSpace &w = s->contacts;
+        const rt::ContactArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), contact_item_node(s), fill ? nullptr : w.counts, fill ? w.offsets : nullptr, pairs,
+                                    static_cast<T *>(gap), counters, (T)margin, n_nodes, s->n_items, capacity };
+        if (fill) hipLaunchKernelGGL((rt::k_contact_pairs<T, false, true>), query_grid(s->n_items), query_block(), 0, stream, a);
+        else with_flags([&](auto count) { hipLaunchKernelGGL((rt::k_contact_pairs<T, count(), false>), query_grid(s->n_items), query_block(), 0, stream, a); }, counters != nullptr);
+    });
     HIP_TRY(hipGetLastError());
     return RT_OK;
 }
 
+// The first pass and the scan: counts, then offsets[n_items + 1] in the workspace and, where given, in the caller's device memory.
+rt_status enqueue_contacts_count(const rt_scene *s, const void *nodes, uint32_t n_nodes, double margin, uint64_t *offsets_out, uint64_t *total_out,
+                                 rt::Counters *counters, hipStream_t stream)
+{
+    const rt_status st = enqueue_contacts_pass(s, nodes, n_nodes, margin, false, 0u, nullptr, nullptr, counters, stream);
+    return st != RT_OK ? st : enqueue_list_scan(s->contacts, s->n_items, offsets_out, total_out, stream);
+}
+
 rt_status enqueue_contacts_fill(const rt_scene *s, const void *nodes, uint32_t n_nodes, double margin, uint32_t capacity, int32_t *pairs, void *gap, hipStream_t stream)
 {
-    return s->precision == RT_F32 ? enqueue_contacts_fill<float>(s, nodes, n_nodes, margin, capacity, pairs, gap, stream)
-                                  : enqueue_contacts_fill<double>(s, nodes, n_nodes, margin, capacity, pairs, gap, stream);
+    return enqueue_contacts_pass(s, nodes, n_nodes, margin, true, capacity, pairs, gap, nullptr, stream);
 }
 
 // ---- impact pairs (rt_scene_impacts*, rt_impacts.hpp) ----
@@ -1070,31 +1033,36 @@ bool impacts_args_ok(const rt_scene *s, const void *disp, uint32_t capacity, con
     if (!s || !disp || !total) { snprintf(g_err, sizeof g_err, "%s: NULL scene, disp or total_out", what); return false; }
     if (capacity > 0x7FFFFFFFu) { snprintf(g_err, sizeof g_err, "%s: capacity %u is above 2^31 - 1", what, capacity); return false; }
     if (time && !pairs) { snprintf(g_err, sizeof g_err, "%s: time_out without pairs_out", what); return false; }
-    if ((reinterpret_cast<uintptr_t>(pairs) & 3u) != 0) { snprintf(g_err, sizeof g_err, "%s: pairs_out must be 4-byte aligned", what); return false; }
-    const struct { const void *p; const char *name; } longs[] = { { offsets, "offsets_out" }, { total, "total_out" } };
-    for (const auto &w : longs)
-        if ((reinterpret_cast<uintptr_t>(w.p) & 7u) != 0) { snprintf(g_err, sizeof g_err, "%s: %s must be 8-byte aligned", what, w.name); return false; }
-    const uintptr_t esz = s->precision == RT_F32 ? sizeof(float) : sizeof(double);
-    const struct { const void *p; const char *name; } reals[] = { { disp, "disp" }, { time, "time_out" } };
-    for (const auto &w : reals)
-        if ((reinterpret_cast<uintptr_t>(w.p) % esz) != 0) { snprintf(g_err, sizeof g_err, "%s: %s must be %u-byte aligned", what, w.name, (unsigned)esz); return false; }
-    return true;
+    return aligned_ok(what, 4, { { pairs, "pairs_out" } }) && aligned_ok(what, 8, { { offsets, "offsets_out" }, { total, "total_out" } })
+           && aligned_ok(what, real_size(s), { { disp, "disp" }, { time, "time_out" } });
 }
 
-// The host entry's domain: every component finite and within +-1e15, the scene's own bound on a length.
-template <typename T>
-bool impacts_disp_valid(const T *disp, uint32_t n_items, const char *what)
+// The host entry's domain: the displacement of every slot.
+bool impacts_disp_valid(const rt_scene *s, const void *disp, uint32_t n_items, const char *what)
 {
-    for (size_t k = 0; k < 3 * (size_t)n_items; ++k)
-        if (!std::isfinite(disp[k]) || std::fabs((double)disp[k]) > 1e15) {
-            snprintf(g_err, sizeof g_err, "%s: disp of slot %u has a non-finite component or one beyond +-1e15", what, (unsigned)(k / 3));
-            return false;
-        }
-    return true;
+    return each_valid(s, n_items, [&](auto real, uint32_t i) {
+        return triple_ok(static_cast<const decltype(real) *>(disp) + 3 * (size_t)i, i, what, "disp of slot", "component");
+    });
 }
 
-// Room for a motion table of `n_nodes` nodes in *table (its nodes' lengths, their chunk maxima, the call's magnitude and the bound nodes'
-// radii behind it).  `w`: the workspace behind whose event the calls that use this table run -- a table that has to grow waits for it.
+// Where the parts of a motion table of `cap` nodes lie, in bytes: the nodes' motions at 0, their lengths, the lengths' chunk maxima, the
+// call's magnitude (a word of its own) and the bound nodes' radii.
+struct MotionLayout { size_t length, chunk, magnitude, radius, bytes; };
+MotionLayout motion_table_layout(size_t esz, uint32_t cap)
+{
+    const auto padded = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
+    const size_t n = cap ? cap : 1, n_chunks = (n + rt::kMotionChunk - 1) / rt::kMotionChunk;
+    MotionLayout l{};
+    l.length = padded(4 * esz * n);
+    l.chunk = l.length + padded(esz * n);
+    l.magnitude = l.chunk + padded(esz * n_chunks);
+    l.radius = l.magnitude + 256;
+    l.bytes = l.radius + padded(esz * n);
+    return l;
+}
+
+// Room for a motion table of `n_nodes` nodes in *table.  `w`: the workspace behind whose event the calls that use this table run -- a
+// table that has to grow waits for it.
 rt_status motion_table_begin(rt_scene *s, const ListSpace &w, void **table, uint32_t *cap, uint32_t n_nodes, const char *what)
 {
     if (n_nodes <= *cap && *table) return RT_OK;
@@ -1103,11 +1071,9 @@ rt_status motion_table_begin(rt_scene *s, const ListSpace &w, void **table, uint
         HIP_TRY(hipFree(*table));
         *table = nullptr; *cap = 0;
     }
-    const size_t esz = s->precision == RT_F32 ? sizeof(float) : sizeof(double);
-    const size_t n = n_nodes ? n_nodes : 1, n_chunks = (n + rt::kMotionChunk - 1) / rt::kMotionChunk;
-    const size_t o_length = (4 * esz * n + 255) & ~(size_t)255, o_chunk = o_length + ((esz * n + 255) & ~(size_t)255);
-    const size_t o_radius = o_chunk + ((esz * n_chunks + 255) & ~(size_t)255) + 256;                   // (+ the call's magnitude, a word of its own)
-    HIP_TRY(hipMalloc(table, o_radius + ((esz * n + 255) & ~(size_t)255)));
+    const size_t esz = real_size(s);
+    const MotionLayout l = motion_table_layout(esz, n_nodes);
+    HIP_TRY(hipMalloc(table, l.bytes));
     *cap = n_nodes;
     // the radii of the bound nodes: a static scene's never change and go up once; a dynamic scene's are gathered per call
     if (!s->dynamic && s->n_nodes != 0u) {
@@ -1115,7 +1081,7 @@ rt_status motion_table_begin(rt_scene *s, const ListSpace &w, void **table, uint
             snprintf(g_err, sizeof g_err, "%s: internal: the scene kept no radii for its %u nodes", what, s->n_nodes);
             return RT_ERR_INVALID_ARGUMENT;
         }
-        HIP_TRY(hipMemcpy(static_cast<uint8_t *>(*table) + o_radius, s->h_node_radius.data(), s->h_node_radius.size(), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(static_cast<uint8_t *>(*table) + l.radius, s->h_node_radius.data(), s->h_node_radius.size(), hipMemcpyHostToDevice));
     }
     return RT_OK;
 }
@@ -1132,16 +1098,11 @@ template <typename T> struct ImpactsSpace { rt::Motion<T> *motion; T *length, *c
 template <typename T>
 ImpactsSpace<T> motion_table_space(void *table, uint32_t cap)
 {
-    const size_t n = cap ? cap : 1;
-    const size_t n_chunks = (n + rt::kMotionChunk - 1) / rt::kMotionChunk;
-    const size_t o_length = (4 * sizeof(T) * n + 255) & ~(size_t)255, o_chunk = o_length + ((sizeof(T) * n + 255) & ~(size_t)255);
-    const size_t o_magnitude = o_chunk + ((sizeof(T) * n_chunks + 255) & ~(size_t)255);
+    const MotionLayout l = motion_table_layout(sizeof(T), cap);
     uint8_t *const d = static_cast<uint8_t *>(table);
-    return { reinterpret_cast<rt::Motion<T> *>(d), reinterpret_cast<T *>(d + o_length), reinterpret_cast<T *>(d + o_chunk), reinterpret_cast<T *>(d + o_magnitude),
-             reinterpret_cast<T *>(d + o_magnitude + 256) };
+    return { reinterpret_cast<rt::Motion<T> *>(d), reinterpret_cast<T *>(d + l.length), reinterpret_cast<T *>(d + l.chunk), reinterpret_cast<T *>(d + l.magnitude),
+             reinterpret_cast<T *>(d + l.radius) };
 }
-template <typename T>
-ImpactsSpace<T> impacts_space(const rt_scene *s) { return motion_table_space<T>(s->d_impacts, s->impacts_cap); }
 
 // The motion table of one call into `w`, on `stream`: *w.magnitude must already be 0 or hold what the call folds in besides the scene.
 // disp == NULL: the scene stands still (every e and D is 0).
@@ -1160,51 +1121,39 @@ rt_status enqueue_motion_table(const rt_scene *s, const rt::Node<T> *st, uint32_
     return RT_OK;
 }
 
-// The motion table, the first pass and the scan on `stream`.  counters != NULL runs the counting flavour (same counts).
-template <typename T>
+// One pass of the walk on `stream`.  The first (fill == false) makes the motion table and counts; counters != NULL runs its counting
+// flavour (same counts).  The second is the same walk over the table the first left, pair offsets[i] + rank written below `capacity`.
+rt_status enqueue_impacts_pass(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *disp, bool fill, uint32_t capacity, int32_t *pairs, void *time,
+                               rt::Counters *counters, hipStream_t stream)
+{
+    return by_precision(s, [&](auto real) -> rt_status {
+        using T = decltype(real);
+        const ImpactsSpace<T> w = motion_table_space<T>(s->d_impacts, s->impacts_cap);
+        const rt::Node<T> *const st = static_cast<const rt::Node<T> *>(nodes);
+        if (!fill) {
+            HIP_TRY(hipMemsetAsync(w.magnitude, 0, sizeof(T), stream));
+            if (const rt_status mt = enqueue_motion_table<T>(s, st, n_nodes, static_cast<const T *>(disp), w, stream); mt != RT_OK) return mt;
+        }
+        const rt::ImpactArgs<T> a{ st, w.motion, w.magnitude, contact_item_node(s), fill ? nullptr : s->contacts.counts, fill ? s->contacts.offsets : nullptr, pairs,
+                                   static_cast<T *>(time), counters, n_nodes, s->n_items, capacity };
+        if (fill) hipLaunchKernelGGL((rt::k_impact_pairs<T, false, true>), query_grid(s->n_items), query_block(), 0, stream, a);
+        else with_flags([&](auto count) { hipLaunchKernelGGL((rt::k_impact_pairs<T, count(), false>), query_grid(s->n_items), query_block(), 0, stream, a); }, counters != nullptr);
+        HIP_TRY(hipGetLastError());
+        return RT_OK;
+    });
+}
+
+// The motion table, the first pass and the scan.
 rt_status enqueue_impacts_count(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *disp, uint64_t *offsets_out, uint64_t *total_out,
                                 rt::Counters *counters, hipStream_t stream)
 {
-    const uint32_t n = s->n_items;
-    const ImpactsSpace<T> w = impacts_space<T>(s);
-    const rt::Node<T> *const st = static_cast<const rt::Node<T> *>(nodes);
-    HIP_TRY(hipMemsetAsync(w.magnitude, 0, sizeof(T), stream));
-    if (const rt_status mt = enqueue_motion_table<T>(s, st, n_nodes, static_cast<const T *>(disp), w, stream); mt != RT_OK) return mt;
-    const uint32_t *const item_node = s->n_nodes ? (s->d_item_node ? s->d_item_node : s->d_contacts_item_node) : nullptr;
-    const rt::ImpactArgs<T> a{ st, w.motion, w.magnitude, item_node, s->contacts.counts, nullptr, nullptr, nullptr, counters, n_nodes, n, 0u };
-    const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
-    if (counters) hipLaunchKernelGGL((rt::k_impact_pairs<T, true, false>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((rt::k_impact_pairs<T, false, false>), grid, block, 0, stream, a);
-    HIP_TRY(hipGetLastError());
-    return enqueue_list_scan(s->contacts, n, offsets_out, total_out, stream);
-}
-
-rt_status enqueue_impacts_count(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *disp, uint64_t *offsets_out, uint64_t *total_out,
-                                rt::Counters *counters, hipStream_t stream)
-{
-    return s->precision == RT_F32 ? enqueue_impacts_count<float>(s, nodes, n_nodes, disp, offsets_out, total_out, counters, stream)
-                                  : enqueue_impacts_count<double>(s, nodes, n_nodes, disp, offsets_out, total_out, counters, stream);
-}
-
-// The second pass on `stream`: the same walk over the motion table the first pass left, pair offsets[i] + rank written below `capacity`.
-template <typename T>
-rt_status enqueue_impacts_fill(const rt_scene *s, const void *nodes, uint32_t n_nodes, uint32_t capacity, int32_t *pairs, void *time, hipStream_t stream)
-{
-    const uint32_t n = s->n_items;
-    const uint32_t *const item_node = s->n_nodes ? (s->d_item_node ? s->d_item_node : s->d_contacts_item_node) : nullptr;
-    const ImpactsSpace<T> w = impacts_space<T>(s);
-    const rt::ImpactArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), w.motion, w.magnitude, item_node, nullptr, s->contacts.offsets, pairs, static_cast<T *>(time), nullptr,
-                               n_nodes, n, capacity };
-    const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
-    hipLaunchKernelGGL((rt::k_impact_pairs<T, false, true>), grid, block, 0, stream, a);
-    HIP_TRY(hipGetLastError());
-    return RT_OK;
+    const rt_status st = enqueue_impacts_pass(s, nodes, n_nodes, disp, false, 0u, nullptr, nullptr, counters, stream);
+    return st != RT_OK ? st : enqueue_list_scan(s->contacts, s->n_items, offsets_out, total_out, stream);
 }
 
 rt_status enqueue_impacts_fill(const rt_scene *s, const void *nodes, uint32_t n_nodes, uint32_t capacity, int32_t *pairs, void *time, hipStream_t stream)
 {
-    return s->precision == RT_F32 ? enqueue_impacts_fill<float>(s, nodes, n_nodes, capacity, pairs, time, stream)
-                                  : enqueue_impacts_fill<double>(s, nodes, n_nodes, capacity, pairs, time, stream);
+    return enqueue_impacts_pass(s, nodes, n_nodes, nullptr, true, capacity, pairs, time, nullptr, stream);
 }
 
 // ---- overlap lists (rt_overlap_spheres*, rt_overlap.hpp) ----
@@ -1217,36 +1166,17 @@ bool overlap_args_ok(const rt_scene *s, const void *queries, uint32_t n, double 
     if (std::isnan(margin)) { snprintf(g_err, sizeof g_err, "%s: margin is NaN", what); return false; }
     if (capacity > 0x7FFFFFFFu) { snprintf(g_err, sizeof g_err, "%s: capacity %u is above 2^31 - 1", what, capacity); return false; }
     if (gap && !items) { snprintf(g_err, sizeof g_err, "%s: gap_out without items_out", what); return false; }
-    const struct { const void *p; const char *name; } words[] = { { items, "items_out" }, { exclude, "exclude" }, { order, "order" } };
-    for (const auto &w : words)
-        if ((reinterpret_cast<uintptr_t>(w.p) & 3u) != 0) { snprintf(g_err, sizeof g_err, "%s: %s must be 4-byte aligned", what, w.name); return false; }
-    const struct { const void *p; const char *name; } longs[] = { { offsets, "offsets_out" }, { total, "total_out" } };
-    for (const auto &w : longs)
-        if ((reinterpret_cast<uintptr_t>(w.p) & 7u) != 0) { snprintf(g_err, sizeof g_err, "%s: %s must be 8-byte aligned", what, w.name); return false; }
-    const uintptr_t esz = s->precision == RT_F32 ? sizeof(float) : sizeof(double);
-    const struct { const void *p; const char *name; } reals[] = { { queries, "queries" }, { gap, "gap_out" } };
-    for (const auto &w : reals)
-        if ((reinterpret_cast<uintptr_t>(w.p) % esz) != 0) { snprintf(g_err, sizeof g_err, "%s: %s must be %u-byte aligned", what, w.name, (unsigned)esz); return false; }
-    return true;
+    return aligned_ok(what, 4, { { items, "items_out" }, { exclude, "exclude" }, { order, "order" } })
+           && aligned_ok(what, 8, { { offsets, "offsets_out" }, { total, "total_out" } }) && aligned_ok(what, real_size(s), { { queries, "queries" }, { gap, "gap_out" } });
 }
 
-// The host entry's domain: centres finite with |coordinate| <= 1e15 (rt_near_spheres's points) and a radius in 0 .. 1e15 (rt_sweep_spheres's).
-template <typename T>
-bool overlap_queries_valid(const T *queries, uint32_t n, const char *what)
+// The host entry's domain: per query sphere its centre (rt_near_spheres's points) and a radius in 0 .. 1e15 (rt_sweep_spheres's).
+bool overlap_queries_valid(const rt_scene *s, const void *queries, uint32_t n, const char *what)
 {
-    for (uint32_t i = 0; i < n; ++i) {
-        const T *rec = queries + 4 * (size_t)i;
-        for (int c = 0; c < 3; ++c)
-            if (!std::isfinite(rec[c]) || std::fabs((double)rec[c]) > 1e15) {
-                snprintf(g_err, sizeof g_err, "%s: query %u has a non-finite coordinate or one beyond +-1e15", what, i);
-                return false;
-            }
-        if (!(rec[3] >= T(0.0) && (double)rec[3] <= 1e15)) {         // (NaN fails the first comparison)
-            snprintf(g_err, sizeof g_err, "%s: query %u's radius %g is not in 0 .. 1e15", what, i, (double)rec[3]);
-            return false;
-        }
-    }
-    return true;
+    return each_valid(s, n, [&](auto real, uint32_t i) {
+        const decltype(real) *rec = static_cast<const decltype(real) *>(queries) + 4 * (size_t)i;
+        return triple_ok(rec, i, what, "query", "coordinate") && radius_ok(rec[3], i, what, "query ", "'s radius");
+    });
 }
 
 // The scene's overlap workspace for `n` queries, and this call's place behind the one before it.  Under s->overlap.mu.  The first call
@@ -1264,48 +1194,36 @@ rt_status overlap_begin(rt_scene *s, uint32_t n, hipStream_t stream)
     return RT_OK;
 }
 
-// The first pass and the scan on `stream`: counts, then offsets[n + 1] in the workspace and, where given, in the caller's device memory.
-// counters != NULL runs the counting flavour (same counts).  With an order a query that no thread carries keeps the count 0.
-template <typename T>
-rt_status enqueue_overlap_count(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *queries, uint32_t n, double margin, const int32_t *exclude,
-                                const uint32_t *order, uint64_t *offsets_out, uint64_t *total_out, rt::Counters *counters, hipStream_t stream)
+// One pass of the walk on `stream`.  The first (fill == false) counts; counters != NULL runs its counting flavour (same counts); with an
+// order a query that no thread carries keeps the count 0.  The second is the same walk by the queries that counted something, entry
+// offsets[g] + rank written where it lies below `capacity`.
+rt_status enqueue_overlap_pass(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *queries, uint32_t n, double margin, const int32_t *exclude,
+                               const uint32_t *order, bool fill, uint32_t capacity, int32_t *items, void *gap, rt::Counters *counters, hipStream_t stream)
 {
-    const rt::OverlapArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), static_cast<const T *>(queries), exclude, order, s->overlap.counts, nullptr, nullptr, nullptr,
-                                counters, (T)margin, n_nodes, n, 0u };
-    if (order) HIP_TRY(hipMemsetAsync(s->overlap.counts, 0, sizeof(uint32_t) * (size_t)n, stream));
-    const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
-    if (counters) hipLaunchKernelGGL((rt::k_overlap_spheres<T, true, false>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((rt::k_overlap_spheres<T, false, false>), grid, block, 0, stream, a);
-    HIP_TRY(hipGetLastError());
-    return enqueue_list_scan(s->overlap, n, offsets_out, total_out, stream);
-}
-
-rt_status enqueue_overlap_count(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *queries, uint32_t n, double margin, const int32_t *exclude,
-                                const uint32_t *order, uint64_t *offsets_out, uint64_t *total_out, rt::Counters *counters, hipStream_t stream)
-{
-    return s->precision == RT_F32 ? enqueue_overlap_count<float>(s, nodes, n_nodes, queries, n, margin, exclude, order, offsets_out, total_out, counters, stream)
-                                  : enqueue_overlap_count<double>(s, nodes, n_nodes, queries, n, margin, exclude, order, offsets_out, total_out, counters, stream);
-}
-
-// The second pass on `stream`: the same walk by the queries that counted something, entry offsets[g] + rank written where it lies below
-// `capacity`.
-template <typename T>
-rt_status enqueue_overlap_fill(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *queries, uint32_t n, double margin, const int32_t *exclude,
-                               const uint32_t *order, uint32_t capacity, int32_t *items, void *gap, hipStream_t stream)
-{
-    const rt::OverlapArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), static_cast<const T *>(queries), exclude, order, s->overlap.counts, s->overlap.offsets, items,
-                                static_cast<T *>(gap), nullptr, (T)margin, n_nodes, n, capacity };
-    const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
-    hipLaunchKernelGGL((rt::k_overlap_spheres<T, false, true>), grid, block, 0, stream, a);
+    if (!fill && order) HIP_TRY(hipMemsetAsync(s->overlap.counts, 0, sizeof(uint32_t) * (size_t)n, stream));
+    by_precision(s, [&](auto real) {
+        using T = decltype(real);
+        const rt::OverlapArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), static_cast<const T *>(queries), exclude, order, s->overlap.counts,
+                                    fill ? s->overlap.offsets : nullptr, items, static_cast<T *>(gap), counters, (T)margin, n_nodes, n, capacity };
+        if (fill) hipLaunchKernelGGL((rt::k_overlap_spheres<T, false, true>), query_grid(n), query_block(), 0, stream, a);
+        else with_flags([&](auto count) { hipLaunchKernelGGL((rt::k_overlap_spheres<T, count(), false>), query_grid(n), query_block(), 0, stream, a); }, counters != nullptr);
+    });
     HIP_TRY(hipGetLastError());
     return RT_OK;
 }
 
+// The first pass and the scan: counts, then offsets[n + 1] in the workspace and, where given, in the caller's device memory.
+rt_status enqueue_overlap_count(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *queries, uint32_t n, double margin, const int32_t *exclude,
+                                const uint32_t *order, uint64_t *offsets_out, uint64_t *total_out, rt::Counters *counters, hipStream_t stream)
+{
+    const rt_status st = enqueue_overlap_pass(s, nodes, n_nodes, queries, n, margin, exclude, order, false, 0u, nullptr, nullptr, counters, stream);
+    return st != RT_OK ? st : enqueue_list_scan(s->overlap, n, offsets_out, total_out, stream);
+}
+
 rt_status enqueue_overlap_fill(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *queries, uint32_t n, double margin, const int32_t *exclude,
                                const uint32_t *order, uint32_t capacity, int32_t *items, void *gap, hipStream_t stream)
 {
-    return s->precision == RT_F32 ? enqueue_overlap_fill<float>(s, nodes, n_nodes, queries, n, margin, exclude, order, capacity, items, gap, stream)
-                                  : enqueue_overlap_fill<double>(s, nodes, n_nodes, queries, n, margin, exclude, order, capacity, items, gap, stream);
+    return enqueue_overlap_pass(s, nodes, n_nodes, queries, n, margin, exclude, order, true, capacity, items, gap, nullptr, stream);
 }
 
 // ---- swept overlap lists (rt_swept_overlaps*, rt_swept.hpp) ----
@@ -1322,29 +1240,17 @@ bool swept_args_ok(const rt_scene *s, const void *queries, const void *qdisp, ui
     if (capacity > 0x7FFFFFFFu) { snprintf(g_err, sizeof g_err, "%s: capacity %u is above 2^31 - 1", what, capacity); return false; }
     if (time && !items) { snprintf(g_err, sizeof g_err, "%s: time_out without items_out", what); return false; }
     if (normal && !items) { snprintf(g_err, sizeof g_err, "%s: normal_out without items_out", what); return false; }
-    const struct { const void *p; const char *name; } words[] = { { items, "items_out" }, { exclude, "exclude" }, { order, "order" } };
-    for (const auto &w : words)
-        if ((reinterpret_cast<uintptr_t>(w.p) & 3u) != 0) { snprintf(g_err, sizeof g_err, "%s: %s must be 4-byte aligned", what, w.name); return false; }
-    const struct { const void *p; const char *name; } longs[] = { { offsets, "offsets_out" }, { total, "total_out" } };
-    for (const auto &w : longs)
-        if ((reinterpret_cast<uintptr_t>(w.p) & 7u) != 0) { snprintf(g_err, sizeof g_err, "%s: %s must be 8-byte aligned", what, w.name); return false; }
-    const uintptr_t esz = s->precision == RT_F32 ? sizeof(float) : sizeof(double);
-    const struct { const void *p; const char *name; } reals[] = { { queries, "queries" }, { qdisp, "qdisp" }, { disp, "disp" }, { time, "time_out" }, { normal, "normal_out" } };
-    for (const auto &w : reals)
-        if ((reinterpret_cast<uintptr_t>(w.p) % esz) != 0) { snprintf(g_err, sizeof g_err, "%s: %s must be %u-byte aligned", what, w.name, (unsigned)esz); return false; }
-    return true;
+    return aligned_ok(what, 4, { { items, "items_out" }, { exclude, "exclude" }, { order, "order" } })
+           && aligned_ok(what, 8, { { offsets, "offsets_out" }, { total, "total_out" } })
+           && aligned_ok(what, real_size(s), { { queries, "queries" }, { qdisp, "qdisp" }, { disp, "disp" }, { time, "time_out" }, { normal, "normal_out" } });
 }
 
-// The host entry's domain for the queries' displacements: every component finite and within +-1e15, as a scene's own.
-template <typename T>
-bool swept_qdisp_valid(const T *qdisp, uint32_t n, const char *what)
+// The host entry's domain for the queries' displacements.
+bool swept_qdisp_valid(const rt_scene *s, const void *qdisp, uint32_t n, const char *what)
 {
-    for (size_t k = 0; k < 3 * (size_t)n; ++k)
-        if (!std::isfinite(qdisp[k]) || std::fabs((double)qdisp[k]) > 1e15) {
-            snprintf(g_err, sizeof g_err, "%s: qdisp of query %u has a non-finite component or one beyond +-1e15", what, (unsigned)(k / 3));
-            return false;
-        }
-    return true;
+    return each_valid(s, n, [&](auto real, uint32_t i) {
+        return triple_ok(static_cast<const decltype(real) *>(qdisp) + 3 * (size_t)i, i, what, "qdisp of query", "component");
+    });
 }
 
 // overlap_begin, and room for this entry's motion table of `n_nodes` nodes.  Under s->overlap.mu.
@@ -1355,56 +1261,54 @@ rt_status swept_begin(rt_scene *s, uint32_t n, uint32_t n_nodes, hipStream_t str
     return motion_table_begin(s, s->overlap, &s->d_swept, &s->swept_cap, n_nodes, "rt_swept_overlaps");
 }
 
-// The queries' magnitude, the motion table, the first pass and the scan on `stream`.  counters != NULL runs the counting flavour (same
-// counts).  With an order a query that no thread carries keeps the count 0.
+// What a walk of moving queries runs first on `stream`: the queries' magnitude into *w.magnitude, then the motion table.
 template <typename T>
-rt_status enqueue_swept_count(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *queries, const void *qdisp, uint32_t n, const void *disp,
-                              const int32_t *exclude, const uint32_t *order, uint64_t *offsets_out, uint64_t *total_out, rt::Counters *counters, hipStream_t stream)
+rt_status enqueue_query_motion(const rt_scene *s, const rt::Node<T> *st, uint32_t n_nodes, const T *queries, const T *qdisp, uint32_t n, const T *disp,
+                               const ImpactsSpace<T> &w, hipStream_t stream)
 {
-    const ImpactsSpace<T> w = motion_table_space<T>(s->d_swept, s->swept_cap);
-    const rt::Node<T> *const st = static_cast<const rt::Node<T> *>(nodes);
     HIP_TRY(hipMemsetAsync(w.magnitude, 0, sizeof(T), stream));
-    hipLaunchKernelGGL(rt::k_swept_query_magnitude<T>, dim3((unsigned)(((uint64_t)n + 255) / 256)), dim3(256), 0, stream, static_cast<const T *>(queries),
-                       static_cast<const T *>(qdisp), n, w.magnitude);
+    hipLaunchKernelGGL(rt::k_swept_query_magnitude<T>, dim3((unsigned)(((uint64_t)n + 255) / 256)), dim3(256), 0, stream, queries, qdisp, n, w.magnitude);
     HIP_TRY(hipGetLastError());
-    if (const rt_status mt = enqueue_motion_table<T>(s, st, n_nodes, static_cast<const T *>(disp), w, stream); mt != RT_OK) return mt;
-    const rt::SweptArgs<T> a{ st, w.motion, w.magnitude, static_cast<const T *>(queries), static_cast<const T *>(qdisp), exclude, order, s->overlap.counts, nullptr,
-                              nullptr, nullptr, nullptr, counters, n_nodes, n, 0u };
-    if (order) HIP_TRY(hipMemsetAsync(s->overlap.counts, 0, sizeof(uint32_t) * (size_t)n, stream));
-    const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
-    if (counters) hipLaunchKernelGGL((rt::k_swept_overlaps<T, true, false>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((rt::k_swept_overlaps<T, false, false>), grid, block, 0, stream, a);
-    HIP_TRY(hipGetLastError());
-    return enqueue_list_scan(s->overlap, n, offsets_out, total_out, stream);
+    return enqueue_motion_table<T>(s, st, n_nodes, disp, w, stream);
 }
 
+// One pass of the walk on `stream`.  The first (fill == false) runs enqueue_query_motion and counts; counters != NULL runs its counting
+// flavour (same counts); with an order a query that no thread carries keeps the count 0.  The second is the same walk over the table the
+// first left, by the queries that counted something; entry offsets[g] + rank written where it lies below `capacity`.
+rt_status enqueue_swept_pass(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *queries, const void *qdisp, uint32_t n, const void *disp,
+                             const int32_t *exclude, const uint32_t *order, bool fill, uint32_t capacity, int32_t *items, void *time, void *normal,
+                             rt::Counters *counters, hipStream_t stream)
+{
+    return by_precision(s, [&](auto real) -> rt_status {
+        using T = decltype(real);
+        const ImpactsSpace<T> w = motion_table_space<T>(s->d_swept, s->swept_cap);
+        const rt::Node<T> *const st = static_cast<const rt::Node<T> *>(nodes);
+        const T *const q = static_cast<const T *>(queries), *const qd = static_cast<const T *>(qdisp);
+        if (!fill) {
+            if (const rt_status mt = enqueue_query_motion<T>(s, st, n_nodes, q, qd, n, static_cast<const T *>(disp), w, stream); mt != RT_OK) return mt;
+            if (order) HIP_TRY(hipMemsetAsync(s->overlap.counts, 0, sizeof(uint32_t) * (size_t)n, stream));
+        }
+        const rt::SweptArgs<T> a{ st, w.motion, w.magnitude, q, qd, exclude, order, s->overlap.counts, fill ? s->overlap.offsets : nullptr, items,
+                                  static_cast<T *>(time), static_cast<T *>(normal), counters, n_nodes, n, capacity };
+        if (fill) hipLaunchKernelGGL((rt::k_swept_overlaps<T, false, true>), query_grid(n), query_block(), 0, stream, a);
+        else with_flags([&](auto count) { hipLaunchKernelGGL((rt::k_swept_overlaps<T, count(), false>), query_grid(n), query_block(), 0, stream, a); }, counters != nullptr);
+        HIP_TRY(hipGetLastError());
+        return RT_OK;
+    });
+}
+
+// The queries' magnitude, the motion table, the first pass and the scan.
 rt_status enqueue_swept_count(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *queries, const void *qdisp, uint32_t n, const void *disp,
                               const int32_t *exclude, const uint32_t *order, uint64_t *offsets_out, uint64_t *total_out, rt::Counters *counters, hipStream_t stream)
 {
-    return s->precision == RT_F32 ? enqueue_swept_count<float>(s, nodes, n_nodes, queries, qdisp, n, disp, exclude, order, offsets_out, total_out, counters, stream)
-                                  : enqueue_swept_count<double>(s, nodes, n_nodes, queries, qdisp, n, disp, exclude, order, offsets_out, total_out, counters, stream);
-}
-
-// The second pass on `stream`: the same walk over the motion table the first pass left, by the queries that counted something; entry
-// offsets[g] + rank written where it lies below `capacity`.
-template <typename T>
-rt_status enqueue_swept_fill(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *queries, const void *qdisp, uint32_t n, const int32_t *exclude,
-                             const uint32_t *order, uint32_t capacity, int32_t *items, void *time, void *normal, hipStream_t stream)
-{
-    const ImpactsSpace<T> w = motion_table_space<T>(s->d_swept, s->swept_cap);
-    const rt::SweptArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), w.motion, w.magnitude, static_cast<const T *>(queries), static_cast<const T *>(qdisp), exclude, order,
-                              s->overlap.counts, s->overlap.offsets, items, static_cast<T *>(time), static_cast<T *>(normal), nullptr, n_nodes, n, capacity };
-    const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
-    hipLaunchKernelGGL((rt::k_swept_overlaps<T, false, true>), grid, block, 0, stream, a);
-    HIP_TRY(hipGetLastError());
-    return RT_OK;
+    const rt_status st = enqueue_swept_pass(s, nodes, n_nodes, queries, qdisp, n, disp, exclude, order, false, 0u, nullptr, nullptr, nullptr, counters, stream);
+    return st != RT_OK ? st : enqueue_list_scan(s->overlap, n, offsets_out, total_out, stream);
 }
 
 rt_status enqueue_swept_fill(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *queries, const void *qdisp, uint32_t n, const int32_t *exclude,
                              const uint32_t *order, uint32_t capacity, int32_t *items, void *time, void *normal, hipStream_t stream)
 {
-    return s->precision == RT_F32 ? enqueue_swept_fill<float>(s, nodes, n_nodes, queries, qdisp, n, exclude, order, capacity, items, time, normal, stream)
-                                  : enqueue_swept_fill<double>(s, nodes, n_nodes, queries, qdisp, n, exclude, order, capacity, items, time, normal, stream);
+    return enqueue_swept_pass(s, nodes, n_nodes, queries, qdisp, n, nullptr, exclude, order, true, capacity, items, time, normal, nullptr, stream);
 }
 
 // ---- first contacts (rt_first_contacts*, rt_first.hpp) ----
@@ -1419,57 +1323,34 @@ bool first_args_ok(const rt_scene *s, rt_sweep mode, const void *queries, const 
     if (!qdisp) { snprintf(g_err, sizeof g_err, "%s: NULL qdisp", what); return false; }
     if (!time) { snprintf(g_err, sizeof g_err, "%s: NULL time_out", what); return false; }
     if (n == 0) { snprintf(g_err, sizeof g_err, "%s: n == 0", what); return false; }
-    const struct { const void *p; const char *name; } words[] = { { item, "item_out" }, { exclude, "exclude" }, { order, "order" } };
-    for (const auto &w : words)
-        if ((reinterpret_cast<uintptr_t>(w.p) & 3u) != 0) { snprintf(g_err, sizeof g_err, "%s: %s must be 4-byte aligned", what, w.name); return false; }
-    const uintptr_t esz = s->precision == RT_F32 ? sizeof(float) : sizeof(double);
-    const struct { const void *p; const char *name; } reals[] = { { queries, "queries" }, { qdisp, "qdisp" }, { disp, "disp" }, { time, "time_out" }, { normal, "normal_out" } };
-    for (const auto &w : reals)
-        if ((reinterpret_cast<uintptr_t>(w.p) % esz) != 0) { snprintf(g_err, sizeof g_err, "%s: %s must be %u-byte aligned", what, w.name, (unsigned)esz); return false; }
-    return true;
-}
-
-template <typename T, bool COUNT>
-void launch_first(dim3 grid, dim3 block, hipStream_t stream, bool any, const rt::FirstArgs<T> &a)
-{
-    if (any) hipLaunchKernelGGL((rt::k_first_contacts<T, COUNT, true>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((rt::k_first_contacts<T, COUNT, false>), grid, block, 0, stream, a);
-}
-
-// The queries' magnitude, the motion table and the one walk on `stream`, in the swept entry's table.  counters != NULL runs the counting
-// flavour (same bytes).  Under s->overlap.mu, behind swept_begin.
-template <typename T>
-rt_status enqueue_first(const rt_scene *s, const void *nodes, uint32_t n_nodes, rt_sweep mode, const void *queries, const void *qdisp, uint32_t n, const void *disp,
-                        const int32_t *exclude, const uint32_t *order, void *time, int32_t *item, void *normal, rt::Counters *counters, hipStream_t stream)
-{
-    const ImpactsSpace<T> w = motion_table_space<T>(s->d_swept, s->swept_cap);
-    const rt::Node<T> *const st = static_cast<const rt::Node<T> *>(nodes);
-    HIP_TRY(hipMemsetAsync(w.magnitude, 0, sizeof(T), stream));
-    hipLaunchKernelGGL(rt::k_swept_query_magnitude<T>, dim3((unsigned)(((uint64_t)n + 255) / 256)), dim3(256), 0, stream, static_cast<const T *>(queries),
-                       static_cast<const T *>(qdisp), n, w.magnitude);
-    HIP_TRY(hipGetLastError());
-    if (const rt_status mt = enqueue_motion_table<T>(s, st, n_nodes, static_cast<const T *>(disp), w, stream); mt != RT_OK) return mt;
-    const rt::FirstArgs<T> a{ st, w.motion, w.magnitude, static_cast<const T *>(queries), static_cast<const T *>(qdisp), exclude, order, static_cast<T *>(time), item,
-                              static_cast<T *>(normal), counters, n_nodes, n };
-    const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
-    if (counters) launch_first<T, true>(grid, block, stream, mode == RT_SWEEP_ANY, a);
-    else launch_first<T, false>(grid, block, stream, mode == RT_SWEEP_ANY, a);
-    HIP_TRY(hipGetLastError());
-    return RT_OK;
+    return aligned_ok(what, 4, { { item, "item_out" }, { exclude, "exclude" }, { order, "order" } })
+           && aligned_ok(what, real_size(s), { { queries, "queries" }, { qdisp, "qdisp" }, { disp, "disp" }, { time, "time_out" }, { normal, "normal_out" } });
 }
 
 // One first-contacts call's place among the overlap and swept calls of its scene, and its kernels: under s->overlap.mu it goes behind
-// the call before it (swept_begin; it brings no counts, so the list workspace does not grow for it), uses the swept entry's motion table,
-// and leaves the event the next call waits for -- host calls too: the outputs are the call's own, only the table is shared, so the call
-// need not hold the mutex until its stream is drained.
+// the call before it (swept_begin; it brings no counts, so the list workspace does not grow for it), uses the swept entry's motion table
+// (enqueue_query_motion, then the one walk; counters != NULL runs the counting flavour, same bytes), and leaves the event the next call
+// waits for -- host calls too: the outputs are the call's own, only the table is shared, so the call need not hold the mutex until its
+// stream is drained.
 rt_status enqueue_first(rt_scene *s, const void *nodes, uint32_t n_nodes, rt_sweep mode, const void *queries, const void *qdisp, uint32_t n, const void *disp,
                         const int32_t *exclude, const uint32_t *order, void *time, int32_t *item, void *normal, rt::Counters *counters, hipStream_t stream)
 {
     std::lock_guard<std::mutex> lk(s->overlap.mu);
     rt_status st = swept_begin(s, 0u, n_nodes, stream);
     if (st != RT_OK) return st;
-    st = s->precision == RT_F32 ? enqueue_first<float>(s, nodes, n_nodes, mode, queries, qdisp, n, disp, exclude, order, time, item, normal, counters, stream)
-                                : enqueue_first<double>(s, nodes, n_nodes, mode, queries, qdisp, n, disp, exclude, order, time, item, normal, counters, stream);
+    st = by_precision(s, [&](auto real) -> rt_status {
+        using T = decltype(real);
+        const ImpactsSpace<T> w = motion_table_space<T>(s->d_swept, s->swept_cap);
+        const rt::Node<T> *const stream_nodes = static_cast<const rt::Node<T> *>(nodes);
+        const T *const q = static_cast<const T *>(queries), *const qd = static_cast<const T *>(qdisp);
+        if (const rt_status mt = enqueue_query_motion<T>(s, stream_nodes, n_nodes, q, qd, n, static_cast<const T *>(disp), w, stream); mt != RT_OK) return mt;
+        const rt::FirstArgs<T> a{ stream_nodes, w.motion, w.magnitude, q, qd, exclude, order, static_cast<T *>(time), item, static_cast<T *>(normal), counters, n_nodes, n };
+        with_flags([&](auto count, auto any) {
+            hipLaunchKernelGGL((rt::k_first_contacts<T, count(), any()>), query_grid(n), query_block(), 0, stream, a);
+        }, counters != nullptr, mode == RT_SWEEP_ANY);
+        HIP_TRY(hipGetLastError());
+        return RT_OK;
+    });
     // whatever was enqueued uses the table: the next call goes behind it
     if (hipEventRecord(s->overlap.ev, stream) == hipSuccess) s->overlap.recorded = true;
     else { (void)hipGetLastError(); (void)hipStreamSynchronize(stream); }
@@ -1481,12 +1362,11 @@ rt_status enqueue_first(rt_scene *s, const void *nodes, uint32_t n_nodes, rt_swe
 // The camera domain both rt_render_camera entries check (in double, before the device is touched): 12 finite values, |eye coordinate|
 // <= 1e15 (rt_scene_create's eye), every axis of length within [1e-2, 1e2] and |det(right, up, forward)| >= 1e-2 |right| |up| |forward|.
 // Within it no sample direction is zero, underflows or overflows, so every normalised direction lies in the ray queries' domain.
-template <typename T>
-bool camera_valid(const T *cam, const char *what)
+bool camera_valid(const rt_scene *s, const void *cam, const char *what)
 {
     double v[12];
     for (int k = 0; k < 12; ++k) {
-        v[k] = (double)cam[k];
+        v[k] = by_precision(s, [&](auto real) { return (double)static_cast<const decltype(real) *>(cam)[k]; });
         if (!std::isfinite(v[k])) { snprintf(g_err, sizeof g_err, "%s: camera value %d is not finite", what, k); return false; }
     }
     for (int k = 0; k < 3; ++k)
@@ -1509,11 +1389,6 @@ bool camera_valid(const T *cam, const char *what)
     return true;
 }
 
-bool camera_valid(const rt_scene *s, const void *cam, const char *what)
-{
-    return s->precision == RT_F32 ? camera_valid(static_cast<const float *>(cam), what) : camera_valid(static_cast<const double *>(cam), what);
-}
-
 // Pointers and sizes both rt_trace_rays entries check (device pointers are not dereferenced here).
 bool trace_args_ok(const rt_scene *s, const void *rays, uint32_t n, const void *color, const void *alpha, const char *what)
 {
@@ -1521,77 +1396,53 @@ bool trace_args_ok(const rt_scene *s, const void *rays, uint32_t n, const void *
         snprintf(g_err, sizeof g_err, "%s: NULL scene, rays or color_out, or n == 0", what);
         return false;
     }
-    const uintptr_t esz = s->precision == RT_F32 ? sizeof(float) : sizeof(double);
-    for (const void *p : { rays, color, alpha })
-        if ((reinterpret_cast<uintptr_t>(p) % esz) != 0) { snprintf(g_err, sizeof g_err, "%s: REAL buffers must be %u-byte aligned", what, (unsigned)esz); return false; }
-    return true;
+    return aligned_ok(what, real_size(s), { { rays, "REAL buffers" }, { color, "REAL buffers" }, { alpha, "REAL buffers" } });
 }
 
-// One rt_trace_rays launch (rays != NULL) or one camera frame over a device tile table on `stream`; counters != NULL runs the counting
-// flavour (same bytes).
-template <typename T>
-rt_status enqueue_trace(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *rays, uint32_t n, void *color, void *alpha,
-                        const rt_options *o, const void *cam, const rt::TileDev *d_tab, uint32_t n_tiles, uint32_t blocks, uint8_t *d_out,
-                        rt::Counters *counters, hipStream_t stream, const uint32_t *order)
-{
-    rt::TraceArgs<T> a{};
-    a.stream = static_cast<const rt::Node<T> *>(nodes);
-    a.items = static_cast<const rt::Item<T> *>(s->d_items);
-    a.counters = counters;
-    a.rays = static_cast<const T *>(rays);
-    a.color = static_cast<T *>(color);
-    a.alpha = static_cast<T *>(alpha);
-    a.tiles = d_tab;
-    a.out = d_out;
-    if (cam) for (int k = 0; k < 12; ++k) a.cam[k] = static_cast<const T *>(cam)[k];
-    for (int k = 0; k < 3; ++k) a.light[k] = (T)s->light[k];
-    a.n_nodes = n_nodes;
-    if (rays) {
-        a.n = n;
-        const dim3 grid((unsigned)(((uint64_t)n + rt::kBlockThreads - 1) / rt::kBlockThreads)), block(rt::kBlockThreads);
-        if (order) {                                                 // the rays in a given order (rt_order.hpp)
-            if (counters) hipLaunchKernelGGL((rt::k_trace_rays_ordered<T, true>), grid, block, 0, stream, a, order);
-            else hipLaunchKernelGGL((rt::k_trace_rays_ordered<T, false>), grid, block, 0, stream, a, order);
-        } else if (counters) hipLaunchKernelGGL((rt::k_trace_rays<T, true, rt::kTraceRays>), grid, block, 0, stream, a);
-        else hipLaunchKernelGGL((rt::k_trace_rays<T, false, rt::kTraceRays>), grid, block, 0, stream, a);
-    } else {
-        a.n = n_tiles;
-        a.width = o->width; a.height = o->height; a.spp = o->samples_per_pixel;
-        const dim3 grid(blocks), block(rt::kBlockThreads);
-        if (counters) hipLaunchKernelGGL((rt::k_trace_rays<T, true, rt::kTraceCamera>), grid, block, 0, stream, a);
-        else hipLaunchKernelGGL((rt::k_trace_rays<T, false, rt::kTraceCamera>), grid, block, 0, stream, a);
-    }
-    HIP_TRY(hipGetLastError());
-    return RT_OK;
-}
-
+// One rt_trace_rays launch (rays != NULL; with an order, the rays in that order, rt_order.hpp) or one camera frame over a device tile
+// table on `stream`; counters != NULL runs the counting flavour (same bytes).
 rt_status enqueue_trace(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *rays, uint32_t n, void *color, void *alpha,
                         const rt_options *o, const void *cam, const rt::TileDev *d_tab, uint32_t n_tiles, uint32_t blocks, uint8_t *d_out,
                         rt::Counters *counters, hipStream_t stream, const uint32_t *order = nullptr)
 {
-    return s->precision == RT_F32 ? enqueue_trace<float>(s, nodes, n_nodes, rays, n, color, alpha, o, cam, d_tab, n_tiles, blocks, d_out, counters, stream, order)
-                                  : enqueue_trace<double>(s, nodes, n_nodes, rays, n, color, alpha, o, cam, d_tab, n_tiles, blocks, d_out, counters, stream, order);
+    by_precision(s, [&](auto real) {
+        using T = decltype(real);
+        rt::TraceArgs<T> a{};
+        a.stream = static_cast<const rt::Node<T> *>(nodes);
+        a.items = static_cast<const rt::Item<T> *>(s->d_items);
+        a.counters = counters;
+        a.rays = static_cast<const T *>(rays);
+        a.color = static_cast<T *>(color);
+        a.alpha = static_cast<T *>(alpha);
+        a.tiles = d_tab;
+        a.out = d_out;
+        if (cam) for (int k = 0; k < 12; ++k) a.cam[k] = static_cast<const T *>(cam)[k];
+        for (int k = 0; k < 3; ++k) a.light[k] = (T)s->light[k];
+        a.n_nodes = n_nodes;
+        if (rays) {
+            a.n = n;
+            with_flags([&](auto count, auto ordered) {
+                if constexpr (ordered()) hipLaunchKernelGGL((rt::k_trace_rays_ordered<T, count()>), query_grid(n), query_block(), 0, stream, a, order);
+                else hipLaunchKernelGGL((rt::k_trace_rays<T, count(), rt::kTraceRays>), query_grid(n), query_block(), 0, stream, a);
+            }, counters != nullptr, order != nullptr);
+        } else {
+            a.n = n_tiles;
+            a.width = o->width; a.height = o->height; a.spp = o->samples_per_pixel;
+            with_flags([&](auto count) { hipLaunchKernelGGL((rt::k_trace_rays<T, count(), rt::kTraceCamera>), dim3(blocks), query_block(), 0, stream, a); }, counters != nullptr);
+        }
+    });
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
 }
 
-// A counting trace's rt_stats: primary = rays or samples, hits / shadow / occluded as the render counts them, the walks' tests and the
-// primary walks' share of them; the longest-wave fields 0.  Synchronises `stream`.
+// A counting trace's rt_stats: read_counters's (primary = rays or samples), shadow / occluded as the render counts them and the primary
+// walks' share of the tests; the longest-wave fields 0.  Synchronises `stream`.
 rt_status read_trace_stats(Context *c, hipStream_t stream, rt_stats *st)
 {
-    std::vector<rt::Counters> stripes(rt::kCounterStripes);
-    HIP_TRY(hipMemcpyAsync(stripes.data(), c->d_counters, sizeof(rt::Counters) * rt::kCounterStripes, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    rt::Counters h{};
-    for (const rt::Counters &k : stripes) {
-        h.primary += k.primary; h.hits += k.hits; h.shadow += k.shadow; h.occluded += k.occluded;
-        h.sphere_tests += k.sphere_tests; h.bound_tests += k.bound_tests; h.primary_tests += k.primary_tests;
-    }
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    *st = rt_stats{};
-    st->primary = h.primary; st->hits = h.hits; st->shadow = h.shadow; st->occluded = h.occluded;
-    st->sphere_tests = h.sphere_tests; st->bound_tests = h.bound_tests; st->tests_executed = h.sphere_tests + h.bound_tests;
+    rt::Counters h;
+    if (const rt_status rst = read_counters(c, stream, &h, st); rst != RT_OK) return rst;
+    st->shadow = h.shadow; st->occluded = h.occluded;
     st->primary_tests = h.primary_tests;
-    st->device_ms = ms;
     return RT_OK;
 }
 

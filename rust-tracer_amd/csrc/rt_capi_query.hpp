@@ -1,6 +1,8 @@
 // rt_capi_query.hpp -- part of rt_capi.hip: what the query entries of rt_capi_entry.hpp share -- how a call reaches the caller's host
 // buffers (HostStaging) and the skeletons of a single-pass query and of a two-pass list query, each for host and for device memory.  A
-// new query brings its table of buffers and its enqueue calls; nothing here knows which entry runs it.
+// new query brings its table of buffers and its enqueue calls; nothing here knows which entry runs it.  What the layer below shares --
+// the precision and flavour switches, the alignment check, the domain predicates -- stands at the head of rt_capi_launch.hpp's query
+// part; DESIGN.md 4.6 ("Where the host side of a query lives") lists what a new query has to bring to each layer.
 // (included by rt_capi.hip where its text used to stand: nothing here is a header of its own)
 
 struct HostDest { bool pinned = false; uint8_t *dev_alias = nullptr; bool bad = false; size_t room = 0; };
