@@ -17,11 +17,10 @@ import re
 import subprocess
 import sys
 
+from asm_gen import UNDECLARED as FLAVOURS, marker_flavour      # flavour -> (its kernels' name prefixes, the registers); shared with the generators
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEFAULT_S = os.path.join(ROOT, "rust-tracer_amd", "csrc", "rt_capi.gfx950.s")
-FLAVOURS = {"two-ray": (("void rt::k_render_skip2<", "void rt::k_render_skip2_fast<"), (32, 72, 73)),
-            "f64": (("void rt::k_render_skip_f64<", "void rt::k_render_skip_f64_coop<"), (88, 89)),
-            "f64-lo": (("void rt::k_render_skip_fast64_coop<",), (32,))}
 
 
 def sgprs_of(text):
@@ -49,9 +48,9 @@ def check(path=DEFAULT_S):
             elif t.startswith((";;#ASMEND", ";NO_APP")):
                 in_app = False
             elif in_app:
-                m = re.search(r"; rt-loops ([\w-]+): undeclared", t)
-                if m:
-                    flavours.add(m.group(1))
+                fl = marker_flavour(t)
+                if fl:
+                    flavours.add(fl)
             elif t and not t.startswith((";", ".")) and not t.endswith(":"):
                 outside.append(t)
         if not flavours:

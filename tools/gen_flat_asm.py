@@ -54,6 +54,10 @@ subtraction is an addition with the IEEE sign flip of the neg modifier):
 
 Run:  python3 tools/gen_flat_asm.py   (writes the header; the build does not need this script)."""
 import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))          # asm_gen.py lives beside this script, wherever it is run or loaded from
+from asm_gen import Asm, Pair, RootRegs, clobber_list, pk, pk_fma, root, tiny, write_header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.path.join(ROOT, "rust-tracer_amd", "csrc", "rt_flat_rot.hpp")
@@ -67,107 +71,27 @@ SGPR_LAST = 87
 VGPR_FIRST, VGPR_LAST = 32, 63
 
 
-class Pair:
-    """A VGPR pair: .p the pair, .h[0] / .h[1] its halves (ray 0 / ray 1)."""
-
-    def __init__(self, lo):
-        self.p = "v[%d:%d]" % (lo, lo + 1)
-        self.h = ("v%d" % lo, "v%d" % (lo + 1))
-
-
-class Asm:
-    def __init__(self):
-        self.lines = []
-
-    def op(self, text, comment=None):
-        self.lines.append(("\t", text, comment))
-
-    def label(self, name):
-        self.lines.append(("", name + ":", None))
-
-    def render(self, indent="        "):
-        out = []
-        for tab, text, comment in self.lines:
-            s = '%s"%s%s\\n"' % (indent, "" if tab == "" else "\\t", text)
-            if comment:
-                s += "  /* %s */" % comment
-            out.append(s)
-        return "\n".join(out)
-
-
 def sreg(bank, field, k):
     """SGPR number of item k's field in a bank: fields are stored [field][item]."""
     return BANK[bank] + 3 * field + k
-
-
-def pk(a, op, dst, x, y, sx=None, sy=None, neg_y=False, comment=None):
-    """dst = x op y on both rays.  sx / sy: SGPR NUMBER whose value is broadcast to both rays in place of a VGPR pair."""
-    sel, sel_hi = [0, 0], [1, 1]
-    if sx is not None:
-        x = "s[%d:%d]" % (sx & ~1, (sx & ~1) + 1)
-        sel[0] = sel_hi[0] = sx & 1
-    if sy is not None:
-        y = "s[%d:%d]" % (sy & ~1, (sy & ~1) + 1)
-        sel[1] = sel_hi[1] = sy & 1
-    mods = ""
-    if sel != [0, 0]:
-        mods += " op_sel:[%d,%d]" % tuple(sel)
-    if sel_hi != [1, 1]:
-        mods += " op_sel_hi:[%d,%d]" % tuple(sel_hi)
-    if neg_y:
-        mods += " neg_lo:[0,1] neg_hi:[0,1]"
-    a.op("v_pk_%s_f32 %s, %s, %s%s" % (op, dst, x, y, mods), comment)
-
-
-def pk_fma(a, dst, x, y, z, sx=None, sz=None, comment=None):
-    """dst = x * y + z on both rays, ONE rounding (the conservative filter only; never on the exact path)."""
-    sel, sel_hi = [0, 0, 0], [1, 1, 1]
-    if sx is not None:
-        x = "s[%d:%d]" % (sx & ~1, (sx & ~1) + 1)
-        sel[0] = sel_hi[0] = sx & 1
-    if sz is not None:
-        z = "s[%d:%d]" % (sz & ~1, (sz & ~1) + 1)
-        sel[2] = sel_hi[2] = sz & 1
-    mods = ""
-    if sel != [0, 0, 0]:
-        mods += " op_sel:[%d,%d,%d]" % tuple(sel)
-    if sel_hi != [1, 1, 1]:
-        mods += " op_sel_hi:[%d,%d,%d]" % tuple(sel_hi)
-    a.op("v_pk_fma_f32 %s, %s, %s, %s%s" % (dst, x, y, z, mods), comment)
 
 
 def load(a, bank, off, comment=None):
     a.op("s_load_dwordx16 s[%d:%d], %%[base], %s" % (BANK[bank], BANK[bank] + 15, off), comment)
 
 
-def refine(a, x, t0, t1, root):
-    a.op("v_mul_f32_e32 %s, %s, %s" % (root, x, t0), "g = x*y")
-    a.op("v_mul_f32_e32 %s, 0.5, %s" % (t0, t0), "h = y/2")
-    a.op("v_fma_f32 %s, -%s, %s, %s" % (t1, root, root, x), "r = x - g*g")
-    a.op("v_fma_f32 %s, %s, %s, %s" % (root, t1, t0, root), "g + r*h")
+def lean_root(r):
+    """The registers of the exact root: every lane of EXEC is a candidate, and VCC is free for the zero test."""
+    return RootRegs(t0=r.t0, t1=r.t1, scaled=r.t2, root=r.root, tiny=TINY, zero="vcc", need=None)
 
 
 def exact_root(a, disc, tag, r):
     """Correctly rounded sqrt(disc) into r.root for the lanes in EXEC (== sqrt_rn_lean)."""
-    a.op("v_rsq_f32_e32 %s, %s" % (r.t0, disc))
-    a.op("v_cmp_lt_f32_e64 %s, |%s|, %%[tiny]" % (TINY, disc))
-    a.op("s_cmp_lg_u64 %s, 0" % TINY)
-    a.op("s_cbranch_scc1 .Lfl_tiny_%s_%%=" % tag, "a lane below 2^-96 (zero included): scaled path")
-    refine(a, disc, r.t0, r.t1, r.root)
-    a.label(".Lfl_rooted_%s_%%=" % tag)
+    root(a, r.lean, disc, None, ".Lfl_rooted_%s_%%=" % tag, ".Lfl_tiny_%s_%%=" % tag)
 
 
 def exact_tiny(a, disc, tag, r):
-    a.label(".Lfl_tiny_%s_%%=" % tag)
-    a.op("v_mul_f32_e32 %s, 0x5f800000, %s" % (r.t0, disc), "root with the 2^64 / 2^-32 scaling for tiny lanes (the scaled operand stays >= 2^-85: its residual is never subnormal)")
-    a.op("v_cndmask_b32_e64 %s, %s, %s, %s" % (r.t2, disc, r.t0, TINY))
-    a.op("v_rsq_f32_e32 %s, %s" % (r.t0, r.t2))
-    a.op("v_cmp_eq_f32_e32 vcc, 0, %s" % r.t2, "sqrt(+-0) = +-0 (rsq would make it 0 * inf)")
-    refine(a, r.t2, r.t0, r.t1, r.root)
-    a.op("v_cndmask_b32_e32 %s, %s, %s, vcc" % (r.root, r.root, r.t2))
-    a.op("v_mul_f32_e32 %s, 0x2f800000, %s" % (r.t0, r.root))
-    a.op("v_cndmask_b32_e64 %s, %s, %s, %s" % (r.root, r.root, r.t0, TINY))
-    a.op("s_branch .Lfl_rooted_%s_%%=" % tag)
+    tiny(a, r.lean, disc, ".Lfl_tiny_%s_%%=" % tag, ".Lfl_rooted_%s_%%=" % tag)
 
 
 def any_candidate(a, r, bank):
@@ -193,6 +117,7 @@ class PrimaryRegs:
         self.B, self.DISC = Pair(v + 24), Pair(v + 26)
         self.root = "v%d" % (v + 28)
         self.t0, self.t1, self.t2 = self.T0.h[0], self.T0.h[1], self.T1.h[0]
+        self.lean = lean_root(self)
 
 
 def fsreg(bank, field, k):
@@ -282,6 +207,7 @@ class ShadowRegs:
         self.OCC = Pair(v + 36)
         self.root = "v%d" % (v + 38)
         self.t0, self.t1, self.t2 = self.T0.h[0], self.T0.h[1], self.T1.h[0]
+        self.lean = lean_root(self)
 
 
 SHADOW_VGPR_LAST = VGPR_FIRST + 38
@@ -454,16 +380,7 @@ __device__ __forceinline__ void flat_shadow_scan(const void *groups, unsigned be
 
 
 def clobbers(vgpr_last=VGPR_LAST):
-    regs = ['"s%d"' % r for r in range(36, SGPR_LAST + 1)] + ['"v%d"' % r for r in range(VGPR_FIRST, vgpr_last + 1)]
-    lines, cur = [], '"memory", "vcc", "scc"'
-    for r in regs:
-        if len(cur) + len(r) + 2 > 118:
-            lines.append(cur + ",")
-            cur = "          " + r
-        else:
-            cur += ", " + r
-    lines.append(cur)
-    return "\n".join(lines)
+    return clobber_list(range(36, SGPR_LAST + 1), range(VGPR_FIRST, vgpr_last + 1))
 
 
 def primary():
@@ -527,9 +444,7 @@ def main():
     text += PRIMARY % {"body": primary(), "clobbers": clobbers()}
     text += SHADOW % {"body": shadow_body(), "clobbers": clobbers(SHADOW_VGPR_LAST)}
     text += "}  // namespace rt\n"
-    with open(OUT, "w") as f:
-        f.write(text)
-    print("wrote", OUT, "(%d lines)" % text.count("\n"))
+    write_header(OUT, text)
 
 
 if __name__ == "__main__":

@@ -22,15 +22,14 @@ s[24:73]; listed as clobbers).
 
 Run:  python3 tools/gen_skip2_asm.py   (writes the header; the build does not need this script)."""
 import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))          # asm_gen.py lives beside this script, wherever it is run or loaded from
+from asm_gen import UNDECLARED, Asm, Pair, RootRegs, Rotation, clobber_list, loops_marker, pk, pk_fma, root, sp, tiny, write_header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.path.join(ROOT, "rust-tracer_amd", "csrc", "rt_skip2_rot.hpp")
 
-COPIES = {"A": (0, 1, 2), "B": (1, 0, 2), "C": (2, 0, 1)}          # current, next, skip
-NEXT_COPY = {"A": "B", "B": "A", "C": "A"}
-SKIP_COPY = {"A": "C", "B": "C", "C": "B"}
-LAYOUT = "ACB"
-FLAG_LIMIT = "0x3fffffff"
 STRIDE = 32
 # The loops' scalar registers start at SB.  24 (not the 36 of the one-ray loops): the filtered shadow walk needs 50, and a CU admits eight
 # workgroups' worth of waves only up to .sgpr_count 80 (MI355X_MICROARCH.md, "Residency") -- s[24:73] + the hardware's six; the kernel keeps
@@ -40,45 +39,13 @@ BANK = (SB, SB + 8, SB + 16)
 NX = "s%d" % (SB + 24)
 LIGHT = SB + 42                                                      # three registers: the shadow rays' direction (the fourth pads the pair)
 SGPR_LAST, VGPR_FIRST, VGPR_LAST = SB + 45, 32, 63
-RESERVED = (32, 72, 73)
-
-
-def sp(first):
-    return "s[%d:%d]" % (first, first + 1)
+ROT = Rotation(".Lr2_", NX, STRIDE)
+FLAVOUR = "two-ray"                                                  # of asm_gen.UNDECLARED: the registers the clobber lists leave out
 
 
 ACT = (sp(SB + 26), sp(SB + 28))          # per half: the rays awake at the current node
 C = (sp(SB + 30), sp(SB + 32))            # per half: candidates -> the rays that go on (enter / hit)
 M, M2, TINY, EX = sp(SB + 34), sp(SB + 40), sp(SB + 36), sp(SB + 38)
-
-
-class Pair:
-    def __init__(self, lo):
-        self.p = "v[%d:%d]" % (lo, lo + 1)
-        self.h = ("v%d" % lo, "v%d" % (lo + 1))
-
-
-class Asm:
-    def __init__(self):
-        self.lines = []
-
-    def op(self, text, comment=None):
-        self.lines.append(("\t", text, comment))
-
-    def label(self, name):
-        self.lines.append(("", name + ":", None))
-
-    def extend(self, other):
-        self.lines.extend(other.lines)
-
-    def render(self, indent="        "):
-        out = []
-        for tab, text, comment in self.lines:
-            s = '%s"%s%s\\n"' % (indent, "" if tab == "" else "\\t", text)
-            if comment:
-                s += "  /* %s */" % comment
-            out.append(s)
-        return "\n".join(out)
 
 
 def fld(b, k):
@@ -109,39 +76,6 @@ def load(a, b, off, comment=None):
     a.op("s_load_dwordx8 s[%d:%d], %%[base], %s" % (BANK[b], BANK[b] + 7, off), comment)
 
 
-def pk(a, op, dst, x, y, sx=None, sy=None, neg_y=False, comment=None):
-    """dst = x op y on both rays.  sx / sy: SGPR NUMBER whose value is broadcast to both rays in place of a VGPR pair."""
-    sel, sel_hi = [0, 0], [1, 1]
-    if sx is not None:
-        x = "s[%d:%d]" % (sx & ~1, (sx & ~1) + 1)
-        sel[0] = sel_hi[0] = sx & 1
-    if sy is not None:
-        y = "s[%d:%d]" % (sy & ~1, (sy & ~1) + 1)
-        sel[1] = sel_hi[1] = sy & 1
-    mods = ""
-    if sel != [0, 0]:
-        mods += " op_sel:[%d,%d]" % tuple(sel)
-    if sel_hi != [1, 1]:
-        mods += " op_sel_hi:[%d,%d]" % tuple(sel_hi)
-    if neg_y:
-        mods += " neg_lo:[0,1] neg_hi:[0,1]"
-    a.op("v_pk_%s_f32 %s, %s, %s%s" % (op, dst, x, y, mods), comment)
-
-
-def pk_fma(a, dst, x, y, z, sx=None, comment=None):
-    """dst = x * y + z on both rays; sx: SGPR NUMBER broadcast to both rays in place of x."""
-    sel, sel_hi = [0, 0, 0], [1, 1, 1]
-    if sx is not None:
-        x = "s[%d:%d]" % (sx & ~1, (sx & ~1) + 1)
-        sel[0] = sel_hi[0] = sx & 1
-    mods = ""
-    if sel != [0, 0, 0]:
-        mods += " op_sel:[%d,%d,%d]" % tuple(sel)
-    if sel_hi != [1, 1, 1]:
-        mods += " op_sel_hi:[%d,%d,%d]" % tuple(sel_hi)
-    a.op("v_pk_fma_f32 %s, %s, %s, %s%s" % (dst, x, y, z, mods), comment)
-
-
 class Regs:
     """v[32:63].  Primary: D = ray directions, BEST / BITEM the hit; shadow: D = ray origins, V the centre - origin vector."""
 
@@ -159,6 +93,7 @@ class Regs:
         self.root = "v%d" % (v + 28)
         # 32-bit temporaries of the exact path: the T pairs are free once the step's arithmetic is done
         self.t0, self.t1, self.t3, self.t4, self.t5 = self.T0.h[0], self.T0.h[1], self.T1.h[0], self.T1.h[1], self.T2.h[0]
+        self.lean = lean_root(self)
 
 
 U = (TINY, sp(SB + 46))             # filtered shadow walk, per half: the candidates the bounds cannot settle (TINY is only the root's scratch)
@@ -188,55 +123,12 @@ class RegsSF:
         self.B, self.Q, self.DISC = E[6], E[2], E[1]
         self.t0, self.t1, self.t3, self.t4, self.t5 = E[3].h[0], E[3].h[1], E[4].h[0], E[4].h[1], E[5].h[0]
         self.root = E[5].h[1]
+        self.lean = lean_root(self)
 
 
-def refine(a, r, x):
-    a.op("v_mul_f32_e32 %s, %s, %s" % (r.root, x, r.t0), "g = x*y")
-    a.op("v_mul_f32_e32 %s, 0.5, %s" % (r.t0, r.t0), "h = y/2")
-    a.op("v_fma_f32 %s, -%s, %s, %s" % (r.t1, r.root, r.root, x), "r = x - g*g")
-    a.op("v_fma_f32 %s, %s, %s, %s" % (r.root, r.t1, r.t0, r.root), "g + r*h")
-
-
-def root(a, r, disc, need_mask, done_label, tiny_label):
-    """Correctly rounded sqrt(disc) into r.root (== sqrt_rn_lean).  need_mask: the lanes whose root is used."""
-    a.op("v_rsq_f32_e32 %s, %s" % (r.t0, disc))
-    a.op("v_cmp_lt_f32_e64 %s, |%s|, %%[tiny]" % (TINY, disc))
-    a.op("s_and_b64 %s, %s, %s" % (M2, TINY, need_mask))
-    a.op("s_cbranch_scc1 %s" % tiny_label, "some needed lane below 2^-96 (zero included): scaled path")
-    refine(a, r, disc)
-    a.label(done_label)
-
-
-def tiny(a, r, disc, tiny_label, done_label):
-    a.label(tiny_label)
-    a.op("v_mul_f32_e32 %s, 0x5f800000, %s" % (r.t0, disc), "root with the 2^64 / 2^-32 scaling for tiny lanes (the scaled operand stays >= 2^-85: its residual is never subnormal)")
-    a.op("v_cndmask_b32_e64 %s, %s, %s, %s" % (r.t5, disc, r.t0, TINY))
-    a.op("v_rsq_f32_e32 %s, %s" % (r.t0, r.t5))
-    a.op("v_cmp_eq_f32_e64 %s, 0, %s" % (M2, r.t5), "sqrt(+-0) = +-0 (rsq would make it 0 * inf)")
-    refine(a, r, r.t5)
-    a.op("v_cndmask_b32_e64 %s, %s, %s, %s" % (r.root, r.root, r.t5, M2))
-    a.op("v_mul_f32_e32 %s, 0x2f800000, %s" % (r.t0, r.root))
-    a.op("v_cndmask_b32_e64 %s, %s, %s, %s" % (r.root, r.root, r.t0, TINY))
-    a.op("s_branch %s" % done_label)
-
-
-def top_of(name):
-    return ".Lr2_%s_top_%%=" % name
-
-
-def emit_skip(a, name, c, lab):
-    a.label(lab("skip"))
-    a.op("s_add_u32 %s, %s, %d" % (NX, skip(c), STRIDE), "jump over the subtree")
-    a.op("s_waitcnt lgkmcnt(0)")
-    nxt = SKIP_COPY[name]
-    if LAYOUT.index(nxt) != LAYOUT.index(name) + 1:
-        a.op("s_branch %s" % top_of(nxt))
-
-
-def emit_next(a, name):
-    a.op("s_add_u32 %s, %s, %d" % (NX, NX, STRIDE))
-    a.op("s_waitcnt lgkmcnt(0)")
-    a.op("s_branch %s" % top_of(NEXT_COPY[name]))
+def lean_root(r):
+    """The registers of the exact path's root: `tiny & need_mask` and the zero test share the second scratch mask."""
+    return RootRegs(t0=r.t0, t1=r.t1, scaled=r.t5, root=r.root, tiny=TINY, zero=M2, need=M2)
 
 
 def step_top(a, r, c, s, terms):
@@ -270,7 +162,7 @@ def sleep_culled(a, r, c):
 
 
 def kind_test(a, c, lab):
-    a.op("s_cmp_gt_u32 %s, %s" % (item(c), FLAG_LIMIT), "an ITEM or the END node?  (flag bits of the item word)")
+    a.op("s_cmp_gt_u32 %s, %s" % (item(c), ROT.FLAG_LIMIT), "an ITEM or the END node?  (flag bits of the item word)")
     a.op("s_cbranch_scc1 %s" % lab("flagged"))
 
 
@@ -315,7 +207,7 @@ def primary_go(a, r, h, tag, lab, tinies):
     done = lab("pg%s%d" % (tag, h))
     a.op("s_cmp_eq_u64 %s, 0" % C[h])
     a.op("s_cbranch_scc1 %s" % done)
-    root(a, r, r.DISC.h[h], C[h], lab("rooted%s%d" % (tag, h)), lab("tiny%s%d" % (tag, h)))
+    root(a, r.lean, r.DISC.h[h], C[h], lab("rooted%s%d" % (tag, h)), lab("tiny%s%d" % (tag, h)))
     tinies.append((r.DISC.h[h], lab("tiny%s%d" % (tag, h)), lab("rooted%s%d" % (tag, h))))
     a.op("v_add_f32_e32 %s, %s, %s" % (r.t3, r.B.h[h], r.root), "t2")
     a.op("v_sub_f32_e32 %s, %s, %s" % (r.t4, r.B.h[h], r.root), "t1")
@@ -338,7 +230,6 @@ def primary_update(a, r, h, c, done, own=False):
     a.label(done)
 
 
-FUSED = True                    # the flavour being generated: False = plain streams (a BOUND has no sphere of its own: non-concentric scenes)
 KK = SB + 46                         # s82: 1 + 2^-20 (bound_shortcut), the low half of the pair a packed instruction reads it through
 G = (sp(SB + 42), sp(SB + 44))            # primary loop, per half: the rays the root-free decision lets enter (the shadow loops keep the light there)
 SGPR_LAST_PRIMARY = SB + 47
@@ -367,15 +258,16 @@ def bound_shortcut(a, r, c, lab):
     a.op("s_branch %s" % lab("bdecided"))
 
 
-def primary_copy(r, name):
-    c, n, s = COPIES[name]
-    lab = lambda x: ".Lr2_%s_%s_%%=" % (name, x)
+def primary_copy(r, name, fused):
+    """fused: the stream's BOUND nodes carry the sphere they are built around; False = plain streams (non-concentric scenes)."""
+    c, n, s = ROT.COPIES[name]
+    lab = ROT.lab(name)
     m, k, tinies = Asm(), Asm(), []
     m.label(lab("top"))
     load(m, s, skip(c), "the likely successor, while this node is processed")
     primary_filter(m, r, c)
     m.op("s_cbranch_vccnz %s" % lab("hit"))
-    emit_skip(m, name, c, lab)
+    ROT.emit_skip(m, name, skip(c))
     # ---------------- the bound cannot rule the node out for some ray: the reference's discriminant, for every ray ----------------
     k.label(lab("hit"))
     primary_terms_after_filter(k, r, c)
@@ -393,7 +285,7 @@ def primary_copy(r, name):
     k.op("s_cbranch_scc0 %s" % lab("skip"), "nobody enters (the rays that culled it are awake again at `skip`)")
     load(k, n, NX, "somebody enters: fetch the group's first child")
     sleep_culled(k, r, c)
-    if FUSED:
+    if fused:
         # the group's own sphere, for the rays that entered: same centre, so v, b and b*b - vv are the values just formed
         pk(k, "add", r.DISC.p, None, r.Q.p, sx=own(c), comment="disc = (b*b - vv) + rr of the group's own sphere")
         k.op("v_cmp_le_f32_e64 %s, 0, %s" % (M, r.DISC.h[0]))
@@ -405,7 +297,7 @@ def primary_copy(r, name):
         for h in range(2):
             primary_update(k, r, h, c, primary_go(k, r, h, "f", lab, tinies), own=True)
     k.label(lab("next"))
-    emit_next(k, name)
+    ROT.emit_next(k, name)
     # ITEM (primitive.rs:77-84) or END
     k.label(lab("flagged"))
     k.op("s_bitcmp1_b32 %s, 30" % tag(c))
@@ -414,13 +306,14 @@ def primary_copy(r, name):
         primary_update(k, r, h, c, primary_go(k, r, h, "i", lab, tinies))
     k.op("s_branch %s" % lab("skip"), "an ITEM's `skip` is the node behind it")
     for disc, tl, dl in tinies:
-        tiny(k, r, disc, tl, dl)
+        tiny(k, r.lean, disc, tl, dl)
     return m, k
 
 
 # ------------------------------------------------------------------------------------------------------------------- shadow
 
-def shadow_terms(a, r, c):
+def shadow_terms(a, r, c, rr=None):
+    """rr: SGPR number of the squared radius where it is not the node's fourth term (a group's own sphere)."""
     pk(a, "add", r.VX.p, None, r.DX.p, sx=fld(c, 0), neg_y=True, comment="v = centre - origin, both rays   primitive.rs:56")
     pk(a, "add", r.VY.p, None, r.DY.p, sx=fld(c, 1), neg_y=True)
     pk(a, "add", r.VZ.p, None, r.DZ.p, sx=fld(c, 2), neg_y=True)
@@ -436,7 +329,7 @@ def shadow_terms(a, r, c):
     pk(a, "add", r.VX.p, r.VX.p, r.VZ.p, comment="dot(v, v)")
     pk(a, "mul", r.T0.p, r.B.p, r.B.p)
     pk(a, "add", r.Q.p, r.T0.p, r.VX.p, neg_y=True)
-    pk(a, "add", r.DISC.p, None, r.Q.p, sx=fld(c, 3), comment="disc = (b*b - vv) + rr   primitive.rs:58")
+    pk(a, "add", r.DISC.p, None, r.Q.p, sx=fld(c, 3) if rr is None else rr, comment="disc = (b*b - vv) + rr   primitive.rs:58")
 
 
 def shadow_decide(a, r, h, tag, lab, tinies):
@@ -445,7 +338,7 @@ def shadow_decide(a, r, h, tag, lab, tinies):
     a.op("v_cmp_gt_f32_e64 %s, 0, %s" % (M, r.B.h[h]), "b < 0: t2 may still be negative")
     a.op("s_and_b64 %s, %s, %s" % (M, M, C[h]))
     a.op("s_cbranch_scc0 %s" % done, "nobody needs the root: hit = candidates")
-    root(a, r, r.DISC.h[h], M, lab("rooted%s%d" % (tag, h)), lab("tiny%s%d" % (tag, h)))
+    root(a, r.lean, r.DISC.h[h], M, lab("rooted%s%d" % (tag, h)), lab("tiny%s%d" % (tag, h)))
     tinies.append((r.DISC.h[h], lab("tiny%s%d" % (tag, h)), lab("rooted%s%d" % (tag, h))))
     a.op("v_add_f32_e32 %s, %s, %s" % (r.t3, r.B.h[h], r.root), "t2")
     a.op("v_cmp_gt_f32_e64 %s, 0, %s" % (M2, r.t3), "t2 < 0")
@@ -455,13 +348,13 @@ def shadow_decide(a, r, h, tag, lab, tinies):
 
 
 def shadow_copy(r, name):
-    c, n, s = COPIES[name]
-    lab = lambda x: ".Lr2_%s_%s_%%=" % (name, x)
+    c, n, s = ROT.COPIES[name]
+    lab = ROT.lab(name)
     m, k, tinies = Asm(), Asm(), []
     m.label(lab("top"))
     step_top(m, r, c, s, shadow_terms)
     m.op("s_cbranch_vccnz %s" % lab("hit"))
-    emit_skip(m, name, c, lab)
+    ROT.emit_skip(m, name, skip(c))
     k.label(lab("hit"))
     wake_check(k, r, lab)
     kind_test(k, c, lab)
@@ -484,7 +377,7 @@ def shadow_copy(r, name):
     k.op("s_or_b64 %s, %s, %s" % (M, C[0], C[1]))
     k.op("s_cbranch_scc1 .Lr2_fin_%=", "any hit ends those rays; hand them to the caller")
     k.label(lab("next"))
-    emit_next(k, name)
+    ROT.emit_next(k, name)
     k.label(lab("flagged"))
     k.op("s_bitcmp1_b32 %s, 30" % item(c))
     k.op("s_cbranch_scc1 .Lr2_exit_%=", "END: every ray is awake here and hits it")
@@ -494,7 +387,7 @@ def shadow_copy(r, name):
     k.op("s_cbranch_scc0 %s" % lab("skip"), "an ITEM's `skip` is the node behind it")
     k.op("s_branch .Lr2_fin_%=")
     for disc, tl, dl in tinies:
-        tiny(k, r, disc, tl, dl)
+        tiny(k, r.lean, disc, tl, dl)
     return m, k
 
 # ---------------------------------------------------------------------------------------------------------- shadow, filtered
@@ -556,22 +449,7 @@ def second_chance(k, r, r2o, exact2, none_label, some_label):
 def exact_packed(k, r, src, rr, lab, tag, tinies):
     """The reference's own test (primitive.rs:55-72) for both rays of every lane, node terms from bank `src` (a Node<float> record of
     the exact stream): C[h] = awake rays (ACT[h]) that hit the sphere with squared radius SGPR number `rr`."""
-    pk(k, "add", r.VX.p, None, r.DX.p, sx=fld(src, 0), neg_y=True, comment="v = centre - origin, both rays   primitive.rs:56")
-    pk(k, "add", r.VY.p, None, r.DY.p, sx=fld(src, 1), neg_y=True)
-    pk(k, "add", r.VZ.p, None, r.DZ.p, sx=fld(src, 2), neg_y=True)
-    pk(k, "mul", r.T0.p, None, r.VX.p, sx=LIGHT + 0)
-    pk(k, "mul", r.T1.p, None, r.VY.p, sx=LIGHT + 1)
-    pk(k, "mul", r.T2.p, None, r.VZ.p, sx=LIGHT + 2)
-    pk(k, "add", r.T0.p, r.T0.p, r.T1.p)
-    pk(k, "add", r.B.p, r.T0.p, r.T2.p, comment="b = dot(v, dir)   primitive.rs:57")
-    pk(k, "mul", r.VX.p, r.VX.p, r.VX.p)
-    pk(k, "mul", r.VY.p, r.VY.p, r.VY.p)
-    pk(k, "mul", r.VZ.p, r.VZ.p, r.VZ.p)
-    pk(k, "add", r.VX.p, r.VX.p, r.VY.p)
-    pk(k, "add", r.VX.p, r.VX.p, r.VZ.p, comment="dot(v, v)")
-    pk(k, "mul", r.T0.p, r.B.p, r.B.p)
-    pk(k, "add", r.Q.p, r.T0.p, r.VX.p, neg_y=True)
-    pk(k, "add", r.DISC.p, None, r.Q.p, sx=rr, comment="disc = (b*b - vv) + rr   primitive.rs:58")
+    shadow_terms(k, r, src, rr)
     k.op("v_cmp_le_f32_e64 %s, 0, %s" % (C[0], r.DISC.h[0]))
     k.op("v_cmp_le_f32_e32 vcc, 0, %s" % r.DISC.h[1])
     k.op("s_and_b64 %s, %s, %s" % (C[0], C[0], ACT[0]))
@@ -580,11 +458,11 @@ def exact_packed(k, r, src, rr, lab, tag, tinies):
         shadow_decide(k, r, h, tag, lab, tinies)
 
 
-def shadow_copy_filt(r, name):
+def shadow_copy_filt(r, name, fused):
     """Two-sided flavour of shadow_copy: the walk reads the FNodeS stream (%[base]); a step that leaves some ray between the bounds
     fetches the node's Node record from the exact stream (%[base2]) and runs the reference's arithmetic for every ray."""
-    c, n, s = COPIES[name]
-    lab = lambda x: ".Lr2_%s_%s_%%=" % (name, x)
+    c, n, s = ROT.COPIES[name]
+    lab = ROT.lab(name)
     m, k, tinies = Asm(), Asm(), []
     m.label(lab("top"))
     load(m, s, s_skip(c), "the likely successor, while this node is processed")
@@ -595,11 +473,7 @@ def shadow_copy_filt(r, name):
     m.op("v_min_f32_e32 %s, %s, %s" % (r.E[0].h[0], r.P2.h[0], r.P2.h[1]))
     m.op("v_cmp_ngt_f32_e64 vcc, %s, |%s|" % (r.E[0].h[0], s_r2o(c)), "some ray not beyond the outer bound?  (NaN: a wave with an uncovered ray passes)")
     m.op("s_cbranch_vccnz %s" % lab("hit"))
-    m.label(lab("skip"))
-    m.op("s_add_u32 %s, %s, %d" % (NX, s_skip(c), STRIDE), "jump over the subtree")
-    m.op("s_waitcnt lgkmcnt(0)")
-    if LAYOUT.index(SKIP_COPY[name]) != LAYOUT.index(name) + 1:
-        m.op("s_branch %s" % top_of(SKIP_COPY[name]))
+    ROT.emit_skip(m, name, s_skip(c))
     # ---------------- some ray (awake or not) is inside the outer bound ----------------
     k.label(lab("hit"))
     for h in range(2):
@@ -620,7 +494,7 @@ def shadow_copy_filt(r, name):
         k.op("s_andn2_b64 exec, %s, %s" % (ACT[h], C[h]), "rays that may not enter sleep until `skip`" if h == 0 else None)
         k.op("v_mov_b32_e32 %s, %s" % (r.RES.h[h], s_skip(c)))
     k.op("s_mov_b64 exec, %s" % EX)
-    if FUSED:
+    if fused:
         for h in range(2):
             k.op("s_mov_b64 %s, %s" % (ACT[h], C[h]), "the rays that are awake at the next node" if h == 0 else None)
         outer_cmp(k, r, s_r2o_own(c))
@@ -633,7 +507,7 @@ def shadow_copy_filt(r, name):
         k.op("s_branch .Lr2_fin_%=", "any hit ends those rays; hand them to the caller (it starts again behind this node)")
     k.label(lab("next"))
     load(k, n, NX, "somebody entered: fetch the group's first child")
-    emit_next(k, name)
+    ROT.emit_next(k, name)
     # ITEM or END
     k.label(lab("flagged"))
     k.op("s_bitcmp1_b32 %s, 31" % s_r2o_own(c))
@@ -652,7 +526,7 @@ def shadow_copy_filt(r, name):
     k.op("s_cbranch_scc0 %s" % lab("skip"))
     inner_terms(k, r)                                # the own sphere's bounds read INN and TT again
     k.op("s_branch %s" % lab("decided"))
-    if FUSED:
+    if fused:
         k.label(lab("exactown"))
         second_chance(k, r, s_r2o_own(c), lab("exactown2"), lab("next"), lab("owndecided"))
         k.label(lab("exactown2"))
@@ -665,15 +539,16 @@ def shadow_copy_filt(r, name):
         k.op("s_cbranch_scc0 %s" % lab("next"))
         k.op("s_branch %s" % lab("owndecided"))
     for disc, tl, dl in tinies:
-        tiny(k, r, disc, tl, dl)
+        tiny(k, r.lean, disc, tl, dl)
     return m, k
 
 
-def shadow_filt():
+def shadow_filt(fused):
     """One invocation walks the whole stream: a ray that hits an ITEM (or a group's own sphere) retires INSIDE the loop -- resume =
     n + 1 (asleep at every node, told apart from the rays that never had a shadow ray: resume = n) -- and the walk goes on at the first
     node any ray still wants (the wave minimum of max(resume, NX), a DPP reduction).  The operands are dead once copied in."""
     a, r = Asm(), RegsSF()
+    a.op(loops_marker(FLAVOUR))
     a.op("s_load_dwordx16 s[%d:%d], %%[fc], 0x0" % (FC, FC + 15), "FilterConsts: m0, e1, e2, l, a0, k1, kc, ro2")
     a.op("s_mov_b64 %s, exec" % EX)
     a.op("s_waitcnt lgkmcnt(0)")
@@ -710,7 +585,7 @@ def shadow_filt():
     a.op("s_mov_b32 %s, %d" % (NX, STRIDE))
     load(a, 0, "0x0")
     a.op("s_waitcnt lgkmcnt(0)")
-    assemble(a, r, shadow_copy_filt)
+    ROT.assemble(a, lambda name: shadow_copy_filt(r, name, fused))
     # ---- some ray hit the ITEM (or the group's own sphere) of the current node: C[h]
     tmp = "s" + M[2:].split(":")[0]
     w, t = r.E[0].h[0], (r.E[0].h[1], r.E[1].h[0])
@@ -740,24 +615,15 @@ def shadow_filt():
     a.op("s_add_u32 %s, %s, %d" % (NX, tmp, STRIDE))
     load(a, 0, tmp)
     a.op("s_waitcnt lgkmcnt(0)")
-    a.op("s_branch %s" % top_of("A"))
+    a.op("s_branch %s" % ROT.top_of("A"))
     a.label(".Lr2_exit_%=")
     a.op("s_waitcnt lgkmcnt(0)")
     return a.render()
 
 
-def assemble(a, r, copy_fn):
-    mains, colds = {}, {}
-    for name in "ABC":
-        mains[name], colds[name] = copy_fn(r, name)
-    for name in LAYOUT:
-        a.extend(mains[name])
-    for name in "ABC":
-        a.extend(colds[name])
-
-
-def primary():
+def primary(fused):
     a, r = Asm(), Regs(False)
+    a.op(loops_marker(FLAVOUR))
     # (the rays' directions, resume and the results ARE the loop's registers: the statement binds its operands to v32.. directly -- eight
     # copies and eight registers fewer at the statement, which is what stood between k_render_skip2 and its eighth wave per SIMD)
     for h in range(2):
@@ -768,7 +634,7 @@ def primary():
     a.op("s_mov_b32 s%d, %%[kk]" % KK, "1 + 2^-20 where a packed instruction can read it")
     load(a, 0, "0x0")
     a.op("s_waitcnt lgkmcnt(0)")
-    assemble(a, r, primary_copy)
+    ROT.assemble(a, lambda name: primary_copy(r, name, fused))
     a.label(".Lr2_exit_%=")
     a.op("s_waitcnt lgkmcnt(0)")
     return a.render()
@@ -776,6 +642,7 @@ def primary():
 
 def shadow():
     a, r = Asm(), Regs(True)
+    a.op(loops_marker(FLAVOUR))
     for h in range(2):
         a.op("v_mov_b32_e32 %s, %%[ox%d]" % (r.DX.h[h], h), "operands into the loop's own registers" if h == 0 else None)
         a.op("v_mov_b32_e32 %s, %%[oy%d]" % (r.DY.h[h], h))
@@ -789,7 +656,7 @@ def shadow():
     a.op("s_mov_b64 %s, exec" % EX)
     load(a, 0, "%[start]")
     a.op("s_waitcnt lgkmcnt(0)")
-    assemble(a, r, shadow_copy)
+    ROT.assemble(a, lambda name: shadow_copy(r, name))
     a.label(".Lr2_fin_%=")
     for h in range(2):
         a.op("v_cndmask_b32_e64 %s, 0, 1, %s" % (r.FIN.h[h], C[h]), "the rays that hit the ITEM (or the group's own sphere) of the current node" if h == 0 else None)
@@ -836,7 +703,6 @@ __device__ __forceinline__ void %(name)s(const void *nodes, const float (&dx)[2]
     const float tiny = 0x1p-96f, kk = 0x1.00001p+0f;       // kk = 1 + 2^-20 (bound_shortcut)
     unsigned res0 = resume[0], res1 = resume[1];          // (the loop's RES pair; what it leaves there is of no interest)
     asm volatile(
-        "\\t; rt-loops two-ray: undeclared s32, s[72:73]\\n"
 %(body)s
         : [best0] "={v52}"(best_out[0]), [best1] "={v53}"(best_out[1]), [item0] "={v54}"(item_out[0]), [item1] "={v55}"(item_out[1]),
           [res0] "+{v38}"(res0), [res1] "+{v39}"(res1)
@@ -859,7 +725,6 @@ __device__ __forceinline__ unsigned skip2_shadow_rot_fused(const void *nodes, un
     unsigned stop;
     start = (unsigned)__builtin_amdgcn_readfirstlane((int)start);       // wave-uniform by construction; the operand must be an SGPR
     asm volatile(
-        "\\t; rt-loops two-ray: undeclared s32, s[72:73]\\n"
 %(body)s
         : [fin0] "=v"(fin[0]), [fin1] "=v"(fin[1]), [rout0] "=v"(resume[0]), [rout1] "=v"(resume[1]), [stop] "=&s"(stop)
         : [base] "s"(nodes), [n] "s"(n_bytes), [start] "s"(start), [ox0] "v"(ox[0]), [ox1] "v"(ox[1]), [oy0] "v"(oy[0]), [oy1] "v"(oy[1]),
@@ -883,7 +748,6 @@ __device__ __forceinline__ void %(name)s(const void *nodes, unsigned n_bytes, co
 {
     const float tiny = 0x1p-96f;
     asm volatile(
-        "\\t; rt-loops two-ray: undeclared s32, s[72:73]\\n"
 %(body)s
         : [res0] "+{v38}"(resume[0]), [res1] "+{v39}"(resume[1])
         : [base] "s"(nodes), [n] "s"(n_bytes), [ox0] "{v32}"(ox[0]), [ox1] "{v33}"(ox[1]), [oy0] "{v34}"(oy[0]), [oy1] "{v35}"(oy[1]),
@@ -904,35 +768,22 @@ def clobbers(last=SGPR_LAST, bound=()):
     # amdgpu_waves_per_eu(8)) -- it never allocates them, and naming them is what `-Winline-asm` objects to.  That the loops may use them
     # rests on the kernel's .sgpr_count and on no compiler-generated instruction touching them: tests/test_kernel_resources.py checks both
     # on the generated assembly (tools/check_reserved_registers.py).
-    regs = ['"s%d"' % r for r in range(SB, last + 1) if r not in RESERVED] + ['"v%d"' % r for r in range(VGPR_FIRST, VGPR_LAST + 1) if r not in bound]
-    lines, cur = [], '"memory", "vcc", "scc"'
-    for r in regs:
-        if len(cur) + len(r) + 2 > 118:
-            lines.append(cur + ",")
-            cur = "          " + r
-        else:
-            cur += ", " + r
-    lines.append(cur)
-    return "\n".join(lines)
+    return clobber_list([r for r in range(SB, last + 1) if r not in UNDECLARED[FLAVOUR][1]],
+                        [r for r in range(VGPR_FIRST, VGPR_LAST + 1) if r not in bound])
 
 
 def main():
     text = HEADER
-    global FUSED
-    text += PRIMARY_FN % {"name": "skip2_primary_rot_fused", "body": primary(), "clobbers": clobbers(SGPR_LAST_PRIMARY, PRIMARY_BOUND)}
+    text += PRIMARY_FN % {"name": "skip2_primary_rot_fused", "body": primary(True), "clobbers": clobbers(SGPR_LAST_PRIMARY, PRIMARY_BOUND)}
     text += SHADOW_FN % {"body": shadow(), "clobbers": clobbers()}
-    text += SHADOW_FN_FILT % {"name": "skip2_shadow_rot_filt_fused", "body": shadow_filt(), "clobbers": clobbers(SGPR_LAST_FILT, SHADOW_BOUND)}
+    text += SHADOW_FN_FILT % {"name": "skip2_shadow_rot_filt_fused", "body": shadow_filt(True), "clobbers": clobbers(SGPR_LAST_FILT, SHADOW_BOUND)}
     # the same two loops over PLAIN filtered streams: scenes whose bounds have no sphere of their own (the automatic hierarchy of an
     # arbitrary sphere list) -- a BOUND step ends where somebody enters
-    FUSED = False
     text += "// The plain-stream flavours (a BOUND node carries no sphere of its own): FNode / FNodeS of the scene's plain streams.\n"
-    text += PRIMARY_FN % {"name": "skip2_primary_rot", "body": primary(), "clobbers": clobbers(SGPR_LAST_PRIMARY, PRIMARY_BOUND)}
-    text += SHADOW_FN_FILT % {"name": "skip2_shadow_rot_filt", "body": shadow_filt(), "clobbers": clobbers(SGPR_LAST_FILT, SHADOW_BOUND)}
-    FUSED = True
+    text += PRIMARY_FN % {"name": "skip2_primary_rot", "body": primary(False), "clobbers": clobbers(SGPR_LAST_PRIMARY, PRIMARY_BOUND)}
+    text += SHADOW_FN_FILT % {"name": "skip2_shadow_rot_filt", "body": shadow_filt(False), "clobbers": clobbers(SGPR_LAST_FILT, SHADOW_BOUND)}
     text += "}  // namespace rt\n"
-    with open(OUT, "w") as f:
-        f.write(text)
-    print("wrote", OUT, "(%d lines)" % text.count("\n"))
+    write_header(OUT, text)
 
 
 if __name__ == "__main__":

@@ -38,42 +38,16 @@ against the IEEE sqrt on all 2^32 inputs): 5 instructions; round 1's v_sqrt_f32 
 
 Run:  python3 tools/gen_skip_asm.py   (writes the header; the build does not need this script)."""
 import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))          # asm_gen.py lives beside this script, wherever it is run or loaded from
+import asm_gen
+from asm_gen import UNDECLARED, Asm, RootRegs, Rotation, clobber_list, loops_marker, sp, write_header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.path.join(ROOT, "rust-tracer_amd", "csrc", "rt_skip_rot.hpp")
-
-COPIES = {"A": (0, 1, 2), "B": (1, 0, 2), "C": (2, 0, 1)}          # current, next, skip
-NEXT_COPY = {"A": "B", "B": "A", "C": "A"}
-SKIP_COPY = {"A": "C", "B": "C", "C": "B"}
-LAYOUT = "ACB"                                                     # main paths in this order: A.skip and C.skip fall through
-FLAG_LIMIT = "0x3fffffff"                                          # item word above this: ITEM (bit 31) or END (bit 30)
-
-
-class Asm:
-    def __init__(self):
-        self.lines = []
-
-    def op(self, text, comment=None):
-        self.lines.append(("\t", text, comment))
-
-    def label(self, name):
-        self.lines.append(("", name + ":", None))
-
-    def extend(self, other):
-        self.lines.extend(other.lines)
-
-    def render(self, indent="        "):
-        out = []
-        for tab, text, comment in self.lines:
-            s = '%s"%s%s\\n"' % (indent, "" if tab == "" else "\\t", text)
-            if comment:
-                s += "  /* %s */" % comment
-            out.append(s)
-        return "\n".join(out)
-
-
-def sp(first, n=2):
-    return "s[%d:%d]" % (first, first + n - 1)
+COPIES, FLAG_LIMIT = Rotation.COPIES, Rotation.FLAG_LIMIT
+FILT_ARGS = ", float q1, float q2, float ol, float a0, float k1, float kc, const void *exact"      # what a filtered shadow walk takes on top
 
 
 # The shadow bound's in-plane distance on packed math: the lane's (q1, q2) sit in an aligned register pair, the node's (w1, w2) are the first
@@ -81,7 +55,6 @@ def sp(first, n=2):
 # of a plain one, profiles/r02_valu_issue_probe.json).  The pairs are physical registers because inline assembly cannot name the halves of
 # a 64-bit operand: QQ is an input ("{v[40:41]}"), TT a clobber.
 QQ, TT = (30, 31), (32, 33)
-PACKED_CLOBBERS = ['"v%d"' % r for r in TT]
 QQ_IN = '[qq] "{v[%d:%d]}"(qq)' % QQ
 QQ_DECL = "\n    const rt_v2f qq = { q1, q2 };"
 
@@ -97,19 +70,31 @@ def packed_p2(a, bank, dst):
 
 
 class Prec:
-    """Register plan and the precision-dependent instruction sequences."""
-    filt = False
+    """Register plan and the precision-dependent instruction sequences.  What tells the flavours apart is declared here, with the value
+    most of them have; main() and the emitters read these and never ask which class they were given."""
+    filt = False                     # a conservative filter in front of every test (F32F)
     shortcut = False                 # the primary BOUND step's root-free decision (F32F.bound_shortcut)
     sure_enter = False               # the f64 primary BOUND step that needs no exact record at all (F64F.sure_enter_path)
+    fn_suffix = ""                   # of the functions' names, between "_filt" and "_fused"
+    flavour = None                   # where the loops leave registers undeclared: their name in asm_gen.UNDECLARED ...
+    reserved = ()                    # ... and those registers
+    lreg = "s"                       # constraint of the shadow rays' direction operands
+    shadow_companion = None          # the class whose loops are this flavour's shadow walk (None: its own)
     primary_extra_args = ""
     primary_extra_in = ""
-    primary_only = False
     shadow_extra_in = ""
     shadow_extra_out = ""
     shadow_extra_decl = ""
-    shadow_vclobbers = []            # vector registers the shadow loops name directly (packed_p2)
+    shadow_vclobbers = ()            # vector registers the shadow loops name directly (packed_p2)
     ftmp = "%[t0]"                   # an f32 scratch register of the two-sided shadow bound
     shadow_subst = ()                # named operands that are such registers
+
+    def __init__(self, pad=(0, 0)):
+        self.pad = pad               # design-time probe (main): idle vector / scalar instructions in every step of the f32 filtered walks
+        self.rot = Rotation(".Lrt_", self.NX, self.stride)
+
+    def shadow_walk(self, name, fused):
+        return shadow_copy(self, name, fused)
 
     def kind_test(self, a, c, lab):
         a.op("s_cmp_gt_u32 %s, %s" % (self.item(c), FLAG_LIMIT), "an ITEM or the END node?  (flag bits of the item word)")
@@ -126,11 +111,12 @@ class Prec:
 
 
 class F32(Prec):
-    name, ctype, stride = "f32", "float", 32
+    ctype, stride = "float", 32
     bank_first, bank_dwords, load_op = (36, 44, 52), 8, "s_load_dwordx8"
     NX = "s60"
     ACT, M54, M56, M58, TINY, EX = sp(62), sp(64), sp(66), sp(68), sp(70), sp(72)
     clobber_lo, clobber_hi = 36, 73
+    lean = RootRegs(t0="%[t0]", t1="%[t1]", scaled="%[t5]", root="%[root]", tiny=TINY, zero=M58, need=M56)      # asm_gen.root
 
     def fld(self, b, k):                             # geometry term k = 0..4
         return "s%d" % (self.bank(b) + k)
@@ -157,7 +143,8 @@ class F32(Prec):
         a.op("v_subrev_f32_e32 %%[q], %s, %%[t0]" % self.fld(c, 3))
         a.op("v_add_f32_e32 %%[disc], %s, %%[q]" % self.fld(c, 4))
 
-    def shadow_terms(self, a, c):
+    def shadow_terms(self, a, c, rr=None):
+        """rr: the register of the squared radius where it is not the node's own (a group's own sphere)."""
         a.op("v_sub_f32_e32 %%[vx], %s, %%[ox]" % self.fld(c, 0), "v = centre - origin   primitive.rs:56")
         a.op("v_sub_f32_e32 %%[vy], %s, %%[oy]" % self.fld(c, 1))
         a.op("v_sub_f32_e32 %%[vz], %s, %%[oz]" % self.fld(c, 2))
@@ -173,40 +160,17 @@ class F32(Prec):
         a.op("v_add_f32_e32 %[t3], %[t3], %[t5]", "dot(v, v)")
         a.op("v_mul_f32_e32 %[t0], %[b], %[b]")
         a.op("v_sub_f32_e32 %[q], %[t0], %[t3]")
-        a.op("v_add_f32_e32 %%[disc], %s, %%[q]" % self.fld(c, 3), "disc = (b*b - vv) + rr   primitive.rs:58")
+        a.op("v_add_f32_e32 %%[disc], %s, %%[q]" % (rr or self.fld(c, 3)), "disc = (b*b - vv) + rr   primitive.rs:58")
 
     def fused_disc(self, a, c):
         a.op("v_add_f32_e32 %%[disc], %s, %%[q]" % self.own(c), "disc = (b*b - vv) + rr of the group's own sphere")
 
-    def refine(self, a, x):
-        """t0 = y ~ 1/sqrt(x) (v_rsq_f32, 1 ulp)  ->  %[root] = the correctly rounded sqrt(x): g = x*y, h = y/2, r = x - g*g (exact,
-        one FMA), root = g + r*h (one FMA).  Equal to the IEEE root for every finite x >= 2^-96 (checked on the device against
-        all of them: rt_selftest_sqrt runs the same sequence, sqrt_rn_lean in rt_math.hpp)."""
-        a.op("v_mul_f32_e32 %%[root], %s, %%[t0]" % x, "g = x*y")
-        a.op("v_mul_f32_e32 %[t0], 0.5, %[t0]", "h = y/2")
-        a.op("v_fma_f32 %%[t1], -%%[root], %%[root], %s" % x, "r = x - g*g")
-        a.op("v_fma_f32 %[root], %[t1], %[t0], %[root]", "g + r*h")
-
     def root(self, a, need_mask, done_label, tiny_label):
         """Correctly rounded sqrt(disc) into %[root] (== sqrt_rn_lean).  need_mask: the lanes whose root is used."""
-        a.op("v_rsq_f32_e32 %[t0], %[disc]")
-        a.op("v_cmp_lt_f32_e64 %s, |%%[disc]|, %%[tiny]" % self.TINY)
-        a.op("s_and_b64 %s, %s, %s" % (self.M56, self.TINY, need_mask))
-        a.op("s_cbranch_scc1 %s" % tiny_label, "some needed lane below 2^-96 (zero included): scaled path")
-        self.refine(a, "%[disc]")
-        a.label(done_label)
+        asm_gen.root(a, self.lean, "%[disc]", need_mask, done_label, tiny_label)
 
     def tiny(self, a, tiny_label, done_label):
-        a.label(tiny_label)
-        a.op("v_mul_f32_e32 %[t0], 0x5f800000, %[disc]", "root with the 2^64 / 2^-32 scaling for tiny lanes (the scaled operand stays >= 2^-85: its residual is never subnormal)")
-        a.op("v_cndmask_b32_e64 %%[t5], %%[disc], %%[t0], %s" % self.TINY)
-        a.op("v_rsq_f32_e32 %[t0], %[t5]")
-        a.op("v_cmp_eq_f32_e64 %s, 0, %%[t5]" % self.M58, "sqrt(+-0) = +-0 (rsq would make it 0 * inf)")
-        self.refine(a, "%[t5]")
-        a.op("v_cndmask_b32_e64 %%[root], %%[root], %%[t5], %s" % self.M58)
-        a.op("v_mul_f32_e32 %[t0], 0x2f800000, %[root]")
-        a.op("v_cndmask_b32_e64 %%[root], %%[root], %%[t0], %s" % self.TINY)
-        a.op("s_branch %s" % done_label)
+        asm_gen.tiny(a, self.lean, "%[disc]", tiny_label, done_label)
 
     def primary_distance(self, a):
         """vcc (live lanes with disc >= 0) -> vcc = go: t2 >= 0 and d < hit.distance; d left in t4."""
@@ -245,7 +209,7 @@ class F32(Prec):
 
 
 class F64(Prec):
-    name, ctype, stride = "f64", "double", 64
+    ctype, stride = "double", 64
     bank_first, bank_dwords, load_op = (36, 52, 68), 16, "s_load_dwordx16"
     NX = "s85"
     ACT, M54, M56, M58, TINY, EX = sp(86), sp(88), sp(90), sp(92), sp(94), sp(96)
@@ -363,16 +327,36 @@ class F64(Prec):
     inf = "__builtin_huge_val()"
 
 
-class F32F(F32):
+class TwoSidedShadow:
+    """The shadow walk over FNodeS records {w1, w2, cl, R2o | ITEM flag, R2i, R2o_own | END flag, R2i_own, skip_off} (shadow_copy_filt): the
+    record's fields, in the bank the class names as `sbank`, and the outer bound every step starts with."""
+    def s_w1(self, b): return "s%d" % (self.sbank(b) + 0)
+    def s_w2(self, b): return "s%d" % (self.sbank(b) + 1)
+    def s_cl(self, b): return "s%d" % (self.sbank(b) + 2)
+    def s_r2o(self, b): return "s%d" % (self.sbank(b) + 3)
+    def s_r2i(self, b): return "s%d" % (self.sbank(b) + 4)
+    def s_r2o_own(self, b): return "s%d" % (self.sbank(b) + 5)
+    def s_r2i_own(self, b): return "s%d" % (self.sbank(b) + 6)
+    def s_skip(self, b): return "s%d" % (self.sbank(b) + 7)
+
+    def shadow_filter(self, a, c):
+        packed_p2(a, self.sbank(c), "%[p2]")
+        a.op("v_cmp_ngt_f32_e64 vcc, %%[p2], |%s|" % self.s_r2o(c), "not beyond the outer bound (a NaN -- a ray the bounds do not cover -- passes)")
+
+    def shadow_walk(self, name, fused):
+        return shadow_copy_filt(self, name, fused)
+
+
+class F32F(TwoSidedShadow, F32):
     """f32 with the conservative FILTER in front of every test: the walk reads FNode streams (rt_skip.hpp) --
     primary {vx, vy, vz, vv, rr, T, skip_off, tag}, shadow {cx, cy, cz, rr, w1, w2, skip_off, tag}; tag = 0 (BOUND), rr of the
     group's own sphere (fused BOUND), item | bit 31 (ITEM), bits 31 + 30 (END).  A step first asks a bound of the test that is
     proven to hold whenever the reference's test can return a finite distance (primary: fma-chain b' >= T; shadow: squared distance
     of the sphere's centre from the ray in the plane perpendicular to the light <= rr * k1 + K0); only when some live lane passes
     does it form the reference's own discriminant, operation for operation, exactly as the unfiltered loops do."""
-    name = "f32"
     filt = True
     shortcut = True
+    sbank = Prec.bank
 
     def item(self, b):
         return "s%d" % (self.bank(b) + 7)            # the tag word: an ITEM's index | bit 31
@@ -396,19 +380,20 @@ class F32F(F32):
         a.op("v_subrev_f32_e32 %%[q], %s, %%[t0]" % self.fld(c, 3))
         a.op("v_add_f32_e32 %%[disc], %s, %%[q]" % self.fld(c, 4))
 
-    # ---- shadow stream (two-sided bound): {w1, w2, cl, R2o | ITEM flag, R2i, R2o_own | END flag, R2i_own, skip_off}
-    def s_w1(self, b): return "s%d" % (self.bank(b) + 0)
-    def s_w2(self, b): return "s%d" % (self.bank(b) + 1)
-    def s_cl(self, b): return "s%d" % (self.bank(b) + 2)
-    def s_r2o(self, b): return "s%d" % (self.bank(b) + 3)
-    def s_r2i(self, b): return "s%d" % (self.bank(b) + 4)
-    def s_r2o_own(self, b): return "s%d" % (self.bank(b) + 5)
-    def s_r2i_own(self, b): return "s%d" % (self.bank(b) + 6)
-    def s_skip(self, b): return "s%d" % (self.bank(b) + 7)
+    exact_mask_note = "the root's scaled path may have used this mask"
 
-    def shadow_filter(self, a, c):
-        packed_p2(a, self.bank(c), "%[p2]")
-        a.op("v_cmp_ngt_f32_e64 vcc, %%[p2], |%s|" % self.s_r2o(c), "not beyond the outer bound (a NaN -- a ray the bounds do not cover -- passes)")
+    def shadow_exact_terms(self, a, c, n, s, own):
+        """The node's Node<float> record of the exact stream into a bank that is free, and the reference's sixteen operations on it."""
+        tmp = "s" + self.M54[2:].split(":")[0]       # the masks are dead here: the reference's test forms the hit mask anew
+        a.op("s_sub_u32 %s, %s, %d" % (tmp, self.NX, self.stride), "this node's offset")
+        bank = s if own else n
+        if own:
+            a.op("s_waitcnt lgkmcnt(0)", "the skip successor's fetch may still be in flight INTO this bank, and scalar loads land out of order")
+        a.op("s_load_dwordx8 %s, %%[base2], %s" % (sp(self.bank(bank), 8), tmp),
+             "its Node record (the skip bank is free: the group is entered)" if own else
+             "its Node record of the exact stream (the `next` bank is free until the group is entered)")
+        a.op("s_waitcnt lgkmcnt(0)")
+        self.shadow_terms(a, bank, self.own(bank) if own else None)
 
     def kind_test(self, a, c, lab):
         a.op("s_bitcmp1_b32 %s, 31" % self.item(c), "an ITEM or the END node?  (flag bits of the tag word)")
@@ -449,7 +434,7 @@ class F32F(F32):
     shadow_extra_in = ', ' + QQ_IN + ', [ol] "v"(ol), [a0] "s"(a0), [k1] "s"(k1), [kc] "v"(kc), [base2] "s"(exact)'
     shadow_extra_out = ', [p2] "=&v"(p2), [av] "=&v"(av), [inn] "=&v"(inn)'
     shadow_extra_decl = "\n    float p2, av, inn;" + QQ_DECL
-    shadow_vclobbers = PACKED_CLOBBERS
+    shadow_vclobbers = TT
     # the shadow loops' temporaries t0 / t1 ARE the halves of TT (two registers fewer at the statement: the lane-cooperative flavour of the
     # kernel sits at the 64-register limit of 8 waves per SIMD)
     # ... and b*b - vv / the discriminant of the reference's arithmetic (shadow_exact) take the registers of v.y / v.x, dead by then
@@ -465,9 +450,7 @@ class F64F(F64):
     fetched (same index, twice the offset) and the reference's f64 test run, instruction for instruction as in F64.  Positions (NX, resume,
     skip_off) are byte offsets into the FNODE stream.  T: rt_skip.hpp primary_filter_threshold64 -- a finite f64 distance needs
     b >= sqrt(vv - rr) (1 - 1e-15), and b' is within 5.3 eps32 sqrt(vv) of b (two f32 roundings of the operands, three of the chain)."""
-    name = "f64"
     filt = True
-    primary_only = True
     stride = 32
     fbank_first = (36, 44, 52)                       # three filter banks of 8; the exact record lives in s[60:75]
     EXACT = 60
@@ -477,8 +460,8 @@ class F64F(F64):
     NX = "s77"
     ACT, M54, M56, M58, TINY, EX = sp(78), sp(80), sp(82), sp(84), sp(86), sp(88)
     clobber_lo, clobber_hi = 36, 89
-    fn_suffix = ""
-    reserved = (88, 89)                              # k_render_skip_f64: amdgpu_num_sgpr(96) + amdgpu_waves_per_eu(7) leave the compiler s[0:87]
+    flavour = "f64"
+    reserved = UNDECLARED[flavour][1]                # s[88:89]: not in the clobber lists (clobbers)
     load_op = "s_load_dwordx8"
 
     def fbank(self, b):
@@ -571,7 +554,7 @@ class F64F(F64):
         a.op("v_cmp_le_f32_e64 %s, %s, %%[tf1]" % (self.M56, self.t_own(c)), "b' >= T_own: the own sphere may be hit")
         a.op("s_and_b64 %s, %s, vcc" % (self.M56, self.M56))
         a.op("s_cbranch_scc1 %s" % lab("exact"))
-        enter_group(a, self, c, n)
+        enter_group(a, self, n)
         sleep_culled(a, self, c)
         a.op("s_branch %s" % lab("next"), "every candidate enters, nobody can hit the own sphere: no exact record needed")
         a.label(lab("exact"))
@@ -588,7 +571,7 @@ class F64F(F64):
     primary_extra_in = ', [dxf] "v"(dxf), [dyf] "v"(dyf), [dzf] "v"(dzf), [base2] "s"(exact), [kk] "s"(kk)'
 
 
-class F64FS(F64F):
+class F64FS(TwoSidedShadow, F64F):
     """The SHADOW walk of f64 scenes behind the f32 walk's TWO-SIDED bound (round 4): the walk reads FNodeS records {w1, w2, cl, R2o | ITEM /
     END flag, R2i, R2o_own | END flag, R2i_own, skip_off} -- the centre in the plane perpendicular to the light and along it, formed in double
     and rounded once, and the f32 walk's bounds with rr rounded up (outer) / down (inner): their margins cover an f32 reference's roundings,
@@ -596,37 +579,19 @@ class F64FS(F64F):
     one (and in front) a hit, behind the origin a miss; only a lane between the bounds fetches the node's Node<double> record and runs the
     reference's sixteen f64 operations (and the f64 root where b < 0) for every lane.  Counting launches hold every verdict against the
     f64 test (rt_skip.hpp, shadow_filter_verdict)."""
-    primary_only = False
-
-    def item(self, b):
-        return "s%d" % (self.EXACT + 10)             # the exact record's item word
-
-    def skip(self, b):
-        return "s%d" % (self.fbank(b) + 7)           # FNodeS::skip_off
-
-    def s_skip(self, b):
-        return self.skip(b)
-
-    def kind_test(self, a, c, lab):
-        F64.kind_test(self, a, c, lab)
-
-    # FNodeS: {w1, w2, cl, R2o | ITEM flag, R2i, R2o_own | END flag, R2i_own, skip_off}
-    def s_cl(self, b): return "s%d" % (self.fbank(b) + 2)
-    def s_r2o(self, b): return "s%d" % (self.fbank(b) + 3)
-    def s_r2i(self, b): return "s%d" % (self.fbank(b) + 4)
-    def s_r2o_own(self, b): return "s%d" % (self.fbank(b) + 5)
-    def s_r2i_own(self, b): return "s%d" % (self.fbank(b) + 6)
+    sbank = F64F.fbank
+    exact_mask_note = "the exact path used this mask"
     ftmp = "%[tf0]"
 
-    def shadow_filter(self, a, c):
-        packed_p2(a, self.fbank(c), "%[p2]")
-        a.op("v_cmp_ngt_f32_e64 vcc, %%[p2], |%s|" % self.s_r2o(c), "not beyond the outer bound (a NaN -- a ray the bounds do not cover -- passes)")
+    def shadow_exact_terms(self, a, c, n, s, own):
+        """The node's Node<double> record (shadow_terms fetches it) and the reference's sixteen f64 operations; own: the group's own sphere, same
+        centre, its rr."""
+        self.shadow_terms(a, c)
+        if own:
+            self.fused_disc(a, c)
 
     def shadow_terms(self, a, c):
-        tmp = self.TMP
-        a.op("s_sub_u32 %s, %s, %d" % (tmp, self.NX, self.stride), "this node's offset in the filter stream ...")
-        a.op("s_lshl_b32 %s, %s, 1" % (tmp, tmp), "... and in the Node<double> stream")
-        a.op("s_load_dwordx16 %s, %%[base2], %s" % (sp(self.EXACT, 16), tmp), "its exact record")
+        self.fetch_exact(a)
         a.op("s_waitcnt lgkmcnt(0)")
         F64.shadow_terms(self, a, c)
 
@@ -636,13 +601,14 @@ class F64FS(F64F):
     shadow_out = F64.shadow_out + ', [p2] "=&v"(p2), [av] "=&v"(av)'
     shadow_subst = (("%[tf0]", "v%d" % TT[0]), ("%[inn]", "v%d" % TT[1]))
     shadow_extra_in = ', ' + QQ_IN + ', [ol] "v"(ol), [a0] "s"(a0), [k1] "s"(k1), [kc] "v"(kc), [base2] "s"(exact)'
-    shadow_vclobbers = PACKED_CLOBBERS
+    shadow_vclobbers = TT
 
 
-class F64F_LO(F64F):
+class LowWindow:
     """Round 6: the same loops in s[20:73] -- for k_render_skip_fast64_coop (rt_skip_fast64.hpp), which keeps so little across the loops that
     s[0:19] are enough for it: .sgpr_count 80, EIGHT waves per SIMD where every other f64 kernel runs seven (MI355X_MICROARCH.md,
-    "Residency").  Nothing is reserved under amdgpu_num_sgpr(82): every register of the window is declared."""
+    "Residency").  Under amdgpu_num_sgpr(82) every register of the window is declared but s32, which the compiler reserves in every kernel
+    (the stack pointer of a kernel that has no stack): the clobber lists leave it out like F64F's s[88:89]."""
     fbank_first = (20, 28, 36)
     EXACT = 44
     TMP = "s60"
@@ -650,56 +616,33 @@ class F64F_LO(F64F):
     ACT, M54, M56, M58, TINY, EX = sp(62), sp(64), sp(66), sp(68), sp(70), sp(72)
     clobber_lo, clobber_hi = 20, 73
     fn_suffix = "_lo"
-    reserved = (32,)                                 # (the stack pointer of a kernel that has no stack: reserved in every kernel)
-    mark_name = "f64-lo"
-    lreg = "s"
+    flavour = "f64-lo"
+    reserved = UNDECLARED[flavour][1]
     # the kernel has s[0:19] for itself AND for the statements' scalar operands: the constants travel in vector registers here
     extra_in = F64.extra_in.replace('[scalec] "s"(scalec)', '[scalec] "v"(scalec)')
 
 
-class F64FS_LO(F64FS):
-    fbank_first = F64F_LO.fbank_first
-    EXACT = F64F_LO.EXACT
-    TMP, NX = F64F_LO.TMP, F64F_LO.NX
-    ACT, M54, M56, M58, TINY, EX = F64F_LO.ACT, F64F_LO.M54, F64F_LO.M56, F64F_LO.M58, F64F_LO.TINY, F64F_LO.EX
-    clobber_lo, clobber_hi = F64F_LO.clobber_lo, F64F_LO.clobber_hi
-    fn_suffix = "_lo"
-    reserved = (32,)
-    mark_name = "f64-lo"
-    extra_in = F64F_LO.extra_in
+class F64F_LO(LowWindow, F64F):
+    pass
+
+
+class F64FS_LO(LowWindow, F64FS):
     shadow_extra_in = F64FS.shadow_extra_in.replace('[a0] "s"(a0)', '[a0] "v"(a0)').replace('[k1] "s"(k1)', '[k1] "v"(k1)')
 
 
-def top_of(name):
-    return ".Lrt_%s_top_%%=" % name
+F64F.shadow_companion, F64F_LO.shadow_companion = F64FS, F64FS_LO
 
 
-def emit_skip(a, P, name, c, lab, skip_reg=None):
-    """`skip` transition: the successor is the node behind the subtree (an ITEM's own successor)."""
-    a.label(lab("skip"))
-    a.op("s_add_u32 %s, %s, %d" % (P.NX, skip_reg or P.skip(c), P.stride), "jump over the subtree")
-    a.op("s_waitcnt lgkmcnt(0)")
-    nxt = SKIP_COPY[name]
-    if LAYOUT.index(nxt) != LAYOUT.index(name) + 1:                # A -> C and C -> B fall through
-        a.op("s_branch %s" % top_of(nxt))
+def node_skip(P, c, walk):
+    return P.s_skip(c) if (P.filt and walk == "shadow") else P.skip(c)
 
 
-def emit_next(a, P, name):
-    a.op("s_add_u32 %s, %s, %d" % (P.NX, P.NX, P.stride))
-    a.op("s_waitcnt lgkmcnt(0)")
-    a.op("s_branch %s" % top_of(NEXT_COPY[name]))
-
-
-def node_skip(P, c, terms):
-    return P.s_skip(c) if (P.filt and terms == P.shadow_terms) else P.skip(c)
-
-
-def step_top(a, P, c, n, s, terms):
-    """The part of a step every node shares: fetch the likely successor, form the live mask and the discriminant."""
+def step_top(a, P, c, n, s, walk):
+    """The part of a step every node shares: fetch the likely successor, form the live mask and the discriminant.  walk: "primary" / "shadow"."""
     # Only `skip` is fetched ahead: three of four BOUND tests end there, and an ITEM's `skip` IS its successor.  The first
     # child of a group is fetched when somebody enters (enter_group): fetched at the top of every BOUND step it doubled the
     # scalar-cache misses (most of those lines are never walked), which cost more than the late fetch on the entered quarter.
-    P.load(a, s, node_skip(P, c, terms), "the likely successor, while this node is processed")
+    P.load(a, s, node_skip(P, c, walk), "the likely successor, while this node is processed")
     if not lazy_wake(P):
         a.op("v_cmp_gt_u32_e64 %s, %s, %%[resume]" % (P.ACT, P.NX), "active = i >= resume  (NX = i + stride)")
     if P.filt:
@@ -707,20 +650,21 @@ def step_top(a, P, c, n, s, terms):
         # missed an enclosing bound and passes the filter of a node inside it in 0.2 % of the quiet steps (1080p, a CPU replay), so the
         # commonest step loses its compare with `resume` and the s_and -- two of its ten instructions.  Lanes without a ray, and shadow
         # lanes that have retired, carry a ray no bound lets through (a NaN direction / an in-plane origin at infinity: rt_skip.hpp).
-        (P.primary_filter if terms == P.primary_terms else P.shadow_filter)(a, c)
-        for _ in range(int(os.environ.get("RT_GEN_PAD_VALU", "0")) if P.ctype == "float" else 0):   # design-time probe: what one more instruction per step costs
+        (P.primary_filter if walk == "primary" else P.shadow_filter)(a, c)
+        pad_valu, pad_salu = P.pad if P.ctype == "float" else (0, 0)
+        for _ in range(pad_valu):                    # design-time probe (main): what one more instruction per step costs
             a.op("v_max_f32_e32 %[t2], %[t2], %[t2]")
-        for _ in range(int(os.environ.get("RT_GEN_PAD_SALU", "0")) if P.ctype == "float" else 0):
+        for _ in range(pad_salu):
             a.op("s_mov_b32 %s, %s" % (P.TINY.split(":")[0].replace("s[", "s"), P.NX))
         if not lazy_wake(P):
             a.op("s_and_b64 vcc, vcc, %s" % P.ACT, "live lanes the bound cannot rule out")
         return
-    terms(a, c)
+    (P.primary_terms if walk == "primary" else P.shadow_terms)(a, c)
     P.cand_cmp(a)
     a.op("s_and_b64 vcc, vcc, %s" % P.ACT, "live lanes whose line meets the sphere")
 
 
-def enter_group(a, P, c, n):
+def enter_group(a, P, n):
     P.load(a, n, P.NX, "somebody enters: fetch the group's first child")
 
 
@@ -728,10 +672,6 @@ def sleep_culled(a, P, c):
     a.op("s_andn2_b64 exec, %s, vcc" % P.ACT, "lanes that may not enter sleep until `skip`")
     a.op("v_mov_b32_e32 %%[resume], %s" % P.skip(c))
     a.op("s_mov_b64 exec, %s" % P.EX)
-
-
-def kind_test(a, P, c, lab):
-    P.kind_test(a, c, lab)
 
 
 def lazy_wake(P):
@@ -750,11 +690,11 @@ def hit_entry(a, P, shadow=False):
         a.op("s_and_b64 vcc, vcc, %s" % P.ACT, "live lanes inside the outer bound")
 
 
-def exact_after_filter(a, P, c, lab, terms):
+def exact_after_filter(a, P, c, lab, walk):
     """Filtered loops: some lane passed the bound -- now the reference's own discriminant, for every lane."""
     if not P.filt:
         return
-    (P.primary_terms_after_filter if terms == P.primary_terms else terms)(a, c)
+    (P.primary_terms_after_filter if walk == "primary" else P.shadow_terms)(a, c)
     P.cand_cmp(a)
     a.op("s_and_b64 vcc, vcc, %s" % P.ACT, "live lanes whose line meets the sphere")
     a.op("s_cbranch_vccz %s" % lab("skip"), "the bound let it through, the test does not: nobody can hit the node")
@@ -762,19 +702,19 @@ def exact_after_filter(a, P, c, lab, terms):
 
 def primary_copy(P, name, fused):
     c, n, s = COPIES[name]
-    lab = lambda x: ".Lrt_%s_%s_%%=" % (name, x)
+    lab = P.rot.lab(name)
     m, k = Asm(), Asm()
     m.label(lab("top"))
-    step_top(m, P, c, n, s, P.primary_terms)
+    step_top(m, P, c, n, s, "primary")
     m.op("s_cbranch_vccnz %s" % lab("hit"))
-    emit_skip(m, P, name, c, lab)          # nobody can hit the node: a BOUND is jumped over, an ITEM changes nothing
+    P.rot.emit_skip(m, name, P.skip(c))    # nobody can hit the node: a BOUND is jumped over, an ITEM changes nothing
     # ---------------- somebody's line meets the sphere ----------------
     k.label(lab("hit"))
     hit_entry(k, P)
     if P.sure_enter and P.filt:
         P.sure_enter_path(k, c, n, name, lab)
-    exact_after_filter(k, P, c, lab, P.primary_terms)
-    kind_test(k, P, c, lab)
+    exact_after_filter(k, P, c, lab, "primary")
+    P.kind_test(k, c, lab)
     # BOUND (group.rs:73)
     if P.shortcut:
         P.bound_shortcut(k, c, lab)
@@ -784,7 +724,7 @@ def primary_copy(P, name, fused):
     if P.shortcut:
         k.label(lab("bdecided"))
     k.op("s_cbranch_vccz %s" % lab("skip"), "nobody enters (the lanes that culled it are awake again at `skip`)")
-    enter_group(k, P, c, n)
+    enter_group(k, P, n)
     sleep_culled(k, P, c)
     if fused:
         # the group's own sphere, for the lanes that entered: same centre, so v, b and b*b - vv are the values just formed
@@ -797,7 +737,7 @@ def primary_copy(P, name, fused):
         P.primary_distance(k)
         P.own_item_update(k, c)
     k.label(lab("next"))
-    emit_next(k, P, name)
+    P.rot.emit_next(k, name)
     P.tiny(k, lab("btiny"), lab("brooted"))
     if fused:
         P.tiny(k, lab("ftiny"), lab("frooted"))
@@ -827,19 +767,19 @@ def shadow_decide(a, P, lab, tag):
 
 def shadow_copy(P, name, fused):
     c, n, s = COPIES[name]
-    lab = lambda x: ".Lrt_%s_%s_%%=" % (name, x)
+    lab = P.rot.lab(name)
     m, k = Asm(), Asm()
     m.label(lab("top"))
-    step_top(m, P, c, n, s, P.shadow_terms)
+    step_top(m, P, c, n, s, "shadow")
     m.op("s_cbranch_vccnz %s" % lab("hit"))
-    emit_skip(m, P, name, c, lab)
+    P.rot.emit_skip(m, name, P.skip(c))
     k.label(lab("hit"))
-    exact_after_filter(k, P, c, lab, P.shadow_terms)
-    kind_test(k, P, c, lab)
+    exact_after_filter(k, P, c, lab, "shadow")
+    P.kind_test(k, c, lab)
     # BOUND: hit.distance is INF, so a bound culls iff the ray misses it
     shadow_decide(k, P, lab, "b")
     k.op("s_cbranch_vccz %s" % lab("skip"))
-    enter_group(k, P, c, n)
+    enter_group(k, P, n)
     sleep_culled(k, P, c)
     if fused:
         k.op("s_mov_b64 %s, vcc" % P.ACT, "the lanes that are live at the next node")
@@ -851,7 +791,7 @@ def shadow_copy(P, name, fused):
         k.op("s_cbranch_vccz %s" % lab("next"))
         k.op("s_branch .Lrt_fin_%=", "any hit ends those rays; hand them to the caller")
     k.label(lab("next"))
-    emit_next(k, P, name)
+    P.rot.emit_next(k, name)
     P.tiny(k, lab("btiny"), lab("brooted"))
     if fused:
         P.tiny(k, lab("ftiny"), lab("frooted"))
@@ -865,29 +805,13 @@ def shadow_copy(P, name, fused):
     return m, k
 
 
-def shadow_exact(k, P, src, lab, tag, rr_reg):
-    """The reference's own test (primitive.rs:55-72) for every lane, node terms from bank `src` (a Node<float> record of the exact stream):
-    vcc = live lanes (P.ACT) whose ray hits the sphere with squared radius rr_reg."""
-    a = k
-    a.op("v_sub_f32_e32 %%[vx], %s, %%[ox]" % P.fld(src, 0), "v = centre - origin   primitive.rs:56")
-    a.op("v_sub_f32_e32 %%[vy], %s, %%[oy]" % P.fld(src, 1))
-    a.op("v_sub_f32_e32 %%[vz], %s, %%[oz]" % P.fld(src, 2))
-    a.op("v_mul_f32_e32 %[t0], %[lx], %[vx]")
-    a.op("v_mul_f32_e32 %[t1], %[ly], %[vy]")
-    a.op("v_mul_f32_e32 %[t2], %[lz], %[vz]")
-    a.op("v_add_f32_e32 %[t0], %[t0], %[t1]")
-    a.op("v_add_f32_e32 %[b], %[t0], %[t2]", "b = dot(v, dir)   primitive.rs:57")
-    a.op("v_mul_f32_e32 %[t3], %[vx], %[vx]")
-    a.op("v_mul_f32_e32 %[t4], %[vy], %[vy]")
-    a.op("v_mul_f32_e32 %[t5], %[vz], %[vz]")
-    a.op("v_add_f32_e32 %[t3], %[t3], %[t4]")
-    a.op("v_add_f32_e32 %[t3], %[t3], %[t5]", "dot(v, v)")
-    a.op("v_mul_f32_e32 %[t0], %[b], %[b]")
-    a.op("v_sub_f32_e32 %[q], %[t0], %[t3]")
-    a.op("v_add_f32_e32 %%[disc], %s, %%[q]" % rr_reg, "disc = (b*b - vv) + rr   primitive.rs:58")
-    P.cand_cmp(a)
-    a.op("s_and_b64 vcc, vcc, %s" % P.ACT)
-    shadow_decide(a, P, lab, tag)
+def shadow_exact(k, P, c, n, s, lab, tag, own):
+    """The reference's own test (primitive.rs:55-72) for every lane, on the node's record of the exact stream (P.shadow_exact_terms fetches
+    it): vcc = live lanes (P.ACT) whose ray hits the sphere (own: the group's own sphere, same centre, its rr)."""
+    P.shadow_exact_terms(k, c, n, s, own)
+    P.cand_cmp(k)
+    k.op("s_and_b64 vcc, vcc, %s" % P.ACT)
+    shadow_decide(k, P, lab, tag)
 
 
 def shadow_two_sided(a, P, r2i, exact_label, tag):
@@ -916,14 +840,14 @@ def shadow_second_chance(k, P, r2o, exact2, none_label, some_label):
 
 
 def shadow_copy_filt(P, name, fused):
-    """Two-sided flavour of shadow_copy (f32 filtered streams)."""
+    """Two-sided flavour of shadow_copy (TwoSidedShadow: F32F, and F64FS with the same f32 bound in front and the f64 arithmetic behind it)."""
     c, n, s = COPIES[name]
-    lab = lambda x: ".Lrt_%s_%s_%%=" % (name, x)
+    lab = P.rot.lab(name)
     m, k = Asm(), Asm()
     m.label(lab("top"))
-    step_top(m, P, c, n, s, P.shadow_terms)
+    step_top(m, P, c, n, s, "shadow")
     m.op("s_cbranch_vccnz %s" % lab("hit"))
-    emit_skip(m, P, name, c, lab, P.s_skip(c))
+    P.rot.emit_skip(m, name, P.s_skip(c))
     # ---------------- some live lane is inside the outer bound ----------------
     k.label(lab("hit"))
     if lazy_wake(P):
@@ -950,105 +874,29 @@ def shadow_copy_filt(P, name, fused):
         k.op("s_branch .Lrt_fin_%=", "any hit ends those rays; hand them to the caller (it starts again behind this node)")
     k.label(lab("next"))
     P.load(k, n, P.NX, "somebody entered: fetch the group's first child")
-    emit_next(k, P, name)
+    P.rot.emit_next(k, name)
     # ITEM or END
     k.label(lab("flagged"))
     k.op("s_bitcmp1_b32 %s, 31" % P.s_r2o_own(c))
     k.op("s_cbranch_scc1 .Lrt_exit_%=", "END: every lane is awake here and hits it")
     k.op("s_branch .Lrt_fin_%=")
-    # ---- the reference's test, for the steps whose lanes the bounds cannot settle: terms from the exact stream
+    # ---- lanes between the bounds: first the behind-the-origin test, then the reference's arithmetic on the node's record of the exact stream
     k.label(lab("exact"))
     shadow_second_chance(k, P, P.s_r2o(c), lab("exact2"), lab("skip"), lab("decided"))
     k.label(lab("exact2"))
-    tmp = "s" + P.M54[2:].split(":")[0]            # the masks are dead here: the reference's test forms the hit mask anew
-    k.op("s_sub_u32 %s, %s, %d" % (tmp, P.NX, P.stride), "this node's offset")
-    k.op("s_load_dwordx8 %s, %%[base2], %s" % (sp(P.bank(n), 8), tmp), "its Node record of the exact stream (the `next` bank is free until the group is entered)")
-    k.op("s_waitcnt lgkmcnt(0)")
-    shadow_exact(k, P, n, lab, "x", P.fld(n, 3))
+    shadow_exact(k, P, c, n, s, lab, "x", False)
     k.op("s_cbranch_vccz %s" % lab("skip"))
-    k.op("v_cmp_le_f32_e64 %s, %%[a0], %%[av]" % P.M58, "(the root's scaled path may have used this mask: form `b >= 0 by a margin` again)")
+    k.op("v_cmp_le_f32_e64 %s, %%[a0], %%[av]" % P.M58, "(%s: form `b >= 0 by a margin` again)" % P.exact_mask_note)
     k.op("s_branch %s" % lab("decided"))
     P.tiny(k, lab("xtiny"), lab("xrooted"))
     if fused:
         k.label(lab("exactown"))
         shadow_second_chance(k, P, P.s_r2o_own(c), lab("exactown2"), lab("next"), lab("owndecided"))
         k.label(lab("exactown2"))
-        k.op("s_sub_u32 %s, %s, %d" % (tmp, P.NX, P.stride), "this node's offset")
-        k.op("s_waitcnt lgkmcnt(0)", "the skip successor's fetch may still be in flight INTO this bank, and scalar loads land out of order")
-        k.op("s_load_dwordx8 %s, %%[base2], %s" % (sp(P.bank(s), 8), tmp), "its Node record (the skip bank is free: the group is entered)")
-        k.op("s_waitcnt lgkmcnt(0)")
-        shadow_exact(k, P, s, lab, "y", P.own(s))
+        shadow_exact(k, P, c, n, s, lab, "y", True)
         k.op("s_cbranch_vccz %s" % lab("next"))
         k.op("s_branch %s" % lab("owndecided"))
         P.tiny(k, lab("ytiny"), lab("yrooted"))
-    return m, k
-
-
-def shadow_exact64(k, P, c, lab, tag, own):
-    """F64FS: the reference's own test for every lane -- the node's Node<double> record (fetched here), the sixteen f64 operations, the root where
-    b < 0.  vcc = live lanes (P.ACT) whose ray hits the sphere (own: the group's own sphere, same centre, its rr)."""
-    P.shadow_terms(k, c)
-    if own:
-        P.fused_disc(k, c)
-    P.cand_cmp(k)
-    k.op("s_and_b64 vcc, vcc, %s" % P.ACT)
-    shadow_decide(k, P, lab, tag)
-
-
-def shadow_copy_filt64(P, name, fused):
-    """shadow_copy_filt for f64 scenes (F64FS): the same two-sided f32 bound in front, the f64 arithmetic behind it."""
-    c, n, s = COPIES[name]
-    lab = lambda x: ".Lrt_%s_%s_%%=" % (name, x)
-    m, k = Asm(), Asm()
-    m.label(lab("top"))
-    step_top(m, P, c, n, s, P.shadow_terms)
-    m.op("s_cbranch_vccnz %s" % lab("hit"))
-    emit_skip(m, P, name, c, lab, P.s_skip(c))
-    # ---------------- some live lane is inside the outer bound ----------------
-    k.label(lab("hit"))
-    if lazy_wake(P):
-        hit_entry(k, P, shadow=True)
-        k.op("s_cbranch_vccz %s" % lab("skip"), "only lanes that sleep: nobody can hit the node")
-    k.op("v_sub_f32_e32 %%[av], %s, %%[ol]" % P.s_cl(c), "a ~ b = dot(centre - origin, dir)")
-    k.op("v_cmp_le_f32_e64 %s, %%[a0], %%[av]" % P.M58, "b >= 0, by a margin")
-    k.op("v_fma_f32 %[inn], %[av], %[av], %[p2]", "~ |centre - origin|^2")
-    shadow_two_sided(k, P, P.s_r2i(c), lab("exact"), "")
-    k.label(lab("decided"))
-    k.op("s_bitcmp1_b32 %s, 31" % P.s_r2o(c), "an ITEM or the END node?  (sign bit of the outer bound)")
-    k.op("s_cbranch_scc1 %s" % lab("flagged"))
-    k.op("s_andn2_b64 exec, %s, vcc" % P.ACT, "lanes that may not enter sleep until `skip`")
-    k.op("v_mov_b32_e32 %%[resume], %s" % P.s_skip(c))
-    k.op("s_mov_b64 exec, %s" % P.EX)
-    if fused:
-        k.op("s_mov_b64 %s, vcc" % P.ACT, "the lanes that are live at the next node")
-        k.op("v_cmp_ngt_f32_e64 vcc, %%[p2], |%s|" % P.s_r2o_own(c), "the group's own sphere: same centre, its own bounds")
-        k.op("s_and_b64 vcc, vcc, %s" % P.ACT)
-        k.op("s_cbranch_vccz %s" % lab("next"))
-        shadow_two_sided(k, P, P.s_r2i_own(c), lab("exactown"), "own")
-        k.label(lab("owndecided"))
-        k.op("s_branch .Lrt_fin_%=", "any hit ends those rays; hand them to the caller (it starts again behind this node)")
-    k.label(lab("next"))
-    P.load(k, n, P.NX, "somebody entered: fetch the group's first child")
-    emit_next(k, P, name)
-    k.label(lab("flagged"))
-    k.op("s_bitcmp1_b32 %s, 31" % P.s_r2o_own(c))
-    k.op("s_cbranch_scc1 .Lrt_exit_%=", "END: every lane is awake here and hits it")
-    k.op("s_branch .Lrt_fin_%=")
-    # ---- lanes between the bounds: first the behind-the-origin test, then the reference's f64 arithmetic
-    k.label(lab("exact"))
-    shadow_second_chance(k, P, P.s_r2o(c), lab("exact2"), lab("skip"), lab("decided"))
-    k.label(lab("exact2"))
-    shadow_exact64(k, P, c, lab, "x", False)
-    k.op("s_cbranch_vccz %s" % lab("skip"))
-    k.op("v_cmp_le_f32_e64 %s, %%[a0], %%[av]" % P.M58, "(the exact path used this mask: form `b >= 0 by a margin` again)")
-    k.op("s_branch %s" % lab("decided"))
-    if fused:
-        k.label(lab("exactown"))
-        shadow_second_chance(k, P, P.s_r2o_own(c), lab("exactown2"), lab("next"), lab("owndecided"))
-        k.label(lab("exactown2"))
-        shadow_exact64(k, P, c, lab, "y", True)
-        k.op("s_cbranch_vccz %s" % lab("next"))
-        k.op("s_branch %s" % lab("owndecided"))
     return m, k
 
 
@@ -1142,51 +990,38 @@ __device__ __forceinline__ unsigned %(name)s(const void *nodes, unsigned n_bytes
 
 
 def clobbers(P, vregs=()):
-    # Registers the compiler RESERVES in the one kernel a flavour's loops are built into are not named: it never allocates them, so there is
-    # nothing to tell it -- and naming them is what `-Winline-asm` ("clobber list contains reserved registers") objects to.  That the loops
-    # may use them rests on the kernel's .sgpr_count (the hardware's allocation covers them) and on no compiler-generated instruction
-    # touching them: tests/test_kernel_resources.py checks both on the generated assembly (tools/check_reserved_registers.py).
-    regs = ['"s%d"' % r for r in range(P.clobber_lo, P.clobber_hi + 1) if r not in getattr(P, "reserved", ())] + list(vregs)
-    lines, cur = [], '"memory", "vcc", "scc"'
-    for r in regs:
-        if len(cur) + len(r) + 2 > 118:
-            lines.append(cur + ",")
-            cur = "          " + r
-        else:
-            cur += ", " + r
-    lines.append(cur)
-    return "\n".join(lines)
+    # Registers the compiler RESERVES in the one kernel a flavour's loops are built into (P.reserved) are not named: it never allocates them, and
+    # naming them is what `-Winline-asm` objects to.  What that rests on, and what checks it, stands once beside asm_gen.UNDECLARED.
+    return clobber_list([r for r in range(P.clobber_lo, P.clobber_hi + 1) if r not in P.reserved], vregs)
 
 
-def assemble(a, P, copy_fn, fused):
-    mains, colds = {}, {}
-    for name in "ABC":
-        mains[name], colds[name] = copy_fn(P, name, fused)
-    for name in LAYOUT:
-        a.extend(mains[name])
-    for name in "ABC":
-        a.extend(colds[name])
+def loop_start(P):
+    """(what tools/check_reserved_registers.py finds a flavour's statements by in the compiler's assembly output)"""
+    a = Asm()
+    if P.flavour:
+        a.op(loops_marker(P.flavour))
+    return a
 
 
 def primary(P, fused):
-    a = Asm()
+    a = loop_start(P)
     a.op("s_mov_b32 %s, %d" % (P.NX, P.stride))
     a.op("s_mov_b64 %s, exec" % P.EX)
     P.load(a, 0, "0x0")
     a.op("s_waitcnt lgkmcnt(0)")
-    assemble(a, P, primary_copy, fused)
+    P.rot.assemble(a, lambda name: primary_copy(P, name, fused))
     a.label(".Lrt_exit_%=")
     a.op("s_waitcnt lgkmcnt(0)")
     return a.render()
 
 
 def shadow(P, fused):
-    a = Asm()
+    a = loop_start(P)
     a.op("s_add_u32 %s, %%[start], %d" % (P.NX, P.stride))
     a.op("s_mov_b64 %s, exec" % P.EX)
     P.load(a, 0, "%[start]")
     a.op("s_waitcnt lgkmcnt(0)")
-    assemble(a, P, shadow_copy_filt64 if isinstance(P, F64FS) else shadow_copy_filt if P.filt else shadow_copy, fused)
+    P.rot.assemble(a, lambda name: P.shadow_walk(name, fused))
     a.label(".Lrt_fin_%=")
     a.op("v_cndmask_b32_e64 %[fin], 0, 1, vcc", "the lanes whose ray hit the ITEM (or the group's own sphere) of the current node")
     a.op("s_sub_u32 %%[stop], %s, %d" % (P.NX, P.stride), "its position")
@@ -1202,29 +1037,24 @@ def shadow(P, fused):
 
 
 def main():
+    # design-time probe: n idle vector / scalar instructions in every step of the f32 filtered walks (tools/README.md; the committed header is
+    # the one generated without them)
+    pad = (int(os.environ.get("RT_GEN_PAD_VALU", "0")), int(os.environ.get("RT_GEN_PAD_SALU", "0")))
     text = HEADER
-    for P in (F32(), F64(), F32F(), F64F(), F64F_LO()):
+    for flavour in (F32, F64, F32F, F64F, F64F_LO):
+        P = flavour(pad)
+        S = P.shadow_companion(pad) if P.shadow_companion else P
         for fused in (False, True):
-            sfx = ("_filt" if P.filt else "") + getattr(P, "fn_suffix", "") + ("_fused" if fused else "")
-            common = {"ctype": P.ctype, "stride": P.stride, "inf": P.inf, "extra_in": P.extra_in, "clobbers": clobbers(P), "lreg": getattr(P, "lreg", "s"),
-                      "shadow_extra_in": P.shadow_extra_in, "shadow_extra_out": P.shadow_extra_out, "shadow_extra_decl": P.shadow_extra_decl,
-                      "shadow_extra_args": ", float q1, float q2, float ol, float a0, float k1, float kc, const void *exact" if (P.filt and not P.primary_only) else "",
-                      "primary_extra_args": P.primary_extra_args, "primary_extra_in": P.primary_extra_in}
-            # (what tools/check_reserved_registers.py finds a flavour's statements by in the compiler's assembly output)
-            mark = '        "\\t; rt-loops %s: undeclared s[%d:%d]\\n"\n' % (getattr(P, "mark_name", P.name), P.reserved[0], P.reserved[-1]) if getattr(P, "reserved", ()) else ""
-            text += PRIMARY_FN % dict(common, name="skip_primary_rot" + sfx, body=mark + primary(P, fused), decl=P.primary_decl, out=P.primary_out)
-            if not P.primary_only:
-                text += SHADOW_FN % dict(common, name="skip_shadow_rot" + sfx, body=shadow(P, fused), decl=P.shadow_decl, out=P.shadow_out,
-                                         clobbers=clobbers(P, P.shadow_vclobbers))
-            elif isinstance(P, F64F):
-                S = F64FS_LO() if isinstance(P, F64F_LO) else F64FS()
-                sc = dict(common, shadow_extra_in=S.shadow_extra_in, shadow_extra_out="", shadow_extra_decl="", clobbers=clobbers(S, S.shadow_vclobbers),
-                          shadow_extra_args=", float q1, float q2, float ol, float a0, float k1, float kc, const void *exact")
-                text += SHADOW_FN % dict(sc, name="skip_shadow_rot" + sfx, body=mark + shadow(S, fused), decl=S.shadow_decl, out=S.shadow_out)
+            sfx = ("_filt" if P.filt else "") + P.fn_suffix + ("_fused" if fused else "")
+            text += PRIMARY_FN % {"name": "skip_primary_rot" + sfx, "ctype": P.ctype, "stride": P.stride, "inf": P.inf, "decl": P.primary_decl,
+                                  "body": primary(P, fused), "out": P.primary_out, "extra_in": P.extra_in, "clobbers": clobbers(P),
+                                  "primary_extra_args": P.primary_extra_args, "primary_extra_in": P.primary_extra_in}
+            text += SHADOW_FN % {"name": "skip_shadow_rot" + sfx, "ctype": S.ctype, "decl": S.shadow_decl, "body": shadow(S, fused), "out": S.shadow_out,
+                                 "extra_in": S.extra_in, "lreg": S.lreg, "clobbers": clobbers(S, S.shadow_vclobbers),
+                                 "shadow_extra_args": FILT_ARGS if S.filt else "", "shadow_extra_in": S.shadow_extra_in,
+                                 "shadow_extra_out": S.shadow_extra_out, "shadow_extra_decl": S.shadow_extra_decl}
     text += "}  // namespace rt\n"
-    with open(OUT, "w") as f:
-        f.write(text)
-    print("wrote", OUT, "(%d lines)" % text.count("\n"))
+    write_header(OUT, text)
 
 
 if __name__ == "__main__":
