@@ -47,7 +47,7 @@ SYMBOLS = ("rt_abi_version", "rt_build_hierarchy", "rt_device_count", "rt_scene_
            "rt_first_contacts", "rt_first_contacts_device")
 # csrc/rt_debug.h: only in the -DRT_TEST_HOOKS build
 DEBUG_SYMBOLS = ("rt_debug_set", "rt_debug_count", "rt_debug_wave_trace", "rt_debug_flat_filter_check", "rt_debug_gang_layout", "rt_debug_rccl_library",
-                 "rt_debug_shard_costs", "rt_debug_tight_bounds", "rt_debug_cost_map")
+                 "rt_debug_shard_costs", "rt_debug_tight_bounds", "rt_debug_cost_map", "rt_debug_walk_bounds")
 
 
 class Options(C.Structure):      # rt_options / RenderOptions render.rs:33-38
@@ -199,6 +199,7 @@ lib.rt_build_info.restype = C.c_char_p
 RT_LAUNCH_TWO_RAYS, RT_LAUNCH_COOPERATIVE, RT_LAUNCH_SAMPLE_PARALLEL, RT_LAUNCH_ORDERED, RT_LAUNCH_FLAT_PIPELINE, RT_LAUNCH_COUNTING, RT_LAUNCH_FAST_KERNEL = 1, 2, 4, 8, 16, 32, 64
 RT_LAUNCH_TIGHT_BOUNDS = 128
 RT_LAUNCH_TIGHT_COSTS = 256
+RT_LAUNCH_WALK_BOUNDS = 512
 HAVE_TEST_HOOKS = hasattr(lib, "rt_debug_set")
 
 if lib.rt_abi_version() != ABI_VERSION:
@@ -224,7 +225,8 @@ def last_launch():
     f = lib.rt_last_launch_flags()
     names = (("two_rays", RT_LAUNCH_TWO_RAYS), ("cooperative", RT_LAUNCH_COOPERATIVE), ("sample_parallel", RT_LAUNCH_SAMPLE_PARALLEL),
              ("ordered", RT_LAUNCH_ORDERED), ("flat_pipeline", RT_LAUNCH_FLAT_PIPELINE), ("counting", RT_LAUNCH_COUNTING), ("fast_kernel", RT_LAUNCH_FAST_KERNEL),
-             ("tight_bounds", RT_LAUNCH_TIGHT_BOUNDS), ("tight_costs", RT_LAUNCH_TIGHT_COSTS))
+             ("tight_bounds", RT_LAUNCH_TIGHT_BOUNDS), ("tight_costs", RT_LAUNCH_TIGHT_COSTS),
+             ("walk_bounds", RT_LAUNCH_WALK_BOUNDS))
     return {n for n, bit in names if f & bit}
 
 
@@ -276,7 +278,7 @@ def selftest_rcp(device=0):
 (DEBUG_SKIP_VARIANT, DEBUG_BLOCK_ORDER, DEBUG_NARROW_MAX, DEBUG_PACKED_SAMPLES, DEBUG_PRINT_STEPS, DEBUG_PRINT_COSTS,
  DEBUG_HOST_COPY, DEBUG_COALESCE, DEBUG_LDS_BYTES, DEBUG_WG_POLICY, DEBUG_NARROW_L2, DEBUG_FLAT_KERNELS, DEBUG_SKIP_RAYS,
  DEBUG_FRAME_AHEAD, DEBUG_FILTER_RO_PERCENT, DEBUG_COOP, DEBUG_COOP_THR, DEBUG_COOP_MAX, DEBUG_COOP_LEVEL, DEBUG_COOP_REST, DEBUG_ASYNC_ORDERS,
- DEBUG_FAST_KERNEL, DEBUG_EXACT_COSTS, DEBUG_MULTIHIT_BUCKET, DEBUG_TIGHT_BOUNDS, DEBUG_TIGHT_COSTS) = range(26)
+ DEBUG_FAST_KERNEL, DEBUG_EXACT_COSTS, DEBUG_MULTIHIT_BUCKET, DEBUG_TIGHT_BOUNDS, DEBUG_TIGHT_COSTS, DEBUG_WALK_BOUNDS) = range(27)
 if HAVE_TEST_HOOKS:
     lib.rt_debug_set.argtypes = [C.c_int, C.c_longlong]
     lib.rt_debug_wave_trace.argtypes = [C.c_char_p]
@@ -288,6 +290,8 @@ if HAVE_TEST_HOOKS:
     lib.rt_debug_rccl_library.argtypes = [C.c_char_p]
     lib.rt_debug_cost_map.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     lib.rt_debug_tight_bounds.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "rt_debug_walk_bounds"):          # (tools load older hooks builds for A/B runs)
+        lib.rt_debug_walk_bounds.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]
 
 
 def _need_hooks(what):
@@ -347,6 +351,26 @@ def tight_bounds(items, light_unit, eye, bounds, ranges):
     check(lib.rt_debug_tight_bounds(items.ctypes.data, len(items), light.ctypes.data, eye.ctypes.data, bounds.ctypes.data, arr, len(bounds),
                                     out.ctypes.data, tight.ctypes.data, consts.ctypes.data), "rt_debug_tight_bounds")
     return out, tight, {"S": consts[0], "eta": consts[1], "volume_ratio": consts[2], "by_rule": bool(consts[3]), "rule": int(consts[3])}
+
+
+def walk_bounds(items, light_unit, eye, bounds, ranges, slack=True):
+    """rt_debug_walk_bounds (no device needed) -> (float32[n_bounds, 12] per-walk records: the primary stream's sphere (4), the threshold it
+    carries, T', w1', w2', cl', R2o', R2i', flags (1 eye sphere, 2 light disc), {the shadow filter's frame and constants, cone_ratio, disc_ratio}).
+    slack=False: the records without their rounding terms (what the rim fixtures must catch)."""
+    import numpy as np
+    _need_hooks("rt_debug_walk_bounds")
+    items = np.ascontiguousarray(items, dtype=np.float32).reshape(-1, 4)
+    bounds = np.ascontiguousarray(bounds, dtype=np.float32).reshape(-1, 4)
+    light = np.ascontiguousarray(light_unit, dtype=np.float32)
+    eye = np.ascontiguousarray(eye, dtype=np.float32)
+    arr = (Range * len(ranges))(*[Range(int(f), int(c)) for f, c in ranges])
+    out = np.zeros((len(bounds), 12), dtype=np.float32)
+    fr = np.zeros(20, dtype=np.float64)
+    check(lib.rt_debug_walk_bounds(items.ctypes.data, len(items), light.ctypes.data, eye.ctypes.data, bounds.ctypes.data, arr, len(bounds),
+                                   1 if slack else 0, out.ctypes.data, fr.ctypes.data), "rt_debug_walk_bounds")
+    return out, {"m0": fr[0:3].astype(np.float32), "e1": fr[3:6].astype(np.float32), "e2": fr[6:9].astype(np.float32), "l": fr[9:12].astype(np.float32),
+                 "a0": np.float32(fr[12]), "k1": np.float32(fr[13]), "kc": np.float32(fr[14]), "ro2": np.float32(fr[15]), "S": fr[16], "eta": fr[17],
+                 "cone_ratio": fr[18], "disc_ratio": fr[19]}
 
 
 def gang_layout(regions, n_devices):

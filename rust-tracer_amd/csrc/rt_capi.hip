@@ -247,7 +247,17 @@ struct rt_scene {
     std::atomic<bool> tight_ready{ false };
     void *d_tight = nullptr, *d_tprim = nullptr, *d_tshad = nullptr, *d_txprim = nullptr, *d_txshad = nullptr;
     uint32_t n_tight = 0;
-    bool fused = false;            // every BOUND is followed by an ITEM with the same centre (rt_skip.hpp, Node)
+    // PER-WALK streams (rt_tight.hpp build_walk): the tight streams' FNode / FNodeS copies once more, every BOUND that qualifies
+    // carrying an eye sphere with T' in the primary copy and a light disc in the shadow copy; node order, skip offsets, exact shadow records
+    // and item table are the tight streams'.  Made once, by the scene's worker behind the tight dispatch orders (ensure_walk); ONE allocation.
+    std::vector<rt::RawNode<float>> raw_tight;     // the raw stream with the tight spheres, kept from ensure_tight for that day
+    std::vector<uint8_t> tight_mask;               // per node: 1 = a BOUND that carries a tight ball (rt_tight::Result::tight)
+    std::mutex walk_mu;
+    bool walk_tried = false;
+    std::atomic<bool> walk_ready{ false };
+    void *d_walk = nullptr, *d_wxprim = nullptr, *d_wxshad = nullptr;
+    uint32_t n_walk_primary = 0, n_walk_shadow = 0;
+    bool fused = false;           // every BOUND is followed by an ITEM with the same centre (rt_skip.hpp, Node)
     // the hierarchy once more in sibling-contiguous order for the lane-cooperative walk (rt_coop.hpp; f64: CNode64); coop.fanout == 0: none
     void *d_coop_prim = nullptr, *d_coop_shad = nullptr;
     rt::CoopView coop{};

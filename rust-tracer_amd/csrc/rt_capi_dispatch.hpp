@@ -874,6 +874,17 @@ void build_orders_async(rt_scene *s, size_t index, std::vector<rt::TileDev> tab,
     }
     clk.lap("worker: tight dispatch orders");
     (void)hipGetLastError();
+    // The per-walk filter streams (ensure_walk) behind all of that.  The lists' orders stay the ones built from the tight streams' costs -- the
+    // counting path walks Node streams, and the per-walk records live in the filter streams only --; a list whose orders were tried on the
+    // tight streams is tried once more on the streams its launches read from now on.
+    const bool had_walk = s->walk_ready.load(std::memory_order_acquire);
+    if (knob(RT_DEBUG_WALK_BOUNDS) != 0 && ensure_walk(s) && !had_walk) {
+        std::lock_guard<std::mutex> lk(s->mu);
+        for (rt_scene::CachedTable &t : s->tables)
+            if (t.from_worker && !t.building && !t.tight_pending && t.orders.size() > 1 && t.orders[0].e0[0] && table_walks_tight(s, t.host, t.passes, t.tight_knob)) t.retrial = true;
+    }
+    clk.lap("worker: per-walk streams");
+    (void)hipGetLastError();
 }
 
 rt_status device_table(rt_scene *s, Context *c, const std::vector<rt::TileDev> &tab, hipStream_t stream, const rt::TileDev **out, int slot,
@@ -889,7 +900,7 @@ rt_status device_table(rt_scene *s, Context *c, const std::vector<rt::TileDev> &
     long long coop_key = 0;
     if (o && order_out)
         for (int k : { RT_DEBUG_COOP, RT_DEBUG_COOP_THR, RT_DEBUG_COOP_MAX, RT_DEBUG_COOP_LEVEL, RT_DEBUG_COOP_REST, RT_DEBUG_NARROW_MAX, RT_DEBUG_NARROW_L2, RT_DEBUG_SKIP_RAYS, RT_DEBUG_EXACT_COSTS,
-                       RT_DEBUG_TIGHT_BOUNDS, RT_DEBUG_TIGHT_COSTS })
+                       RT_DEBUG_TIGHT_BOUNDS, RT_DEBUG_TIGHT_COSTS, RT_DEBUG_WALK_BOUNDS })
             coop_key = coop_key * 1000003ll + (knob(k) + 2);
     if (cacheable) {
         std::lock_guard<std::mutex> lk(s->mu);

@@ -233,6 +233,50 @@ rt_status rt_debug_tight_bounds(const float *dfs_items, uint32_t n_items, const 
     }
     return RT_OK;
 }
+
+// ... and the per-walk records it would get (rt_tight.hpp build_walk), on the host alone.
+rt_status rt_debug_walk_bounds(const float *dfs_items, uint32_t n_items, const float *light_unit, const float *eye, const float *bounds, const rt_range *ranges,
+                               uint32_t n_bounds, int slack, float *records_out, double frame_out[20])
+{
+    rt_scene *none = nullptr;
+    if (rt_status ast = scene_items_ok("rt_debug_walk_bounds", RT_F32, dfs_items, n_items, light_unit, eye, bounds, ranges, n_bounds, false, &none); ast != RT_OK) return ast;
+    if (!n_bounds || !records_out) { snprintf(g_err, sizeof g_err, "rt_debug_walk_bounds: no bounds or no output"); return RT_ERR_INVALID_ARGUMENT; }
+    std::unique_ptr<rt_scene> s(new (std::nothrow) rt_scene());      // (host fields only: nothing of it ever reaches a device)
+    if (!s) return RT_ERR_OUT_OF_MEMORY;
+    s->precision = RT_F32; s->n_items = n_items; s->n_bounds = n_bounds;
+    if (rt_status vst = scene_view_ok("rt_debug_walk_bounds", s.get(), light_unit, eye); vst != RT_OK) return vst;
+    std::vector<rt::RawNode<float>> raw;
+    if (rt_status st = build_raw_stream<float>(dfs_items, n_items, bounds, ranges, n_bounds, raw); st != RT_OK) return st;
+    filter_constants<float>(s.get(), raw, dfs_items);
+    rt_tight::Result tr;
+    tight_spheres_of(s.get(), raw, tr);
+    for (size_t i = 0; i < raw.size(); ++i)
+        if (tr.tight[i]) { raw[i].cx = tr.sphere[4 * i]; raw[i].cy = tr.sphere[4 * i + 1]; raw[i].cz = tr.sphere[4 * i + 2]; raw[i].r = tr.sphere[4 * i + 3]; }
+    rt_tight::WalkResult wr;
+    walk_records_of(s.get(), raw, tr.tight, wr, slack != 0);
+    memset(records_out, 0, sizeof(float) * 12 * n_bounds);
+    uint32_t b = 0;
+    for (size_t i = 0; i < raw.size(); ++i) {
+        if (raw[i].skip == 0u) continue;
+        while (b < n_bounds && ranges[b].count == 0) ++b;                // (groups without items have no node)
+        if (b >= n_bounds) break;
+        float *r = records_out + 12 * b++;
+        const rt_bounds::WalkOverride &o = wr.ovr[i];
+        memcpy(r, &wr.eye_sphere[4 * i], sizeof(float) * 4);
+        // the threshold the stream carries: max(T of the eye sphere, T'), as k_build_streams / k_build_fstreams form it
+        const float vx = r[0] - (float)s->eye[0], vy = r[1] - (float)s->eye[1], vz = r[2] - (float)s->eye[2];
+        const float ts = rt_bounds::primary_threshold((vx * vx + vy * vy) + vz * vz, r[3] * r[3]);
+        r[4] = (o.flags & rt_bounds::kWalkPrimary) && ts > -__builtin_huge_valf() && o.tp > ts ? o.tp : ts;
+        r[5] = o.tp; r[6] = o.w1; r[7] = o.w2; r[8] = o.cl; r[9] = o.r2o; r[10] = o.r2i; r[11] = (float)o.flags;
+    }
+    if (frame_out) {
+        const rt::FilterConsts &fc = s->fc;
+        for (int k = 0; k < 3; ++k) { frame_out[k] = fc.m0[k]; frame_out[3 + k] = fc.e1[k]; frame_out[6 + k] = fc.e2[k]; frame_out[9 + k] = fc.l[k]; }
+        frame_out[12] = fc.a0; frame_out[13] = fc.k1; frame_out[14] = fc.kc; frame_out[15] = fc.ro2; frame_out[16] = fc.S; frame_out[17] = fc.eta;
+        frame_out[18] = wr.cone_ratio; frame_out[19] = wr.disc_ratio;
+    }
+    return RT_OK;
+}
 #endif  // RT_TEST_HOOKS
 
 rt_status rt_scene_create(int device, rt_precision precision, const void *dfs_items, uint32_t n_items,
@@ -349,7 +393,7 @@ rt_status rt_scene_destroy(rt_scene *s)
     if (s->d_swept) (void)hipFree(s->d_swept);
     if (s->d_cprim) (void)hipFree(s->d_cprim);
     if (s->d_cshad) (void)hipFree(s->d_cshad);
-    for (void *p : { s->d_xprim, s->d_xshad, s->d_xcprim, s->d_xcshad, s->d_xown, s->d_fc, s->d_coop_prim, s->d_coop_shad, s->d_cost_arena, s->d_tight }) if (p) (void)hipFree(p);
+    for (void *p : { s->d_xprim, s->d_xshad, s->d_xcprim, s->d_xcshad, s->d_xown, s->d_fc, s->d_coop_prim, s->d_coop_shad, s->d_cost_arena, s->d_tight, s->d_walk }) if (p) (void)hipFree(p);
     if (s->cost_stream) { (void)hipStreamSynchronize(s->cost_stream); (void)hipStreamDestroy(s->cost_stream); }
     if (s->h_cost) (void)hipHostFree(s->h_cost);
     if (s->h_up) (void)hipHostFree(s->h_up);

@@ -153,11 +153,20 @@ rt::Fast2Args fast2_args(const rt_scene *s, const rt::BlockList &order, unsigned
 // Does this launch walk the scene's TIGHT streams (walks_tight_with, rt_capi_dispatch.hpp)?  A question only: whoever wants the streams
 // made at the launch (RT_DEBUG_TIGHT_BOUNDS at 1 or 2: tests, tools) calls ensure_tight first -- launch_render does.
 bool walks_tight(const rt_scene *s, int v, uint64_t total_px, unsigned spp) { return walks_tight_with(s, v, total_px, spp, knob(RT_DEBUG_TIGHT_BOUNDS)); }
+// ... and does such a launch read the scene's PER-WALK filter streams in their places (rt_tight.hpp build_walk)?  RT_DEBUG_WALK_BOUNDS: 0 never,
+// 1 the rule, 2 wherever the scene has them; default: the rule (kWalkByRule, DESIGN.md 4.1: what the A/B against the parent said).
+constexpr bool kWalkByRule = true;
+bool walks_per_walk(const rt_scene *s)
+{
+    const long long wb = knob(RT_DEBUG_WALK_BOUNDS);
+    if (wb == 0 || !s->walk_ready.load(std::memory_order_acquire)) return false;
+    return wb == 2 || kWalkByRule;
+}
 
 template <typename T, bool COUNT, int VAR>
 rt_status launch_skip_one(const rt_scene *s, Context *c, dim3 grid, hipStream_t stream, unsigned w, unsigned h, unsigned spp,
                           const rt::TileDev *d_tab, unsigned nt, uint64_t total_px, uint8_t *d_out, rt::Counters *cnt, unsigned frame_w,
-                          rt::BlockList order, [[maybe_unused]] bool tight = false)
+                          rt::BlockList order, [[maybe_unused]] int tight = 0)      // (skip_view_of: 0 given, 1 tight, 2 per-walk)
 {
     // two rays per lane (rt_skip2.hpp): f32, fused assembly loops, launches that neither count nor trace
     bool two_rays = false;
@@ -360,10 +369,12 @@ rt_status launch_skip_var(const rt_scene *s, Context *c, dim3 grid, hipStream_t 
             if (walks_tight(s, v, total_px, spp)) {
                 g_launch_flags |= RT_LAUNCH_TIGHT_BOUNDS;
                 if (order.d && order.tight_costs) g_launch_flags |= RT_LAUNCH_TIGHT_COSTS;
+                const int streams = walks_per_walk(s) ? 2 : 1;          // (skip_view_of: the tight streams, or the per-walk filter streams over them)
+                if (streams == 2) g_launch_flags |= RT_LAUNCH_WALK_BOUNDS;
 #ifdef RT_TEST_HOOKS
-                if (v & 8) return launch_skip_one<T, false, 27>(s, c, grid, stream, w, h, spp, d_tab, nt, total_px, d_out, cnt, frame_w, order, true);
+                if (v & 8) return launch_skip_one<T, false, 27>(s, c, grid, stream, w, h, spp, d_tab, nt, total_px, d_out, cnt, frame_w, order, streams);
 #endif
-                return launch_skip_one<T, false, 19>(s, c, grid, stream, w, h, spp, d_tab, nt, total_px, d_out, cnt, frame_w, order, true);
+                return launch_skip_one<T, false, 19>(s, c, grid, stream, w, h, spp, d_tab, nt, total_px, d_out, cnt, frame_w, order, streams);
             }
         }
         switch (v) {
@@ -452,6 +463,8 @@ rt_status launch_render(rt_scene *s, Context *c, const rt_options *o, rt_travers
     const unsigned w = o->width, h = o->height, spp = o->samples_per_pixel;
     // RT_DEBUG_TIGHT_BOUNDS 1 / 2 (tests, tools): the tight streams are made here and now if the scene's worker has not made them yet
     if (trav == RT_TRAVERSAL_SKIP && !cnt && knob(RT_DEBUG_TIGHT_BOUNDS) >= 1) (void)ensure_tight(s);
+    // ... and RT_DEBUG_WALK_BOUNDS 1 / 2 the per-walk streams over them
+    if (trav == RT_TRAVERSAL_SKIP && !cnt && knob(RT_DEBUG_WALK_BOUNDS) >= 1 && knob(RT_DEBUG_TIGHT_BOUNDS) != 0 && ensure_tight(s)) (void)ensure_walk(s);
     if (spp == 0) {
         // render.rs:219-250 with no sample to take: 0 * inf = NaN in every channel, and `NaN as u8` is 0 (set_pixel_from_vector, render.rs:96-108)
         g_launch_flags = cnt ? RT_LAUNCH_COUNTING : 0u;

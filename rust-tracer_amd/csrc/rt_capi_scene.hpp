@@ -230,9 +230,10 @@ rt::FlatScView flat_sc_view_of(const rt_scene *s)
     return v;
 }
 
-// tight: the tight streams in the places of the plain ones (f32 scenes whose tight_ready is set; the un-fused loops only)
+// tight 1: the tight streams in the places of the plain ones (f32 scenes whose tight_ready is set; the un-fused loops only); 2: and the
+// per-walk filter streams in the places of the tight ones' FNode / FNodeS copies (walk_ready is set; the exact records stay the tight ones)
 template <typename T>
-rt::SkipView<T> skip_view_of(const rt_scene *s, bool tight = false)
+rt::SkipView<T> skip_view_of(const rt_scene *s, int tight = 0)
 {
     rt::SkipView<T> v;
     v.prim = static_cast<const rt::Node<T> *>(tight ? s->d_tprim : s->d_prim);
@@ -244,8 +245,8 @@ rt::SkipView<T> skip_view_of(const rt_scene *s, bool tight = false)
     v.n_fnodes = s->n_fnodes;
     v.light = { (T)s->light[0], (T)s->light[1], (T)s->light[2] };
     v.eye = { (T)s->eye[0], (T)s->eye[1], (T)s->eye[2] };
-    v.xprim = static_cast<const rt::FNode *>(tight ? s->d_txprim : s->d_xprim);
-    v.xshad = static_cast<const rt::FNodeS *>(tight ? s->d_txshad : s->d_xshad);
+    v.xprim = static_cast<const rt::FNode *>(tight == 2 ? s->d_wxprim : tight ? s->d_txprim : s->d_xprim);
+    v.xshad = static_cast<const rt::FNodeS *>(tight == 2 ? s->d_wxshad : tight ? s->d_txshad : s->d_xshad);
     v.xfprim = static_cast<const rt::FNode *>(s->d_xcprim);
     v.xfshad = static_cast<const rt::FNodeS *>(s->d_xcshad);
     v.xown = static_cast<const uint32_t *>(s->d_xown);
@@ -255,7 +256,7 @@ rt::SkipView<T> skip_view_of(const rt_scene *s, bool tight = false)
 
 // The one argument of the render kernels (rt_skip.hpp SkipArgs: what a wave needs first lies first).
 template <typename T>
-rt::SkipArgs<T> skip_args_of(const rt_scene *s, bool tight, const rt::BlockDesc *order, const uint32_t *wg_first, unsigned w, unsigned h, unsigned frame_w, uint8_t *out,
+rt::SkipArgs<T> skip_args_of(const rt_scene *s, int tight, const rt::BlockDesc *order, const uint32_t *wg_first, unsigned w, unsigned h, unsigned frame_w, uint8_t *out,
                              const rt::TileDev *tiles, unsigned n_tiles, unsigned spp, rt::Counters *counters, uint32_t *lane_cost, rt::SampleBuf<T> sb,
                              rt::CoopView cv = rt::CoopView{}, const uint64_t *holes = nullptr, unsigned n_holes = 0)
 {
@@ -265,11 +266,13 @@ rt::SkipArgs<T> skip_args_of(const rt_scene *s, bool tight, const rt::BlockDesc 
     // a counting launch walks the given streams and holds every ITEM test that counts against the tight ones, where the scene has them
     if (counters && !tight && sizeof(T) == 4 && s->tight_ready.load(std::memory_order_acquire)) {
         a.tprim = static_cast<const rt::Node<T> *>(s->d_tprim); a.tshad = static_cast<const rt::Node<T> *>(s->d_tshad);
+        // ... and against the per-walk records: T' with the eye sphere, the light disc with its front
+        if (s->walk_ready.load(std::memory_order_acquire)) { a.wprim = static_cast<const rt::FNode *>(s->d_wxprim); a.wshad = static_cast<const rt::FNodeS *>(s->d_wxshad); }
     }
     return a;
 }
 template <typename T, typename... A>
-rt::SkipArgs<T> skip_args(const rt_scene *s, const rt::BlockDesc *order, A... rest) { return skip_args_of<T>(s, false, order, rest...); }      // (the given streams)
+rt::SkipArgs<T> skip_args(const rt_scene *s, const rt::BlockDesc *order, A... rest) { return skip_args_of<T>(s, 0, order, rest...); }      // (the given streams)
 
 
 // Constants of the filtered loops' shadow bounds (rt_skip.hpp FilterConsts, shadow_filter_bounds; derivation in DESIGN.md 4.1).
@@ -572,7 +575,79 @@ bool ensure_tight(rt_scene *s)
     s->d_tight = d; s->d_tprim = d; s->d_tshad = d + 32 * total; s->d_txprim = d + 64 * total; s->d_txshad = d + 96 * total;
     s->n_tight = tr.n_tight;
     s->tight_by_rule = tight_rule(tr, s->fused);
+    s->raw_tight = std::move(raw);              // (ensure_walk: 37 bytes per node of host memory until the per-walk streams are made)
+    s->tight_mask = std::move(tr.tight);
     s->tight_ready.store(true, std::memory_order_release);
+    return true;
+}
+
+// What rt_tight::build_walk needs on top: the eye as the stream kernels see it, and the shadow filter's frame.
+rt_tight::WalkParams walk_params(const rt_scene *s)
+{
+    rt_tight::WalkParams w{};
+    w.base = tight_params(s);
+    for (int k = 0; k < 3; ++k) { w.eye[k] = (float)s->eye[k]; w.m0[k] = s->fc.m0[k]; w.e1[k] = s->fc.e1[k]; w.e2[k] = s->fc.e2[k]; w.l[k] = s->fc.l[k]; }
+    w.fS = s->fc.S; w.feta = s->fc.eta;
+    return w;
+}
+
+void walk_records_of(const rt_scene *s, const std::vector<rt::RawNode<float>> &raw_tight, const std::vector<uint8_t> &mask, rt_tight::WalkResult &out, bool slack = true)
+{
+    rt_tight::Result tr;
+    std::vector<uint32_t> skip(raw_tight.size());
+    tr.sphere.resize(4 * raw_tight.size());
+    for (size_t i = 0; i < raw_tight.size(); ++i) {
+        tr.sphere[4 * i] = raw_tight[i].cx; tr.sphere[4 * i + 1] = raw_tight[i].cy; tr.sphere[4 * i + 2] = raw_tight[i].cz; tr.sphere[4 * i + 3] = raw_tight[i].r;
+        skip[i] = raw_tight[i].skip;
+    }
+    tr.tight = mask;
+    for (uint8_t m : mask) tr.n_tight += m;
+    // (ITEM nodes carry the given values in the tight stream, bit for bit: it serves as the stream of the items too)
+    rt_tight::build_walk(tr.sphere.data(), skip.data(), (uint32_t)raw_tight.size(), tr, walk_params(s), out, 32, slack);
+}
+
+// Makes the per-walk streams of an f32 scene that has tight streams (once; normally the scene's worker behind the tight dispatch orders).
+// true: they are there.  A scene without a single record gets none.
+bool ensure_walk(rt_scene *s)
+{
+    if (s->walk_ready.load(std::memory_order_acquire)) return true;
+    if (!s->tight_ready.load(std::memory_order_acquire)) return false;
+    std::lock_guard<std::mutex> lk(s->walk_mu);
+    if (s->walk_tried) return s->walk_ready.load(std::memory_order_acquire);
+    s->walk_tried = true;
+    std::vector<rt::RawNode<float>> raw;
+    std::vector<uint8_t> mask;
+    raw.swap(s->raw_tight); mask.swap(s->tight_mask);
+    if (raw.empty() || mask.size() != raw.size()) return false;
+    rt_tight::WalkResult wr;
+    walk_records_of(s, raw, mask, wr);
+    if (wr.n_primary == 0 && wr.n_shadow == 0) return false;
+    for (size_t i = 0; i < raw.size(); ++i)
+        if (wr.ovr[i].flags & rt_bounds::kWalkPrimary) { raw[i].cx = wr.eye_sphere[4 * i]; raw[i].cy = wr.eye_sphere[4 * i + 1]; raw[i].cz = wr.eye_sphere[4 * i + 2]; raw[i].r = wr.eye_sphere[4 * i + 3]; }
+    const size_t n = raw.size(), total = n + rt::kNodePad;
+    // the two streams that stay, then what the build launches read: the eye spheres' Node streams, the raw stream, the records
+    char *d = nullptr;
+    if (hipMalloc(&d, 128 * total + sizeof(rt::RawNode<float>) * n + sizeof(rt_bounds::WalkOverride) * n) != hipSuccess) { (void)hipGetLastError(); return false; }
+    rt::RawNode<float> *d_raw = reinterpret_cast<rt::RawNode<float> *>(d + 128 * total);
+    rt_bounds::WalkOverride *d_ovr = reinterpret_cast<rt_bounds::WalkOverride *>(d + 128 * total + sizeof(rt::RawNode<float>) * n);
+    hipError_t e = hipMemcpy(d_raw, raw.data(), sizeof(rt::RawNode<float>) * n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_ovr, wr.ovr.data(), sizeof(rt_bounds::WalkOverride) * n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        const rt::V3<float> eye = { (float)s->eye[0], (float)s->eye[1], (float)s->eye[2] };
+        rt::Node<float> *ep = reinterpret_cast<rt::Node<float> *>(d + 64 * total), *es = reinterpret_cast<rt::Node<float> *>(d + 96 * total);
+        const dim3 grid((unsigned)((total + 255) / 256));
+        hipLaunchKernelGGL((rt::k_build_streams<float>), grid, dim3(256), 0, s->cost_stream, d_raw, (unsigned)n, eye, false, ep, es);
+        // primary terms from the eye spheres, shadow terms from the TIGHT stream (its exact records are the ones the shadow walk fetches)
+        hipLaunchKernelGGL(rt::k_build_fstreams, grid, dim3(256), 0, s->cost_stream, ep, static_cast<const rt::Node<float> *>(s->d_tshad), (unsigned)total, false, s->fc,
+                           reinterpret_cast<rt::FNode *>(d), reinterpret_cast<rt::FNodeS *>(d + 32 * total), static_cast<uint32_t *>(nullptr), d_ovr, (unsigned)n);
+        e = hipGetLastError();
+        const hipError_t se = hipStreamSynchronize(s->cost_stream);
+        if (e == hipSuccess) e = se;
+    }
+    if (e != hipSuccess) { (void)hipGetLastError(); (void)hipFree(d); return false; }
+    s->d_walk = d; s->d_wxprim = d; s->d_wxshad = d + 32 * total;
+    s->n_walk_primary = wr.n_primary; s->n_walk_shadow = wr.n_shadow;
+    s->walk_ready.store(true, std::memory_order_release);
     return true;
 }
 

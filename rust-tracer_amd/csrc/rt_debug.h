@@ -67,7 +67,11 @@ typedef enum rt_debug_key {
                                     the scene's worker has not yet; default: the rule, from the launch on that finds them made.  All must render the same bytes */
     RT_DEBUG_TIGHT_COSTS = 25,   /* which costs the dispatch orders of a list whose launches walk the tight streams are built from (read when a tile list is first
                                     seen): 0 the given streams' (what every other list gets; A/B runs); default: the tight streams' */
-    RT_DEBUG_KEYS = 26
+    RT_DEBUG_WALK_BOUNDS = 26,   /* the per-walk streams of an f32 scene (rt_tight.hpp build_walk: an eye sphere with T' for the primary walk, a light disc for the
+                                    shadow walk), for launches that walk the tight streams: 0 never, 1 the library's rule, 2 wherever a scene has them -- 1 and 2
+                                    make them at the launch if the scene's worker has not yet; default: the rule, from the launch on that finds them made.
+                                    All must render the same bytes */
+    RT_DEBUG_KEYS = 27
 } rt_debug_key;
 
 /* value < 0 restores the default. */
@@ -106,6 +110,12 @@ rt_status rt_debug_flat_filter_check(rt_scene *scene, uint32_t width, uint32_t h
  * for bit (0), tight_out[n_bounds].  consts_out (optional): { S, eta, summed-volume ratio tight / given, the selection rule's verdict: 0 never, 1 every launch that can, 2 one-sample passes of a million pixels or more }. */
 rt_status rt_debug_tight_bounds(const float *dfs_items, uint32_t n_items, const float *light_unit, const float *eye, const float *bounds, const rt_range *ranges,
                                 uint32_t n_bounds, float *spheres_out, uint8_t *tight_out, double consts_out[4]);
+/* ... and for the per-walk streams (rt_tight.hpp build_walk), host only: per bound, records_out[12 * n_bounds] = { the sphere the primary per-walk stream
+ * carries (4), the threshold it carries, T', w1', w2', cl', R2o', R2i', flags (1: eye sphere, 2: light disc) }.  slack = 0 takes the rounding terms out of
+ * T', R2o' and cl' (what the rim fixtures must catch).  frame_out (optional): FilterConsts { m0, e1, e2, l (3 each), a0, k1, kc, ro2, S, eta }, then the
+ * mean cone half-angle and disc radius of the records relative to the tight ball's. */
+rt_status rt_debug_walk_bounds(const float *dfs_items, uint32_t n_items, const float *light_unit, const float *eye, const float *bounds, const rt_range *ranges,
+                               uint32_t n_bounds, int slack, float *records_out, double frame_out[20]);
 
 /* Test infrastructure for the multi-GPU paths.  rt_debug_gang_layout: the sharding arithmetic of rt_gang_render_frame(s) without a
  * device -- for bucket i its device (i % n_devices) and its first pixel inside that device's tile-major shard; per device the pixels

@@ -14,6 +14,7 @@
 // reference performs for its ray -- including the reference's behaviour when a ray starts inside a bound.
 #pragma once
 #include "rt_kernels.hpp"
+#include "rt_filter_bounds.hpp"
 #include "rt_skip_rot.hpp"
 #include "rt_coop.hpp"
 
@@ -87,34 +88,12 @@ struct FilterConsts {
 };
 
 // Outer / inner bound of P2 for a sphere with squared radius rr (as the reference rounds it): DESIGN.md 4.1.
-__device__ __forceinline__ float next_f32_above(float f)      // finite f
-{
-    const uint32_t u = __float_as_uint(f);
-    if ((u << 1) == 0u) return __uint_as_float(0x00000001u);
-    return __uint_as_float((u >> 31) ? u - 1u : u + 1u);
-}
-__device__ __forceinline__ float next_f32_below(float f);
+// (one statement for device and host: rt_filter_bounds.hpp -- rt_tight.hpp derives the per-walk records from the same values)
+__device__ __forceinline__ float next_f32_above(float f) { return rt_bounds::next_above(f); }      // finite f
+__device__ __forceinline__ float next_f32_below(float f) { return rt_bounds::next_below(f); }      // finite f
 __device__ __forceinline__ void shadow_filter_bounds(const FilterConsts &fc, float rr_f, float &r2o, float &r2i)
 {
-    const double eps = 0x1p-24, rr = rr_f, S2 = fc.S * fc.S, a9 = 9.7 * eps * fc.S;
-    if (!(rr < 1e300)) { r2o = r2i = __builtin_huge_valf(); return; }       // END: rr = +inf
-    const double so = __builtin_sqrt(rr * (1.0 + 1.01 * eps) + (fc.eta + 12.0 * eps) * S2) + a9;
-    const double o = so * so * (1.0 + 2.01 * eps) + 1e-36;
-    float of = (float)o;
-    if ((double)of < o) of = next_f32_above(of);
-    r2o = next_f32_above(of);
-    // inner bound, for the test  P2 + k1 (P2 + a^2) <= R2i  (FilterConsts::k1 carries the part that grows with the ray's own distance)
-    const double tau = 0x1p-10, es2 = eps * fc.S * eps * fc.S;
-    const double c2 = 102.7 * (1.0 + 1.0 / tau) * es2 * (1.0 + fc.eta);
-    const double X = (1.0 + fc.eta + 10.2 * eps) * c2 * (1.0 + 6.0 * eps) + 94.1 * es2 * (1.0 + 1.0 / tau);
-    const double i = (rr * (1.0 - eps) - X) / ((1.0 + tau) * (1.0 + 2.1 * eps) * (1.0 + fc.eta) * (1.0 + 40.0 * eps)) * (1.0 - 8.0 * eps) - 1e-36;
-    r2i = -1.0f;
-    if (i > 0.0) {
-        float inf_ = (float)i;
-        if ((double)inf_ > i) inf_ = next_f32_below(inf_);
-        inf_ = next_f32_below(inf_);
-        r2i = inf_ > 0.0f ? inf_ : -1.0f;
-    }
+    rt_bounds::shadow_bounds(fc.S, fc.eta, rr_f, r2o, r2i);
 }
 
 template <typename T> struct SkipView {
@@ -136,24 +115,7 @@ template <typename T> struct SkipView {
 // direction d (a normalised f32 vector, | |d|^2 - 1 | <= 16 eps) for which Sphere::distance_from_ray returns a finite distance has
 // fma(vz, dz, fma(vy, dy, vx*dx)) >= T.  -inf (every ray passes) when the eye is not clearly outside the sphere or the squares are
 // near the subnormal range.  DESIGN.md 4.1 carries the derivation.
-__device__ __forceinline__ float next_f32_below(float f)      // finite f
-{
-    const uint32_t u = __float_as_uint(f);
-    if ((u << 1) == 0u) return __uint_as_float(0x80000001u);
-    return __uint_as_float((u >> 31) ? u + 1u : u - 1u);
-}
-__device__ __forceinline__ float primary_filter_threshold(float vv_f, float rr_f)
-{
-    const double eps = 0x1p-24, vv = vv_f, rr = rr_f;
-    // (vv >= 1e-14: |v| >= 1e-7, so that b >= sqrt(60 eps vv) keeps the squares of the BOUND step's root-free decision -- differences of
-    // values of b's magnitude -- in the normal range: bound_shortcut_verdict)
-    if (!(vv >= 1e-14) || !(vv - rr >= 64.0 * eps * (vv + rr))) return -__builtin_huge_valf();
-    const double m0 = vv - rr * (1.0 + 2.0 * eps) - 1e-44;
-    const double t = __builtin_sqrt(m0 * (1.0 - 2.0 * eps)) - 8.0 * eps * __builtin_sqrt(vv);
-    float tf = (float)t;
-    if ((double)tf > t) tf = next_f32_below(tf);
-    return next_f32_below(tf);
-}
+__device__ __forceinline__ float primary_filter_threshold(float vv_f, float rr_f) { return rt_bounds::primary_threshold(vv_f, rr_f); }
 
 // The same threshold for an f64 scene's PRIMARY walk (rt_skip_rot.hpp, the double overloads of skip_primary_rot_filt*): the f64 test
 // returns a finite distance only if b >= sqrt(vv - rr) (1 - 1e-15) (disc >= 0 and, the eye clearly outside, b > 0); the filter's
@@ -245,8 +207,11 @@ __global__ void k_build_fstream64(const Node<double> *__restrict__ prim, const N
 
 // Filtered copies of a pair of Node<float> streams (plain or compacted; END nodes included).
 __global__ void k_build_fstreams(const Node<float> *__restrict__ prim, const Node<float> *__restrict__ shad, unsigned n_total, bool compacted,
-                                 FilterConsts fc, FNode *__restrict__ xprim, FNodeS *__restrict__ xshad, uint32_t *__restrict__ own_item)
+                                 FilterConsts fc, FNode *__restrict__ xprim, FNodeS *__restrict__ xshad, uint32_t *__restrict__ own_item,
+                                 const rt_bounds::WalkOverride *__restrict__ ovr = nullptr, unsigned n_ovr = 0)
 {
+    // ovr (optional; the per-walk streams of rt_tight.hpp build_walk): records of the first n_ovr nodes -- the END nodes carry none -- that
+    // replace what a BOUND's filter terms would be derived from its sphere; `prim` is then the stream of the eye spheres, `shad` the tight one
     const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_total) return;
     const Node<float> p = prim[i], s = shad[i];
@@ -267,6 +232,11 @@ __global__ void k_build_fstreams(const Node<float> *__restrict__ prim, const Nod
     if (compacted && !end && !item) shadow_filter_bounds(fc, s.own_rr, fs.r2o_own, fs.r2i_own);
     if (end) fs.r2o_own = -0.0f;                                            // sign bit: END
     fs.skip_off = s.skip_off;
+    if (ovr && i < n_ovr && !end && !item) {
+        const rt_bounds::WalkOverride o = ovr[i];
+        if ((o.flags & rt_bounds::kWalkPrimary) != 0u && fp.f5 > -__builtin_huge_valf() && o.tp > fp.f5) fp.f5 = o.tp;
+        if ((o.flags & rt_bounds::kWalkShadow) != 0u) { fs.w1 = o.w1; fs.w2 = o.w2; fs.cl = o.cl; fs.r2o = o.r2o; fs.r2i = o.r2i; }
+    }
     xprim[i] = fp;
     xshad[i] = fs;
     if (own_item) own_item[i] = (compacted && !end && !item) ? p.item : 0u;
@@ -423,6 +393,7 @@ template <typename T> struct SkipArgs {
     SkipView<T> sc;
     Counters *counters; uint32_t *lane_cost; const uint64_t *holes; unsigned n_holes; SampleBuf<T> sb; CoopView cv;
     const Node<T> *tprim, *tshad;       // counting launches: the scene's TIGHT plain streams (rt_tight.hpp) to hold the walk against, or NULL
+    const FNode *wprim; const FNodeS *wshad;    // ... and its PER-WALK filter streams (rt_tight.hpp build_walk), or NULL
 };
 typedef unsigned rt_u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned rt_u32x4 __attribute__((ext_vector_type(4)));
@@ -464,7 +435,8 @@ __device__ __forceinline__ void render_skip_body(const BlockDesc *__restrict__ o
                                                  Counters *__restrict__ counters, uint32_t *__restrict__ lane_cost,
                                                  const uint64_t *__restrict__ holes, unsigned n_holes, SampleBuf<T> sb, SkipView<T> sc, CoopView cv,
                                                  [[maybe_unused]] unsigned long long r_entry,      // (wave trace: the wave's very first instruction)
-                                                 [[maybe_unused]] const Node<T> *__restrict__ tprim = nullptr, [[maybe_unused]] const Node<T> *__restrict__ tshad = nullptr)
+                                                 [[maybe_unused]] const Node<T> *__restrict__ tprim = nullptr, [[maybe_unused]] const Node<T> *__restrict__ tshad = nullptr,
+                                                 [[maybe_unused]] const FNode *__restrict__ wprim = nullptr, [[maybe_unused]] const FNodeS *__restrict__ wshad = nullptr)
 {
     constexpr bool PACKED = MODE == kSkipPacked, SPLIT = MODE == kSkipSplit || PACKED, ONE = MODE == kSkipOne;
     static_assert(!COOP || (!COUNT && ONE && (VAR & 2) != 0 && (sizeof(T) == 4 || (VAR & 16) != 0)), "the cooperative walk serves spp-1 passes of the assembly loops (f64: the filtered ones)");
@@ -617,7 +589,7 @@ __device__ __forceinline__ void render_skip_body(const BlockDesc *__restrict__ o
             Node<T> nd = sc.prim[0];                                    // wave-uniform record -> SGPRs
             // (counting launches, tight streams: the stream position up to which a tight BOUND would have put this lane to sleep -- the walk
             // itself stays on the given streams, so that its counters are the CPU path's)
-            [[maybe_unused]] unsigned tsleep = 0u;
+            [[maybe_unused]] unsigned tsleep = 0u, wsleep = 0u;        // (wsleep: the same for the per-walk record)
             for (;;) {
                 const bool active = i >= resume;
                 // Sphere::distance_from_ray with the ray-independent parts pre-formed (primitive.rs:55-72)
@@ -683,6 +655,24 @@ __device__ __forceinline__ void render_skip_body(const BlockDesc *__restrict__ o
                                 }
                                 if (active && i >= tsleep && td >= best) tsleep = nd.skip();
                             } else if (active && i < tsleep && !(d >= best)) ++c_tviol;
+                        }
+                        if (wprim) {
+                            if (nd.is_bound()) {
+                                // the per-walk record as the filtered loops take it: the filter with T' first, then the reference's test on the eye sphere
+                                const FNode wn = wprim[i];
+                                bool quiet = !primary_filter_pass(wn, dir.x, dir.y, dir.z);
+                                if (!quiet) {
+                                    const T wb = (wn.a0 * dir.x + wn.a1 * dir.y) + wn.a2 * dir.z;
+                                    const T wdisc = (wb * wb - wn.a3) + wn.a4;
+                                    T wd = inf<T>();
+                                    if (!(wdisc < T(0.0))) {
+                                        const T ws = (VAR & 1) ? sqrt_rn_lean(wdisc) : rsqrt_exact(wdisc);
+                                        if (!((wb + ws) < T(0.0))) wd = (wb - ws) > T(0.0) ? wb - ws : wb + ws;
+                                    }
+                                    quiet = wd >= best;
+                                }
+                                if (active && i >= wsleep && quiet) wsleep = nd.skip();
+                            } else if (active && i < wsleep && !(d >= best)) ++c_tviol;
                         }
                     }
                     if (nd.is_bound()) {                                // BOUND  group.rs:73
@@ -790,7 +780,7 @@ __device__ __forceinline__ void render_skip_body(const BlockDesc *__restrict__ o
                 if constexpr (COUNT && sizeof(T) == 4) { if (sc.xshad) { cfc = *sc.fc; shadow_filter_origin(cfc, sp.x, sp.y, sp.z, fq1, fq2, fql); } }
                 if constexpr (COUNT && sizeof(T) == 8) { if (sc.xshad) { cfc = *sc.fc; shadow_filter_origin64(cfc, sp.x, sp.y, sp.z, fq1, fq2, fql); } }
                 Node<T> nd = sc.shad[0];
-                [[maybe_unused]] unsigned tsleep = 0u;                  // (as in the primary walk)
+                [[maybe_unused]] unsigned tsleep = 0u, wsleep = 0u;      // (as in the primary walk)
                 for (;;) {
                     const bool active = i >= resume;
                     const V3<T> v = { nd.a0 - sp.x, nd.a1 - sp.y, nd.a2 - sp.z };
@@ -828,6 +818,22 @@ __device__ __forceinline__ void render_skip_body(const BlockDesc *__restrict__ o
                                 if (!(tdisc < T(0.0))) thit = !((tb + ((VAR & 1) ? sqrt_rn_lean(tdisc) : rsqrt_exact(tdisc))) < T(0.0));
                                 if (active && i >= tsleep && !thit) tsleep = nd.skip();
                             } else if (active && i < tsleep && hit) ++c_tviol;
+                        }
+                        if (wshad && tshad && sc.xshad) {
+                            if (nd.is_bound()) {
+                                // the per-walk record as the one-ray loops take it: the light disc (MISS), the inner disc (HIT: the lane enters), the
+                                // front (behind the origin: MISS), and between them the reference's test on the tight ball
+                                const int wv = shadow_filter_verdict<true>(wshad[i], cfc, fq1, fq2, fql);
+                                bool enters = wv == 2;
+                                if (wv == 1) {
+                                    const Node<T> tn = tshad[i];
+                                    const V3<T> tv = { tn.a0 - sp.x, tn.a1 - sp.y, tn.a2 - sp.z };
+                                    const T tb = dot(tv, sdir);
+                                    const T tdisc = (tb * tb - dot(tv, tv)) + tn.a3;
+                                    if (!(tdisc < T(0.0))) enters = !((tb + ((VAR & 1) ? sqrt_rn_lean(tdisc) : rsqrt_exact(tdisc))) < T(0.0));
+                                }
+                                if (active && i >= wsleep && !enters) wsleep = nd.skip();
+                            } else if (active && i < wsleep && hit) ++c_tviol;
                         }
                     }
                     unsigned ni;
@@ -947,7 +953,7 @@ __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(6
     if constexpr (!COUNT && (VAR & 8) != 0) r_entry = __builtin_amdgcn_s_memrealtime();
     const SkipArgs<T> &a = args;
     render_skip_body<T, COUNT, VAR, MODE, COOP>(a.order, a.wg_first, a.width, a.height, a.frame_w, a.out, a.tiles, a.n_tiles, a.spp_arg, a.counters, a.lane_cost, a.holes,
-                     a.n_holes, a.sb, a.sc, a.cv, r_entry, a.tprim, a.tshad);
+                     a.n_holes, a.sb, a.sc, a.cv, r_entry, a.tprim, a.tshad, a.wprim, a.wshad);
 }
 
 // The same kernel for f32 launches that do not count, held to 74 scalar registers -- 80 with the hardware's six, and 80 is what a CU admits

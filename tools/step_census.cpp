@@ -9,7 +9,13 @@
 // --tight: the un-fused walk over the tight bounds of rt_tight.hpp (a BOUND's own sphere is the ITEM step behind it), the prediction the
 // GPU numbers of the tight streams are read against; the hash of every pixel's hit item and shadow verdict must equal the plain run's.
 //
-//   g++ -O2 -ffp-contract=off -o /tmp/step_census tools/step_census.cpp && /tmp/step_census [w h [level]] [--tight]
+// --walk: the same walk over the per-walk records of rt_tight.hpp build_walk -- primary: a BOUND carries its eye sphere and max(T of it, T'),
+// a lane sleeps where the fused chain b' stays below that or the reference's test of the eye sphere culls; shadow: a BOUND carries its light
+// disc, a lane sleeps where P2 > R2o' or the front says "behind the origin", enters where the inner disc says so, and runs the reference's
+// test of the TIGHT ball in between.  A step is quiet when no live lane passes the node's filter.  The hash must equal the other runs'.
+// Both print the steps of the heaviest waves and the longest single pixel.
+//
+//   g++ -O2 -ffp-contract=off -o /tmp/step_census tools/step_census.cpp && /tmp/step_census [w h [level]] [--tight | --walk]
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -25,6 +31,9 @@ static inline V3 mulf(V3 a, float m) { return { a.x * m, a.y * m, a.z * m }; }
 static inline float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 static inline V3 normalized(V3 a) { float l = sqrtf(dot(a, a)); return mulf(a, 1.0f / l); }
 struct Node { V3 c; float r; uint32_t skip; int item; };
+// --walk: what the filter streams carry for a node (k_build_fstreams with the records of build_walk)
+struct Filt { V3 pc; float pr, f5, w1, w2, cl, r2o, r2i; };
+static std::vector<Filt> filt;
 static std::vector<Node> nodes;
 static void pyramid(unsigned level, V3 p, float r)
 {
@@ -44,9 +53,10 @@ static inline float dist(V3 c, float r, V3 o, V3 d, float *disc_out)
 }
 int main(int argc, char **argv)
 {
-    bool tight = false;
+    bool tight = false, walk = false;
     std::vector<char *> pos;
-    for (int a = 1; a < argc; ++a) { if (!strcmp(argv[a], "--tight")) tight = true; else pos.push_back(argv[a]); }
+    for (int a = 1; a < argc; ++a) { if (!strcmp(argv[a], "--tight")) tight = true; else if (!strcmp(argv[a], "--walk")) tight = walk = true; else pos.push_back(argv[a]); }
+    float fq_m0[3] = { 0, 0, 0 }, fq_e1[3] = { 0, 0, 0 }, fq_e2[3] = { 0, 0, 0 }, fq_l[3] = { 0, 0, 0 }, fq_a0 = 0, fq_k1 = 0, fq_kc = 0;
     const unsigned W = pos.size() > 0 ? atoi(pos[0]) : 1920, H = pos.size() > 1 ? atoi(pos[1]) : 1080, level = pos.size() > 2 ? atoi(pos[2]) : 8;
     pyramid(level, { 0, -1, 0 }, 1.0f);
     const size_t n = nodes.size();
@@ -75,19 +85,73 @@ int main(int argc, char **argv)
         rt_tight::build(sph.data(), skip.data(), (uint32_t)n, p, tr);
         for (size_t i = 0; i < n; ++i) if (tr.tight[i]) { nodes[i].c = { tr.sphere[4 * i], tr.sphere[4 * i + 1], tr.sphere[4 * i + 2] }; nodes[i].r = tr.sphere[4 * i + 3]; }
         printf("tight: %u of %u bounds carry a tight sphere, volume ratio %.4f (S %.4f)\n", tr.n_tight, tr.n_bounds, tr.volume_ratio, p.S);
+        if (walk) {
+            // the shadow filter's frame and constants (rt_capi_scene.hpp filter_constants), then the library's own build_walk
+            rt_tight::WalkParams wp{};
+            wp.base = p;
+            const double l[3] = { sdir.x, sdir.y, sdir.z }, ln = sqrt(l2), lh[3] = { l[0] / ln, l[1] / ln, l[2] / ln };
+            int ax = 0;
+            for (int k = 1; k < 3; ++k) if (fabs(lh[k]) < fabs(lh[ax])) ax = k;
+            double a[3] = { 0, 0, 0 }; a[ax] = 1.0;
+            double e1[3] = { lh[1] * a[2] - lh[2] * a[1], lh[2] * a[0] - lh[0] * a[2], lh[0] * a[1] - lh[1] * a[0] };
+            const double n1 = sqrt(e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]);
+            for (int k = 0; k < 3; ++k) e1[k] /= n1;
+            const double e2[3] = { lh[1] * e1[2] - lh[2] * e1[1], lh[2] * e1[0] - lh[0] * e1[2], lh[0] * e1[1] - lh[1] * e1[0] };
+            const float eyef[3] = { eye.x, eye.y, eye.z };
+            for (int k = 0; k < 3; ++k) { wp.eye[k] = eyef[k]; wp.m0[k] = fq_m0[k] = (float)p.m0[k]; wp.e1[k] = fq_e1[k] = (float)e1[k]; wp.e2[k] = fq_e2[k] = (float)e2[k]; wp.l[k] = fq_l[k] = (float)l[k]; }
+            wp.feta = fabs(l2 - 1.0); wp.fS = (rc + ro * (1.0 + 4.0 * rt_tight::kEps)) * (1.0 + 1e-9);
+            auto up = [](double v) { float f = (float)v; if ((double)f < v) f = nextafterf(f, INFINITY); return nextafterf(f, INFINITY); };
+            fq_a0 = up(11.0 * rt_tight::kEps * wp.fS + 1e-37);
+            fq_k1 = up((wp.feta + 10.2 * rt_tight::kEps) * (1.0 + wp.feta) * (1.0 + 12.0 * rt_tight::kEps));
+            { float kc = (float)(1.0 / (1.0 + 4.0 * 0x1p-10)); if ((double)kc > 1.0 / (1.0 + 4.0 * 0x1p-10)) kc = nextafterf(kc, 0.0f); fq_kc = nextafterf(kc, 0.0f); }
+            rt_tight::WalkResult wr;
+            rt_tight::build_walk(tr.sphere.data(), skip.data(), (uint32_t)n, tr, wp, wr);
+            printf("walk: %u eye spheres, %u light discs of %u tight bounds; cone half-angle %.3f, disc radius %.3f of the tight ball's\n", wr.n_primary, wr.n_shadow, tr.n_tight, wr.cone_ratio, wr.disc_ratio);
+            filt.resize(n);
+            for (size_t i = 0; i < n; ++i) {
+                Filt &f = filt[i];
+                const rt_bounds::WalkOverride &o = wr.ovr[i];
+                f.pc = { wr.eye_sphere[4 * i], wr.eye_sphere[4 * i + 1], wr.eye_sphere[4 * i + 2] }; f.pr = wr.eye_sphere[4 * i + 3];
+                const V3 v = sub(f.pc, eye);
+                f.f5 = rt_bounds::primary_threshold((v.x * v.x + v.y * v.y) + v.z * v.z, f.pr * f.pr);
+                if ((o.flags & rt_bounds::kWalkPrimary) && f.f5 > -INFINITY && o.tp > f.f5) f.f5 = o.tp;
+                const double cx = (double)nodes[i].c.x - (double)fq_m0[0], cy = (double)nodes[i].c.y - (double)fq_m0[1], cz = (double)nodes[i].c.z - (double)fq_m0[2];
+                f.w1 = (float)((cx * (double)fq_e1[0] + cy * (double)fq_e1[1]) + cz * (double)fq_e1[2]);
+                f.w2 = (float)((cx * (double)fq_e2[0] + cy * (double)fq_e2[1]) + cz * (double)fq_e2[2]);
+                f.cl = (float)((cx * (double)fq_l[0] + cy * (double)fq_l[1]) + cz * (double)fq_l[2]);
+                rt_bounds::shadow_bounds(wp.fS, wp.feta, nodes[i].r * nodes[i].r, f.r2o, f.r2i);
+                if (o.flags & rt_bounds::kWalkShadow) { f.w1 = o.w1; f.w2 = o.w2; f.cl = o.cl; f.r2o = o.r2o; f.r2i = o.r2i; }
+            }
+        }
     }
+    std::vector<uint32_t> wave_steps;
+    unsigned longest_px = 0;
     uint64_t hash = 1469598103934665603ull;
     uint64_t pQ = 0, pB0 = 0, pB1 = 0, pB2 = 0, pI = 0, pLeafQ = 0, sQ = 0, sH = 0, sEnt = 0, waves = 0, swaves = 0;
     uint64_t dec1 = 0, dec2 = 0, dec1_b0 = 0;    // B0 steps in which every candidate lane has b >= best (root-free "no" possible) 
     for (unsigned y0 = 0; y0 < H; y0 += 8) for (unsigned x0 = 0; x0 < W; x0 += 8) {
-        V3 dir[64]; bool in[64]; float best[64]; int bi[64]; uint32_t res[64];
+        V3 dir[64]; bool in[64]; float best[64]; int bi[64]; uint32_t res[64]; unsigned awake[64]; uint32_t wsteps = 0;
+        for (unsigned l = 0; l < 64; ++l) awake[l] = 0;
         for (unsigned l = 0; l < 64; ++l) { unsigned x = x0 + l % 8, y = y0 + l / 8; in[l] = x < W && y < H; dir[l] = normalized({ (float)x - W / 2.0f, ((float)H - (float)y) - H / 2.0f, (float)W }); best[l] = INFINITY; bi[l] = -1; res[l] = in[l] ? 0u : 0xFFFFFFFFu; }
         ++waves;
         for (size_t i = 0; i < n;) {
             const Node &nd = nodes[i];
             bool cand = false, enter = false, undecided = false, undecided2 = false;
+            ++wsteps;
             for (unsigned l = 0; l < 64; ++l) {
                 if (i < res[l]) continue;
+                ++awake[l];
+                if (walk) {
+                    // the filter first (rt_skip.hpp primary_filter_pass), then the reference's test on the sphere the stream carries
+                    const Filt &f = filt[i];
+                    const V3 v = sub(f.pc, eye);
+                    const bool pass = f.f5 <= fmaf(v.z, dir[l].z, fmaf(v.y, dir[l].y, v.x * dir[l].x));
+                    float wdisc; const float wd = pass ? dist(f.pc, f.pr, eye, dir[l], &wdisc) : INFINITY;
+                    if (pass) cand = true;
+                    if (!nd.item) { if (!pass || wd >= best[l]) res[l] = nd.skip; else enter = true; }
+                    else if (pass && !(wd >= best[l])) { best[l] = wd; bi[l] = (int)i; }
+                    continue;
+                }
                 float disc; const float d = dist(nd.c, nd.r, eye, dir[l], &disc);
                 if (disc >= 0) cand = true;
                 if (disc >= 0 && !nd.item) {
@@ -131,11 +195,36 @@ int main(int argc, char **argv)
         if (!nn) continue;
         ++swaves;
         for (unsigned l = 0; l < 64; ++l) res[l] = need[l] ? 0u : 0xFFFFFFFFu;
+        float q1[64], q2[64], ol[64];
+        if (walk) for (unsigned l = 0; l < 64; ++l) {
+            if (!need[l]) continue;
+            const float x = sp[l].x - fq_m0[0], y = sp[l].y - fq_m0[1], z = sp[l].z - fq_m0[2];      // (rt_skip.hpp shadow_filter_origin; every origin is covered here)
+            q1[l] = fmaf(z, fq_e1[2], fmaf(y, fq_e1[1], x * fq_e1[0])); q2[l] = fmaf(z, fq_e2[2], fmaf(y, fq_e2[1], x * fq_e2[0])); ol[l] = fmaf(z, fq_l[2], fmaf(y, fq_l[1], x * fq_l[0]));
+        }
         for (size_t i = 0; i < n;) {
             const Node &nd = nodes[i];
             bool cand = false, enter = false, fin = false;
+            ++wsteps;
             for (unsigned l = 0; l < 64; ++l) {
                 if (i < res[l]) continue;
+                ++awake[l];
+                if (walk) {
+                    // rt_skip.hpp shadow_filter_verdict<true>, then the reference's test of the tight ball for the lanes in between
+                    const Filt &f = filt[i];
+                    const float t0 = f.w1 - q1[l], t1 = f.w2 - q2[l], p2 = t0 * t0 + t1 * t1;
+                    int verdict = 1;
+                    if (p2 > f.r2o) verdict = 0;
+                    else {
+                        cand = true;
+                        const float av = f.cl - ol[l], inn = fmaf(av, av, p2);
+                        if (fmaf(inn, fq_k1, p2) <= f.r2i && (fq_a0 <= av || inn <= f.r2i)) verdict = 2;
+                        else if (av <= -fq_a0 && f.r2o <= fq_kc * inn) verdict = 0;
+                    }
+                    float wdisc; const bool whit = verdict == 2 || (verdict == 1 && dist(nd.c, nd.r, sp[l], sdir, &wdisc) < INFINITY);
+                    if (!nd.item) { if (!whit) res[l] = nd.skip; else enter = true; }
+                    else if (verdict == 1 ? whit : dist(nd.c, nd.r, sp[l], sdir, &wdisc) < INFINITY) { res[l] = 0xFFFFFFFFu; fin = true; }
+                    continue;
+                }
                 float disc; const bool hit = dist(nd.c, nd.r, sp[l], sdir, &disc) < INFINITY;
                 if (disc >= 0) cand = true;
                 if (!nd.item) { if (!hit) res[l] = nd.skip; else enter = true; }
@@ -148,7 +237,13 @@ int main(int argc, char **argv)
             i = ni;
         }
         for (unsigned l = 0; l < 64; ++l) if (need[l]) hash = (hash ^ (res[l] == 0xFFFFFFFFu ? 1u : 2u)) * 1099511628211ull;
+        wave_steps.push_back(wsteps);
+        for (unsigned l = 0; l < 64; ++l) longest_px = std::max(longest_px, awake[l]);
     }
+    std::sort(wave_steps.begin(), wave_steps.end(), [](uint32_t a, uint32_t b) { return a > b; });
+    auto rank = [&](size_t k) { return k <= wave_steps.size() ? wave_steps[k - 1] : 0u; };
+    printf("steps of the heaviest 8x8 wave (with a shadow walk) / rank 5 / rank 20 / rank 100 / rank 500: %u / %u / %u / %u / %u; longest single pixel (nodes its lane is awake at, both walks): %u\n",
+           rank(1), rank(5), rank(20), rank(100), rank(500), longest_px);
     printf("%ux%u: %llu waves (%llu with shadow rays)\n", W, H, (unsigned long long)waves, (unsigned long long)swaves);
     printf("primary: quiet BOUND %llu, quiet ITEM %llu, BOUND cand/no enter %llu, BOUND enter/own quiet %llu, BOUND enter/own cand %llu, ITEM cand %llu\n", (unsigned long long)pQ, (unsigned long long)pLeafQ,
            (unsigned long long)pB0, (unsigned long long)pB1, (unsigned long long)pB2, (unsigned long long)pI);
