@@ -923,9 +923,12 @@ int rt_abi_version(void);
  *   RT_LAUNCH_TIGHT_COSTS      (with RT_LAUNCH_TIGHT_BOUNDS and RT_LAUNCH_ORDERED) the dispatch order was built from costs counted on those
  *                              tight streams, not on the scene's given ones
  *   RT_LAUNCH_WALK_BOUNDS      (with RT_LAUNCH_TIGHT_BOUNDS) the walk's filters read the scene's per-walk streams: a cone from the eye for
- *                              the primary rays, a disc across the light for the shadow rays, at no change to any byte */
+ *                              the primary rays, a disc across the light for the shadow rays, at no change to any byte
+ *   RT_LAUNCH_LEAN_BOUNDS      (with RT_LAUNCH_WALK_BOUNDS) the primary walk settled the bounds that carry a cone from the filter's own dot product,
+ *                              without the reference's arithmetic on the bound, at no change to any byte */
 enum { RT_LAUNCH_TWO_RAYS = 1u, RT_LAUNCH_COOPERATIVE = 2u, RT_LAUNCH_SAMPLE_PARALLEL = 4u, RT_LAUNCH_ORDERED = 8u, RT_LAUNCH_FLAT_PIPELINE = 16u,
-       RT_LAUNCH_COUNTING = 32u, RT_LAUNCH_FAST_KERNEL = 64u, RT_LAUNCH_TIGHT_BOUNDS = 128u, RT_LAUNCH_TIGHT_COSTS = 256u, RT_LAUNCH_WALK_BOUNDS = 512u };
+       RT_LAUNCH_COUNTING = 32u, RT_LAUNCH_FAST_KERNEL = 64u, RT_LAUNCH_TIGHT_BOUNDS = 128u, RT_LAUNCH_TIGHT_COSTS = 256u, RT_LAUNCH_WALK_BOUNDS = 512u,
+       RT_LAUNCH_LEAN_BOUNDS = 1024u };
 uint32_t rt_last_launch_flags(void);
 
 /* The toolchain this library was built with, e.g. "hipcc: HIP version: 7.2.x ... | clang ... | kernels <sha1 of the kernel sources>"

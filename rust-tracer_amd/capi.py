@@ -47,7 +47,7 @@ SYMBOLS = ("rt_abi_version", "rt_build_hierarchy", "rt_device_count", "rt_scene_
            "rt_first_contacts", "rt_first_contacts_device")
 # csrc/rt_debug.h: only in the -DRT_TEST_HOOKS build
 DEBUG_SYMBOLS = ("rt_debug_set", "rt_debug_count", "rt_debug_wave_trace", "rt_debug_flat_filter_check", "rt_debug_gang_layout", "rt_debug_rccl_library",
-                 "rt_debug_shard_costs", "rt_debug_tight_bounds", "rt_debug_cost_map", "rt_debug_walk_bounds")
+                 "rt_debug_shard_costs", "rt_debug_tight_bounds", "rt_debug_cost_map", "rt_debug_walk_bounds", "rt_debug_lean_bounds")
 
 
 class Options(C.Structure):      # rt_options / RenderOptions render.rs:33-38
@@ -200,6 +200,7 @@ RT_LAUNCH_TWO_RAYS, RT_LAUNCH_COOPERATIVE, RT_LAUNCH_SAMPLE_PARALLEL, RT_LAUNCH_
 RT_LAUNCH_TIGHT_BOUNDS = 128
 RT_LAUNCH_TIGHT_COSTS = 256
 RT_LAUNCH_WALK_BOUNDS = 512
+RT_LAUNCH_LEAN_BOUNDS = 1024
 HAVE_TEST_HOOKS = hasattr(lib, "rt_debug_set")
 
 if lib.rt_abi_version() != ABI_VERSION:
@@ -226,7 +227,7 @@ def last_launch():
     names = (("two_rays", RT_LAUNCH_TWO_RAYS), ("cooperative", RT_LAUNCH_COOPERATIVE), ("sample_parallel", RT_LAUNCH_SAMPLE_PARALLEL),
              ("ordered", RT_LAUNCH_ORDERED), ("flat_pipeline", RT_LAUNCH_FLAT_PIPELINE), ("counting", RT_LAUNCH_COUNTING), ("fast_kernel", RT_LAUNCH_FAST_KERNEL),
              ("tight_bounds", RT_LAUNCH_TIGHT_BOUNDS), ("tight_costs", RT_LAUNCH_TIGHT_COSTS),
-             ("walk_bounds", RT_LAUNCH_WALK_BOUNDS))
+             ("walk_bounds", RT_LAUNCH_WALK_BOUNDS), ("lean_bounds", RT_LAUNCH_LEAN_BOUNDS))
     return {n for n, bit in names if f & bit}
 
 
@@ -278,7 +279,7 @@ def selftest_rcp(device=0):
 (DEBUG_SKIP_VARIANT, DEBUG_BLOCK_ORDER, DEBUG_NARROW_MAX, DEBUG_PACKED_SAMPLES, DEBUG_PRINT_STEPS, DEBUG_PRINT_COSTS,
  DEBUG_HOST_COPY, DEBUG_COALESCE, DEBUG_LDS_BYTES, DEBUG_WG_POLICY, DEBUG_NARROW_L2, DEBUG_FLAT_KERNELS, DEBUG_SKIP_RAYS,
  DEBUG_FRAME_AHEAD, DEBUG_FILTER_RO_PERCENT, DEBUG_COOP, DEBUG_COOP_THR, DEBUG_COOP_MAX, DEBUG_COOP_LEVEL, DEBUG_COOP_REST, DEBUG_ASYNC_ORDERS,
- DEBUG_FAST_KERNEL, DEBUG_EXACT_COSTS, DEBUG_MULTIHIT_BUCKET, DEBUG_TIGHT_BOUNDS, DEBUG_TIGHT_COSTS, DEBUG_WALK_BOUNDS) = range(27)
+ DEBUG_FAST_KERNEL, DEBUG_EXACT_COSTS, DEBUG_MULTIHIT_BUCKET, DEBUG_TIGHT_BOUNDS, DEBUG_TIGHT_COSTS, DEBUG_WALK_BOUNDS, DEBUG_LEAN_BOUNDS) = range(28)
 if HAVE_TEST_HOOKS:
     lib.rt_debug_set.argtypes = [C.c_int, C.c_longlong]
     lib.rt_debug_wave_trace.argtypes = [C.c_char_p]
@@ -292,6 +293,8 @@ if HAVE_TEST_HOOKS:
     lib.rt_debug_tight_bounds.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
     if hasattr(lib, "rt_debug_walk_bounds"):          # (tools load older hooks builds for A/B runs)
         lib.rt_debug_walk_bounds.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "rt_debug_lean_bounds"):
+        lib.rt_debug_lean_bounds.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
 
 
 def _need_hooks(what):
@@ -371,6 +374,23 @@ def walk_bounds(items, light_unit, eye, bounds, ranges, slack=True):
     return out, {"m0": fr[0:3].astype(np.float32), "e1": fr[3:6].astype(np.float32), "e2": fr[6:9].astype(np.float32), "l": fr[9:12].astype(np.float32),
                  "a0": np.float32(fr[12]), "k1": np.float32(fr[13]), "kc": np.float32(fr[14]), "ro2": np.float32(fr[15]), "S": fr[16], "eta": fr[17],
                  "cone_ratio": fr[18], "disc_ratio": fr[19]}
+
+
+def lean_bounds(items, light_unit, eye, bounds, ranges):
+    """rt_debug_lean_bounds (no device needed) -> (the records of walk_bounds, float32[n_bounds] Rq of the lean BOUND step: 0 where the bound
+    has no eye sphere and keeps the reference's test)."""
+    import numpy as np
+    _need_hooks("rt_debug_lean_bounds")
+    items = np.ascontiguousarray(items, dtype=np.float32).reshape(-1, 4)
+    bounds = np.ascontiguousarray(bounds, dtype=np.float32).reshape(-1, 4)
+    light = np.ascontiguousarray(light_unit, dtype=np.float32)
+    eye = np.ascontiguousarray(eye, dtype=np.float32)
+    arr = (Range * len(ranges))(*[Range(int(f), int(c)) for f, c in ranges])
+    out = np.zeros((len(bounds), 12), dtype=np.float32)
+    rq = np.zeros(len(bounds), dtype=np.float32)
+    check(lib.rt_debug_lean_bounds(items.ctypes.data, len(items), light.ctypes.data, eye.ctypes.data, bounds.ctypes.data, arr, len(bounds),
+                                   out.ctypes.data, rq.ctypes.data), "rt_debug_lean_bounds")
+    return out, rq
 
 
 def gang_layout(regions, n_devices):

@@ -257,6 +257,7 @@ struct rt_scene {
     std::atomic<bool> walk_ready{ false };
     void *d_walk = nullptr, *d_wxprim = nullptr, *d_wxshad = nullptr;
     uint32_t n_walk_primary = 0, n_walk_shadow = 0;
+    bool walk_lean = false;                     // the per-walk primary stream carries lean BOUNDs (k_build_fstreams `lean`; written before walk_ready)
     bool fused = false;           // every BOUND is followed by an ITEM with the same centre (rt_skip.hpp, Node)
     // the hierarchy once more in sibling-contiguous order for the lane-cooperative walk (rt_coop.hpp; f64: CNode64); coop.fanout == 0: none
     void *d_coop_prim = nullptr, *d_coop_shad = nullptr;

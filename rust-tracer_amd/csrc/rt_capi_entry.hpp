@@ -235,8 +235,8 @@ rt_status rt_debug_tight_bounds(const float *dfs_items, uint32_t n_items, const 
 }
 
 // ... and the per-walk records it would get (rt_tight.hpp build_walk), on the host alone.
-rt_status rt_debug_walk_bounds(const float *dfs_items, uint32_t n_items, const float *light_unit, const float *eye, const float *bounds, const rt_range *ranges,
-                               uint32_t n_bounds, int slack, float *records_out, double frame_out[20])
+static rt_status debug_walk_records(const float *dfs_items, uint32_t n_items, const float *light_unit, const float *eye, const float *bounds, const rt_range *ranges,
+                                    uint32_t n_bounds, int slack, float *records_out, double frame_out[20], float *rq_out)
 {
     rt_scene *none = nullptr;
     if (rt_status ast = scene_items_ok("rt_debug_walk_bounds", RT_F32, dfs_items, n_items, light_unit, eye, bounds, ranges, n_bounds, false, &none); ast != RT_OK) return ast;
@@ -268,6 +268,7 @@ rt_status rt_debug_walk_bounds(const float *dfs_items, uint32_t n_items, const f
         const float ts = rt_bounds::primary_threshold((vx * vx + vy * vy) + vz * vz, r[3] * r[3]);
         r[4] = (o.flags & rt_bounds::kWalkPrimary) && ts > -__builtin_huge_valf() && o.tp > ts ? o.tp : ts;
         r[5] = o.tp; r[6] = o.w1; r[7] = o.w2; r[8] = o.cl; r[9] = o.r2o; r[10] = o.r2i; r[11] = (float)o.flags;
+        if (rq_out) rq_out[b - 1] = (o.flags & rt_bounds::kWalkPrimary) ? o.rq : 0.0f;
     }
     if (frame_out) {
         const rt::FilterConsts &fc = s->fc;
@@ -276,6 +277,18 @@ rt_status rt_debug_walk_bounds(const float *dfs_items, uint32_t n_items, const f
         frame_out[18] = wr.cone_ratio; frame_out[19] = wr.disc_ratio;
     }
     return RT_OK;
+}
+rt_status rt_debug_walk_bounds(const float *dfs_items, uint32_t n_items, const float *light_unit, const float *eye, const float *bounds, const rt_range *ranges,
+                               uint32_t n_bounds, int slack, float *records_out, double frame_out[20])
+{
+    return debug_walk_records(dfs_items, n_items, light_unit, eye, bounds, ranges, n_bounds, slack, records_out, frame_out, nullptr);
+}
+// ... with Rq of every bound that carries an eye sphere (rt_filter_bounds.hpp lean_radius; 0: the bound has none and keeps the reference's test).
+rt_status rt_debug_lean_bounds(const float *dfs_items, uint32_t n_items, const float *light_unit, const float *eye, const float *bounds, const rt_range *ranges,
+                               uint32_t n_bounds, float *records_out, float *rq_out)
+{
+    if (!rq_out) { snprintf(g_err, sizeof g_err, "rt_debug_lean_bounds: no output"); return RT_ERR_INVALID_ARGUMENT; }
+    return debug_walk_records(dfs_items, n_items, light_unit, eye, bounds, ranges, n_bounds, 1, records_out, nullptr, rq_out);
 }
 #endif  // RT_TEST_HOOKS
 

@@ -371,6 +371,7 @@ rt_status launch_skip_var(const rt_scene *s, Context *c, dim3 grid, hipStream_t 
                 if (order.d && order.tight_costs) g_launch_flags |= RT_LAUNCH_TIGHT_COSTS;
                 const int streams = walks_per_walk(s) ? 2 : 1;          // (skip_view_of: the tight streams, or the per-walk filter streams over them)
                 if (streams == 2) g_launch_flags |= RT_LAUNCH_WALK_BOUNDS;
+                if (streams == 2 && s->walk_lean) g_launch_flags |= RT_LAUNCH_LEAN_BOUNDS;      // (the flag is data: the loops take the lean step where a node says so)
 #ifdef RT_TEST_HOOKS
                 if (v & 8) return launch_skip_one<T, false, 27>(s, c, grid, stream, w, h, spp, d_tab, nt, total_px, d_out, cnt, frame_w, order, streams);
 #endif

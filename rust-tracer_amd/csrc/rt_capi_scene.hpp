@@ -632,6 +632,8 @@ bool ensure_walk(rt_scene *s)
     rt_bounds::WalkOverride *d_ovr = reinterpret_cast<rt_bounds::WalkOverride *>(d + 128 * total + sizeof(rt::RawNode<float>) * n);
     hipError_t e = hipMemcpy(d_raw, raw.data(), sizeof(rt::RawNode<float>) * n, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_ovr, wr.ovr.data(), sizeof(rt_bounds::WalkOverride) * n, hipMemcpyHostToDevice);
+    // the lean BOUND step: every launch that reads these streams takes it where a node carries the flag (RT_DEBUG_LEAN_BOUNDS 0: no node does)
+    const bool lean = knob(RT_DEBUG_LEAN_BOUNDS) != 0 && wr.n_primary != 0;
     if (e == hipSuccess) {
         const rt::V3<float> eye = { (float)s->eye[0], (float)s->eye[1], (float)s->eye[2] };
         rt::Node<float> *ep = reinterpret_cast<rt::Node<float> *>(d + 64 * total), *es = reinterpret_cast<rt::Node<float> *>(d + 96 * total);
@@ -639,14 +641,14 @@ bool ensure_walk(rt_scene *s)
         hipLaunchKernelGGL((rt::k_build_streams<float>), grid, dim3(256), 0, s->cost_stream, d_raw, (unsigned)n, eye, false, ep, es);
         // primary terms from the eye spheres, shadow terms from the TIGHT stream (its exact records are the ones the shadow walk fetches)
         hipLaunchKernelGGL(rt::k_build_fstreams, grid, dim3(256), 0, s->cost_stream, ep, static_cast<const rt::Node<float> *>(s->d_tshad), (unsigned)total, false, s->fc,
-                           reinterpret_cast<rt::FNode *>(d), reinterpret_cast<rt::FNodeS *>(d + 32 * total), static_cast<uint32_t *>(nullptr), d_ovr, (unsigned)n);
+                           reinterpret_cast<rt::FNode *>(d), reinterpret_cast<rt::FNodeS *>(d + 32 * total), static_cast<uint32_t *>(nullptr), d_ovr, (unsigned)n, lean);
         e = hipGetLastError();
         const hipError_t se = hipStreamSynchronize(s->cost_stream);
         if (e == hipSuccess) e = se;
     }
     if (e != hipSuccess) { (void)hipGetLastError(); (void)hipFree(d); return false; }
     s->d_walk = d; s->d_wxprim = d; s->d_wxshad = d + 32 * total;
-    s->n_walk_primary = wr.n_primary; s->n_walk_shadow = wr.n_shadow;
+    s->n_walk_primary = wr.n_primary; s->n_walk_shadow = wr.n_shadow; s->walk_lean = lean;
     s->walk_ready.store(true, std::memory_order_release);
     return true;
 }

@@ -71,7 +71,10 @@ typedef enum rt_debug_key {
                                     shadow walk), for launches that walk the tight streams: 0 never, 1 the library's rule, 2 wherever a scene has them -- 1 and 2
                                     make them at the launch if the scene's worker has not yet; default: the rule, from the launch on that finds them made.
                                     All must render the same bytes */
-    RT_DEBUG_KEYS = 27
+    RT_DEBUG_LEAN_BOUNDS = 27,   /* the lean BOUND step of the per-walk primary stream (rt_filter_bounds.hpp lean_radius: a BOUND with an eye sphere carries Rq and is
+                                    decided from the filter's b' alone), read when a scene's per-walk streams are made: 0 never -- the build kernel writes no flag --,
+                                    1 the library's rule, 2 wherever a record exists; default: the rule, which is every eye sphere.  All must render the same bytes */
+    RT_DEBUG_KEYS = 28
 } rt_debug_key;
 
 /* value < 0 restores the default. */
@@ -116,6 +119,10 @@ rt_status rt_debug_tight_bounds(const float *dfs_items, uint32_t n_items, const 
  * mean cone half-angle and disc radius of the records relative to the tight ball's. */
 rt_status rt_debug_walk_bounds(const float *dfs_items, uint32_t n_items, const float *light_unit, const float *eye, const float *bounds, const rt_range *ranges,
                                uint32_t n_bounds, int slack, float *records_out, double frame_out[20]);
+/* ... and for the lean BOUND step: the same records (slack 1) and rq_out[n_bounds], Rq of every bound with an eye sphere (0: none -- such a bound keeps
+ * the reference's test).  The un-fused filtered f32 primary loop enters such a bound iff b' >= T' and b' - Rq < hit.distance. */
+rt_status rt_debug_lean_bounds(const float *dfs_items, uint32_t n_items, const float *light_unit, const float *eye, const float *bounds, const rt_range *ranges,
+                               uint32_t n_bounds, float *records_out, float *rq_out);
 
 /* Test infrastructure for the multi-GPU paths.  rt_debug_gang_layout: the sharding arithmetic of rt_gang_render_frame(s) without a
  * device -- for bucket i its device (i % n_devices) and its first pixel inside that device's tile-major shard; per device the pixels

@@ -67,15 +67,32 @@ RT_BOUNDS_FN float primary_threshold(float vv_f, float rr_f)
     return next_below(tf);
 }
 
+// Rq of an eye sphere X with the stored terms vv = dot(v', v'), rr (both as the reference rounds them): the reference's distance to X is
+// d_X >= b' - Rq for every ray on which it is finite, b' = fma(v'z, dz, fma(v'y, dy, v'x dx)) as the filter forms it (NOTES.md "Lean bound
+// steps").  ES2 = A S^2 of rt_tight.hpp: E(rr) = ES2 + 2 eps rr bounds the f32 discriminant's error, so disc^ <= rr + E(rr) (b^2 - vv <= 0 up
+// to those roundings), s^ = RN(sqrt(disc^)) <= sqrt(rr + E(rr)) (1 + eps); b^ is within 4 eps |v'| of b', and the rounding of b^ - s^ costs
+// eps (|b^| + s^) <= eps (1.01 |v'| + s^).  Rounded up twice.  +inf where nothing is known (the lean step then culls nobody).
+RT_BOUNDS_FN float lean_radius(float vv_f, float rr_f, double ES2)
+{
+    const double eps = 0x1p-24, vv = vv_f, rr = rr_f;
+    if (!(vv < 1e300) || !(rr < 1e300) || !(ES2 < 1e300)) return __builtin_huge_valf();
+    const double q = __builtin_sqrt(rr * (1.0 + 2.0 * eps) + ES2) * (1.0 + 4.0 * eps) + 8.0 * eps * __builtin_sqrt(vv) + 1e-44;
+    float qf = (float)q;
+    if ((double)qf < q) qf = next_above(qf);
+    return qf < __builtin_huge_valf() ? next_above(qf) : qf;
+}
+
 // What a BOUND node of the per-walk streams carries instead of the values derived from its sphere (rt_tight.hpp build_walk makes them on the
 // host, k_build_fstreams applies them): the primary record takes max(T of its sphere, tp); the shadow record takes the disc whole.
 struct WalkOverride {
     float tp;                       // kWalkPrimary: T', the cone that holds every item's cap, about the node's own v
     float w1, w2, cl, r2o, r2i;     // kWalkShadow: the light disc (centre in the plane across the light, front along it, outer / inner bound)
     uint32_t flags;
-    uint32_t pad;
+    float rq;                       // kWalkPrimary: Rq of the eye sphere (lean_radius): a lane with b' - Rq >= hit.distance has nothing to find below
 };
 constexpr uint32_t kWalkPrimary = 1u, kWalkShadow = 2u;
+// FNode::tag of a BOUND of the per-walk primary stream that is decided by b' alone (a4 = Rq instead of rr): neither bit 31 (ITEM / END) nor bit 30 (END)
+constexpr uint32_t kTagLeanBound = 0x20000000u;
 static_assert(sizeof(WalkOverride) == 32, "one 32-byte record per node, like the streams");
 
 }  // namespace rt_bounds

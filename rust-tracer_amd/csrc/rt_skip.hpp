@@ -64,6 +64,7 @@ template <typename T> struct RawNode {
 //            same for the group's own sphere (compacted stream).  Sign bit of R2o: ITEM (or END); sign bit of R2o_own: END.
 // primary tag: 0 for a BOUND (compacted stream: rr of the group's own sphere, a non-negative float), item | kNodeItem for an ITEM,
 // kNodeItem | kNodeEnd for END.  The own sphere's item index of a compacted BOUND lives in the stream's own_item table.
+// Per-walk primary stream only: rt_bounds::kTagLeanBound for a BOUND with an eye sphere, whose a4 is Rq, not rr (k_build_fstreams, `lean`).
 struct alignas(32) FNode {
     float a0, a1, a2, a3, a4, f5;
     uint32_t skip_off, tag;
@@ -208,10 +209,12 @@ __global__ void k_build_fstream64(const Node<double> *__restrict__ prim, const N
 // Filtered copies of a pair of Node<float> streams (plain or compacted; END nodes included).
 __global__ void k_build_fstreams(const Node<float> *__restrict__ prim, const Node<float> *__restrict__ shad, unsigned n_total, bool compacted,
                                  FilterConsts fc, FNode *__restrict__ xprim, FNodeS *__restrict__ xshad, uint32_t *__restrict__ own_item,
-                                 const rt_bounds::WalkOverride *__restrict__ ovr = nullptr, unsigned n_ovr = 0)
+                                 const rt_bounds::WalkOverride *__restrict__ ovr = nullptr, unsigned n_ovr = 0, bool lean = false)
 {
     // ovr (optional; the per-walk streams of rt_tight.hpp build_walk): records of the first n_ovr nodes -- the END nodes carry none -- that
     // replace what a BOUND's filter terms would be derived from its sphere; `prim` is then the stream of the eye spheres, `shad` the tight one
+    // lean (with ovr, plain streams): a BOUND with an eye sphere carries Rq in the place of rr and kTagLeanBound -- the un-fused filtered f32
+    // primary loop decides it from the filter's b' alone (rt_skip_rot.hpp, lean_bound); nothing else may walk such a stream
     const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_total) return;
     const Node<float> p = prim[i], s = shad[i];
@@ -235,6 +238,7 @@ __global__ void k_build_fstreams(const Node<float> *__restrict__ prim, const Nod
     if (ovr && i < n_ovr && !end && !item) {
         const rt_bounds::WalkOverride o = ovr[i];
         if ((o.flags & rt_bounds::kWalkPrimary) != 0u && fp.f5 > -__builtin_huge_valf() && o.tp > fp.f5) fp.f5 = o.tp;
+        if (lean && !compacted && (o.flags & rt_bounds::kWalkPrimary) != 0u && fp.f5 > -__builtin_huge_valf() && o.rq > 0.0f) { fp.a4 = o.rq; fp.tag = rt_bounds::kTagLeanBound; }
         if ((o.flags & rt_bounds::kWalkShadow) != 0u) { fs.w1 = o.w1; fs.w2 = o.w2; fs.cl = o.cl; fs.r2o = o.r2o; fs.r2i = o.r2i; }
     }
     xprim[i] = fp;
@@ -346,6 +350,13 @@ __device__ __forceinline__ void shadow_filter_origin64(const FilterConsts &fc, d
 __device__ __forceinline__ bool primary_filter_pass(const FNode &f, float dx, float dy, float dz)
 {
     return f.f5 <= __builtin_fmaf(f.a2, dz, __builtin_fmaf(f.a1, dy, f.a0 * dx));
+}
+// The lean BOUND step (a node tagged kTagLeanBound: a4 = Rq), as the un-fused filtered f32 primary loop evaluates it behind the filter
+// (tools/gen_skip_asm.py lean_bound; NOTES.md "Lean bound steps"): the lane enters iff b' - Rq < hit.distance.  The counting launches hold
+// every ITEM test that counts against it: an item that wins has d_I >= b'_X - Rq_X for every enclosing lean BOUND X.
+__device__ __forceinline__ bool lean_bound_enters(const FNode &f, float dx, float dy, float dz, float best)
+{
+    return __builtin_fmaf(f.a2, dz, __builtin_fmaf(f.a1, dy, f.a0 * dx)) - f.a4 < best;
 }
 // The root-free decision of a primary BOUND step, as the filtered loops evaluate it (tools/gen_skip_asm.py bound_shortcut): for a
 // node the eye is clearly outside of (FNode::f5 > -inf) and a lane with disc >= 0 -- 0: the lane does not enter, 2: it enters, 1: the root decides.
@@ -661,7 +672,8 @@ __device__ __forceinline__ void render_skip_body(const BlockDesc *__restrict__ o
                                 // the per-walk record as the filtered loops take it: the filter with T' first, then the reference's test on the eye sphere
                                 const FNode wn = wprim[i];
                                 bool quiet = !primary_filter_pass(wn, dir.x, dir.y, dir.z);
-                                if (!quiet) {
+                                if (!quiet && wn.tag == rt_bounds::kTagLeanBound) quiet = !lean_bound_enters(wn, dir.x, dir.y, dir.z, (float)best);
+                                else if (!quiet) {
                                     const T wb = (wn.a0 * dir.x + wn.a1 * dir.y) + wn.a2 * dir.z;
                                     const T wdisc = (wb * wb - wn.a3) + wn.a4;
                                     T wd = inf<T>();

@@ -170,6 +170,8 @@ inline void build(const float *sph, const uint32_t *skip, uint32_t n, const Para
 //   an EYE SPHERE {c', r'}: c' on the axis of the narrowest cap (seen from the eye) that holds every item's cap -- an item's cap is what its
 //       own primary_threshold admits --, r' what rules (a) and (c) above need, |c' - m0| <= rc; the exact test of the primary walk runs on it;
 //   T': finite distance_from_ray for any item of the subtree implies  fma(v'z, dz, fma(v'y, dy, v'x dx)) >= T'  (v' = fl(c' - eye));
+//   Rq: that fma chain b' minus Rq is no larger than the reference's distance to the eye sphere, hence to any item of the subtree
+//       (rt_filter_bounds.hpp lean_radius): the lean BOUND step of the primary loop enters iff b' >= T' and b' - Rq < hit.distance;
 //   a LIGHT DISC {w1', w2', R2o'}: P2' > R2o' as the loops form it implies P2_I > R2o_I for every item, which implies that the reference says MISS;
 //   its FRONT cl': fl(cl' - ol) <= -a0 implies that every item fulfils its own behind-the-origin test (the loops' second chance reads cl);
 //   R2i': the disc of that radius about (w1', w2') lies inside the tight ball's inner disc (-1: no room).
@@ -376,6 +378,10 @@ inline void build_walk(const float *sph, const uint32_t *skip, uint32_t n, const
             if (!(cos_new > cos_ball) || !(cos_new < 1.0)) break;      // keep it only where the cone is narrower than the tight ball's
             out.eye_sphere[4 * i] = cf[0]; out.eye_sphere[4 * i + 1] = cf[1]; out.eye_sphere[4 * i + 2] = cf[2]; out.eye_sphere[4 * i + 3] = rf;
             o.tp = tp; o.flags |= rt_bounds::kWalkPrimary;
+            {   // Rq from vv and rr as k_build_streams forms them for this sphere (the lean BOUND step, NOTES.md "Lean bound steps")
+                const float vx = cf[0] - wp.eye[0], vy = cf[1] - wp.eye[1], vz = cf[2] - wp.eye[2];
+                o.rq = rt_bounds::lean_radius((vx * vx + vy * vy) + vz * vz, rf * rf, AS2);
+            }
             ++out.n_primary;
             cone_sum += std::acos(cos_new) / std::acos(std::min(1.0, std::max(cos_ball, 0.0)));
             break;

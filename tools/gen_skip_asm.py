@@ -75,6 +75,7 @@ class Prec:
     filt = False                     # a conservative filter in front of every test (F32F)
     shortcut = False                 # the primary BOUND step's root-free decision (F32F.bound_shortcut)
     sure_enter = False               # the f64 primary BOUND step that needs no exact record at all (F64F.sure_enter_path)
+    lean_bounds = False              # the un-fused primary BOUND step settled from the filter's b' alone where the node says so (F32F.lean_bound)
     fn_suffix = ""                   # of the functions' names, between "_filt" and "_fused"
     flavour = None                   # where the loops leave registers undeclared: their name in asm_gen.UNDECLARED ...
     reserved = ()                    # ... and those registers
@@ -356,6 +357,7 @@ class F32F(TwoSidedShadow, F32):
     does it form the reference's own discriminant, operation for operation, exactly as the unfiltered loops do."""
     filt = True
     shortcut = True
+    lean_bounds = True
     sbank = Prec.bank
 
     def item(self, b):
@@ -420,6 +422,24 @@ class F32F(TwoSidedShadow, F32):
         a.op("s_or_b64 %s, %s, %s" % (self.M58, self.M58, self.M56), "settled lanes")
         a.op("s_andn2_b64 %s, vcc, %s" % (self.M58, self.M58), "candidates nothing above settles")
         a.op("s_cbranch_scc1 %s" % lab("bexact"), "(vcc lost only lanes with b <= 0, which the root path rejects as well)")
+        a.op("s_and_b64 vcc, vcc, %s" % self.M56, "go")
+        a.op("s_branch %s" % lab("bdecided"))
+
+    LEAN_TAG = "0x20000000"                          # rt_filter_bounds.hpp kTagLeanBound: the whole tag word of a lean BOUND
+
+    def lean_test(self, a, c, lab):
+        """Some lane passed the filter: is this a BOUND of a per-walk stream that b' alone decides?  One scalar compare of the whole tag word --
+        an ITEM's has bit 31, any other BOUND's is 0."""
+        a.op("s_cmp_eq_u32 %s, %s" % (self.item(c), self.LEAN_TAG), "a BOUND with an eye sphere: a4 is Rq, and b' decides (NOTES.md, lean bound steps)")
+        a.op("s_cbranch_scc1 %s" % lab("lean"))
+
+    def lean_bound(self, a, c, lab):
+        """The lean BOUND step, vcc = the lanes inside the cone (b' >= T', %[disc] still holds b'): a lane enters iff it is awake and
+        b' - Rq < hit.distance -- no item below can be nearer than b' - Rq (rt_filter_bounds.hpp lean_radius), and entering is always harmless."""
+        a.label(lab("lean"))
+        a.op("v_subrev_f32_e32 %%[t0], %s, %%[disc]" % self.fld(c, 4), "b' - Rq: no item of the subtree is nearer")
+        a.op("s_and_b64 vcc, vcc, %s" % self.ACT, "live lanes inside the cone")
+        a.op("v_cmp_lt_f32_e64 %s, %%[t0], %%[best]" % self.M56, "b' - Rq < hit.distance")
         a.op("s_and_b64 vcc, vcc, %s" % self.M56, "go")
         a.op("s_branch %s" % lab("bdecided"))
 
@@ -711,6 +731,8 @@ def primary_copy(P, name, fused):
     # ---------------- somebody's line meets the sphere ----------------
     k.label(lab("hit"))
     hit_entry(k, P)
+    if P.lean_bounds and not fused:
+        P.lean_test(k, c, lab)
     if P.sure_enter and P.filt:
         P.sure_enter_path(k, c, n, name, lab)
     exact_after_filter(k, P, c, lab, "primary")
@@ -750,6 +772,8 @@ def primary_copy(P, name, fused):
     P.item_update(k, c)
     k.op("s_branch %s" % lab("skip"), "an ITEM's `skip` is the node behind it")
     P.tiny(k, lab("itiny"), lab("irooted"))
+    if P.lean_bounds and not fused:
+        P.lean_bound(k, c, lab)
     return m, k
 
 

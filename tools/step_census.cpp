@@ -15,7 +15,11 @@
 // test of the TIGHT ball in between.  A step is quiet when no live lane passes the node's filter.  The hash must equal the other runs'.
 // Both print the steps of the heaviest waves and the longest single pixel.
 //
-//   g++ -O2 -ffp-contract=off -o /tmp/step_census tools/step_census.cpp && /tmp/step_census [w h [level]] [--tight | --walk]
+// --lean: the --walk records with the lean BOUND step (NOTES.md "Lean bound steps"): a BOUND with an eye sphere is decided by the filter's b'
+// and the library's own Rq (rt_filter_bounds.hpp lean_radius) -- a lane enters iff b' >= T' and b' - Rq < hit.distance --, every other node as
+// under --walk.  Prints the split of the candidate BOUND steps and complains on stderr if a lane sleeps at an ITEM the exact test makes a winner.
+//
+//   g++ -O2 -ffp-contract=off -o /tmp/step_census tools/step_census.cpp && /tmp/step_census [w h [level]] [--tight | --walk | --lean]
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -32,7 +36,7 @@ static inline float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; 
 static inline V3 normalized(V3 a) { float l = sqrtf(dot(a, a)); return mulf(a, 1.0f / l); }
 struct Node { V3 c; float r; uint32_t skip; int item; };
 // --walk: what the filter streams carry for a node (k_build_fstreams with the records of build_walk)
-struct Filt { V3 pc; float pr, f5, w1, w2, cl, r2o, r2i; };
+struct Filt { V3 pc; float pr, f5, w1, w2, cl, r2o, r2i, rq; };      // rq > 0: a lean BOUND (--lean)
 static std::vector<Filt> filt;
 static std::vector<Node> nodes;
 static void pyramid(unsigned level, V3 p, float r)
@@ -53,9 +57,9 @@ static inline float dist(V3 c, float r, V3 o, V3 d, float *disc_out)
 }
 int main(int argc, char **argv)
 {
-    bool tight = false, walk = false;
+    bool tight = false, walk = false, lean = false;
     std::vector<char *> pos;
-    for (int a = 1; a < argc; ++a) { if (!strcmp(argv[a], "--tight")) tight = true; else if (!strcmp(argv[a], "--walk")) tight = walk = true; else pos.push_back(argv[a]); }
+    for (int a = 1; a < argc; ++a) { if (!strcmp(argv[a], "--tight")) tight = true; else if (!strcmp(argv[a], "--walk")) tight = walk = true; else if (!strcmp(argv[a], "--lean")) tight = walk = lean = true; else pos.push_back(argv[a]); }
     float fq_m0[3] = { 0, 0, 0 }, fq_e1[3] = { 0, 0, 0 }, fq_e2[3] = { 0, 0, 0 }, fq_l[3] = { 0, 0, 0 }, fq_a0 = 0, fq_k1 = 0, fq_kc = 0;
     const unsigned W = pos.size() > 0 ? atoi(pos[0]) : 1920, H = pos.size() > 1 ? atoi(pos[1]) : 1080, level = pos.size() > 2 ? atoi(pos[2]) : 8;
     pyramid(level, { 0, -1, 0 }, 1.0f);
@@ -115,6 +119,7 @@ int main(int argc, char **argv)
                 const V3 v = sub(f.pc, eye);
                 f.f5 = rt_bounds::primary_threshold((v.x * v.x + v.y * v.y) + v.z * v.z, f.pr * f.pr);
                 if ((o.flags & rt_bounds::kWalkPrimary) && f.f5 > -INFINITY && o.tp > f.f5) f.f5 = o.tp;
+                f.rq = (lean && !nodes[i].item && (o.flags & rt_bounds::kWalkPrimary) && f.f5 > -INFINITY && o.rq > 0.0f) ? o.rq : 0.0f;      // (k_build_fstreams, `lean`)
                 const double cx = (double)nodes[i].c.x - (double)fq_m0[0], cy = (double)nodes[i].c.y - (double)fq_m0[1], cz = (double)nodes[i].c.z - (double)fq_m0[2];
                 f.w1 = (float)((cx * (double)fq_e1[0] + cy * (double)fq_e1[1]) + cz * (double)fq_e1[2]);
                 f.w2 = (float)((cx * (double)fq_e2[0] + cy * (double)fq_e2[1]) + cz * (double)fq_e2[2]);
@@ -128,6 +133,7 @@ int main(int argc, char **argv)
     unsigned longest_px = 0;
     uint64_t hash = 1469598103934665603ull;
     uint64_t pQ = 0, pB0 = 0, pB1 = 0, pB2 = 0, pI = 0, pLeafQ = 0, sQ = 0, sH = 0, sEnt = 0, waves = 0, swaves = 0;
+    uint64_t pL0 = 0, pL1 = 0, lean_wrong = 0;   // --lean: candidate steps at lean BOUNDs nobody enters / somebody enters; sleeping lanes the exact test makes winners
     uint64_t dec1 = 0, dec2 = 0, dec1_b0 = 0;    // B0 steps in which every candidate lane has b >= best (root-free "no" possible) 
     for (unsigned y0 = 0; y0 < H; y0 += 8) for (unsigned x0 = 0; x0 < W; x0 += 8) {
         V3 dir[64]; bool in[64]; float best[64]; int bi[64]; uint32_t res[64]; unsigned awake[64]; uint32_t wsteps = 0;
@@ -139,13 +145,25 @@ int main(int argc, char **argv)
             bool cand = false, enter = false, undecided = false, undecided2 = false;
             ++wsteps;
             for (unsigned l = 0; l < 64; ++l) {
+                if (lean && nd.item && in[l] && i < res[l]) {      // asleep: the exact test must not make this item a winner
+                    const Filt &f = filt[i]; const V3 v = sub(f.pc, eye); float xdisc;
+                    if (f.f5 <= fmaf(v.z, dir[l].z, fmaf(v.y, dir[l].y, v.x * dir[l].x)) && !(dist(f.pc, f.pr, eye, dir[l], &xdisc) >= best[l])) {
+                        if (!lean_wrong++) fprintf(stderr, "LEAN SLEEP WRONG: node %zu, pixel %u %u\n", i, x0 + l % 8, y0 + l / 8);
+                    }
+                }
                 if (i < res[l]) continue;
                 ++awake[l];
                 if (walk) {
                     // the filter first (rt_skip.hpp primary_filter_pass), then the reference's test on the sphere the stream carries
                     const Filt &f = filt[i];
                     const V3 v = sub(f.pc, eye);
-                    const bool pass = f.f5 <= fmaf(v.z, dir[l].z, fmaf(v.y, dir[l].y, v.x * dir[l].x));
+                    const float bp = fmaf(v.z, dir[l].z, fmaf(v.y, dir[l].y, v.x * dir[l].x));
+                    const bool pass = f.f5 <= bp;
+                    if (f.rq > 0.0f) {                             // the lean BOUND step (rt_skip.hpp lean_bound_enters)
+                        if (pass) cand = true;
+                        if (pass && bp - f.rq < best[l]) enter = true; else res[l] = nd.skip;
+                        continue;
+                    }
                     float wdisc; const float wd = pass ? dist(f.pc, f.pr, eye, dir[l], &wdisc) : INFINITY;
                     if (pass) cand = true;
                     if (!nd.item) { if (!pass || wd >= best[l]) res[l] = nd.skip; else enter = true; }
@@ -173,6 +191,7 @@ int main(int argc, char **argv)
             }
             if (nd.item) { if (cand) ++pI; else ++pLeafQ; ++i; continue; }
             if (!cand) { ++pQ; i = nd.skip; continue; }
+            if (lean && filt[i].rq > 0.0f) { if (enter) ++pL1; else ++pL0; }
             if (!undecided) ++dec1; if (!undecided2) ++dec2;
             if (!enter) { ++pB0; if (!undecided) ++dec1_b0; i = nd.skip; continue; }
             if (tight) { ++pB1; ++i; continue; }      // un-fused: the own sphere is the ITEM step behind the BOUND
@@ -250,6 +269,12 @@ int main(int argc, char **argv)
     const double valu = 5.0 * (pQ + pLeafQ) + 25.0 * pB0 + 28.0 * pB1 + 42.0 * pB2 + 27.0 * pI;
     printf("primary VALU estimate: %.2f M (quiet %.2f, B0 %.2f, B1 %.2f, B2 %.2f, I %.2f)\n", valu / 1e6, 5.0 * (pQ + pLeafQ) / 1e6, 25.0 * pB0 / 1e6, 28.0 * pB1 / 1e6, 42.0 * pB2 / 1e6, 27.0 * pI / 1e6);
     printf("BOUND-cand steps decided by A/N alone: %llu (of which no-enter %llu), by A/N/G: %llu, of %llu\n", (unsigned long long)dec1, (unsigned long long)dec1_b0, (unsigned long long)dec2, (unsigned long long)(pB0 + pB1 + pB2));
+    if (lean) {
+        printf("lean: candidate BOUND steps %llu -- lean, nobody enters %llu; lean, entered %llu; the reference's test (no eye sphere) %llu; sleeping lanes the exact test makes winners %llu\n",
+               (unsigned long long)(pB0 + pB1 + pB2), (unsigned long long)pL0, (unsigned long long)pL1, (unsigned long long)(pB0 + pB1 + pB2 - pL0 - pL1), (unsigned long long)lean_wrong);
+        const double lv = valu - 20.0 * pL0 - 23.0 * pL1;
+        printf("lean: primary VALU estimate %.2f M (a lean candidate BOUND step: 6 -- the quiet step's four, who is awake, b' - Rq and its compare)\n", lv / 1e6);
+    }
     printf("steps: primary %llu, shadow %llu; hash of hit items and shadow verdicts %016llx\n", (unsigned long long)(pQ + pLeafQ + pB0 + pB1 + pB2 + pI), (unsigned long long)(sQ + sH), (unsigned long long)hash);
     // the shadow walk here always takes every node as a step of its own (the UN-FUSED walk); today's fused walk over the given bounds saves one per entered group
     if (!tight) printf("shadow steps of the FUSED walk (an entered group's own sphere tested in its BOUND step): %llu\n", (unsigned long long)(sQ + sH - sEnt));
