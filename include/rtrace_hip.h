@@ -896,6 +896,49 @@ rt_status rt_first_contacts_device(rt_scene *scene, rt_sweep mode, const void *q
                                    const int32_t *exclude, const uint32_t *order, void *time_out, int32_t *item_out, void *normal_out, rt_stats *stats,
                                    void *hip_stream);
 
+/* ---- contact islands (additive to ABI 5): the connected groups of touching spheres ----
+ * A caller that steps spheres wants one thing straight behind the pair list: which spheres belong together -- what it puts to sleep,
+ * solves on its own, merges into a cluster or counts as one floating piece.  These entries give that without the pair list ever
+ * existing: one int32 per sphere.
+ *   E is the set of pairs rt_scene_contacts lists for this scene and `margin` -- the walk's pairs, lower slot as the query, its behaviour
+ * on bounds that do not enclose included.  G is the graph on the LIVE item slots with the edges E; a slot is live exactly when the
+ * contacts walk gives it a query: it has a node in the stream and its rr > 0.
+ *   label_out (int32[n_items], required): label[i] = the smallest slot of i's connected component of G; -1 for a slot that is not live;
+ *     a live slot without a contact is an island of one, label[i] = i.
+ *   index_out (int32[n_items] or NULL): index[i] = the number of islands whose label is below label[i] -- dense, 0 .. n_islands - 1, in
+ *     ascending label order; -1 where label[i] is -1.
+ *   size_out (uint32[n_items] or NULL): size[i] = the slots of i's island; 0 where label[i] is -1.
+ *   n_islands_out (uint64 or NULL): the number of i with label[i] == i.
+ * The IMPACT form is the same with E the pairs rt_scene_impacts lists for `disp`: the groups a continuous-collision step has to resolve
+ * together.
+ *   The walk is the pair entries' own, test for test; where it would list a pair it unites the two slots in a union-find in which the
+ * lower root always wins (a root changes only by a compare-and-swap from itself, so the root of every component ends as its minimum).
+ * The labels are therefore one fixed function of the edge set, whatever order the lanes unite in: the same bytes every time, like every
+ * query here.  stats (may be NULL) is exactly what the counting pass of rt_scene_contacts, or rt_scene_impacts, reports for the same
+ * arguments: primary = live slots, hits = slots that are the lower slot of a pair, sphere_tests / bound_tests / tests_executed, every
+ * other counter 0; asking for it runs the counting flavour (same bytes).
+ *   The forest -- two uint32 per item slot -- is made by the first islands call and freed with the scene.  An islands call takes its
+ * turn with the contacts and impacts calls of its scene: it uses their counts and offsets, and the impact form their motion table. */
+/* Host memory.  RT_ERR_INVALID_ARGUMENT before the device is touched for a NULL scene or label_out, a NaN margin, a misaligned buffer
+ * (label_out, index_out, size_out 4 bytes, n_islands_out 8 bytes) and a buffer in device memory.  Pinned memory is used in place,
+ * pageable memory goes through the call's device workspace.  Returns when the results are in place.  The call is a READ in the sense of
+ * ORDER above, on static, dynamic, live and flat scenes alike. */
+rt_status rt_scene_islands(rt_scene *scene, double margin, int32_t *label_out, int32_t *index_out, uint32_t *size_out, uint64_t *n_islands_out,
+                           rt_stats *stats);
+/* The same over DEVICE memory (n_islands_out too), enqueued on `hip_stream` without a host synchronisation: only pointers and alignment
+ * are checked.  A call goes behind the contacts, impacts or islands call before it, whichever stream that was on.  stats != NULL:
+ * filled after an internal synchronisation of hip_stream. */
+rt_status rt_scene_islands_device(rt_scene *scene, double margin, int32_t *label_out, int32_t *index_out, uint32_t *size_out, uint64_t *n_islands_out,
+                                  rt_stats *stats, void *hip_stream);
+/* The impact form, host memory: disp is REAL[3 n_items] exactly as rt_scene_impacts takes it, and is refused as there -- NULL,
+ * misaligned, a component that is not finite or beyond +-1e15 -- next to what rt_scene_islands refuses. */
+rt_status rt_scene_impact_islands(rt_scene *scene, const void *disp, int32_t *label_out, int32_t *index_out, uint32_t *size_out, uint64_t *n_islands_out,
+                                  rt_stats *stats);
+/* The impact form over DEVICE memory (disp too), as rt_scene_islands_device: displacements outside the host entry's domain give
+ * unspecified labels, never a fault. */
+rt_status rt_scene_impact_islands_device(rt_scene *scene, const void *disp, int32_t *label_out, int32_t *index_out, uint32_t *size_out,
+                                         uint64_t *n_islands_out, rt_stats *stats, void *hip_stream);
+
 /* Bytes rt_render_tiles writes for this tile list (4 * total area), or 0 on an invalid list. */
 uint64_t rt_tiles_rgba_bytes(const rt_region *tiles, uint32_t n_tiles);
 

@@ -44,7 +44,8 @@ SYMBOLS = ("rt_abi_version", "rt_build_hierarchy", "rt_device_count", "rt_scene_
            "rt_near_spheres", "rt_near_spheres_device", "rt_sweep_spheres", "rt_sweep_spheres_device",
            "rt_scene_contacts", "rt_scene_contacts_device", "rt_overlap_spheres", "rt_overlap_spheres_device",
            "rt_scene_impacts", "rt_scene_impacts_device", "rt_swept_overlaps", "rt_swept_overlaps_device",
-           "rt_first_contacts", "rt_first_contacts_device")
+           "rt_first_contacts", "rt_first_contacts_device",
+           "rt_scene_islands", "rt_scene_islands_device", "rt_scene_impact_islands", "rt_scene_impact_islands_device")
 # csrc/rt_debug.h: only in the -DRT_TEST_HOOKS build
 DEBUG_SYMBOLS = ("rt_debug_set", "rt_debug_count", "rt_debug_wave_trace", "rt_debug_flat_filter_check", "rt_debug_gang_layout", "rt_debug_rccl_library",
                  "rt_debug_shard_costs", "rt_debug_tight_bounds", "rt_debug_cost_map", "rt_debug_walk_bounds", "rt_debug_lean_bounds")
@@ -189,6 +190,11 @@ lib.rt_swept_overlaps_device.argtypes = lib.rt_swept_overlaps.argtypes + [C.c_vo
 lib.rt_first_contacts.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.POINTER(Stats)]
 lib.rt_first_contacts_device.argtypes = lib.rt_first_contacts.argtypes + [C.c_void_p]
+# contact islands: (scene, margin -- the impact form: disp --, label_out, index_out or NULL, size_out or NULL, n_islands_out or NULL, stats[, stream])
+lib.rt_scene_islands.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+lib.rt_scene_islands_device.argtypes = lib.rt_scene_islands.argtypes + [C.c_void_p]
+lib.rt_scene_impact_islands.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+lib.rt_scene_impact_islands_device.argtypes = lib.rt_scene_impact_islands.argtypes + [C.c_void_p]
 lib.rt_tiles_rgba_bytes.restype = C.c_uint64
 lib.rt_tiles_rgba_bytes.argtypes = [C.c_void_p, C.c_uint32]
 lib.rt_strerror.restype = C.c_char_p

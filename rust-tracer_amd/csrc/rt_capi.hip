@@ -23,6 +23,7 @@
 #include "rt_contacts.hpp"
 #include "rt_overlap.hpp"
 #include "rt_impacts.hpp"
+#include "rt_islands.hpp"
 #include "rt_swept.hpp"
 #include "rt_first.hpp"
 #include "rt_order.hpp"
@@ -386,6 +387,9 @@ struct rt_scene {
     // chunk maxima behind it, made by the first impacts call under contacts.mu; impacts calls share the contacts workspace
     void *d_impacts = nullptr;
     uint32_t impacts_cap = 0;          // nodes d_impacts has room for
+    // ---- contact islands (rt_scene_islands*, rt_scene_impact_islands*, rt_islands.hpp): the forest, parent[n_items] and size_root[n_items]
+    // behind it, made by the first islands call under contacts.mu; islands calls share the contacts workspace and the motion table
+    uint32_t *d_islands = nullptr;
     // ---- overlap lists (rt_overlap_spheres*, rt_overlap.hpp): the workspace of the two passes, for overlap.cap queries: made by the first call,
     // grown when a call brings more queries than any before it (behind overlap.ev)
     ListSpace overlap;

@@ -402,6 +402,7 @@ rt_status rt_scene_destroy(rt_scene *s)
     if (s->query_items_ev) (void)hipEventDestroy(s->query_items_ev);
     s->contacts.free_all();
     if (s->d_impacts) (void)hipFree(s->d_impacts);
+    if (s->d_islands) (void)hipFree(s->d_islands);
     s->overlap.free_all();
     if (s->d_swept) (void)hipFree(s->d_swept);
     if (s->d_cprim) (void)hipFree(s->d_cprim);
@@ -1287,6 +1288,66 @@ rt_status rt_scene_impacts(rt_scene *s, const void *disp, uint32_t capacity, int
         [&](const void *nodes, uint32_t n_nodes, hipStream_t stream) {
             return enqueue_impacts_fill(s, nodes, n_nodes, capacity, hs.dev<int32_t>(1), hs.dev(2), stream);
         });
+}
+
+// ---- contact islands: the connected groups of the contacts, or of the impacts of one step (rt_islands.hpp) ----
+
+// Both device entries: everything on the caller's stream, in the contacts workspace's turn; nothing is waited for unless stats is given.
+static rt_status islands_device(rt_scene *s, bool moving, double margin, const void *disp, int32_t *label_out, int32_t *index_out, uint32_t *size_out,
+                                uint64_t *n_islands_out, rt_stats *stats, void *hip_stream, const char *what)
+{
+    if (!islands_args_ok(s, moving, margin, disp, label_out, index_out, size_out, n_islands_out, what)) return RT_ERR_INVALID_ARGUMENT;
+    return device_list_query(
+        s, s->contacts, false, stats, static_cast<hipStream_t>(hip_stream),
+        [&](const void *nodes, uint32_t n_nodes, hipStream_t stream) { return islands_begin(s, moving, nodes, n_nodes, stream); },
+        [&](const void *nodes, uint32_t n_nodes, rt::Counters *counters, hipStream_t stream) {
+            return enqueue_islands(s, nodes, n_nodes, moving, margin, disp, label_out, index_out, size_out, n_islands_out, counters, stream);
+        },
+        [](const void *, uint32_t, hipStream_t) { return RT_OK; });      // (one pass: there is no list to fill)
+}
+
+// Both host entries: the list skeleton with nothing to fill -- the scan's total, read through the workspace's pinned word, is n_islands.
+static rt_status islands_host(rt_scene *s, bool moving, double margin, const void *disp, int32_t *label_out, int32_t *index_out, uint32_t *size_out,
+                              uint64_t *n_islands_out, rt_stats *stats, const char *what)
+{
+    if (!islands_args_ok(s, moving, margin, disp, label_out, index_out, size_out, n_islands_out, what)) return RT_ERR_INVALID_ARGUMENT;
+    const size_t esz = real_size(s), n = s->n_items;
+    HostStaging::Row rows[] = { { disp, 3 * esz * n, kStageIn }, { label_out, sizeof(int32_t) * n, kStageOut }, { index_out, sizeof(int32_t) * n, kStageOut },
+                                { size_out, sizeof(uint32_t) * n, kStageOut } };
+    HostStaging hs(rows);
+    if (rt_status pst = hs.plan(what, n_islands_out); pst != RT_OK) return pst;
+    if (moving && !impacts_disp_valid(s, disp, s->n_items, what)) return RT_ERR_INVALID_ARGUMENT;
+    uint64_t n_islands = 0;
+    return host_list_query(
+        s, s->contacts, hs, 0u, false, n_islands_out ? n_islands_out : &n_islands, stats,
+        [&](const void *nodes, uint32_t n_nodes, hipStream_t stream) { return islands_begin(s, moving, nodes, n_nodes, stream); },
+        [&](const void *nodes, uint32_t n_nodes, rt::Counters *counters, hipStream_t stream) {
+            return enqueue_islands(s, nodes, n_nodes, moving, margin, hs.dev(0), hs.dev<int32_t>(1), hs.dev<int32_t>(2), hs.dev<uint32_t>(3), s->contacts.d_total, counters,
+                                   stream);
+        },
+        [](const void *, uint32_t, hipStream_t) { return RT_OK; });
+}
+
+rt_status rt_scene_islands_device(rt_scene *s, double margin, int32_t *label_out, int32_t *index_out, uint32_t *size_out, uint64_t *n_islands_out, rt_stats *stats,
+                                  void *hip_stream)
+{
+    return islands_device(s, false, margin, nullptr, label_out, index_out, size_out, n_islands_out, stats, hip_stream, "rt_scene_islands_device");
+}
+
+rt_status rt_scene_islands(rt_scene *s, double margin, int32_t *label_out, int32_t *index_out, uint32_t *size_out, uint64_t *n_islands_out, rt_stats *stats)
+{
+    return islands_host(s, false, margin, nullptr, label_out, index_out, size_out, n_islands_out, stats, "rt_scene_islands");
+}
+
+rt_status rt_scene_impact_islands_device(rt_scene *s, const void *disp, int32_t *label_out, int32_t *index_out, uint32_t *size_out, uint64_t *n_islands_out,
+                                         rt_stats *stats, void *hip_stream)
+{
+    return islands_device(s, true, 0.0, disp, label_out, index_out, size_out, n_islands_out, stats, hip_stream, "rt_scene_impact_islands_device");
+}
+
+rt_status rt_scene_impact_islands(rt_scene *s, const void *disp, int32_t *label_out, int32_t *index_out, uint32_t *size_out, uint64_t *n_islands_out, rt_stats *stats)
+{
+    return islands_host(s, true, 0.0, disp, label_out, index_out, size_out, n_islands_out, stats, "rt_scene_impact_islands");
 }
 
 // ---- overlap lists: every sphere of the scene within a margin of each query sphere (rt_overlap.hpp) ----

@@ -1170,6 +1170,66 @@ rt_status enqueue_impacts_fill(const rt_scene *s, const void *nodes, uint32_t n_
     return enqueue_impacts_pass(s, nodes, n_nodes, nullptr, true, capacity, pairs, time, nullptr, stream);
 }
 
+// ---- contact islands (rt_scene_islands*, rt_scene_impact_islands*, rt_islands.hpp) ----
+
+// What the four islands entries check (device pointers are not dereferenced here).  moving: the impact form, which takes disp and no margin.
+bool islands_args_ok(const rt_scene *s, bool moving, double margin, const void *disp, const int32_t *label, const int32_t *index, const uint32_t *size,
+                     const uint64_t *n_islands, const char *what)
+{
+    if (!s || !label || (moving && !disp)) { snprintf(g_err, sizeof g_err, "%s: NULL scene%s or label_out", what, moving ? ", disp" : ""); return false; }
+    if (!moving && std::isnan(margin)) { snprintf(g_err, sizeof g_err, "%s: margin is NaN", what); return false; }
+    return aligned_ok(what, 4, { { label, "label_out" }, { index, "index_out" }, { size, "size_out" } }) && aligned_ok(what, 8, { { n_islands, "n_islands_out" } })
+           && aligned_ok(what, real_size(s), { { disp, "disp" } });
+}
+
+// contacts_begin (moving: impacts_begin), and the scene's forest: parent[n_items] and size_root[n_items] behind it, made by the first
+// islands call.  Under s->contacts.mu: islands calls take their turn with the contacts and impacts calls, whose counts and offsets they use.
+rt_status islands_begin(rt_scene *s, bool moving, const void *nodes, uint32_t n_nodes, hipStream_t stream)
+{
+    const rt_status st = moving ? impacts_begin(s, nodes, n_nodes, stream) : contacts_begin(s, nodes, n_nodes, stream);
+    if (st != RT_OK || s->d_islands) return st;
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_islands), 2 * sizeof(uint32_t) * (size_t)s->n_items));
+    return RT_OK;
+}
+
+// One islands call on `stream`: the forest's start, the hook walk (moving: behind its motion table), the labels, the scan of the roots --
+// whose total is n_islands -- and, where index or size is wanted, the last kernel.  counters != NULL runs the walk's counting flavour (same
+// labels).  label: required; index, size, n_islands: device pointers or NULL.
+rt_status enqueue_islands(const rt_scene *s, const void *nodes, uint32_t n_nodes, bool moving, double margin, const void *disp, int32_t *label, int32_t *index,
+                          uint32_t *size, uint64_t *n_islands, rt::Counters *counters, hipStream_t stream)
+{
+    const uint32_t n = s->n_items;
+    uint32_t *const parent = s->d_islands, *const size_root = size ? s->d_islands + n : nullptr;
+    const dim3 grid((n + 255) / 256), block(256);
+    const ListSpace &w = s->contacts;
+    const rt_status st = by_precision(s, [&](auto real) -> rt_status {
+        using T = decltype(real);
+        const rt::Node<T> *const stn = static_cast<const rt::Node<T> *>(nodes);
+        hipLaunchKernelGGL(rt::k_island_init, grid, block, 0, stream, parent, size_root, n);
+        rt::IslandArgs<T> a{ nullptr, contact_item_node(s), counters, moving ? T(0.0) : (T)margin, n_nodes, n };
+        const rt::Motion<T> *motion = nullptr;
+        if (moving) {
+            const ImpactsSpace<T> m = motion_table_space<T>(s->d_impacts, s->impacts_cap);
+            HIP_TRY(hipMemsetAsync(m.magnitude, 0, sizeof(T), stream));
+            if (const rt_status mt = enqueue_motion_table<T>(s, stn, n_nodes, static_cast<const T *>(disp), m, stream); mt != RT_OK) return mt;
+            motion = m.motion;
+            a.magnitude = m.magnitude;
+        }
+        with_flags([&](auto count, auto mov) { hipLaunchKernelGGL((rt::k_island_hook<T, count(), mov()>), query_grid(n), query_block(), 0, stream, a, stn, motion, parent); },
+                   counters != nullptr, moving);
+        hipLaunchKernelGGL(rt::k_island_labels<T>, grid, block, 0, stream, stn, contact_item_node(s), parent, n_nodes, n, label, w.counts, size_root);
+        HIP_TRY(hipGetLastError());
+        return RT_OK;
+    });
+    if (st != RT_OK) return st;
+    if (const rt_status sc = enqueue_list_scan(w, n, nullptr, n_islands, stream); sc != RT_OK) return sc;
+    if (index || size) {
+        hipLaunchKernelGGL(rt::k_island_finish, grid, block, 0, stream, label, w.offsets, size_root, n, index, size);
+        HIP_TRY(hipGetLastError());
+    }
+    return RT_OK;
+}
+
 // ---- overlap lists (rt_overlap_spheres*, rt_overlap.hpp) ----
 
 // What both overlap entries check (device pointers are not dereferenced here).

@@ -389,6 +389,58 @@ def pair_impacts(spheres, disp, i, j, inflate=None, scale=None):
     return np.where(solid, t, R(np.inf)).astype(R, copy=False)
 
 
+def pair_islands(pairs, n_items, live=None):
+    """The islands of the graph on `n_items` slots with the edges `pairs` (m x 2 integers, each a pair of slots; any order, repeats
+    allowed) -> (label int32[n_items], index int32[n_items], size uint32[n_items], n_islands), the definition of rt_scene_islands and
+    rt_scene_impact_islands restated in numpy (include/rtrace_hip.h states it): label[i] is the smallest slot of i's connected component,
+    index[i] the number of islands whose label is below label[i] (dense, 0 .. n_islands - 1, ascending in the label), size[i] the slots
+    of i's island, n_islands the number of i with label[i] == i.  live (bool or uint8 [n_items], or None: every slot): a slot that is
+    not live belongs to no island -- label -1, index -1, size 0 -- and must be in no pair.  A live slot in no pair is an island of one.
+    With the pairs of DeviceScene.contacts(margin), or of impacts(disp), and the scene's live slots this is what islands(margin), or
+    impact_islands(disp), returns."""
+    n = int(n_items)
+    if n < 0:
+        raise ValueError("n_items must not be negative")
+    p = np.asarray(pairs)
+    if p.size == 0:
+        p = np.zeros((0, 2), np.int64)
+    if p.dtype.kind not in "iu" or p.ndim != 2 or p.shape[1] != 2:
+        raise ValueError("pairs must be an (m, 2) integer array")
+    p = p.astype(np.int64)
+    if p.size and (int(p.min()) < 0 or int(p.max()) >= n):
+        raise ValueError("pairs must name slots 0 .. n_items - 1")
+    if live is None:
+        alive = np.ones(n, bool)
+    else:
+        alive = np.asarray(live)
+        if alive.dtype not in (np.uint8, np.bool_) or alive.shape != (n,):
+            raise ValueError("live must be None or an (n_items,) array of uint8 or bool")
+        alive = alive != 0
+    if not alive[p].all():
+        raise ValueError("a pair names a slot that is not live")
+    i, j = p[:, 0], p[:, 1]
+    parent = np.arange(n, dtype=np.int64)
+    while True:                                  # every tree is flat here: parent[x] is x's root, and a root is its tree's smallest slot
+        ri, rj = parent[i], parent[j]
+        lo, hi = np.minimum(ri, rj), np.maximum(ri, rj)
+        apart = lo != hi
+        if not apart.any():
+            break
+        np.minimum.at(parent, hi[apart], lo[apart])                          # the higher root goes below the lowest root it has an edge to
+        while True:
+            up = parent[parent]
+            if np.array_equal(up, parent):
+                break
+            parent = up
+    label = np.where(alive, parent, -1).astype(np.int32)
+    root = label == np.arange(n)
+    rank = np.cumsum(root) - 1
+    index = np.where(alive, rank[parent], -1).astype(np.int32)
+    members = np.bincount(parent[alive], minlength=n) if n else np.zeros(0, np.int64)
+    size = np.where(alive, members[parent], 0).astype(np.uint32)
+    return label, index, size, int(root.sum())
+
+
 def _swept_terms(queries, qdisp, spheres, disp, inflate, scale):
     """(t, v, w) of swept_times: REAL[n, m], REAL[n, m, 3], REAL[n, m, 3]."""
     qs, qd, s = np.asarray(queries), np.asarray(qdisp), np.asarray(spheres)
@@ -1370,6 +1422,52 @@ class DeviceScene:
         return self._list_query("rt_scene_impacts", self._side(disp), (disp,), (("disp", 3, _ITEMS, False),), None, None, capacity,
                                 (True, times), (((2,), np.int32), ((), "R")), offsets, stats, stream, "the step has %d impacts",
                                 lambda xs, n, ex, o: (xs[0],))
+
+    def _islands_query(self, entry, side, moving, disp, head, index, sizes, stats, stream):
+        """The body of islands and impact_islands: `entry` + side.suffix is called with the scene, head(disp pointer; moving: the impact
+        form, which takes one) and then label, index or NULL, size or NULL, n_islands, stats[, stream]; -> (label[, index][, size],
+        n_islands[, stats dict]).  The host side gives n_islands as an int; the device side waits for nothing: it is a 0-d int64 tensor."""
+        st = capi.Stats()
+        stp = C.byref(st) if stats else None
+        ptr = side.ptr
+        with side.scope(self, stream, (disp,)) as tail:
+            n_items = self.scene.items.shape[0]
+            d = side.real_rows(disp, "disp", 3, n_items) if moving else None
+            label = side.empty((n_items,), np.int32)
+            idx = side.empty((n_items,), np.int32) if index else None
+            size = side.empty((n_items,), np.uint32) if sizes else None
+            total, totp = side.total_cell()
+            rc = getattr(capi.lib, entry + side.suffix)(self._h, *head(ptr(d)), ptr(label), ptr(idx), ptr(size), totp, stp, *tail)
+        capi.check(rc, entry + side.suffix)
+        res = [x for x in (label, idx, size) if x is not None]
+        res.append(side.read_total(total) if side.trims else total)
+        if stats:
+            res.append(st.as_dict())
+        return tuple(res)
+
+    def islands(self, margin=0.0, index=False, sizes=False, stats=False, device=False, stream=None):
+        """rt_scene_islands / rt_scene_islands_device: the connected groups of the scene's contacts at `margin` -- the graph on the live
+        slots whose edges are the pairs contacts(margin) lists (pair_islands is the definition) -> (label[, index][, size],
+        n_islands[, stats dict]), without the pairs ever existing.  label: int32[n_items], the smallest slot of each slot's island, the
+        same bytes every time; -1 for a dead slot of a dynamic scene; a live slot without a contact is an island of one.  index=True:
+        int32[n_items], the islands numbered 0 .. n_islands - 1 in ascending label order (-1 for a dead slot).  sizes=True:
+        uint32[n_items], the slots of each slot's island (0 for a dead slot).  n_islands: how many islands there are.  stats: the
+        counters of contacts(margin, capacity=0, stats=True) -- the same walk, test for test.  device=False: the host entry, numpy
+        results.  device=True: the device entry on `stream` (a torch stream or a hipStream_t as int; default the current torch stream),
+        torch tensors on the scene's device -- nothing is waited for, and n_islands is a 0-d int64 tensor."""
+        margin = float(margin)
+        if margin != margin:
+            raise ValueError("margin must not be NaN")
+        return self._islands_query("rt_scene_islands", self._side(device=device), False, None, lambda d: (margin,), index, sizes, stats, stream)
+
+    def impact_islands(self, disp, index=False, sizes=False, stats=False, stream=None):
+        """rt_scene_impact_islands / rt_scene_impact_islands_device: the connected groups of the impacts of one step -- islands() with the
+        pairs impacts(disp) lists as the edges (`disp`: n_items x 3, the scene's REAL dtype, as impacts() takes it): the groups a
+        continuous-collision step has to resolve together -> (label[, index][, size], n_islands[, stats dict]) as islands() gives
+        them; stats: the counters of impacts(disp, capacity=0, stats=True).  A numpy array goes through the host entry and gives numpy
+        results; its components must be finite and within +-1e15.  A torch tensor on this scene's device goes through the device entry
+        on `stream` and gives torch tensors -- nothing is waited for, and n_islands is a 0-d int64 tensor."""
+        return self._islands_query("rt_scene_impact_islands", self._side(disp), True, disp, lambda d: (d,), index, sizes, stats, stream)
 
     def swept_overlaps(self, queries, qdisp, disp=None, exclude=None, order=None, capacity=None, times=False, normals=False, offsets=False, stats=False,
                        stream=None):
