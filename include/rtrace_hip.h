@@ -728,6 +728,44 @@ rt_status rt_overlap_spheres_device(rt_scene *scene, const void *queries, uint32
                                     uint32_t capacity, int32_t *items_out, void *gap_out, uint64_t *offsets_out, uint64_t *total_out, rt_stats *stats,
                                     void *hip_stream);
 
+/* ---- box overlap lists (additive to ABI 5): every sphere of the scene within a margin of each axis-aligned query box ----
+ * The other volume a caller holds: a trigger or kill volume, a selection rectangle, the broad-phase box of a body that is no sphere, a
+ * grid cell, the world's bounds -- and, with infinite sides, a slab or a half-space ("everything below this floor").  Passing the box's
+ * circumscribed sphere to rt_overlap_spheres and filtering on the host works, but a flat box or a slab makes that superset most of the
+ * scene.
+ *   Query g is boxes[6g .. 6g+6] = {lo.x, lo.y, lo.z, hi.x, hi.y, hi.z} in REAL.  For a record {c, rr} of the scene's stream -- rr is the
+ * radius squared, rounded once -- in REAL, every operation rounded once, no FMA, every root the IEEE one, per axis k:
+ *   e_k = lo_k - c_k
+ *   f_k = c_k - hi_k
+ *   e_k = f_k > e_k ? f_k : e_k
+ *   e_k = e_k > 0 ? e_k : 0                           comparisons, not fmax: a NaN fails them
+ *   dd  = (e.x*e.x + e.y*e.y) + e.z*e.z
+ *   gap = rr > 0 ? sqrt(dd) - sqrt(rr) : +inf
+ * the distance from the box to the sphere's SURFACE, floored at -r: a centre inside the box has gap = -r however deep it lies.  This is
+ * no signed depth: a negative margin -m lists the spheres that reach more than m into the box, a reach that counts as r at the most, and
+ * says nothing about how far inside the box a sphere lies.  An item is LISTED when !(gap >= margin); a bound CULLS when gap >= margin, and a bound without a positive rr always
+ * culls.  A box carries a query exactly when lo_k <= hi_k on all three axes; NaN fails the comparison.  An inverted box carries no query:
+ * it makes no test and its row is empty.  Infinite sides are valid: lo = -inf and / or hi = +inf give slabs and half-spaces, the
+ * all-infinite box lists every live sphere with gap = -sqrt(rr), and no step of the arithmetic above makes a NaN from them.  A point box
+ * lo == hi == p gives the gap of rt_overlap_spheres with q = 0 bit for bit.  A dead item is at +inf and never listed, at margin = +inf
+ * too; a dead bound culls at its one test.  rust_tracer_amd.box_gaps restates the gap in numpy, bit for bit.
+ *   The walk, the two passes, capacity and the exact prefix, the sorted entries, the same bytes every time and in every order,
+ * offsets_out, *total_out, stats (primary = boxes carried, hits = boxes with an entry), exclude, and the READ under the scene's lock on
+ * static, dynamic, live and flat scenes are exactly those of rt_overlap_spheres.  The calls use that entry's workspace and take their
+ * turn with the overlap, swept-overlap and first-contact calls of their scene. */
+/* Host memory.  RT_ERR_INVALID_ARGUMENT before the device is touched for a NULL scene, boxes or total_out, n == 0, a NaN margin, a
+ * misaligned buffer (items_out, exclude, order 4 bytes, boxes and gap_out REAL, offsets_out and total_out 8 bytes), gap_out without
+ * items_out, capacity > 2^31 - 1, a buffer in device memory, a box coordinate that is NaN or finite and beyond +-1e15 (an infinite one is
+ * accepted), a box with lo_k > hi_k on some axis and an order that is no permutation of 0 .. n-1. */
+rt_status rt_overlap_boxes(rt_scene *scene, const void *boxes, uint32_t n, double margin, const int32_t *exclude, const uint32_t *order,
+                           uint32_t capacity, int32_t *items_out, void *gap_out, uint64_t *offsets_out, uint64_t *total_out, rt_stats *stats);
+/* The same over DEVICE memory (total_out too), enqueued on `hip_stream` without a host synchronisation: only pointers, alignment, n, the
+ * margin and the capacity are checked.  An inverted or NaN box and an order entry >= n carry no query, and a box that no thread carries
+ * has count 0; any input bits end the walk without a fault. */
+rt_status rt_overlap_boxes_device(rt_scene *scene, const void *boxes, uint32_t n, double margin, const int32_t *exclude, const uint32_t *order,
+                                  uint32_t capacity, int32_t *items_out, void *gap_out, uint64_t *offsets_out, uint64_t *total_out, rt_stats *stats,
+                                  void *hip_stream);
+
 /* ---- impact pairs (additive to ABI 5): which spheres of the scene come into contact during one step, and when ----
  * The continuous form of rt_scene_contacts.  A contacts call sees one pose: a pair that is apart at the start of a step and apart at its
  * end but passes through each other in between is in neither list.  rt_sweep_spheres moves one sphere against a scene that stands still.

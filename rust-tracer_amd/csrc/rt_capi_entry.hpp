@@ -1395,6 +1395,52 @@ rt_status rt_overlap_spheres(rt_scene *s, const void *queries, uint32_t n, doubl
         });
 }
 
+// ---- box overlap lists: every sphere of the scene within a margin of each axis-aligned query box (rt_box.hpp) ----
+
+rt_status rt_overlap_boxes_device(rt_scene *s, const void *boxes, uint32_t n, double margin, const int32_t *exclude, const uint32_t *order, uint32_t capacity,
+                                  int32_t *items_out, void *gap_out, uint64_t *offsets_out, uint64_t *total_out, rt_stats *stats, void *hip_stream)
+{
+    const char *const what = "rt_overlap_boxes_device";
+    if (!boxes_args_ok(s, boxes, n, margin, exclude, order, capacity, items_out, gap_out, offsets_out, total_out, what)) return RT_ERR_INVALID_ARGUMENT;
+    // box calls take their turn with overlap, swept and first-contact calls: they share the counts and the offsets
+    return device_list_query(
+        s, s->overlap, capacity != 0u && items_out, stats, static_cast<hipStream_t>(hip_stream),
+        [&](const void *, uint32_t, hipStream_t stream) { return overlap_begin(s, n, stream); },
+        [&](const void *nodes, uint32_t n_nodes, rt::Counters *counters, hipStream_t stream) {
+            return enqueue_boxes_count(s, nodes, n_nodes, boxes, n, margin, exclude, order, offsets_out, total_out, counters, stream);
+        },
+        [&](const void *nodes, uint32_t n_nodes, hipStream_t stream) {
+            return enqueue_boxes_fill(s, nodes, n_nodes, boxes, n, margin, exclude, order, capacity, items_out, gap_out, stream);
+        });
+}
+
+rt_status rt_overlap_boxes(rt_scene *s, const void *boxes, uint32_t n, double margin, const int32_t *exclude, const uint32_t *order, uint32_t capacity,
+                           int32_t *items_out, void *gap_out, uint64_t *offsets_out, uint64_t *total_out, rt_stats *stats)
+{
+    const char *const what = "rt_overlap_boxes";
+    if (!boxes_args_ok(s, boxes, n, margin, exclude, order, capacity, items_out, gap_out, offsets_out, total_out, what)) return RT_ERR_INVALID_ARGUMENT;
+    const bool fill = capacity != 0u && items_out;
+    const size_t esz = real_size(s);
+    HostStaging::Row rows[] = { { boxes, 6 * esz * (size_t)n, kStageIn }, { exclude, sizeof(int32_t) * (size_t)n, kStageIn }, { order, sizeof(uint32_t) * (size_t)n, kStageIn },
+                                { fill ? items_out : nullptr, sizeof(int32_t) * (size_t)capacity, kStageOut, sizeof(int32_t) },
+                                { fill ? gap_out : nullptr, esz * (size_t)capacity, kStageOut, esz },
+                                { offsets_out, sizeof(uint64_t) * ((size_t)n + 1), kStageOut } };
+    HostStaging hs(rows);
+    if (rt_status pst = hs.plan(what, total_out); pst != RT_OK) return pst;
+    if (!boxes_valid(s, boxes, n, what)) return RT_ERR_INVALID_ARGUMENT;
+    if (order && !order_is_permutation(order, n, what)) return RT_ERR_INVALID_ARGUMENT;
+    return host_list_query(
+        s, s->overlap, hs, capacity, fill, total_out, stats,
+        [&](const void *, uint32_t, hipStream_t stream) { return overlap_begin(s, n, stream); },
+        [&](const void *nodes, uint32_t n_nodes, rt::Counters *counters, hipStream_t stream) {
+            return enqueue_boxes_count(s, nodes, n_nodes, hs.dev(0), n, margin, hs.dev<const int32_t>(1), hs.dev<const uint32_t>(2), hs.dev<uint64_t>(5), s->overlap.d_total,
+                                       counters, stream);
+        },
+        [&](const void *nodes, uint32_t n_nodes, hipStream_t stream) {
+            return enqueue_boxes_fill(s, nodes, n_nodes, hs.dev(0), n, margin, hs.dev<const int32_t>(1), hs.dev<const uint32_t>(2), capacity, hs.dev<int32_t>(3), hs.dev(4), stream);
+        });
+}
+
 // ---- swept overlap lists: every sphere of the scene a moving outside sphere comes into contact with during one step (rt_swept.hpp) ----
 
 rt_status rt_swept_overlaps_device(rt_scene *s, const void *queries, const void *qdisp, uint32_t n, const void *disp, const int32_t *exclude, const uint32_t *order,

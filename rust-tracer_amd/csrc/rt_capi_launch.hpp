@@ -1300,6 +1300,75 @@ rt_status enqueue_overlap_fill(const rt_scene *s, const void *nodes, uint32_t n_
     return enqueue_overlap_pass(s, nodes, n_nodes, queries, n, margin, exclude, order, true, capacity, items, gap, nullptr, stream);
 }
 
+// ---- box overlap lists (rt_overlap_boxes*, rt_box.hpp): the overlap lists' workspace (overlap_begin) and their turn ----
+
+// What both box entries check (device pointers are not dereferenced here).
+bool boxes_args_ok(const rt_scene *s, const void *boxes, uint32_t n, double margin, const int32_t *exclude, const uint32_t *order, uint32_t capacity,
+                   const int32_t *items, const void *gap, const uint64_t *offsets, const uint64_t *total, const char *what)
+{
+    if (!s) { snprintf(g_err, sizeof g_err, "%s: NULL scene", what); return false; }
+    if (!boxes) { snprintf(g_err, sizeof g_err, "%s: NULL boxes", what); return false; }
+    if (!total) { snprintf(g_err, sizeof g_err, "%s: NULL total_out", what); return false; }
+    if (n == 0) { snprintf(g_err, sizeof g_err, "%s: n == 0", what); return false; }
+    if (std::isnan(margin)) { snprintf(g_err, sizeof g_err, "%s: margin is NaN", what); return false; }
+    if (capacity > 0x7FFFFFFFu) { snprintf(g_err, sizeof g_err, "%s: capacity %u is above 2^31 - 1", what, capacity); return false; }
+    if (gap && !items) { snprintf(g_err, sizeof g_err, "%s: gap_out without items_out", what); return false; }
+    return aligned_ok(what, 4, { { items, "items_out" }, { exclude, "exclude" }, { order, "order" } })
+           && aligned_ok(what, 8, { { offsets, "offsets_out" }, { total, "total_out" } }) && aligned_ok(what, real_size(s), { { boxes, "boxes" }, { gap, "gap_out" } });
+}
+
+// The host entry's domain: no coordinate is NaN, a finite one lies within +-1e15 (an infinite side is a slab's or a half-space's), and
+// lo <= hi on every axis.
+bool boxes_valid(const rt_scene *s, const void *boxes, uint32_t n, const char *what)
+{
+    return each_valid(s, n, [&](auto real, uint32_t i) {
+        const decltype(real) *b = static_cast<const decltype(real) *>(boxes) + 6 * (size_t)i;
+        for (int k = 0; k < 6; ++k)
+            if (std::isnan(b[k]) || (std::isfinite(b[k]) && std::fabs((double)b[k]) > 1e15)) {
+                snprintf(g_err, sizeof g_err, "%s: box %u has a NaN coordinate or a finite one beyond +-1e15", what, i);
+                return false;
+            }
+        for (int k = 0; k < 3; ++k)
+            if (b[k] > b[k + 3]) {
+                snprintf(g_err, sizeof g_err, "%s: box %u is inverted: lo %g > hi %g on axis %d", what, i, (double)b[k], (double)b[k + 3], k);
+                return false;
+            }
+        return true;
+    });
+}
+
+// One pass of the walk on `stream`, as enqueue_overlap_pass: the first (fill == false) counts, counters != NULL runs its counting flavour
+// (same counts), and with an order a box that no thread carries keeps the count 0; the second is the same walk by the boxes that counted
+// something, entry offsets[g] + rank written where it lies below `capacity`.
+rt_status enqueue_boxes_pass(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *boxes, uint32_t n, double margin, const int32_t *exclude,
+                             const uint32_t *order, bool fill, uint32_t capacity, int32_t *items, void *gap, rt::Counters *counters, hipStream_t stream)
+{
+    if (!fill && order) HIP_TRY(hipMemsetAsync(s->overlap.counts, 0, sizeof(uint32_t) * (size_t)n, stream));
+    by_precision(s, [&](auto real) {
+        using T = decltype(real);
+        const rt::BoxArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), static_cast<const T *>(boxes), exclude, order, s->overlap.counts,
+                                fill ? s->overlap.offsets : nullptr, items, static_cast<T *>(gap), counters, (T)margin, n_nodes, n, capacity };
+        if (fill) hipLaunchKernelGGL((rt::k_overlap_boxes<T, false, true>), query_grid(n), query_block(), 0, stream, a);
+        else with_flags([&](auto count) { hipLaunchKernelGGL((rt::k_overlap_boxes<T, count(), false>), query_grid(n), query_block(), 0, stream, a); }, counters != nullptr);
+    });
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+// The first pass and the scan: counts, then offsets[n + 1] in the workspace and, where given, in the caller's device memory.
+rt_status enqueue_boxes_count(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *boxes, uint32_t n, double margin, const int32_t *exclude,
+                              const uint32_t *order, uint64_t *offsets_out, uint64_t *total_out, rt::Counters *counters, hipStream_t stream)
+{
+    const rt_status st = enqueue_boxes_pass(s, nodes, n_nodes, boxes, n, margin, exclude, order, false, 0u, nullptr, nullptr, counters, stream);
+    return st != RT_OK ? st : enqueue_list_scan(s->overlap, n, offsets_out, total_out, stream);
+}
+
+rt_status enqueue_boxes_fill(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *boxes, uint32_t n, double margin, const int32_t *exclude,
+                             const uint32_t *order, uint32_t capacity, int32_t *items, void *gap, hipStream_t stream)
+{
+    return enqueue_boxes_pass(s, nodes, n_nodes, boxes, n, margin, exclude, order, true, capacity, items, gap, nullptr, stream);
+}
+
 // ---- swept overlap lists (rt_swept_overlaps*, rt_swept.hpp) ----
 
 // What both swept entries check (device pointers are not dereferenced here).

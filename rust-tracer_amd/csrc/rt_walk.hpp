@@ -1,6 +1,6 @@
-// rt_walk.hpp -- the pieces every query kernel's skip-pointer walk is made of, one copy of each: the lane's query index, the three
+// rt_walk.hpp -- the pieces every query kernel's skip-pointer walk is made of, one copy of each: the lane's query index, the four
 // metrics, the wave's BOUND and retiring ITEM steps and the counter flush.  The query headers (rt_query.hpp, rt_multihit.hpp,
-// rt_near.hpp, rt_sweep.hpp, rt_contacts.hpp, rt_overlap.hpp, rt_impacts.hpp, rt_swept.hpp, rt_first.hpp) call them;
+// rt_near.hpp, rt_sweep.hpp, rt_contacts.hpp, rt_overlap.hpp, rt_impacts.hpp, rt_swept.hpp, rt_first.hpp, rt_box.hpp) call them;
 // each kernel keeps its own visible loop -- what accepts, what a hit does, what a lane carries differ in kind -- and its own header says
 // what its metric MEANS.  Here is only how each piece is computed.
 //
@@ -66,6 +66,23 @@ __device__ __forceinline__ T centre_gap(const Node<T> &nd, V3<T> p, T q)
     const T vv = dot(v, v);
     T t = inf<T>();
     if (nd.a3 > T(0.0)) t = (sqrt_rn_lean(vv) - sqrt_rn_lean(nd.a3)) - q;
+    return t;
+}
+
+// The gap between the record and the axis-aligned box [lo, hi] (rt_box.hpp): per axis how far the record's centre lies outside the box --
+// the larger of lo - c and c - hi, floored at 0 -- the root of the squares' sum, minus the record's radius.  Comparisons, not fmax: a NaN
+// excess fails both and ends as 0.  An infinite side gives an excess of -inf, which the floor takes: no step makes a NaN from lo = -inf or
+// hi = +inf.  +inf for a record without a positive rr, as centre_gap.
+template <typename T>
+__device__ __forceinline__ T box_gap(const Node<T> &nd, V3<T> lo, V3<T> hi)
+{
+    V3<T> e = { lo.x - nd.a0, lo.y - nd.a1, lo.z - nd.a2 };
+    const V3<T> f = { nd.a0 - hi.x, nd.a1 - hi.y, nd.a2 - hi.z };
+    e = { f.x > e.x ? f.x : e.x, f.y > e.y ? f.y : e.y, f.z > e.z ? f.z : e.z };
+    e = { e.x > T(0.0) ? e.x : T(0.0), e.y > T(0.0) ? e.y : T(0.0), e.z > T(0.0) ? e.z : T(0.0) };
+    const T dd = dot(e, e);
+    T t = inf<T>();
+    if (nd.a3 > T(0.0)) t = sqrt_rn_lean(dd) - sqrt_rn_lean(nd.a3);
     return t;
 }
 

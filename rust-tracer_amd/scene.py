@@ -307,6 +307,32 @@ def overlap_gaps(queries, spheres):
     return np.where((rr > 0)[None, :], gap, R(np.inf)).astype(R, copy=False)
 
 
+def box_gaps(boxes, spheres):
+    """The gap between every axis-aligned box of `boxes` (n x 6: lo.x, lo.y, lo.z, hi.x, hi.y, hi.z) and every sphere of `spheres` (m x 4:
+    cx, cy, cz, r) -> REAL[n, m], the metric of rt_overlap_boxes restated in numpy bit for bit (include/rtrace_hip.h states it), in the
+    arrays' dtype (float32 or float64, the same for both), every operation rounded once:  rr = r * r;  per axis e = lo - c, f = c - hi,
+    e = f where f > e, e = 0 where not e > 0;  dd = (e.x*e.x + e.y*e.y) + e.z*e.z;  gap = sqrt(dd) - sqrt(rr) where rr > 0, else +inf.
+    The distance from the box to the sphere's surface, floored at -r: a centre inside the box has gap = -r, however deep it lies.  A
+    point box lo == hi == p gives overlap_gaps with q = 0.  Infinite sides are slabs and half-spaces; the all-infinite box is at
+    -sqrt(rr) from every live sphere.  A record without a positive rr -- radius 0: a dead slot -- is at +inf from every box.
+    DeviceScene.box_overlaps lists, per box with lo <= hi on every axis, the spheres with !(gap >= margin); a box that is inverted or
+    holds a NaN carries no query there, and its row here is whatever the arithmetic gives."""
+    b, s = np.asarray(boxes), np.asarray(spheres)
+    if b.dtype not in (np.float32, np.float64) or s.dtype != b.dtype or b.ndim != 2 or b.shape[1] != 6 or s.ndim != 2 or s.shape[1] != 4:
+        raise ValueError("boxes must be (n, 6) and spheres (m, 4), both float32 or both float64")
+    R = b.dtype.type
+    rr = s[:, 3] * s[:, 3]
+    with np.errstate(invalid="ignore", over="ignore"):
+        c = s[None, :, :3]
+        e = b[:, None, :3] - c
+        f = c - b[:, None, 3:]
+        e = np.where(f > e, f, e)
+        e = np.where(e > 0, e, R(0.0))
+        dd = (e[..., 0] * e[..., 0] + e[..., 1] * e[..., 1]) + e[..., 2] * e[..., 2]
+        gap = np.sqrt(dd) - np.sqrt(np.where(rr > 0, rr, R(1.0)))[None, :]
+    return np.where((rr > 0)[None, :], gap, R(np.inf)).astype(R, copy=False)
+
+
 def impact_scale(spheres, disp, queries=None, qdisp=None):
     """S of rt_scene_impacts (include/rtrace_hip.h) for the records `spheres` (m x 4: cx, cy, cz, r) and their motion-table rows `disp`
     (m x 3, or None: 0) -> a power of two in the arrays' dtype.  M is the largest of |cx|, |cy|, |cz|, r, |dx|, |dy|, |dz| over the records
@@ -1402,6 +1428,26 @@ class DeviceScene:
             raise ValueError("margin must not be NaN")
         return self._list_query("rt_overlap_spheres", self._side(queries), (queries,), (("queries", 4, None, False),), exclude, order, capacity,
                                 (True, gaps), (((), np.int32), ((), "R")), offsets, stats, stream, "the queries have %d entries",
+                                lambda xs, n, ex, o: (xs[0], n, margin, ex, o))
+
+    def box_overlaps(self, boxes, margin=0.0, exclude=None, order=None, capacity=None, gaps=False, offsets=False, stats=False, stream=None):
+        """rt_overlap_boxes / rt_overlap_boxes_device: every sphere of the scene within `margin` of each axis-aligned box of `boxes` (n x 6:
+        lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, the scene's REAL dtype; box_gaps is the metric: the distance from the box to the sphere's
+        surface, -r for a centre inside the box; margin 0: the spheres a box touches, a positive margin is a skin, +inf lists every live
+        sphere) -> (items[, gap][, offsets], total[, stats dict]), with the shapes, capacity, exclude, stream and the host / device routing
+        of overlaps().  A side may be infinite (a slab, a half-space); lo == hi is a point.  The host entry refuses a NaN coordinate and
+        an inverted box (lo > hi on some axis); through the device entry such a box carries no query and has an empty row.
+        order (uint32[n]): thread j carries box order[j] -- the same bytes and counters in every order.  order=True is refused: there is
+        no sphere array to order by.  For finite boxes a coherent order is the sphere order of their centres with radius 1:
+            centres = 0.5 * (boxes[:, :3] + boxes[:, 3:])
+            order = dev.sphere_order(np.concatenate([centres, np.ones((n, 1), boxes.dtype)], axis=1))."""
+        margin = float(margin)
+        if margin != margin:
+            raise ValueError("margin must not be NaN")
+        if order is True:
+            raise ValueError("order=True is not available for boxes: pass sphere_order of the boxes' centres with radius 1")
+        return self._list_query("rt_overlap_boxes", self._side(boxes), (boxes,), (("boxes", 6, None, False),), exclude, order, capacity,
+                                (True, gaps), (((), np.int32), ((), "R")), offsets, stats, stream, "the boxes have %d entries",
                                 lambda xs, n, ex, o: (xs[0], n, margin, ex, o))
 
     def impacts(self, disp, capacity=None, times=False, offsets=False, stats=False, stream=None):
