@@ -766,6 +766,55 @@ rt_status rt_overlap_boxes_device(rt_scene *scene, const void *boxes, uint32_t n
                                   uint32_t capacity, int32_t *items_out, void *gap_out, uint64_t *offsets_out, uint64_t *total_out, rt_stats *stats,
                                   void *hip_stream);
 
+/* ---- region overlap lists (additive to ABI 5): every sphere of the scene that reaches into each convex region of six planes ----
+ * A renderer's first spatial question -- which spheres can this camera, this screen rectangle, this tilted trigger volume see -- and the
+ * oriented box rt_overlap_boxes cannot hold.  It is asked with FEW regions that each cover much of the scene, so the walk is the inverse
+ * of the other queries': one region per WAVE, and the lanes carry sections of the node stream (below).
+ *   Region g is planes[24g .. 24g+24] = six planes {n.x, n.y, n.z, d} in REAL.  The OUTSIDE of a plane is where n.c + d > 0.  For a
+ * record {c, rr} of the scene's stream -- rr is the radius squared, rounded once -- in REAL, every operation rounded once, no FMA, the
+ * root the IEEE one:
+ *   s_k = ((n_k.x*c.x + n_k.y*c.y) + n_k.z*c.z) + d_k        for k = 0 .. 5
+ *   m   = -inf;  for k = 0 .. 5:  m = s_k > m ? s_k : m       a comparison, not fmax
+ *   gap = rr > 0 ? m - sqrt(rr) : +inf
+ * An item is LISTED when !(gap >= margin); a bound CULLS when gap >= margin, and a bound without a positive rr always culls.
+ *   With unit normals m is the largest signed plane distance of the centre.  It is never above the true distance from the region to the
+ * centre, so the list is a SUPERSET of the exact touch list: never short of it, and larger only for spheres outside the region near one
+ * of its edges or corners.  This is the usual sphere / frustum test.  Normals are expected to have length 1; a shorter normal only
+ * weakens its plane.  In exact arithmetic with |n_k| <= 1 a bound that encloses an item never culls what the item's own test lists: each
+ * s_k is 1-Lipschitz in c and so is their maximum, so m(item) >= m(bound) - |c_item - c_bound| and the item's gap is at least the bound's.
+ * In REAL the two sides round separately, and the walk can differ from a brute-force pass over the items only within a few ulp of the
+ * margin.  As everywhere here, the result is DEFINED as the walk's: the one-lane walk of rt_overlap_spheres over the scene's plain
+ * per-origin stream from node 0 with this metric.
+ *   An ABSENT plane is {0, 0, 0, -inf}: s = -inf for every finite centre, which is how fewer than six planes are passed; six absent
+ * planes list every live sphere.  A region carries a query exactly when none of its 24 reals is NaN; any other region makes no test and
+ * has an empty row.  A dead item is at +inf and never listed; a dead bound culls at its one test.  rust_tracer_amd.region_gaps restates
+ * the gap in numpy, bit for bit.
+ *   sections: each region is cut into J sections of the stream, section j the nodes [floor(j N / J), floor((j + 1) N / J)), N the
+ * stream's node count; 64 consecutive sections of one region make a wave.  A section's lane first descends from node 0 -- it tests
+ * (and counts) only the bounds whose subtree holds its first node, and where one culls it continues behind that subtree -- then walks its
+ * nodes as the one-lane walk does.  The sections' lists, in order, ARE the one-lane walk's list: the same bytes for every J.  The caller's
+ * value is clamped to 1 .. N; 0 lets the library choose, by a rule that is a pure function of (n, N), never of the device:
+ *   J = max(1, min(floor(2^18 / n), floor(N / 8)))
+ * (rust_tracer_amd.region_sections restates it).  A product n * J above 2^26 is refused.
+ *   The two passes, capacity and the exact prefix, the entries sorted by (g, item slot), the same bytes every time, offsets_out[n + 1],
+ * *total_out and the READ under the scene's lock on static, dynamic, live and flat scenes are those of rt_overlap_spheres; there is no
+ * exclude and no order (regions are no items, and there are few of them).  stats: primary = regions carried, hits = regions with an
+ * entry, sphere_tests / bound_tests = the tests actually made, the descents' included -- they depend on J, and at J = 1 they are the
+ * one-lane walk's.  The calls use rt_overlap_spheres's workspace, for n * J counts, and take their turn with the overlap, box,
+ * swept-overlap and first-contact calls of their scene. */
+/* Host memory.  RT_ERR_INVALID_ARGUMENT before the device is touched for a NULL scene, planes or total_out, n == 0, a NaN margin, a
+ * misaligned buffer (items_out 4 bytes, planes and gap_out REAL, offsets_out and total_out 8 bytes), gap_out without items_out,
+ * capacity > 2^31 - 1, n * J > 2^26, a buffer in device memory, and -- with the region's and the plane's index -- a NaN in a plane, an
+ * infinite normal component, a zero normal whose d is not -inf, a d of +inf, a finite |d| above 1e15 and a normal with
+ * |n.n - 1| > 2^-10 (this catches input that was never normalised; it is no tolerance of the metric). */
+rt_status rt_overlap_regions(rt_scene *scene, const void *planes, uint32_t n, double margin, uint32_t sections, uint32_t capacity,
+                             int32_t *items_out, void *gap_out, uint64_t *offsets_out, uint64_t *total_out, rt_stats *stats);
+/* The same over DEVICE memory (total_out too), enqueued on `hip_stream` without a host synchronisation: only pointers, alignment, n, the
+ * margin, the capacity and n * J are checked.  A region with a NaN carries no query; any input bits end the walk without a fault. */
+rt_status rt_overlap_regions_device(rt_scene *scene, const void *planes, uint32_t n, double margin, uint32_t sections, uint32_t capacity,
+                                    int32_t *items_out, void *gap_out, uint64_t *offsets_out, uint64_t *total_out, rt_stats *stats,
+                                    void *hip_stream);
+
 /* ---- impact pairs (additive to ABI 5): which spheres of the scene come into contact during one step, and when ----
  * The continuous form of rt_scene_contacts.  A contacts call sees one pose: a pair that is apart at the start of a step and apart at its
  * end but passes through each other in between is in neither list.  rt_sweep_spheres moves one sphere against a scene that stands still.

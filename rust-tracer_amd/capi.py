@@ -43,7 +43,7 @@ SYMBOLS = ("rt_abi_version", "rt_build_hierarchy", "rt_device_count", "rt_scene_
            "rt_scene_update_live", "rt_scene_update_live_device", "rt_scene_rebuild_n", "rt_scene_rebuild_n_device", "rt_scene_live",
            "rt_near_spheres", "rt_near_spheres_device", "rt_sweep_spheres", "rt_sweep_spheres_device",
            "rt_scene_contacts", "rt_scene_contacts_device", "rt_overlap_spheres", "rt_overlap_spheres_device",
-           "rt_overlap_boxes", "rt_overlap_boxes_device",
+           "rt_overlap_boxes", "rt_overlap_boxes_device", "rt_overlap_regions", "rt_overlap_regions_device",
            "rt_scene_impacts", "rt_scene_impacts_device", "rt_swept_overlaps", "rt_swept_overlaps_device",
            "rt_first_contacts", "rt_first_contacts_device",
            "rt_scene_islands", "rt_scene_islands_device", "rt_scene_impact_islands", "rt_scene_impact_islands_device")
@@ -181,6 +181,10 @@ lib.rt_overlap_spheres_device.argtypes = lib.rt_overlap_spheres.argtypes + [C.c_
 # box overlap lists: (scene, boxes, n, margin, ...) and everything behind it as for the overlap lists
 lib.rt_overlap_boxes.argtypes = list(lib.rt_overlap_spheres.argtypes)
 lib.rt_overlap_boxes_device.argtypes = lib.rt_overlap_boxes.argtypes + [C.c_void_p]
+# region overlap lists: (scene, planes, n, margin, sections, capacity, items_out or NULL, gap_out or NULL, offsets_out or NULL, total_out, stats[, stream])
+lib.rt_overlap_regions.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.POINTER(Stats)]
+lib.rt_overlap_regions_device.argtypes = lib.rt_overlap_regions.argtypes + [C.c_void_p]
 # impact pairs: (scene, disp, capacity, pairs_out or NULL, time_out or NULL, offsets_out or NULL, total_out, stats[, stream])
 lib.rt_scene_impacts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
 lib.rt_scene_impacts_device.argtypes = lib.rt_scene_impacts.argtypes + [C.c_void_p]

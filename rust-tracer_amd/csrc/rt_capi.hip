@@ -23,6 +23,7 @@
 #include "rt_contacts.hpp"
 #include "rt_overlap.hpp"
 #include "rt_box.hpp"
+#include "rt_region.hpp"
 #include "rt_impacts.hpp"
 #include "rt_islands.hpp"
 #include "rt_swept.hpp"
@@ -392,7 +393,8 @@ struct rt_scene {
     // behind it, made by the first islands call under contacts.mu; islands calls share the contacts workspace and the motion table
     uint32_t *d_islands = nullptr;
     // ---- overlap lists (rt_overlap_spheres*, rt_overlap.hpp): the workspace of the two passes, for overlap.cap queries: made by the first call,
-    // grown when a call brings more queries than any before it (behind overlap.ev); the box overlap lists (rt_overlap_boxes*, rt_box.hpp) use it too
+    // grown when a call brings more queries than any before it (behind overlap.ev); the box overlap lists (rt_overlap_boxes*, rt_box.hpp) use it too,
+    // and the region overlap lists (rt_overlap_regions*, rt_region.hpp) with one count per section
     ListSpace overlap;
     // ---- swept overlap lists (rt_swept_overlaps*, rt_swept.hpp): a motion table of their own -- laid out as d_impacts -- that belongs to the
     // overlap workspace: made by the first swept call under overlap.mu, used behind overlap.ev

@@ -1441,6 +1441,52 @@ rt_status rt_overlap_boxes(rt_scene *s, const void *boxes, uint32_t n, double ma
         });
 }
 
+// ---- region overlap lists: every sphere of the scene that reaches into each convex region of six planes (rt_region.hpp) ----
+
+rt_status rt_overlap_regions_device(rt_scene *s, const void *planes, uint32_t n, double margin, uint32_t sections, uint32_t capacity, int32_t *items_out,
+                                    void *gap_out, uint64_t *offsets_out, uint64_t *total_out, rt_stats *stats, void *hip_stream)
+{
+    const char *const what = "rt_overlap_regions_device";
+    if (!regions_args_ok(s, planes, n, margin, sections, capacity, items_out, gap_out, offsets_out, total_out, what)) return RT_ERR_INVALID_ARGUMENT;
+    const uint32_t J = region_sections_of(s, n, sections);
+    // region calls take their turn with overlap, box, swept and first-contact calls: they share the counts and the offsets
+    return device_list_query(
+        s, s->overlap, capacity != 0u && items_out, stats, static_cast<hipStream_t>(hip_stream),
+        [&](const void *, uint32_t, hipStream_t stream) { return overlap_begin(s, n * J, stream); },
+        [&](const void *nodes, uint32_t n_nodes, rt::Counters *counters, hipStream_t stream) {
+            return enqueue_regions_count(s, nodes, n_nodes, planes, n, margin, J, offsets_out, total_out, counters, stream);
+        },
+        [&](const void *nodes, uint32_t n_nodes, hipStream_t stream) {
+            return enqueue_regions_fill(s, nodes, n_nodes, planes, n, margin, J, capacity, items_out, gap_out, stream);
+        });
+}
+
+rt_status rt_overlap_regions(rt_scene *s, const void *planes, uint32_t n, double margin, uint32_t sections, uint32_t capacity, int32_t *items_out, void *gap_out,
+                             uint64_t *offsets_out, uint64_t *total_out, rt_stats *stats)
+{
+    const char *const what = "rt_overlap_regions";
+    if (!regions_args_ok(s, planes, n, margin, sections, capacity, items_out, gap_out, offsets_out, total_out, what)) return RT_ERR_INVALID_ARGUMENT;
+    const uint32_t J = region_sections_of(s, n, sections);
+    const bool fill = capacity != 0u && items_out;
+    const size_t esz = real_size(s);
+    HostStaging::Row rows[] = { { planes, 24 * esz * (size_t)n, kStageIn },
+                                { fill ? items_out : nullptr, sizeof(int32_t) * (size_t)capacity, kStageOut, sizeof(int32_t) },
+                                { fill ? gap_out : nullptr, esz * (size_t)capacity, kStageOut, esz },
+                                { offsets_out, sizeof(uint64_t) * ((size_t)n + 1), kStageOut } };
+    HostStaging hs(rows);
+    if (rt_status pst = hs.plan(what, total_out); pst != RT_OK) return pst;
+    if (!regions_valid(s, planes, n, what)) return RT_ERR_INVALID_ARGUMENT;
+    return host_list_query(
+        s, s->overlap, hs, capacity, fill, total_out, stats,
+        [&](const void *, uint32_t, hipStream_t stream) { return overlap_begin(s, n * J, stream); },
+        [&](const void *nodes, uint32_t n_nodes, rt::Counters *counters, hipStream_t stream) {
+            return enqueue_regions_count(s, nodes, n_nodes, hs.dev(0), n, margin, J, hs.dev<uint64_t>(3), s->overlap.d_total, counters, stream);
+        },
+        [&](const void *nodes, uint32_t n_nodes, hipStream_t stream) {
+            return enqueue_regions_fill(s, nodes, n_nodes, hs.dev(0), n, margin, J, capacity, hs.dev<int32_t>(1), hs.dev(2), stream);
+        });
+}
+
 // ---- swept overlap lists: every sphere of the scene a moving outside sphere comes into contact with during one step (rt_swept.hpp) ----
 
 rt_status rt_swept_overlaps_device(rt_scene *s, const void *queries, const void *qdisp, uint32_t n, const void *disp, const int32_t *exclude, const uint32_t *order,

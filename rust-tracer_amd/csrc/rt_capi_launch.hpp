@@ -1369,6 +1369,112 @@ rt_status enqueue_boxes_fill(const rt_scene *s, const void *nodes, uint32_t n_no
     return enqueue_boxes_pass(s, nodes, n_nodes, boxes, n, margin, exclude, order, true, capacity, items, gap, nullptr, stream);
 }
 
+// ---- region overlap lists (rt_overlap_regions*, rt_region.hpp): the overlap lists' workspace (overlap_begin) for n J counts, and their turn ----
+
+// The rule for sections == 0 (include/rtrace_hip.h states it, rust_tracer_amd.region_sections restates it): a pure function of (n, n_nodes).
+// As many sections as bring the call to kRegionLanes lanes, none shorter than kRegionSectionNodes nodes.  DESIGN.md 4.23 has the sweep
+// (tools/region_rate.py) that chose the two constants.
+constexpr uint32_t kRegionLanes = 1u << 18, kRegionSectionNodes = 8u, kRegionMaxCounts = 1u << 26;
+
+inline uint32_t region_sections_rule(uint32_t n, uint32_t n_nodes)
+{
+    return std::max(1u, std::min(kRegionLanes / std::max(n, 1u), n_nodes / kRegionSectionNodes));
+}
+
+// J of a call: the caller's `sections` clamped to 1 .. n_nodes, or the rule's for 0.  The stream a region call walks has s->n_nodes nodes,
+// or -- a scene without bounds -- one per item (query_stream); neither changes after the scene is made.
+inline uint32_t region_sections_of(const rt_scene *s, uint32_t n, uint32_t sections)
+{
+    const uint32_t n_nodes = std::max(1u, s->n_nodes ? s->n_nodes : s->n_items);
+    return sections == 0u ? region_sections_rule(n, n_nodes) : std::min(sections, n_nodes);
+}
+
+// What both region entries check (device pointers are not dereferenced here).
+bool regions_args_ok(const rt_scene *s, const void *planes, uint32_t n, double margin, uint32_t sections, uint32_t capacity, const int32_t *items, const void *gap,
+                     const uint64_t *offsets, const uint64_t *total, const char *what)
+{
+    if (!s) { snprintf(g_err, sizeof g_err, "%s: NULL scene", what); return false; }
+    if (!planes) { snprintf(g_err, sizeof g_err, "%s: NULL planes", what); return false; }
+    if (!total) { snprintf(g_err, sizeof g_err, "%s: NULL total_out", what); return false; }
+    if (n == 0) { snprintf(g_err, sizeof g_err, "%s: n == 0", what); return false; }
+    if (std::isnan(margin)) { snprintf(g_err, sizeof g_err, "%s: margin is NaN", what); return false; }
+    if (capacity > 0x7FFFFFFFu) { snprintf(g_err, sizeof g_err, "%s: capacity %u is above 2^31 - 1", what, capacity); return false; }
+    if (gap && !items) { snprintf(g_err, sizeof g_err, "%s: gap_out without items_out", what); return false; }
+    if (!(aligned_ok(what, 4, { { items, "items_out" } }) && aligned_ok(what, 8, { { offsets, "offsets_out" }, { total, "total_out" } })
+          && aligned_ok(what, real_size(s), { { planes, "planes" }, { gap, "gap_out" } })))
+        return false;
+    const uint32_t J = region_sections_of(s, n, sections);
+    if ((uint64_t)n * J > kRegionMaxCounts) {
+        snprintf(g_err, sizeof g_err, "%s: n * sections = %u * %u is above 2^26", what, n, J);
+        return false;
+    }
+    return true;
+}
+
+// The host entry's domain, plane k of region i: no NaN; a normal that is finite and of length 1 (|n.n - 1| <= 2^-10: what catches input
+// that was never normalised, no tolerance of the metric) with a d that is -inf or finite within +-1e15; or the absent plane, a zero normal
+// with d = -inf.
+bool regions_valid(const rt_scene *s, const void *planes, uint32_t n, const char *what)
+{
+    return each_valid(s, n, [&](auto real, uint32_t i) {
+        const decltype(real) *r = static_cast<const decltype(real) *>(planes) + 24 * (size_t)i;
+        for (int k = 0; k < 6; ++k) {
+            const double x = (double)r[4 * k], y = (double)r[4 * k + 1], z = (double)r[4 * k + 2], d = (double)r[4 * k + 3];
+            const char *bad = nullptr;
+            const double nn = (x * x + y * y) + z * z;
+            if (std::isnan(x) || std::isnan(y) || std::isnan(z) || std::isnan(d)) bad = "holds a NaN";
+            else if (std::isinf(x) || std::isinf(y) || std::isinf(z)) bad = "has an infinite normal component";
+            else if (d == std::numeric_limits<double>::infinity()) bad = "has d = +inf";
+            else if (std::isfinite(d) && std::fabs(d) > 1e15) bad = "has a finite |d| above 1e15";
+            else if (nn == 0.0 && std::isfinite(d)) bad = "has a zero normal and a d that is not -inf";
+            else if (nn != 0.0 && std::fabs(nn - 1.0) > 0x1p-10) bad = "has a normal that is not of length 1";
+            if (bad) {
+                snprintf(g_err, sizeof g_err, "%s: region %u, plane %d %s", what, i, k, bad);
+                return false;
+            }
+        }
+        return true;
+    });
+}
+
+// One pass of the sectioned walk on `stream` (rt_region.hpp): ceil(J / 64) waves per region.  The first (fill == false) writes every one of
+// the n J counts; counters != NULL runs its counting flavour (same counts).  The second is the same walk by the sections that counted
+// something, entry offsets[g J + j] + rank written where it lies below `capacity`.
+rt_status enqueue_regions_pass(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *planes, uint32_t n, double margin, uint32_t J, bool fill,
+                               uint32_t capacity, int32_t *items, void *gap, rt::Counters *counters, hipStream_t stream)
+{
+    const uint64_t waves = (uint64_t)n * ((J + 63u) / 64u);                    // <= n J <= 2^26
+    const dim3 grid((unsigned)((waves * 64u + rt::kBlockThreads - 1) / rt::kBlockThreads));
+    by_precision(s, [&](auto real) {
+        using T = decltype(real);
+        const rt::RegionArgs<T> a{ static_cast<const rt::Node<T> *>(nodes), static_cast<const T *>(planes), s->overlap.counts, fill ? s->overlap.offsets : nullptr,
+                                   items, static_cast<T *>(gap), counters, (T)margin, n_nodes, n, J, capacity };
+        if (fill) hipLaunchKernelGGL((rt::k_overlap_regions<T, false, true>), grid, query_block(), 0, stream, a);
+        else with_flags([&](auto count) { hipLaunchKernelGGL((rt::k_overlap_regions<T, count(), false>), grid, query_block(), 0, stream, a); }, counters != nullptr);
+    });
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+// The first pass, the scan over the n J counts -- offsets[n J + 1] in the workspace, the total where the caller wants it -- and the rows:
+// offsets_out[g] = offsets[g J] where given, and the regions with an entry into the counters' hits.
+rt_status enqueue_regions_count(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *planes, uint32_t n, double margin, uint32_t J,
+                                uint64_t *offsets_out, uint64_t *total_out, rt::Counters *counters, hipStream_t stream)
+{
+    rt_status st = enqueue_regions_pass(s, nodes, n_nodes, planes, n, margin, J, false, 0u, nullptr, nullptr, counters, stream);
+    if (st == RT_OK) st = enqueue_list_scan(s->overlap, n * J, nullptr, total_out, stream);
+    if (st != RT_OK || (!offsets_out && !counters)) return st;
+    hipLaunchKernelGGL(rt::k_region_rows, query_grid(n + 1u), query_block(), 0, stream, s->overlap.offsets, n, J, offsets_out, counters);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+rt_status enqueue_regions_fill(const rt_scene *s, const void *nodes, uint32_t n_nodes, const void *planes, uint32_t n, double margin, uint32_t J, uint32_t capacity,
+                               int32_t *items, void *gap, hipStream_t stream)
+{
+    return enqueue_regions_pass(s, nodes, n_nodes, planes, n, margin, J, true, capacity, items, gap, nullptr, stream);
+}
+
 // ---- swept overlap lists (rt_swept_overlaps*, rt_swept.hpp) ----
 
 // What both swept entries check (device pointers are not dereferenced here).

@@ -1,6 +1,6 @@
-// rt_walk.hpp -- the pieces every query kernel's skip-pointer walk is made of, one copy of each: the lane's query index, the four
+// rt_walk.hpp -- the pieces every query kernel's skip-pointer walk is made of, one copy of each: the lane's query index, the five
 // metrics, the wave's BOUND and retiring ITEM steps and the counter flush.  The query headers (rt_query.hpp, rt_multihit.hpp,
-// rt_near.hpp, rt_sweep.hpp, rt_contacts.hpp, rt_overlap.hpp, rt_impacts.hpp, rt_swept.hpp, rt_first.hpp, rt_box.hpp) call them;
+// rt_near.hpp, rt_sweep.hpp, rt_contacts.hpp, rt_overlap.hpp, rt_impacts.hpp, rt_swept.hpp, rt_first.hpp, rt_box.hpp, rt_region.hpp) call them;
 // each kernel keeps its own visible loop -- what accepts, what a hit does, what a lane carries differ in kind -- and its own header says
 // what its metric MEANS.  Here is only how each piece is computed.
 //
@@ -83,6 +83,24 @@ __device__ __forceinline__ T box_gap(const Node<T> &nd, V3<T> lo, V3<T> hi)
     const T dd = dot(e, e);
     T t = inf<T>();
     if (nd.a3 > T(0.0)) t = sqrt_rn_lean(dd) - sqrt_rn_lean(nd.a3);
+    return t;
+}
+
+// The gap between the record and the convex region of six planes pl[4k .. 4k+4] = {n.x, n.y, n.z, d} (rt_region.hpp): the largest of the
+// six signed plane distances n_k . c + d_k -- each in dot()'s order, then + d -- minus the record's radius.  A comparison, not fmax, from
+// -inf: an absent plane {0, 0, 0, -inf} gives -inf for every finite centre and never wins.  +inf for a record without a positive rr, as
+// centre_gap.  The planes are the same in every lane of a wave (scalar registers); the record is the lane's own.
+template <typename T>
+__device__ __forceinline__ T region_gap(const Node<T> &nd, const T (&pl)[24])
+{
+    T m = -inf<T>();
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const T s = dot(V3<T>{ pl[4 * k], pl[4 * k + 1], pl[4 * k + 2] }, V3<T>{ nd.a0, nd.a1, nd.a2 }) + pl[4 * k + 3];
+        m = s > m ? s : m;
+    }
+    T t = inf<T>();
+    if (nd.a3 > T(0.0)) t = m - sqrt_rn_lean(nd.a3);
     return t;
 }
 

@@ -333,6 +333,146 @@ def box_gaps(boxes, spheres):
     return np.where((rr > 0)[None, :], gap, R(np.inf)).astype(R, copy=False)
 
 
+ABSENT_PLANE = (0.0, 0.0, 0.0, -np.inf)
+
+
+def _as_regions(planes, what="planes"):
+    """`planes` as (n, 24) in its own float dtype: (n, 6, 4) or (n, 24) in."""
+    p = np.asarray(planes)
+    if p.dtype not in (np.float32, np.float64) or not ((p.ndim == 3 and p.shape[1:] == (6, 4)) or (p.ndim == 2 and p.shape[1] == 24)):
+        raise ValueError("%s must be (n, 6, 4) or (n, 24), float32 or float64" % what)
+    return p.reshape(p.shape[0], 24)
+
+
+def region_gaps(planes, spheres):
+    """The gap between every convex region of `planes` (n x 6 x 4 or n x 24: six planes {n.x, n.y, n.z, d}; outside is n.c + d > 0) and every
+    sphere of `spheres` (m x 4: cx, cy, cz, r) -> REAL[n, m], the metric of rt_overlap_regions restated in numpy bit for bit
+    (include/rtrace_hip.h states it), in the arrays' dtype (float32 or float64, the same for both), every operation rounded once:
+    rr = r * r;  s_k = ((n_k.x*c.x + n_k.y*c.y) + n_k.z*c.z) + d_k;  m = -inf, then m = s_k where s_k > m, k = 0 .. 5;  gap = m - sqrt(rr)
+    where rr > 0, else +inf.  With unit normals: the largest signed plane distance of the centre, minus the radius -- never above the
+    true distance from the region to the sphere's surface.  An absent plane is (0, 0, 0, -inf).  A record without a positive rr -- radius
+    0: a dead slot -- is at +inf from every region.  DeviceScene.region_overlaps lists, per region without a NaN, the spheres with
+    !(gap >= margin); the row of a region with a NaN is here whatever the arithmetic gives."""
+    try:
+        p = _as_regions(planes)
+    except ValueError:
+        p = None
+    s = np.asarray(spheres)
+    if p is None or s.dtype != p.dtype or s.ndim != 2 or s.shape[1] != 4:
+        raise ValueError("planes must be (n, 6, 4) or (n, 24) and spheres (m, 4), both float32 or both float64")
+    R = p.dtype.type
+    rr = s[:, 3] * s[:, 3]
+    m = np.full((p.shape[0], s.shape[0]), -np.inf, dtype=R)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for k in range(6):
+            nx, ny, nz, d = (p[:, 4 * k + c, None] for c in range(4))
+            sk = ((nx * s[None, :, 0] + ny * s[None, :, 1]) + nz * s[None, :, 2]) + d
+            m = np.where(sk > m, sk, m)
+        gap = m - np.sqrt(np.where(rr > 0, rr, R(1.0)))[None, :]
+    return np.where((rr > 0)[None, :], gap, R(np.inf)).astype(R, copy=False)
+
+
+def _unit_planes(normals, points, dtype):
+    """REAL[..., 4] = {n / |n|, -(n / |n|) . p}: normalised in float64, rounded to `dtype` once."""
+    nrm = np.asarray(normals, dtype=np.float64)
+    nrm = nrm / np.sqrt((nrm * nrm).sum(axis=-1, keepdims=True))
+    d = -(nrm * np.asarray(points, dtype=np.float64)).sum(axis=-1, keepdims=True)
+    return np.concatenate([nrm, d], axis=-1).astype(dtype)
+
+
+def box_planes(lo, hi, rotation=None, dtype=None):
+    """The six unit planes of the box [lo, hi] for DeviceScene.region_overlaps -> REAL[n, 6, 4] (lo, hi: (n, 3) or (3,), float32 or float64;
+    dtype: the result's, default lo's).  rotation=None: the axis-aligned box; rotation (3 x 3, or n x 3 x 3, orthonormal): the box
+    {c + rotation @ x : lo <= c + x <= hi componentwise} -- the box turned about its own centre c = (lo + hi) / 2, the rotation's columns
+    its axes.  Planes 2k and 2k + 1 are the low and the high side of axis k: {-a_k, a_k . c - h_k} and {a_k, -a_k . c - h_k} with h the
+    half-extents.  An infinite side becomes the absent plane (0, 0, 0, -inf) (with a rotation, only where the centre of that axis is
+    still finite: a box infinite on both sides of a rotated axis has no centre to turn about and is refused).  Formed in float64, rounded
+    to REAL once.  For an axis-aligned box region_gaps <= box_gaps: the largest excess is never above the root of the squares' sum."""
+    lo_a = np.asarray(lo)
+    R = np.dtype(dtype if dtype is not None else lo_a.dtype).type
+    if R not in (np.float32, np.float64):
+        raise ValueError("box_planes: lo and hi must be float32 or float64 (or pass dtype)")
+    lo64, hi64 = np.atleast_2d(np.asarray(lo, np.float64)), np.atleast_2d(np.asarray(hi, np.float64))
+    if lo64.shape != hi64.shape or lo64.ndim != 2 or lo64.shape[1] != 3 or np.isnan(lo64).any() or np.isnan(hi64).any() or (lo64 > hi64).any():
+        raise ValueError("box_planes: lo and hi must be (n, 3) or (3,) without NaN and with lo <= hi")
+    n = lo64.shape[0]
+    out = np.empty((n, 6, 4), dtype=R)
+    if rotation is None:
+        axes = np.broadcast_to(np.eye(3), (n, 3, 3))
+        for k in range(3):
+            out[:, 2 * k, :3] = -axes[:, :, k]
+            out[:, 2 * k, 3] = lo64[:, k]                                       # -c_k + lo_k <= 0
+            out[:, 2 * k + 1, :3] = axes[:, :, k]
+            out[:, 2 * k + 1, 3] = -hi64[:, k]
+    else:
+        rot = np.broadcast_to(np.asarray(rotation, dtype=np.float64), (n, 3, 3))
+        if not np.allclose(np.einsum("nij,nik->njk", rot, rot), np.eye(3), atol=1e-9):
+            raise ValueError("box_planes: rotation must be orthonormal")
+        fin = np.isfinite(lo64) & np.isfinite(hi64)
+        if (np.isinf(lo64) & np.isinf(hi64)).any():
+            raise ValueError("box_planes: a rotated box must have a finite side on every axis")
+        with np.errstate(invalid="ignore"):
+            c = np.where(fin, 0.5 * (lo64 + hi64), np.where(np.isfinite(lo64), lo64, hi64))     # (a half-infinite axis turns about its finite side)
+        below, above = np.where(np.isfinite(lo64), lo64 - c, 0.0), np.where(np.isfinite(hi64), hi64 - c, 0.0)     # (an infinite side: absent below)
+        for k in range(3):
+            a = rot[:, :, k]
+            out[:, 2 * k] = _unit_planes(-a, c + a * below[:, k, None], R)
+            out[:, 2 * k + 1] = _unit_planes(a, c + a * above[:, k, None], R)
+    for k in range(3):
+        out[np.isinf(lo64[:, k]), 2 * k] = ABSENT_PLANE
+        out[np.isinf(hi64[:, k]), 2 * k + 1] = ABSENT_PLANE
+    return out + R(0.0)                                                          # (no component is a negative zero)
+
+
+def camera_planes(camera, width, height, rect=None, near=None, far=None):
+    """The planes that enclose what a look_at camera sees through a pixel rectangle, for DeviceScene.region_overlaps -> REAL[1, 6, 4] in the
+    camera's dtype.  camera: REAL[12] = eye, right, up, forward (look_at); width, height: the frame's; rect = (l, t, r, b): the pixels
+    l <= x < r, b <= y < t as render_camera's regions name them (None: the whole frame).
+    Planes 0 .. 3 are the four sides through the eye.  render_camera's sample (x, y, ssx, ssy) looks along (right*u + up*v) + forward*width
+    with u = xres - width/2, v = (height - yres) - height/2, x <= xres < x + 1 and y <= yres < y + 1 (include/rtrace_hip.h): the
+    rectangle's samples have u in [l - width/2, r - width/2] and v in [(height - t) - height/2, (height - b) - height/2].  Both ranges
+    are rounded outward to whole numbers and then widened by one pixel more on every side, so that the planes' own rounding to REAL never
+    puts a sample ray outside: every point eye + t*dir, t >= 0, of every sample ray has s_k < 0 on all four sides at any t > 0.  In
+    the camera's (possibly skewed) axes a direction right*a + up*b + forward*c lies inside u <= u1 exactly when width*a - u1*c <= 0,
+    which is a plane through the eye whose normal is read off the dual basis; all four normals are normalised in float64 and rounded to
+    REAL once.  Plane 4 is the near plane (points closer than `near` along forward / |forward| are outside), plane 5 the far plane;
+    None leaves them absent, (0, 0, 0, -inf)."""
+    cam = np.asarray(camera)
+    if cam.dtype not in (np.float32, np.float64) or cam.shape != (12,):
+        raise ValueError("camera_planes: camera must be float32[12] or float64[12] (look_at)")
+    R = cam.dtype.type
+    w, h = int(width), int(height)
+    l, t, r, b = (0, h, w, 0) if rect is None else (int(v) for v in rect)
+    if not (w > 0 and h > 0 and 0 <= l < r <= w and 0 <= b < t <= h):
+        raise ValueError("camera_planes: rect (l, t, r, b) must be a non-empty rectangle inside the %dx%d frame" % (w, h))
+    c64 = cam.astype(np.float64)
+    eye, axes = c64[:3], c64[3:].reshape(3, 3)                                  # rows: right, up, forward
+    dual = np.linalg.inv(axes.T)                                                # rows: a(d) = dual[0] . d, b(d) = dual[1] . d, c(d) = dual[2] . d
+    u0, u1 = np.floor(l - w / 2.0) - 1.0, np.ceil(r - w / 2.0) + 1.0
+    v0, v1 = np.floor((h - t) - h / 2.0) - 1.0, np.ceil((h - b) - h / 2.0) + 1.0
+    normals = [u0 * dual[2] - w * dual[0], w * dual[0] - u1 * dual[2], v0 * dual[2] - w * dual[1], w * dual[1] - v1 * dual[2]]
+    out = np.empty((1, 6, 4), dtype=R)
+    out[0, :4] = _unit_planes(np.array(normals), eye[None, :], R)
+    f = axes[2] / np.sqrt(axes[2] @ axes[2])
+    out[0, 4] = ABSENT_PLANE if near is None else _unit_planes(-f, eye + f * float(near), R)
+    out[0, 5] = ABSENT_PLANE if far is None else _unit_planes(f, eye + f * float(far), R)
+    return out + R(0.0)
+
+
+REGION_LANES, REGION_SECTION_NODES, REGION_MAX_COUNTS = 1 << 18, 8, 1 << 26
+
+
+def region_sections(n, n_nodes, sections=0):
+    """The J of an rt_overlap_regions call over n regions on a stream of n_nodes nodes (a scene without bounds: its items) -- sections=0:
+    the library's rule, a pure function of (n, n_nodes): max(1, min(2^18 // n, n_nodes // 8)) -- as many sections as bring the call to
+    2^18 lanes, none shorter than 8 nodes (DESIGN.md 4.23 has the sweep that chose the constants); any other value: clamped to
+    1 .. n_nodes, as the library clamps it."""
+    n, n_nodes, sections = int(n), max(int(n_nodes), 1), int(sections)
+    if n < 1 or sections < 0:
+        raise ValueError("region_sections: n must be >= 1 and sections >= 0")
+    return max(1, min(REGION_LANES // n, n_nodes // REGION_SECTION_NODES)) if sections == 0 else min(sections, n_nodes)
+
+
 def impact_scale(spheres, disp, queries=None, qdisp=None):
     """S of rt_scene_impacts (include/rtrace_hip.h) for the records `spheres` (m x 4: cx, cy, cz, r) and their motion-table rows `disp`
     (m x 3, or None: 0) -> a power of two in the arrays' dtype.  M is the largest of |cx|, |cy|, |cz|, r, |dx|, |dy|, |dz| over the records
@@ -1449,6 +1589,28 @@ class DeviceScene:
         return self._list_query("rt_overlap_boxes", self._side(boxes), (boxes,), (("boxes", 6, None, False),), exclude, order, capacity,
                                 (True, gaps), (((), np.int32), ((), "R")), offsets, stats, stream, "the boxes have %d entries",
                                 lambda xs, n, ex, o: (xs[0], n, margin, ex, o))
+
+    def region_overlaps(self, planes, margin=0.0, sections=None, capacity=None, gaps=False, offsets=False, stats=False, stream=None):
+        """rt_overlap_regions / rt_overlap_regions_device: every sphere of the scene that reaches into each convex region of `planes`
+        (n x 6 x 4 or n x 24, the scene's REAL dtype: six planes {n.x, n.y, n.z, d} with unit normals, outside where n.c + d > 0, an absent
+        plane (0, 0, 0, -inf); region_gaps is the metric: the largest signed plane distance of the centre minus the radius, so the list is
+        a superset of the exact touch list; camera_planes and box_planes make such regions) -> (items[, gap][, offsets], total[, stats
+        dict]), with the shapes, capacity, stream and the host / device routing of overlaps().  The call is made for FEW regions that
+        each cover much of the scene: a wave carries one region and its lanes sections of the node stream.  sections (None or 0: the
+        library's rule, region_sections(n, n_nodes)): how many sections a region is cut into -- the list is the same bytes for every
+        value, only the time and the test counters differ.  The host entry refuses a NaN in a plane and a normal that is not of
+        length 1; through the device entry a region with a NaN carries no query and has an empty row."""
+        margin = float(margin)
+        if margin != margin:
+            raise ValueError("margin must not be NaN")
+        sections = 0 if sections is None else int(sections)
+        if not 0 <= sections <= 0xFFFFFFFF:
+            raise ValueError("sections must be None or 0 .. 2^32 - 1, not %d" % sections)
+        if getattr(planes, "ndim", None) == 3 and tuple(planes.shape[1:]) == (6, 4):
+            planes = planes.reshape(planes.shape[0], 24)
+        return self._list_query("rt_overlap_regions", self._side(planes), (planes,), (("planes", 24, None, False),), None, None, capacity,
+                                (True, gaps), (((), np.int32), ((), "R")), offsets, stats, stream, "the regions have %d entries",
+                                lambda xs, n, ex, o: (xs[0], n, margin, sections))
 
     def impacts(self, disp, capacity=None, times=False, offsets=False, stats=False, stream=None):
         """rt_scene_impacts / rt_scene_impacts_device: every pair of spheres of the scene that comes into contact while sphere k moves from
